@@ -1,9 +1,25 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X stereo-SLAM compute core.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps of the headline region below and prints one short JSON line (`value`,
+`ms_per_step`, the workload).  --dump-outputs DIR writes what rank 0's last timed step handed back as DIR/<name>.npy (float32 /
+float64; the inputs are seeded, so two builds can be compared output for output):
+  frontend_counts       [B, 4]  nL, nR, matches, triangulated of every pair, as the step collected them
+  frontend_keypoints    [n, 8]  pair, side (0 left / 1 right), x, y, size, angle, response, octave -- a fixed sample of 8 pairs of
+                                the batch the step ran (ssx_stereo_batch_fetch)
+  frontend_descriptors  [n, 32] the BRIEF bytes of those keypoints, same rows
+  frontend_matches      [m, 7]  pair, right index, Hamming distance, triangulated flag, x, y, z (0 where not triangulated) per left
+                                keypoint of the sample
+  backend_windows       [B, 7]  window, keyframes, landmarks, rounds, LM iterations, inliers, outliers of every window's solve
+                                (a fixed sample of 128 windows when B is larger)
+  backend_poses         [sum keyframes, 7], backend_landmarks [sum landmarks, 3]  the optimised estimates, window after window
+                                (ssx_ba_window_export order)
+--full adds every other figure listed below (other regions, sizes, legs, CPU baselines, roofline); --lean and --profile-kernels
+trim the --full run for the profiling tools and imply it.
 
 Metric (BASELINE.json): "stereo frames/s (ORB+match+local-BA) on 1241x376".  One STEP = one batch of B synthetic
 1241x376 stereo pairs per GPU through the WHOLE hot path, in ONE timed region, the way a live system produces it:
@@ -24,7 +40,7 @@ Metric (BASELINE.json): "stereo frames/s (ORB+match+local-BA) on 1241x376".  One
 `value` = pairs completed per second, whole job, all GPUs.  N > 1 runs one process per GPU on independent pairs and
 windows (replicas, no data-path collective): weak scaling.
 
-Also in the same JSON line:
+With --full, also in the same JSON line:
   frozen_batch    rounds 2-4's headline: the same front-end step beside a FROZEN batch of C3 windows (ssx_ba_batch: marshalled
                   and uploaded before the clock starts, re-solved from the same state every step, poses downloaded)
   resident        the frozen batch with the images resident in HBM too and nothing downloaded (rounds 1-3's `value`)
@@ -74,6 +90,61 @@ def level_pixels(rows, cols, scale=1.2, nlevels=8):
     return px
 
 
+def _stereo_pair(seed):
+    from tools.synth import make_stereo_pair
+    return np.stack(make_stereo_pair(seed=seed)[:2])
+
+
+def make_pairs(seeds, ranks):
+    """[len(seeds)][2][H][W] u8, pair i = tools.synth.make_stereo_pair(seed=seeds[i]) (0.1 s of numpy each), rendered by forked
+    worker processes on a share of 16 host cores per rank.  Called before this process touches the GPU: a forked child must not
+    inherit an initialised HIP runtime."""
+    import multiprocessing
+    workers = max(1, min(16, os.cpu_count() or 1) // ranks)
+    with cf.ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("fork")) as ex:
+        return np.stack(list(ex.map(_stereo_pair, seeds, chunksize=2)))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(ctx, fe_stream, counts, windows, n_pairs=8, n_windows=128):
+    """the arrays --dump-outputs writes (module docstring): `counts` as the last step collected them, a fixed sample of the pairs of
+    the batch that step ran (fetched after it finished), `windows` = tools.bench_live.LiveBackend.results() of that step; more than
+    n_windows windows are sampled the same way"""
+    from ssvio_amd import orb
+    rng = np.random.default_rng(0)
+    pairs = np.sort(rng.choice(len(counts), min(n_pairs, len(counts)), replace=False))
+    wsel = np.sort(rng.choice(len(windows), min(n_windows, len(windows)), replace=False))
+    cap = fe_stream.orb.nfeatures + 260 * fe_stream.orb.nlevels + 64
+    kps, descs, matches = [], [], []
+    for p in pairs:
+        f = orb.stereo_batch_fetch(ctx, int(p), cap)
+        for side, (k, d) in enumerate(((f["kL"], f["dL"]), (f["kR"], f["dR"]))):
+            kps.append(np.stack([np.full(len(k), p), np.full(len(k), side), k["x"], k["y"], k["size"], k["angle"], k["response"],
+                                 k["octave"]], 1).astype(np.float64))
+            descs.append(d.astype(np.float32))
+        ok = f["ok"] != 0
+        matches.append(np.column_stack([np.full(len(ok), p), f["match_idx"], f["match_dist"], ok,
+                                        np.where(ok[:, None], f["xyz"], 0.0)]).astype(np.float64))
+    sel = [windows[i] for i in wsel]
+    return {"frontend_counts": counts.astype(np.float64),
+            "frontend_keypoints": np.concatenate(kps), "frontend_descriptors": np.concatenate(descs),
+            "frontend_matches": np.concatenate(matches),
+            "backend_windows": np.array([(i, len(po), len(pt), *s) for i, (po, pt, s) in zip(wsel, sel)], dtype=np.float64),
+            "backend_poses": np.concatenate([po for po, _, _ in sel]), "backend_landmarks": np.concatenate([pt for _, pt, _ in sel])}
+
+
+def write_outputs(path, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -90,7 +161,15 @@ def main():
                     "frozen-batch composite and the line says so")
     ap.add_argument("--lean", action="store_true", help="only the headline region + the per-kernel pass (what tools/collect_profiles.sh "
                     "profiles: every launch of a kernel then has the same shape, so rocprofv3's per-kernel averages mean something)")
+    ap.add_argument("--full", action="store_true", help="every figure of the line, not only the headline: the other timed regions, "
+                    "the per-kernel pass and roofline, C4, configs[0] / configs[4], the next rows, the CPU baseline (implied by --lean "
+                    "and --profile-kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what rank 0's last timed headline step handed back as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.lean or args.profile_kernels:
+        args.full = True
+    if args.dump_outputs and args.profile_kernels:
+        ap.error("--dump-outputs writes the headline region's outputs; --profile-kernels leaves that region out")
 
     # `python bench.py --gpus N` started WITHOUT a launcher: one rank per GPU is this script's job then -- it re-executes itself under
     # torch.distributed.run (one process per GPU over RCCL, rendezvous on 127.0.0.1) and fails loudly if that cannot be done; it never
@@ -116,7 +195,7 @@ def main():
     # and core), started before this process touches the GPU and collected when the GPU regions are done
     c1_dir = f"/tmp/ssx_c1_corridor_{args.c1_frames}"
     c1_gen = None
-    if rank == 0 and args.gpus == 1 and args.c1_frames > 0 and not args.lean and not os.path.exists(os.path.join(c1_dir, "times.txt")):
+    if rank == 0 and args.gpus == 1 and args.c1_frames > 0 and args.full and not args.lean and not os.path.exists(os.path.join(c1_dir, "times.txt")):
         import subprocess
         c1_gen = subprocess.Popen([sys.executable, "-m", "tools.synth", "corridor", c1_dir, str(args.c1_frames)], cwd=ROOT,
                                   stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
@@ -124,10 +203,13 @@ def main():
     # ::test_c1_hard_drive_keeps_the_backend_busy renders the same one)
     hard_dir = "/tmp/ssx_c1_hard_240"
     hard_gen = None
-    if rank == 0 and args.gpus == 1 and args.c1_frames > 0 and not args.lean and not os.path.exists(os.path.join(hard_dir, "times.txt")):
+    if rank == 0 and args.gpus == 1 and args.c1_frames > 0 and args.full and not args.lean and not os.path.exists(os.path.join(hard_dir, "times.txt")):
         import subprocess
         hard_gen = subprocess.Popen([sys.executable, "-m", "tools.synth", "corridor", hard_dir, "240", "32", "1.6", "1.0"], cwd=ROOT,
                                     stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+    # the B synthetic KITTI-shaped stereo pairs of this rank
+    B = args.pairs
+    host = make_pairs([rank * 1000 + i for i in range(B)], int(os.environ.get("WORLD_SIZE", "1")))   # [B][2][H][W] u8
 
     import torch
     import torch.distributed as dist
@@ -180,9 +262,9 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # ---------------- inputs: B synthetic KITTI-shaped stereo pairs per GPU, resident in HBM; C3-shaped windows ----------------
-    B = args.pairs
-    host = np.stack([np.stack(make_stereo_pair(seed=rank * 1000 + i)[:2]) for i in range(B)])   # [B][2][H][W] u8
+    # ---------------- inputs: the B stereo pairs per GPU, resident in HBM; C3-shaped windows (--full) ----------------
+    # (a plain run keeps the resident pass too: the headline has always been timed after it -- without it the same region measured
+    # 16.5 k instead of 17.9 k frames/s on MI355X, a 200-step warm-up included)
     imgs = torch.from_numpy(host).to(dev)
     torch.cuda.synchronize(dev)
     counts = orb.stereo_batch_dev(ctx, imgs.data_ptr(), B, KITTI_W, KITTI_H, KITTI_W)   # plans, runs once, syncs
@@ -190,15 +272,16 @@ def main():
     ring = [torch.from_numpy(host).pin_memory(), torch.from_numpy(np.ascontiguousarray(host[::-1])).pin_memory()]
     fe_stream = orb.StereoStream(ctx, B, KITTI_H, KITTI_W)
     h2d_bytes_per_step = int(ring[0].numel())
-    N_WIN = 16 if not args.lean else 4                                 # distinct C3 graphs, used round-robin
-    # (uv_f32: the measurements are float values, as the reference's keypoints are -- cv::KeyPoint::pt; it only matters to the
-    # host-buffer regions, where the library then sends 8 instead of 16 bytes of coordinates per observation)
-    wins = [make_ba_problem(P=10, L=4000, seed=1 + 17 * k + 1000 * rank, uv_f32=True) for k in range(N_WIN)]
-    step_windows = [wins[i % N_WIN] for i in range(B)]
-    # the windows are resident in HBM like the images (ssx_ba_batch_create: marshalled + uploaded before the clock starts);
-    # a second, non-resident batch object measures the same work with host marshalling + PCIe inside the region
-    batch = ba.BaBatch(ctx_ba, step_windows, resident=True, with_edge_errors=False)
-    batch_host = ba.BaBatch(ctx_ba, step_windows)
+    if args.full:
+        N_WIN = 16 if not args.lean else 4                             # distinct C3 graphs, used round-robin
+        # (uv_f32: the measurements are float values, as the reference's keypoints are -- cv::KeyPoint::pt; it only matters to the
+        # host-buffer regions, where the library then sends 8 instead of 16 bytes of coordinates per observation)
+        wins = [make_ba_problem(P=10, L=4000, seed=1 + 17 * k + 1000 * rank, uv_f32=True) for k in range(N_WIN)]
+        step_windows = [wins[i % N_WIN] for i in range(B)]
+        # the windows are resident in HBM like the images (ssx_ba_batch_create: marshalled + uploaded before the clock starts);
+        # a second, non-resident batch object measures the same work with host marshalling + PCIe inside the region
+        batch = ba.BaBatch(ctx_ba, step_windows, resident=True, with_edge_errors=False)
+        batch_host = ba.BaBatch(ctx_ba, step_windows)
 
     step_no = [0]
 
@@ -268,6 +351,8 @@ def main():
         assert fe_pairs[0] == B * args.steps, "a stereo pair came back without keypoints"
         assert min(live.steps_done) == args.steps, "a backend group did not finish its steps"
         lm_iters = sum(live.iters)
+        if args.dump_outputs and rank == 0:                                # (fe_stream.counts: what the last timed step collected)
+            write_outputs(args.dump_outputs, step_outputs(ctx, fe_stream, fe_stream.counts.copy(), live.results()))
         value = frames / elapsed
         nkf_w, nlm_w, nob_w = live.window_size()
         live_info = {"host_threads": live.G, "streams_per_group": live.batch_groups or 2, "steps_a_group_may_lag": LIVE_LAG, "ms_per_step_inside_solve_calls": round(max(live.t_solve) / args.steps * 1e3, 4),
@@ -287,6 +372,44 @@ def main():
         lm_iters = 0
         fe_stream.wait_counts()
         fe_stream.run(); fe_stream.wait_counts()
+
+    def result_line():
+        """the headline part of the JSON line (all of a plain run's line)"""
+        return {
+            "metric": "stereo frames/s (ORB extract + row-band match + triangulate + one local BA per frame) on 1241x376",
+            **({"profiling_mode": "--profile-kernels: the live-backend region was left out; value = frozen_batch"} if args.profile_kernels else {}),
+            "value": round(value, 2), "unit": "stereo frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u8 (front-end) + f64 (BA)", "data": "synthetic",
+            "config": {"workload": "C2 + C3: 1241x376 synthetic stereo, 2000 ORB feats/img, 8 levels, extract+match+triangulate, then one "
+                                   "local BA per pair on a live sliding window (10 KF x 20000 edges, one keyframe replaced per step, <= 5 x "
+                                   "optimize(10), analytic Jacobians)",
+                       "pairs_per_step_per_gpu": B, "ba_windows_per_step_per_gpu": B,
+                       "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
+                       "avg_keypoints_per_image": round(float(counts[:, 0].sum() + counts[:, 1].sum()) / (2 * B), 1),
+                       "avg_matches_per_pair": round(float(counts[:, 2].mean()), 1),
+                       "avg_triangulated_per_pair": round(float(counts[:, 3].mean()), 1),
+                       "lm_iterations_per_window": round(lm_iters / (args.steps * B), 2),
+                       "images": "host -> device every step (pinned ring of 2 batches; ssx_stereo_batch_upload of step k + 1's batch on the library's "
+                                 "copy stream beside step k's kernels, ssx_stereo_batch_run on the batch uploaded during the step before)",
+                       "h2d_bytes_per_step_per_gpu": h2d_bytes_per_step,
+                       "downloaded_every_step": "keypoint / match / triangulation counts of every pair (collected one step behind: the batch of step "
+                                                "k - 1 while batch k is in the front-end) + the optimised keyframe poses AND landmarks of every window",
+                       "windows": "B live sliding windows (ssx_ba_window) resident in HBM: per step every window pops its oldest keyframe and pushes a "
+                                  "new one by landmark slots (pose, ~400 landmarks, 2000 observations -- one ssx_ba_window_update_batch call per group), "
+                                  "then ssx_ba_window_solve_batch optimises the group's windows where they lie (backend.cpp:88-169, map.cpp:27-56, 89-160)",
+                       "window": live_info["window"], "backend_groups": live_info["host_threads"]},
+            "live_backend": live_info,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line()))
+        ctx.close()
+        ctx_ba.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---------------- timed region 1f: rounds 2-4's headline -- the same front-end step beside a FROZEN batch of C3 windows ----------------
     fe_stream.upload(ring[0].data_ptr()); fe_stream.run()
@@ -935,31 +1058,9 @@ def main():
                 c1["cpu_oracle_runner"] = {"skipped": str(e)[:200]}
 
     if rank == 0:
-        out = {
-            "metric": "stereo frames/s (ORB extract + row-band match + triangulate + one local BA per frame) on 1241x376",
-            **({"profiling_mode": "--profile-kernels: the live-backend region was left out; value = frozen_batch"} if args.profile_kernels else {}),
-            "value": round(value, 2), "unit": "stereo frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8 (front-end) + f64 (BA)", "data": "synthetic",
-            "config": {"workload": "C2 + C3: 1241x376 synthetic stereo, 2000 ORB feats/img, 8 levels, extract+match+triangulate, then one "
-                                   "local BA per pair on a live sliding window (10 KF x 20000 edges, one keyframe replaced per step, <= 5 x "
-                                   "optimize(10), analytic Jacobians)",
-                       "pairs_per_step_per_gpu": B, "ba_windows_per_step_per_gpu": B, "ba_groups": ba_groups,
-                       "parallelism": f"replicas x{world}" if world > 1 else "single GPU",
-                       "avg_keypoints_per_image": round(kp_total / I, 1),
-                       "avg_matches_per_pair": round(float(counts[:, 2].mean()), 1),
-                       "avg_triangulated_per_pair": round(float(counts[:, 3].mean()), 1),
-                       "lm_iterations_per_window": round(lm_iters / (args.steps * B), 2),
-                       "images": "host -> device every step (pinned ring of 2 batches; ssx_stereo_batch_upload of step k + 1's batch on the library's "
-                                 "copy stream beside step k's kernels, ssx_stereo_batch_run on the batch uploaded during the step before)",
-                       "h2d_bytes_per_step_per_gpu": h2d_bytes_per_step,
-                       "downloaded_every_step": "keypoint / match / triangulation counts of every pair (collected one step behind: the batch of step "
-                                                "k - 1 while batch k is in the front-end) + the optimised keyframe poses AND landmarks of every window",
-                       "windows": "B live sliding windows (ssx_ba_window) resident in HBM: per step every window pops its oldest keyframe and pushes a "
-                                  "new one by landmark slots (pose, ~400 landmarks, 2000 observations -- one ssx_ba_window_update_batch call per group), "
-                                  "then ssx_ba_window_solve_batch optimises the group's windows where they lie (backend.cpp:88-169, map.cpp:27-56, 89-160)",
-                       "window": live_info["window"], "backend_groups": live_info["host_threads"]},
-            "live_backend": live_info,
+        out = result_line()
+        out["config"]["ba_groups"] = ba_groups
+        out.update({
             "c5": (c1 or {}).get("c5_batched_streams") if isinstance(c1, dict) else None,   # configs[4] on one GPU: S batched streams, closed loop
             "nccl_ranks": (c4.get("rccl_rank_world") if world > 1 else [0, 1]),    # (rank, ranks) of the RCCL communicator inside libssx.so: ssx_comm_info
             "frozen_batch": {"value": round(frozen_value, 2), "unit": "stereo frames/s", "ms_per_step": round(frozen_elapsed / FROZEN_STEPS * 1e3, 4),
@@ -992,7 +1093,7 @@ def main():
             "ba_c4": c4,
             "next_rows": next_rows,
             "cpu_baseline": cpu,
-        }
+        })
         if cpu:
             out["speedup_vs_cpu_1core"] = {"ratio": round(value / cpu["value"], 1),
                                            "caveat": "against ONE core running a SCALAR restatement of the front-end (no SIMD; OpenCV's FAST / ORB "

@@ -1,4 +1,4 @@
-"""One line of the bench's JSON: python bench.py ... | python tools/bench_brief.py [ba|fe|host]"""
+"""One line of the bench's JSON: python bench.py --full ... | python tools/bench_brief.py [ba|fe|host]"""
 import json, sys
 what = sys.argv[1] if len(sys.argv) > 1 else "ba"
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -160,6 +160,7 @@ class LiveBackend:
                 a = self.feeds[i % n_traj][k]
                 w.push_slots(k, a["pose"], new_ids=a["new_ids"], new_xyz=a["new_xyz"], new_fixed=a["new_fixed"], obs_slot=a["obs_slot"], obs_uv=a["obs_uv"])
         self._keep = []
+        self._out = [None] * B                                          # per window: its (poses, landmarks) result buffers
         self.groups = []
         max_lm = 0
         for fd in self.feeds:
@@ -171,7 +172,7 @@ class LiveBackend:
             res = (BaResult * len(idx))()
             for j in range(len(idx)):                                   # result buffers: poses + landmarks of the window, every step
                 po = np.zeros((win_kf + 2, 7)); pt = np.zeros((max_lm + 64, 3))
-                self._keep.append((po, pt))
+                self._out[idx[j]] = (po, pt)
                 res[j].poses_out = ptr(po, dbl_p); res[j].points_out = ptr(pt, dbl_p)
             upd = {}
             for k in range(win_kf, n_kf):                               # the edits of every step, built once (a C caller fills them from its map)
@@ -263,6 +264,18 @@ class LiveBackend:
 
     def window_size(self):
         return self.wins[0].size()
+
+    def results(self):
+        """what the last finished step's solve handed back, window by window: (poses [P, 7], landmarks [L, 3] in the order of
+        ssx_ba_window_export, (rounds, LM iterations, inliers, outliers)); call it while no step is in flight"""
+        out = [None] * self.B
+        for idx, _, res, _ in self.groups:
+            for j, i in enumerate(idx):
+                P, L, _ = self.wins[i].size()
+                po, pt = self._out[i]
+                r = res[j]
+                out[i] = (po[:P].copy(), pt[:L].copy(), (r.rounds, r.n_iters, r.n_inliers, r.n_outliers))
+        return out
 
     def close(self):
         self.lib.ssx_ba_device_turns(0)

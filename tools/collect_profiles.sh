@@ -17,7 +17,7 @@ cd /tmp
 # one group of BA windows per launch while the counters run: a batched kernel then covers the whole batch and has the chip
 # to itself (the default, two groups on two streams, is what the bench line after the passes is taken with)
 export SSX_BA_GROUPS=1
-CMD="python $R/bench.py --steps 5 --warmup 2 --lean --profile-kernels"
+CMD="python $R/bench.py --steps 5 --warmup 2 --full --lean --profile-kernels"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- $CMD > "$OUT/stats.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/fetch" -- $CMD > "$OUT/fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/write" -- $CMD > "$OUT/write.log" 2>&1
@@ -27,7 +27,7 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY S
     --kernel-trace --output-format csv -d "$OUT/sq2" -- $CMD > "$OUT/sq2.log" 2>&1
 cd "$R"
 unset SSX_BA_GROUPS
-python bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --steps 20 --warmup 3 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"
 # the raw per-dispatch tables are hundreds of MB (gpurun merges <= 64 MiB back): summarise HERE, keep the summaries
 mkdir -p "$OUT/summary"; cp "profiles/${3:-r03}/kernel_resources.csv" "$OUT/summary/" 2>/dev/null

@@ -8,6 +8,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for P in [int(a) for a in sys.argv[1:]] or [16, 128]:
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--lean", "--steps", "20", "--pairs", str(P)], capture_output=True, text=True).stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--lean", "--steps", "20", "--pairs", str(P)], capture_output=True, text=True).stdout
     d = json.loads(out.strip().splitlines()[-1])
     print(P, " ".join(f"{n}={v['ms_per_step'] * 128 / P:.3f}" for n, v in d["kernels"].items() if v["part"] == "frontend"), flush=True)
