@@ -36,7 +36,7 @@ SSX_API double ssx_ba_debug_prepare_seconds(const ssx_ba_problem* prob, int32_t 
 /* tools / tests hook, needs no GPU: how ssx_ba_solve / ssx_ba_solve_batch would send this problem's observation arrays
  * across PCIe (lossless narrowing): bit 0 = keyframe indices as bytes, bit 1 = landmark indices as 16-bit words, bit 2 =
  * pixel coordinates as floats (every edge_uv value is a float's value, as the reference's cv::KeyPoint::pt measurements
- * are); 0 = as handed over (large windows, SSX_BA_WIDE_UPLOAD / SSX_BA_HOST_PREP set); -1 = invalid problem */
+ * are); 0 = as handed over (large windows, SSX_BA_HOST_PREP set); -1 = invalid problem */
 SSX_API int32_t ssx_ba_debug_upload_format(const ssx_ba_problem* prob);
 
 /* test hook, needs no GPU: FNV-1a digest of the host marshalling of a LARGE window (per-landmark offsets, every observation's rank

@@ -3,8 +3,8 @@
 // Replaces the arithmetic behind Backend::OptimizeActiveMap (/root/reference/src/ssvio/backend.cpp:78-245):
 // g2o's SparseOptimizer + BlockSolver<6,3> + OptimizationAlgorithmLevenberg over ssvio's
 // VertexPose / VertexXYZ / EdgeProjection (include/ssvio/g2otypes.hpp).  No g2o, no Eigen: the normal
-// equations are built, Schur-reduced, solved and applied by the kernels below; the host only runs the
-// LM accept/reject logic on a handful of scalars per trial (one stream synchronisation per LM trial).
+// equations are built, Schur-reduced, solved and applied by the kernels below, and the LM accept/reject
+// logic runs on the device too (lm_step): the host enqueues a whole optimize(iters) and synchronises once.
 //
 // Data layout in HBM (one arena per ctx, grow-only):
 //   edges are SORTED BY LANDMARK (then by pose inside a landmark) on upload so that all observations of
@@ -1277,23 +1277,23 @@ __device__ __forceinline__ void k_schur_body(const BaDev& d, const int bx, int c
   }
 }
 
-__device__ __forceinline__ void k_schur_entry(const BaDev& d, int bx, int cur, double lambda_arg, int use_dev_lambda)
+__device__ __forceinline__ void k_schur_entry(const BaDev& d, int bx)
 {
   extern __shared__ __attribute__((aligned(16))) char schur_smem[];
   ChunkLists cl;
   chunk_lists_load(d, bx, schur_smem, true, cl);
-  if (use_dev_lambda == 2 && d.scal[SC_STOP] != 0.0) return;      // device-driven LM, already terminated
-  if (cur < 0) cur = (int)d.scal[SC_CUR];
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  if (d.scal[SC_STOP] != 0.0) return;                             // device-driven LM, already terminated
+  const int cur = (int)d.scal[SC_CUR];
+  const double lambda = d.scal[SC_LAMBDA];
   k_schur_body(d, bx, cur, lambda, schur_smem, cl, nullptr, nullptr, nullptr, d.schur_slab + (size_t)bx * (d.nBlk * 36 + d.nP * 6));
 }
-__global__ __launch_bounds__(CH) void k_schur(BaDev d, int cur, double lambda_arg, int use_dev_lambda) { k_schur_entry(d, blockIdx.x, cur, lambda_arg, use_dev_lambda); }
+__global__ __launch_bounds__(CH) void k_schur(BaDev d) { k_schur_entry(d, blockIdx.x); }
 // batched: blockIdx.y = window; every window brings its own BaDev (device array)
-__global__ __launch_bounds__(CH) void k_schur_b(const BaDev* __restrict__ dv, int cur, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(CH) void k_schur_b(const BaDev* __restrict__ dv)
 {
   const BaDev& d = dv[blockIdx.y];       // by reference: a private copy of the 500-byte struct ends up in scratch memory
   if ((int)blockIdx.x >= d.nCh) return;
-  k_schur_entry(d, blockIdx.x, cur, lambda_arg, use_dev_lambda);
+  k_schur_entry(d, blockIdx.x);
 }
 
 // k_lin_schur: one slot of the device-driven LM loop whose damping is already known (every slot but the first of an
@@ -1441,17 +1441,15 @@ __global__ __launch_bounds__(CH) void k_reduce_schur_b(const BaDev* __restrict__
 // residuals / robust chi2 of the TRIAL state (computeActiveErrors + activeRobustChi2,
 // sparse_optimizer.cpp:63-116).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void k_backsub_residual_body(const BaDev& d, const int bx, int cur, double lambda_arg, int use_dev_lambda, int finish)
+__device__ __forceinline__ void k_backsub_residual_body(const BaDev& d, const int bx, int finish)
 {
   __shared__ double sPt[3][CH];
   __shared__ double sPart[3][CH];
   __shared__ double sRed[CH];
   const int c = bx, t = threadIdx.x;
-  if (cur < 0) {
-    if (d.scal[SC_STOP] != 0.0) return;
-    cur = (int)d.scal[SC_CUR];
-  }
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  if (d.scal[SC_STOP] != 0.0) return;                             // device-driven LM, already terminated
+  const int cur = (int)d.scal[SC_CUR];
+  const double lambda = d.scal[SC_LAMBDA];
   const int4 cd = d.ch_desc[c];
   const int e0 = cd.x, ne = cd.y, lm0 = cd.z, nl = cd.w;
   const double* pt_src = d.point[cur];
@@ -1583,13 +1581,13 @@ __device__ __forceinline__ void k_backsub_residual_body(const BaDev& d, const in
   }
 }
 
-__global__ __launch_bounds__(CH) void k_backsub_residual(BaDev d, int cur, double lambda_arg, int use_dev_lambda, int finish) { k_backsub_residual_body(d, blockIdx.x, cur, lambda_arg, use_dev_lambda, finish); }
+__global__ __launch_bounds__(CH) void k_backsub_residual(BaDev d, int finish) { k_backsub_residual_body(d, blockIdx.x, finish); }
 // batched: blockIdx.y = window; every window brings its own BaDev (device array)
-__global__ __launch_bounds__(CH) void k_backsub_residual_b(const BaDev* __restrict__ dv, int cur, double lambda_arg, int use_dev_lambda, int finish)
+__global__ __launch_bounds__(CH) void k_backsub_residual_b(const BaDev* __restrict__ dv, int finish)
 {
   const BaDev& d = dv[blockIdx.y];       // by reference: a private copy of the 500-byte struct ends up in scratch memory
   if ((int)blockIdx.x >= (d.nCh)) return;
-  k_backsub_residual_body(d, blockIdx.x, cur, lambda_arg, use_dev_lambda, finish);
+  k_backsub_residual_body(d, blockIdx.x, finish);
 }
 
 __device__ __forceinline__ void k_reduce_trial_body(const BaDev& d, const int bx, int lm)
@@ -1626,13 +1624,13 @@ __global__ __launch_bounds__(CH) void k_reduce_trial_b(const BaDev* __restrict__
 }
 
 // copy the (all-reduced) trial scalars next to the others so that ONE 64-byte download returns everything
-__global__ void k_publish_trial(BaDev d, int lm)
+__global__ void k_publish_trial(BaDev d)
 {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     d.scal[SC_TEMP_CHI] = d.scal_comm[0];
     d.scal[SC_SCALE_L] = d.scal_comm[1];
     d.scal[SC_NOUT] = d.scal_comm[2];
-    if (lm) lm_step(d);                            // every rank takes the same decision from the all-reduced scalars
+    lm_step(d);                                    // every rank takes the same decision from the all-reduced scalars
   }
 }
 
@@ -1810,7 +1808,7 @@ class ParPool {
  public:
   ~ParPool()
   {
-    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; gen_.fetch_add(1, std::memory_order_release); }
+    { std::lock_guard<std::mutex> lk(mu_); stop_ = true; ++gen_; }
     cv_.notify_all();
     for (auto& t : th_) t.join();
   }
@@ -1818,8 +1816,8 @@ class ParPool {
   // wider call join in as well); returns when all are done.
   // The per-window pieces of a batched call are SHORT (a 10 KB copy, a counting pass over 2 000 observations) and a call runs five
   // such phases back to back: items are claimed in runs (one lock per run, not two per item -- 258 copies of 10 KB took 0.28 ms,
-  // most of it on the mutex: 0.12 - 0.16 now); with SSX_POOL_SPIN=1 a worker that ran out of work polls the generation counter for
-  // a moment before it parks on the condition variable, and so does the caller before it waits for the stragglers.
+  // most of it on the mutex: 0.12 - 0.16 now).  Idle workers park on the condition variable (polling before they park measured no
+  // gain in the headline region: profiles/r06/host_pool_ab.txt).
   template <class F>
   void run(int n, int T, F&& fn)
   {
@@ -1830,15 +1828,10 @@ class ParPool {
       while ((int)th_.size() < T - 1) th_.emplace_back([this] { loop(); });
       job_ = &f; n_ = n; next_ = 0; pending_ = n;
       grain_ = std::max(1, n / (4 * (int)(th_.size() + 1)));
-      gen_.fetch_add(1, std::memory_order_release);
+      ++gen_;
     }
     cv_.notify_all();
     work();
-    if (spin_) {
-      const auto t0 = std::chrono::steady_clock::now();
-      while (done_gen_.load(std::memory_order_acquire) != gen_.load(std::memory_order_relaxed) &&
-             std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(200)) __builtin_ia32_pause();
-    }
     std::unique_lock<std::mutex> lk(mu_);
     done_cv_.wait(lk, [this] { return pending_ == 0; });
     job_ = nullptr;
@@ -1858,35 +1851,29 @@ class ParPool {
       for (int w = w0; w < w1; ++w) (*f)(w);
       std::lock_guard<std::mutex> lk(mu_);
       pending_ -= w1 - w0;
-      if (pending_ == 0) { done_gen_.store(gen_.load(std::memory_order_relaxed), std::memory_order_release); done_cv_.notify_all(); }
+      if (pending_ == 0) done_cv_.notify_all();
     }
   }
   void loop()
   {
     unsigned long seen = 0;
     for (;;) {
-      if (spin_) {
-        const auto t0 = std::chrono::steady_clock::now();
-        while (gen_.load(std::memory_order_acquire) == seen && std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(150)) __builtin_ia32_pause();
-      }
       {
         std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || gen_.load(std::memory_order_relaxed) != seen; });
+        cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
         if (stop_) return;
-        seen = gen_.load(std::memory_order_relaxed);
+        seen = gen_;
       }
       work();
     }
   }
-  std::mutex mu_;
+  std::mutex mu_;                        // guards every member below
   std::condition_variable cv_, done_cv_;
   std::vector<std::thread> th_;
   const std::function<void(int)>* job_ = nullptr;
   int n_ = 0, next_ = 0, pending_ = 0, grain_ = 1;
-  std::atomic<unsigned long> gen_{0}, done_gen_{0};
+  unsigned long gen_ = 0;                // one more per job: wakes the parked workers
   bool stop_ = false;
-  // polling is OFF by default: measured in the headline region it changes nothing (profiles/r06/host_pool_ab.txt); SSX_POOL_SPIN=1 turns it on
-  const bool spin_ = [] { const char* e = getenv("SSX_POOL_SPIN"); return e ? atoi(e) != 0 : false; }();
 };
 
 // ssx_ba_device_turns: the device phases of batched solves of DIFFERENT contexts run one after the other on the device (FIFO).
@@ -2111,8 +2098,7 @@ ssx_status prepare(ssx_ctx* ctx, const ssx_ba_problem* pr, HostPrep& h, bool all
   // landmark indices as 16-bit words, and the pixel coordinates as floats when every one of them IS a float's value -- the
   // reference's measurements are cv::KeyPoint::pt (Point2f) widened to double (frontend.cpp:232-236, backend.cpp:126-160).
   h.raw_fmt = 0;
-  static const bool wide_env = getenv("SSX_BA_WIDE_UPLOAD") != nullptr;
-  if (h.dev_prep && !h.big && !dead_ok && !wide_env) {
+  if (h.dev_prep && !h.big && !dead_ok) {
     if (P <= 256) h.raw_fmt |= 1;
     if (L <= 65536) h.raw_fmt |= 2;
     bool exact = true;
@@ -2129,7 +2115,6 @@ ssx_status prepare(ssx_ctx* ctx, const ssx_ba_problem* pr, HostPrep& h, bool all
   // sort buys is locality for every input: the landmarks of a chunk then share their poses, a chunk contributes to 15-25 of the
   // 55 blocks of a 10-keyframe reduced system instead of all of them, and writes / the reductions read only those (BaDev::touch).
   const bool lm_ordered = ext && ext->lm_order;
-  static const bool no_lm_sort = getenv("SSX_BA_NO_LM_SORT") != nullptr;   // (experiments)
   const int n_visit = lm_ordered ? ext->n_lm_order : L;
   std::vector<int>& visit = h.visit_tmp;
   visit.clear();
@@ -2142,7 +2127,7 @@ ssx_status prepare(ssx_ctx* ctx, const ssx_ba_problem* pr, HostPrep& h, bool all
     }
     visit.push_back(l);
   }
-  if (!no_lm_sort && !h.big) {
+  if (!h.big) {
     std::vector<int>& out = h.visit2_tmp;
     int bucket[SSX_BA_SMALL_P + 3] = {0};
     for (int l : visit) bucket[first_pf[l] + 1]++;
@@ -3369,14 +3354,16 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
   // large windows: Schur blocks -> dense S (+ rhs row) -> all-reduce -> blocked Cholesky (MFMA) -> back-substitution
   // fuse_iter: the trial's all-reduce also carries iter_comm (pose blocks, chi2, max-diagonal slots of the linearisation), which
   // then needs no collective of its own: two all-reduces per LM trial instead of three
-  auto big_trial = [&](double lambda, int dev_lambda, int cur_, bool fuse_iter = false) -> ssx_status {
+  // (damping, state buffer and stop flag come from the device's LM control block: the kernels shared with the pose graph are told
+  // so by cur = -1, lambda_arg = 0, use_dev_lambda = 2)
+  auto big_trial = [&](bool fuse_iter) -> ssx_status {
     hipStream_t s = ctx->stream;
     if (bnd.on) {
       // Schur blocks straight into the band layout -> (all-reduce) -> segments || -> separator system -> segments ||
       const size_t band_doubles = (size_t)bnd.nP * (bnd.w + 1) * 36;
       SSX_HIP_TRY(ctx, hipMemsetAsync(bnd.Sb, 0, sizeof(double) * band_doubles, s));
-      if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(nCh), dim3(CH), lds_prep, s, d, bd, lambda, dev_lambda));
-      SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks_band, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd, bnd, dev_lambda == 2 ? 1 : 0));
+      if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(nCh), dim3(CH), lds_prep, s, d, bd));
+      SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks_band, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd, bnd));
       SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_bs_band, dim3(d.nP), dim3(CH), 0, s, d, bd, bnd));
       ssx_status st2 = allreduce(ctx, cm, bnd.Sb, band_doubles + (size_t)bd.n + (fuse_iter ? (size_t)d.nP * 27 + 1 + d.world : 0));
       if (st2 != SSX_OK) return st2;
@@ -3384,36 +3371,35 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
       if (bnd.bcr.on) {
         // block cyclic reduction: log2(N) levels of concurrent super-block eliminations, then as many of back-substitution
         const std::vector<int>& lv = bp.bcr.lvl;
-        const int dlm = dev_lambda == 2 ? 1 : 0;
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_build, dim3(bnd.bcr.N), dim3(256), 0, s, d, bnd, bnd.bcr, lambda, dev_lambda));
+        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_build, dim3(bnd.bcr.N), dim3(256), 0, s, d, bnd, bnd.bcr, 0.0, 2));
         const bool m24 = bnd.bcr.m == 24;
         const std::vector<int>& lm = bp.bcr.lvM;
         for (size_t q = 0; q < lm.size(); ++q) {
           const int cnt = lv[q + 1] - lv[q], sh = (int)q;
-          if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<24>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], dlm));
-          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<36>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], dlm));
+          if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<24>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], 1));
+          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<36>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], 1));
         }
         for (size_t q = lm.size(); q-- > 0;) {
           const int cnt = lv[q + 1] - lv[q], sh = (int)q;
-          if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<24>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], dlm));
-          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<36>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], dlm));
+          if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<24>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], 1));
+          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<36>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], 1));
         }
       } else {
       if (bnd.K > 1) {
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_seg, dim3(bnd.K), dim3(BAND_T), lds_seg, s, d, bnd, lambda, dev_lambda));
+        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_seg, dim3(bnd.K), dim3(BAND_T), lds_seg, s, d, bnd));
         const int total = bnd.nPr * (bnd.wr + 1) * 36 + 6 * bnd.nPr;
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_assemble, dim3(std::min(64, (total + BAND_T - 1) / BAND_T)), dim3(BAND_T), 0, s, d, bnd, lambda, dev_lambda));
+        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_assemble, dim3(std::min(64, (total + BAND_T - 1) / BAND_T)), dim3(BAND_T), 0, s, d, bnd));
       }
-      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_top, dim3(1), dim3(BAND_TOP_T), lds_top, s, d, bnd, bd, lambda, dev_lambda));
-      if (bnd.K > 1) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_back, dim3(bnd.K), dim3(BAND_T), lds_back, s, d, bnd, bd, dev_lambda == 2 ? 1 : 0));
+      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_top, dim3(1), dim3(BAND_TOP_T), lds_top, s, d, bnd, bd));
+      if (bnd.K > 1) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_back, dim3(bnd.K), dim3(BAND_T), lds_back, s, d, bnd, bd));
       }
       const int nparts = std::min(32, (d.P + CH - 1) / CH);
-      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, s, d, bd, cur_, lambda, dev_lambda));
+      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, s, d, bd, -1, 0.0, 2));
       SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_scale_finish, dim3(1), dim3(64), 0, s, d, bd, nparts));
       return SSX_OK;
     }
     SSX_HIP_TRY(ctx, hipMemsetAsync(bd.S, 0, sizeof(double) * (size_t)(bd.n_pad + 1) * bd.ld, s));
-    if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(nCh), dim3(CH), lds_prep, s, d, bd, lambda, dev_lambda));
+    if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(nCh), dim3(CH), lds_prep, s, d, bd));
     SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd));
     SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_bs, dim3(d.nP), dim3(CH), 0, s, d, bd));
     if (cm.fn) {
@@ -3423,7 +3409,7 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
       if (st2 != SSX_OK) return st2;
       hipLaunchKernelGGL(k_pack_tiles, dim3(bd.n_init + 1), dim3(CH), 0, s, bd, 1);
     }
-    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_add_lambda, dim3((bd.n + 255) / 256), dim3(256), 0, s, d, bd, lambda, dev_lambda));
+    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_add_lambda, dim3((bd.n + 255) / 256), dim3(256), 0, s, d, bd, 0.0, 2));
     for (int kb = 0; kb < bd.T; ++kb) {
       if (kb == 0 || !tl_next_diag[kb - 1])   // else the previous panel's k_syrk64 has factored this diagonal tile
         SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(CH), 0, s, d, bd, kb));
@@ -3433,7 +3419,7 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
     }
     SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(1024), 0, s, bd));
     const int nparts = std::min(32, (d.P + CH - 1) / CH);
-    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, s, d, bd, cur_, lambda, dev_lambda));
+    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, s, d, bd, -1, 0.0, 2));
     SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_scale_finish, dim3(1), dim3(64), 0, s, d, bd, nparts));
     return SSX_OK;
   };
@@ -3455,208 +3441,113 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
   const bool active = (nCh > 0) || cm.fn != nullptr;
   double n_out_total = 0.0;
   while (round < opt.outer_rounds) {
-    // ---- one g2o optimize(iters): OptimizationAlgorithmLevenberg::solve per iteration ----
-    double lambda = -1.0, ni = 2.0;
-    // An accepted trial is the rule, so the NEXT iteration's linearisation (at the trial state) is enqueued before
-    // the host waits for the trial's scalars: the GPU works through the ~25 us of the host round trip instead of
-    // idling.  A rejected trial pays one extra linearisation at the kept state (identical values: deterministic).
-    bool spec_done = false;
-    static const bool host_lm_env = getenv("SSX_BA_HOST_LM") != nullptr;   // large windows: the former host-driven LM loop (A/B, tests)
-    if (!d.big || !host_lm_env) {
-      // ---- the whole optimize(iters) is enqueued; lm_step() on the device decides after every trial (large windows too:
-      // their former loop paid one stream synchronisation per LM trial, 0.4 of 1.26 ms per iteration at C4) ----
-      // One slot = (re)linearise if needed + one trial.  A rejected trial consumes a slot without finishing its
-      // iteration, so after the first `iters` slots the host looks at the control block once and tops up.
-      hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(1), 0, ctx->stream, d, cur, opt.iters, res->n_iters, active ? 0 : 1);
-      int slots_total = 0;
-      bool first_slot = true;
-      while (active && opt.iters > 0) {
-        int slots = slots_total == 0 ? opt.iters : std::max(1, opt.iters - (int)hscal[SC_IT]);
-        for (int sidx = 0; sidx < slots; ++sidx) {
-          // the first slot of an optimize() needs lambda_0 between the linearisation and the Schur complement; every
-          // later slot (and every slot with a collective between the two) knows its damping: one fused kernel
-          const bool fused = !d.big && !first_slot && !cm.fn && nCh > 0 && n > 0;
-          if (d.big) {
-            // (k_linearize skips itself while the kept linearisation is valid; the pose blocks too unless a collective follows:
-            // their all-reduced copy must be rebuilt from this rank's part before it is summed again)
-            const int pb_cur = cm.fn ? -1 : -2;
-            if (nCh > 0) {
-              if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
-              else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
-            }
-            if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_NUMERIC_G2O>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
-            else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_ANALYTIC>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
-            SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin_big, dim3(1), dim3(CH), 0, ctx->stream, d));
-          } else
-          if (fused) {
-            if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), lds_fused, ctx->stream, d));
-            else SSX_PROF(ctx, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), lds_fused, ctx->stream, d));
-          } else if (nCh > 0) {
+    // ---- one g2o optimize(iters): OptimizationAlgorithmLevenberg::solve per iteration.  The whole optimize(iters) is enqueued;
+    // lm_step() on the device decides after every trial (no stream synchronisation per trial) ----
+    // One slot = (re)linearise if needed + one trial.  A rejected trial consumes a slot without finishing its
+    // iteration, so after the first `iters` slots the host looks at the control block once and tops up.
+    hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(1), 0, ctx->stream, d, cur, opt.iters, res->n_iters, active ? 0 : 1);
+    int slots_total = 0;
+    bool first_slot = true;
+    while (active && opt.iters > 0) {
+      int slots = slots_total == 0 ? opt.iters : std::max(1, opt.iters - (int)hscal[SC_IT]);
+      for (int sidx = 0; sidx < slots; ++sidx) {
+        // the first slot of an optimize() needs lambda_0 between the linearisation and the Schur complement; every
+        // later slot (and every slot with a collective between the two) knows its damping: one fused kernel
+        const bool fused = !d.big && !first_slot && !cm.fn && nCh > 0 && n > 0;
+        if (d.big) {
+          // (k_linearize skips itself while the kept linearisation is valid; the pose blocks too unless a collective follows:
+          // their all-reduced copy must be rebuilt from this rank's part before it is summed again)
+          const int pb_cur = cm.fn ? -1 : -2;
+          if (nCh > 0) {
             if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
             else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
           }
-          // later slots of a single-rank solve: the two reductions as one launch (the first slot needs lambda between them, ranks an all-reduce)
-          static const bool no_both_env = getenv("SSX_BA_SPLIT_REDUCE") != nullptr;   // (tools: the two launches, for A/B timing)
-          const bool both = !d.big && fused && !first_slot && !cm.fn && n > 0 && !no_both_env;
-          const int n_rl = std::max(1, (d.nP * 27 + 63) / 64);
-          if (both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_both, dim3(n_rl + (nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d, n_rl));
-          else if (!d.big) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin, dim3(n_rl), dim3(CH), 0, ctx->stream, d));
-          // (band solver, later slots: lambda is known, so the linearisation's sums travel with the trial's reduced system)
-          static const bool no_fuse_env = getenv("SSX_BA_NO_FUSED_ALLREDUCE") != nullptr;
-          const bool fuse_iter = d.big && bnd.on && cm.fn && !first_slot && !no_fuse_env;
-          if (!fuse_iter) {
-            st = allreduce(ctx, cm, d.iter_comm, (size_t)d.nP * 27 + 1 + d.world);
-            if (st != SSX_OK) return st;
-            if (first_slot || cm.fn) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(64), 0, ctx->stream, d, first_slot ? 1 : 0));
-          }
-          first_slot = false;
-          if (d.big) {
-            st = big_trial(0.0, 2, -1, fuse_iter);
-            if (st != SSX_OK) return st;
-          } else {
-          if (n > 0) {
-            if (nCh > 0 && !fused) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur, dim3(nCh), dim3(CH), lds_schur, ctx->stream, d, -1, 0.0, 2));
-            if (!both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur, dim3((nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d));
-            st = allreduce(ctx, cm, d.trial_comm, (size_t)n * n + n);
-            if (st != SSX_OK) return st;
-          }
-          if (n <= NB) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64, dim3(1), dim3(CH), 0, ctx->stream, d, -1, 0.0, 1));
-          else if (n <= 80) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80, dim3(1), dim3(CH), 0, ctx->stream, d, -1, 0.0, 1));
-          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve, dim3(1), dim3(CH), 0, ctx->stream, d, -1, 0.0, 1));
-          }
-          // one GPU: the last chunk of k_backsub_residual sums the trial and takes the LM decision itself (finish)
-          const bool finish = nCh > 0 && !cm.fn && g_trial_finish.load() != 0;
-          if (nCh > 0) SSX_PROF(ctx, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual, dim3(nCh), dim3(CH), 0, ctx->stream, d, -1, 0.0, 1, finish ? 1 : 0));
-          if (!finish) SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial, dim3(1), dim3(CH), 0, ctx->stream, d, cm.fn ? 0 : 1));
-          if (cm.fn) {
-            st = allreduce(ctx, cm, d.scal_comm, 3);
-            if (st != SSX_OK) return st;
-            SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_publish_trial, dim3(1), dim3(1), 0, ctx->stream, d, 1));
-          }
+          if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_NUMERIC_G2O>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
+          else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_ANALYTIC>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
+          SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin_big, dim3(1), dim3(CH), 0, ctx->stream, d));
+        } else
+        if (fused) {
+          if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), lds_fused, ctx->stream, d));
+          else SSX_PROF(ctx, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), lds_fused, ctx->stream, d));
+        } else if (nCh > 0) {
+          if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
+          else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
         }
-        slots_total += slots;
-        SSX_HIP_TRY(ctx, hipGetLastError());
-        if (pack_ok) {
-          // one rank: the control block, the statistics and the estimate (and the per-edge chi2 of a device-marshalled window) leave in
-          // ONE kernel-written block behind the last slot -- if this optimize() was the last one the download below finds everything there
-          if (pack_err) {
-            hipLaunchKernelGGL(k_c2_out, dim3((d.E + CH - 1) / CH), dim3(CH), 0, ctx->stream, d, have_trial_err ? 1 : 2);
-            hipLaunchKernelGGL(k_stream_out, dim3((unsigned)std::min<size_t>(256, ((size_t)d.E_raw + 2 * CH - 1) / (2 * CH))), dim3(CH), 0, ctx->stream, (const double*)d.c2_out, pk_err, (size_t)d.E_raw);
-          }
-          const size_t n_pack = SC_N + 3 * SSX_BA_MAX_STATS + 7 * (size_t)d.P + 3 * (size_t)d.L;
-          hipLaunchKernelGGL(k_pack_one, dim3((unsigned)std::min<size_t>(256, (n_pack + CH - 1) / CH)), dim3(CH), 0, ctx->stream, d, hscal, pk_pose, pk_point);
-          SSX_HIP_TRY(ctx, hipGetLastError());
-          packed = true;
-        } else {
-          SSX_HIP_TRY(ctx, hipMemcpyAsync(hscal, d.scal, sizeof(double) * SC_N, hipMemcpyDeviceToHost, ctx->stream));
+        // later slots of a single-rank solve: the two reductions as one launch (the first slot needs lambda between them, ranks an all-reduce)
+        static const bool no_both_env = getenv("SSX_BA_SPLIT_REDUCE") != nullptr;   // (tools: the two launches, for A/B timing)
+        const bool both = !d.big && fused && !first_slot && !cm.fn && n > 0 && !no_both_env;
+        const int n_rl = std::max(1, (d.nP * 27 + 63) / 64);
+        if (both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_both, dim3(n_rl + (nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d, n_rl));
+        else if (!d.big) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin, dim3(n_rl), dim3(CH), 0, ctx->stream, d));
+        // (band solver, later slots: lambda is known, so the linearisation's sums travel with the trial's reduced system)
+        const bool fuse_iter = d.big && bnd.on && cm.fn && !first_slot;
+        if (!fuse_iter) {
+          st = allreduce(ctx, cm, d.iter_comm, (size_t)d.nP * 27 + 1 + d.world);
+          if (st != SSX_OK) return st;
+          if (first_slot || cm.fn) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(64), 0, ctx->stream, d, first_slot ? 1 : 0));
         }
-        SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the one host round trip of an optimize(iters)
-        if (hscal[SC_STOP] != 0.0) break;
-      }
-      if (active && opt.iters > 0) {
-        cur = (int)hscal[SC_CUR];
-        n_out_total = hscal[SC_NOUT];
-        if (hscal[SC_TRIALS_RUN] > 0.0) have_trial_err = true;
-        const int n_done = (int)hscal[SC_NSTAT];
-        if (n_done > res->n_iters) {
-          double* hstat = hscal + SC_N;                                // pinned, behind the scalar block
-          if (!packed) {                                               // (k_pack_one brought them along)
-            SSX_HIP_TRY(ctx, hipMemcpyAsync(hstat, d.lm_stat, sizeof(double) * 3 * SSX_BA_MAX_STATS, hipMemcpyDeviceToHost, ctx->stream));
-            SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-          }
-          for (int k = res->n_iters; k < n_done && k < SSX_BA_MAX_STATS; ++k) {
-            res->iter_chi2[k] = hstat[k];
-            res->iter_lambda[k] = hstat[SSX_BA_MAX_STATS + k];
-            res->iter_trials[k] = (int)hstat[2 * SSX_BA_MAX_STATS + k];
-          }
-          res->n_iters = n_done;
-        }
-      }
-    } else
-    for (int it = 0; it < opt.iters && active; ++it) {
-      if (!spec_done) {
-        st = launch_linearize(ctx, d, bd, cm, opt.jac_mode, cur, it == 0);
-        if (st != SSX_OK) return st;
-      }
-      spec_done = false;
-      double currentChi = 0.0, rho = 0.0, tempChi = 0.0;
-      int qmax = 0;
-      bool lambda_bad = false;
-      do {
-        // lambda: known to the host except on the very first trial of a round, where k_lambda_init left it on the device
-        const int dev_lambda = (it == 0 && qmax == 0) ? 1 : 0;
+        first_slot = false;
         if (d.big) {
-          st = big_trial(lambda, dev_lambda, cur);
+          st = big_trial(fuse_iter);
           if (st != SSX_OK) return st;
         } else {
         if (n > 0) {
-          if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur, dim3(nCh), dim3(CH), lds_schur, ctx->stream, d, cur, lambda, dev_lambda));
-          SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur, dim3((nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d));
+          if (nCh > 0 && !fused) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur, dim3(nCh), dim3(CH), lds_schur, ctx->stream, d));
+          if (!both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur, dim3((nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d));
           st = allreduce(ctx, cm, d.trial_comm, (size_t)n * n + n);
           if (st != SSX_OK) return st;
         }
-        if (n <= NB) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64, dim3(1), dim3(CH), 0, ctx->stream, d, cur, lambda, dev_lambda));
-        else if (n <= 80) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80, dim3(1), dim3(CH), 0, ctx->stream, d, cur, lambda, dev_lambda));
-        else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve, dim3(1), dim3(CH), 0, ctx->stream, d, cur, lambda, dev_lambda));
+        if (n <= NB) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64, dim3(1), dim3(CH), 0, ctx->stream, d));
+        else if (n <= 80) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80, dim3(1), dim3(CH), 0, ctx->stream, d));
+        else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve, dim3(1), dim3(CH), 0, ctx->stream, d));
         }
-        if (nCh > 0) SSX_PROF(ctx, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual, dim3(nCh), dim3(CH), 0, ctx->stream, d, cur, lambda, dev_lambda, 0));
-        SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial, dim3(1), dim3(CH), 0, ctx->stream, d, 0));
+        // one GPU: the last chunk of k_backsub_residual sums the trial and takes the LM decision itself (finish)
+        const bool finish = nCh > 0 && !cm.fn && g_trial_finish.load() != 0;
+        if (nCh > 0) SSX_PROF(ctx, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual, dim3(nCh), dim3(CH), 0, ctx->stream, d, finish ? 1 : 0));
+        if (!finish) SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial, dim3(1), dim3(CH), 0, ctx->stream, d, cm.fn ? 0 : 1));
         if (cm.fn) {
           st = allreduce(ctx, cm, d.scal_comm, 3);
           if (st != SSX_OK) return st;
-          SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_publish_trial, dim3(1), dim3(1), 0, ctx->stream, d, 0));
+          SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_publish_trial, dim3(1), dim3(1), 0, ctx->stream, d));
         }
+      }
+      slots_total += slots;
+      SSX_HIP_TRY(ctx, hipGetLastError());
+      if (pack_ok) {
+        // one rank: the control block, the statistics and the estimate (and the per-edge chi2 of a device-marshalled window) leave in
+        // ONE kernel-written block behind the last slot -- if this optimize() was the last one the download below finds everything there
+        if (pack_err) {
+          hipLaunchKernelGGL(k_c2_out, dim3((d.E + CH - 1) / CH), dim3(CH), 0, ctx->stream, d, have_trial_err ? 1 : 2);
+          hipLaunchKernelGGL(k_stream_out, dim3((unsigned)std::min<size_t>(256, ((size_t)d.E_raw + 2 * CH - 1) / (2 * CH))), dim3(CH), 0, ctx->stream, (const double*)d.c2_out, pk_err, (size_t)d.E_raw);
+        }
+        const size_t n_pack = SC_N + 3 * SSX_BA_MAX_STATS + 7 * (size_t)d.P + 3 * (size_t)d.L;
+        hipLaunchKernelGGL(k_pack_one, dim3((unsigned)std::min<size_t>(256, (n_pack + CH - 1) / CH)), dim3(CH), 0, ctx->stream, d, hscal, pk_pose, pk_point);
         SSX_HIP_TRY(ctx, hipGetLastError());
-        SSX_HIP_TRY(ctx, hipMemcpyAsync(hscal, d.scal, sizeof(double) * 8, hipMemcpyDeviceToHost, ctx->stream));
-        const bool spec_pending = it + 1 < opt.iters;
-        if (spec_pending) {
-          SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev_spec, ctx->stream));      // the scalars are complete here
-          st = launch_linearize(ctx, d, bd, cm, opt.jac_mode, cur ^ 1, 0);
-          if (st != SSX_OK) return st;
-          SSX_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_spec));              // the one host round trip of an LM trial
-        } else {
+        packed = true;
+      } else {
+        SSX_HIP_TRY(ctx, hipMemcpyAsync(hscal, d.scal, sizeof(double) * SC_N, hipMemcpyDeviceToHost, ctx->stream));
+      }
+      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the one host round trip of an optimize(iters)
+      if (hscal[SC_STOP] != 0.0) break;
+    }
+    if (active && opt.iters > 0) {
+      cur = (int)hscal[SC_CUR];
+      n_out_total = hscal[SC_NOUT];
+      if (hscal[SC_TRIALS_RUN] > 0.0) have_trial_err = true;
+      const int n_done = (int)hscal[SC_NSTAT];
+      if (n_done > res->n_iters) {
+        double* hstat = hscal + SC_N;                                // pinned, behind the scalar block
+        if (!packed) {                                               // (k_pack_one brought them along)
+          SSX_HIP_TRY(ctx, hipMemcpyAsync(hstat, d.lm_stat, sizeof(double) * 3 * SSX_BA_MAX_STATS, hipMemcpyDeviceToHost, ctx->stream));
           SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
-        have_trial_err = true;
-        if (qmax == 0) {
-          currentChi = hscal[SC_CHI2_CUR];
-          if (it == 0) { lambda = hscal[SC_LAMBDA]; ni = 2.0; }
+        for (int k = res->n_iters; k < n_done && k < SSX_BA_MAX_STATS; ++k) {
+          res->iter_chi2[k] = hstat[k];
+          res->iter_lambda[k] = hstat[SSX_BA_MAX_STATS + k];
+          res->iter_trials[k] = (int)hstat[2 * SSX_BA_MAX_STATS + k];
         }
-        const bool ok2 = hscal[SC_SOLVE_OK] != 0.0;
-        tempChi = hscal[SC_TEMP_CHI];
-        n_out_total = hscal[SC_NOUT];
-        if (!ok2) tempChi = std::numeric_limits<double>::max();
-        rho = currentChi - tempChi;
-        double scale = hscal[SC_SCALE_P] + hscal[SC_SCALE_L];
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          lambda *= std::max(1. / 3., alpha);
-          ni = 2;
-          currentChi = tempChi;
-          cur ^= 1;   // accept: the trial buffers become the state
-          spec_done = spec_pending;
-        } else {
-          lambda *= ni;
-          ni *= 2;
-          if (!std::isfinite(lambda)) { lambda_bad = true; break; }
-          if (spec_pending && rho < 0 && qmax + 1 < 10) {
-            // rejected and another trial follows: bring the linearisation of the kept state back
-            st = launch_linearize(ctx, d, bd, cm, opt.jac_mode, cur, 0);
-            if (st != SSX_OK) return st;
-          }
-        }
-        qmax++;
-      } while (rho < 0 && qmax < 10);
-      if (res->n_iters < SSX_BA_MAX_STATS) {
-        res->iter_chi2[res->n_iters] = tempChi;
-        res->iter_lambda[res->n_iters] = lambda;
-        res->iter_trials[res->n_iters] = qmax;
+        res->n_iters = n_done;
       }
-      res->n_iters++;
-      if (qmax == 10 || rho == 0 || lambda_bad) break;
     }
     res->rounds++;
     // outlier statistics of this round from the errors of the last evaluated trial (backend.cpp:181-194);
@@ -4030,12 +3921,12 @@ ssx_status batch_run(ssx_ba_batch* B, ssx_ba_result* results, int32_t* lm_iterat
           if (both) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_both_b, dim3(B->max_rl + B->max_rs, hn), dim3(CH), 0, hs, hv, B->max_rl));
           else SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin_b, gRl, dim3(CH), 0, hs, hv));
           if (first_slot) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init_b, gOne, dim3(64), 0, hs, hv, 1));
-          if (!fused) SSX_PROF_ON(ctx, hs, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_b, gWg, dim3(CH), lds_schur, hs, hv, -1, 0.0, 2));
+          if (!fused) SSX_PROF_ON(ctx, hs, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_b, gWg, dim3(CH), lds_schur, hs, hv));
           if (!both) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur_b, gRs, dim3(CH), 0, hs, hv));
-          if (B->any_solve64) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64_b, gOne, dim3(CH), 0, hs, hv, -1, 0.0, 1));
-          if (B->any_solve80) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80_b, gOne, dim3(CH), 0, hs, hv, -1, 0.0, 1));
-          if (B->any_solve) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve_b, gOne, dim3(CH), 0, hs, hv, -1, 0.0, 1));
-          SSX_PROF_ON(ctx, hs, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual_b, gCh, dim3(CH), 0, hs, hv, -1, 0.0, 1, fin_b ? 1 : 0));
+          if (B->any_solve64) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64_b, gOne, dim3(CH), 0, hs, hv));
+          if (B->any_solve80) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80_b, gOne, dim3(CH), 0, hs, hv));
+          if (B->any_solve) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve_b, gOne, dim3(CH), 0, hs, hv));
+          SSX_PROF_ON(ctx, hs, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual_b, gCh, dim3(CH), 0, hs, hv, fin_b ? 1 : 0));
           if (!fin_b) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial_b, gOne, dim3(CH), 0, hs, hv, 1));   // (a window without chunks: nobody would finish its trial)
         }
         first_slot = false;

@@ -559,11 +559,11 @@ static inline size_t band_lds_back(int w, int nF, int nslots)
 }
 
 // ---- level 0: one workgroup per segment ----------------------------------------------------------------------------
-__global__ __launch_bounds__(BAND_T, 1) void k_band_seg(BaDev d, BandDev bd, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(BAND_T, 1) void k_band_seg(BaDev d, BandDev bd)
 {
   extern __shared__ __attribute__((aligned(16))) double band_smem[];
-  if (use_dev_lambda == 2 && d.scal[SC_STOP] != 0.0) return;          // device-driven LM, already terminated
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  if (d.scal[SC_STOP] != 0.0) return;                                  // device-driven LM, already terminated
+  const double lambda = d.scal[SC_LAMBDA];
   const int k = blockIdx.x, t = threadIdx.x, w = bd.w;
   BandSys sy{bd.nP, w, bd.Sb, bd.bsv};
   BandJob jb{bd.seg_p0[k], bd.seg_m[k], w, w, 0, 1};
@@ -600,9 +600,9 @@ __global__ __launch_bounds__(BAND_T, 1) void k_band_seg(BaDev d, BandDev bd, dou
 
 // ---- separator system: S_sep + lambda I + the segments' updates, in band layout (nPr = K w poses, bandwidth 2w-1) --------
 // reduced pose i = k w + a  <->  pose seg_p0[k] + seg_m[k] + a  (separator k sits behind segment k's interior)
-__global__ __launch_bounds__(BAND_T) void k_band_assemble(BaDev d, BandDev bd, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(BAND_T) void k_band_assemble(BaDev d, BandDev bd)
 {
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  const double lambda = d.scal[SC_LAMBDA];
   const int w = bd.w, K = bd.K, wr = bd.wr, nPr = bd.nPr;
   const int NU = 12 * w + 1;
   BandSys sy{bd.nP, w, bd.Sb, bd.bsv};
@@ -642,13 +642,13 @@ __global__ __launch_bounds__(BAND_T) void k_band_assemble(BaDev d, BandDev bd, d
 // ---- top level: complete factorisation + back-substitution of a (small) cyclic band system by ONE workgroup ------------
 // single level (K == 1): the whole reduced pose system, the last w poses as fixed rows (they carry the wrap-around);
 // K > 1: the separator system from k_band_assemble (lambda already inside).
-__global__ __launch_bounds__(BAND_TOP_T, 1) void k_band_top(BaDev d, BandDev bd, BigDev b, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(BAND_TOP_T, 1) void k_band_top(BaDev d, BandDev bd, BigDev b)
 {
   extern __shared__ __attribute__((aligned(16))) double band_smem[];
   const int t = threadIdx.x;
-  if (use_dev_lambda == 2 && d.scal[SC_STOP] != 0.0) return;          // device-driven LM, already terminated
+  if (d.scal[SC_STOP] != 0.0) return;                                  // device-driven LM, already terminated
   const bool single = bd.K == 1;
-  const double lambda = single ? (use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg) : 0.0;
+  const double lambda = single ? d.scal[SC_LAMBDA] : 0.0;
   const int nP = single ? bd.nP : bd.nPr, w = single ? bd.w : bd.wr, nF = bd.w;
   const double* Sb = single ? bd.Sb : bd.Sr;
   BandSys sy{nP, w, Sb, Sb + (size_t)nP * (w + 1) * 36};
@@ -677,10 +677,10 @@ __global__ __launch_bounds__(BAND_TOP_T, 1) void k_band_top(BaDev d, BandDev bd,
 }
 
 // ---- level 0 back-substitution: one workgroup per segment ---------------------------------------------------------------
-__global__ __launch_bounds__(BAND_T, 1) void k_band_back(BaDev d, BandDev bd, BigDev b, int dev_lm)
+__global__ __launch_bounds__(BAND_T, 1) void k_band_back(BaDev d, BandDev bd, BigDev b)
 {
   extern __shared__ __attribute__((aligned(16))) double band_smem[];
-  if (d.scal[SC_SOLVE_OK] == 0.0 || (dev_lm && d.scal[SC_STOP] != 0.0)) return;
+  if (d.scal[SC_SOLVE_OK] == 0.0 || d.scal[SC_STOP] != 0.0) return;
   const int k = blockIdx.x, t = threadIdx.x, w = bd.w;
   BandSys sy{bd.nP, w, bd.Sb, bd.bsv};
   BandJob jb{bd.seg_p0[k], bd.seg_m[k], w, w, 0, 1};
@@ -701,9 +701,9 @@ __global__ __launch_bounds__(BAND_T, 1) void k_band_back(BaDev d, BandDev bd, Bi
 }
 
 // one wave per non-zero block of S (as k_schur_blocks), written into the band layout; wrap-around blocks transposed
-__global__ __launch_bounds__(CH) void k_schur_blocks_band(BaDev d, BigDev b, BandDev bd, int dev_lm)
+__global__ __launch_bounds__(CH) void k_schur_blocks_band(BaDev d, BigDev b, BandDev bd)
 {
-  if (dev_lm && d.scal[SC_STOP] != 0.0) return;                       // device-driven LM, already terminated
+  if (d.scal[SC_STOP] != 0.0) return;                                  // device-driven LM, already terminated
   const int lane = threadIdx.x & 63;
   const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), qr = (lane >> 1) & 1, qc = lane & 1;
   if (blk >= b.nBlkS) return;

@@ -201,15 +201,15 @@ __global__ __launch_bounds__(CH) void k_reduce_lin_big(BaDev d)
 }
 
 // ---- Schur complement --------------------------------------------------------------------------
-__global__ __launch_bounds__(CH) void k_schur_prep(BaDev d, BigDev b, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(CH) void k_schur_prep(BaDev d, BigDev b)
 {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* sW = reinterpret_cast<double*>(smem);   // [18][PW]
   double* sDinv = sW + 18 * PW;                   // [9][PW]
   double* sDb = sDinv + 9 * PW;                   // [3][PW]
   const int c = blockIdx.x, t = threadIdx.x;
-  if (use_dev_lambda == 2 && d.scal[SC_STOP] != 0.0) return;          // device-driven LM, already terminated
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  if (d.scal[SC_STOP] != 0.0) return;                                  // device-driven LM, already terminated
+  const double lambda = d.scal[SC_LAMBDA];
   const int lm0 = d.ch_lm[c], lm1 = d.ch_lm[c + 1];
   const int e0 = d.lm_ptr[lm0], e1 = d.lm_ptr[lm1];
   const int ne = e1 - e0, nl = lm1 - lm0;
@@ -794,7 +794,7 @@ __global__ void k_scale_finish(BaDev d, BigDev b, int nparts)
 // pivots, one thread per row below it -- 52 000 cycles of factorisation, now 43 000, of which the 64 dependent pivots are
 // ~13 000.)
 template <int TS>
-__device__ __forceinline__ void k_solve_tiles_body(const BaDev& d, const int bx, int cur, double lambda_arg, int use_dev_lambda)
+__device__ __forceinline__ void k_solve_tiles_body(const BaDev& d, const int bx)
 {
   constexpr int NT = 16 * TS, T2 = TS * TS;
   __shared__ __attribute__((aligned(16))) double sDg[2][T2];          // L_kk row-major; the diagonal entries hold 1 / l_cc
@@ -821,11 +821,9 @@ __device__ __forceinline__ void k_solve_tiles_body(const BaDev& d, const int bx,
   for (int c = 0; c < TS; ++c) R[c] = (ty == 15 && TS * tx + c < n) ? bs[TS * tx + c] : 0.0;
   const double bp0 = (t < n) ? d.iter_comm[d.nP * UPPER6 + t] : 0.0;   // the (all-reduced) pose part of b, for the scale at the end
   const double bp1 = (NT > 64 && t < 64 && t + 64 < n) ? d.iter_comm[d.nP * UPPER6 + t + 64] : 0.0;
-  if (cur < 0) {                                   // device-driven LM
-    if (d.scal[SC_STOP] != 0.0) return;
-    cur = (int)d.scal[SC_CUR];
-  }
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  if (d.scal[SC_STOP] != 0.0) return;              // device-driven LM, already terminated
+  const int cur = (int)d.scal[SC_CUR];
+  const double lambda = d.scal[SC_LAMBDA];
   // the poses this workgroup updates at the end: on their way during the factorisation
   const double* src = d.pose[cur];
   double* dst = d.pose[cur ^ 1];
@@ -1036,7 +1034,7 @@ __device__ __forceinline__ void k_solve_tiles_body(const BaDev& d, const int bx,
 // the NEXT pivot row is updated first and goes out to LDS before the other 15 fmas.  60 steps of ~450 cycles against 15 tile steps
 // of ~2 900 (diagonal tile by one thread, panel, trailing update: two barriers each); the back-substitution reads row t of L^T
 // into lane t's registers once and runs unrolled on readlane.  25 -> 15 us per solve (profiles/r05/solve64.md).
-__device__ __forceinline__ void k_solve_rows64_body(const BaDev& d, int cur, double lambda_arg, int use_dev_lambda)
+__device__ __forceinline__ void k_solve_rows64_body(const BaDev& d)
 {
   constexpr int M = 64, RG = 4, NR = M / RG, RHS = M - 1, OP = M + 1;     // OP: row pitch of O (lane t reads row t: no bank conflicts)
   __shared__ double O[M * OP];                                            // O[k][c] = L[c][k] (c > k), 1 / L[k][k] (c == k), y_k (c == RHS)
@@ -1062,11 +1060,9 @@ __device__ __forceinline__ void k_solve_rows64_body(const BaDev& d, int cur, dou
     for (int nn = 0; nn < NR; ++nn) a[nn] = (rg + RG * nn < n && (colS || colR)) ? v[nn] : 0.0;
   }
   const double bp0 = (t < n) ? d.iter_comm[d.nP * UPPER6 + t] : 0.0;   // the (all-reduced) pose part of b, for the scale at the end
-  if (cur < 0) {                                   // device-driven LM
-    if (d.scal[SC_STOP] != 0.0) return;
-    cur = (int)d.scal[SC_CUR];
-  }
-  const double lambda = use_dev_lambda ? d.scal[SC_LAMBDA] : lambda_arg;
+  if (d.scal[SC_STOP] != 0.0) return;              // device-driven LM, already terminated
+  const int cur = (int)d.scal[SC_CUR];
+  const double lambda = d.scal[SC_LAMBDA];
   // the poses this workgroup updates at the end: on their way during the factorisation
   const double* src = d.pose[cur];
   double* dst = d.pose[cur ^ 1];
@@ -1170,25 +1166,25 @@ __device__ __forceinline__ void k_solve_rows64_body(const BaDev& d, int cur, dou
   }
 }
 
-__global__ __launch_bounds__(CH) void k_solve64(BaDev d, int cur, double lambda_arg, int use_dev_lambda) { k_solve_rows64_body(d, cur, lambda_arg, use_dev_lambda); }
-__global__ __launch_bounds__(CH) void k_solve80(BaDev d, int cur, double lambda_arg, int use_dev_lambda) { k_solve_tiles_body<5>(d, blockIdx.x, cur, lambda_arg, use_dev_lambda); }
-__global__ __launch_bounds__(CH) void k_solve(BaDev d, int cur, double lambda_arg, int use_dev_lambda) { k_solve_tiles_body<6>(d, blockIdx.x, cur, lambda_arg, use_dev_lambda); }
+__global__ __launch_bounds__(CH) void k_solve64(BaDev d) { k_solve_rows64_body(d); }
+__global__ __launch_bounds__(CH) void k_solve80(BaDev d) { k_solve_tiles_body<5>(d, blockIdx.x); }
+__global__ __launch_bounds__(CH) void k_solve(BaDev d) { k_solve_tiles_body<6>(d, blockIdx.x); }
 // batched: blockIdx.y = window; every window brings its own BaDev (device array)
-__global__ __launch_bounds__(CH) void k_solve64_b(const BaDev* __restrict__ dv, int cur, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(CH) void k_solve64_b(const BaDev* __restrict__ dv)
 {
   const BaDev& d = dv[blockIdx.y];       // by reference: a private copy of the 500-byte struct ends up in scratch memory
   if ((int)blockIdx.x >= ((6 * d.nP <= 64) ? 1 : 0)) return;
-  k_solve_rows64_body(d, cur, lambda_arg, use_dev_lambda);
+  k_solve_rows64_body(d);
 }
-__global__ __launch_bounds__(CH) void k_solve_b(const BaDev* __restrict__ dv, int cur, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(CH) void k_solve_b(const BaDev* __restrict__ dv)
 {
   const BaDev& d = dv[blockIdx.y];
   if ((int)blockIdx.x >= ((6 * d.nP > 80) ? 1 : 0)) return;
-  k_solve_tiles_body<6>(d, blockIdx.x, cur, lambda_arg, use_dev_lambda);
+  k_solve_tiles_body<6>(d, blockIdx.x);
 }
-__global__ __launch_bounds__(CH) void k_solve80_b(const BaDev* __restrict__ dv, int cur, double lambda_arg, int use_dev_lambda)
+__global__ __launch_bounds__(CH) void k_solve80_b(const BaDev* __restrict__ dv)
 {
   const BaDev& d = dv[blockIdx.y];
   if ((int)blockIdx.x >= ((6 * d.nP > 64 && 6 * d.nP <= 80) ? 1 : 0)) return;
-  k_solve_tiles_body<5>(d, blockIdx.x, cur, lambda_arg, use_dev_lambda);
+  k_solve_tiles_body<5>(d, blockIdx.x);
 }

@@ -55,7 +55,6 @@ ssx_status ssx_ctx_create(const ssx_config* cfg, ssx_ctx** out)
     // the auxiliary stream carries work that fills the gaps of the main stream's dependent chain: lowest priority
     if (c->make_stream(&c->aux, true) != hipSuccess) (void)hipGetLastError();
   }
-  (void)hipEventCreateWithFlags(&c->ev_spec, hipEventDisableTiming);
   (void)hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
   (void)hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
   (void)hipEventCreateWithFlags(&c->ev_pyr, hipEventDisableTiming);
@@ -77,7 +76,6 @@ void ssx_ctx_destroy(ssx_ctx* ctx)
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }
-  if (ctx->ev_spec) (void)hipEventDestroy(ctx->ev_spec);
   for (int g = 0; g < 3; ++g) {
     if (ctx->grp[g]) { (void)hipStreamSynchronize(ctx->grp[g]); (void)hipStreamDestroy(ctx->grp[g]); }
     if (ctx->grp_ev[g]) (void)hipEventDestroy(ctx->grp_ev[g]);
