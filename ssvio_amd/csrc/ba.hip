@@ -1764,7 +1764,7 @@ inline int dense_slabs_mode()
   }
   return m;
 }
-struct HostPrep {
+struct HostPrep {                    // what prepare() of ba_marshal.inc fills in (here: BaWorkspace below keeps them by value)
   int P, L, E, nP, nLm, nCh, nBlk;
   int E_raw = 0;                     // entries of the caller's edge arrays (E of them alive; see BaDev::E_raw)
   int raw_fmt = 0;                   // BaDev::raw_fmt of the blob this window is uploaded in
@@ -1962,1036 +1962,45 @@ static void ssx_ba_workspace_free(BaWorkspace* w)
   delete w;
 }
 
+// the context's BA workspace, created on first use
+static BaWorkspace* ba_workspace(ssx_ctx* ctx) { if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; } return ctx->ba; }
+
 namespace {
+#include "ba_marshal.inc"
 
+// dynamic LDS of k_schur, of the fused k_lin_schur, of k_schur_prep
+constexpr size_t SCHUR_LDS_BYTES = BA_LDS_BYTES, FUSED_LDS_BYTES = std::max(BA_LDS_BYTES, LIN_LDS_BYTES), SCHUR_PREP_LDS_BYTES = sizeof(double) * (18 + 9 + 3) * PW + 64;
+#define SSX_TRY(expr) do { const ssx_status _st = (expr); if (_st != SSX_OK) return _st; } while (0)   // a failed step ends the call
+// the analytic or the numeric (g2o's central differences) instantiation of a kernel template: LAUNCH_JAC(jac, k_x, grid, block, lds, stream, args...)
+#define LAUNCH_JAC(jac, kernel, ...) \
+  do { if ((jac) == SSX_JAC_NUMERIC_G2O) hipLaunchKernelGGL(kernel<SSX_JAC_NUMERIC_G2O>, __VA_ARGS__); else hipLaunchKernelGGL(kernel<SSX_JAC_ANALYTIC>, __VA_ARGS__); } while (0)
+// The instantiations of the kernel templates lie in the code object in the order in which host code first names them: named here
+// once, so that the device code does not depend on how the host code below and in the included files is arranged.
+[[maybe_unused]] const void* const KERNEL_TEMPLATE_ORDER[] = {(const void*)k_linearize<1>, (const void*)k_linearize<0>, (const void*)k_pose_blocks<1>,
+    (const void*)k_pose_blocks<0>, (const void*)k_lin_schur<0>, (const void*)k_lin_schur<1>, (const void*)k_bcr_fwd<24>, (const void*)k_bcr_fwd<36>, (const void*)k_bcr_bwd<24>,
+    (const void*)k_bcr_bwd<36>, (const void*)k_lin_schur_b<0>, (const void*)k_lin_schur_b<1>, (const void*)k_linearize_b<0>, (const void*)k_linearize_b<1>};
 
-// chunks of whole landmarks, <= CH_E edges and <= CH_L landmarks each (h.lm_ptr, h.nLm given)
-void make_chunks(HostPrep& h)
+// Raise the dynamic-LDS limits of the kernels that are launched with more than the default: once per process for the small-window
+// kernels (single and batched), once per size class for the band kernels (their LDS depends on the window: SolveDev::lds_*).
+void raise_lds_limits(size_t lds_seg = 0, size_t lds_top = 0, size_t lds_back = 0)
 {
-  h.ch_lm.clear();
-  h.ch_lm.push_back(0);
-  int acc_e = 0, acc_l = 0;
-  for (int lc = 0; lc < h.nLm; ++lc) {
-    const int k = h.lm_ptr[lc + 1] - h.lm_ptr[lc];
-    if (acc_e + k > CH_E || acc_l + 1 > CH_L) {
-      h.ch_lm.push_back(lc);
-      acc_e = 0; acc_l = 0;
-    }
-    acc_e += k; acc_l += 1;
+  auto raise_lds = [](auto* kernel, size_t bytes) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+  static bool attr_set = false;
+  if (!attr_set) {
+    raise_lds(k_lin_schur<SSX_JAC_ANALYTIC>, FUSED_LDS_BYTES); raise_lds(k_lin_schur<SSX_JAC_NUMERIC_G2O>, FUSED_LDS_BYTES);
+    raise_lds(k_linearize<SSX_JAC_ANALYTIC>, LIN_LDS_BYTES); raise_lds(k_linearize<SSX_JAC_NUMERIC_G2O>, LIN_LDS_BYTES);
+    raise_lds(k_schur, SCHUR_LDS_BYTES); raise_lds(k_schur_prep, SCHUR_PREP_LDS_BYTES); raise_lds(k_schur_b, SCHUR_LDS_BYTES);
+    raise_lds(k_lin_schur_b<SSX_JAC_ANALYTIC>, FUSED_LDS_BYTES); raise_lds(k_lin_schur_b<SSX_JAC_NUMERIC_G2O>, FUSED_LDS_BYTES);
+    raise_lds(k_linearize_b<SSX_JAC_ANALYTIC>, LIN_LDS_BYTES); raise_lds(k_linearize_b<SSX_JAC_NUMERIC_G2O>, LIN_LDS_BYTES);
+    attr_set = true;
   }
-  if (h.nLm > 0) h.ch_lm.push_back(h.nLm);
-  h.nCh = (int)h.ch_lm.size() - 1;
-  if (h.nCh < 0) h.nCh = 0;
+  static size_t set_seg = 0, set_top = 0, set_back = 0;
+  if (lds_seg > set_seg) { raise_lds(k_band_seg, lds_seg); set_seg = lds_seg; }
+  if (lds_top > set_top) { raise_lds(k_band_top, lds_top); set_top = lds_top; }
+  if (lds_back > set_back) { raise_lds(k_band_back, lds_back); set_back = lds_back; }
 }
 
-// A window whose raw observation arrays and state live in device buffers of their own (ssx_ba_window): upload() then sends
-// only the counting tables, and the solve starts from / leaves its result in the window's state buffers.
-struct WinExt {
-  const int* r_edge_pose = nullptr; const int* r_edge_point = nullptr; const double* r_edge_uv = nullptr; const uint8_t* r_edge_cam = nullptr;
-  double* pose[2] = {nullptr, nullptr}; double* point[2] = {nullptr, nullptr};
-  int cur = 0;                       // in: the buffer that holds the current estimate; out: the one that holds the result
-  // the order the solve gives its vertices: the window's live keyframe / landmark SLOTS sorted by the caller's ids (what g2o does
-  // with its vertex ids, sparse_optimizer.cpp:305-330) -- free-pose indices, the order of a landmark's edges, the landmark order of
-  // the chunks all follow it, so the bits of a solve do not depend on which slots the window happened to reuse
-  const int* pose_order = nullptr; int n_pose_order = 0;
-  const int* lm_order = nullptr; int n_lm_order = 0;
-};
-
-static int g_prep_threads_override = 0;   // test hook (ssx_ba_debug_prepare_digest): threads of the large-window observation pass
-
-// allow_dev_prep: small windows leave everything beyond counting to the device (see HostPrep::dev_prep); SSX_BA_HOST_PREP=1
-// keeps the host marshalling below as the reference of the tests (same bits: test_device_marshalling_equals_host_marshalling)
-ssx_status prepare(ssx_ctx* ctx, const ssx_ba_problem* pr, HostPrep& h, bool allow_dev_prep = true, const WinExt* ext = nullptr)
-{
-  const bool dead_ok = ext != nullptr;
-  const int P = pr->P, L = pr->L, E = pr->E;
-  if (P <= 0 || L < 0 || E < 0 || !pr->poses || (L && !pr->points) ||
-      (E && (!pr->edge_pose || !pr->edge_point || !pr->edge_uv))) {
-    ctx->set_error("ssx_ba: invalid problem (P=%d L=%d E=%d or null arrays)", P, L, E);
-    return SSX_ERR_INVALID_ARG;
-  }
-  h.P = P; h.L = L; h.E = E; h.E_raw = E;
-  h.pose_free.assign(P, -1);
-  h.nP = 0;
-  h.pose_rank.clear();
-  if (ext && ext->pose_order) {
-    h.pose_rank.assign(P, P);                             // (dead slots: behind every live keyframe; nothing refers to them)
-    for (int i = 0; i < ext->n_pose_order; ++i) {
-      const int sl = ext->pose_order[i];
-      h.pose_rank[sl] = i;
-      if (!(pr->pose_fixed && pr->pose_fixed[sl])) h.pose_free[sl] = h.nP++;
-    }
-  } else
-  for (int i = 0; i < P; ++i)
-    if (!(pr->pose_fixed && pr->pose_fixed[i])) h.pose_free[i] = h.nP++;
-  static const bool host_prep_env = getenv("SSX_BA_HOST_PREP") != nullptr;
-  static const bool host_lists_env = getenv("SSX_BA_HOST_LISTS") != nullptr;
-  h.big = h.nP > SSX_BA_SMALL_P;
-  h.dev_prep = allow_dev_prep && !host_prep_env && !host_lists_env;
-  // counting sort of the edges by landmark
-  std::vector<int>& cnt = h.cnt_tmp;
-  cnt.assign(L + 1, 0);
-  std::vector<int>& first_pf = h.first_pf_tmp;            // per landmark: the first free pose (in free-pose order) that observes it
-  first_pf.assign((size_t)L + 1, h.nP + 1);
-  if (h.dev_prep) h.slot8.resize((size_t)std::max(E, 1));
-  int n_dead = 0;
-  const bool big_dev = h.big && h.dev_prep;               // large window, device-marshalled: the host also counts edges per free pose
-  if (big_dev) h.pe_ptr.assign((size_t)h.nP + 1, 0);
-  // The one pass over the observations.  A large window (480 000 observations at BASELINE configs[3]: 1.05 ms on one core, a sixth of
-  // a 10-iteration solve) takes it on the worker pool: every thread counts its range into tables of its own (slot8 = the rank
-  // inside the range), the per-landmark offsets of the ranges are summed landmark-parallel, a second pass adds them -- the same
-  // ranks as the serial loop, whatever the number of threads.
-  static const int prep_threads = [] { const char* e = getenv("SSX_BA_PREP_THREADS"); const int v = e ? atoi(e) : 0;
-                                       return v > 0 ? std::min(v, 32) : std::min(32, std::max(std::min(8, std::max(1, (int)std::thread::hardware_concurrency())), (int)std::thread::hardware_concurrency() / 2)); }();   // (measured at configs[3] on a 256-core host: 1.70 / 1.27 / 0.74 ms of prepare() on 8 / 16 / 32 threads, profiles/r06/c4_prepare_threads.txt)
-  const int T = (big_dev && !dead_ok && E >= (1 << 16) && ctx->ba) ? (g_prep_threads_override > 0 ? g_prep_threads_override : prep_threads) : 1;
-  if (T > 1) {
-    h.thr_cnt.resize((size_t)T * L); h.thr_pe.resize((size_t)T * (h.nP + 1));
-    std::vector<int> bad(T, -1);
-    auto lo = [&](int t, int n) { return (int)((long long)n * t / T); };
-    ctx->ba->pool.run(T, T, [&](int t) {
-      int* c = h.thr_cnt.data() + (size_t)t * L; int* pe = h.thr_pe.data() + (size_t)t * (h.nP + 1);
-      std::fill(c, c + L, 0); std::fill(pe, pe + h.nP + 1, 0);
-      for (int e = lo(t, E), e1 = lo(t + 1, E); e < e1; ++e) {
-        const int l = pr->edge_point[e], p = pr->edge_pose[e];
-        if (l < 0 || l >= L || p < 0 || p >= P) { bad[t] = e; return; }
-        h.slot8[e] = (uint8_t)c[l];
-        c[l]++;
-        const int pf = h.pose_free[p];
-        if (pf >= 0) pe[pf + 1]++;
-      }
-    });
-    for (int t = 0; t < T; ++t)
-      if (bad[t] >= 0) {
-        ctx->set_error("ssx_ba: edge %d references pose %d / point %d out of range", bad[t], pr->edge_pose[bad[t]], pr->edge_point[bad[t]]);
-        return SSX_ERR_INVALID_ARG;
-      }
-    ctx->ba->pool.run(T, T, [&](int t) {
-      for (int l = lo(t, L), l1 = lo(t + 1, L); l < l1; ++l) {
-        int run = 0;
-        for (int tt = 0; tt < T; ++tt) { int& c = h.thr_cnt[(size_t)tt * L + l]; const int k = c; c = run; run += k; }
-        cnt[l + 1] = run;
-      }
-    });
-    ctx->ba->pool.run(T - 1, T - 1, [&](int t1) {
-      const int t = t1 + 1;
-      const int* c = h.thr_cnt.data() + (size_t)t * L;
-      for (int e = lo(t, E), e1 = lo(t + 1, E); e < e1; ++e) h.slot8[e] = (uint8_t)(h.slot8[e] + c[pr->edge_point[e]]);
-    });
-    for (int t = 0; t < T; ++t)
-      for (int p = 0; p < h.nP; ++p) h.pe_ptr[p + 1] += h.thr_pe[(size_t)t * (h.nP + 1) + p + 1];
-  } else
-  for (int e = 0; e < E; ++e) {
-    const int l = pr->edge_point[e], p = pr->edge_pose[e];
-    if (dead_ok && l < 0) { ++n_dead; continue; }           // a window's storage: observation of a removed keyframe
-    if (l < 0 || l >= L || p < 0 || p >= P) {
-      ctx->set_error("ssx_ba: edge %d references pose %d / point %d out of range", e, p, l);
-      return SSX_ERR_INVALID_ARG;
-    }
-    if (h.dev_prep) h.slot8[e] = (uint8_t)cnt[l + 1];      // (a count beyond CH_E is reported below: the wrapped value is never used)
-    cnt[l + 1]++;
-    { const int pfk = h.pose_free[p] >= 0 ? h.pose_free[p] : h.nP; if (pfk < first_pf[l]) first_pf[l] = pfk; }
-    if (big_dev) { const int pf = h.pose_free[p]; if (pf >= 0) h.pe_ptr[pf + 1]++; }
-  }
-  if (n_dead && !h.dev_prep) { ctx->set_error("ssx_ba: dead observations need the device-side marshalling"); return SSX_ERR_UNSUPPORTED; }
-  h.E = E - n_dead;
-  // Lossless narrowing of the raw arrays on their way across PCIe (26 -> 13 bytes per observation): pose indices as bytes,
-  // landmark indices as 16-bit words, and the pixel coordinates as floats when every one of them IS a float's value -- the
-  // reference's measurements are cv::KeyPoint::pt (Point2f) widened to double (frontend.cpp:232-236, backend.cpp:126-160).
-  h.raw_fmt = 0;
-  if (h.dev_prep && !h.big && !dead_ok) {
-    if (P <= 256) h.raw_fmt |= 1;
-    if (L <= 65536) h.raw_fmt |= 2;
-    bool exact = true;
-    const double* uvp = pr->edge_uv;
-    for (size_t i = 0; i < 2 * (size_t)E; ++i) exact &= (double)(float)uvp[i] == uvp[i];
-    if (exact) h.raw_fmt |= 4;
-  }
-  h.lm_id.clear(); h.lm_ptr.clear(); h.lm_fixed.clear();
-  std::vector<int>& lm_compact = h.lm_compact;
-  std::vector<int>& start = h.start_tmp;
-  lm_compact.assign(L, -1); start.assign(L + 1, 0);
-  // The compact order of the landmarks: the caller's order (a window: ascending ids), then -- stable -- by the FIRST free pose that
-  // observes a landmark.  Map points are created keyframe by keyframe, so real windows arrive almost sorted already; what the
-  // sort buys is locality for every input: the landmarks of a chunk then share their poses, a chunk contributes to 15-25 of the
-  // 55 blocks of a 10-keyframe reduced system instead of all of them, and writes / the reductions read only those (BaDev::touch).
-  const bool lm_ordered = ext && ext->lm_order;
-  const int n_visit = lm_ordered ? ext->n_lm_order : L;
-  std::vector<int>& visit = h.visit_tmp;
-  visit.clear();
-  for (int i = 0; i < n_visit; ++i) {
-    const int l = lm_ordered ? ext->lm_order[i] : i;
-    if (cnt[l + 1] == 0) continue;
-    if (cnt[l + 1] > CH_E) {
-      ctx->set_error("ssx_ba: landmark %d has %d observations (> %d per landmark unsupported)", l, cnt[l + 1], CH_E);
-      return SSX_ERR_UNSUPPORTED;
-    }
-    visit.push_back(l);
-  }
-  if (!h.big) {
-    std::vector<int>& out = h.visit2_tmp;
-    int bucket[SSX_BA_SMALL_P + 3] = {0};
-    for (int l : visit) bucket[first_pf[l] + 1]++;
-    for (int b = 0; b < SSX_BA_SMALL_P + 2; ++b) bucket[b + 1] += bucket[b];
-    out.resize(visit.size());
-    for (int l : visit) out[bucket[first_pf[l]]++] = l;
-    visit.swap(out);
-  }
-  int run = 0;
-  for (int l : visit) {
-    lm_compact[l] = (int)h.lm_id.size();
-    h.lm_id.push_back(l);
-    h.lm_ptr.push_back(run);
-    run += cnt[l + 1];
-    h.lm_fixed.push_back(pr->point_fixed ? (pr->point_fixed[l] ? 1 : 0) : 0);
-  }
-  if (run != E - n_dead) { ctx->set_error("ssx_ba_window: an observation refers to a landmark that is not in the window's order list"); return SSX_ERR_INVALID_ARG; }
-  h.lm_ptr.push_back(h.E);
-  h.nLm = (int)h.lm_id.size();
-  if (h.dev_prep) {
-    // ---- the light path: chunks + chunk descriptors + the block table; the device does the rest ----
-    make_chunks(h);
-    h.ch_desc.resize(4 * (size_t)std::max(h.nCh, 1));
-    for (int c = 0; c < h.nCh; ++c) {
-      const int lm0 = h.ch_lm[c], lm1 = h.ch_lm[c + 1], e0 = h.lm_ptr[lm0], e1 = h.lm_ptr[lm1];
-      int* cd = &h.ch_desc[4 * (size_t)c];
-      cd[0] = e0; cd[1] = e1 - e0; cd[2] = lm0; cd[3] = lm1 - lm0;
-    }
-    h.blk_pa.clear(); h.blk_pb.clear();
-    h.band_w = -1;
-    h.perm.clear(); h.pptr.clear(); h.pair_ptr.clear(); h.pair_a.clear(); h.pair_b.clear(); h.bseg.clear(); h.bseg_ptr.clear();
-    h.pe_edge.clear(); h.sblk_pa.clear(); h.sblk_pb.clear(); h.spair_ptr.assign(1, 0);
-    if (h.big) {
-      if (h.nP > 2048) { ctx->set_error("ssx_ba: %d free poses exceed the supported 2048", h.nP); return SSX_ERR_UNSUPPORTED; }
-      for (int p = 0; p < h.nP; ++p) h.pe_ptr[p + 1] += h.pe_ptr[p];   // counts -> offsets; the edge list itself is the device's (big_records)
-      h.nBlk = 0;
-      h.dev_lists = false;
-      return SSX_OK;
-    }
-    h.pe_ptr.clear();
-    for (int a = 0; a < h.nP; ++a)
-      for (int b = a; b < h.nP; ++b) { h.blk_pa.push_back((int8_t)a); h.blk_pb.push_back((int8_t)b); }
-    h.nBlk = (int)h.blk_pa.size();
-    h.dev_lists = true;
-    return SSX_OK;
-  }
-  h.perm.assign(E, 0);
-  {
-    std::vector<int> fill((size_t)L, 0);
-    for (int l = 0; l < L; ++l) if (lm_compact[l] >= 0) fill[l] = h.lm_ptr[lm_compact[l]];
-    for (int e = 0; e < E; ++e) h.perm[fill[pr->edge_point[e]]++] = e;
-  }
-  // inside a landmark: stable sort by pose so that duplicates of a (landmark,pose) pair are adjacent
-  for (int lc = 0; lc < h.nLm; ++lc) {
-    const int a = h.lm_ptr[lc], b = h.lm_ptr[lc + 1];
-    bool sorted = true;
-    for (int s = a + 1; s < b && sorted; ++s) sorted = pr->edge_pose[h.perm[s - 1]] <= pr->edge_pose[h.perm[s]];
-    if (!sorted)
-      std::stable_sort(h.perm.begin() + a, h.perm.begin() + b, [&](int x, int y) { return pr->edge_pose[x] < pr->edge_pose[y]; });
-  }
-  h.e_pose.resize(E); h.e_lmc.resize(E); h.e_cam.resize(E); h.e_dup.assign(E, 0); h.e_uv.resize(2 * (size_t)E);
-  for (int s = 0; s < E; ++s) {
-    const int e = h.perm[s];
-    h.e_pose[s] = pr->edge_pose[e];
-    h.e_lmc[s] = lm_compact[pr->edge_point[e]];
-    h.e_cam[s] = pr->edge_cam ? (pr->edge_cam[e] ? 1 : 0) : 0;
-    h.e_uv[s] = pr->edge_uv[2 * (size_t)e];
-    h.e_uv[(size_t)E + s] = pr->edge_uv[2 * (size_t)e + 1];
-    if (s > 0 && h.e_lmc[s] == h.e_lmc[s - 1] && h.e_pose[s] == h.e_pose[s - 1]) h.e_dup[s] = 1;
-  }
-  make_chunks(h);
-  h.ch_desc.resize(4 * (size_t)std::max(h.nCh, 1)); h.e_rec.resize(4 * (size_t)std::max(E, 1)); h.l_rec.resize(4 * (size_t)std::max(h.nLm, 1));
-  h.lm_chunk.resize((size_t)std::max(h.nLm, 1));
-  for (int c = 0; c < h.nCh; ++c) {
-    const int lm0 = h.ch_lm[c], lm1 = h.ch_lm[c + 1], e0 = h.lm_ptr[lm0], e1 = h.lm_ptr[lm1];
-    int* cd = &h.ch_desc[4 * (size_t)c];
-    cd[0] = e0; cd[1] = e1 - e0; cd[2] = lm0; cd[3] = lm1 - lm0;
-    for (int lc = lm0; lc < lm1; ++lc) {
-      h.lm_chunk[lc] = c;
-      int* lr = &h.l_rec[4 * (size_t)lc];
-      lr[0] = h.lm_ptr[lc] - e0; lr[1] = h.lm_ptr[lc + 1] - h.lm_ptr[lc]; lr[2] = h.lm_id[lc]; lr[3] = h.lm_fixed[lc];
-      for (int s2 = h.lm_ptr[lc]; s2 < h.lm_ptr[lc + 1]; ++s2) {
-        int* er = &h.e_rec[4 * (size_t)s2];
-        er[0] = h.e_pose[s2]; er[1] = h.pose_free[h.e_pose[s2]]; er[2] = h.lm_id[lc];
-        const int next_dup = (s2 + 1 < h.lm_ptr[lc + 1] && h.e_dup[s2 + 1]) ? 1 : 0;   // duplicates are of the same landmark
-        er[3] = (int)h.e_cam[s2] | ((int)h.e_dup[s2] << 1) | ((int)h.lm_fixed[lc] << 2) | (next_dup << 3) |
-                ((h.pose_free[h.e_pose[s2]] < 0 ? 1 : 0) << 5) | ((lc - lm0) << 8);
-      }
-    }
-  }
-  h.blk_pa.clear(); h.blk_pb.clear();
-  if (h.nP <= SSX_BA_SMALL_P)
-    for (int a = 0; a < h.nP; ++a)
-      for (int b = a; b < h.nP; ++b) { h.blk_pa.push_back((int8_t)a); h.blk_pb.push_back((int8_t)b); }
-  h.nBlk = (int)h.blk_pa.size();
-  if (h.big) {
-    const int nP = h.nP;
-    if (nP > 2048) { ctx->set_error("ssx_ba: %d free poses exceed the supported 2048", nP); return SSX_ERR_UNSUPPORTED; }
-    // pose-major edge list (free poses)
-    h.pe_ptr.assign(nP + 1, 0);
-    for (int s = 0; s < E; ++s) { const int pf = h.pose_free[h.e_pose[s]]; if (pf >= 0) h.pe_ptr[pf + 1]++; }
-    for (int p = 0; p < nP; ++p) h.pe_ptr[p + 1] += h.pe_ptr[p];
-    h.pe_edge.assign(std::max(h.pe_ptr[nP], 1), 0);
-    {
-      std::vector<int> fill(h.pe_ptr.begin(), h.pe_ptr.end() - 1);
-      for (int s = 0; s < E; ++s) { const int pf = h.pose_free[h.e_pose[s]]; if (pf >= 0) h.pe_edge[fill[pf]++] = s; }
-    }
-    // the non-zero blocks of the reduced system and their (edge, edge) pair lists are built on the device (build_pairs)
-    h.sblk_pa.clear(); h.sblk_pb.clear(); h.spair_ptr.assign(1, 0);
-    h.nBlk = 0;
-    h.band_w = -1;
-    h.bseg.clear(); h.bseg_ptr.clear();
-    h.dev_lists = false;
-    return SSX_OK;
-  }
-  // per-chunk index lists: edges grouped by free pose; leader pairs grouped by reduced-system block
-  h.dev_lists = !host_lists_env;                // (SSX_BA_HOST_LISTS: the host builder stays as the reference of the tests)
-  const int nP = h.nP, nBlk = h.nBlk;
-  h.pptr.assign((size_t)h.nCh * (nP + 1) + 1, 0);
-  h.pair_ptr.assign((size_t)h.nCh * (nBlk + 1) + 1, 0);
-  h.pair_a.clear(); h.pair_b.clear();
-  h.bseg.clear(); h.bseg_ptr.assign(2 * (size_t)h.nCh + 2, 0);
-  h.touch.assign(TOUCH_WORDS * (size_t)(h.nCh + 1), 0u);
-  std::vector<int> blk_of((size_t)std::max(nP, 1) * std::max(nP, 1), -1);
-  for (int b = 0; b < nBlk; ++b) blk_of[(size_t)h.blk_pa[b] * nP + h.blk_pb[b]] = b;
-  std::vector<int> pc(nP + 1), bc(nBlk + 1);
-  std::vector<uint32_t>& tmp_pairs = h.tmp_pairs;
-  std::vector<std::pair<int, int>>& order = h.tmp_order;   // (-part length, block)
-  h.bseg.reserve(4 * ((size_t)h.nCh * (nBlk + 8)));
-  for (int c = 0; c < h.nCh; ++c) {
-    const int lm0 = h.ch_lm[c], lm1 = h.ch_lm[c + 1];
-    const int e0 = h.lm_ptr[lm0], e1 = h.lm_ptr[lm1];
-    // --- by pose ---
-    std::fill(pc.begin(), pc.end(), 0);
-    for (int s = e0; s < e1; ++s) { const int pf = h.pose_free[h.e_pose[s]]; if (pf >= 0) pc[pf + 1]++; }
-    for (int p = 0; p < nP; ++p) pc[p + 1] += pc[p];
-    uint16_t* pp = &h.pptr[(size_t)c * (nP + 1)];
-    for (int p = 0; p <= nP; ++p) pp[p] = (uint16_t)pc[p];
-    int tail = pc[nP];
-    for (int s = e0; s < e1; ++s) {
-      const int pf = h.pose_free[h.e_pose[s]];
-      const int pos = pf >= 0 ? pc[pf]++ : tail++;
-      h.e_rec[4 * (size_t)s + 3] = (h.e_rec[4 * (size_t)s + 3] & 0xFFFF) | (pos << 16);   // the inverse map, for the kernels that store pose-major
-    }
-    if (h.dev_lists) continue;                    // k_build_lists (same lists, on the device)
-    // --- pairs by block: one pass over the landmarks of the chunk lists (block, edge a, edge b), a counting sort by
-    // block keeps the landmark order inside a block ---
-    std::fill(bc.begin(), bc.end(), 0);
-    tmp_pairs.clear();
-    for (int lc = lm0; lc < lm1; ++lc) {
-      if (h.lm_fixed[lc]) continue;
-      int nl = 0;
-      uint8_t led[CH_E]; int16_t lpf[CH_E];
-      for (int s = h.lm_ptr[lc]; s < h.lm_ptr[lc + 1]; ++s) {
-        const int pf = h.pose_free[h.e_pose[s]];
-        if (pf >= 0 && !h.e_dup[s]) { led[nl] = (uint8_t)(s - e0); lpf[nl] = (int16_t)pf; ++nl; }
-      }
-      for (int i = 0; i < nl; ++i) {
-        const int* row = &blk_of[(size_t)lpf[i] * nP];
-        for (int j = i; j < nl; ++j) {
-          const int b = row[lpf[j]];                        // pa <= pb: edges of a landmark are sorted by pose
-          bc[b + 1]++;
-          tmp_pairs.push_back((uint32_t)b << 16 | (uint32_t)led[i] << 8 | led[j]);
-        }
-      }
-    }
-    {
-      const int base = (int)h.pair_a.size();
-      bc[0] = base;
-      for (int b = 0; b < nBlk; ++b) bc[b + 1] += bc[b];
-      int* bp = &h.pair_ptr[(size_t)c * (nBlk + 1)];
-      for (int b = 0; b <= nBlk; ++b) bp[b] = bc[b];
-      h.pair_a.resize(bc[nBlk]); h.pair_b.resize(bc[nBlk]);
-      for (const uint32_t k : tmp_pairs) {
-        const int q = bc[k >> 16]++;
-        h.pair_a[q] = (uint8_t)(k >> 8); h.pair_b[q] = (uint8_t)k;
-      }
-    }
-    // --- work items of the block phase.  A lane walks ONE pair list and a wave takes as long as its longest list, so
-    // the lists (0 .. 40 pairs in a local window) are cut into parts of about the same length, the parts sorted by
-    // length, and the parts of one block kept inside one wave (their partial sums meet through wave shuffles).
-    {
-      const int* bp = &h.pair_ptr[(size_t)c * (nBlk + 1)];
-      const int base = bp[0];
-      int maxlen = 0;
-      for (int b = 0; b < nBlk; ++b) maxlen = std::max(maxlen, bp[b + 1] - bp[b]);
-      const int seg = std::max(BSEG_MIN, (maxlen + BSEG_PARTS - 1) / BSEG_PARTS);
-      const bool dense = dense_slabs_mode() != 0;
-      // (BaDev::touch, as k_build_lists writes it: blocks with pairs, poses with edges)
-      unsigned int* tm = &h.touch[(size_t)c * TOUCH_WORDS];
-      for (int b = 0; b < nBlk + nP; ++b) {
-        const bool on = b < nBlk ? (bp[b + 1] > bp[b]) : (pp[b - nBlk + 1] > pp[b - nBlk]);
-        if (on || dense) tm[b >> 5] |= 1u << (b & 31);
-      }
-      order.clear();
-      for (int b = 0; b < nBlk; ++b) {
-        const int n = bp[b + 1] - bp[b], k = (n == 0 && !dense) ? 0 : std::max(1, (n + seg - 1) / seg);
-        order.push_back({k ? -((n + k - 1) / k) : 0, b});
-      }
-      std::stable_sort(order.begin(), order.end());
-      h.bseg_ptr[2 * c] = (int)(h.bseg.size() / 4);
-      int pos = 0;                                // in items (16 per wave, four lanes each; a block's parts inside one row of 16 lanes)
-      for (const auto& ob : order) {
-        const int b = ob.second, n = bp[b + 1] - bp[b], k = (n == 0 && !dense) ? 0 : std::max(1, (n + seg - 1) / seg), len = k ? (n + k - 1) / k : 0;
-        while ((pos & 3) + k > 4) { h.bseg.push_back(-1); h.bseg.push_back(0); h.bseg.push_back(0); h.bseg.push_back(1 << 4); ++pos; }
-        for (int i = 0; i < k; ++i) {
-          const int q0 = bp[b] - base + std::min(n, i * len), q1 = bp[b] - base + std::min(n, (i + 1) * len);
-          h.bseg.push_back(b); h.bseg.push_back(q0); h.bseg.push_back(q1); h.bseg.push_back(i | (k << 4));
-          ++pos;
-        }
-      }
-      h.bseg_ptr[2 * c + 1] = (int)(h.bseg.size() / 4) - h.bseg_ptr[2 * c];
-    }
-  }
-  return SSX_OK;
-}
-
-// carve the arena and upload the problem
-// Segment plan of the band solver (ba_band.inc): w > 0 switches it on.  K interiors of >= w poses separated by w poses.
-struct BandPlan {
-  int w = 0, K = 1;
-  std::vector<int> seg_p0, seg_m;
-  BcrPlan bcr;                       // bcr.on: block cyclic reduction (ba_bcr.inc) solves the band instead of the segments
-};
-
-void plan_band(int nP, int w, BandPlan& bp)
-{
-  bp.w = w; bp.K = 1; bp.seg_p0.assign(1, 0); bp.seg_m.assign(1, nP - w);
-  if (w <= 0) return;
-  if (nP >= 48) {
-    // dependent chain ~ nP / K interior pivots + 1.5 K w separator pivots (the top window is wider)
-    int K = (int)std::lround(std::sqrt((double)nP / (1.5 * w)));
-    K = std::max(2, std::min(K, 64));
-    while (K > 1 && (nP - K * w) / K < w) --K;                      // every interior must hold >= w poses
-    while ((nP - K * w + K - 1) / K > 480) ++K;                     // LDS of the back-substitution
-    bp.K = K;
-  }
-  if (bp.K == 1) return;
-  const int K = bp.K, inner = nP - K * w, base = inner / K, rem = inner % K;
-  bp.seg_p0.resize(K); bp.seg_m.resize(K);
-  int p = 0;
-  for (int k = 0; k < K; ++k) {
-    bp.seg_p0[k] = p;
-    bp.seg_m[k] = base + (k < rem ? 1 : 0);
-    p += bp.seg_m[k] + w;
-  }
-}
-
-struct UploadPlace {          // where a window of a batch lives (nullptr = a single window in the ctx arena)
-  bool dry = false;            // sizing pass: only in_bytes / rest_bytes are computed
-  size_t in_bytes = 0, rest_bytes = 0;
-  char* in_dev = nullptr;      // uploaded blob on the device
-  char* rest_dev = nullptr;    // scratch on the device
-  char* in_host = nullptr;     // pinned mirror of the blob
-  bool keep_init = false;      // a RESIDENT batch keeps a pristine copy of the uploaded state (it is solved again from it)
-};
-
-ssx_status upload(ssx_ctx* ctx, const ssx_ba_problem* pr, const HostPrep& h, double huber_delta, double chi2_th,
-                  int world, int rank, BaDev& d, BigDev& bd, const BandPlan& bp, BandDev& bnd, UploadPlace* place = nullptr,
-                  const WinExt* ext = nullptr, const BaDev* recs = nullptr, const int* pe_ptr_dev = nullptr, const int* pe_edge_dev = nullptr)
-{
-  const bool rz = recs != nullptr;               // large window whose records / columns / raw arrays already live on the device (big_records)
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
-  const bool dup_state = place != nullptr;       // batched windows: the second state buffer is part of the uploaded blob
-  const int P = h.P, L = h.L, E = h.E, nP = h.nP, nLm = h.nLm, nCh = h.nCh, nBlk = h.nBlk;
-  const int n = 6 * nP;
-  const bool big = h.big;
-  const bool dev_lists = h.dev_lists && !big;
-  const int bseg_cap = dev_lists ? 2 * nBlk * BSEG_PARTS + 16 : 0;
-  const size_t nPairs = dev_lists ? 0 : h.pair_a.size();
-  const int lin_stride = big ? 2 : nP * 27 + 2;
-  const int n_pad = big ? ((n + NB - 1) / NB) * NB : 0;
-  const size_t nBlkS = h.sblk_pa.size();
-  Layout in;   // input blob (mirrored in pinned staging)
-  const size_t o_pose_free = in.take(rz ? 0 : sizeof(int) * P);
-  // (the landmark / chunk tables and the structure-of-arrays edge columns are read by the large-window kernels only: the
-  // small-window kernels take everything from the packed records -- a quarter of a C3 window's blob not staged, not sent)
-  const bool dev_prep = h.dev_prep && !big;
-  const bool lm_tables = big || dev_prep;
-  const size_t o_lm_fixed = in.take(lm_tables && !rz ? nLm : 0);
-  const size_t o_lm_id = in.take(lm_tables && !rz ? sizeof(int) * nLm : 0);
-  const size_t o_lm_ptr = in.take(lm_tables && !rz ? sizeof(int) * (nLm + 1) : 0);
-  const size_t o_ch_lm = in.take(big && !rz ? sizeof(int) * (nCh + 1) : 0);
-  const size_t o_e_pose = in.take(big && !rz ? sizeof(int) * E : 0);
-  const size_t o_e_lmc = in.take(big && !rz ? sizeof(int) * E : 0);
-  const size_t o_e_cam = in.take(big && !rz ? E : 0);
-  // (device-marshalled windows upload the caller's arrays; the sorted columns / records are scratch, written by k_prep_chunk)
-  size_t o_e_dup = (dev_prep || rz) ? 0 : in.take(E);
-  size_t o_e_uv = (dev_prep || rz) ? 0 : in.take(sizeof(double) * 2 * E);
-  const size_t o_ch_desc = in.take(rz ? 0 : sizeof(int) * 4 * (size_t)(nCh + 1));
-  size_t o_e_rec = (dev_prep || rz) ? 0 : in.take(sizeof(int) * 4 * (size_t)(E + 1));
-  size_t o_l_rec = (dev_prep || rz) ? 0 : in.take(sizeof(int) * 4 * (size_t)(nLm + 1));
-  const size_t o_blk_pa = in.take(nBlk + 1);
-  const size_t o_blk_pb = in.take(nBlk + 1);
-  size_t o_pptr = (dev_prep || rz) ? 0 : in.take(sizeof(uint16_t) * (h.pptr.size() + 1));
-  // (an ssx_ba_window keeps the raw observation arrays and the state in device buffers of its own: `ext`)
-  const int E_raw = h.E_raw;
-  const bool raw_in = dev_prep && !ext;
-  const bool have_cam = dev_prep && (ext ? ext->r_edge_cam != nullptr : pr->edge_cam != nullptr);
-  const size_t o_lm_compact = in.take(dev_prep ? sizeof(int) * (size_t)(L + 1) : 0);
-  const bool have_rank = dev_prep && !h.pose_rank.empty();
-  const size_t o_pose_rank = in.take(have_rank ? sizeof(int) * (size_t)P : 0);
-  const int raw_fmt = raw_in && !rz ? h.raw_fmt : 0;
-  const size_t o_r_pose = in.take(raw_in ? ((raw_fmt & 1) ? 1 : sizeof(int)) * (size_t)(E + 1) : 0);
-  const size_t o_r_point = in.take(raw_in ? ((raw_fmt & 2) ? sizeof(uint16_t) : sizeof(int)) * (size_t)(E + 1) : 0);
-  const size_t o_r_uv = in.take(raw_in ? ((raw_fmt & 4) ? sizeof(float) : sizeof(double)) * 2 * (size_t)(E + 1) : 0);
-  const size_t o_r_cam = in.take(have_cam && raw_in ? (size_t)E + 1 : 0);
-  const size_t o_slot8 = in.take(dev_prep ? (size_t)E_raw + 1 : 0);
-  // (host-built lists travel with the blob; device-built ones are scratch behind it, a fixed capacity per chunk)
-  size_t o_pair_a = dev_lists ? 0 : in.take(nPairs + 1);
-  size_t o_pair_b = dev_lists ? 0 : in.take(nPairs + 1);
-  size_t o_pair_ptr = dev_lists ? 0 : in.take(sizeof(int) * (h.pair_ptr.size() + 1));
-  size_t o_bseg = dev_lists ? 0 : in.take(sizeof(int) * (h.bseg.size() + 4));
-  size_t o_bseg_ptr = dev_lists ? 0 : in.take(sizeof(int) * (h.bseg_ptr.size() + 1));
-  const size_t touch_bytes = big ? 0 : sizeof(unsigned int) * TOUCH_WORDS * (size_t)(nCh + 1);
-  size_t o_touch = (dev_lists || big) ? 0 : in.take(touch_bytes);
-  const size_t o_pe_ptr = in.take(rz ? 0 : sizeof(int) * (h.pe_ptr.size() + 1));
-  const size_t o_pe_edge = in.take(rz ? 0 : sizeof(int) * (h.pe_edge.size() + 1));
-  const size_t o_sblk_pa = in.take(sizeof(int) * (nBlkS + 1));
-  const size_t o_sblk_pb = in.take(sizeof(int) * (nBlkS + 1));
-  const size_t o_spair_ptr = in.take(sizeof(int) * (h.spair_ptr.size() + 1));
-  const bool band = big && bp.w > 0;
-  const size_t o_seg_p0 = in.take(sizeof(int) * (bp.seg_p0.size() + 1));
-  const size_t o_seg_m = in.take(sizeof(int) * (bp.seg_m.size() + 1));
-  const bool bcr = band && bp.bcr.on;                                 // block cyclic reduction of the band (ba_bcr.inc)
-  const size_t o_bcr_p0 = in.take(bcr ? sizeof(int) * (bp.bcr.p0.size() + 1) : 0);
-  const size_t o_bcr_elim = in.take(bcr ? sizeof(int) * (bp.bcr.elim.size() + 4) : 0);
-  if (ext && !dev_prep) { ctx->set_error("ssx_ba: a window needs the device-side marshalling (<= %d free keyframes, no SSX_BA_HOST_PREP)", SSX_BA_SMALL_P); return SSX_ERR_UNSUPPORTED; }
-  const size_t o_pose0 = in.take(ext ? 0 : sizeof(double) * 7 * P);
-  const size_t o_point0 = in.take(ext ? 0 : sizeof(double) * 3 * (L + 1));
-  // (the state crosses PCIe ONCE: the second buffer and, for a resident batch, the pristine copy are made on the device,
-  // k_dup_state_b -- the blob of a C3 window carried three copies of its 96 KB of landmarks)
-  const size_t in_bytes = in.off;
-  Layout all = in;
-  const size_t o_pose1 = ext ? 0 : all.take(sizeof(double) * 7 * P);
-  const size_t o_point1 = ext ? 0 : all.take(sizeof(double) * 3 * (L + 1));
-  const bool keep_init = dup_state && !ext && place->keep_init;
-  const size_t o_pose_init = keep_init ? all.take(sizeof(double) * 7 * P) : 0;
-  const size_t o_point_init = keep_init ? all.take(sizeof(double) * 3 * (L + 1)) : 0;
-  size_t o_perm = 0, o_c2 = 0;
-  if (dev_prep) {
-    o_e_dup = all.take((size_t)E + 1);
-    o_e_uv = all.take(sizeof(double) * 2 * (size_t)(E + 1));
-    o_e_rec = all.take(sizeof(int) * 4 * (size_t)(E + 1));
-    o_l_rec = all.take(sizeof(int) * 4 * (size_t)(nLm + 1));
-    o_pptr = all.take(sizeof(uint16_t) * ((size_t)(nCh + 1) * (nP + 1) + 1));
-    o_perm = all.take(sizeof(int) * (size_t)(E + 1));
-    o_c2 = all.take(sizeof(double) * (size_t)(E_raw + 1));
-  }
-  if (dev_lists) {
-    o_pair_a = all.take((size_t)(nCh + 1) * MAX_PAIRS);
-    o_pair_b = all.take((size_t)(nCh + 1) * MAX_PAIRS);
-    o_pair_ptr = all.take(sizeof(int) * ((size_t)(nCh + 1) * (nBlk + 1) + 1));
-    o_bseg = all.take(sizeof(int) * 4 * ((size_t)(nCh + 1) * bseg_cap + 1));
-    o_bseg_ptr = all.take(sizeof(int) * (2 * (size_t)nCh + 2));
-    o_touch = all.take(touch_bytes);
-  }
-  const size_t o_W = all.take(sizeof(double) * 18 * (size_t)E);
-  const size_t o_err_lin = all.take(sizeof(double) * 2 * (size_t)E);
-  const size_t o_err_trial = all.take(sizeof(double) * 2 * (size_t)E);
-  const size_t o_Hll = all.take(sizeof(double) * 6 * (size_t)nLm);
-  const size_t o_bl = all.take(sizeof(double) * 3 * (size_t)nLm);
-  const size_t o_lin_slab = all.take(sizeof(double) * (size_t)(nCh + 1) * lin_stride);
-  const size_t o_Hpp = all.take(sizeof(double) * (nP + 1) * UPPER6);
-  const size_t o_bp = all.take(sizeof(double) * (nP + 1) * 6);
-  const size_t iter_count = (size_t)nP * 27 + 1 + world;
-  // (band solver: iter_comm sits right behind [band | rhs] so that ONE all-reduce per trial carries the reduced system AND the
-  // linearisation's pose blocks / chi2 -- see big_trial)
-  const bool band_pre = big && bp.w > 0;
-  size_t o_iter = band_pre ? 0 : all.take(sizeof(double) * (iter_count + 1));
-  const size_t o_schur = all.take(big ? 256 : sizeof(double) * (size_t)(nCh + 1) * (nBlk * 36 + nP * 6));
-  const size_t o_trial_comm = all.take(big ? 256 : sizeof(double) * ((size_t)n * n + n + 1));
-  const size_t o_BDa = all.take(big ? sizeof(double) * 18 * (size_t)(E + 1) : 256);
-  const size_t o_Wma = all.take(big ? sizeof(double) * 18 * (size_t)(E + 1) : 256);
-  const size_t o_Cv = all.take(big ? sizeof(double) * 6 * (size_t)(E + 1) : 256);
-  const size_t o_S = all.take((big && !band) ? sizeof(double) * (size_t)(n_pad + NB) * n_pad : 256);
-  // band solver: band + rhs, segment updates, factors of both levels, the separator system
-  const int bw = bp.w, bK = bp.K, bnPr = bK * bw, bwr = 2 * bw - 1;
-  const int NW0 = 6 * (2 * bw + 1) + 1, LS0 = 36 + NW0 * 6;
-  const int w1 = bK == 1 ? bw : bwr, NW1 = 6 * (w1 + 1 + bw) + 1, LS1 = 36 + NW1 * 6;
-  const int NU = 12 * bw + 1;
-  const size_t sb_count = band ? (size_t)nP * (bw + 1) * 36 + (size_t)n : 0;
-  const size_t sr_count = (band && bK > 1) ? (size_t)bnPr * (bwr + 1) * 36 + 6 * (size_t)bnPr : 0;
-  const size_t o_Sb = all.take(sizeof(double) * (sb_count + 1 + (band ? iter_count + 1 : 0)));
-  if (band) o_iter = o_Sb + sizeof(double) * sb_count;
-  const size_t o_U = all.take(band ? sizeof(double) * (size_t)bK * NU * NU : 256);
-  const size_t o_Ls0 = all.take((band && bK > 1) ? sizeof(double) * (size_t)nP * LS0 : 256);
-  const size_t o_Sr = all.take(sizeof(double) * (sr_count + 1));
-  const size_t o_Ls1 = all.take(band ? sizeof(double) * (size_t)(bK > 1 ? bnPr : nP) * LS1 : 256);
-  const size_t o_bcr_mem = all.take(bcr ? sizeof(double) * (bcr_mem_doubles(bp.bcr.N, bp.bcr.m) + 8) : 256);
-  const size_t o_xr = all.take(sizeof(double) * (6 * (size_t)bnPr + 8));
-  const size_t o_x = all.take(sizeof(double) * (n_pad + 8));
-  const size_t o_Ld = all.take(sizeof(double) * NB * NB);
-  const size_t o_invd = all.take(sizeof(double) * (n_pad + 8));
-  const size_t o_Ninv = all.take(sizeof(double) * 4 * 256);
-  const size_t o_scale_part = all.take(sizeof(double) * 64);
-  const size_t o_xp = all.take(sizeof(double) * (n + 1));
-  const size_t o_trial = all.take(sizeof(double) * 3 * (nCh + 1));
-  const size_t o_scal_comm = all.take(sizeof(double) * 4);
-  const size_t o_scal = all.take(sizeof(double) * SC_N);
-  const size_t o_lmstat = all.take(sizeof(double) * 3 * SSX_BA_MAX_STATS);
-  const size_t o_ticket = all.take(sizeof(unsigned int) * 4);
-
-  if (place && place->dry) {                     // sizing pass of a batch
-    place->in_bytes = in_bytes;
-    place->rest_bytes = all.off - in_bytes;
-    return SSX_OK;
-  }
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!place) {
-    SSX_HIP_TRY(ctx, ws->arena.reserve(all.off));
-    SSX_HIP_TRY(ctx, ws->stage.reserve(std::max(in_bytes, sizeof(double) * (7 * (size_t)P + 3 * (size_t)L + 2 * (size_t)E + (size_t)h.E_raw))));
-    SSX_HIP_TRY(ctx, ws->scal.reserve(sizeof(double) * (SC_N + 3 * SSX_BA_MAX_STATS)));
-  }
-  char* hs = place ? place->in_host : ws->stage.as<char>();
-  if (!rz) memcpy(hs + o_pose_free, h.pose_free.data(), sizeof(int) * P);
-  if (lm_tables && nLm && !rz) {
-    memcpy(hs + o_lm_fixed, h.lm_fixed.data(), nLm);
-    memcpy(hs + o_lm_id, h.lm_id.data(), sizeof(int) * nLm);
-  }
-  if (lm_tables && !rz) memcpy(hs + o_lm_ptr, h.lm_ptr.data(), sizeof(int) * (nLm + 1));
-  if (nCh && !rz) memcpy(hs + o_ch_desc, h.ch_desc.data(), sizeof(int) * 4 * (size_t)nCh);
-  if (dev_prep) {
-    if (L) memcpy(hs + o_lm_compact, h.lm_compact.data(), sizeof(int) * (size_t)L);
-    if (have_rank) memcpy(hs + o_pose_rank, h.pose_rank.data(), sizeof(int) * (size_t)P);
-    if (E && raw_in) {
-      if (raw_fmt & 1) { uint8_t* o = (uint8_t*)(hs + o_r_pose); for (int e = 0; e < E; ++e) o[e] = (uint8_t)pr->edge_pose[e]; }
-      else memcpy(hs + o_r_pose, pr->edge_pose, sizeof(int) * (size_t)E);
-      if (raw_fmt & 2) { uint16_t* o = (uint16_t*)(hs + o_r_point); for (int e = 0; e < E; ++e) o[e] = (uint16_t)pr->edge_point[e]; }
-      else memcpy(hs + o_r_point, pr->edge_point, sizeof(int) * (size_t)E);
-      if (raw_fmt & 4) { float* o = (float*)(hs + o_r_uv); for (size_t i = 0; i < 2 * (size_t)E; ++i) o[i] = (float)pr->edge_uv[i]; }
-      else memcpy(hs + o_r_uv, pr->edge_uv, sizeof(double) * 2 * (size_t)E);
-      if (have_cam) memcpy(hs + o_r_cam, pr->edge_cam, (size_t)E);
-    }
-    if (E_raw) memcpy(hs + o_slot8, h.slot8.data(), (size_t)E_raw);
-  } else if (!rz) {
-  if (E) memcpy(hs + o_e_rec, h.e_rec.data(), sizeof(int) * 4 * (size_t)E);
-  if (nLm) memcpy(hs + o_l_rec, h.l_rec.data(), sizeof(int) * 4 * (size_t)nLm);
-  }
-  if (big && !rz) memcpy(hs + o_ch_lm, h.ch_lm.data(), sizeof(int) * h.ch_lm.size());
-  if (E && !rz) {
-    if (big) {
-      memcpy(hs + o_e_pose, h.e_pose.data(), sizeof(int) * E);
-      memcpy(hs + o_e_lmc, h.e_lmc.data(), sizeof(int) * E);
-      memcpy(hs + o_e_cam, h.e_cam.data(), E);
-    }
-    if (!dev_prep) {
-      memcpy(hs + o_e_dup, h.e_dup.data(), E);
-      memcpy(hs + o_e_uv, h.e_uv.data(), sizeof(double) * 2 * E);
-    }
-  }
-  if (nBlk) {
-    memcpy(hs + o_blk_pa, h.blk_pa.data(), nBlk);
-    memcpy(hs + o_blk_pb, h.blk_pb.data(), nBlk);
-  }
-  if (!dev_prep && !h.pptr.empty()) memcpy(hs + o_pptr, h.pptr.data(), sizeof(uint16_t) * h.pptr.size());
-  if (nPairs) {
-    memcpy(hs + o_pair_a, h.pair_a.data(), nPairs);
-    memcpy(hs + o_pair_b, h.pair_b.data(), nPairs);
-  }
-  if (!dev_lists) {
-    if (!h.pair_ptr.empty()) memcpy(hs + o_pair_ptr, h.pair_ptr.data(), sizeof(int) * h.pair_ptr.size());
-    if (!h.bseg.empty()) memcpy(hs + o_bseg, h.bseg.data(), sizeof(int) * h.bseg.size());
-    if (!h.bseg_ptr.empty()) memcpy(hs + o_bseg_ptr, h.bseg_ptr.data(), sizeof(int) * h.bseg_ptr.size());
-    if (!big && !h.touch.empty()) memcpy(hs + o_touch, h.touch.data(), sizeof(unsigned int) * h.touch.size());
-  }
-  if (big && !rz) {
-    memcpy(hs + o_pe_ptr, h.pe_ptr.data(), sizeof(int) * h.pe_ptr.size());
-    memcpy(hs + o_pe_edge, h.pe_edge.data(), sizeof(int) * h.pe_edge.size());
-  }
-  if (big) {
-    memcpy(hs + o_sblk_pa, h.sblk_pa.data(), sizeof(int) * nBlkS);
-    memcpy(hs + o_sblk_pb, h.sblk_pb.data(), sizeof(int) * nBlkS);
-    memcpy(hs + o_spair_ptr, h.spair_ptr.data(), sizeof(int) * h.spair_ptr.size());
-  }
-  if (band) {
-    memcpy(hs + o_seg_p0, bp.seg_p0.data(), sizeof(int) * bp.seg_p0.size());
-    memcpy(hs + o_seg_m, bp.seg_m.data(), sizeof(int) * bp.seg_m.size());
-    if (bcr) {
-      memcpy(hs + o_bcr_p0, bp.bcr.p0.data(), sizeof(int) * bp.bcr.p0.size());
-      memcpy(hs + o_bcr_elim, bp.bcr.elim.data(), sizeof(int) * bp.bcr.elim.size());
-    }
-  }
-  if (!ext) {
-    memcpy(hs + o_pose0, pr->poses, sizeof(double) * 7 * P);
-    if (L) memcpy(hs + o_point0, pr->points, sizeof(double) * 3 * L);
-  }
-  // device addresses: the uploaded blob and the scratch behind it (one arena; a batch keeps all blobs together so that
-  // ONE copy uploads every window)
-  char* base_in = place ? place->in_dev : ws->arena.as<char>();
-  char* base_rest = place ? place->rest_dev : base_in + in_bytes;
-  auto at = [&](size_t o) -> char* { return o < in_bytes ? base_in + o : base_rest + (o - in_bytes); };
-  if (!place) {
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(base_in, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    // the second state buffer starts as a copy (landmarks without edges are never rewritten)
-    if (!ext) {
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(at(o_pose1), at(o_pose0), sizeof(double) * 7 * P, hipMemcpyDeviceToDevice, ctx->stream));
-    if (L)
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(at(o_point1), at(o_point0), sizeof(double) * 3 * L, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-  }
-
-  d.P = P; d.L = L; d.E = E; d.nP = nP; d.nLm = nLm; d.nCh = nCh; d.nBlk = nBlk; d.world = world; d.rank = rank;
-  d.big = big ? 1 : 0; d.lin_stride = lin_stride;
-  d.dense_slabs = dense_slabs_mode();
-  d.touch = (unsigned int*)(at(o_touch));
-  d.store_w = 1;                                 // the caller clears it for small windows with analytic Jacobians
-  d.pose_free = (const int*)(at(o_pose_free));
-  d.lm_fixed = (const uint8_t*)(at(o_lm_fixed));
-  d.lm_id = (const int*)(at(o_lm_id));
-  d.lm_ptr = (const int*)(at(o_lm_ptr));
-  d.ch_lm = (const int*)(at(o_ch_lm));
-  d.e_pose = (const int*)(at(o_e_pose));
-  d.e_lmc = (const int*)(at(o_e_lmc));
-  d.e_cam = (const uint8_t*)(at(o_e_cam));
-  d.e_dup = (const uint8_t*)(at(o_e_dup));
-  d.e_uv = (const double*)(at(o_e_uv));
-  d.ch_desc = (const int4*)(at(o_ch_desc)); d.e_rec = (const int4*)(at(o_e_rec)); d.l_rec = (const int4*)(at(o_l_rec));
-  d.blk_pa = (const int8_t*)(at(o_blk_pa));
-  d.blk_pb = (const int8_t*)(at(o_blk_pb));
-  d.pptr = (const uint16_t*)(at(o_pptr));
-  d.pair_a = (uint8_t*)(at(o_pair_a));
-  d.pair_b = (uint8_t*)(at(o_pair_b));
-  d.pair_ptr = (int*)(at(o_pair_ptr));
-  d.bseg = (int4*)(at(o_bseg)); d.bseg_ptr = (int*)(at(o_bseg_ptr));
-  d.bseg_cap = bseg_cap;
-  d.dev_prep = dev_prep ? 1 : 0;
-  d.E_raw = E_raw;
-  d.raw_fmt = raw_fmt;
-  d.no_err = 0;                                  // (the solve entry points set it when no per-edge errors were asked for)
-  if (ext) {
-    d.r_edge_pose = ext->r_edge_pose; d.r_edge_point = ext->r_edge_point; d.r_edge_uv = ext->r_edge_uv; d.r_edge_cam = ext->r_edge_cam;
-  } else {
-  d.r_edge_pose = (const int*)(dev_prep ? at(o_r_pose) : nullptr); d.r_edge_point = (const int*)(dev_prep ? at(o_r_point) : nullptr);
-  d.r_edge_uv = (const double*)(dev_prep ? at(o_r_uv) : nullptr); d.r_edge_cam = (const uint8_t*)(have_cam ? at(o_r_cam) : nullptr);
-  }
-  d.r_slot8 = (const uint8_t*)(dev_prep ? at(o_slot8) : nullptr); d.lm_compact = (const int*)(dev_prep ? at(o_lm_compact) : nullptr);
-  d.perm = (int*)(dev_prep ? at(o_perm) : nullptr); d.c2_out = (double*)(dev_prep ? at(o_c2) : nullptr);
-  d.pose_rank = (const int*)(have_rank ? at(o_pose_rank) : nullptr);
-  d.K = Cam{pr->K[0], pr->K[1], pr->K[2], pr->K[3]};
-  for (int i = 0; i < 14; ++i) d.ext[i] = pr->cam_ext[i];
-  d.huber_delta = huber_delta; d.chi2_th = chi2_th;
-  d.pose_init = keep_init ? (const double*)(at(o_pose_init)) : nullptr;
-  d.point_init = keep_init ? (const double*)(at(o_point_init)) : nullptr;
-  if (ext) {
-    d.pose[0] = ext->pose[0]; d.pose[1] = ext->pose[1]; d.point[0] = ext->point[0]; d.point[1] = ext->point[1];
-  } else {
-  d.pose[0] = (double*)(at(o_pose0)); d.pose[1] = (double*)(at(o_pose1));
-  d.point[0] = (double*)(at(o_point0)); d.point[1] = (double*)(at(o_point1));
-  }
-  d.W = (double*)(at(o_W));
-  d.err_lin = (double*)(at(o_err_lin));
-  d.err_trial = (double*)(at(o_err_trial));
-  d.Hll = (double*)(at(o_Hll)); d.bl = (double*)(at(o_bl));
-  d.lin_slab = (double*)(at(o_lin_slab));
-  d.Hpp = (double*)(at(o_Hpp)); d.bp = (double*)(at(o_bp));
-  d.iter_comm = (double*)(at(o_iter));
-  d.schur_slab = (double*)(at(o_schur));
-  d.trial_comm = (double*)(at(o_trial_comm));
-  d.xp = (double*)(at(o_xp));
-  d.trial_slab = (double*)(at(o_trial));
-  d.scal_comm = (double*)(at(o_scal_comm));
-  d.scal = (double*)(at(o_scal));
-  d.lm_stat = (double*)(at(o_lmstat));
-  d.ticket = (unsigned int*)(at(o_ticket));
-  if (rz) {                                      // the records, columns and raw arrays of big_records
-    d.dev_prep = 1; d.E_raw = recs->E_raw;
-    d.pose_free = recs->pose_free; d.lm_fixed = recs->lm_fixed; d.lm_id = recs->lm_id; d.lm_ptr = recs->lm_ptr; d.ch_lm = recs->ch_lm;
-    d.e_pose = recs->e_pose; d.e_lmc = recs->e_lmc; d.e_cam = recs->e_cam; d.e_dup = recs->e_dup; d.e_uv = recs->e_uv;
-    d.ch_desc = recs->ch_desc; d.e_rec = recs->e_rec; d.l_rec = recs->l_rec; d.perm = recs->perm; d.c2_out = recs->c2_out; d.lm_chunk = recs->lm_chunk;
-    d.r_edge_pose = recs->r_edge_pose; d.r_edge_point = recs->r_edge_point; d.r_edge_uv = recs->r_edge_uv; d.r_edge_cam = recs->r_edge_cam;
-    d.r_slot8 = recs->r_slot8; d.lm_compact = recs->lm_compact; d.pose_rank = nullptr;
-  }
-  bd = BigDev{};
-  bnd = BandDev{};
-  if (big) {
-    bd.n = n; bd.n_pad = n_pad; bd.ld = n_pad; bd.T = n_pad / NB; bd.nBlkS = (int)nBlkS;
-    bd.pe_ptr = rz ? pe_ptr_dev : (const int*)(at(o_pe_ptr)); bd.pe_edge = rz ? pe_edge_dev : (const int*)(at(o_pe_edge));
-    bd.sblk_pa = (const int*)(at(o_sblk_pa)); bd.sblk_pb = (const int*)(at(o_sblk_pb));
-    bd.spair_ptr = (const int*)(at(o_spair_ptr)); bd.spair_ab = nullptr;   // the pair lists live in the workspace of build_pairs
-    bd.BDa = (double*)(at(o_BDa)); bd.Wma = (double*)(at(o_Wma)); bd.Cv = (double*)(at(o_Cv));
-    bnd = BandDev{};
-    if (band) {
-      bnd.on = 1; bnd.w = bw; bnd.K = bK; bnd.nP = nP; bnd.nPr = bnPr; bnd.wr = bwr;
-      bnd.Sb = (double*)(at(o_Sb)); bnd.bsv = bnd.Sb + (size_t)nP * (bw + 1) * 36;
-      bnd.seg_p0 = (const int*)(at(o_seg_p0)); bnd.seg_m = (const int*)(at(o_seg_m));
-      bnd.U = (double*)(at(o_U)); bnd.Ls0 = (double*)(at(o_Ls0)); bnd.Sr = (double*)(at(o_Sr));
-      bnd.Ls1 = (double*)(at(o_Ls1)); bnd.xr = (double*)(at(o_xr)); bnd.LS0 = LS0; bnd.LS1 = LS1;
-      bnd.bcr = BcrDev{};
-      if (bcr) {
-        BcrDev& q = bnd.bcr;
-        q.on = 1; q.N = bp.bcr.N; q.m = bp.bcr.m;
-        q.p0 = (const int*)(at(o_bcr_p0)); q.elim = (const int4*)(at(o_bcr_elim));
-        const size_t mmN = (size_t)q.N * q.m * q.m, mN = (size_t)q.N * q.m;
-        double* base = (double*)(at(o_bcr_mem));
-        q.D = base; q.E = q.D + mmN; q.DL = q.E + 2 * mmN;   /* E: two buffers, bcr_e_buf */ q.DR = q.DL + mmN; q.Lf = q.DR + mmN; q.Ul = q.Lf + mmN; q.Ur = q.Ul + mmN;
-        q.R = q.Ur + mmN; q.RL = q.R + mN; q.RR = q.RL + mN; q.Y = q.RR + mN; q.X = q.Y + mN;
-      }
-    }
-    bd.S = (double*)(at(o_S)); bd.x = (double*)(at(o_x)); bd.Ld = (double*)(at(o_Ld)); bd.invd = (double*)(at(o_invd)); bd.Ninv = (double*)(at(o_Ninv)); bd.scale_part = (double*)(at(o_scale_part));
-  }
-  if (!place && nCh > 0 && (dev_lists || dev_prep)) {   // (a batch marshals all its windows with one launch pair: batch_build)
-    if (dev_prep) {
-      hipLaunchKernelGGL(k_prep_scatter, dim3((E_raw + CH - 1) / CH), dim3(CH), 0, ctx->stream, d);
-      hipLaunchKernelGGL(k_prep_chunk, dim3(nCh), dim3(CH), 0, ctx->stream, d);
-    } else {
-      hipLaunchKernelGGL(k_build_lists, dim3(nCh), dim3(CH), 0, ctx->stream, d);
-    }
-    SSX_HIP_TRY(ctx, hipGetLastError());
-  }
-  return SSX_OK;
-}
-
-// Large windows: the non-zero blocks of the reduced system and their pair lists, on the device (kernels in ba_big.inc).
-// Fills h.sblk_pa / h.sblk_pb / h.spair_ptr (sorted by (pa, pb); every diagonal block present, possibly with an empty
-// list) and h.band_w; the lists themselves stay in the workspace: *ab_dev.
-// Large windows, device-side marshalling (HostPrep::dev_prep): the caller's arrays and the host's counting tables go up once
-// (25 bytes per observation instead of ~62 of marshalled records and columns, and none of the ~3 ms of host work a
-// 480 000-observation window cost), k_prep_scatter / k_prep_chunk build the (landmark, pose) order, the packed records and the
-// structure-of-arrays columns, and a stable radix sort by free pose gives the pose-major edge list.  Everything lives in
-// ws->recs for the duration of the solve; `r` receives the pointers (the pair builder and upload() take them from there).
-// The observation columns as the caller holds them (pose index, landmark index, uv, camera) into pinned staging on the worker
-// pool and on their way to the device; nothing here depends on prepare()'s counting, which then runs beside the copy.
-ssx_status raw_upload_early(ssx_ctx* ctx, const ssx_ba_problem* pr)
-{
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
-  ws->raw_early.valid = false;
-  const int E = pr->E;
-  if (E <= 0 || !pr->edge_pose || !pr->edge_point || !pr->edge_uv) return SSX_OK;      // (prepare() reports it)
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const bool have_cam = pr->edge_cam != nullptr;
-  Layout in;
-  BaWorkspace::RawEarly re;
-  re.o_pose = in.take(sizeof(int) * (size_t)(E + 1)); re.o_point = in.take(sizeof(int) * (size_t)(E + 1));
-  re.o_uv = in.take(sizeof(double) * 2 * (size_t)(E + 1)); re.o_cam = in.take(have_cam ? (size_t)E + 1 : 0);
-  SSX_HIP_TRY(ctx, ws->raw_d.reserve(in.off));
-  SSX_HIP_TRY(ctx, ws->raw_h.reserve(in.off));
-  char* hs = ws->raw_h.as<char>();
-  struct Cp { size_t off; const void* src; size_t n; };
-  std::vector<Cp> cps;
-  auto add = [&](size_t off, const void* src, size_t n) {
-    for (size_t a = 0; a < n; a += (size_t)1 << 20) cps.push_back({off + a, (const char*)src + a, std::min(n - a, (size_t)1 << 20)});
-  };
-  add(re.o_pose, pr->edge_pose, sizeof(int) * (size_t)E); add(re.o_point, pr->edge_point, sizeof(int) * (size_t)E);
-  add(re.o_uv, pr->edge_uv, sizeof(double) * 2 * (size_t)E);
-  if (have_cam) add(re.o_cam, pr->edge_cam, (size_t)E);
-  ws->pool.run((int)cps.size(), std::min<int>(16, (int)cps.size()), [&](int q) { memcpy(hs + cps[q].off, cps[q].src, cps[q].n); });
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(ws->raw_d.p, hs, in.off, hipMemcpyHostToDevice, ctx->stream));
-  re.valid = true; re.key = pr->edge_pose; re.E = E;
-  ws->raw_early = re;
-  return SSX_OK;
-}
-
-ssx_status big_records(ssx_ctx* ctx, const ssx_ba_problem* pr, const HostPrep& h, BaDev& r, const int** pe_ptr_dev, const int** pe_edge_dev)
-{
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
-  hipStream_t s = ctx->stream;
-  const int P = h.P, L = h.L, E = h.E, nP = h.nP, nLm = h.nLm, nCh = h.nCh;
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int key_bits = 1;
-  while ((1u << key_bits) < (unsigned)(nP + 1)) ++key_bits;
-  size_t sort_tmp = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (unsigned int*)nullptr, (unsigned int*)nullptr, (unsigned int*)nullptr, (unsigned int*)nullptr, (size_t)std::max(E, 1), 0, key_bits, s);
-  const bool have_cam = pr->edge_cam != nullptr;
-  // (the observation columns may be on the device already: raw_upload_early)
-  const BaWorkspace::RawEarly early = ws->raw_early;
-  const bool sent = early.valid && early.key == pr->edge_pose && early.E == E && E == h.E_raw;
-  ws->raw_early.valid = false;
-  Layout in;
-  const size_t o_pose_free = in.take(sizeof(int) * P), o_lm_compact = in.take(sizeof(int) * (size_t)(L + 1));
-  const size_t o_lm_ptr = in.take(sizeof(int) * (size_t)(nLm + 1)), o_lm_id = in.take(sizeof(int) * (size_t)(nLm + 1)), o_lm_fixed = in.take((size_t)nLm + 1);
-  const size_t o_ch_lm = in.take(sizeof(int) * (size_t)(nCh + 1)), o_ch_desc = in.take(sizeof(int) * 4 * (size_t)(nCh + 1)), o_pe_ptr = in.take(sizeof(int) * (size_t)(nP + 1));
-  const size_t o_r_pose = in.take(sent ? 0 : sizeof(int) * (size_t)(E + 1)), o_r_point = in.take(sent ? 0 : sizeof(int) * (size_t)(E + 1));
-  const size_t o_r_uv = in.take(sent ? 0 : sizeof(double) * 2 * (size_t)(E + 1));
-  const size_t o_r_cam = in.take(have_cam && !sent ? (size_t)E + 1 : 0), o_slot8 = in.take((size_t)E + 1);
-  const size_t in_bytes = in.off;
-  Layout all = in;
-  const size_t o_perm = all.take(sizeof(int) * (size_t)(E + 1)), o_e_rec = all.take(sizeof(int) * 4 * (size_t)(E + 1)), o_l_rec = all.take(sizeof(int) * 4 * (size_t)(nLm + 1));
-  const size_t o_e_dup = all.take((size_t)E + 1), o_e_uv = all.take(sizeof(double) * 2 * (size_t)(E + 1));
-  const size_t o_e_pose = all.take(sizeof(int) * (size_t)(E + 1)), o_e_lmc = all.take(sizeof(int) * (size_t)(E + 1)), o_e_cam = all.take((size_t)E + 1);
-  const size_t o_lm_chunk = all.take(sizeof(int) * (size_t)(nLm + 1)), o_pe_edge = all.take(sizeof(int) * (size_t)(E + 1)), o_c2 = all.take(sizeof(double) * (size_t)(E + 1));
-  const size_t o_k0 = all.take(sizeof(int) * (size_t)(E + 1)), o_k1 = all.take(sizeof(int) * (size_t)(E + 1)), o_v0 = all.take(sizeof(int) * (size_t)(E + 1));
-  const size_t o_tmp = all.take(sort_tmp + 256);
-  SSX_HIP_TRY(ctx, ws->recs.reserve(all.off));
-  SSX_HIP_TRY(ctx, ws->recs_h.reserve(in_bytes));
-  char* hs = ws->recs_h.as<char>();
-  char* dv = ws->recs.as<char>();
-  memcpy(hs + o_pose_free, h.pose_free.data(), sizeof(int) * P);
-  if (L) memcpy(hs + o_lm_compact, h.lm_compact.data(), sizeof(int) * (size_t)L);
-  memcpy(hs + o_lm_ptr, h.lm_ptr.data(), sizeof(int) * (size_t)(nLm + 1));
-  if (nLm) { memcpy(hs + o_lm_id, h.lm_id.data(), sizeof(int) * (size_t)nLm); memcpy(hs + o_lm_fixed, h.lm_fixed.data(), (size_t)nLm); }
-  memcpy(hs + o_ch_lm, h.ch_lm.data(), sizeof(int) * h.ch_lm.size());
-  if (nCh) memcpy(hs + o_ch_desc, h.ch_desc.data(), sizeof(int) * 4 * (size_t)nCh);
-  memcpy(hs + o_pe_ptr, h.pe_ptr.data(), sizeof(int) * (size_t)(nP + 1));
-  // the big columns on the worker pool (12 MB at 480 000 observations)
-  struct Cp { size_t off; const void* src; size_t n; };
-  std::vector<Cp> cps;
-  auto add = [&](size_t off, const void* src, size_t n) {
-    for (size_t a = 0; a < n; a += (size_t)1 << 20) cps.push_back({off + a, (const char*)src + a, std::min(n - a, (size_t)1 << 20)});
-  };
-  if (E) {
-    if (!sent) {
-      add(o_r_pose, pr->edge_pose, sizeof(int) * (size_t)E); add(o_r_point, pr->edge_point, sizeof(int) * (size_t)E);
-      add(o_r_uv, pr->edge_uv, sizeof(double) * 2 * (size_t)E);
-      if (have_cam) add(o_r_cam, pr->edge_cam, (size_t)E);
-    }
-    add(o_slot8, h.slot8.data(), (size_t)E);
-  }
-  ws->pool.run((int)cps.size(), std::min<int>(16, (int)cps.size()), [&](int q) { memcpy(hs + cps[q].off, cps[q].src, cps[q].n); });
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(dv, hs, in_bytes, hipMemcpyHostToDevice, s));
-  r = BaDev{};
-  r.P = P; r.L = L; r.E = E; r.E_raw = h.E_raw; r.nP = nP; r.nLm = nLm; r.nCh = nCh; r.nBlk = 0; r.big = 1; r.dev_prep = 1; r.bseg_cap = 0;
-  r.pose_rank = nullptr;
-  r.pose_free = (const int*)(dv + o_pose_free); r.lm_compact = (const int*)(dv + o_lm_compact); r.lm_ptr = (const int*)(dv + o_lm_ptr);
-  r.lm_id = (const int*)(dv + o_lm_id); r.lm_fixed = (const uint8_t*)(dv + o_lm_fixed); r.ch_lm = (const int*)(dv + o_ch_lm);
-  r.ch_desc = (const int4*)(dv + o_ch_desc);
-  if (sent) {
-    char* rd = ws->raw_d.as<char>();
-    r.r_edge_pose = (const int*)(rd + early.o_pose); r.r_edge_point = (const int*)(rd + early.o_point); r.r_edge_uv = (const double*)(rd + early.o_uv);
-    r.r_edge_cam = (const uint8_t*)(have_cam ? rd + early.o_cam : nullptr);
-  } else {
-    r.r_edge_pose = (const int*)(dv + o_r_pose); r.r_edge_point = (const int*)(dv + o_r_point); r.r_edge_uv = (const double*)(dv + o_r_uv);
-    r.r_edge_cam = (const uint8_t*)(have_cam ? dv + o_r_cam : nullptr);
-  }
-  r.r_slot8 = (const uint8_t*)(dv + o_slot8);
-  r.perm = (int*)(dv + o_perm); r.e_rec = (const int4*)(dv + o_e_rec); r.l_rec = (const int4*)(dv + o_l_rec); r.e_dup = (const uint8_t*)(dv + o_e_dup);
-  r.e_uv = (const double*)(dv + o_e_uv); r.e_pose = (const int*)(dv + o_e_pose); r.e_lmc = (const int*)(dv + o_e_lmc); r.e_cam = (const uint8_t*)(dv + o_e_cam);
-  r.lm_chunk = (int*)(dv + o_lm_chunk); r.c2_out = (double*)(dv + o_c2);
-  r.pptr = (const uint16_t*)nullptr;
-  *pe_ptr_dev = (const int*)(dv + o_pe_ptr);
-  *pe_edge_dev = (const int*)(dv + o_pe_edge);
-  if (E > 0 && nCh > 0) {
-    hipLaunchKernelGGL(k_prep_scatter, dim3((h.E_raw + CH - 1) / CH), dim3(CH), 0, s, r);
-    hipLaunchKernelGGL(k_prep_chunk, dim3(nCh), dim3(CH), 0, s, r);
-    hipLaunchKernelGGL(k_pe_keys, dim3((E + CH - 1) / CH), dim3(CH), 0, s, r, (unsigned int*)(dv + o_k0), (unsigned int*)(dv + o_v0));
-    if (rocprim::radix_sort_pairs(dv + o_tmp, sort_tmp, (unsigned int*)(dv + o_k0), (unsigned int*)(dv + o_k1), (unsigned int*)(dv + o_v0),
-                                  (unsigned int*)(dv + o_pe_edge), (size_t)E, 0, key_bits, s) != hipSuccess) {
-      ctx->set_error("ssx_ba: rocprim::radix_sort_pairs failed (pose-major edge list)"); return SSX_ERR_HIP;
-    }
-    SSX_HIP_TRY(ctx, hipGetLastError());
-  }
-  return SSX_OK;
-}
-
-// recs (nullable): the records already on the device (big_records)
-ssx_status build_pairs(ssx_ctx* ctx, HostPrep& h, const unsigned long long** ab_dev, const BaDev* recs = nullptr)
-{
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
-  hipStream_t s = ctx->stream;
-  const int nLm = h.nLm, nP = h.nP, E = h.E, nCh = h.nCh;
-  *ab_dev = nullptr;
-  h.sblk_pa.clear(); h.sblk_pb.clear();
-  auto add_diagonals_only = [&] {
-    for (int p = 0; p < nP; ++p) { h.sblk_pa.push_back(p); h.sblk_pb.push_back(p); }
-    h.spair_ptr.assign((size_t)nP + 1, 0);
-    h.band_w = 0;
-  };
-  if (nLm == 0 || E == 0) { add_diagonals_only(); return SSX_OK; }
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // ---- stage A: records in, count + scan
-  size_t scan_tmp = 0;
-  (void)rocprim::exclusive_scan(nullptr, scan_tmp, (int*)nullptr, (int*)nullptr, 0, (size_t)nLm + 1, rocprim::plus<int>(), s);
-  Layout la;
-  const size_t a_erec = la.take(sizeof(int) * 4 * (size_t)E), a_lrec = la.take(sizeof(int) * 4 * (size_t)nLm), a_cd = la.take(sizeof(int) * 4 * (size_t)nCh);
-  const size_t a_lmc = la.take(sizeof(int) * (size_t)nLm);
-  const size_t a_in_bytes = la.off;
-  const size_t a_cnt = la.take(sizeof(int) * ((size_t)nLm + 1)), a_off = la.take(sizeof(int) * ((size_t)nLm + 1)), a_scal = la.take(64), a_tmp = la.take(scan_tmp + 256);
-  SSX_HIP_TRY(ctx, ws->pairs_a.reserve(la.off));
-  SSX_HIP_TRY(ctx, ws->pairs_h.reserve(std::max(a_in_bytes, sizeof(int) * 2 * ((size_t)nP * (nP + 1) / 2 + 8))));
-  char* da = ws->pairs_a.as<char>();
-  char* hh = ws->pairs_h.as<char>();
-  if (!recs) {
-    memcpy(hh + a_erec, h.e_rec.data(), sizeof(int) * 4 * (size_t)E);
-    memcpy(hh + a_lrec, h.l_rec.data(), sizeof(int) * 4 * (size_t)nLm);
-    memcpy(hh + a_cd, h.ch_desc.data(), sizeof(int) * 4 * (size_t)nCh);
-    memcpy(hh + a_lmc, h.lm_chunk.data(), sizeof(int) * (size_t)nLm);
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(da, hh, a_in_bytes, hipMemcpyHostToDevice, s));
-  }
-  SSX_HIP_TRY(ctx, hipMemsetAsync(da + a_cnt, 0, sizeof(int) * ((size_t)nLm + 1), s));
-  SSX_HIP_TRY(ctx, hipMemsetAsync(da + a_scal, 0, 64, s));
-  const int4* d_erec = recs ? (const int4*)recs->e_rec.p : (const int4*)(da + a_erec);
-  const int4* d_lrec = recs ? (const int4*)recs->l_rec.p : (const int4*)(da + a_lrec);
-  const int4* d_cd = recs ? (const int4*)recs->ch_desc.p : (const int4*)(da + a_cd);
-  const int* d_lmc = recs ? (const int*)recs->lm_chunk.p : (const int*)(da + a_lmc);
-  int* d_cnt = (int*)(da + a_cnt); int* d_off = (int*)(da + a_off); int* d_scal = (int*)(da + a_scal);
-  hipLaunchKernelGGL(k_pairs_count, dim3((nLm + CH - 1) / CH), dim3(CH), 0, s, d_erec, d_lrec, d_cd, d_lmc, nLm, nP, d_cnt, d_scal);
-  if (rocprim::exclusive_scan(da + a_tmp, scan_tmp, d_cnt, d_off, 0, (size_t)nLm + 1, rocprim::plus<int>(), s) != hipSuccess) {
-    ctx->set_error("ssx_ba: rocprim::exclusive_scan failed"); return SSX_ERR_HIP;
-  }
-  int h_np_w[2] = {0, 0};
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(&h_np_w[0], d_off + nLm, sizeof(int), hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(&h_np_w[1], d_scal, sizeof(int), hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  const size_t NP = (size_t)h_np_w[0];
-  if (NP == 0) { add_diagonals_only(); return SSX_OK; }
-  // ---- stage B: emit, sort by block key, run-length encode
-  int key_bits = 1;
-  while ((1ull << key_bits) < (unsigned long long)nP * nP) ++key_bits;
-  size_t sort_tmp = 0, rle_tmp = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, sort_tmp, (unsigned int*)nullptr, (unsigned int*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr, NP, 0,
-                                  key_bits, s);
-  (void)rocprim::run_length_encode(nullptr, rle_tmp, (unsigned int*)nullptr, (unsigned int)NP, (unsigned int*)nullptr, (unsigned int*)nullptr, (unsigned int*)nullptr, s);
-  const size_t max_blk = std::min((size_t)nP * (nP + 1) / 2, NP);
-  Layout lb;
-  const size_t b_k0 = lb.take(sizeof(unsigned int) * NP), b_k1 = lb.take(sizeof(unsigned int) * NP), b_v0 = lb.take(sizeof(unsigned long long) * NP);
-  const size_t b_uq = lb.take(sizeof(unsigned int) * (max_blk + 1)), b_ct = lb.take(sizeof(unsigned int) * (max_blk + 1)), b_nr = lb.take(64);
-  const size_t b_tmp = lb.take(std::max(sort_tmp, rle_tmp) + 256);
-  SSX_HIP_TRY(ctx, ws->pairs_b.reserve(lb.off));
-  SSX_HIP_TRY(ctx, ws->pairs_c.reserve(sizeof(unsigned long long) * NP + 64));
-  char* db = ws->pairs_b.as<char>();
-  unsigned int* d_k0 = (unsigned int*)(db + b_k0); unsigned int* d_k1 = (unsigned int*)(db + b_k1);
-  unsigned long long* d_v0 = (unsigned long long*)(db + b_v0);
-  unsigned long long* d_v1 = ws->pairs_c.as<unsigned long long>();   // the sorted values = the final lists
-  unsigned int* d_uq = (unsigned int*)(db + b_uq); unsigned int* d_ct = (unsigned int*)(db + b_ct); unsigned int* d_nr = (unsigned int*)(db + b_nr);
-  hipLaunchKernelGGL(k_pairs_emit, dim3((nLm + CH - 1) / CH), dim3(CH), 0, s, d_erec, d_lrec, d_cd, d_lmc, nLm, nP, (const int*)d_off, d_k0, d_v0);
-  if (rocprim::radix_sort_pairs(db + b_tmp, sort_tmp, d_k0, d_k1, d_v0, d_v1, NP, 0, key_bits, s) != hipSuccess ||
-      rocprim::run_length_encode(db + b_tmp, rle_tmp, d_k1, (unsigned int)NP, d_uq, d_ct, d_nr, s) != hipSuccess) {
-    ctx->set_error("ssx_ba: rocprim radix_sort_pairs / run_length_encode failed"); return SSX_ERR_HIP;
-  }
-  unsigned int n_runs = 0;
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(&n_runs, d_nr, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  unsigned int* h_uq = reinterpret_cast<unsigned int*>(hh);
-  unsigned int* h_ct = h_uq + n_runs;
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(h_uq, d_uq, sizeof(unsigned int) * n_runs, hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(h_ct, d_ct, sizeof(unsigned int) * n_runs, hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  // ---- the block list: the runs (sorted by key) merged with the diagonal blocks that have no pair (a pose whose
-  // landmarks are all fixed still owns its Hpp block)
-  h.spair_ptr.clear(); h.spair_ptr.push_back(0);
-  unsigned int r = 0;
-  int run_sum = 0;
-  for (int p = 0; p < nP; ++p) {
-    const unsigned int diag = (unsigned int)p * nP + p;
-    bool have_diag = false;
-    while (r < n_runs && h_uq[r] / (unsigned int)nP == (unsigned int)p) {      // the blocks of block-row p, ascending pb
-      if (h_uq[r] > diag && !have_diag) { h.sblk_pa.push_back(p); h.sblk_pb.push_back(p); h.spair_ptr.push_back(run_sum); have_diag = true; }
-      if (h_uq[r] == diag) have_diag = true;
-      h.sblk_pa.push_back(p); h.sblk_pb.push_back((int)(h_uq[r] % (unsigned int)nP));
-      run_sum += (int)h_ct[r];
-      h.spair_ptr.push_back(run_sum);
-      ++r;
-    }
-    if (!have_diag) { h.sblk_pa.push_back(p); h.sblk_pb.push_back(p); h.spair_ptr.push_back(run_sum); }
-  }
-  h.band_w = h_np_w[1];
-  *ab_dev = d_v1;
-  return SSX_OK;
-}
-
-size_t schur_lds_bytes()
-{
-  return BA_LDS_BYTES;
-}
-
-struct Comm {
-  ssx_allreduce_fn fn = nullptr;
-  void* user = nullptr;
-  int world = 1;
-};
+struct Comm { ssx_allreduce_fn fn = nullptr; void* user = nullptr; int world = 1; };
 
 ssx_status allreduce(ssx_ctx* ctx, const Comm& cm, double* buf, size_t count)
 {
@@ -3005,23 +2014,48 @@ ssx_status allreduce(ssx_ctx* ctx, const Comm& cm, double* buf, size_t count)
   return SSX_OK;
 }
 
-ssx_status launch_linearize(ssx_ctx* ctx, const BaDev& d, const BigDev& bd, const Comm& cm, int jac, int cur, int first_iteration)
+// the collective of a solve from its options; an RCCL communicator fills in opt.rank / opt.world_size
+// (world_size 1 with a hook is allowed -- the hook is then an identity: it exercises the collective plumbing)
+ssx_status make_comm(ssx_ctx* ctx, ssx_ba_options& opt, Comm& cm)
 {
-  if (d.nCh > 0) {
-    if (jac == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_NUMERIC_G2O>, dim3(d.nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, cur));
-    else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(d.nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, cur));
+  if (opt.comm) {                                   // RCCL inside the library (comm.hip): ncclAllReduce on the ctx stream
+    cm.fn = ssx_comm_allreduce_f64; cm.user = opt.comm;
+    (void)ssx_comm_info(opt.comm, &opt.rank, &opt.world_size);
+    cm.world = opt.world_size;
+  } else
+  if (opt.allreduce && opt.world_size >= 1) { cm.fn = opt.allreduce; cm.user = opt.allreduce_user; cm.world = opt.world_size; }
+  if (cm.fn && (opt.rank < 0 || opt.rank >= cm.world || cm.world > 64)) {
+    ctx->set_error("ssx_ba_solve: invalid rank %d / world_size %d", opt.rank, cm.world);
+    return SSX_ERR_INVALID_ARG;
   }
+  return SSX_OK;
+}
+
+// the linearisation of one window into its per-chunk slabs and their sum over the chunks (cur / pb_cur: the state buffer the
+// observations / the pose blocks of a large window are taken at; < 0: see k_linearize, k_pose_blocks)
+void launch_lin_kernels(ssx_ctx* ctx, const BaDev& d, const BigDev& bd, int jac, int cur, int pb_cur)
+{
+  if (d.nCh > 0) SSX_PROF(ctx, KID_BA_LINEARIZE, LAUNCH_JAC(jac, k_linearize, dim3(d.nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, cur));
   if (d.big) {
-    if (jac == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_NUMERIC_G2O>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, cur));
-    else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_ANALYTIC>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, cur));
+    SSX_PROF(ctx, KID_BA_LINEARIZE, LAUNCH_JAC(jac, k_pose_blocks, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
     SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin_big, dim3(1), dim3(CH), 0, ctx->stream, d));
   } else
   SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin, dim3(std::max(1, (d.nP * 27 + 63) / 64)), dim3(CH), 0, ctx->stream, d));
-  ssx_status st = allreduce(ctx, cm, d.iter_comm, (size_t)d.nP * 27 + 1 + d.world);
-  if (st != SSX_OK) return st;
-  // lambda_0 (first iteration of a round) and, after a collective, the global chi2
+}
+
+// the ranks' sum of a linearisation, then lambda_0 (first iteration of a round) and, after a collective, the global chi2
+ssx_status share_linearization(ssx_ctx* ctx, const BaDev& d, const Comm& cm, int first_iteration)
+{
+  SSX_TRY(allreduce(ctx, cm, d.iter_comm, (size_t)d.nP * 27 + 1 + d.world));
   if (first_iteration || cm.fn)
     SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(64), 0, ctx->stream, d, first_iteration));
+  return SSX_OK;
+}
+
+ssx_status launch_linearize(ssx_ctx* ctx, const BaDev& d, const BigDev& bd, const Comm& cm, int jac, int cur, int first_iteration)
+{
+  launch_lin_kernels(ctx, d, bd, jac, cur, cur);
+  SSX_TRY(share_linearization(ctx, d, cm, first_iteration));
   SSX_HIP_TRY(ctx, hipGetLastError());
   return SSX_OK;
 }
@@ -3033,7 +2067,6 @@ ssx_status build_tile_lists(ssx_ctx* ctx, BaWorkspace* ws, const std::vector<int
                             const Comm& cm, BigDev& bd, std::vector<int>& tl_row_cnt, std::vector<int>& tl_pair_cnt,
                             std::vector<uint8_t>& tl_next_diag)
 {
-  ssx_status st = SSX_OK;
   {
   // large windows: which 64x64 tiles of the factor can be non-zero.  The local co-visibility gives the tiles of this
   // rank's share of S; the union over the ranks (one small all-reduce of the T x T indicator) is the pattern of
@@ -3052,8 +2085,7 @@ ssx_status build_tile_lists(ssx_ctx* ctx, BaWorkspace* ws, const std::vector<int
     if (cm.fn) {
       SSX_HIP_TRY(ctx, ws->tiles.reserve(sizeof(double) * (size_t)T * T + 64));
       SSX_HIP_TRY(ctx, hipMemcpyAsync(ws->tiles.p, hp, sizeof(double) * (size_t)T * T, hipMemcpyHostToDevice, ctx->stream));
-      st = allreduce(ctx, cm, ws->tiles.as<double>(), (size_t)T * T);
-      if (st != SSX_OK) return st;
+      SSX_TRY(allreduce(ctx, cm, ws->tiles.as<double>(), (size_t)T * T));
       SSX_HIP_TRY(ctx, hipMemcpyAsync(hp, ws->tiles.p, sizeof(double) * (size_t)T * T, hipMemcpyDeviceToHost, ctx->stream));
       SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
@@ -3117,6 +2149,72 @@ ssx_status build_tile_lists(ssx_ctx* ctx, BaWorkspace* ws, const std::vector<int
   return SSX_OK;
 }
 
+// ---- the outer loop of Backend::OptimizeActiveMap (backend.cpp:175-203: optimize(iters), count the outliers, compare the inlier
+// ratio, go again), stated once for ssx_ba_solve and the batched solves ----------------------------------------------------------
+// What an entry point does with a window in which no optimize() can run (no chunk on any rank, or iters <= 0).  The two entry points
+// have always differed here and callers see it in ssx_ba_result: ssx_ba_solve still walks the rounds of such a window (rounds = 1 and
+// n_inliers = E when the inlier ratio lets it stop, else outer_rounds), a batch never starts them (rounds = 0, n_inliers = 0).
+enum IdleRounds { IDLE_ROUNDS_COUNTED, IDLE_ROUNDS_SKIPPED };
+
+struct OuterState {                                                        // host state of one window in that loop
+  int cur = 0, round = 0, rounds = 0, n_iters = 0, n_in = 0, n_outl = 0;   // cur: index of the accepted state buffer
+  bool done = false, trial_err = false; double n_out = 0;                  // trial_err: err_trial holds the errors of the last trial evaluated
+  void begin(int cur0, bool idle, int outer_rounds, IdleRounds ir) { cur = cur0; done = outer_rounds <= 0 || (idle && ir == IDLE_ROUNDS_SKIPPED); }
+  // After one optimize(iters): sc = the window's control scalars (nullptr: idle, nothing ran), n_edges = its edges on all ranks.
+  // Outlier statistics of the last evaluated trial (backend.cpp:181-194); done when the inlier ratio is reached or the rounds are used up.
+  void after_optimize(const double* sc, double n_edges, const ssx_ba_options& opt)
+  {
+    if (sc) {
+      cur = (int)sc[SC_CUR];
+      n_out = sc[SC_NOUT];
+      if (sc[SC_TRIALS_RUN] > 0.0) trial_err = true;
+      n_iters = std::max(n_iters, (int)sc[SC_NSTAT]);
+    }
+    rounds++;
+    const double cnt_in = n_edges - n_out;
+    n_outl = (int)n_out; n_in = (int)cnt_in;
+    const double ratio = n_edges > 0 ? cnt_in / (cnt_in + n_out) : 1.0;
+    done = ratio > opt.inlier_ratio || ++round >= opt.outer_rounds;
+  }
+  void report(ssx_ba_result& r) const { r.rounds = rounds; r.n_iters = n_iters; r.n_inliers = n_in; r.n_outliers = n_outl; }
+};
+
+// LM slots (one = (re)linearise if needed + one trial) to enqueue now for n windows, hscal = their control scalars; 0: all have finished.
+// The whole optimize(iters) first; a rejected trial consumes a slot without finishing its iteration, so then the host tops up: at least 1.
+int slots_to_enqueue(int iters, bool first_pass, const double* hscal, const OuterState* st, int n)
+{
+  if (first_pass) return iters;
+  int slots = 0;
+  for (int w = 0; w < n; ++w)
+    if (!st[w].done && hscal[(size_t)w * SC_N + SC_STOP] == 0.0) slots = std::max({slots, 1, iters - (int)hscal[(size_t)w * SC_N + SC_IT]});
+  return slots;
+}
+
+// LM history of the iterations [k0, k1) from a window's pinned statistics block (chi2 | lambda | trials, SSX_BA_MAX_STATS each)
+void copy_lm_history(ssx_ba_result& r, const double* hstat, int k0, int k1)
+{
+  for (int k = k0; k < k1 && k < SSX_BA_MAX_STATS; ++k) {
+    r.iter_chi2[k] = hstat[k];
+    r.iter_lambda[k] = hstat[SSX_BA_MAX_STATS + k];
+    r.iter_trials[k] = (int)hstat[2 * SSX_BA_MAX_STATS + k];
+  }
+}
+
+// Per-edge chi2 and outlier flags of one window from either storage form.  perm == nullptr: err = chi2 per entry of the caller's
+// arrays (E_raw of them, a device-marshalled window); dead_point[e] < 0 marks a dead entry of an ssx_ba_window's storage, never
+// evaluated.  Else err = the two error columns of the E sorted edges, and perm[s] is the caller's edge of sorted edge s.
+void unpack_edge_errors(ssx_ba_result& r, const double* err, int E, int E_raw, const int* perm, const int* dead_point, double chi2_th)
+{
+  if (!r.edge_chi2 && !r.edge_outlier) return;
+  for (int s = 0, n = perm ? E : E_raw; s < n; ++s) {
+    if (!perm && dead_point && dead_point[s] < 0) continue;
+    const int e = perm ? perm[s] : s;
+    const double c2 = perm ? err[s] * err[s] + err[(size_t)E + s] * err[(size_t)E + s] : err[s];
+    if (r.edge_chi2) r.edge_chi2[e] = c2;
+    if (r.edge_outlier) r.edge_outlier[e] = c2 > chi2_th;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -3143,19 +2241,16 @@ ssx_status ssx_ba_linearize(ssx_ctx* ctx, const ssx_ba_problem* prob, double hub
   if (!ctx || !prob) return SSX_ERR_INVALID_ARG;
   // the index lists are rebuilt per call (the window changes with every keyframe) but their storage is kept with the ctx:
   // ~20 vectors of up to E entries are not re-allocated and re-faulted every solve
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  HostPrep& h = ctx->ba->prep1;
+  HostPrep& h = ba_workspace(ctx)->prep1;
   ssx_status st = prepare(ctx, prob, h, false);        // this hook returns per-edge blocks in the caller's order: it keeps the host's sort
   if (st != SSX_OK) return st;
   BaDev d;
   BigDev bd;
   BandPlan no_band;
   BandDev bnd;
-  st = upload(ctx, prob, h, huber_delta, 5.891, 1, 0, d, bd, no_band, bnd);
-  if (st != SSX_OK) return st;
+  SSX_TRY(upload(ctx, prob, h, huber_delta, 5.891, 1, 0, d, bd, no_band, bnd));
   Comm cm;
-  st = launch_linearize(ctx, d, bd, cm, jac_mode, 0, 1);
-  if (st != SSX_OK) return st;
+  SSX_TRY(launch_linearize(ctx, d, bd, cm, jac_mode, 0, 1));
   const int P = h.P, L = h.L, E = h.E, nP = h.nP, nLm = h.nLm;
   std::vector<double> hHpp((size_t)nP * UPPER6 + 1), hbp((size_t)nP * 6 + 1), hHll((size_t)6 * nLm + 1), hbl((size_t)3 * nLm + 1),
       hW((size_t)18 * E + 1), herr((size_t)2 * E + 1), hscal(SC_N);
@@ -3210,6 +2305,260 @@ ssx_status ssx_ba_linearize(ssx_ctx* ctx, const ssx_ba_problem* prob, double hub
 
 }  // extern "C"
 
+namespace {   // ---- ssx_ba_solve in steps
+
+// what the steps of one solve share: the device views, the solver plan of a large window, the launch sizes that depend on it
+struct SolveDev {
+  BaDev d; BigDev bd; BandDev bnd; BandPlan bp; Comm cm;
+  int jac = SSX_JAC_ANALYTIC;
+  size_t lds_seg = 0, lds_top = 0, lds_back = 0;                                 // band solver (bnd.on): dynamic LDS of its kernels
+  std::vector<int> tl_row_cnt, tl_pair_cnt; std::vector<uint8_t> tl_next_diag;   // tile Cholesky (d.big && !bnd.on): build_tile_lists
+  // one rank: control block, statistics, estimate (pack_err: and per-edge chi2) leave in ONE kernel-written pinned block (fetch_control)
+  bool pack_ok = false, pack_err = false, packed = false;
+};
+
+// a LARGE window (more than 16 free keyframes) with many observations: its columns start crossing PCIe before they are counted
+ssx_status start_early_upload(ssx_ctx* ctx, const ssx_ba_problem* prob, const WinExt* ext)
+{
+  static const bool host_prep_env = getenv("SSX_BA_HOST_PREP") != nullptr || getenv("SSX_BA_HOST_LISTS") != nullptr;
+  if (ext || host_prep_env || prob->E < (1 << 16) || prob->P <= SSX_BA_SMALL_P || !prob->poses) return SSX_OK;
+  int n_free = 0;
+  for (int i = 0; i < prob->P; ++i) n_free += !(prob->pose_fixed && prob->pose_fixed[i]);
+  return n_free > SSX_BA_SMALL_P ? raw_upload_early(ctx, prob) : SSX_OK;
+}
+
+// Large windows: trajectory-shaped co-visibility (cyclic block band) -> the sliding-window / nested-dissection solver
+// of ba_band.inc; anything else -> the 64x64-tile sparse Cholesky of ba_big.inc.  With several ranks the decision
+// must be common: the ranks exchange which bandwidth class their shard falls in (one tiny all-reduce).
+ssx_status plan_large_solver(ssx_ctx* ctx, const HostPrep& h, const ssx_ba_options& opt, const Comm& cm, BandPlan& bp)
+{
+  if (!h.big) return SSX_OK;
+  if (opt.large_solver != SSX_LARGE_SOLVER_TILES) {
+    int w = std::max(h.band_w, 1);
+    if (w > BAND_WMAX) w = BAND_WMAX + 1;
+    if (cm.fn) {
+      BaWorkspace* w0 = ba_workspace(ctx);
+      double hist[BAND_WMAX + 2] = {0};
+      hist[w] = 1.0;
+      SSX_HIP_TRY(ctx, w0->tiles.reserve(sizeof(hist)));
+      SSX_HIP_TRY(ctx, hipMemcpyAsync(w0->tiles.p, hist, sizeof(hist), hipMemcpyHostToDevice, ctx->stream));
+      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      SSX_TRY(allreduce(ctx, cm, w0->tiles.as<double>(), BAND_WMAX + 2));
+      SSX_HIP_TRY(ctx, hipMemcpyAsync(hist, w0->tiles.p, sizeof(hist), hipMemcpyDeviceToHost, ctx->stream));
+      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      for (int i = 1; i <= BAND_WMAX + 1; ++i) if (hist[i] != 0.0) w = i;
+    }
+    if (w <= BAND_WMAX && h.nP >= 2 * w + 2) { plan_band(h.nP, w, bp); plan_bcr(h.nP, w, bp.bcr); }
+  }
+  if (opt.large_solver == SSX_LARGE_SOLVER_BAND && bp.w == 0) {
+    ctx->set_error("ssx_ba_solve: the band solver was requested but the co-visibility bandwidth is %d poses (> %d)", h.band_w, BAND_WMAX);
+    return SSX_ERR_UNSUPPORTED;
+  }
+  return SSX_OK;
+}
+
+// the end of every trial of a large window: the step applied to the poses, the sums of its scale
+void big_trial_update(ssx_ctx* ctx, const SolveDev& S)
+{
+  const int nparts = std::min(32, (S.d.P + CH - 1) / CH);
+  SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, ctx->stream, S.d, S.bd, -1, 0.0, 2));
+  SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_scale_finish, dim3(1), dim3(64), 0, ctx->stream, S.d, S.bd, nparts));
+}
+
+// One trial of a large window.  Damping, state buffer and stop flag come from the device's LM control block: the kernels shared with the
+// pose graph are told so by cur = -1, lambda_arg = 0, use_dev_lambda = 2.
+// BAND solver: Schur blocks straight into the band layout -> (all-reduce) -> block cyclic reduction, or segments || -> separator system
+// -> segments ||.  fuse_iter: the trial's all-reduce also carries iter_comm (pose blocks, chi2, max-diagonal slots of the linearisation),
+// which then needs no collective of its own: two all-reduces per LM trial instead of three
+ssx_status big_trial_band(ssx_ctx* ctx, const SolveDev& S, bool fuse_iter)
+{
+  const BaDev& d = S.d; const BigDev& bd = S.bd; const BandDev& bnd = S.bnd; const Comm& cm = S.cm;
+  const size_t lds_seg = S.lds_seg, lds_top = S.lds_top, lds_back = S.lds_back;
+  hipStream_t s = ctx->stream;
+  const size_t band_doubles = (size_t)bnd.nP * (bnd.w + 1) * 36;
+  SSX_HIP_TRY(ctx, hipMemsetAsync(bnd.Sb, 0, sizeof(double) * band_doubles, s));
+  if (d.nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(d.nCh), dim3(CH), SCHUR_PREP_LDS_BYTES, s, d, bd));
+  SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks_band, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd, bnd));
+  SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_bs_band, dim3(d.nP), dim3(CH), 0, s, d, bd, bnd));
+  SSX_TRY(allreduce(ctx, cm, bnd.Sb, band_doubles + (size_t)bd.n + (fuse_iter ? (size_t)d.nP * 27 + 1 + d.world : 0)));
+  if (fuse_iter) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(64), 0, s, d, 0));   // the global chi2 of the linearisation
+  if (bnd.bcr.on) {
+    // block cyclic reduction: log2(N) levels of concurrent super-block eliminations, then as many of back-substitution
+    const std::vector<int>& lv = S.bp.bcr.lvl;
+    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_build, dim3(bnd.bcr.N), dim3(256), 0, s, d, bnd, bnd.bcr, 0.0, 2));
+    const bool m24 = bnd.bcr.m == 24;
+    const std::vector<int>& lm = S.bp.bcr.lvM;
+    for (size_t q = 0; q < lm.size(); ++q) {
+      const int cnt = lv[q + 1] - lv[q], sh = (int)q;
+      if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<24>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], 1));
+      else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<36>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], 1));
+    }
+    for (size_t q = lm.size(); q-- > 0;) {
+      const int cnt = lv[q + 1] - lv[q], sh = (int)q;
+      if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<24>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], 1));
+      else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<36>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], 1));
+    }
+  } else {
+    if (bnd.K > 1) {
+      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_seg, dim3(bnd.K), dim3(BAND_T), lds_seg, s, d, bnd));
+      const int total = bnd.nPr * (bnd.wr + 1) * 36 + 6 * bnd.nPr;
+      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_assemble, dim3(std::min(64, (total + BAND_T - 1) / BAND_T)), dim3(BAND_T), 0, s, d, bnd));
+    }
+    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_top, dim3(1), dim3(BAND_TOP_T), lds_top, s, d, bnd, bd));
+    if (bnd.K > 1) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_back, dim3(bnd.K), dim3(BAND_T), lds_back, s, d, bnd, bd));
+  }
+  big_trial_update(ctx, S);
+  return SSX_OK;
+}
+
+// TILE solver: Schur blocks -> dense S -> (all-reduce of the non-zero tiles) -> blocked Cholesky (MFMA) -> back-substitution
+ssx_status big_trial_tiles(ssx_ctx* ctx, const SolveDev& S)
+{
+  const BaDev& d = S.d; const BigDev& bd = S.bd; const Comm& cm = S.cm;
+  const std::vector<int>& tl_row_cnt = S.tl_row_cnt; const std::vector<int>& tl_pair_cnt = S.tl_pair_cnt; const std::vector<uint8_t>& tl_next_diag = S.tl_next_diag;
+  hipStream_t s = ctx->stream;
+  SSX_HIP_TRY(ctx, hipMemsetAsync(bd.S, 0, sizeof(double) * (size_t)(bd.n_pad + 1) * bd.ld, s));
+  if (d.nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(d.nCh), dim3(CH), SCHUR_PREP_LDS_BYTES, s, d, bd));
+  SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd));
+  SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_bs, dim3(d.nP), dim3(CH), 0, s, d, bd));
+  if (cm.fn) {
+    // exchange the non-zero tiles and the rhs row only
+    hipLaunchKernelGGL(k_pack_tiles, dim3(bd.n_init + 1), dim3(CH), 0, s, bd, 0);
+    SSX_TRY(allreduce(ctx, cm, bd.Spack, (size_t)bd.n_init * NB_TILE + bd.n_pad));
+    hipLaunchKernelGGL(k_pack_tiles, dim3(bd.n_init + 1), dim3(CH), 0, s, bd, 1);
+  }
+  SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_add_lambda, dim3((bd.n + 255) / 256), dim3(256), 0, s, d, bd, 0.0, 2));
+  for (int kb = 0; kb < bd.T; ++kb) {
+    if (kb == 0 || !tl_next_diag[kb - 1])   // else the previous panel's k_syrk64 has factored this diagonal tile
+      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(CH), 0, s, d, bd, kb));
+    // the structurally non-zero row tiles below the panel (always the rhs row tile), then their pairs
+    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_trsm64, dim3(tl_row_cnt[kb]), dim3(CH), 0, s, bd, kb));
+    if (tl_pair_cnt[kb] > 0) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_syrk64, dim3(tl_pair_cnt[kb]), dim3(CH), 0, s, d, bd, kb));
+  }
+  SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(1024), 0, s, bd));
+  big_trial_update(ctx, S);
+  return SSX_OK;
+}
+
+// the end of every trial: back-substitution, the trial's residuals, its sums and the LM decision (lm_step on the device);
+// one GPU: the last chunk of k_backsub_residual sums the trial and takes the LM decision itself (finish)
+ssx_status finish_trial(ssx_ctx* ctx, const SolveDev& S)
+{
+  const BaDev& d = S.d; const Comm& cm = S.cm;
+  const bool finish = d.nCh > 0 && !cm.fn && g_trial_finish.load() != 0;
+  if (d.nCh > 0) SSX_PROF(ctx, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual, dim3(d.nCh), dim3(CH), 0, ctx->stream, d, finish ? 1 : 0));
+  if (!finish) SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial, dim3(1), dim3(CH), 0, ctx->stream, d, cm.fn ? 0 : 1));
+  if (cm.fn) {
+    SSX_TRY(allreduce(ctx, cm, d.scal_comm, 3));
+    SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_publish_trial, dim3(1), dim3(1), 0, ctx->stream, d));
+  }
+  return SSX_OK;
+}
+
+// One LM slot of a SMALL window.  The first slot of an optimize() needs lambda_0 between the linearisation and the Schur
+// complement; every later slot of a single-rank solve knows its damping: one fused kernel, and the two reductions as one launch.
+ssx_status enqueue_slot_small(ssx_ctx* ctx, const SolveDev& S, bool first_slot)
+{
+  const BaDev& d = S.d; const Comm& cm = S.cm;
+  const int n = 6 * d.nP, nCh = d.nCh, nSchurEntries = d.nBlk * 36 + d.nP * 6;
+  const bool fused = !first_slot && !cm.fn && nCh > 0 && n > 0;
+  static const bool no_both_env = getenv("SSX_BA_SPLIT_REDUCE") != nullptr;   // (tools: the two launches, for A/B timing)
+  const bool both = fused && !no_both_env;
+  if (fused) {
+    const int n_rl = std::max(1, (d.nP * 27 + 63) / 64);
+    SSX_PROF(ctx, KID_BA_LIN_SCHUR, LAUNCH_JAC(S.jac, k_lin_schur, dim3(nCh), dim3(CH), FUSED_LDS_BYTES, ctx->stream, d));
+    if (both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_both, dim3(n_rl + (nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d, n_rl));
+    else SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin, dim3(n_rl), dim3(CH), 0, ctx->stream, d));
+  } else
+    launch_lin_kernels(ctx, d, S.bd, S.jac, -1, -1);
+  SSX_TRY(share_linearization(ctx, d, cm, first_slot ? 1 : 0));
+  if (n > 0) {
+    if (nCh > 0 && !fused) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur, dim3(nCh), dim3(CH), SCHUR_LDS_BYTES, ctx->stream, d));
+    if (!both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur, dim3((nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d));
+    SSX_TRY(allreduce(ctx, cm, d.trial_comm, (size_t)n * n + n));
+  }
+  if (n <= NB) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64, dim3(1), dim3(CH), 0, ctx->stream, d));
+  else if (n <= 80) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80, dim3(1), dim3(CH), 0, ctx->stream, d));
+  else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve, dim3(1), dim3(CH), 0, ctx->stream, d));
+  return finish_trial(ctx, S);
+}
+
+// One LM slot of a LARGE window.  k_linearize skips itself while the kept linearisation is valid; the pose blocks too unless a
+// collective follows: their all-reduced copy must be rebuilt from this rank's part before it is summed again.
+ssx_status enqueue_slot_big(ssx_ctx* ctx, const SolveDev& S, bool first_slot)
+{
+  launch_lin_kernels(ctx, S.d, S.bd, S.jac, -1, S.cm.fn ? -1 : -2);
+  // (band solver, later slots: lambda is known, so the linearisation's sums travel with the trial's reduced system)
+  const bool fuse_iter = S.bnd.on && S.cm.fn && !first_slot;
+  ssx_status st = fuse_iter ? SSX_OK : share_linearization(ctx, S.d, S.cm, first_slot ? 1 : 0);
+  if (st == SSX_OK) st = S.bnd.on ? big_trial_band(ctx, S, fuse_iter) : big_trial_tiles(ctx, S);
+  return st != SSX_OK ? st : finish_trial(ctx, S);
+}
+
+// Behind the last slot of an optimize(): the control block to the host, on one rank with everything else a last round leaves
+// (SolveDev::pack_ok).  stage = the download block in pinned memory (poses | points | errors).
+ssx_status fetch_control(ssx_ctx* ctx, SolveDev& S, double* hscal, double* stage, bool have_trial_err)
+{
+  const BaDev& d = S.d;
+  if (!S.pack_ok) {
+    SSX_HIP_TRY(ctx, hipMemcpyAsync(hscal, d.scal, sizeof(double) * SC_N, hipMemcpyDeviceToHost, ctx->stream));
+    return SSX_OK;
+  }
+  double* const pk_point = stage + 7 * (size_t)d.P;
+  if (S.pack_err) {
+    hipLaunchKernelGGL(k_c2_out, dim3((d.E + CH - 1) / CH), dim3(CH), 0, ctx->stream, d, have_trial_err ? 1 : 2);
+    hipLaunchKernelGGL(k_stream_out, dim3((unsigned)std::min<size_t>(256, ((size_t)d.E_raw + 2 * CH - 1) / (2 * CH))), dim3(CH), 0, ctx->stream, (const double*)d.c2_out, pk_point + 3 * (size_t)d.L, (size_t)d.E_raw);
+  }
+  const size_t n_pack = SC_N + 3 * SSX_BA_MAX_STATS + 7 * (size_t)d.P + 3 * (size_t)d.L;
+  hipLaunchKernelGGL(k_pack_one, dim3((unsigned)std::min<size_t>(256, (n_pack + CH - 1) / CH)), dim3(CH), 0, ctx->stream, d, hscal, stage, pk_point);
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  S.packed = true;
+  return SSX_OK;
+}
+
+// enqueue what the caller asked for and the pinned block does not hold yet: the estimate, the per-edge errors
+ssx_status enqueue_download(ssx_ctx* ctx, const SolveDev& S, double* stage, const OuterState& os, bool want_err)
+{
+  const BaDev& d = S.d;
+  double* h_point = stage + 7 * (size_t)d.P;
+  double* h_err = h_point + 3 * (size_t)d.L;
+  if (!S.packed) {
+    SSX_HIP_TRY(ctx, hipMemcpyAsync(stage, d.pose[os.cur], sizeof(double) * 7 * d.P, hipMemcpyDeviceToHost, ctx->stream));
+    if (d.L) SSX_HIP_TRY(ctx, hipMemcpyAsync(h_point, d.point[os.cur], sizeof(double) * 3 * d.L, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (!want_err || (S.packed && S.pack_err)) return SSX_OK;
+  if (!os.trial_err) {   // iters == 0: errors of the input state
+    Comm none;
+    SSX_TRY(launch_linearize(ctx, d, S.bd, none, SSX_JAC_ANALYTIC, os.cur, 0));
+  }
+  if (d.dev_prep) {                                  // chi2 per edge, already in the caller's order
+    hipLaunchKernelGGL(k_c2_out, dim3((d.E + CH - 1) / CH), dim3(CH), 0, ctx->stream, d, os.trial_err ? 1 : 0);
+    SSX_HIP_TRY(ctx, hipMemcpyAsync(h_err, d.c2_out, sizeof(double) * (size_t)d.E_raw, hipMemcpyDeviceToHost, ctx->stream));
+  } else
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(h_err, os.trial_err ? d.err_trial : d.err_lin, sizeof(double) * 2 * (size_t)d.E, hipMemcpyDeviceToHost, ctx->stream));
+  return SSX_OK;
+}
+
+// collect_stats: the HIP-event records of this call, summed per phase
+void sum_phase_times(ssx_ctx* ctx, ssx_ba_result* res)
+{
+  for (const auto& r : ctx->prof.recs) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, r.a, r.b) != hipSuccess) continue;
+    switch (r.id) {
+      case KID_BA_LINEARIZE: res->ms_linearize += t; break;
+      case KID_BA_SCHUR: res->ms_schur += t; break;
+      case KID_BA_LIN_SCHUR: res->ms_schur += t; break;        // (the fused slot: linearisation + elimination in one kernel)
+      case KID_BA_SOLVE: res->ms_linear_solution += t; break;
+      case KID_BA_BACKSUB: res->ms_update += t; break;
+      case KID_BA_COMM: res->ms_comm += t; break;
+      default: res->ms_reduce += t; break;
+    }
+  }
+}
+
+}  // namespace
+
 // ssx_ba_solve, and the solve of one ssx_ba_window (`ext`: raw arrays and state resident in the window's buffers)
 static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const ssx_ba_options* opt_in, ssx_ba_result* res, WinExt* ext)
 {
@@ -3218,44 +2567,24 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
   if (opt_in) opt = *opt_in; else ssx_ba_default_options(&opt);
   // the index lists are rebuilt per call (the window changes with every keyframe) but their storage is kept with the ctx:
   // ~20 vectors of up to E entries are not re-allocated and re-faulted every solve
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  HostPrep& h = ctx->ba->prep1;
+  BaWorkspace* ws = ba_workspace(ctx);
+  HostPrep& h = ws->prep1;
   static const bool timing = getenv("SSX_BA_TIMING") != nullptr;       // host phases of the call on stderr (tools/ba_c4_slope.py)
   const auto tc0 = std::chrono::steady_clock::now();
   auto tc_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc0).count(); };
   double tph[6] = {0, 0, 0, 0, 0, 0};
-  {
-    // a LARGE window (more than 16 free keyframes) with many observations: its columns start crossing PCIe before they are counted
-    static const bool host_prep_env = getenv("SSX_BA_HOST_PREP") != nullptr || getenv("SSX_BA_HOST_LISTS") != nullptr;
-    if (!ext && !host_prep_env && prob->E >= (1 << 16) && prob->P > SSX_BA_SMALL_P && prob->poses) {
-      int n_free = 0;
-      for (int i = 0; i < prob->P; ++i) n_free += !(prob->pose_fixed && prob->pose_fixed[i]);
-      if (n_free > SSX_BA_SMALL_P) {
-        const ssx_status st0 = raw_upload_early(ctx, prob);
-        if (st0 != SSX_OK) return st0;
-      }
-    }
-  }
-  ssx_status st = prepare(ctx, prob, h, true, ext);
-  if (st != SSX_OK || !(h.big && h.dev_prep)) ctx->ba->raw_early.valid = false;   // (never reaches big_records: the early copy is dropped)
+  SSX_TRY(start_early_upload(ctx, prob, ext));
+  const ssx_status st = prepare(ctx, prob, h, true, ext);
+  if (st != SSX_OK || !(h.big && h.dev_prep)) ws->raw_early.valid = false;   // (never reaches big_records: the early copy is dropped)
   if (st != SSX_OK) return st;
   tph[0] = tc_ms();
   if (ext && (!h.dev_prep || h.big)) {
     ctx->set_error("ssx_ba_window: %d free keyframes (a window holds at most %d) or the device-side marshalling is switched off", h.nP, SSX_BA_SMALL_P);
     return SSX_ERR_UNSUPPORTED;
   }
-  Comm cm;
-  // world_size 1 with a hook is allowed (the hook is then an identity): it exercises the collective plumbing
-  if (opt.comm) {                                   // RCCL inside the library (comm.hip): ncclAllReduce on the ctx stream
-    cm.fn = ssx_comm_allreduce_f64; cm.user = opt.comm;
-    (void)ssx_comm_info(opt.comm, &opt.rank, &opt.world_size);
-    cm.world = opt.world_size;
-  } else
-  if (opt.allreduce && opt.world_size >= 1) { cm.fn = opt.allreduce; cm.user = opt.allreduce_user; cm.world = opt.world_size; }
-  if (cm.fn && (opt.rank < 0 || opt.rank >= cm.world || cm.world > 64)) {
-    ctx->set_error("ssx_ba_solve: invalid rank %d / world_size %d", opt.rank, cm.world);
-    return SSX_ERR_INVALID_ARG;
-  }
+  SolveDev S; BaDev& d = S.d;
+  SSX_TRY(make_comm(ctx, opt, S.cm));
+  const Comm& cm = S.cm;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   // collect_stats: every launch of this call is bracketed by HIP events (the SSX_PROF machinery of ssx_profile_begin),
@@ -3266,354 +2595,84 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
   } stats_guard{ctx, opt.collect_stats != 0 && !ctx->prof.on};
   if (stats_guard.mine) { ctx->prof.on = true; ctx->prof.used = 0; ctx->prof.recs.clear(); }
   res->ms_linearize = res->ms_schur = res->ms_linear_solution = res->ms_update = res->ms_reduce = res->ms_comm = 0.f;
-  BaDev d;
-  BigDev bd;
-  // large windows: trajectory-shaped co-visibility (cyclic block band) -> the sliding-window / nested-dissection solver
-  // of ba_band.inc; anything else -> the 64x64-tile sparse Cholesky of ba_big.inc.  With several ranks the decision
-  // must be common: the ranks exchange which bandwidth class their shard falls in (one tiny all-reduce).
   const unsigned long long* pairs_dev = nullptr;
   BaDev recs;
   const int* pe_ptr_dev = nullptr; const int* pe_edge_dev = nullptr;
   const bool big_dev = h.big && h.dev_prep;
-  if (big_dev) {
-    st = big_records(ctx, prob, h, recs, &pe_ptr_dev, &pe_edge_dev);
-    if (st != SSX_OK) return st;
-  }
-  if (h.big) {
-    st = build_pairs(ctx, h, &pairs_dev, big_dev ? &recs : nullptr);
-    if (st != SSX_OK) return st;
-  }
+  if (big_dev) SSX_TRY(big_records(ctx, prob, h, recs, &pe_ptr_dev, &pe_edge_dev));
+  if (h.big) SSX_TRY(build_pairs(ctx, h, &pairs_dev, big_dev ? &recs : nullptr));
   tph[1] = tc_ms();
-  BandPlan bp;
-  if (h.big && opt.large_solver != SSX_LARGE_SOLVER_TILES) {
-    int w = std::max(h.band_w, 1);
-    if (w > BAND_WMAX) w = BAND_WMAX + 1;
-    if (cm.fn) {
-      if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-      BaWorkspace* w0 = ctx->ba;
-      double hist[BAND_WMAX + 2] = {0};
-      hist[w] = 1.0;
-      SSX_HIP_TRY(ctx, w0->tiles.reserve(sizeof(hist)));
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(w0->tiles.p, hist, sizeof(hist), hipMemcpyHostToDevice, ctx->stream));
-      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      st = allreduce(ctx, cm, w0->tiles.as<double>(), BAND_WMAX + 2);
-      if (st != SSX_OK) return st;
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(hist, w0->tiles.p, sizeof(hist), hipMemcpyDeviceToHost, ctx->stream));
-      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      for (int i = 1; i <= BAND_WMAX + 1; ++i) if (hist[i] != 0.0) w = i;
-    }
-    if (w <= BAND_WMAX && h.nP >= 2 * w + 2) { plan_band(h.nP, w, bp); plan_bcr(h.nP, w, bp.bcr); }
-  }
-  if (h.big && opt.large_solver == SSX_LARGE_SOLVER_BAND && bp.w == 0) {
-    ctx->set_error("ssx_ba_solve: the band solver was requested but the co-visibility bandwidth is %d poses (> %d)", h.band_w, BAND_WMAX);
-    return SSX_ERR_UNSUPPORTED;
-  }
-  BandDev bnd;
-  st = upload(ctx, prob, h, opt.huber_delta, opt.chi2_th, cm.world, cm.fn ? opt.rank : 0, d, bd, bp, bnd, nullptr, ext, big_dev ? &recs : nullptr, pe_ptr_dev, pe_edge_dev);
-  if (st != SSX_OK) return st;
+  SSX_TRY(plan_large_solver(ctx, h, opt, cm, S.bp));
+  SSX_TRY(upload(ctx, prob, h, opt.huber_delta, opt.chi2_th, cm.world, cm.fn ? opt.rank : 0, d, S.bd, S.bp, S.bnd, nullptr, ext, big_dev ? &recs : nullptr, pe_ptr_dev, pe_edge_dev));
   tph[2] = tc_ms();
   d.store_w = (d.big || opt.jac_mode == SSX_JAC_NUMERIC_G2O) ? 1 : 0;
   d.no_err = (!d.big && !(res->edge_chi2 || res->edge_outlier)) ? 1 : 0;
-  bd.spair_ab = pairs_dev;
-  BaWorkspace* ws = ctx->ba;
+  S.bd.spair_ab = pairs_dev;
+  S.jac = opt.jac_mode;
   double* hscal = ws->scal.as<double>();
-  const int n = 6 * d.nP;
-  const int nCh = d.nCh;
-  const size_t lds_schur = schur_lds_bytes();
-  const size_t lds_fused = std::max(lds_schur, LIN_LDS_BYTES);
-  const size_t lds_prep = sizeof(double) * (18 + 9 + 3) * PW + 64;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lin_schur<SSX_JAC_ANALYTIC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fused);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lin_schur<SSX_JAC_NUMERIC_G2O>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fused);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_linearize<SSX_JAC_ANALYTIC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LIN_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_linearize<SSX_JAC_NUMERIC_G2O>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LIN_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_schur);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_prep), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep);
-    attr_set = true;
-  }
-  std::vector<int> tl_row_cnt, tl_pair_cnt;
-  std::vector<uint8_t> tl_next_diag;
-  if (d.big && !bnd.on) {
-    st = build_tile_lists(ctx, ws, h.sblk_pa, h.sblk_pb, cm, bd, tl_row_cnt, tl_pair_cnt, tl_next_diag);
-    if (st != SSX_OK) return st;
-  }
-  size_t lds_seg = 0, lds_top = 0, lds_back = 0;
-  if (bnd.on) {
+  double* const stage = reinterpret_cast<double*>(ws->stage.as<char>());   // the download block in pinned memory (poses | points | errors)
+  if (S.bnd.on) {
+    const BandDev& bnd = S.bnd;
     const int w1 = bnd.K == 1 ? bnd.w : bnd.wr, n1 = bnd.K == 1 ? bnd.nP : bnd.nPr;
-    int m_max = 0;
-    for (int m : bp.seg_m) m_max = std::max(m_max, m);
-    lds_seg = band_lds_elim(bnd.w, bnd.w);
-    lds_top = std::max(band_lds_elim(w1, bnd.w), band_lds_back(w1, bnd.w, n1));
-    lds_back = band_lds_back(bnd.w, bnd.w, m_max + 2 * bnd.w);
-    static size_t set_seg = 0, set_top = 0, set_back = 0;            // raise the dynamic-LDS limits once per size class
-    if (lds_seg > set_seg) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_band_seg), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_seg); set_seg = lds_seg; }
-    if (lds_top > set_top) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_band_top), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_top); set_top = lds_top; }
-    if (lds_back > set_back) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_band_back), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_back); set_back = lds_back; }
+    const int m_max = *std::max_element(S.bp.seg_m.begin(), S.bp.seg_m.end());
+    S.lds_seg = band_lds_elim(bnd.w, bnd.w);
+    S.lds_top = std::max(band_lds_elim(w1, bnd.w), band_lds_back(w1, bnd.w, n1));
+    S.lds_back = band_lds_back(bnd.w, bnd.w, m_max + 2 * bnd.w);
   }
-  // large windows: Schur blocks -> dense S (+ rhs row) -> all-reduce -> blocked Cholesky (MFMA) -> back-substitution
-  // fuse_iter: the trial's all-reduce also carries iter_comm (pose blocks, chi2, max-diagonal slots of the linearisation), which
-  // then needs no collective of its own: two all-reduces per LM trial instead of three
-  // (damping, state buffer and stop flag come from the device's LM control block: the kernels shared with the pose graph are told
-  // so by cur = -1, lambda_arg = 0, use_dev_lambda = 2)
-  auto big_trial = [&](bool fuse_iter) -> ssx_status {
-    hipStream_t s = ctx->stream;
-    if (bnd.on) {
-      // Schur blocks straight into the band layout -> (all-reduce) -> segments || -> separator system -> segments ||
-      const size_t band_doubles = (size_t)bnd.nP * (bnd.w + 1) * 36;
-      SSX_HIP_TRY(ctx, hipMemsetAsync(bnd.Sb, 0, sizeof(double) * band_doubles, s));
-      if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(nCh), dim3(CH), lds_prep, s, d, bd));
-      SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks_band, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd, bnd));
-      SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_bs_band, dim3(d.nP), dim3(CH), 0, s, d, bd, bnd));
-      ssx_status st2 = allreduce(ctx, cm, bnd.Sb, band_doubles + (size_t)bd.n + (fuse_iter ? (size_t)d.nP * 27 + 1 + d.world : 0));
-      if (st2 != SSX_OK) return st2;
-      if (fuse_iter) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(64), 0, s, d, 0));   // the global chi2 of the linearisation
-      if (bnd.bcr.on) {
-        // block cyclic reduction: log2(N) levels of concurrent super-block eliminations, then as many of back-substitution
-        const std::vector<int>& lv = bp.bcr.lvl;
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_build, dim3(bnd.bcr.N), dim3(256), 0, s, d, bnd, bnd.bcr, 0.0, 2));
-        const bool m24 = bnd.bcr.m == 24;
-        const std::vector<int>& lm = bp.bcr.lvM;
-        for (size_t q = 0; q < lm.size(); ++q) {
-          const int cnt = lv[q + 1] - lv[q], sh = (int)q;
-          if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<24>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], 1));
-          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_fwd<36>, dim3(cnt, BCR_S), dim3(BCR_T), 0, s, d, bnd.bcr, sh, lm[q], 1));
-        }
-        for (size_t q = lm.size(); q-- > 0;) {
-          const int cnt = lv[q + 1] - lv[q], sh = (int)q;
-          if (m24) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<24>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], 1));
-          else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_bcr_bwd<36>, dim3(cnt), dim3(256), 0, s, d, bnd.bcr, bd, sh, lm[q], 1));
-        }
-      } else {
-      if (bnd.K > 1) {
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_seg, dim3(bnd.K), dim3(BAND_T), lds_seg, s, d, bnd));
-        const int total = bnd.nPr * (bnd.wr + 1) * 36 + 6 * bnd.nPr;
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_assemble, dim3(std::min(64, (total + BAND_T - 1) / BAND_T)), dim3(BAND_T), 0, s, d, bnd));
-      }
-      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_top, dim3(1), dim3(BAND_TOP_T), lds_top, s, d, bnd, bd));
-      if (bnd.K > 1) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_band_back, dim3(bnd.K), dim3(BAND_T), lds_back, s, d, bnd, bd));
-      }
-      const int nparts = std::min(32, (d.P + CH - 1) / CH);
-      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, s, d, bd, -1, 0.0, 2));
-      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_scale_finish, dim3(1), dim3(64), 0, s, d, bd, nparts));
-      return SSX_OK;
-    }
-    SSX_HIP_TRY(ctx, hipMemsetAsync(bd.S, 0, sizeof(double) * (size_t)(bd.n_pad + 1) * bd.ld, s));
-    if (nCh > 0) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_prep, dim3(nCh), dim3(CH), lds_prep, s, d, bd));
-    SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_blocks, dim3((bd.nBlkS + 3) / 4), dim3(CH), 0, s, d, bd));
-    SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_bs, dim3(d.nP), dim3(CH), 0, s, d, bd));
-    if (cm.fn) {
-      // exchange the non-zero tiles and the rhs row only
-      hipLaunchKernelGGL(k_pack_tiles, dim3(bd.n_init + 1), dim3(CH), 0, s, bd, 0);
-      ssx_status st2 = allreduce(ctx, cm, bd.Spack, (size_t)bd.n_init * NB_TILE + bd.n_pad);
-      if (st2 != SSX_OK) return st2;
-      hipLaunchKernelGGL(k_pack_tiles, dim3(bd.n_init + 1), dim3(CH), 0, s, bd, 1);
-    }
-    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_add_lambda, dim3((bd.n + 255) / 256), dim3(256), 0, s, d, bd, 0.0, 2));
-    for (int kb = 0; kb < bd.T; ++kb) {
-      if (kb == 0 || !tl_next_diag[kb - 1])   // else the previous panel's k_syrk64 has factored this diagonal tile
-        SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_potrf64, dim3(1), dim3(CH), 0, s, d, bd, kb));
-      // the structurally non-zero row tiles below the panel (always the rhs row tile), then their pairs
-      SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_trsm64, dim3(tl_row_cnt[kb]), dim3(CH), 0, s, bd, kb));
-      if (tl_pair_cnt[kb] > 0) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_syrk64, dim3(tl_pair_cnt[kb]), dim3(CH), 0, s, d, bd, kb));
-    }
-    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_backsolve, dim3(1), dim3(1024), 0, s, bd));
-    const int nparts = std::min(32, (d.P + CH - 1) / CH);
-    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_pose_update_big, dim3(nparts), dim3(CH), 0, s, d, bd, -1, 0.0, 2));
-    SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_scale_finish, dim3(1), dim3(64), 0, s, d, bd, nparts));
-    return SSX_OK;
-  };
-  const int nSchurEntries = d.nBlk * 36 + d.nP * 6;
-
+  raise_lds_limits(S.lds_seg, S.lds_top, S.lds_back);
+  if (d.big && !S.bnd.on) SSX_TRY(build_tile_lists(ctx, ws, h.sblk_pa, h.sblk_pb, cm, S.bd, S.tl_row_cnt, S.tl_pair_cnt, S.tl_next_diag));
   res->rounds = 0; res->n_iters = 0; res->n_inliers = 0; res->n_outliers = 0;
-  int cur = ext ? ext->cur : 0; // index of the accepted state buffer
-  // the download block in pinned memory (poses | points | errors), written by k_pack_one behind the last slot of an optimize() on one rank
-  double* const pk_pose = reinterpret_cast<double*>(ws->stage.as<char>());
-  double* const pk_point = pk_pose + 7 * (size_t)d.P;
-  double* const pk_err = pk_point + 3 * (size_t)d.L;
+  const bool want_err = (res->edge_chi2 || res->edge_outlier) && d.E > 0;
   static const bool no_pack_env = getenv("SSX_BA_NO_PACK") != nullptr;       // (tools: the three copies of before, for A/B timing)
-  const bool pack_ok = !cm.fn && !no_pack_env;
-  const bool pack_err = pack_ok && (res->edge_chi2 || res->edge_outlier) && d.E > 0 && d.dev_prep;
-  bool packed = false;                                                       // the pinned block holds the state the stream will end with
-  bool have_trial_err = false; // err_trial holds the errors of the last trial evaluated
-  int round = 0;
+  S.pack_ok = !cm.fn && !no_pack_env;
+  S.pack_err = S.pack_ok && want_err && d.dev_prep;
   // with several ranks every rank must take part in every collective, even with an empty shard
-  const bool active = (nCh > 0) || cm.fn != nullptr;
-  double n_out_total = 0.0;
-  while (round < opt.outer_rounds) {
+  const bool active = (d.nCh > 0) || cm.fn != nullptr;
+  const bool idle = !active || opt.iters <= 0;
+  OuterState os;
+  os.begin(ext ? ext->cur : 0, idle, opt.outer_rounds, IDLE_ROUNDS_COUNTED);
+  while (!os.done) {
     // ---- one g2o optimize(iters): OptimizationAlgorithmLevenberg::solve per iteration.  The whole optimize(iters) is enqueued;
     // lm_step() on the device decides after every trial (no stream synchronisation per trial) ----
-    // One slot = (re)linearise if needed + one trial.  A rejected trial consumes a slot without finishing its
-    // iteration, so after the first `iters` slots the host looks at the control block once and tops up.
-    hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(1), 0, ctx->stream, d, cur, opt.iters, res->n_iters, active ? 0 : 1);
-    int slots_total = 0;
+    hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(1), 0, ctx->stream, d, os.cur, opt.iters, os.n_iters, active ? 0 : 1);
     bool first_slot = true;
-    while (active && opt.iters > 0) {
-      int slots = slots_total == 0 ? opt.iters : std::max(1, opt.iters - (int)hscal[SC_IT]);
-      for (int sidx = 0; sidx < slots; ++sidx) {
-        // the first slot of an optimize() needs lambda_0 between the linearisation and the Schur complement; every
-        // later slot (and every slot with a collective between the two) knows its damping: one fused kernel
-        const bool fused = !d.big && !first_slot && !cm.fn && nCh > 0 && n > 0;
-        if (d.big) {
-          // (k_linearize skips itself while the kept linearisation is valid; the pose blocks too unless a collective follows:
-          // their all-reduced copy must be rebuilt from this rank's part before it is summed again)
-          const int pb_cur = cm.fn ? -1 : -2;
-          if (nCh > 0) {
-            if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
-            else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
-          }
-          if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_NUMERIC_G2O>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
-          else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_pose_blocks<SSX_JAC_ANALYTIC>, dim3(d.nP), dim3(CH), 0, ctx->stream, d, bd, pb_cur));
-          SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin_big, dim3(1), dim3(CH), 0, ctx->stream, d));
-        } else
-        if (fused) {
-          if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), lds_fused, ctx->stream, d));
-          else SSX_PROF(ctx, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), lds_fused, ctx->stream, d));
-        } else if (nCh > 0) {
-          if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_NUMERIC_G2O>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
-          else SSX_PROF(ctx, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(nCh), dim3(CH), LIN_LDS_BYTES, ctx->stream, d, -1));
-        }
-        // later slots of a single-rank solve: the two reductions as one launch (the first slot needs lambda between them, ranks an all-reduce)
-        static const bool no_both_env = getenv("SSX_BA_SPLIT_REDUCE") != nullptr;   // (tools: the two launches, for A/B timing)
-        const bool both = !d.big && fused && !first_slot && !cm.fn && n > 0 && !no_both_env;
-        const int n_rl = std::max(1, (d.nP * 27 + 63) / 64);
-        if (both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_both, dim3(n_rl + (nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d, n_rl));
-        else if (!d.big) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin, dim3(n_rl), dim3(CH), 0, ctx->stream, d));
-        // (band solver, later slots: lambda is known, so the linearisation's sums travel with the trial's reduced system)
-        const bool fuse_iter = d.big && bnd.on && cm.fn && !first_slot;
-        if (!fuse_iter) {
-          st = allreduce(ctx, cm, d.iter_comm, (size_t)d.nP * 27 + 1 + d.world);
-          if (st != SSX_OK) return st;
-          if (first_slot || cm.fn) SSX_PROF(ctx, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(64), 0, ctx->stream, d, first_slot ? 1 : 0));
-        }
-        first_slot = false;
-        if (d.big) {
-          st = big_trial(fuse_iter);
-          if (st != SSX_OK) return st;
-        } else {
-        if (n > 0) {
-          if (nCh > 0 && !fused) SSX_PROF(ctx, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur, dim3(nCh), dim3(CH), lds_schur, ctx->stream, d));
-          if (!both) SSX_PROF(ctx, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur, dim3((nSchurEntries + 63) / 64), dim3(CH), 0, ctx->stream, d));
-          st = allreduce(ctx, cm, d.trial_comm, (size_t)n * n + n);
-          if (st != SSX_OK) return st;
-        }
-        if (n <= NB) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64, dim3(1), dim3(CH), 0, ctx->stream, d));
-        else if (n <= 80) SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80, dim3(1), dim3(CH), 0, ctx->stream, d));
-        else SSX_PROF(ctx, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve, dim3(1), dim3(CH), 0, ctx->stream, d));
-        }
-        // one GPU: the last chunk of k_backsub_residual sums the trial and takes the LM decision itself (finish)
-        const bool finish = nCh > 0 && !cm.fn && g_trial_finish.load() != 0;
-        if (nCh > 0) SSX_PROF(ctx, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual, dim3(nCh), dim3(CH), 0, ctx->stream, d, finish ? 1 : 0));
-        if (!finish) SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial, dim3(1), dim3(CH), 0, ctx->stream, d, cm.fn ? 0 : 1));
-        if (cm.fn) {
-          st = allreduce(ctx, cm, d.scal_comm, 3);
-          if (st != SSX_OK) return st;
-          SSX_PROF(ctx, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_publish_trial, dim3(1), dim3(1), 0, ctx->stream, d));
-        }
-      }
-      slots_total += slots;
+    for (int pass = 0; !idle; ++pass) {
+      const int slots = slots_to_enqueue(opt.iters, pass == 0, hscal, &os, 1);
+      if (slots == 0) break;
+      for (int sidx = 0; sidx < slots; ++sidx, first_slot = false) SSX_TRY(d.big ? enqueue_slot_big(ctx, S, first_slot) : enqueue_slot_small(ctx, S, first_slot));
       SSX_HIP_TRY(ctx, hipGetLastError());
-      if (pack_ok) {
-        // one rank: the control block, the statistics and the estimate (and the per-edge chi2 of a device-marshalled window) leave in
-        // ONE kernel-written block behind the last slot -- if this optimize() was the last one the download below finds everything there
-        if (pack_err) {
-          hipLaunchKernelGGL(k_c2_out, dim3((d.E + CH - 1) / CH), dim3(CH), 0, ctx->stream, d, have_trial_err ? 1 : 2);
-          hipLaunchKernelGGL(k_stream_out, dim3((unsigned)std::min<size_t>(256, ((size_t)d.E_raw + 2 * CH - 1) / (2 * CH))), dim3(CH), 0, ctx->stream, (const double*)d.c2_out, pk_err, (size_t)d.E_raw);
-        }
-        const size_t n_pack = SC_N + 3 * SSX_BA_MAX_STATS + 7 * (size_t)d.P + 3 * (size_t)d.L;
-        hipLaunchKernelGGL(k_pack_one, dim3((unsigned)std::min<size_t>(256, (n_pack + CH - 1) / CH)), dim3(CH), 0, ctx->stream, d, hscal, pk_pose, pk_point);
-        SSX_HIP_TRY(ctx, hipGetLastError());
-        packed = true;
-      } else {
-        SSX_HIP_TRY(ctx, hipMemcpyAsync(hscal, d.scal, sizeof(double) * SC_N, hipMemcpyDeviceToHost, ctx->stream));
-      }
+      SSX_TRY(fetch_control(ctx, S, hscal, stage, os.trial_err));
       SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // the one host round trip of an optimize(iters)
-      if (hscal[SC_STOP] != 0.0) break;
     }
-    if (active && opt.iters > 0) {
-      cur = (int)hscal[SC_CUR];
-      n_out_total = hscal[SC_NOUT];
-      if (hscal[SC_TRIALS_RUN] > 0.0) have_trial_err = true;
-      const int n_done = (int)hscal[SC_NSTAT];
-      if (n_done > res->n_iters) {
-        double* hstat = hscal + SC_N;                                // pinned, behind the scalar block
-        if (!packed) {                                               // (k_pack_one brought them along)
-          SSX_HIP_TRY(ctx, hipMemcpyAsync(hstat, d.lm_stat, sizeof(double) * 3 * SSX_BA_MAX_STATS, hipMemcpyDeviceToHost, ctx->stream));
-          SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        for (int k = res->n_iters; k < n_done && k < SSX_BA_MAX_STATS; ++k) {
-          res->iter_chi2[k] = hstat[k];
-          res->iter_lambda[k] = hstat[SSX_BA_MAX_STATS + k];
-          res->iter_trials[k] = (int)hstat[2 * SSX_BA_MAX_STATS + k];
-        }
-        res->n_iters = n_done;
+    if (!idle && (int)hscal[SC_NSTAT] > os.n_iters) {
+      double* hstat = hscal + SC_N;                                  // pinned, behind the scalar block
+      if (!S.packed) {                                               // (k_pack_one brought them along)
+        SSX_HIP_TRY(ctx, hipMemcpyAsync(hstat, d.lm_stat, sizeof(double) * 3 * SSX_BA_MAX_STATS, hipMemcpyDeviceToHost, ctx->stream));
+        SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       }
+      copy_lm_history(*res, hstat, os.n_iters, (int)hscal[SC_NSTAT]);
     }
-    res->rounds++;
-    // outlier statistics of this round from the errors of the last evaluated trial (backend.cpp:181-194);
-    // with several ranks n_out_total is already the global count: compare with the global edge count
-    double n_edges_total = (double)d.E;
+    double n_edges_total = (double)d.E;                              // with several ranks n_out is the global count: so must this be
     if (cm.fn) {
       double e_local = (double)d.E;
       SSX_HIP_TRY(ctx, hipMemcpyAsync(d.scal_comm, &e_local, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
       SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // e_local is a stack variable
-      st = allreduce(ctx, cm, d.scal_comm, 1);
-      if (st != SSX_OK) return st;
+      SSX_TRY(allreduce(ctx, cm, d.scal_comm, 1));
       SSX_HIP_TRY(ctx, hipMemcpyAsync(&n_edges_total, d.scal_comm, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    const double cnt_out = n_out_total, cnt_in = n_edges_total - cnt_out;
-    res->n_outliers = (int)cnt_out;
-    res->n_inliers = (int)cnt_in;
-    const double ratio = (n_edges_total > 0) ? cnt_in / (cnt_in + cnt_out) : 1.0;
-    if (ratio > opt.inlier_ratio) break;
-    ++round;
+    os.after_optimize(idle ? nullptr : hscal, n_edges_total, opt);
+    os.report(*res);
   }
-
-  // ---- download ----
-  char* hs = ws->stage.as<char>();
-  double* h_pose = reinterpret_cast<double*>(hs);
-  double* h_point = h_pose + 7 * (size_t)d.P;
-  double* h_err = h_point + 3 * (size_t)d.L;
-  if (!packed) {
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(h_pose, d.pose[cur], sizeof(double) * 7 * d.P, hipMemcpyDeviceToHost, ctx->stream));
-    if (d.L) SSX_HIP_TRY(ctx, hipMemcpyAsync(h_point, d.point[cur], sizeof(double) * 3 * d.L, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  const bool want_err = (res->edge_chi2 || res->edge_outlier) && d.E > 0;
-  if (want_err && !(packed && pack_err)) {
-    if (!have_trial_err) {   // iters == 0: errors of the input state
-      Comm none;
-      st = launch_linearize(ctx, d, bd, none, SSX_JAC_ANALYTIC, cur, 0);
-      if (st != SSX_OK) return st;
-    }
-    if (d.dev_prep) {                                  // chi2 per edge, already in the caller's order
-      hipLaunchKernelGGL(k_c2_out, dim3((d.E + CH - 1) / CH), dim3(CH), 0, ctx->stream, d, have_trial_err ? 1 : 0);
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(h_err, d.c2_out, sizeof(double) * (size_t)d.E_raw, hipMemcpyDeviceToHost, ctx->stream));
-    } else
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(h_err, have_trial_err ? d.err_trial : d.err_lin, sizeof(double) * 2 * (size_t)d.E,
-                                    hipMemcpyDeviceToHost, ctx->stream));
-  }
+  SSX_TRY(enqueue_download(ctx, S, stage, os, want_err));
   SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   tph[3] = tc_ms();
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   tph[4] = tc_ms();
-  if (res->poses_out) memcpy(res->poses_out, h_pose, sizeof(double) * 7 * d.P);
-  if (res->points_out && d.L) memcpy(res->points_out, h_point, sizeof(double) * 3 * d.L);
-  if (ext) ext->cur = cur;
-  if (want_err && d.dev_prep) {
-    for (int e = 0; e < d.E_raw; ++e) {
-      if (ext && prob->edge_point[e] < 0) continue;                  // a dead entry of the window's storage: never evaluated
-      if (res->edge_chi2) res->edge_chi2[e] = h_err[e];
-      if (res->edge_outlier) res->edge_outlier[e] = h_err[e] > opt.chi2_th;
-    }
-  } else if (want_err) {
-    for (int s = 0; s < d.E; ++s) {
-      const int e = h.perm[s];
-      const double c2 = h_err[s] * h_err[s] + h_err[(size_t)d.E + s] * h_err[(size_t)d.E + s];
-      if (res->edge_chi2) res->edge_chi2[e] = c2;
-      if (res->edge_outlier) res->edge_outlier[e] = c2 > opt.chi2_th;
-    }
-  }
+  if (res->poses_out) memcpy(res->poses_out, stage, sizeof(double) * 7 * d.P);
+  if (res->points_out && d.L) memcpy(res->points_out, stage + 7 * (size_t)d.P, sizeof(double) * 3 * d.L);
+  if (ext) ext->cur = os.cur;
+  if (want_err) unpack_edge_errors(*res, stage + 7 * (size_t)d.P + 3 * (size_t)d.L, d.E, d.E_raw, d.dev_prep ? nullptr : h.perm.data(), ext ? prob->edge_point : nullptr, opt.chi2_th);
   float ms = 0.f;
   (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
   res->ms_total = ms;
@@ -3622,434 +2681,13 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
     fprintf(stderr, "ssx_ba_solve P %d L %d E %d: (columns staged + sent early, large windows) + prepare %.3f | records + pairs %.3f | plan + upload %.3f | LM enqueued (and its host round trips) %.3f | "
                     "last sync %.3f | results %.3f ms (host clock); GPU first to last event %.3f ms\n", d.P, d.L, d.E, tph[0], tph[1] - tph[0],
             tph[2] - tph[1], tph[3] - tph[2], tph[4] - tph[3], tc_ms() - tph[4], ms);
-  if (stats_guard.mine)
-    for (const auto& r : ctx->prof.recs) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, r.a, r.b) != hipSuccess) continue;
-      switch (r.id) {
-        case KID_BA_LINEARIZE: res->ms_linearize += t; break;
-        case KID_BA_SCHUR: res->ms_schur += t; break;
-        case KID_BA_LIN_SCHUR: res->ms_schur += t; break;        // (the fused slot: linearisation + elimination in one kernel)
-        case KID_BA_SOLVE: res->ms_linear_solution += t; break;
-        case KID_BA_BACKSUB: res->ms_update += t; break;
-        case KID_BA_COMM: res->ms_comm += t; break;
-        default: res->ms_reduce += t; break;
-      }
-    }
+  if (stats_guard.mine) sum_phase_times(ctx, res);
   return SSX_OK;
 }
 
-extern "C" ssx_status ssx_ba_solve(ssx_ctx* ctx, const ssx_ba_problem* prob, const ssx_ba_options* opt_in, ssx_ba_result* res)
-{
-  return ba_solve_impl(ctx, prob, opt_in, res, nullptr);
-}
+extern "C" ssx_status ssx_ba_solve(ssx_ctx* ctx, const ssx_ba_problem* prob, const ssx_ba_options* opt_in, ssx_ba_result* res) { return ba_solve_impl(ctx, prob, opt_in, res, nullptr); }
 
-// ---- batches of small windows ----------------------------------------------------------------------------------------------
-// Many small windows together (one window per stereo pair of a batch, per stream of BASELINE configs[4], ...): every
-// kernel of the small-window path runs ONCE for all windows (blockIdx.y = window), the device-driven LM loop of each
-// window advances independently, one upload and one download carry all windows.  Same arithmetic as n calls of
-// ssx_ba_solve -- identical bits per window.
-
-struct ssx_ba_batch {
-  ssx_ctx* ctx = nullptr;
-  int device = 0;                                    // the ctx's device (ssx_ba_batch_destroy must not read it through ctx)
-  int n = 0;
-  ssx_ba_options opt;
-  DevBuf arena_own; HostBuf stage_own, scal_own;     // a resident batch owns its memory; the one-call path borrows the ctx workspace
-  DevBuf* arena = nullptr; HostBuf* stage = nullptr; HostBuf* scal = nullptr;
-  std::vector<BaDev> devs;
-  std::vector<std::vector<int>> perm;                // sorted edge -> caller's edge, per window
-  std::vector<int> P, L, E, E_raw;
-  std::vector<WinExt*> exts;                         // windows of ssx_ba_window objects (one-shot batches only), else empty
-  const ssx_ba_problem* probs = nullptr;             // (valid during a one-shot call: the dead entries of a window's storage)
-  std::vector<size_t> out_off;
-  size_t out_total = 0, a_out = 0, a_gather = 0, a_head = 0, in_total = 0, o_dv = 0, o_ctrl = 0, o_ooff = 0;
-  int max_ch = 1, max_rl = 1, max_rs = 1, total_ch = 0, min_ch = 0;
-  bool any_solve64 = false, any_solve80 = false, any_solve = false, with_err = false, fresh = false;
-  int threads = 1;
-  int groups = 0;                                    // ssx_ba_batch_set_groups; 0: batch_groups(n)
-};
-
-namespace {
-
-// Groups of windows a batch is run in, each on its own stream (batch_run).  Two: measured 2.61 / 2.45 / 2.39 / 3.01 ms for
-// 64 windows in 1 / 2 / 3 / 4 groups in a process with nothing else on the GPU, but 2.61 / 2.45 / 3.24 ms next to a
-// front-end on its own two streams (more streams than hardware queues: the groups then wait for each other).
-int batch_groups(int n)
-{
-  static const int groups_env = getenv("SSX_BA_GROUPS") ? atoi(getenv("SSX_BA_GROUPS")) : 2;
-  return n >= 8 ? std::min(std::max(groups_env, 1), 4) : 1;
-}
-
-// marshal + upload n small windows; SSX_ERR_UNSUPPORTED when one of them is a large window (> 16 free keyframes)
-ssx_status batch_build(ssx_ctx* ctx, int n, const ssx_ba_problem* probs, const ssx_ba_options& opt, bool with_err, bool own, ssx_ba_batch* B,
-                       WinExt* const* exts = nullptr)
-{
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
-  // (the marshalling scratch of the windows is kept with the ctx between calls; after a batch larger than PREPS_KEEP
-  // windows it is trimmed back, see the end of this function)
-  if ((int)ws->preps.size() < n) ws->preps.resize(n);
-  std::vector<HostPrep>& preps = ws->preps;
-  const int hw = (int)std::thread::hardware_concurrency();
-  const int T = std::max(1, std::min({n, host_threads_cap(), hw > 1 ? hw / 2 : 1}));
-  B->ctx = ctx; B->device = ctx->device; B->n = n; B->opt = opt; B->threads = T; B->with_err = with_err;
-  if (!own) B->groups = ctx->ba_batch_groups;                       // (a resident batch has its own setting: ssx_ba_batch_set_groups)
-  static const int timing_mode = getenv("SSX_BATCH_TIMING") ? std::max(atoi(getenv("SSX_BATCH_TIMING")), 1) : 0;   // phase times on stderr
-  const bool timing = timing_mode == 1;                              // 1: with synchronisations (tools/batch_time.py), 2: host clocks only
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); };
-  const auto t_begin = now();
-  // ---- 1. host marshalling of every window (edge sort, chunks, index lists), T threads
-  std::vector<ssx_status> sts(n, SSX_OK);
-  ws->pool.run(n, T, [&](int w) { sts[w] = prepare(ctx, &probs[w], preps[w], true, exts ? exts[w] : nullptr); });
-  for (int w = 0; w < n; ++w) if (sts[w] != SSX_OK) return sts[w];
-  for (int w = 0; w < n; ++w) if (preps[w].big || (exts && !preps[w].dev_prep)) return SSX_ERR_UNSUPPORTED;
-  const double t_prepare = ms_since(t_begin);
-  B->probs = probs;
-  if (exts) B->exts.assign(exts, exts + n); else B->exts.clear();
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  B->arena = own ? &B->arena_own : &ws->arena;
-  B->stage = own ? &B->stage_own : &ws->stage;
-  B->scal = own ? &B->scal_own : &ws->scal;
-  // ---- 2. sizes, one arena: [blobs of all windows | BaDev[n] | ctrl int[3n] | out offsets | scratch of all windows | packed outputs | gather]
-  std::vector<UploadPlace> place(n);
-  B->devs.assign(n, BaDev{});
-  BandPlan no_band;
-  size_t in_total = 0, rest_total = 0, out_total = 0;
-  std::vector<size_t> in_off(n), rest_off(n);
-  B->out_off.assign(n, 0); B->P.resize(n); B->L.resize(n); B->E.resize(n); B->E_raw.resize(n); B->perm.resize(n);
-  for (int w = 0; w < n; ++w) {
-    BigDev bd; BandDev bnd;
-    place[w].dry = true;
-    place[w].keep_init = own;
-    ssx_status st = upload(ctx, &probs[w], preps[w], opt.huber_delta, opt.chi2_th, 1, 0, B->devs[w], bd, no_band, bnd, &place[w], exts ? exts[w] : nullptr);
-    if (st != SSX_OK) return st;
-    in_off[w] = in_total; in_total += place[w].in_bytes;
-    rest_off[w] = rest_total; rest_total += place[w].rest_bytes;
-    B->out_off[w] = out_total;
-    B->P[w] = preps[w].P; B->L[w] = preps[w].L; B->E[w] = preps[w].E; B->E_raw[w] = preps[w].E_raw;
-    out_total += 7 * (size_t)preps[w].P + 3 * (size_t)preps[w].L + (with_err ? std::max(2 * (size_t)preps[w].E, (size_t)preps[w].E_raw) : 0);
-  }
-  Layout tail;
-  B->o_dv = tail.take(sizeof(BaDev) * n); B->o_ctrl = tail.take(sizeof(int) * 3 * n); B->o_ooff = tail.take(sizeof(size_t) * n);
-  const size_t head_bytes = in_total + tail.off;                     // everything that is uploaded
-  Layout arena;
-  B->a_head = arena.take(head_bytes);
-  const size_t a_rest = arena.take(rest_total);
-  B->a_out = arena.take(sizeof(double) * (out_total + 1));
-  B->a_gather = arena.take(sizeof(double) * (size_t)n * (3 * SSX_BA_MAX_STATS));
-  B->in_total = in_total; B->out_total = out_total;
-  // (resident windows: their storage grows with every keyframe until it is rewritten at twice the live size, and a grown arena
-  // is a hipFree -- a device-wide synchronisation, 5-20 ms in the middle of a step -- so a reallocation asks for 2.5x the need)
-  const double grow = exts ? 2.5 : 1.25;
-  SSX_HIP_TRY(ctx, B->arena->reserve(arena.off, grow));
-  SSX_HIP_TRY(ctx, B->stage->reserve(std::max(head_bytes, sizeof(double) * (out_total + 1)), grow));
-  SSX_HIP_TRY(ctx, B->scal->reserve(sizeof(double) * (size_t)n * (SC_N + 3 * SSX_BA_MAX_STATS) + sizeof(int) * 3 * n + 64));
-  char* dev_base = B->arena->as<char>();
-  char* hst = B->stage->as<char>();
-  // ---- 3. fill the pinned mirror (T threads) and upload it, in Q pieces: the copy engine moves one piece while the threads fill
-  // the next (128 C3 windows: 0.7 ms of filling, 1.65 ms on PCIe for 86 MB)
-  static const int pieces_env = getenv("SSX_BA_UPLOAD_PIECES") ? std::min(std::max(atoi(getenv("SSX_BA_UPLOAD_PIECES")), 1), 16) : 4;
-  const int Q = n >= 32 && !exts ? pieces_env : 1;                   // (resident windows send a few KB each: one piece)
-  for (int q = 0; q < Q; ++q) {
-  const int q0 = (int)((long long)n * q / Q), q1 = (int)((long long)n * (q + 1) / Q);
-  ws->pool.run(q1 - q0, T, [&](int wi) {
-    const int w = q0 + wi;
-    BigDev bd; BandDev bnd;
-    place[w].dry = false;
-    place[w].in_dev = dev_base + B->a_head + in_off[w];
-    place[w].rest_dev = dev_base + a_rest + rest_off[w];
-    place[w].in_host = hst + in_off[w];
-    sts[w] = upload(ctx, &probs[w], preps[w], opt.huber_delta, opt.chi2_th, 1, 0, B->devs[w], bd, no_band, bnd, &place[w], exts ? exts[w] : nullptr);
-    B->devs[w].store_w = opt.jac_mode == SSX_JAC_NUMERIC_G2O ? 1 : 0;
-    B->devs[w].no_err = with_err ? 0 : 1;
-    if (with_err) B->perm[w] = preps[w].perm;
-  });
-  for (int w = q0; w < q1; ++w) if (sts[w] != SSX_OK) { (void)hipStreamSynchronize(ctx->stream); return sts[w]; }
-  if (q + 1 < Q) {
-    const size_t b0 = in_off[q0], b1 = in_off[q1];
-    if (b1 > b0) SSX_HIP_TRY(ctx, hipMemcpyAsync(dev_base + B->a_head + b0, hst + b0, b1 - b0, hipMemcpyHostToDevice, ctx->stream));
-  }
-  }
-  const size_t up0 = Q > 1 ? in_off[(int)((long long)n * (Q - 1) / Q)] : 0;   // the last piece goes with the tail
-  memcpy(hst + in_total + B->o_dv, B->devs.data(), sizeof(BaDev) * n);
-  memset(hst + in_total + B->o_ctrl, 0, sizeof(int) * 3 * n);
-  memcpy(hst + in_total + B->o_ooff, B->out_off.data(), sizeof(size_t) * n);
-  for (int w = 0; w < n; ++w) {
-    const BaDev& d = B->devs[w];
-    B->max_ch = std::max(B->max_ch, d.nCh);
-    B->min_ch = w == 0 ? d.nCh : std::min(B->min_ch, d.nCh);
-    B->total_ch += d.nCh;
-    B->max_rl = std::max(B->max_rl, (d.nP * 27 + 63) / 64);
-    B->max_rs = std::max(B->max_rs, (d.nBlk * 36 + d.nP * 6 + 63) / 64);
-    if (6 * d.nP <= NB) B->any_solve64 = true; else if (6 * d.nP <= 80) B->any_solve80 = true; else B->any_solve = true;
-  }
-  const double t_fill = ms_since(t_begin);
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(dev_base + B->a_head + up0, hst + up0, head_bytes - up0, hipMemcpyHostToDevice, ctx->stream));
-  double t_up = 0.0;
-  if (timing) { (void)hipStreamSynchronize(ctx->stream); t_up = ms_since(t_begin); }
-  {
-    // pair lists + work items of every window, on the device (windows marshalled with SSX_BA_HOST_LISTS brought theirs along)
-    const BaDev* dvb = reinterpret_cast<const BaDev*>(dev_base + B->a_head + in_total + B->o_dv);
-    if (!exts) hipLaunchKernelGGL(k_dup_state_b, dim3(16, n), dim3(CH), 0, ctx->stream, dvb);   // (windows keep both buffers themselves)
-    int max_e = 1;
-    bool any_prep = false;
-    for (int w = 0; w < n; ++w) { max_e = std::max(max_e, B->devs[w].E_raw); any_prep = any_prep || B->devs[w].dev_prep; }
-    if (any_prep) hipLaunchKernelGGL(k_prep_scatter_b, dim3((max_e + CH - 1) / CH, n), dim3(CH), 0, ctx->stream, dvb);
-    hipLaunchKernelGGL(k_prep_chunk_b, dim3(B->max_ch, n), dim3(CH), 0, ctx->stream, dvb);
-    SSX_HIP_TRY(ctx, hipGetLastError());
-  }
-  if (timing_mode == 2)
-    fprintf(stderr, "[batch_build n=%d, no syncs] prepare %.3f | sizes + fill %.3f | enqueue of upload + marshalling kernels %.3f ms\n", n, t_prepare,
-            t_fill - t_prepare, ms_since(t_begin) - t_fill);
-  if (timing) {
-    (void)hipStreamSynchronize(ctx->stream);
-    fprintf(stderr, "[batch_build n=%d] prepare %.3f | sizes + fill (+ upload of 3 pieces of 4) %.3f | %.1f MB on the device %.3f later | device marshalling %.3f ms\n", n, t_prepare,
-            t_fill - t_prepare, head_bytes / 1e6, t_up - t_fill, ms_since(t_begin) - t_up);
-  }
-  B->fresh = true;                                                   // the state buffers hold the uploaded state
-  const size_t lds_schur = schur_lds_bytes();
-  static bool attr_set_b = false;
-  if (!attr_set_b) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_schur_b), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_schur);
-    const int lf = (int)std::max(lds_schur, LIN_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lin_schur_b<SSX_JAC_ANALYTIC>), hipFuncAttributeMaxDynamicSharedMemorySize, lf);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_lin_schur_b<SSX_JAC_NUMERIC_G2O>), hipFuncAttributeMaxDynamicSharedMemorySize, lf);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_linearize_b<SSX_JAC_ANALYTIC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LIN_LDS_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_linearize_b<SSX_JAC_NUMERIC_G2O>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LIN_LDS_BYTES);
-    attr_set_b = true;
-  }
-  // the marshalling scratch stays allocated between calls up to 64 MB (device-marshalled windows keep ~6 bytes per observation:
-  // 64 C3 windows = 8 MB; host-marshalled ones ~100 bytes: the cache is trimmed back to 16 windows after such a batch)
-  size_t prep_bytes = 0;
-  for (const HostPrep& hp : ws->preps)
-    prep_bytes += hp.slot8.capacity() + sizeof(int) * (hp.cnt_tmp.capacity() + hp.start_tmp.capacity() + hp.lm_compact.capacity() + hp.e_rec.capacity() +
-                                                       hp.perm.capacity() + hp.e_pose.capacity() + hp.e_lmc.capacity() + hp.bseg.capacity()) +
-                  sizeof(double) * hp.e_uv.capacity() + hp.pair_a.capacity() + hp.pair_b.capacity();
-  constexpr size_t PREPS_KEEP = 16;
-  if (ws->preps.size() > PREPS_KEEP && prep_bytes > (size_t(64) << 20)) { ws->preps.resize(PREPS_KEEP); ws->preps.shrink_to_fit(); }
-  return SSX_OK;
-}
-
-// optimise every window of a built batch; results may be null (nothing is downloaded then, counters only in `summary`)
-ssx_status batch_run(ssx_ba_batch* B, ssx_ba_result* results, int32_t* lm_iterations_total)
-{
-  ssx_ctx* ctx = B->ctx;
-  const int n = B->n;
-  const ssx_ba_options& opt = B->opt;
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  char* dev_base = B->arena->as<char>();
-  const BaDev* dv = reinterpret_cast<const BaDev*>(dev_base + B->a_head + B->in_total + B->o_dv);
-  const size_t* d_ooff = reinterpret_cast<const size_t*>(dev_base + B->a_head + B->in_total + B->o_ooff);
-  hipStream_t s = ctx->stream;
-  const int wg_x = B->max_ch;                                        // workgroups per window of the linearise / Schur kernels
-  if (!B->fresh) hipLaunchKernelGGL(k_reset_state_b, dim3(16, n), dim3(CH), 0, s, dv);
-  B->fresh = false;
-  // per-window host state of Backend::OptimizeActiveMap's outer loop (backend.cpp:175-203)
-  struct WinState { int cur = 0, round = 0, rounds = 0, n_iters = 0, n_in = 0, n_outl = 0; bool done = false, trial_err = false; double n_out = 0; };
-  std::vector<WinState> wsn(n);
-  // nobody asked for landmarks or per-edge errors: only the poses cross PCIe (560 B instead of 97 KB per C3 window), and they are
-  // requested speculatively at the end of every outer round (below)
-  bool spec_poses = results != nullptr && !B->with_err;
-  int spec_maxP = 0;
-  if (results) for (int w = 0; w < n; ++w) { spec_poses = spec_poses && !results[w].points_out; spec_maxP = std::max(spec_maxP, B->P[w]); }
-  spec_poses = spec_poses && (size_t)n * 7 * spec_maxP <= B->out_total;
-  bool spec_done = false;                                            // a speculative poses download was really enqueued (no LM round may run at all)
-  double* hscal = B->scal->as<double>();                             // n x SC_N, then n x 3 x MAX_STATS, then the ctrl words
-  int* h_ctrl = reinterpret_cast<int*>(hscal + (size_t)n * (SC_N + 3 * SSX_BA_MAX_STATS));
-  for (int w = 0; w < n; ++w) wsn[w].done = !(B->devs[w].nCh > 0) || opt.outer_rounds <= 0;
-  if (!B->exts.empty()) for (int w = 0; w < n; ++w) wsn[w].cur = B->exts[w]->cur;   // windows: the buffer that holds their estimate
-  const size_t lds_schur = schur_lds_bytes();
-  const size_t lds_fused = std::max(lds_schur, LIN_LDS_BYTES);
-  int G = std::min(B->groups > 0 ? std::min(B->groups, 4) : batch_groups(n), std::max(n, 1));   // never an empty group (gridDim.y == 0)
-  for (int g = 0; g + 1 < G; ++g) {
-    if (!ctx->grp[g] && ctx->make_stream(&ctx->grp[g], false) != hipSuccess) { (void)hipGetLastError(); G = g + 1; break; }
-    if (!ctx->grp_ev[g] && hipEventCreateWithFlags(&ctx->grp_ev[g], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); G = g + 1; break; }
-  }
-  const bool split = G > 1;
-  const bool turns_on = g_turns.enabled() && ctx->ba != nullptr;
-  if (turns_on && !ctx->ba->ev_turn && hipEventCreateWithFlags(&ctx->ba->ev_turn, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); ctx->ba->ev_turn = nullptr; }
-  auto all_done = [&] { for (int w = 0; w < n; ++w) if (!wsn[w].done) return false; return true; };
-  while (!all_done() && opt.iters > 0) {
-    for (int w = 0; w < n; ++w) { h_ctrl[w] = wsn[w].cur; h_ctrl[n + w] = wsn[w].n_iters; h_ctrl[2 * n + w] = wsn[w].done ? 1 : 0; }
-    // (no copies: the control words are READ by the kernel from the pinned block, the state words and results are WRITTEN by the
-    // gather / pack kernels into pinned host memory -- a hipMemcpyAsync of this runtime runs as a blit KERNEL on the compute units
-    // whenever the SDMA engines are taken, tools/microbench/copy_engine.hip, and costs the host ~10 us each)
-    hipLaunchKernelGGL(k_lm_begin_batch, dim3(n), dim3(64), 0, s, dv, (const int*)h_ctrl, n, opt.iters);
-    int slots_total = 0;
-    bool first_slot = true;
-    for (;;) {
-      // ssx_ba_device_turns: this round's kernels run after the round enqueued before it, whichever context enqueued that
-      struct TurnScope {
-        bool on; BaWorkspace* w; int dev; hipStream_t st;
-        TurnScope(bool o, BaWorkspace* w_, int d, hipStream_t s_) : on(o), w(w_), dev(d), st(s_) { if (on) g_turns.begin(w, dev, st); }
-        void close() { if (on) { g_turns.end(w, dev, w->ev_turn, st); on = false; } }
-        ~TurnScope() { close(); }
-      } turn(turns_on, ctx->ba, ctx->device, s);
-      int slots = opt.iters;
-      if (slots_total > 0) {
-        slots = 1;
-        for (int w = 0; w < n; ++w)
-          if (!wsn[w].done && hscal[(size_t)w * SC_N + SC_STOP] == 0.0) slots = std::max(slots, opt.iters - (int)hscal[(size_t)w * SC_N + SC_IT]);
-      }
-      // The batch in G groups of windows on G streams: the narrow kernels of one half (one workgroup per window: the reduced
-      // solve, the reductions -- a third of an iteration's time on a quarter of the chip) run beside the wide kernels
-      // of the other.  The windows are independent; the halves meet again before the state words are gathered.
-      if (split) {
-        SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
-        for (int g = 0; g + 1 < G; ++g) SSX_HIP_TRY(ctx, hipStreamWaitEvent(ctx->grp[g], ctx->ev_fork, 0));
-      }
-      for (int sidx = 0; sidx < slots; ++sidx) {
-        const bool fused = !first_slot;                                // see ssx_ba_solve: lambda is known after the first slot
-        for (int g = 0; g < G; ++g) {
-          hipStream_t hs = g ? ctx->grp[g - 1] : s;
-          const int w0 = (int)((long long)n * g / G), hn = (int)((long long)n * (g + 1) / G) - w0;
-          const BaDev* hv = dv + w0;
-          const dim3 gCh(B->max_ch, hn), gWg(wg_x, hn), gRl(B->max_rl, hn), gRs(B->max_rs, hn), gOne(1, hn);
-          const bool fin_b = B->min_ch > 0 && g_trial_finish.load() != 0;   // the last chunk of k_backsub_residual finishes the trial
-          if (fused) {
-            if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF_ON(ctx, hs, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur_b<SSX_JAC_NUMERIC_G2O>, gWg, dim3(CH), lds_fused, hs, hv));
-            else SSX_PROF_ON(ctx, hs, KID_BA_LIN_SCHUR, hipLaunchKernelGGL(k_lin_schur_b<SSX_JAC_ANALYTIC>, gWg, dim3(CH), lds_fused, hs, hv));
-          } else {
-            if (opt.jac_mode == SSX_JAC_NUMERIC_G2O) SSX_PROF_ON(ctx, hs, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize_b<SSX_JAC_NUMERIC_G2O>, gWg, dim3(CH), LIN_LDS_BYTES, hs, hv, -1));
-            else SSX_PROF_ON(ctx, hs, KID_BA_LINEARIZE, hipLaunchKernelGGL(k_linearize_b<SSX_JAC_ANALYTIC>, gWg, dim3(CH), LIN_LDS_BYTES, hs, hv, -1));
-          }
-          static const bool no_both_env = getenv("SSX_BA_SPLIT_REDUCE") != nullptr;   // (tools: the two launches, for A/B timing)
-          const bool both = fused && !first_slot && !no_both_env;    // (the first slot needs lambda between the two reductions)
-          if (both) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_both_b, dim3(B->max_rl + B->max_rs, hn), dim3(CH), 0, hs, hv, B->max_rl));
-          else SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_reduce_lin_b, gRl, dim3(CH), 0, hs, hv));
-          if (first_slot) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_LIN, hipLaunchKernelGGL(k_lambda_init_b, gOne, dim3(64), 0, hs, hv, 1));
-          if (!fused) SSX_PROF_ON(ctx, hs, KID_BA_SCHUR, hipLaunchKernelGGL(k_schur_b, gWg, dim3(CH), lds_schur, hs, hv));
-          if (!both) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_SCHUR, hipLaunchKernelGGL(k_reduce_schur_b, gRs, dim3(CH), 0, hs, hv));
-          if (B->any_solve64) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve64_b, gOne, dim3(CH), 0, hs, hv));
-          if (B->any_solve80) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve80_b, gOne, dim3(CH), 0, hs, hv));
-          if (B->any_solve) SSX_PROF_ON(ctx, hs, KID_BA_SOLVE, hipLaunchKernelGGL(k_solve_b, gOne, dim3(CH), 0, hs, hv));
-          SSX_PROF_ON(ctx, hs, KID_BA_BACKSUB, hipLaunchKernelGGL(k_backsub_residual_b, gCh, dim3(CH), 0, hs, hv, fin_b ? 1 : 0));
-          if (!fin_b) SSX_PROF_ON(ctx, hs, KID_BA_REDUCE_TRIAL, hipLaunchKernelGGL(k_reduce_trial_b, gOne, dim3(CH), 0, hs, hv, 1));   // (a window without chunks: nobody would finish its trial)
-        }
-        first_slot = false;
-      }
-      for (int g = 0; g + 1 < G; ++g) {
-        SSX_HIP_TRY(ctx, hipEventRecord(ctx->grp_ev[g], ctx->grp[g]));
-        SSX_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->grp_ev[g], 0));
-      }
-      slots_total += slots;
-      SSX_HIP_TRY(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_gather_scal_b, dim3(n), dim3(CH), 0, s, dv, n, hscal, 0);
-      if (spec_poses) {
-        // poses-only results ride behind the control words of this round, before the host has looked at them: if the round turns
-        // out to be the last one (the usual case) the solve ends on ONE synchronisation instead of two; otherwise the next round
-        // overwrites them.  The packing kernel takes the state buffer index from the window's own control block.
-        hipLaunchKernelGGL(k_gather_scal_b, dim3(n), dim3(CH), 0, s, dv, n, hscal + (size_t)n * SC_N, 1);
-        hipLaunchKernelGGL(k_pack_poses_b, dim3(n), dim3(CH), 0, s, dv, (const int*)nullptr, n, spec_maxP, B->stage->as<double>());
-        SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-        spec_done = true;
-      }
-      turn.close();
-      SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-      bool stopped = true;
-      for (int w = 0; w < n; ++w) if (!wsn[w].done && hscal[(size_t)w * SC_N + SC_STOP] == 0.0) stopped = false;
-      if (stopped) break;
-    }
-    for (int w = 0; w < n; ++w) {
-      WinState& st = wsn[w];
-      if (st.done) continue;
-      const double* sc = hscal + (size_t)w * SC_N;
-      st.cur = (int)sc[SC_CUR];
-      st.n_out = sc[SC_NOUT];
-      if (sc[SC_TRIALS_RUN] > 0.0) st.trial_err = true;
-      st.n_iters = std::max(st.n_iters, (int)sc[SC_NSTAT]);
-      st.rounds++;
-      const double n_edges = (double)B->devs[w].E, cnt_in = n_edges - st.n_out;
-      st.n_outl = (int)st.n_out; st.n_in = (int)cnt_in;
-      const double ratio = n_edges > 0 ? cnt_in / (cnt_in + st.n_out) : 1.0;
-      if (ratio > opt.inlier_ratio) st.done = true;
-      if (++st.round >= opt.outer_rounds) st.done = true;
-    }
-  }
-  if (lm_iterations_total) { int t = 0; for (int w = 0; w < n; ++w) t += wsn[w].n_iters; *lm_iterations_total = t; }
-  if (!B->exts.empty()) for (int w = 0; w < n; ++w) B->exts[w]->cur = wsn[w].cur;   // ... and the one that holds the result
-  if (!results) {                                                    // nothing to download: the caller only wants the work done
-    SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-    SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-    return SSX_OK;
-  }
-  // ---- statistics + results: one packing kernel, one download
-  const bool want_err = B->with_err;
-  // (iters <= 0, outer_rounds <= 0 or windows without a single chunk: no round ran, nothing was staged -- the ordinary
-  // gather / pack / download returns the input state)
-  const bool poses_only = spec_poses && spec_done;
-  const int maxP = spec_maxP;
-  double* h_out = B->stage->as<double>();
-  if (!poses_only) {
-  for (int w = 0; w < n; ++w) { h_ctrl[w] = wsn[w].cur; h_ctrl[n + w] = wsn[w].trial_err ? 1 : 0; h_ctrl[2 * n + w] = 1; }
-  hipLaunchKernelGGL(k_gather_scal_b, dim3(n), dim3(CH), 0, s, dv, n, hscal + (size_t)n * SC_N, 1);
-  if (want_err)                                                       // windows that never ran a trial: errors of the input state
-    for (int w = 0; w < n; ++w)
-      if (!wsn[w].trial_err && B->devs[w].nCh > 0)
-        hipLaunchKernelGGL(k_linearize<SSX_JAC_ANALYTIC>, dim3(B->devs[w].nCh), dim3(CH), LIN_LDS_BYTES, s, B->devs[w], wsn[w].cur);
-  if (want_err) {
-    // (per-edge chi2 goes back in the CALLER's order: a scatter of 8-byte words, which belongs in HBM -- over PCIe every one of them
-    // would be a transaction of its own; a streaming kernel then moves the packed block)
-    double* d_out = reinterpret_cast<double*>(dev_base + B->a_out);
-    hipLaunchKernelGGL(k_pack_out_b, dim3(64, n), dim3(CH), 0, s, dv, (const int*)h_ctrl, n, d_ooff, d_out, 1);
-    hipLaunchKernelGGL(k_stream_out, dim3((unsigned)std::min<size_t>(1024, (B->out_total + 2 * CH - 1) / (2 * CH))), dim3(CH), 0, s, (const double*)d_out, h_out, B->out_total);
-  } else {
-    hipLaunchKernelGGL(k_pack_out_b, dim3(64, n), dim3(CH), 0, s, dv, (const int*)h_ctrl, n, d_ooff, h_out, 0);
-  }
-  SSX_HIP_TRY(ctx, hipEventRecord(ctx->ev1, s));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  }   // (!poses_only)
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-  static const bool timing = getenv("SSX_BATCH_TIMING") != nullptr;
-  const auto t_unpack = std::chrono::steady_clock::now();
-  // (poses only: 560 bytes per window -- waking the worker threads costs more than copying them here)
-  ctx->ba->pool.run(n, poses_only ? 1 : B->threads, [&](int w) {
-    ssx_ba_result& r = results[w];
-    const WinState& st = wsn[w];
-    const int P = B->P[w], L = B->L[w], E = B->E[w];
-    r.rounds = st.rounds; r.n_iters = st.n_iters; r.n_inliers = st.n_in; r.n_outliers = st.n_outl;
-    r.ms_linearize = r.ms_schur = r.ms_linear_solution = r.ms_update = r.ms_reduce = r.ms_comm = 0.f;
-    const double* o = poses_only ? h_out + (size_t)w * 7 * maxP : h_out + B->out_off[w];
-    if (r.poses_out) memcpy(r.poses_out, o, sizeof(double) * 7 * P);
-    if (r.points_out && L) memcpy(r.points_out, o + 7 * (size_t)P, sizeof(double) * 3 * L);
-    if (want_err && (r.edge_chi2 || r.edge_outlier) && B->devs[w].dev_prep) {
-      const double* c2 = o + 7 * (size_t)P + 3 * (size_t)L;          // already in the caller's order
-      const int* ept = (!B->exts.empty() && B->probs) ? B->probs[w].edge_point : nullptr;
-      for (int eo = 0; eo < B->E_raw[w]; ++eo) {
-        if (ept && ept[eo] < 0) continue;                            // a dead entry of a window's storage
-        if (r.edge_chi2) r.edge_chi2[eo] = c2[eo];
-        if (r.edge_outlier) r.edge_outlier[eo] = c2[eo] > opt.chi2_th;
-      }
-    } else if (want_err && (r.edge_chi2 || r.edge_outlier)) {
-      const double* e = o + 7 * (size_t)P + 3 * (size_t)L;
-      const std::vector<int>& perm = B->perm[w];
-      for (int sidx = 0; sidx < E; ++sidx) {
-        const int eo = perm[sidx];
-        const double c2 = e[sidx] * e[sidx] + e[(size_t)E + sidx] * e[(size_t)E + sidx];
-        if (r.edge_chi2) r.edge_chi2[eo] = c2;
-        if (r.edge_outlier) r.edge_outlier[eo] = c2 > opt.chi2_th;
-      }
-    }
-    const double* hstat = hscal + (size_t)n * SC_N + (size_t)w * 3 * SSX_BA_MAX_STATS;
-    for (int k = 0; k < r.n_iters && k < SSX_BA_MAX_STATS; ++k) {
-      r.iter_chi2[k] = hstat[k];
-      r.iter_lambda[k] = hstat[SSX_BA_MAX_STATS + k];
-      r.iter_trials[k] = (int)hstat[2 * SSX_BA_MAX_STATS + k];
-    }
-    r.ms_total = ms;
-    r.ms_setup = 0.f;
-  });
-  if (timing)
-    fprintf(stderr, "[batch_run n=%d] solve + download of %.1f MB %.3f (GPU clock) | unpack %.3f ms\n", n, sizeof(double) * B->out_total / 1e6, ms,
-            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_unpack).count());
-  return SSX_OK;
-}
-
-}  // namespace
+#include "ba_batch.inc"
 
 extern "C" {
 
@@ -4070,7 +2708,7 @@ int64_t ssx_debug_kernel_dynamic_lds(const char* kernel)
   const std::string k(kernel);
   auto starts = [&](const char* p) { return k.rfind(p, 0) == 0; };
   if (starts("k_lin_schur") || starts("k_linearize") || k == "k_schur" || k == "k_schur_b") return (int64_t)BA_LDS_BYTES;
-  if (k == "k_schur_prep") return (int64_t)(sizeof(double) * (18 + 9 + 3) * PW + 64);
+  if (k == "k_schur_prep") return (int64_t)SCHUR_PREP_LDS_BYTES;
   if (starts("k_band_")) return -1;
   return 0;
 }
@@ -4124,79 +2762,6 @@ int32_t ssx_ba_debug_upload_format(const ssx_ba_problem* prob)
   return h.raw_fmt;
 }
 #endif  // SSX_NO_TEST_HOOKS
-
-ssx_status ssx_ba_solve_batch(ssx_ctx* ctx, int32_t n, const ssx_ba_problem* probs, const ssx_ba_options* opt_in, ssx_ba_result* results)
-{
-  if (!ctx || n < 0 || (n > 0 && (!probs || !results))) return SSX_ERR_INVALID_ARG;
-  if (n == 0) return SSX_OK;
-  ssx_ba_options opt;
-  if (opt_in) opt = *opt_in; else ssx_ba_default_options(&opt);
-  auto sequential = [&]() -> ssx_status {
-    for (int w = 0; w < n; ++w) {
-      const ssx_status st = ssx_ba_solve(ctx, &probs[w], &opt, &results[w]);
-      if (st != SSX_OK) return st;
-    }
-    return SSX_OK;
-  };
-  if (opt.comm || opt.allreduce || n == 1) return sequential();
-  bool with_err = false;
-  for (int w = 0; w < n; ++w) if (results[w].edge_chi2 || results[w].edge_outlier) with_err = true;
-  ssx_ba_batch B;
-  ssx_status st = batch_build(ctx, n, probs, opt, with_err, false, &B);
-  if (st == SSX_ERR_UNSUPPORTED) return sequential();                 // a large window in the batch
-  if (st != SSX_OK) return st;
-  return batch_run(&B, results, nullptr);
-}
-
-// A RESIDENT batch: the windows are marshalled and uploaded once and stay in HBM; every ssx_ba_batch_solve optimises
-// them again from the uploaded state (bench.py times this with nothing crossing PCIe but the LM control words).
-ssx_status ssx_ba_batch_create(ssx_ctx* ctx, int32_t n, const ssx_ba_problem* probs, const ssx_ba_options* opt_in, int32_t with_edge_errors,
-                               ssx_ba_batch** out)
-{
-  if (!ctx || n <= 0 || !probs || !out) return SSX_ERR_INVALID_ARG;
-  *out = nullptr;
-  ssx_ba_options opt;
-  if (opt_in) opt = *opt_in; else ssx_ba_default_options(&opt);
-  if (opt.comm || opt.allreduce) { ctx->set_error("ssx_ba_batch_create: batches do not take a collective"); return SSX_ERR_UNSUPPORTED; }
-  ssx_ba_batch* B = new ssx_ba_batch();
-  const ssx_status st = batch_build(ctx, n, probs, opt, with_edge_errors != 0, true, B);
-  if (st != SSX_OK) {
-    if (st == SSX_ERR_UNSUPPORTED) ctx->set_error("ssx_ba_batch_create: a window has more than %d free keyframes (use ssx_ba_solve)", SSX_BA_SMALL_P);
-    ssx_ba_batch_destroy(B);
-    return st;
-  }
-  *out = B;
-  return SSX_OK;
-}
-
-ssx_status ssx_ba_batch_solve(ssx_ba_batch* batch, ssx_ba_result* results, int32_t* lm_iterations_total)
-{
-  if (!batch) return SSX_ERR_INVALID_ARG;
-  return batch_run(batch, results, lm_iterations_total);
-}
-
-void ssx_ba_device_turns(int32_t enable) { g_turns.enable(enable != 0); }
-
-ssx_status ssx_ba_set_batch_groups(ssx_ctx* ctx, int32_t groups)
-{
-  if (!ctx || groups < 0 || groups > 4) return SSX_ERR_INVALID_ARG;
-  ctx->ba_batch_groups = groups;
-  return SSX_OK;
-}
-
-int32_t ssx_ba_batch_size(const ssx_ba_batch* batch) { return batch ? batch->n : 0; }
-
-int32_t ssx_ba_batch_groups(const ssx_ba_batch* batch) { return !batch ? 0 : (batch->groups > 0 ? std::min(batch->groups, 4) : batch_groups(batch->n)); }
-
-void ssx_ba_batch_set_groups(ssx_ba_batch* batch, int32_t groups) { if (batch) batch->groups = groups > 0 ? groups : 0; }
-
-void ssx_ba_batch_destroy(ssx_ba_batch* batch)
-{
-  if (!batch) return;
-  (void)hipSetDevice(batch->device);
-  batch->arena_own.release(); batch->stage_own.release(); batch->scal_own.release();
-  delete batch;
-}
 
 }  // extern "C"
 

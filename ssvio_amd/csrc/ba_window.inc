@@ -306,8 +306,7 @@ ssx_status win_sync_many(int n, ssx_ba_window* const* wins)
   ssx_ctx* ctx = wins[0]->ctx;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
+  BaWorkspace* ws = ba_workspace(ctx);
   static const bool timing = getenv("SSX_WIN_TIMING") != nullptr;
   const auto tq0 = std::chrono::steady_clock::now();
   auto tq_ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count(); };
@@ -742,9 +741,8 @@ ssx_status ssx_ba_window_update_batch(int32_t n, ssx_ba_window* const* wins, con
   std::vector<ssx_status> sts(n, SSX_OK);
   ssx_ctx* ctx = wins[0]->ctx;
   if (ctx && n > 1) {
-    if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
     const int hw = (int)std::thread::hardware_concurrency();
-    ctx->ba->pool.run(n, std::max(1, std::min({n, host_threads_cap(), hw > 1 ? hw / 2 : 1})), [&](int i) { sts[i] = one(i); });
+    ba_workspace(ctx)->pool.run(n, std::max(1, std::min({n, host_threads_cap(), hw > 1 ? hw / 2 : 1})), [&](int i) { sts[i] = one(i); });
   } else {
     for (int i = 0; i < n; ++i) sts[i] = one(i);
   }
@@ -881,8 +879,7 @@ ssx_status ssx_ba_window_solve_batch(int32_t n, ssx_ba_window* const* wins, ssx_
     if (st0 != SSX_OK) return st0;
   }
   const auto tp1 = std::chrono::steady_clock::now();
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  ctx->ba->pool.run(n, std::min(n, host_threads_cap()), [&](int i) {    // (the fix-rule pass and the id order are per-window host work)
+  ba_workspace(ctx)->pool.run(n, std::min(n, host_threads_cap()), [&](int i) {    // (the fix-rule pass and the id order are per-window host work)
     ssx_ba_window* w = wins[i];
     win_view(w, &prs[i]);
     w->r_pose.resize(7 * w->kf.size() + 1); w->r_point.resize(3 * w->lm_id.size() + 1);

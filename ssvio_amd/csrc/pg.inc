@@ -187,8 +187,7 @@ ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, 
     }
   if (nP == 0 || E == 0) return SSX_OK;                        // nothing to optimise (g2o: optimize() returns -1)
   if (nP > 2048) { ctx->set_error("ssx_pose_graph_opt: %d free keyframes exceed the supported 2048", nP); return SSX_ERR_UNSUPPORTED; }
-  if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; }
-  BaWorkspace* ws = ctx->ba;
+  BaWorkspace* ws = ba_workspace(ctx);
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // ---- host lists: non-zero blocks (diagonal first) with their contributing (edge, kind) in edge order ----
   std::vector<uint8_t> active(E);
