@@ -1765,33 +1765,37 @@ inline int dense_slabs_mode()
   return m;
 }
 struct HostPrep {                    // what prepare() of ba_marshal.inc fills in (here: BaWorkspace below keeps them by value)
+  // counting results: written on every path of prepare() (band_w: by build_pairs), read by the plan of the arena
   int P, L, E, nP, nLm, nCh, nBlk;
   int E_raw = 0;                     // entries of the caller's edge arrays (E of them alive; see BaDev::E_raw)
   int raw_fmt = 0;                   // BaDev::raw_fmt of the blob this window is uploaded in
-  std::vector<int> pose_free, lm_id, lm_ptr, ch_lm, e_pose, e_lmc, perm, pair_ptr;
-  std::vector<uint8_t> lm_fixed, e_cam, e_dup, pair_a, pair_b;
-  std::vector<uint16_t> pptr;
-  std::vector<double> e_uv;
-  std::vector<int8_t> blk_pa, blk_pb;
-  // large-window path
-  bool big = false;
-  std::vector<int> pe_ptr, pe_edge, sblk_pa, sblk_pb, spair_ptr;
-  std::vector<int> bseg, bseg_ptr;   // see BaDev
-  std::vector<int> thr_cnt, thr_pe;  // prepare() of a large window on several threads: per-thread landmark / pose counts
-  std::vector<unsigned int> touch;   // host-built lists only: BaDev::touch
+  bool big = false;                  // more than SSX_BA_SMALL_P free poses: the large-window path
   bool dev_lists = false;            // small window: pair lists + work items are built by k_build_lists, not here
-  bool dev_prep = false;             // small window: the edge sort by (landmark, pose), the packed records, the pose-major order and the
-                                     // sorted uv columns are built ON THE DEVICE (k_prep_scatter / k_prep_chunk) from the caller's raw
-                                     // arrays; the host only counts (slot8: rank of an edge among its landmark's edges in caller order)
-  std::vector<uint8_t> slot8;
+  bool dev_prep = false;             // the edge sort by (landmark, pose), the packed records, the pose-major order and the sorted uv columns
+                                     // are built ON THE DEVICE (k_prep_scatter / k_prep_chunk) from the caller's raw arrays; the host only counts
+  int band_w = -1;                   // cyclic block bandwidth of this rank's part of the reduced system (max over its non-zero blocks)
+  // the light tables: built on every path, all that a device-marshalled window uploads beside the caller's arrays
+  std::vector<int> pose_free, lm_id, lm_ptr, ch_lm;
+  std::vector<uint8_t> lm_fixed, slot8;   // slot8: rank of an edge among its landmark's edges in caller order (device-marshalled windows)
   std::vector<int> lm_compact;       // caller's landmark -> compact landmark or -1
   std::vector<int> pose_rank;        // empty, or BaDev::pose_rank (a window's keyframes in the order of their ids)
-  std::vector<int> cnt_tmp, start_tmp, first_pf_tmp, visit_tmp, visit2_tmp;
-  std::vector<uint32_t> tmp_pairs;   // scratch of prepare(), kept between calls
+  std::vector<int> ch_desc;          // packed chunk records (4 ints each), see BaDev
+  std::vector<int8_t> blk_pa, blk_pb;
+  // the host reference's arrays (ref_* of ba_marshal.inc; the device builds them otherwise): sorted columns, packed records, per-chunk lists
+  std::vector<int> e_pose, e_lmc, perm, pair_ptr;
+  std::vector<uint8_t> e_cam, e_dup, pair_a, pair_b;
+  std::vector<uint16_t> pptr;
+  std::vector<double> e_uv;
+  std::vector<int> e_rec, l_rec;     // packed records (4 ints each), see BaDev
+  std::vector<int> lm_chunk;         // compact landmark -> chunk (large windows: the device-side pair builder)
+  std::vector<int> bseg, bseg_ptr;   // see BaDev
+  std::vector<unsigned int> touch;   // BaDev::touch
+  // the large-window lists: pe_ptr by prepare() (pe_edge by the reference only), the block list by build_pairs
+  std::vector<int> pe_ptr, pe_edge, sblk_pa, sblk_pb, spair_ptr;
+  // scratch of prepare(), kept between calls (thr_*: per-thread landmark / pose counts of a large window counted on several threads)
+  std::vector<int> thr_cnt, thr_pe, cnt_tmp, start_tmp, first_pf_tmp, visit_tmp, visit2_tmp;
+  std::vector<uint32_t> tmp_pairs;
   std::vector<std::pair<int, int>> tmp_order;
-  std::vector<int> ch_desc, e_rec, l_rec;   // packed records (4 ints each), see BaDev
-  std::vector<int> lm_chunk;                // compact landmark -> chunk (large windows: the device-side pair builder)
-  int band_w = -1;          // cyclic block bandwidth of this rank's part of the reduced system (max over its non-zero blocks)
 };
 }  // namespace
 
@@ -1965,12 +1969,12 @@ static void ssx_ba_workspace_free(BaWorkspace* w)
 // the context's BA workspace, created on first use
 static BaWorkspace* ba_workspace(ssx_ctx* ctx) { if (!ctx->ba) { ctx->ba = new BaWorkspace(); ctx->ba_free = ssx_ba_workspace_free; } return ctx->ba; }
 
+#define SSX_TRY(expr) do { const ssx_status _st = (expr); if (_st != SSX_OK) return _st; } while (0)   // a failed step ends the call
 namespace {
 #include "ba_marshal.inc"
 
 // dynamic LDS of k_schur, of the fused k_lin_schur, of k_schur_prep
 constexpr size_t SCHUR_LDS_BYTES = BA_LDS_BYTES, FUSED_LDS_BYTES = std::max(BA_LDS_BYTES, LIN_LDS_BYTES), SCHUR_PREP_LDS_BYTES = sizeof(double) * (18 + 9 + 3) * PW + 64;
-#define SSX_TRY(expr) do { const ssx_status _st = (expr); if (_st != SSX_OK) return _st; } while (0)   // a failed step ends the call
 // the analytic or the numeric (g2o's central differences) instantiation of a kernel template: LAUNCH_JAC(jac, k_x, grid, block, lds, stream, args...)
 #define LAUNCH_JAC(jac, kernel, ...) \
   do { if ((jac) == SSX_JAC_NUMERIC_G2O) hipLaunchKernelGGL(kernel<SSX_JAC_NUMERIC_G2O>, __VA_ARGS__); else hipLaunchKernelGGL(kernel<SSX_JAC_ANALYTIC>, __VA_ARGS__); } while (0)
@@ -2603,7 +2607,7 @@ static ssx_status ba_solve_impl(ssx_ctx* ctx, const ssx_ba_problem* prob, const 
   if (h.big) SSX_TRY(build_pairs(ctx, h, &pairs_dev, big_dev ? &recs : nullptr));
   tph[1] = tc_ms();
   SSX_TRY(plan_large_solver(ctx, h, opt, cm, S.bp));
-  SSX_TRY(upload(ctx, prob, h, opt.huber_delta, opt.chi2_th, cm.world, cm.fn ? opt.rank : 0, d, S.bd, S.bp, S.bnd, nullptr, ext, big_dev ? &recs : nullptr, pe_ptr_dev, pe_edge_dev));
+  SSX_TRY(upload(ctx, prob, h, opt.huber_delta, opt.chi2_th, cm.world, cm.fn ? opt.rank : 0, d, S.bd, S.bp, S.bnd, ext, big_dev ? &recs : nullptr, pe_ptr_dev, pe_edge_dev));
   tph[2] = tc_ms();
   d.store_w = (d.big || opt.jac_mode == SSX_JAC_NUMERIC_G2O) ? 1 : 0;
   d.no_err = (!d.big && !(res->edge_chi2 || res->edge_outlier)) ? 1 : 0;
@@ -2732,8 +2736,10 @@ double ssx_ba_debug_prepare_seconds(const ssx_ba_problem* prob, int32_t reps)
   return best;
 }
 
-// test hook (no GPU needed): FNV-1a digest of what prepare() hands on for a large window (per-landmark offsets, the rank of
-// every observation inside its landmark, per-pose counts, chunk cuts), counted on `threads` host threads
+// test hook (no GPU needed): FNV-1a digest of everything prepare() hands on to the upload -- every scalar and array of HostPrep the
+// upload reads -- with the large window's observations counted on `threads` host threads, and of the plan of the arena made from it:
+// every offset in declaration order, the blob's bytes and the total, without and with the pristine copy of a resident batch (a single
+// window is laid out like a window of a one-shot batch), for one and two ranks and as a resident window, a large window also on the band solver
 uint64_t ssx_ba_debug_prepare_digest(const ssx_ba_problem* prob, int32_t threads)
 {
   if (!prob) return 0;
@@ -2748,8 +2754,28 @@ uint64_t ssx_ba_debug_prepare_digest(const ssx_ba_problem* prob, int32_t threads
   if (st != SSX_OK) return 0;
   uint64_t d = 1469598103934665603ull;
   auto eat = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; ++i) { d ^= b[i]; d *= 1099511628211ull; } };
-  eat(h.lm_ptr.data(), sizeof(int) * h.lm_ptr.size()); eat(h.lm_id.data(), sizeof(int) * h.lm_id.size());
-  eat(h.slot8.data(), (size_t)h.E_raw); eat(h.pe_ptr.data(), sizeof(int) * h.pe_ptr.size()); eat(h.ch_lm.data(), sizeof(int) * h.ch_lm.size());
+  auto eat_v = [&](const auto& v, size_t n) { n = std::min(n, v.size()); eat(&n, sizeof(n)); eat(v.data(), sizeof(v[0]) * n); };
+  const size_t all = ~size_t(0), ref = h.dev_prep ? 0 : all;         // (a device-marshalled window leaves the reference's arrays as they were)
+  const int sc[13] = {h.P, h.L, h.E, h.E_raw, h.nP, h.nLm, h.nCh, h.nBlk, h.raw_fmt, h.big, h.dev_lists, h.dev_prep, h.band_w};
+  eat(sc, sizeof(sc));
+  eat_v(h.lm_ptr, all); eat_v(h.lm_id, all); eat_v(h.slot8, h.dev_prep ? h.E_raw : 0); eat_v(h.pe_ptr, all); eat_v(h.ch_lm, all);
+  eat_v(h.pose_free, all); eat_v(h.lm_fixed, all); eat_v(h.lm_compact, all); eat_v(h.pose_rank, all); eat_v(h.ch_desc, 4 * (size_t)h.nCh);
+  eat_v(h.blk_pa, all); eat_v(h.blk_pb, all);
+  eat_v(h.e_pose, ref); eat_v(h.e_lmc, ref); eat_v(h.e_cam, ref); eat_v(h.e_dup, ref); eat_v(h.e_uv, ref); eat_v(h.perm, all);
+  eat_v(h.e_rec, std::min(ref, 4 * (size_t)h.E)); eat_v(h.l_rec, std::min(ref, 4 * (size_t)h.nLm)); eat_v(h.lm_chunk, std::min(ref, (size_t)h.nLm));
+  eat_v(h.pptr, all); eat_v(h.pair_a, all); eat_v(h.pair_b, all); eat_v(h.pair_ptr, all); eat_v(h.bseg, all); eat_v(h.bseg_ptr, all);
+  eat_v(h.touch, (ref && !h.big) ? all : 0);
+  eat_v(h.pe_edge, all); eat_v(h.sblk_pa, all); eat_v(h.sblk_pb, all); eat_v(h.spair_ptr, all);
+  BandPlan bands[2];
+  if (h.big) { plan_band(h.nP, 3, bands[1]); plan_bcr(h.nP, 3, bands[1].bcr); }
+  const WinExt win;                                                  // (a resident window: state and raw arrays in buffers of its own)
+  for (int v = 0; v < (h.dev_prep && !h.big ? 3 : 2); ++v)           // one rank, one of two ranks, a resident window
+   for (int keep_init = 0; keep_init < 2; ++keep_init)
+    for (int b = 0; b < (h.big ? 2 : 1); ++b) {
+      const ArenaPlan p = plan_arena(prob, h, bands[b], v == 1 ? 2 : 1, keep_init != 0, v == 2 ? &win : nullptr, h.big && h.dev_prep);
+      for (const Span* s = p.spans_begin(); s != p.spans_end(); ++s) eat(&s->off, sizeof(size_t));
+      eat(&p.in_bytes, sizeof(size_t)); eat(&p.total, sizeof(size_t));
+    }
   return d;
 }
 

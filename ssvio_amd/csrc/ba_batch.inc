@@ -67,19 +67,16 @@ ssx_status batch_build(ssx_ctx* ctx, int n, const ssx_ba_problem* probs, const s
   B->stage = own ? &B->stage_own : &ws->stage;
   B->scal = own ? &B->scal_own : &ws->scal;
   // ---- 2. sizes, one arena: [blobs of all windows | BaDev[n] | ctrl int[3n] | out offsets | scratch of all windows | packed outputs | gather]
-  std::vector<UploadPlace> place(n);
+  std::vector<ArenaPlan> plans(n);                                   // (each window is planned once; the pool threads fill and wire from the plan)
   B->devs.assign(n, BaDev{});
   BandPlan no_band;
   size_t in_total = 0, rest_total = 0, out_total = 0;
   std::vector<size_t> in_off(n), rest_off(n);
   B->out_off.assign(n, 0); B->P.resize(n); B->L.resize(n); B->E.resize(n); B->E_raw.resize(n); B->perm.resize(n);
   for (int w = 0; w < n; ++w) {
-    BigDev bd; BandDev bnd;
-    place[w].dry = true;
-    place[w].keep_init = own;
-    SSX_TRY(upload(ctx, &probs[w], preps[w], opt.huber_delta, opt.chi2_th, 1, 0, B->devs[w], bd, no_band, bnd, &place[w], exts ? exts[w] : nullptr));
-    in_off[w] = in_total; in_total += place[w].in_bytes;
-    rest_off[w] = rest_total; rest_total += place[w].rest_bytes;
+    plans[w] = plan_arena(&probs[w], preps[w], no_band, 1, own, exts ? exts[w] : nullptr, false);
+    in_off[w] = in_total; in_total += plans[w].in_bytes;
+    rest_off[w] = rest_total; rest_total += plans[w].total - plans[w].in_bytes;
     B->out_off[w] = out_total;
     B->P[w] = preps[w].P; B->L[w] = preps[w].L; B->E[w] = preps[w].E; B->E_raw[w] = preps[w].E_raw;
     out_total += 7 * (size_t)preps[w].P + 3 * (size_t)preps[w].L + (with_err ? std::max(2 * (size_t)preps[w].E, (size_t)preps[w].E_raw) : 0);
@@ -110,16 +107,13 @@ ssx_status batch_build(ssx_ctx* ctx, int n, const ssx_ba_problem* probs, const s
   ws->pool.run(q1 - q0, T, [&](int wi) {
     const int w = q0 + wi;
     BigDev bd; BandDev bnd;
-    place[w].dry = false;
-    place[w].in_dev = dev_base + B->a_head + in_off[w];
-    place[w].rest_dev = dev_base + a_rest + rest_off[w];
-    place[w].in_host = hst + in_off[w];
-    sts[w] = upload(ctx, &probs[w], preps[w], opt.huber_delta, opt.chi2_th, 1, 0, B->devs[w], bd, no_band, bnd, &place[w], exts ? exts[w] : nullptr);
+    fill_blob(plans[w], &probs[w], preps[w], no_band, hst + in_off[w]);
+    wire_arena(plans[w], dev_base + B->a_head + in_off[w], dev_base + a_rest + rest_off[w], &probs[w], opt.huber_delta, opt.chi2_th, 1, 0,
+               exts ? exts[w] : nullptr, nullptr, nullptr, nullptr, B->devs[w], bd, bnd);
     B->devs[w].store_w = opt.jac_mode == SSX_JAC_NUMERIC_G2O ? 1 : 0;
     B->devs[w].no_err = with_err ? 0 : 1;
     if (with_err) B->perm[w] = preps[w].perm;
   });
-  for (int w = q0; w < q1; ++w) if (sts[w] != SSX_OK) { (void)hipStreamSynchronize(ctx->stream); return sts[w]; }
   if (q + 1 < Q) {
     const size_t b0 = in_off[q0], b1 = in_off[q1];
     if (b1 > b0) SSX_HIP_TRY(ctx, hipMemcpyAsync(dev_base + B->a_head + b0, hst + b0, b1 - b0, hipMemcpyHostToDevice, ctx->stream));

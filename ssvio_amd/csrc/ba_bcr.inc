@@ -86,6 +86,17 @@ __device__ __forceinline__ void bcr_who(int sh, int Mq, int b, int& j, int& l, i
 }
 
 static inline size_t bcr_mem_doubles(int N, int m) { return (size_t)N * (8 * (size_t)m * m + 5 * (size_t)m); }
+// the memory of a reduction of N super-blocks of m columns, carved from the bcr_mem_doubles(N, m) doubles at base
+static inline void bcr_carve(BcrDev& q, double* base, int N, int m)
+{
+  q.on = 1; q.N = N; q.m = m;
+  const size_t mmN = (size_t)N * m * m, mN = (size_t)N * m;
+  q.D = base; q.E = q.D + mmN; q.DL = q.E + 2 * mmN;   /* E: two buffers, bcr_e_buf */ q.DR = q.DL + mmN; q.Lf = q.DR + mmN; q.Ul = q.Lf + mmN; q.Ur = q.Ul + mmN;
+  q.R = q.Ur + mmN; q.RL = q.R + mN; q.RR = q.RL + mN; q.Y = q.RR + mN; q.X = q.Y + mN;
+}
+// doubles of the band of nP poses at bandwidth w (BandDev::Sb), and of [band | rhs] (the rhs, BandDev::bsv, starts behind the band)
+static inline size_t band_doubles(int nP, int w) { return (size_t)nP * (w + 1) * 36; }
+static inline size_t band_rhs_doubles(int nP, int w) { return band_doubles(nP, w) + 6 * (size_t)nP; }
 
 // The coupling blocks E live in TWO buffers (BcrDev::E, E + N m m).  The BCR_S workgroups that eliminate j all read E_l, and one of
 // them stores the new coupling (l, r) = - U_l^T U_r under the same index l: written where it is read, a workgroup dispatched late

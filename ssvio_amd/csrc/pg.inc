@@ -252,7 +252,7 @@ ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, 
   const size_t o_eblk = all.take(sizeof(double) * PG_EBLK * (size_t)E), o_err = all.take(sizeof(double) * 6 * (size_t)E);
   const size_t o_maxd = all.take(sizeof(double) * nP), o_iter = all.take(sizeof(double) * ((size_t)nP * 27 + 8));
   const size_t o_S = all.take(use_bcr ? 256 : sizeof(double) * (size_t)(n_pad + NB) * n_pad), o_x = all.take(sizeof(double) * (n_pad + 8));
-  const size_t sb_count = use_bcr ? (size_t)nP * (band_w + 1) * 36 + (size_t)n : 0;
+  const size_t sb_count = use_bcr ? band_rhs_doubles(nP, band_w) : 0;
   const size_t o_Sb = all.take(sizeof(double) * (sb_count + 1)), o_bcr_mem = all.take(use_bcr ? sizeof(double) * (bcr_mem_doubles(bcrp.N, bcrp.m) + 8) : 256);
   const size_t o_Ld = all.take(sizeof(double) * NB * NB), o_invd = all.take(sizeof(double) * (n_pad + 8)), o_Ninv = all.take(sizeof(double) * 4 * 256);
   const size_t o_sp = all.take(sizeof(double) * 64), o_xp = all.take(sizeof(double) * (n + 1)), o_scal = all.take(sizeof(double) * SC_N);
@@ -296,14 +296,9 @@ ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, 
   BandDev bnd{};
   if (use_bcr) {
     bnd.on = 1; bnd.w = band_w; bnd.K = 1; bnd.nP = nP;
-    bnd.Sb = (double*)(base + o_Sb); bnd.bsv = bnd.Sb + (size_t)nP * (band_w + 1) * 36;
-    BcrDev& q = bnd.bcr;
-    q.on = 1; q.N = bcrp.N; q.m = bcrp.m;
-    q.p0 = (const int*)(base + o_bcr_p0); q.elim = (const int4*)(base + o_bcr_elim);
-    const size_t mmN = (size_t)q.N * q.m * q.m, mN = (size_t)q.N * q.m;
-    double* mem = (double*)(base + o_bcr_mem);
-    q.D = mem; q.E = q.D + mmN; q.DL = q.E + 2 * mmN; q.DR = q.DL + mmN; q.Lf = q.DR + mmN; q.Ul = q.Lf + mmN; q.Ur = q.Ul + mmN;
-    q.R = q.Ur + mmN; q.RL = q.R + mN; q.RR = q.RL + mN; q.Y = q.RR + mN; q.X = q.Y + mN;
+    bnd.Sb = (double*)(base + o_Sb); bnd.bsv = bnd.Sb + band_doubles(nP, band_w);
+    bnd.bcr.p0 = (const int*)(base + o_bcr_p0); bnd.bcr.elim = (const int4*)(base + o_bcr_elim);
+    bcr_carve(bnd.bcr, (double*)(base + o_bcr_mem), bcrp.N, bcrp.m);
   } else {
     st = build_tile_lists(ctx, ws, blk_pa, blk_pb, cm, bd, tl_row_cnt, tl_pair_cnt, tl_next_diag);
     if (st != SSX_OK) return st;
