@@ -44,6 +44,25 @@ SSX_API int32_t ssx_ba_debug_upload_format(const ssx_ba_problem* prob);
  * take it on the worker pool; SSX_BA_PREP_THREADS, default min(8, cores)).  The digest must not depend on `threads`.  0 = invalid. */
 SSX_API uint64_t ssx_ba_debug_prepare_digest(const ssx_ba_problem* prob, int32_t threads);
 
+/* tests / tools hook, needs no GPU: the plan of the ORB front-end (pyramid geometry, cell grid, capacities, tilings, cv::resize
+ * tables, arena layout) for `images` images of rows x cols, built exactly as the entry points build it but without a device.
+ *   status / error   what the entry point would return and ssx_last_error() would show; the rest is filled for SSX_OK only
+ *   digest           FNV-1a of [0] every scalar of the device view, [1] every buffer's offset and the arena's bytes, [2] the cell and the two
+ *                    resize tables byte for byte (tools/orb_plan_ab.py compares them between two builds of the library)
+ *   buf_off / _bytes the arena's buffers in memory order
+ * unchecked != 0 skips the argument checks that come first (but for the number of levels, which sizes arrays), so that the refusals
+ * behind them can be reached and their order tested. */
+typedef struct ssx_orb_plan_info {
+  int32_t status, n_buffers;
+  uint64_t digest[3];
+  uint64_t arena_bytes, buf_off[32], buf_bytes[32];
+  int32_t nlevels, out_cap;
+  int32_t lvl_rows[8], lvl_cols[8], feat[8], lvl_cell0[9], gauss_tile0[9];
+  char error[256];
+} ssx_orb_plan_info;
+SSX_API ssx_status ssx_orb_debug_plan(int32_t rows, int32_t cols, int32_t images, const ssx_orb_params* prm, int32_t has_mask,
+                                      int32_t detect_only, int32_t unchecked, ssx_orb_plan_info* out);
+
 /* ---- kernel taps (moved here from ssx.h in 0.1.20): intermediate results of the kernels, for the parity tests and tools ---- */
 
 /* One linearisation of the problem at its current state (no update): the blocks the kernels build,

@@ -1055,8 +1055,8 @@ static void orb_ws_free(OrbWorkspace* w)
 {
   if (!w) return;
   w->arena.release(); w->input.release(); w->stereo.release(); w->stage.release(); w->fetch.release();
-  w->ingest[0].release(); w->ingest[1].release(); w->counts_pinned.release();
-  for (int b = 0; b < 2; ++b) { if (w->ev_up[b]) (void)hipEventDestroy(w->ev_up[b]); if (w->ev_free[b]) (void)hipEventDestroy(w->ev_free[b]); if (w->ev_counts[b]) (void)hipEventDestroy(w->ev_counts[b]); }
+  w->up[0].buf.release(); w->up[1].buf.release(); w->counts_pinned.release();
+  for (hipEvent_t e : {w->up[0].ev_up, w->up[1].ev_up, w->up[0].ev_free, w->up[1].ev_free, w->cnt[0].ev, w->cnt[1].ev}) if (e) (void)hipEventDestroy(e);
   if (w->copy_stream) { (void)hipStreamSynchronize(w->copy_stream); (void)hipStreamDestroy(w->copy_stream); }
   delete w;
 }
@@ -1102,128 +1102,135 @@ void make_cells(int rows, int cols, int level, std::vector<Cell>& out)
   }
 }
 
-}  // namespace
+// ---- the plan as a plain value: from here down to build_plan() host arithmetic only -- no HIP call, no ctx ----
+constexpr int ARENA_BUFS = 17, PLAN_ERR = 256;   // buffers of the arena; bytes of the text that says why a plan cannot be made
+struct OrbPlan {
+  OrbDev dev{};                  // every scalar; the buffer pointers stay null until plan() wires them
+  std::vector<Cell> cells; std::vector<ResizeQuad> xtab; std::vector<uint2> ytab;   // the host tables, uploaded into the first three buffers
+  size_t off[ARENA_BUFS], bytes[ARENA_BUFS], arena_bytes = 0;   // the buffers in memory order (for_each_buffer), each rounded to 256 bytes
+};
+template <class... A> ssx_status plan_fail(char* err, ssx_status st, const char* fmt, A... a) { snprintf(err, PLAN_ERR, fmt, a...); return st; }
 
-ssx_status plan(ssx_ctx* ctx, int rows, int cols, int I, const ssx_orb_params& prm, bool has_mask, bool detect_only)
+ssx_status check_key(const PlanKey& k, const ssx_orb_params& prm, char* err)
 {
-  OrbWorkspace* ws = get_ws(ctx);
-  const int nlevels = detect_only ? 1 : prm.nlevels;
-  if (rows <= 2 * EDGE_THRESHOLD || cols <= 2 * EDGE_THRESHOLD || rows > 4000 || cols > 4000) {
-    ctx->set_error("ssx_orb: image %dx%d outside the supported range (40..4000 per side)", cols, rows);
-    return SSX_ERR_INVALID_ARG;
-  }
-  if (nlevels < 1 || nlevels > MAX_LEVELS || !(prm.scale_factor > 1.0f) || prm.nfeatures < 1 || prm.nfeatures > SEL_CAP - 8 || I < 1) {
-    ctx->set_error("ssx_orb: unsupported parameters (nlevels=%d scale=%g nfeatures=%d)", prm.nlevels, (double)prm.scale_factor, prm.nfeatures);
-    return SSX_ERR_INVALID_ARG;
-  }
-  if (ws->planned && ws->rows == rows && ws->cols == cols && ws->I == I && ws->nlevels == nlevels &&
-      ws->nfeatures == prm.nfeatures && ws->ini_th == prm.ini_th_fast && ws->min_th == prm.min_th_fast &&
-      ws->has_mask == (int)has_mask && ws->detect_only == (int)detect_only && ws->scale_factor == prm.scale_factor)
-    return SSX_OK;
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // re-planning invalidates buffers in flight
-  OrbDev d{};
-  d.I = I; d.nlevels = nlevels; d.ini_th = prm.ini_th_fast; d.min_th = prm.min_th_fast;
-  d.has_mask = has_mask; d.detect_only = detect_only;
-  // ORBextractor ctor tables (orbextractor.cpp:133-168)
+  if (k.rows <= 2 * EDGE_THRESHOLD || k.cols <= 2 * EDGE_THRESHOLD || k.rows > 4000 || k.cols > 4000)
+    return plan_fail(err, SSX_ERR_INVALID_ARG, "ssx_orb: image %dx%d outside the supported range (40..4000 per side)", k.cols, k.rows);
+  if (k.nlevels < 1 || k.nlevels > MAX_LEVELS || !(k.scale_factor > 1.0f) || k.nfeatures < 1 || k.nfeatures > SEL_CAP - 8 || k.I < 1)
+    return plan_fail(err, SSX_ERR_INVALID_ARG, "ssx_orb: unsupported parameters (nlevels=%d scale=%g nfeatures=%d)", prm.nlevels, (double)k.scale_factor, k.nfeatures);
+  return SSX_OK;
+}
+
+// levels and per-level budgets: the ORBextractor ctor tables (orbextractor.cpp:133-168) and ComputePyramid's sizes (:999-1001)
+ssx_status plan_levels(const PlanKey& k, OrbPlan& p, char* err)
+{
+  OrbDev& d = p.dev;
+  const int nlevels = d.nlevels = k.nlevels;
+  d.I = k.I; d.ini_th = k.ini_th; d.min_th = k.min_th; d.has_mask = k.has_mask; d.detect_only = k.detect_only;
   float scale[MAX_LEVELS], inv[MAX_LEVELS];
   scale[0] = 1.0f;
-  for (int i = 1; i < nlevels; ++i) scale[i] = scale[i - 1] * prm.scale_factor;
+  for (int i = 1; i < nlevels; ++i) scale[i] = scale[i - 1] * k.scale_factor;
   for (int i = 0; i < nlevels; ++i) inv[i] = 1.0f / scale[i];
-  if (detect_only) {
-    d.feat[0] = prm.nfeatures;
+  if (k.detect_only) {
+    d.feat[0] = k.nfeatures;
   } else {
-    const float factor = 1.0f / prm.scale_factor;
-    float nDesired = prm.nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
+    const float factor = 1.0f / k.scale_factor;
+    float nDesired = k.nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
     int sum = 0;
-    for (int l = 0; l < nlevels - 1; ++l) {
-      d.feat[l] = h_round(nDesired);
-      sum += d.feat[l];
-      nDesired *= factor;
-    }
-    d.feat[nlevels - 1] = std::max(prm.nfeatures - sum, 0);
+    for (int l = 0; l < nlevels - 1; ++l) { d.feat[l] = h_round(nDesired); sum += d.feat[l]; nDesired *= factor; }
+    d.feat[nlevels - 1] = std::max(k.nfeatures - sum, 0);
   }
-  std::vector<Cell> cells;
   size_t off = 0;
-  int out_cap = 32;
   for (int l = 0; l < nlevels; ++l) {
     d.scale[l] = scale[l];
-    d.lvl_cols[l] = h_round((float)cols * inv[l]);   // ComputePyramid, orbextractor.cpp:999-1001
-    d.lvl_rows[l] = h_round((float)rows * inv[l]);
+    d.lvl_cols[l] = h_round((float)k.cols * inv[l]);
+    d.lvl_rows[l] = h_round((float)k.rows * inv[l]);
     d.lvl_pitch[l] = (d.lvl_cols[l] + 127) & ~127;
     d.lvl_off[l] = off;
     off += (size_t)d.lvl_pitch[l] * d.lvl_rows[l];
-    d.lvl_cell0[l] = (int)cells.size();
-    make_cells(d.lvl_rows[l], d.lvl_cols[l], l, cells);
+    if (d.feat[l] + 8 > SEL_CAP) return plan_fail(err, SSX_ERR_UNSUPPORTED, "ssx_orb: %d features on level %d exceed the octree node capacity", d.feat[l], l);
+  }
+  d.pyr_bytes = (off + 255) & ~size_t(255);
+  return SSX_OK;
+}
+
+// the cell grid of every level, and the keypoints one image can return
+void plan_cells(OrbPlan& p)
+{
+  OrbDev& d = p.dev;
+  d.out_cap = 32;
+  for (int l = 0; l < d.nlevels; ++l) {
+    d.lvl_cell0[l] = (int)p.cells.size();
+    make_cells(d.lvl_rows[l], d.lvl_cols[l], l, p.cells);
     // a level yields at most max(N + 3, 4 * nIni) keypoints: the quadtree stops within 3 nodes of its budget N, but
     // its very first subdivision already makes up to 4 * nIni nodes (nIni = aspect ratio of the level) however
     // small N is (DistributeOctTree, orbextractor.cpp:347-349, 394-470)
-    {
-      const int bw = d.lvl_cols[l] - 2 * (EDGE_THRESHOLD - 3), bh = d.lvl_rows[l] - 2 * (EDGE_THRESHOLD - 3);
-      const int n_ini = bh > 0 ? (int)std::lround((double)bw / (double)bh) : 0;
-      out_cap += std::max(d.feat[l] + 4, 4 * std::max(n_ini, 0) + 4);
-    }
-    if (d.feat[l] + 8 > SEL_CAP) {
-      ctx->set_error("ssx_orb: %d features on level %d exceed the octree node capacity", d.feat[l], l);
-      return SSX_ERR_UNSUPPORTED;
-    }
+    const int bw = d.lvl_cols[l] - 2 * (EDGE_THRESHOLD - 3), bh = d.lvl_rows[l] - 2 * (EDGE_THRESHOLD - 3);
+    const int n_ini = bh > 0 ? (int)std::lround((double)bw / (double)bh) : 0;
+    d.out_cap += std::max(d.feat[l] + 4, 4 * std::max(n_ini, 0) + 4);
   }
-  d.lvl_cell0[nlevels] = (int)cells.size();
-  for (int l = nlevels + 1; l <= MAX_LEVELS; ++l) d.lvl_cell0[l] = (int)cells.size();
-  d.n_cells = (int)cells.size();
-  d.pyr_bytes = (off + 255) & ~size_t(255);
-  d.out_cap = out_cap;
-  {
-    // octree node-table capacity: a round of phase 1 never ends above N nodes (it is only entered while
-    // size + 3 * expandable <= N) except the first one (<= 4 * nIni <= 256), phase 2 stops within N + 2
-    int maxN = 256;
-    for (int l = 0; l < (detect_only ? 1 : nlevels); ++l) maxN = std::max(maxN, d.feat[l]);
-    d.oct_ln = (maxN + 8 + 7) & ~7;
-    d.oct_max_cells = 1;
-    for (int l = 0; l < nlevels; ++l) d.oct_max_cells = std::max(d.oct_max_cells, d.lvl_cell0[l + 1] - d.lvl_cell0[l]);
-    // per-key state: in LDS for images up to ~0.6 Mpx (16384 candidates per level), else in global scratch
-    d.oct_global_keys = (size_t)d.lvl_rows[0] * d.lvl_cols[0] > 600000;
-    d.oct_cand_cap = d.oct_global_keys ? CAND_CAP_BIG : CAND_CAP;
-    const size_t key_lds = d.oct_global_keys ? 0 : 6 * (size_t)CAND_CAP;
-    if (4 * (size_t)(d.oct_max_cells + 8) + key_lds > (size_t)OCT_LDS_BUDGET) {
-      ctx->set_error("ssx_orb: %d grid cells on one level exceed the octree workgroup's LDS", d.oct_max_cells);
-      return SSX_ERR_UNSUPPORTED;
-    }
-    d.oct_global_tab = (size_t)OCT_NODE_BYTES * d.oct_ln + 4 * (size_t)(d.oct_max_cells + 8) + key_lds > (size_t)OCT_LDS_BUDGET;
-    d.oct_stride = ((d.oct_global_keys ? 6 * (size_t)CAND_CAP_BIG : 0) + (d.oct_global_tab ? (size_t)OCT_NODE_BYTES * d.oct_ln : 0) + 255) & ~size_t(255);
-    if (!d.oct_global_keys && !d.oct_global_tab) d.oct_stride = 0;
+  for (int l = d.nlevels; l <= MAX_LEVELS; ++l) d.lvl_cell0[l] = (int)p.cells.size();
+  d.n_cells = (int)p.cells.size();
+}
+
+// octree capacities: the node table, and what lives in LDS and what in global scratch
+ssx_status plan_octree(OrbPlan& p, char* err)
+{
+  OrbDev& d = p.dev;
+  // node-table capacity: a round of phase 1 never ends above N nodes (it is only entered while
+  // size + 3 * expandable <= N) except the first one (<= 4 * nIni <= 256), phase 2 stops within N + 2
+  int maxN = 256;
+  for (int l = 0; l < (d.detect_only ? 1 : d.nlevels); ++l) maxN = std::max(maxN, d.feat[l]);
+  d.oct_ln = (maxN + 8 + 7) & ~7;
+  d.oct_max_cells = 1;
+  for (int l = 0; l < d.nlevels; ++l) d.oct_max_cells = std::max(d.oct_max_cells, d.lvl_cell0[l + 1] - d.lvl_cell0[l]);
+  // per-key state: in LDS for images up to ~0.6 Mpx (16384 candidates per level), else in global scratch
+  d.oct_global_keys = (size_t)d.lvl_rows[0] * d.lvl_cols[0] > 600000;
+  d.oct_cand_cap = d.oct_global_keys ? CAND_CAP_BIG : CAND_CAP;
+  const size_t key_lds = d.oct_global_keys ? 0 : 6 * (size_t)CAND_CAP;
+  if (4 * (size_t)(d.oct_max_cells + 8) + key_lds > (size_t)OCT_LDS_BUDGET)
+    return plan_fail(err, SSX_ERR_UNSUPPORTED, "ssx_orb: %d grid cells on one level exceed the octree workgroup's LDS", d.oct_max_cells);
+  d.oct_global_tab = (size_t)OCT_NODE_BYTES * d.oct_ln + 4 * (size_t)(d.oct_max_cells + 8) + key_lds > (size_t)OCT_LDS_BUDGET;
+  d.oct_stride = ((d.oct_global_keys ? 6 * (size_t)CAND_CAP_BIG : 0) + (d.oct_global_tab ? (size_t)OCT_NODE_BYTES * d.oct_ln : 0) + 255) & ~size_t(255);
+  if (!d.oct_global_keys && !d.oct_global_tab) d.oct_stride = 0;
+  return SSX_OK;
+}
+
+// FAST and blur tiling: the LDS of one cell's wave, the blur's runs of tiles per level
+void plan_tiles(OrbPlan& p)
+{
+  OrbDev& d = p.dev;
+  int tile = 16, npx = 1, t0 = 0;
+  for (const Cell& c : p.cells) {
+    const int tw = ((c.x0 & 3) + c.w + 3) & ~3;
+    tile = std::max(tile, tw * (int)c.h);
+    npx = std::max(npx, std::max(c.w - 6, 0) * std::max(c.h - 6, 0));
   }
-  {
-    int tile = 16, npx = 1, t0 = 0;
-    for (const Cell& c : cells) {
-      const int tw = ((c.x0 & 3) + c.w + 3) & ~3;
-      tile = std::max(tile, tw * (int)c.h);
-      npx = std::max(npx, std::max(c.w - 6, 0) * std::max(c.h - 6, 0));
-    }
-    d.fast_tile_bytes = (tile + 15) & ~15;
-    d.fast_lds_per_wave = 2 * d.fast_tile_bytes + ((2 * npx + 15) & ~15);
-    d.gauss_run = I > 8 ? GT_RUN : 1;
-    for (int l = 0; l < nlevels; ++l) {
-      d.gauss_tile0[l] = t0;
-      t0 += ((((d.lvl_cols[l] + GT_W - 1) / GT_W) + d.gauss_run - 1) / d.gauss_run) * ((d.lvl_rows[l] + GT_H - 1) / GT_H);   // runs of tiles
-    }
-    for (int l = nlevels; l <= MAX_LEVELS; ++l) d.gauss_tile0[l] = t0;
+  d.fast_tile_bytes = (tile + 15) & ~15;
+  d.fast_lds_per_wave = 2 * d.fast_tile_bytes + ((2 * npx + 15) & ~15);
+  d.gauss_run = d.I > 8 ? GT_RUN : 1;
+  for (int l = 0; l < d.nlevels; ++l) {
+    d.gauss_tile0[l] = t0;
+    t0 += ((((d.lvl_cols[l] + GT_W - 1) / GT_W) + d.gauss_run - 1) / d.gauss_run) * ((d.lvl_rows[l] + GT_H - 1) / GT_H);   // runs of tiles
   }
-  // cv::resize INTER_LINEAR tables (resize.cpp: inv_scale = dsize/ssize, scale = 1/inv_scale; fx = (dx+0.5)*scale-0.5
-  // in float, sx = floor, clamps, cvRound of the weights * 2048): one (index, weight) pair row per destination
-  // column / row of every level.  Column tables are padded to a multiple of 4 with zero rows.
-  std::vector<ResizeQuad> xtab;
-  std::vector<uint2> ytab;
-  for (int l = 1; l < nlevels; ++l) {
+  for (int l = d.nlevels; l <= MAX_LEVELS; ++l) d.gauss_tile0[l] = t0;
+}
+
+// cv::resize INTER_LINEAR tables (resize.cpp: inv_scale = dsize/ssize, scale = 1/inv_scale; fx = (dx+0.5)*scale-0.5
+// in float, sx = floor, clamps, cvRound of the weights * 2048): one (index, weight) pair row per destination
+// column / row of every level.  Column tables are padded to a multiple of 4 with zero rows.
+ssx_status plan_resize(const PlanKey& k, OrbPlan& p, char* err)
+{
+  OrbDev& d = p.dev;
+  for (int l = 1; l < d.nlevels; ++l) {
     const int scols = d.lvl_cols[l - 1], srows = d.lvl_rows[l - 1], dcols = d.lvl_cols[l], drows = d.lvl_rows[l];
     const double scale_x = 1. / ((double)dcols / scols), scale_y = 1. / ((double)drows / srows);
-    d.rs_xoff[l] = (int)xtab.size();
-    d.rs_yoff[l] = (int)ytab.size();
+    d.rs_xoff[l] = (int)p.xtab.size();
+    d.rs_yoff[l] = (int)p.ytab.size();
     d.rs_wide8[l] = 1;
     for (int q = 0; 4 * q < dcols; ++q) {
       ResizeQuad rq{};
-      for (int k = 0; k < 4 && 4 * q + k < dcols; ++k) {
-        const int dx = 4 * q + k;
+      for (int j = 0; j < 4 && 4 * q + j < dcols; ++j) {
+        const int dx = 4 * q + j;
         float fx = (float)((dx + 0.5) * scale_x - 0.5);
         int sx = (int)std::floor(fx);
         fx -= sx;
@@ -1231,18 +1238,15 @@ ssx_status plan(ssx_ctx* ctx, int rows, int cols, int I, const ssx_orb_params& p
         if (sx >= scols - 1) { fx = 0; sx = scols - 1; }       // dx >= xmax: the right neighbour gets weight 0
         const int a0 = h_round((1.f - fx) * 2048), a1 = h_round(fx * 2048);
         const int sx1 = std::min(sx + 1, scols - 1);
-        if (k == 0) rq.s0 = (uint32_t)sx;
+        if (j == 0) rq.s0 = (uint32_t)sx;
         const int o0 = sx - (int)rq.s0, o1 = sx1 - (int)rq.s0;
         if (o1 > 7) d.rs_wide8[l] = 0;
-        if (o1 > 255) {
-          ctx->set_error("ssx_orb: pyramid scale factor %g is too large for the resize tables", (double)prm.scale_factor);
-          return SSX_ERR_UNSUPPORTED;
-        }
-        rq.sel0 |= (uint32_t)o0 << (8 * k);
-        rq.sel1 |= (uint32_t)o1 << (8 * k);
-        rq.w[k] = (uint32_t)a0 | ((uint32_t)a1 << 16);
+        if (o1 > 255) return plan_fail(err, SSX_ERR_UNSUPPORTED, "ssx_orb: pyramid scale factor %g is too large for the resize tables", (double)k.scale_factor);
+        rq.sel0 |= (uint32_t)o0 << (8 * j);
+        rq.sel1 |= (uint32_t)o1 << (8 * j);
+        rq.w[j] = (uint32_t)a0 | ((uint32_t)a1 << 16);
       }
-      xtab.push_back(rq);
+      p.xtab.push_back(rq);
     }
     for (int dy = 0; dy < drows; ++dy) {
       float fy = (float)((dy + 0.5) * scale_y - 0.5);
@@ -1250,63 +1254,101 @@ ssx_status plan(ssx_ctx* ctx, int rows, int cols, int I, const ssx_orb_params& p
       fy -= sy;
       const int b0 = h_round((1.f - fy) * 2048), b1 = h_round(fy * 2048);
       const int sy0 = std::min(std::max(sy, 0), srows - 1), sy1 = std::min(std::max(sy + 1, 0), srows - 1);
-      ytab.push_back(make_uint2((uint32_t)sy0 | ((uint32_t)sy1 << 16), (uint32_t)b0 | ((uint32_t)b1 << 16)));
+      p.ytab.push_back(make_uint2((uint32_t)sy0 | ((uint32_t)sy1 << 16), (uint32_t)b0 | ((uint32_t)b1 << 16)));
     }
   }
-  for (const Cell& c : cells)
-    if (c.w > ROI_MAX || c.h > ROI_MAX) {
-      ctx->set_error("ssx_orb: grid cell %dx%d exceeds the %d-px LDS tile", c.w, c.h, ROI_MAX);
-      return SSX_ERR_UNSUPPORTED;
-    }
+  return SSX_OK;
+}
+
+// Every buffer of the arena, stated ONCE: f(its pointer in OrbDev, its bytes), in memory order.
+template <class F> void for_each_buffer(OrbPlan& p, F&& f)
+{
+  OrbDev& d = p.dev;
+  const size_t I = (size_t)d.I, IL = I * d.nlevels, cells = (size_t)std::max(d.n_cells, 1);
+  f(d.cells, sizeof(Cell) * std::max<size_t>(p.cells.size(), 1));
+  f(d.rs_xtab, sizeof(ResizeQuad) * std::max<size_t>(p.xtab.size(), 1)); f(d.rs_ytab, sizeof(uint2) * std::max<size_t>(p.ytab.size(), 4));
+  f(d.pyr, d.pyr_bytes * I); f(d.maskpyr, d.has_mask ? d.pyr_bytes * I : 256); f(d.blur, d.pyr_bytes * I);
+  f(d.cell_count, sizeof(int) * I * cells); f(d.cell_cand, sizeof(uint32_t) * I * cells * CELL_CAP);
+  f(d.oct, std::max<size_t>(d.oct_stride * IL, 256)); f(d.lvl_ncand, sizeof(int) * IL); f(d.sel_count, sizeof(int) * IL);
+  f(d.sel, sizeof(uint32_t) * IL * SEL_CAP); f(d.sel_angle, sizeof(float) * IL * SEL_CAP);
+  f(d.status, sizeof(int) * I); f(d.out_kps, sizeof(ssx_keypoint) * I * d.out_cap); f(d.out_desc, (size_t)32 * I * d.out_cap); f(d.out_n, sizeof(int) * I);
+}
+
+void plan_arena(OrbPlan& p)
+{
   Layout lay;
-  const size_t o_cells = lay.take(sizeof(Cell) * std::max<size_t>(cells.size(), 1));
-  const size_t o_xtab = lay.take(sizeof(ResizeQuad) * std::max<size_t>(xtab.size(), 1));
-  const size_t o_ytab = lay.take(sizeof(uint2) * std::max<size_t>(ytab.size(), 4));
-  const size_t o_pyr = lay.take(d.pyr_bytes * I);
-  const size_t o_mask = lay.take(has_mask ? d.pyr_bytes * I : 256);
-  const size_t o_blur = lay.take(d.pyr_bytes * I);
-  const size_t o_ccount = lay.take(sizeof(int) * (size_t)I * std::max(d.n_cells, 1));
-  const size_t o_ccand = lay.take(sizeof(uint32_t) * (size_t)I * std::max(d.n_cells, 1) * CELL_CAP);
-  const size_t o_oct = lay.take(std::max<size_t>(d.oct_stride * (size_t)I * nlevels, 256));
-  const size_t o_ncand = lay.take(sizeof(int) * (size_t)I * nlevels);
-  const size_t o_selc = lay.take(sizeof(int) * (size_t)I * nlevels);
-  const size_t o_sel = lay.take(sizeof(uint32_t) * (size_t)I * nlevels * SEL_CAP);
-  const size_t o_ang = lay.take(sizeof(float) * (size_t)I * nlevels * SEL_CAP);
-  const size_t o_status = lay.take(sizeof(int) * (size_t)I);
-  const size_t o_kps = lay.take(sizeof(ssx_keypoint) * (size_t)I * out_cap);
-  const size_t o_desc = lay.take((size_t)32 * I * out_cap);
-  const size_t o_n = lay.take(sizeof(int) * (size_t)I);
-  SSX_HIP_TRY(ctx, ws->arena.reserve(lay.off));
-  char* base = ws->arena.as<char>();
-  d.cells = (const Cell*)(base + o_cells);
-  d.rs_xtab = (const ResizeQuad*)(base + o_xtab);
-  d.rs_ytab = (const uint2*)(base + o_ytab);
-  d.pyr = (uint8_t*)(base + o_pyr);
-  d.maskpyr = (uint8_t*)(base + o_mask);
-  d.blur = (uint8_t*)(base + o_blur);
-  d.cell_count = (int*)(base + o_ccount);
-  d.cell_cand = (uint32_t*)(base + o_ccand);
-  d.oct = (uint8_t*)(base + o_oct);
-  d.lvl_ncand = (int*)(base + o_ncand);
-  d.sel_count = (int*)(base + o_selc);
-  d.sel = (uint32_t*)(base + o_sel);
-  d.sel_angle = (float*)(base + o_ang);
-  d.status = (int*)(base + o_status);
-  d.out_kps = (uint8_t*)(base + o_kps);
-  d.out_desc = (uint8_t*)(base + o_desc);
-  d.out_n = (int*)(base + o_n);
-  if (!cells.empty())
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(base + o_cells, cells.data(), sizeof(Cell) * cells.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (!xtab.empty()) {
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(base + o_xtab, xtab.data(), sizeof(ResizeQuad) * xtab.size(), hipMemcpyHostToDevice, ctx->stream));
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(base + o_ytab, ytab.data(), sizeof(uint2) * ytab.size(), hipMemcpyHostToDevice, ctx->stream));
+  int n = 0;
+  for_each_buffer(p, [&](auto*&, size_t bytes) { p.bytes[n] = bytes; p.off[n++] = lay.take(bytes); });
+  p.arena_bytes = lay.off;
+}
+
+// The plan of a key.  Of several reasons to refuse a key the first in this order is reported: a level's budget, the octree's LDS,
+// the resize scale, a grid cell larger than the FAST tile.
+ssx_status build_plan(const PlanKey& k, OrbPlan& p, char* err)
+{
+  ssx_status st = plan_levels(k, p, err);
+  if (st != SSX_OK) return st;
+  plan_cells(p);
+  if ((st = plan_octree(p, err)) != SSX_OK) return st;
+  plan_tiles(p);
+  if ((st = plan_resize(k, p, err)) != SSX_OK) return st;
+  for (const Cell& c : p.cells)   // (never true: make_cells keeps a cell's ROI within 66 pixels; the parent's check, due for removal)
+    if (c.w > ROI_MAX || c.h > ROI_MAX) return plan_fail(err, SSX_ERR_UNSUPPORTED, "ssx_orb: grid cell %dx%d exceeds the %d-px LDS tile", c.w, c.h, ROI_MAX);
+  plan_arena(p);
+  return SSX_OK;
+}
+
+#ifndef SSX_NO_TEST_HOOKS
+// FNV-1a digests of a plan (ssx_orb_debug_plan): [0] every scalar of OrbDev, [1] the buffers' offsets and the arena's bytes, [2] the three tables
+void plan_digest(const OrbDev& d, const size_t* offs, int n_offs, const std::vector<Cell>& cells, const std::vector<ResizeQuad>& xtab,
+                 const std::vector<uint2>& ytab, uint64_t out[3])
+{
+  uint64_t h = 0;
+  auto eat = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } };
+#define SSX_EAT(x) eat(&d.x, sizeof(d.x))
+  h = 1469598103934665603ull;
+  SSX_EAT(I); SSX_EAT(nlevels); SSX_EAT(lvl_rows); SSX_EAT(lvl_cols); SSX_EAT(lvl_pitch); SSX_EAT(lvl_off); SSX_EAT(pyr_bytes); SSX_EAT(scale); SSX_EAT(feat);
+  SSX_EAT(lvl_cell0); SSX_EAT(n_cells); SSX_EAT(ini_th); SSX_EAT(min_th); SSX_EAT(has_mask); SSX_EAT(detect_only); SSX_EAT(out_cap); SSX_EAT(fast_tile_bytes);
+  SSX_EAT(fast_lds_per_wave); SSX_EAT(gauss_tile0); SSX_EAT(gauss_run); SSX_EAT(rs_xoff); SSX_EAT(rs_yoff); SSX_EAT(rs_wide8); SSX_EAT(oct_stride);
+  SSX_EAT(oct_max_cells); SSX_EAT(oct_cand_cap); SSX_EAT(oct_global_keys); SSX_EAT(oct_ln); SSX_EAT(oct_global_tab);
+#undef SSX_EAT
+  out[0] = h;
+  h = 1469598103934665603ull;
+  eat(offs, sizeof(size_t) * n_offs);
+  out[1] = h;
+  h = 1469598103934665603ull;
+  const size_t n[3] = {cells.size(), xtab.size(), ytab.size()};
+  eat(n, sizeof(n)); eat(cells.data(), sizeof(Cell) * n[0]); eat(xtab.data(), sizeof(ResizeQuad) * n[1]); eat(ytab.data(), sizeof(uint2) * n[2]);
+  out[2] = h;
+}
+#endif
+
+}  // namespace
+
+// check, cache hit, build the plan, synchronise, reserve, wire, upload the three tables, synchronise, commit
+ssx_status plan(ssx_ctx* ctx, int rows, int cols, int I, const ssx_orb_params& prm, bool has_mask, bool detect_only)
+{
+  OrbWorkspace* ws = get_ws(ctx);
+  const PlanKey key{rows, cols, I, detect_only ? 1 : prm.nlevels, prm.nfeatures, prm.ini_th_fast, prm.min_th_fast, has_mask, detect_only, prm.scale_factor};
+  char err[PLAN_ERR] = {0};
+  ssx_status st = check_key(key, prm, err);
+  if (st == SSX_OK && ws->planned && ws->key == key) return SSX_OK;
+  OrbPlan p;
+  if (st == SSX_OK) st = build_plan(key, p, err);
+  if (st != SSX_OK) { ctx->set_error("%s", err); return st; }   // (the previous plan stays in force)
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // re-planning invalidates buffers in flight
+  SSX_HIP_TRY(ctx, ws->arena.reserve(p.arena_bytes));
+  int n = 0;
+  for_each_buffer(p, [&](auto*& ptr, size_t) { wire(ptr, ws->arena.as<char>(), p.off[n++]); });
+  const OrbDev& d = p.dev;
+  if (!p.cells.empty()) SSX_HIP_TRY(ctx, hipMemcpyAsync((void*)d.cells, p.cells.data(), sizeof(Cell) * p.cells.size(), hipMemcpyHostToDevice, ctx->stream));
+  if (!p.xtab.empty()) {
+    SSX_HIP_TRY(ctx, hipMemcpyAsync((void*)d.rs_xtab, p.xtab.data(), sizeof(ResizeQuad) * p.xtab.size(), hipMemcpyHostToDevice, ctx->stream));
+    SSX_HIP_TRY(ctx, hipMemcpyAsync((void*)d.rs_ytab, p.ytab.data(), sizeof(uint2) * p.ytab.size(), hipMemcpyHostToDevice, ctx->stream));
   }
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // `cells` and the tables are pageable temporaries
-  ws->dev = d;
-  ws->rows = rows; ws->cols = cols; ws->I = I; ws->nlevels = nlevels; ws->nfeatures = prm.nfeatures;
-  ws->ini_th = prm.ini_th_fast; ws->min_th = prm.min_th_fast; ws->has_mask = has_mask; ws->detect_only = detect_only;
-  ws->scale_factor = prm.scale_factor;
-  ws->planned = true;
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the plan's tables are pageable temporaries
+  ws->dev = d; ws->key = key; ws->planned = true;
   return SSX_OK;
 }
 
@@ -1326,15 +1368,14 @@ static void launch_pyramid(ssx_ctx* ctx, const OrbDev& d, hipStream_t s, int ima
   }
 }
 
-ssx_status stage_level0(ssx_ctx* ctx, const uint8_t* imgs_dev, int stride, size_t img_bytes, const uint8_t* masks_dev,
-                        int mask_stride, size_t mask_bytes)
+ssx_status stage_level0(ssx_ctx* ctx, const uint8_t* imgs_dev, int stride, size_t img_bytes, const uint8_t* masks_dev, int mask_stride, size_t mask_bytes)
 {
   OrbWorkspace* ws = get_ws(ctx);
   const OrbDev& d = ws->dev;
   const dim3 grid((d.lvl_cols[0] + 511) / 512, (d.lvl_rows[0] + 3) / 4, d.I);
   SSX_PROF(ctx, KID_ORB_MISC, hipLaunchKernelGGL(k_copy_level0, grid, dim3(64, 4), 0, ctx->stream, imgs_dev, stride, img_bytes, d.pyr, d.pyr_bytes,
                      d.lvl_rows[0], d.lvl_cols[0], d.lvl_pitch[0]));
-  if (d.has_mask)
+  if (masks_dev)
     SSX_PROF(ctx, KID_ORB_MISC, hipLaunchKernelGGL(k_copy_level0, grid, dim3(64, 4), 0, ctx->stream, masks_dev, mask_stride, mask_bytes, d.maskpyr,
                        d.pyr_bytes, d.lvl_rows[0], d.lvl_cols[0], d.lvl_pitch[0]));
   SSX_HIP_TRY(ctx, hipGetLastError());
@@ -1402,9 +1443,22 @@ ssx_status run_pipeline(ssx_ctx* ctx)
 
 namespace {
 
-// upload one host image (+ optional mask) and run; shared by ssx_orb_detect / ssx_orb_extract
-ssx_status run_host_image(ssx_ctx* ctx, const uint8_t* img, int stride, int rows, int cols, const uint8_t* mask,
-                          int mask_stride, const ssx_orb_params& prm, bool detect_only)
+// A host image to level 0.  The caller has reserved ws->input and ws->stage and may have put arrays of its own behind the image's place
+// in the pinned block: the rows (and the mask's, right behind them) go in, the first `up_bytes` go up in ONE copy, level 0 is built.
+ssx_status host_image_to_level0(ssx_ctx* ctx, const uint8_t* img, int stride, int rows, int cols, const uint8_t* mask, int mask_stride, size_t up_bytes)
+{
+  OrbWorkspace* ws = get_ws(ctx);
+  const size_t bytes = (size_t)rows * cols;
+  uint8_t *hs = ws->stage.as<uint8_t>(), *in = ws->input.as<uint8_t>();
+  copy_rows(hs, cols, img, stride, rows, cols);
+  if (mask) copy_rows(hs + bytes, cols, mask, mask_stride, rows, cols);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(ws->input.p, hs, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+  return stage_level0(ctx, in, cols, bytes, mask ? in + bytes : nullptr, cols, bytes);
+}
+
+// upload one host image (+ optional mask), run, fetch the result; shared by ssx_orb_detect (no descriptors) / ssx_orb_extract
+ssx_status run_host_image(ssx_ctx* ctx, const uint8_t* img, int stride, int rows, int cols, const uint8_t* mask, int mask_stride, const ssx_orb_params& prm, bool detect_only,
+                          int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n)
 {
   ssx_status st = plan(ctx, rows, cols, 1, prm, mask != nullptr, detect_only);
   if (st != SSX_OK) return st;
@@ -1412,17 +1466,15 @@ ssx_status run_host_image(ssx_ctx* ctx, const uint8_t* img, int stride, int rows
   const size_t bytes = (size_t)rows * cols;
   SSX_HIP_TRY(ctx, ws->input.reserve(2 * bytes + 512));
   SSX_HIP_TRY(ctx, ws->stage.reserve(2 * bytes + 512));
-  uint8_t* hs = ws->stage.as<uint8_t>();
-  for (int y = 0; y < rows; ++y) memcpy(hs + (size_t)y * cols, img + (size_t)y * stride, cols);
-  if (mask)
-    for (int y = 0; y < rows; ++y) memcpy(hs + bytes + (size_t)y * cols, mask + (size_t)y * mask_stride, cols);
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(ws->input.p, hs, mask ? 2 * bytes : bytes, hipMemcpyHostToDevice, ctx->stream));
-  st = stage_level0(ctx, ws->input.as<uint8_t>(), cols, bytes, ws->input.as<uint8_t>() + bytes, cols, bytes);
+  st = host_image_to_level0(ctx, img, stride, rows, cols, mask, mask_stride, mask ? 2 * bytes : bytes);
+  if (st == SSX_OK) st = run_pipeline(ctx);
   if (st != SSX_OK) return st;
-  return run_pipeline(ctx);
+  return fetch_image(ctx, 0, cap, kps_out, desc_out, n);
 }
 
-ssx_status fetch_image_result(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n)
+}  // namespace
+
+ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n)
 {
   OrbWorkspace* ws = get_ws(ctx);
   const OrbDev& d = ws->dev;
@@ -1430,32 +1482,17 @@ ssx_status fetch_image_result(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kp
   SSX_HIP_TRY(ctx, hipMemcpyAsync(&hn[0], d.out_n + image, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipMemcpyAsync(&hn[1], d.status + image, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (hn[1] != 0) {
-    ctx->set_error("ssx_orb: internal capacity exceeded (status bits %d: 1=candidates 2=octree nodes 4=outputs)", hn[1]);
-    return SSX_ERR_CAPACITY;
-  }
+  if (hn[1] != 0) { ctx->set_error("ssx_orb: internal capacity exceeded (status bits %d: 1=candidates 2=octree nodes 4=outputs)", hn[1]); return SSX_ERR_CAPACITY; }
   *n = hn[0];
-  if (hn[0] > cap) {
-    ctx->set_error("ssx_orb: %d keypoints but capacity %d", hn[0], cap);
-    return SSX_ERR_CAPACITY;
-  }
+  if (hn[0] > cap) { ctx->set_error("ssx_orb: %d keypoints but capacity %d", hn[0], cap); return SSX_ERR_CAPACITY; }
   if (hn[0] > 0) {
     if (kps_out)
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(kps_out, d.out_kps + (size_t)image * d.out_cap * sizeof(ssx_keypoint),
-                                      sizeof(ssx_keypoint) * hn[0], hipMemcpyDeviceToHost, ctx->stream));
+      SSX_HIP_TRY(ctx, hipMemcpyAsync(kps_out, d.out_kps + (size_t)image * d.out_cap * sizeof(ssx_keypoint), sizeof(ssx_keypoint) * hn[0], hipMemcpyDeviceToHost, ctx->stream));
     if (desc_out && !d.detect_only)
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(desc_out, d.out_desc + (size_t)image * d.out_cap * 32, (size_t)32 * hn[0],
-                                      hipMemcpyDeviceToHost, ctx->stream));
+      SSX_HIP_TRY(ctx, hipMemcpyAsync(desc_out, d.out_desc + (size_t)image * d.out_cap * 32, (size_t)32 * hn[0], hipMemcpyDeviceToHost, ctx->stream));
     SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return SSX_OK;
-}
-
-}  // namespace
-
-ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n)
-{
-  return fetch_image_result(ctx, image, cap, kps_out, desc_out, n);
 }
 
 }  // namespace ssxorb
@@ -1481,9 +1518,7 @@ ssx_status ssx_orb_detect(ssx_ctx* ctx, const uint8_t* img, int32_t stride, int3
     ctx->set_error("ssx_orb_detect: stride smaller than the image width, negative capacity or no output array");
     return SSX_ERR_INVALID_ARG;
   }
-  ssx_status st = run_host_image(ctx, img, stride, rows, cols, mask, mask_stride, *prm, true);
-  if (st != SSX_OK) return st;
-  return fetch_image_result(ctx, 0, cap, kps_out, nullptr, n);
+  return run_host_image(ctx, img, stride, rows, cols, mask, mask_stride, *prm, true, cap, kps_out, nullptr, n);
 }
 
 // ORBextractor::Detect with the mask of FrontEnd::DetectFeatures given as its RECTANGLES (frontend.cpp:302-312: 255 everywhere,
@@ -1506,13 +1541,9 @@ ssx_status ssx_orb_detect_boxes(ssx_ctx* ctx, const uint8_t* img, int32_t stride
   const size_t bytes = (size_t)rows * cols, box_off = (bytes + 15) & ~size_t(15), box_bytes = sizeof(int32_t) * 4 * (size_t)n_boxes;
   SSX_HIP_TRY(ctx, ws->input.reserve(box_off + box_bytes + 512));
   SSX_HIP_TRY(ctx, ws->stage.reserve(box_off + box_bytes + 512));
-  uint8_t* hs = ws->stage.as<uint8_t>();
-  for (int y = 0; y < rows; ++y) memcpy(hs + (size_t)y * cols, img + (size_t)y * stride, cols);
-  if (n_boxes) memcpy(hs + box_off, boxes_xyxy, box_bytes);
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(ws->input.p, hs, box_off + box_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const dim3 grid((d.lvl_cols[0] + 511) / 512, (d.lvl_rows[0] + 3) / 4, 1);
-  SSX_PROF(ctx, KID_ORB_MISC, hipLaunchKernelGGL(k_copy_level0, grid, dim3(64, 4), 0, ctx->stream, ws->input.as<uint8_t>(), cols, bytes, d.pyr, d.pyr_bytes,
-                     d.lvl_rows[0], d.lvl_cols[0], d.lvl_pitch[0]));
+  if (n_boxes) memcpy(ws->stage.as<uint8_t>() + box_off, boxes_xyxy, box_bytes);
+  st = host_image_to_level0(ctx, img, stride, rows, cols, nullptr, 0, box_off + box_bytes);   // (the mask is rasterised on the device, below)
+  if (st != SSX_OK) return st;
   SSX_HIP_TRY(ctx, hipMemsetAsync(d.maskpyr + d.lvl_off[0], 255, (size_t)d.lvl_pitch[0] * d.lvl_rows[0], ctx->stream));
   if (n_boxes)
     SSX_PROF(ctx, KID_ORB_MISC, hipLaunchKernelGGL(k_mask_boxes, dim3(n_boxes), dim3(64), 0, ctx->stream, reinterpret_cast<const int4*>(ws->input.as<uint8_t>() + box_off),
@@ -1520,7 +1551,7 @@ ssx_status ssx_orb_detect_boxes(ssx_ctx* ctx, const uint8_t* img, int32_t stride
   SSX_HIP_TRY(ctx, hipGetLastError());
   st = run_pipeline(ctx);
   if (st != SSX_OK) return st;
-  return fetch_image_result(ctx, 0, cap, kps_out, nullptr, n);
+  return fetch_image(ctx, 0, cap, kps_out, nullptr, n);
 }
 
 // ssx_orb_detect_boxes for n images in ONE call (one keyframe of each of n streams: FrontEnd::DetectFeatures, frontend.cpp:302-344):
@@ -1546,9 +1577,7 @@ ssx_status ssx_orb_detect_boxes_batch(ssx_ctx* ctx, int32_t n, const ssx_orb_det
   OrbWorkspace* ws = get_ws(ctx);
   int cap_I = 1;
   while (cap_I < n) cap_I *= 2;
-  if (ws->planned && ws->rows == rows && ws->cols == cols && ws->detect_only && ws->has_mask && ws->nfeatures == prm->nfeatures && ws->ini_th == prm->ini_th_fast &&
-      ws->min_th == prm->min_th_fast && ws->I > cap_I)
-    cap_I = ws->I;                                                   // (a smaller batch runs on the larger plan)
+  if (ws->planned && ws->key.detects_masked(rows, cols, *prm, cap_I)) cap_I = ws->key.I;   // (a smaller batch runs on the larger plan)
   ssx_status st = plan(ctx, rows, cols, cap_I, *prm, true, true);
   if (st != SSX_OK) return st;
   struct RestoreI { OrbWorkspace* w; int I; ~RestoreI() { w->dev.I = I; } } restore{ws, ws->dev.I};
@@ -1575,8 +1604,7 @@ ssx_status ssx_orb_detect_boxes_batch(ssx_ctx* ctx, int32_t n, const ssx_orb_det
     const ssx_orb_detect_job& q = jobs[j];
     if (images_on_device) ptrs[j] = q.img;
     else {
-      uint8_t* dst = reinterpret_cast<uint8_t*>(hs + o_img) + bytes * (size_t)j;
-      for (int y = 0; y < rows; ++y) memcpy(dst + (size_t)y * cols, q.img + (size_t)y * q.stride, cols);
+      copy_rows(reinterpret_cast<uint8_t*>(hs + o_img) + bytes * (size_t)j, cols, q.img, q.stride, rows, cols);
       ptrs[j] = reinterpret_cast<const uint8_t*>(db + o_img) + bytes * (size_t)j;
     }
     if (q.n_boxes) memcpy(hbox + 4 * b0, q.boxes_xyxy, sizeof(int32_t) * 4 * (size_t)q.n_boxes);
@@ -1637,9 +1665,7 @@ ssx_status ssx_orb_extract(ssx_ctx* ctx, const uint8_t* img, int32_t stride, int
     ctx->set_error("ssx_orb_extract: stride smaller than the image width, negative capacity or no output arrays");
     return SSX_ERR_INVALID_ARG;
   }
-  ssx_status st = run_host_image(ctx, img, stride, rows, cols, mask, mask_stride, *prm, false);
-  if (st != SSX_OK) return st;
-  return fetch_image_result(ctx, 0, cap, kps_out, desc_out, n);
+  return run_host_image(ctx, img, stride, rows, cols, mask, mask_stride, *prm, false, cap, kps_out, desc_out, n);
 }
 
 ssx_status ssx_orb_describe_at(ssx_ctx* ctx, const uint8_t* img, int32_t stride, int32_t rows, int32_t cols,
@@ -1657,37 +1683,33 @@ ssx_status ssx_orb_describe_at(ssx_ctx* ctx, const uint8_t* img, int32_t stride,
   if (st != SSX_OK) return st;
   OrbWorkspace* ws = get_ws(ctx);
   const OrbDev& d = ws->dev;
-  const size_t bytes = (size_t)rows * cols;
-  Layout lay;
-  const size_t o_img = lay.take(bytes);
-  const size_t o_in = lay.take(sizeof(ssx_keypoint) * (size_t)n_in);
-  const size_t in_bytes = lay.off;
-  const size_t o_out = lay.take(sizeof(ssx_keypoint) * (size_t)n_in);
-  const size_t o_desc = lay.take((size_t)32 * n_in);
-  const size_t o_keep = lay.take((size_t)n_in);
-  SSX_HIP_TRY(ctx, ws->input.reserve(lay.off));
-  SSX_HIP_TRY(ctx, ws->stage.reserve(lay.off));
-  char* hs = ws->stage.as<char>();
-  for (int y = 0; y < rows; ++y) memcpy(hs + o_img + (size_t)y * cols, img + (size_t)y * stride, cols);
-  memcpy(hs + o_in, kps_in, sizeof(ssx_keypoint) * n_in);
+  // one block, on the device and (pinned) on the host: [image | keypoints in] go up, [keypoints out | descriptors | keep flags] come back
+  DescribeAt a;
+  const uint8_t* image;
+  auto buffers = [&](auto&& f) {
+    f(image, (size_t)rows * cols); f(a.in, sizeof(ssx_keypoint) * (size_t)n_in);
+    f(a.out, sizeof(ssx_keypoint) * (size_t)n_in); f(a.desc, (size_t)32 * n_in); f(a.keep, (size_t)n_in);
+  };
+  const size_t total = carve(nullptr, buffers);
+  SSX_HIP_TRY(ctx, ws->input.reserve(total));
+  SSX_HIP_TRY(ctx, ws->stage.reserve(total));
   char* base = ws->input.as<char>();
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  st = stage_level0(ctx, (const uint8_t*)(base + o_img), cols, bytes, nullptr, 0, 0);
+  carve(base, buffers); a.n_in = n_in;
+  auto host = [&](const void* dev) { return ws->stage.as<char>() + ((const char*)dev - base); };   // a buffer's place in the pinned block
+  memcpy(host(a.in), kps_in, sizeof(ssx_keypoint) * n_in);
+  st = host_image_to_level0(ctx, img, stride, rows, cols, nullptr, 0, (const char*)a.out - base);
   if (st != SSX_OK) return st;
   hipStream_t s = ctx->stream;
   launch_pyramid(ctx, d, s, 1);           // ComputePyramid(image), orbextractor.cpp:1012-1027
   SSX_PROF(ctx, KID_ORB_GAUSS, hipLaunchKernelGGL(k_gauss7, dim3(d.gauss_tile0[d.nlevels], 1), dim3(256), 0, s, d));
-  DescribeAt a;
-  a.in = (const ssx_keypoint*)(base + o_in); a.out = (ssx_keypoint*)(base + o_out); a.desc = (uint8_t*)(base + o_desc);
-  a.keep = (uint8_t*)(base + o_keep); a.n_in = n_in;
   SSX_PROF(ctx, KID_ORB_BRIEF, hipLaunchKernelGGL(k_describe_at, dim3((n_in + 3) / 4), dim3(256), 0, s, d, a));
   SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_out, base + o_out, lay.off - o_out, hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(host(a.out), a.out, total - ((const char*)a.out - base), hipMemcpyDeviceToHost, s));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
   // order-preserving compaction of the kept keypoints (out_keypoints.push_back order, :893)
-  const ssx_keypoint* ok = (const ssx_keypoint*)(hs + o_out);
-  const uint8_t* od = (const uint8_t*)(hs + o_desc);
-  const uint8_t* keep = (const uint8_t*)(hs + o_keep);
+  const ssx_keypoint* ok = (const ssx_keypoint*)host(a.out);
+  const uint8_t* od = (const uint8_t*)host(a.desc);
+  const uint8_t* keep = (const uint8_t*)host(a.keep);
   int m = 0;
   for (int i = 0; i < n_in; ++i) {
     if (!keep[i]) continue;
@@ -1699,7 +1721,34 @@ ssx_status ssx_orb_describe_at(ssx_ctx* ctx, const uint8_t* img, int32_t stride,
   return SSX_OK;
 }
 
-#ifndef SSX_NO_TEST_HOOKS   // kernel taps of the parity tests (include/ssx_test_hooks.h)
+#ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h
+// test / tools hook (no GPU needed): the plan of a key as plan() would build it, digested
+ssx_status ssx_orb_debug_plan(int32_t rows, int32_t cols, int32_t images, const ssx_orb_params* prm, int32_t has_mask, int32_t detect_only,
+                              int32_t unchecked, ssx_orb_plan_info* out)
+{
+  if (!prm || !out) return SSX_ERR_INVALID_ARG;
+  *out = ssx_orb_plan_info{};
+  const PlanKey key{rows, cols, images, detect_only ? 1 : prm->nlevels, prm->nfeatures, prm->ini_th_fast, prm->min_th_fast, has_mask != 0, detect_only != 0, prm->scale_factor};
+  static_assert(sizeof(out->error) == PLAN_ERR, "ssx_orb_plan_info::error holds the plan's error text");
+  OrbPlan p;
+  // (unchecked: the argument checks skipped, but for the number of levels, which sizes arrays)
+  ssx_status st = unchecked && key.nlevels >= 1 && key.nlevels <= MAX_LEVELS ? SSX_OK : check_key(key, *prm, out->error);
+  if (st == SSX_OK) st = build_plan(key, p, out->error);
+  out->status = st;
+  if (st != SSX_OK) return st;
+  const OrbDev& d = p.dev;
+  size_t offs[ARENA_BUFS + 1];
+  for (int b = 0; b < ARENA_BUFS; ++b) { out->buf_off[b] = offs[b] = p.off[b]; out->buf_bytes[b] = p.bytes[b]; }
+  out->n_buffers = ARENA_BUFS;
+  out->arena_bytes = offs[ARENA_BUFS] = p.arena_bytes;
+  out->nlevels = d.nlevels; out->out_cap = d.out_cap;
+  memcpy(out->lvl_rows, d.lvl_rows, sizeof(d.lvl_rows)); memcpy(out->lvl_cols, d.lvl_cols, sizeof(d.lvl_cols)); memcpy(out->feat, d.feat, sizeof(d.feat));
+  memcpy(out->lvl_cell0, d.lvl_cell0, sizeof(d.lvl_cell0)); memcpy(out->gauss_tile0, d.gauss_tile0, sizeof(d.gauss_tile0));
+  plan_digest(d, offs, ARENA_BUFS + 1, p.cells, p.xtab, p.ytab, out->digest);
+  return SSX_OK;
+}
+
+// kernel taps of the parity tests
 ssx_status ssx_orb_stage_level(ssx_ctx* ctx, int32_t image, int32_t level, int32_t blurred, uint8_t* out,
                                int32_t out_cap, int32_t* rows, int32_t* cols)
 {

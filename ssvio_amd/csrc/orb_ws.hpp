@@ -80,57 +80,78 @@ struct OrbDev {
   int* out_n;                    // [I]
 };
 
+// what a plan depends on: a call whose key equals the workspace's runs on the plan it finds
+struct PlanKey {
+  int rows = 0, cols = 0, I = 0, nlevels = 0, nfeatures = 0, ini_th = 0, min_th = 0, has_mask = 0, detect_only = 0;   // nlevels AS PLANNED: 1 for ORBextractor::Detect
+  float scale_factor = 0.f;
+  bool operator==(const PlanKey& o) const {
+    return rows == o.rows && cols == o.cols && I == o.I && nlevels == o.nlevels && nfeatures == o.nfeatures && ini_th == o.ini_th && min_th == o.min_th &&
+           has_mask == o.has_mask && detect_only == o.detect_only && scale_factor == o.scale_factor;
+  }
+  // a detect-with-mask plan of this shape and these thresholds for at least n images (ssx_orb_detect_boxes_batch: a smaller batch runs on it)
+  bool detects_masked(int rows_, int cols_, const ssx_orb_params& prm, int n) const {
+    return detect_only && has_mask && rows == rows_ && cols == cols_ && nfeatures == prm.nfeatures && ini_th == prm.ini_th_fast && min_th == prm.min_th_fast && I >= n;
+  }
+};
+
+// a FIFO of at most two slots, 0 and 1: the oldest entry sits in `first`, the next push goes to the other one (while count < 2)
+struct Ring2 {
+  int first = 0, count = 0;
+  int push_slot() const { return (first + count) & 1; }
+  int pop() { const int s = first; first ^= 1; --count; return s; }
+};
+
 void launch_octree(const OrbDev& o, hipStream_t s);   // octree.hip
 
 }  // namespace ssxorb
 
-// host-side plan + buffers (one per ctx; re-planned when the geometry / parameters change)
+// host-side plan + buffers (one per ctx; re-planned when the key changes)
 struct OrbWorkspace {
   DevBuf arena;        // pyramids, candidates, octree scratch, outputs
   DevBuf input;        // uploaded host images (host-pointer entry points)
   DevBuf stereo;       // match / triangulation results of the batch entry points
   HostBuf stage;       // pinned staging
   HostBuf fetch;       // pinned: everything ssx_stereo_frame returns, fetched with ONE synchronisation
-  ssxorb::OrbDev dev{};
-  // plan key
-  int rows = 0, cols = 0, I = 0, nlevels = 0, nfeatures = 0, ini_th = 0, min_th = 0, has_mask = 0, detect_only = 0;
-  float scale_factor = 0.f;
-  bool planned = false;
-  // batch state (ssx_stereo_batch_dev / _enqueue / _fetch)
+  ssxorb::PlanKey key; ssxorb::OrbDev dev{}; bool planned = false;   // the plan in force, and what it was made for
+  // batch parameters (ssx_stereo_batch_dev / _run -> _enqueue / _fetch)
   const uint8_t* batch_imgs = nullptr;
   int batch_pairs = 0, batch_stride = 0;
   ssx_orb_params batch_orb{};
   ssx_match_params batch_mp{};
   ssx_stereo_rig batch_rig{};
   // stereo result views inside `stereo`
-  int* match_idx = nullptr;
-  int* match_dist = nullptr;
+  int *match_idx = nullptr, *match_dist = nullptr, *pair_counts = nullptr;   // pair_counts: [pairs][4]
   double* xyz = nullptr;
   uint8_t* tri_ok = nullptr;
-  int* pair_counts = nullptr;   // [pairs][4]
-  // streaming batches (ssx_stereo_batch_host): two device buffers filled from the host on a copy stream of their own, so that
-  // batch k + 1 crosses PCIe while batch k is being processed
-  DevBuf ingest[2];
+  // upload ring (ssx_stereo_batch_upload -> _run): two device buffers filled from the host on a copy stream of their own (batch k + 1 crosses PCIe while
+  // batch k is processed).  Per slot: the buffer, the events "uploaded" and "level 0 of the batch that used the buffer is staged" (pending?), the batch's shape
+  struct Upload { DevBuf buf; hipEvent_t ev_up = nullptr, ev_free = nullptr; bool free_pending = false; int pairs = 0, stride = 0, rows = 0, cols = 0; } up[2];
+  ssxorb::Ring2 up_ring;        // uploaded batches waiting for ssx_stereo_batch_run
   hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-  bool free_pending[2] = {false, false};
-  int up_first = 0, up_count = 0;  // uploaded batches waiting for ssx_stereo_batch_run: buffers up_first, up_first ^ 1
-  int up_shape[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // pairs, stride, rows, cols of an uploaded batch
-  HostBuf counts_pinned;        // [pairs][4] counts + [2 pairs] status words of the last enqueued batch
-  hipEvent_t ev_counts[2] = {nullptr, nullptr};   // per run batch: its counts have reached counts_pinned
-  int cnt_first = 0, cnt_count = 0, cnt_pairs[2] = {0, 0};
-  ssx_status cnt_fail[2] = {SSX_OK, SSX_OK};           // a run that failed after consuming its batch still owns a slot of the FIFO
+  // counts ring (ssx_stereo_batch_run -> _counts).  Per slot: the event "the counts are in counts_pinned", the batch size, the run's status (a failed run owns a slot too)
+  struct Counts { hipEvent_t ev = nullptr; int pairs = 0; ssx_status fail = SSX_OK; } cnt[2];
+  ssxorb::Ring2 cnt_ring;       // batches that were run and not collected yet
+  HostBuf counts_pinned;        // per slot: [pairs][4] counts + [2 pairs] status words
 };
 
 namespace ssxorb {
 OrbWorkspace* get_ws(ssx_ctx* ctx);
-// plan (allocate + upload cell tables) for I images of rows x cols; returns SSX_OK or an error
+// plan (allocate + upload the cell and resize tables) for I images of rows x cols; returns SSX_OK or an error
 ssx_status plan(ssx_ctx* ctx, int rows, int cols, int I, const ssx_orb_params& prm, bool has_mask, bool detect_only);
+// stage level 0 from a device / pinned buffer [I][rows][stride]; the masks likewise when a mask buffer is given
+ssx_status stage_level0(ssx_ctx* ctx, const uint8_t* imgs_dev, int stride, size_t img_bytes, const uint8_t* masks_dev, int mask_stride, size_t mask_bytes);
 // run the extraction pipeline on level-0 images already placed in the pyramid buffers
 ssx_status run_pipeline(ssx_ctx* ctx);
-// stage level 0 from a device/host-layout buffer [I][rows][stride]
 // download the keypoints / descriptors of one image of the last run (synchronises the stream)
 ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n);
-ssx_status stage_level0(ssx_ctx* ctx, const uint8_t* imgs_dev, int stride, size_t img_bytes, const uint8_t* masks_dev,
-                        int mask_stride, size_t mask_bytes);
+// a buffer's pointer, whatever its type, from the base of its block and its offset
+template <class T> void wire(T*& ptr, char* base, size_t off) { ptr = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off); }
+// The buffers of one block, each stated ONCE: `each(f)` calls f(pointer, bytes) for every buffer in memory order.  Wires the pointers
+// from `base` (null: offsets only, to size the block before it is reserved) and returns the bytes the block takes.
+template <class Each> size_t carve(char* base, Each&& each) { Layout lay; each([&](auto*& ptr, size_t bytes) { wire(ptr, base, lay.take(bytes)); }); return lay.off; }
+// rows of `cols` bytes from the caller's pitch to the staging copy's
+inline void copy_rows(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t src_pitch, int rows, int cols)
+{
+  for (int y = 0; y < rows; ++y) memcpy(dst + (size_t)y * dst_pitch, src + (size_t)y * src_pitch, cols);
+}
 }  // namespace ssxorb

@@ -393,28 +393,22 @@ void fill_scale(MatchDev& m)
 }
 
 // allocate the stereo result buffers for `pairs` pairs and build the device view
-ssx_status make_match_dev(ssx_ctx* ctx, int pairs, const ssx_match_params& mp, const ssx_stereo_rig& rig, const double* T_wc,
-                          MatchDev& m)
+ssx_status make_match_dev(ssx_ctx* ctx, int pairs, const ssx_match_params& mp, const ssx_stereo_rig& rig, const double* T_wc, MatchDev& m)
 {
   OrbWorkspace* ws = get_ws(ctx);
   const OrbDev& d = ws->dev;
   if (d.lvl_rows[0] + 2 > BUCKET_ROWS_MAX) { ctx->set_error("ssx_stereo: image too tall for the row buckets"); return SSX_ERR_UNSUPPORTED; }
   if (d.out_cap > 65535) { ctx->set_error("ssx_stereo: more than 65535 keypoints per image"); return SSX_ERR_UNSUPPORTED; }
-  Layout lay;
-  const size_t o_rp = lay.take(sizeof(int) * (size_t)pairs * (d.lvl_rows[0] + 2));
-  const size_t o_sorted = lay.take(sizeof(int) * (size_t)pairs * d.out_cap);
-  const size_t o_idx = lay.take(sizeof(int) * (size_t)pairs * d.out_cap);
-  const size_t o_dist = lay.take(sizeof(int) * (size_t)pairs * d.out_cap);
-  const size_t o_xyz = lay.take(sizeof(double) * 3 * (size_t)pairs * d.out_cap);
-  const size_t o_ok = lay.take((size_t)pairs * d.out_cap);
-  const size_t o_cnt = lay.take(sizeof(int) * 4 * (size_t)pairs);
-  SSX_HIP_TRY(ctx, ws->stereo.reserve(lay.off));
-  char* base = ws->stereo.as<char>();
   m.pairs = pairs; m.out_cap = d.out_cap; m.rows = d.lvl_rows[0];
   m.kps = reinterpret_cast<const ssx_keypoint*>(d.out_kps); m.desc = d.out_desc; m.n = d.out_n;
-  m.row_ptr = (int*)(base + o_rp); m.sorted = (int*)(base + o_sorted);
-  m.match_idx = (int*)(base + o_idx); m.match_dist = (int*)(base + o_dist);
-  m.xyz = (double*)(base + o_xyz); m.ok = (uint8_t*)(base + o_ok); m.counts = (int*)(base + o_cnt);
+  const size_t n = (size_t)pairs * d.out_cap;
+  auto buffers = [&](auto&& f) {
+    f(m.row_ptr, sizeof(int) * (size_t)pairs * (d.lvl_rows[0] + 2));
+    f(m.sorted, sizeof(int) * n); f(m.match_idx, sizeof(int) * n); f(m.match_dist, sizeof(int) * n);
+    f(m.xyz, sizeof(double) * 3 * n); f(m.ok, n); f(m.counts, sizeof(int) * 4 * (size_t)pairs);
+  };
+  SSX_HIP_TRY(ctx, ws->stereo.reserve(carve(nullptr, buffers)));
+  carve(ws->stereo.as<char>(), buffers);
   m.mp = mp; m.rig = rig;
   m.has_T = T_wc ? 1 : 0;
   for (int i = 0; i < 7; ++i) m.T_wc[i] = T_wc ? T_wc[i] : (i == 3 ? 1.0 : 0.0);
@@ -426,20 +420,26 @@ ssx_status make_match_dev(ssx_ctx* ctx, int pairs, const ssx_match_params& mp, c
 ssx_status launch_stereo(ssx_ctx* ctx, const MatchDev& m, char* frame_host = nullptr, const FrameSlots* slots = nullptr)
 {
   hipStream_t s = ctx->stream;
-  if (frame_host) {
-    SSX_PROF(ctx, KID_ST_BUCKET, hipLaunchKernelGGL(k_row_bucket, dim3(m.pairs), dim3(1024), 0, s, m));
-    SSX_PROF(ctx, KID_ST_MATCH, hipLaunchKernelGGL(k_match, dim3((m.out_cap + 3) / 4, m.pairs), dim3(256), 0, s, m));
-    SSX_PROF(ctx, KID_ST_TRIANGULATE, hipLaunchKernelGGL(k_triangulate_matches, dim3((m.out_cap + 255) / 256, m.pairs), dim3(256), 0, s, m));
-    SSX_PROF(ctx, KID_ST_MISC, hipLaunchKernelGGL(k_pack_frame, dim3(1 + 128), dim3(256), 0, s, m, get_ws(ctx)->dev.status, frame_host, *slots));
-    SSX_HIP_TRY(ctx, hipGetLastError());
-    return SSX_OK;
-  }
   SSX_PROF(ctx, KID_ST_BUCKET, hipLaunchKernelGGL(k_row_bucket, dim3(m.pairs), dim3(1024), 0, s, m));
   SSX_PROF(ctx, KID_ST_MATCH, hipLaunchKernelGGL(k_match, dim3((m.out_cap + 3) / 4, m.pairs), dim3(256), 0, s, m));
   SSX_PROF(ctx, KID_ST_TRIANGULATE, hipLaunchKernelGGL(k_triangulate_matches, dim3((m.out_cap + 255) / 256, m.pairs), dim3(256), 0, s, m));
-  SSX_PROF(ctx, KID_ST_MISC, hipLaunchKernelGGL(k_pair_counts, dim3(m.pairs), dim3(256), 0, s, m));
+  if (frame_host)   // a single frame: the counts and every result array of pair 0 go straight into pinned memory
+    SSX_PROF(ctx, KID_ST_MISC, hipLaunchKernelGGL(k_pack_frame, dim3(1 + 128), dim3(256), 0, s, m, get_ws(ctx)->dev.status, frame_host, *slots));
+  else
+    SSX_PROF(ctx, KID_ST_MISC, hipLaunchKernelGGL(k_pair_counts, dim3(m.pairs), dim3(256), 0, s, m));
   SSX_HIP_TRY(ctx, hipGetLastError());
   return SSX_OK;
+}
+
+// extraction, matching and triangulation of a batch whose level 0 is staged
+ssx_status run_batch(ssx_ctx* ctx, int pairs, const ssx_match_params& mp, const ssx_stereo_rig& rig)
+{
+  ssx_status st = run_pipeline(ctx);
+  if (st != SSX_OK) return st;
+  MatchDev m{};
+  st = make_match_dev(ctx, pairs, mp, rig, nullptr, m);
+  if (st != SSX_OK) return st;
+  return launch_stereo(ctx, m);
 }
 
 ssx_status fetch_pair(ssx_ctx* ctx, int pair, ssx_stereo_frame_out* out)
@@ -531,31 +531,24 @@ ssx_status ssx_stereo_match(ssx_ctx* ctx, const ssx_keypoint* kL, const uint8_t*
   for (int j = 0; j < nR; ++j) ymax = std::max(ymax, kR[j].y);
   for (int i = 0; i < nL; ++i) ymax = std::max(ymax, kL[i].y);
   const int rows = std::min((int)ymax + 2, BUCKET_ROWS_MAX - 2);
-  Layout lay;
-  const size_t o_k = lay.take(sizeof(ssx_keypoint) * 2 * (size_t)cap);
-  const size_t o_d = lay.take((size_t)64 * cap);
-  const size_t o_n = lay.take(sizeof(int) * 2);
-  const size_t in_bytes = lay.off;
-  const size_t o_rp = lay.take(sizeof(int) * (rows + 2));
-  const size_t o_sorted = lay.take(sizeof(int) * (size_t)cap);
-  const size_t o_idx = lay.take(sizeof(int) * (size_t)cap);
-  const size_t o_dist = lay.take(sizeof(int) * (size_t)cap);
-  SSX_HIP_TRY(ctx, ws->input.reserve(lay.off));
-  SSX_HIP_TRY(ctx, ws->stage.reserve(lay.off));
-  char* hs = ws->stage.as<char>();
-  memcpy(hs + o_k, kL, sizeof(ssx_keypoint) * nL);
-  if (nR) memcpy(hs + o_k + sizeof(ssx_keypoint) * cap, kR, sizeof(ssx_keypoint) * nR);
-  memcpy(hs + o_d, dL, (size_t)32 * nL);
-  if (nR) memcpy(hs + o_d + (size_t)32 * cap, dR, (size_t)32 * nR);
-  int nn[2] = {nL, nR};
-  memcpy(hs + o_n, nn, sizeof(nn));
+  // one block, on the device and (pinned) on the host: [keypoints | descriptors | counts] go up, the rest is scratch and results
+  MatchDev m{}; m.pairs = 1; m.out_cap = cap; m.rows = rows;
+  auto buffers = [&](auto&& f) {
+    f(m.kps, sizeof(ssx_keypoint) * 2 * (size_t)cap); f(m.desc, (size_t)64 * cap); f(m.n, sizeof(int) * 2);
+    f(m.row_ptr, sizeof(int) * (rows + 2)); f(m.sorted, sizeof(int) * (size_t)cap); f(m.match_idx, sizeof(int) * (size_t)cap); f(m.match_dist, sizeof(int) * (size_t)cap);
+  };
+  const size_t total = carve(nullptr, buffers);
+  SSX_HIP_TRY(ctx, ws->input.reserve(total));
+  SSX_HIP_TRY(ctx, ws->stage.reserve(total));
   char* base = ws->input.as<char>();
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  MatchDev m{};
-  m.pairs = 1; m.out_cap = cap; m.rows = rows;
-  m.kps = (const ssx_keypoint*)(base + o_k); m.desc = (const uint8_t*)(base + o_d); m.n = (const int*)(base + o_n);
-  m.row_ptr = (int*)(base + o_rp); m.sorted = (int*)(base + o_sorted);
-  m.match_idx = (int*)(base + o_idx); m.match_dist = (int*)(base + o_dist);
+  carve(base, buffers);
+  auto host = [&](const void* dev) { return ws->stage.as<char>() + ((const char*)dev - base); };   // a buffer's place in the pinned block
+  memcpy(host(m.kps), kL, sizeof(ssx_keypoint) * nL);
+  if (nR) memcpy(host(m.kps + cap), kR, sizeof(ssx_keypoint) * nR);
+  memcpy(host(m.desc), dL, (size_t)32 * nL);
+  if (nR) memcpy(host(m.desc + (size_t)32 * cap), dR, (size_t)32 * nR);
+  const int nn[2] = {nL, nR}; memcpy(host(m.n), nn, sizeof(nn));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, host(base), (const char*)m.row_ptr - base, hipMemcpyHostToDevice, ctx->stream));
   m.mp = *prm;
   fill_scale(m);
   SSX_PROF(ctx, KID_ST_BUCKET, hipLaunchKernelGGL(k_row_bucket, dim3(1), dim3(1024), 0, ctx->stream, m));
@@ -685,10 +678,8 @@ ssx_status ssx_stereo_frame(ssx_ctx* ctx, const uint8_t* imgL, const uint8_t* im
   const size_t bytes = (size_t)rows * pitch;
   SSX_HIP_TRY(ctx, ws->stage.reserve(2 * bytes + 512));
   uint8_t* hs = ws->stage.as<uint8_t>();
-  for (int y = 0; y < rows; ++y) {
-    memcpy(hs + (size_t)y * pitch, imgL + (size_t)y * stride, cols);
-    memcpy(hs + bytes + (size_t)y * pitch, imgR + (size_t)y * stride, cols);
-  }
+  copy_rows(hs, pitch, imgL, stride, rows, cols);
+  copy_rows(hs + bytes, pitch, imgR, stride, rows, cols);
   // level 0 is built straight from the pinned staging copy (k_copy_level0 reads it over PCIe once): no separate upload
   st = stage_level0(ctx, hs, pitch, bytes, nullptr, 0, 0);
   if (st != SSX_OK) return st;
@@ -709,15 +700,10 @@ ssx_status ssx_stereo_batch_enqueue(ssx_ctx* ctx)
 {
   if (!ctx || !ctx->orb || !ctx->orb->batch_imgs) return SSX_ERR_INVALID_ARG;
   OrbWorkspace* ws = ctx->orb;
-  const size_t img_bytes = (size_t)ws->rows * ws->batch_stride;
+  const size_t img_bytes = (size_t)ws->key.rows * ws->batch_stride;
   ssx_status st = stage_level0(ctx, ws->batch_imgs, ws->batch_stride, img_bytes, nullptr, 0, 0);
   if (st != SSX_OK) return st;
-  st = run_pipeline(ctx);
-  if (st != SSX_OK) return st;
-  MatchDev m{};
-  st = make_match_dev(ctx, ws->batch_pairs, ws->batch_mp, ws->batch_rig, nullptr, m);
-  if (st != SSX_OK) return st;
-  return launch_stereo(ctx, m);
+  return run_batch(ctx, ws->batch_pairs, ws->batch_mp, ws->batch_rig);
 }
 
 ssx_status ssx_stereo_batch_dev(ssx_ctx* ctx, int32_t pairs, const uint8_t* imgs_dev, int32_t stride, int32_t rows,
@@ -757,9 +743,9 @@ static ssx_status batch_ingest_init(ssx_ctx* ctx, OrbWorkspace* ws)
 {
   if (ws->copy_stream) return SSX_OK;
   SSX_HIP_TRY(ctx, ctx->make_stream(&ws->copy_stream, false));
-  for (int b = 0; b < 2; ++b) {
-    SSX_HIP_TRY(ctx, hipEventCreateWithFlags(&ws->ev_up[b], hipEventDisableTiming));
-    SSX_HIP_TRY(ctx, hipEventCreateWithFlags(&ws->ev_free[b], hipEventDisableTiming));
+  for (OrbWorkspace::Upload& u : ws->up) {
+    SSX_HIP_TRY(ctx, hipEventCreateWithFlags(&u.ev_up, hipEventDisableTiming));
+    SSX_HIP_TRY(ctx, hipEventCreateWithFlags(&u.ev_free, hipEventDisableTiming));
   }
   return SSX_OK;
 }
@@ -771,19 +757,19 @@ ssx_status ssx_stereo_batch_upload(ssx_ctx* ctx, int32_t pairs, const uint8_t* i
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ssx_status st = batch_ingest_init(ctx, ws);
   if (st != SSX_OK) return st;
-  if (ws->up_count >= 2) { ctx->set_error("ssx_stereo_batch_upload: two uploaded batches are waiting for ssx_stereo_batch_run already"); return SSX_ERR_INVALID_ARG; }
-  const int b = (ws->up_first + ws->up_count) & 1;
+  if (ws->up_ring.count >= 2) { ctx->set_error("ssx_stereo_batch_upload: two uploaded batches are waiting for ssx_stereo_batch_run already"); return SSX_ERR_INVALID_ARG; }
+  OrbWorkspace::Upload& u = ws->up[ws->up_ring.push_slot()];
   const size_t bytes = 2 * (size_t)pairs * (size_t)rows * stride;
-  if (bytes > ws->ingest[b].cap) {                                    // (grows once; the batch that used the buffer last may still be read)
+  if (bytes > u.buf.cap) {                                            // (grows once; the batch that used the buffer last may still be read)
     SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SSX_HIP_TRY(ctx, ws->ingest[b].reserve(bytes));
-    ws->free_pending[b] = false;
+    SSX_HIP_TRY(ctx, u.buf.reserve(bytes));
+    u.free_pending = false;
   }
-  if (ws->free_pending[b]) SSX_HIP_TRY(ctx, hipStreamWaitEvent(ws->copy_stream, ws->ev_free[b], 0));   // level 0 of the batch that used it is staged
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(ws->ingest[b].p, imgs_host, bytes, hipMemcpyHostToDevice, ws->copy_stream));
-  SSX_HIP_TRY(ctx, hipEventRecord(ws->ev_up[b], ws->copy_stream));
-  ws->up_shape[b][0] = pairs; ws->up_shape[b][1] = stride; ws->up_shape[b][2] = rows; ws->up_shape[b][3] = cols;
-  ws->up_count++;
+  if (u.free_pending) SSX_HIP_TRY(ctx, hipStreamWaitEvent(ws->copy_stream, u.ev_free, 0));   // level 0 of the batch that used it is staged
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(u.buf.p, imgs_host, bytes, hipMemcpyHostToDevice, ws->copy_stream));
+  SSX_HIP_TRY(ctx, hipEventRecord(u.ev_up, ws->copy_stream));
+  u.pairs = pairs; u.stride = stride; u.rows = rows; u.cols = cols;
+  ws->up_ring.count++;
   return SSX_OK;
 }
 
@@ -791,36 +777,31 @@ ssx_status ssx_stereo_batch_run(ssx_ctx* ctx, const ssx_orb_params* orb, const s
 {
   if (!ctx || !orb || !mp || !rig) return SSX_ERR_INVALID_ARG;
   OrbWorkspace* ws = get_ws(ctx);
-  if (ws->up_count < 1) { ctx->set_error("ssx_stereo_batch_run: no uploaded batch (ssx_stereo_batch_upload first)"); return SSX_ERR_INVALID_ARG; }
-  const int b = ws->up_first;
-  const int pairs = ws->up_shape[b][0], stride = ws->up_shape[b][1], rows = ws->up_shape[b][2], cols = ws->up_shape[b][3];
+  if (ws->up_ring.count < 1) { ctx->set_error("ssx_stereo_batch_run: no uploaded batch (ssx_stereo_batch_upload first)"); return SSX_ERR_INVALID_ARG; }
+  OrbWorkspace::Upload& u = ws->up[ws->up_ring.first];
+  const int pairs = u.pairs, stride = u.stride, rows = u.rows, cols = u.cols;
   ssx_status st = plan(ctx, rows, cols, 2 * pairs, *orb, false, false);
   if (st != SSX_OK) return st;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ws->cnt_count >= 2) { ctx->set_error("ssx_stereo_batch_run: the counts of two batches are waiting for ssx_stereo_batch_counts already"); return SSX_ERR_INVALID_ARG; }
-  if (ws->cnt_count > 0 && ws->cnt_pairs[ws->cnt_first] != pairs) { ctx->set_error("ssx_stereo_batch_run: collect the counts of the batches that were run before changing the batch size"); return SSX_ERR_INVALID_ARG; }
+  if (ws->cnt_ring.count >= 2) { ctx->set_error("ssx_stereo_batch_run: the counts of two batches are waiting for ssx_stereo_batch_counts already"); return SSX_ERR_INVALID_ARG; }
+  if (ws->cnt_ring.count > 0 && ws->cnt[ws->cnt_ring.first].pairs != pairs) { ctx->set_error("ssx_stereo_batch_run: collect the counts of the batches that were run before changing the batch size"); return SSX_ERR_INVALID_ARG; }
   SSX_HIP_TRY(ctx, ws->counts_pinned.reserve(2 * sizeof(int) * 6 * (size_t)pairs));
-  for (int q = 0; q < 2; ++q) if (!ws->ev_counts[q]) SSX_HIP_TRY(ctx, hipEventCreateWithFlags(&ws->ev_counts[q], hipEventDisableTiming));
-  SSX_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ws->ev_up[b], 0));
+  for (OrbWorkspace::Counts& c : ws->cnt) if (!c.ev) SSX_HIP_TRY(ctx, hipEventCreateWithFlags(&c.ev, hipEventDisableTiming));
+  SSX_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, u.ev_up, 0));
   const size_t img_bytes = (size_t)rows * stride;
-  ws->batch_imgs = ws->ingest[b].as<uint8_t>(); ws->batch_pairs = pairs; ws->batch_stride = stride;
+  ws->batch_imgs = u.buf.as<uint8_t>(); ws->batch_pairs = pairs; ws->batch_stride = stride;
   ws->batch_orb = *orb; ws->batch_mp = *mp; ws->batch_rig = *rig;
   st = stage_level0(ctx, ws->batch_imgs, stride, img_bytes, nullptr, 0, 0);
   if (st != SSX_OK) return st;
-  SSX_HIP_TRY(ctx, hipEventRecord(ws->ev_free[b], ctx->stream));
-  ws->free_pending[b] = true;
-  ws->up_first ^= 1; ws->up_count--;
+  SSX_HIP_TRY(ctx, hipEventRecord(u.ev_free, ctx->stream));
+  u.free_pending = true;
+  ws->up_ring.pop();
   // From here on the batch is CONSUMED (its buffer is promised to the next upload): whatever happens below, it takes its slot in
   // the counts FIFO, so a caller that pipelines upload / run / counts stays aligned -- a failure is reported by this call AND by
   // the ssx_stereo_batch_counts call that collects this batch, never as another batch's counts.
-  const int slot = (ws->cnt_first + ws->cnt_count) & 1;
+  const int slot = ws->cnt_ring.push_slot();
   auto rest = [&]() -> ssx_status {
-    ssx_status r = run_pipeline(ctx);
-    if (r != SSX_OK) return r;
-    MatchDev m{};
-    r = make_match_dev(ctx, pairs, *mp, *rig, nullptr, m);
-    if (r != SSX_OK) return r;
-    r = launch_stereo(ctx, m);
+    const ssx_status r = run_batch(ctx, pairs, *mp, *rig);
     if (r != SSX_OK) return r;
     // the counts of this batch leave the device before the next batch's kernels overwrite them (stream order); an event per batch
     // lets ssx_stereo_batch_counts wait for THIS batch only -- a caller may run the next batch first and collect one batch behind
@@ -830,11 +811,11 @@ ssx_status ssx_stereo_batch_run(ssx_ctx* ctx, const ssx_orb_params* orb, const s
     return SSX_OK;
   };
   st = rest();
-  const hipError_t ev_err = hipEventRecord(ws->ev_counts[slot], ctx->stream);
+  const hipError_t ev_err = hipEventRecord(ws->cnt[slot].ev, ctx->stream);
   if (st == SSX_OK && ev_err != hipSuccess) { ctx->set_error("ssx_stereo_batch_run: hipEventRecord: %s", hipGetErrorString(ev_err)); st = SSX_ERR_HIP; }
-  ws->cnt_pairs[slot] = pairs;
-  ws->cnt_fail[slot] = st;
-  ws->cnt_count++;
+  ws->cnt[slot].pairs = pairs;
+  ws->cnt[slot].fail = st;
+  ws->cnt_ring.count++;
   return st;
 }
 
@@ -843,7 +824,7 @@ ssx_status ssx_stereo_batch_host(ssx_ctx* ctx, int32_t pairs, const uint8_t* img
 {
   if (!ctx || !orb || !mp || !rig) return SSX_ERR_INVALID_ARG;
   OrbWorkspace* ws = get_ws(ctx);
-  if (ws->up_count != 0) { ctx->set_error("ssx_stereo_batch_host: %d uploaded batch(es) are waiting for ssx_stereo_batch_run", ws->up_count); return SSX_ERR_INVALID_ARG; }
+  if (ws->up_ring.count != 0) { ctx->set_error("ssx_stereo_batch_host: %d uploaded batch(es) are waiting for ssx_stereo_batch_run", ws->up_ring.count); return SSX_ERR_INVALID_ARG; }
   ssx_status st = ssx_stereo_batch_upload(ctx, pairs, imgs_host, stride, rows, cols);
   if (st != SSX_OK) return st;
   return ssx_stereo_batch_run(ctx, orb, mp, rig);
@@ -854,13 +835,13 @@ ssx_status ssx_stereo_batch_counts(ssx_ctx* ctx, int32_t* counts_out)
 {
   if (!ctx || !ctx->orb) return SSX_ERR_INVALID_ARG;
   OrbWorkspace* ws = ctx->orb;
-  if (ws->cnt_count < 1) { ctx->set_error("ssx_stereo_batch_counts: no batch has been run (ssx_stereo_batch_run first)"); return SSX_ERR_INVALID_ARG; }
-  const int slot = ws->cnt_first;
-  const hipError_t sync_err = hipEventSynchronize(ws->ev_counts[slot]);
-  ws->cnt_first ^= 1; ws->cnt_count--;                               // (collected either way: the FIFO stays aligned with the runs)
-  if (ws->cnt_fail[slot] != SSX_OK) { ctx->set_error("ssx_stereo_batch_counts: the run of this batch failed (status %d)", (int)ws->cnt_fail[slot]); return ws->cnt_fail[slot]; }
+  if (ws->cnt_ring.count < 1) { ctx->set_error("ssx_stereo_batch_counts: no batch has been run (ssx_stereo_batch_run first)"); return SSX_ERR_INVALID_ARG; }
+  const hipError_t sync_err = hipEventSynchronize(ws->cnt[ws->cnt_ring.first].ev);
+  const int slot = ws->cnt_ring.pop();                               // (collected either way: the FIFO stays aligned with the runs)
+  const OrbWorkspace::Counts& c = ws->cnt[slot];
+  if (c.fail != SSX_OK) { ctx->set_error("ssx_stereo_batch_counts: the run of this batch failed (status %d)", (int)c.fail); return c.fail; }
   SSX_HIP_TRY(ctx, sync_err);
-  const int pairs = ws->cnt_pairs[slot];
+  const int pairs = c.pairs;
   const int* hc = ws->counts_pinned.as<int>() + (size_t)slot * 6 * pairs;
   for (int i = 0; i < 2 * pairs; ++i)
     if (hc[4 * (size_t)pairs + i]) { ctx->set_error("ssx_stereo_batch: internal capacity exceeded on image %d (bits %d)", i, hc[4 * (size_t)pairs + i]); return SSX_ERR_CAPACITY; }

@@ -1,5 +1,5 @@
 """AddressSanitizer over the HOST side of libssx.so's bundle-adjustment marshalling (prepare(): edge sort, chunks, packed records,
-pair lists, work items), no GPU needed:
+pair lists, work items) and of the ORB front-end's plan (build_plan(): levels, cells, capacities, resize tables, arena), no GPU needed:
     SSX_EXTRA_HIPCC_FLAGS="-fsanitize=address -fno-omit-frame-pointer -g" python -c "from ssvio_amd import build; build.build(force=True)"
     ASAN_OPTIONS=detect_leaks=0 LD_PRELOAD=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so) python tools/asan_prepare.py
 (rebuild without the flags afterwards)"""
@@ -25,3 +25,7 @@ lib.ssx_ba_window_selftest.restype = C.c_int32; lib.ssx_ba_window_selftest.argty
 for seed in (0, 5, 9):
     print("window selftest seed", seed, "->", lib.ssx_ba_window_selftest(seed, 500))
 print("done (window)")
+# the plan of the ORB front-end, every case of tools/orb_plan_ab.py incl. the refusals
+from tools.orb_plan_ab import CASES, FAILING, plan_info
+print("orb plans:", sorted(set(plan_info(lib, c).status for c in CASES + [f[0] for f in FAILING.values()])))
+print("done (orb plan)")
