@@ -662,6 +662,50 @@ SSX_API ssx_status ssx_voc_transform(ssx_vocabulary* voc, const uint8_t* desc, i
 SSX_API double ssx_bow_score_l1(int32_t n1, const int32_t* id1, const double* v1, int32_t n2, const int32_t* id2,
                                 const double* v2);
 
+/* ------------------------------------------------------------------------------------------------
+ * The keyframe database of loop closing, resident on the device -- replaces key_frame_database_ with the two functions
+ * that read it:
+ *   AddToKeyframeDatabase   src/ssvio/loopclosing.cpp:646-649
+ *   DetectLoop              src/ssvio/loopclosing.cpp:72-103
+ *   MatchFeatures           src/ssvio/loopclosing.cpp:105-145
+ * Every keyframe's BowVector and pyramid descriptors stay in HBM; a query uploads only the current keyframe's.
+ * A database belongs to the context it was created on and must be destroyed before it.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct ssx_kf_database ssx_kf_database;
+/* keyframes_hint sizes the first allocation (about 48 KB per keyframe); the database grows as needed */
+SSX_API ssx_status ssx_kfdb_create(ssx_ctx* ctx, int32_t keyframes_hint, ssx_kf_database** out);
+SSX_API void ssx_kfdb_destroy(ssx_kf_database* db);
+SSX_API ssx_status ssx_kfdb_size(const ssx_kf_database* db, int32_t* n_keyframes, int64_t* n_bow_entries,
+                                 int64_t* n_descriptors);
+/* AddToKeyframeDatabase: the BowVector (ids ascending, values) and optionally the keyframe's pyramid descriptors
+ * (n_desc x 32) with the class_id of each (the feature index ProcessNewKeyframe writes, loopclosing.cpp:610-616).
+ * desc == NULL: the keyframe is stored without descriptors and cannot be matched against.  kf_id must be greater than
+ * every id already stored (the std::map's order); otherwise, or when the word ids do not ascend, SSX_ERR_INVALID_ARG. */
+SSX_API ssx_status ssx_kfdb_add(ssx_kf_database* db, int64_t kf_id, int32_t n_bow, const int32_t* ids, const double* vals,
+                                int32_t n_desc, const uint8_t* desc, const int32_t* class_id);
+/* DetectLoop for a current keyframe (query_kf_id, BowVector with ascending ids).  The stored keyframes with
+ * query_kf_id - kf_id >= min_id_gap (the reference: 20) are eligible: a prefix in id order, *n_scored of them.
+ * scores_out (nullable, capacity scores_cap >= *n_scored, else SSX_ERR_CAPACITY): scores_out[i] is, bit for bit,
+ * ssx_bow_score_l1(query, i-th stored keyframe); 0 where either BowVector is empty (the reference skips those).
+ * The winner is the reference's: scores narrowed to float, the maximum starts at 0, a strictly greater score replaces
+ * it (so the lowest id wins among equal floats).  *found = 0 when no score is above 0 or the best float score is below
+ * threshold (Loop.Threshold.Heigher); best_kf_id / best_score (nullable) are written only when *found = 1. */
+SSX_API ssx_status ssx_kfdb_detect_loop(ssx_kf_database* db, int64_t query_kf_id, int32_t n_bow, const int32_t* ids,
+                                        const double* vals, int32_t min_id_gap, float threshold, int32_t* found,
+                                        int64_t* best_kf_id, float* best_score, int32_t scores_cap, double* scores_out,
+                                        int32_t* n_scored);
+/* MatchFeatures against a stored keyframe: cv::BFMatcher(NORM_HAMMING)::match(loop, current) as ssx_bf_match does it
+ * (query = the stored descriptors, train = cur_desc, n_cur <= 65535 else SSX_ERR_UNSUPPORTED), *min_distance = the
+ * smallest distance of all matches, a match is kept when dist <= max(2 * min_distance, 30), and a kept match gives the
+ * pair (cur_class_id[train], class_id[query]).  pairs_out (cap x 2) receives the reference's std::set: unique pairs in
+ * ascending (current, loop) order; *n_pairs = their number (SSX_ERR_CAPACITY when cap is smaller, with the first cap
+ * pairs written).  No descriptors on either side: zero pairs, *min_distance = -1.  SSX_ERR_INVALID_ARG for a
+ * loop_kf_id that is not stored or was stored without descriptors.  The "fewer than 10 pairs" verdict
+ * (loopclosing.cpp:139) is the caller's. */
+SSX_API ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int32_t n_cur, const uint8_t* cur_desc,
+                                           const int32_t* cur_class_id, int32_t cap, int32_t* pairs_out, int32_t* n_pairs,
+                                           int32_t* min_distance);
+
 #ifdef __cplusplus
 }
 #endif

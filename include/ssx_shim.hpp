@@ -10,11 +10,15 @@
 //   ssx::BundleAdjuster          the optimisation of Backend::OptimizeActiveMap (src/ssvio/backend.cpp:78-245)
 //   ssx::StereoFrontEnd          DetectFeatures + FindFeaturesInRight + triangulation in one device-resident call
 //   ssx::calcOpticalFlowPyrLK    cv::calcOpticalFlowPyrLK as frontend.cpp:156-166 / :374-384 call it
+//   ssx::ORBVocabulary           DBoW2 vocabulary: loadFromTextFile / transform / score (loopclosing.cpp:33-41, :84, :633)
+//   ssx::KeyframeDatabase        key_frame_database_ with AddToKeyframeDatabase / DetectLoop / MatchFeatures (loopclosing.cpp:72-145, :646)
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <set>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ssx.h"
@@ -259,6 +263,76 @@ class ORBVocabulary {
  private:
   Context& ctx_;
   ssx_vocabulary* voc_ = nullptr;
+};
+
+// LoopClosing's key_frame_database_ (a std::map<unsigned long, KeyFrame::Ptr>) together with the two functions that read it,
+// kept on the device.  AddToKeyframeDatabase (loopclosing.cpp:646-649) stores what DetectLoop and MatchFeatures need of a
+// keyframe: bow2_vec_, ORBDescriptors_ (n x 32 bytes) and the class_id of every entry of pyramid_key_points_.
+class KeyframeDatabase {
+ public:
+  explicit KeyframeDatabase(Context& ctx, int keyframes_hint = 1024) : ctx_(ctx) { ctx_.check(ssx_kfdb_create(ctx_.get(), keyframes_hint, &db_)); }
+  ~KeyframeDatabase() { ssx_kfdb_destroy(db_); }
+  KeyframeDatabase(const KeyframeDatabase&) = delete;
+  KeyframeDatabase& operator=(const KeyframeDatabase&) = delete;
+
+  // key_frame_database_.insert({current_keyframe_->key_frame_id_, current_keyframe_}); ids ascend as the reference's do
+  void AddToKeyframeDatabase(unsigned long key_frame_id, const BowVector& bow, const std::vector<uint8_t>& descriptors,
+                             const std::vector<int32_t>& class_ids)
+  {
+    if (descriptors.size() != class_ids.size() * 32) throw std::invalid_argument("AddToKeyframeDatabase: one class_id per 32-byte descriptor");
+    static const uint8_t none = 0;                           // an empty descriptor matrix is still a matrix
+    ctx_.check(ssx_kfdb_add(db_, (int64_t)key_frame_id, (int32_t)bow.ids.size(), bow.ids.data(), bow.values.data(), (int32_t)class_ids.size(),
+                            class_ids.empty() ? &none : descriptors.data(), class_ids.empty() ? reinterpret_cast<const int32_t*>(&none) : class_ids.data()));
+  }
+
+  // bool DetectLoop(): true when a stored keyframe at least 20 ids back scores >= loop_threshold_heigher_ against the current
+  // one; loop_key_frame_id is then the id of loop_keyframe_ and *max_score (nullable) the float the reference logs
+  bool DetectLoop(unsigned long current_key_frame_id, const BowVector& current_bow, float loop_threshold_heigher, unsigned long& loop_key_frame_id,
+                  float* max_score = nullptr, int min_id_gap = 20)
+  {
+    int32_t found = 0;
+    int64_t best = 0;
+    float score = 0.f;
+    ctx_.check(ssx_kfdb_detect_loop(db_, (int64_t)current_key_frame_id, (int32_t)current_bow.ids.size(), current_bow.ids.data(), current_bow.values.data(),
+                                    min_id_gap, loop_threshold_heigher, &found, &best, &score, 0, nullptr, nullptr));
+    if (!found) return false;
+    loop_key_frame_id = (unsigned long)best;
+    if (max_score) *max_score = score;
+    return true;
+  }
+
+  // MatchFeatures() up to its verdict: set_valid_feature_matches_ = {(current feature id, loop feature id)}; the caller
+  // keeps `return set.size() >= 10` (loopclosing.cpp:139)
+  std::set<std::pair<int, int>> MatchFeatures(unsigned long loop_key_frame_id, const std::vector<uint8_t>& current_descriptors,
+                                              const std::vector<int32_t>& current_class_ids, int* min_distance = nullptr)
+  {
+    if (current_descriptors.size() != current_class_ids.size() * 32) throw std::invalid_argument("MatchFeatures: one class_id per 32-byte descriptor");
+    std::vector<int32_t> pairs(2 * std::max<size_t>(4096, current_class_ids.size()));   // room for a keyframe of the usual size
+    int32_t n = 0, md = 0;
+    ssx_status st = ssx_kfdb_match_features(db_, (int64_t)loop_key_frame_id, (int32_t)current_class_ids.size(), current_descriptors.data(),
+                                            current_class_ids.data(), (int32_t)(pairs.size() / 2), pairs.data(), &n, &md);
+    if (st == SSX_ERR_CAPACITY) {                            // a larger loop keyframe: its size is known now
+      pairs.resize((size_t)n * 2);
+      st = ssx_kfdb_match_features(db_, (int64_t)loop_key_frame_id, (int32_t)current_class_ids.size(), current_descriptors.data(),
+                                   current_class_ids.data(), n, pairs.data(), &n, &md);
+    }
+    ctx_.check(st);
+    if (min_distance) *min_distance = md;
+    std::set<std::pair<int, int>> out;
+    for (int32_t i = 0; i < n; ++i) out.emplace_hint(out.end(), pairs[2 * i], pairs[2 * i + 1]);
+    return out;
+  }
+
+  int size() const
+  {
+    int32_t n = 0;
+    ssx_kfdb_size(db_, &n, nullptr, nullptr);
+    return n;
+  }
+
+ private:
+  Context& ctx_;
+  ssx_kf_database* db_ = nullptr;
 };
 
 }  // namespace ssx

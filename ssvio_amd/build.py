@@ -31,6 +31,7 @@ PER_FILE = {
     "orb.hip": ["-ffp-contract=off"],
     "stereo.hip": ["-ffp-contract=off"],
     "lk.hip": ["-ffp-contract=off"],
+    "loop.hip": ["-ffp-contract=off"],
 }
 
 

@@ -144,6 +144,8 @@ ssx_status stage_level0(ssx_ctx* ctx, const uint8_t* imgs_dev, int stride, size_
 ssx_status run_pipeline(ssx_ctx* ctx);
 // download the keypoints / descriptors of one image of the last run (synchronises the stream)
 ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n);
+// the brute-force matcher k_bf_match (stereo.hip) on device arrays: idx[i] / dist[i] = nearest of the nt <= 65535 train descriptors to query i
+void launch_bf_match(hipStream_t stream, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist);
 // a buffer's pointer, whatever its type, from the base of its block and its offset
 template <class T> void wire(T*& ptr, char* base, size_t off) { ptr = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off); }
 // The buffers of one block, each stated ONCE: `each(f)` calls f(pointer, bytes) for every buffer in memory order.  Wires the pointers

@@ -504,6 +504,12 @@ ssx_status fetch_frame_fast(ssx_ctx* ctx, const FrameSlots& o, ssx_stereo_frame_
 }
 
 }  // namespace
+
+// k_bf_match on device arrays, for the callers outside this file (loop.hip matches against descriptors that stay in HBM)
+void launch_bf_match(hipStream_t stream, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist)
+{
+  hipLaunchKernelGGL(k_bf_match, dim3((nq + 3) / 4), dim3(256), 0, stream, dq, nq, dt, nt, idx, dist);
+}
 }  // namespace ssxorb
 
 using namespace ssxorb;
@@ -581,8 +587,8 @@ ssx_status ssx_bf_match(ssx_ctx* ctx, const uint8_t* dq, int32_t nq, const uint8
   if (nt) memcpy(hs + o_t, dt, (size_t)32 * nt);
   char* base = ws->input.as<char>();
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  SSX_PROF(ctx, KID_ST_MISC, hipLaunchKernelGGL(k_bf_match, dim3((nq + 3) / 4), dim3(256), 0, ctx->stream, (const uint8_t*)(base + o_q), nq,
-                     (const uint8_t*)(base + o_t), nt, (int*)(base + o_i), (int*)(base + o_d)));
+  SSX_PROF(ctx, KID_ST_MISC, launch_bf_match(ctx->stream, (const uint8_t*)(base + o_q), nq, (const uint8_t*)(base + o_t), nt, (int*)(base + o_i),
+                                             (int*)(base + o_d)));
   SSX_HIP_TRY(ctx, hipGetLastError());
   SSX_HIP_TRY(ctx, hipMemcpyAsync(idx, base + o_i, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipMemcpyAsync(dist, base + o_d, sizeof(int) * nq, hipMemcpyDeviceToHost, ctx->stream));
