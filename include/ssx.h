@@ -706,6 +706,71 @@ SSX_API ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_
                                            const int32_t* cur_class_id, int32_t cap, int32_t* pairs_out, int32_t* n_pairs,
                                            int32_t* min_distance);
 
+/* ------------------------------------------------------------------------------------------------
+ * The pose correction of loop closing -- replaces LoopClosing::ComputeCorrectPose (src/ssvio/loopclosing.cpp:147-243)
+ * with its cv::solvePnPRansac call (:205-206) and LoopClosing::OptimizeCurrentPose (:245-351).
+ *
+ * cv::solvePnPRansac is not restated to the bit: its sampler and its confidence-driven early exit belong to OpenCV's
+ * sequential loop.  The contract of ssx_pnp_ransac is its own, stated in tools/pnp_model.py, which the kernel follows
+ * operation by operation:
+ *   - max_iters hypotheses (the reference passes 100), ALL scored in one launch (no early exit, hence no confidence);
+ *   - hypothesis h draws three distinct points as a pure function of (seed, h, M); its P3P yields up to four poses;
+ *   - a point is an inlier of a pose when its depth is positive and its reprojection error is at most reproj_px PIXELS
+ *     (the reference passes 5.991, its chi-square constant, as this pixel threshold);
+ *   - the winner has the most inliers, then the lowest hypothesis, then the lowest solution.
+ * The reference uses only the pose of the RANSAC, never its inliers; OptimizeCurrentPose then runs g2o over ALL pairs:
+ * one optimize(10) with every edge active, then the procedure of ssx_pose_only_opt (4 rounds x optimize(10), chi2 > chi2_th
+ * => outlier after every round, the robust kernels dropped before the last).  ssx_loop_pose_opt is that, with the arithmetic
+ * of ssx_pose_only_opt.
+ * ------------------------------------------------------------------------------------------------ */
+#define SSX_PNP_MAX_ITERS 4096
+/* xyz M x 3, uv M x 2 (cv::Point2f widened to double), pose_out = qx qy qz qw tx ty tz (normalised, qw >= 0) of the winner,
+ * inlier_out (nullable) M bytes, *best_hypothesis (nullable) = 4 h + s of the winner: hypothesis h, its solution s.
+ * *found = 0 when no hypothesis reaches 4 inliers (a hypothesis explains its own 3 points) or M < 3 -- the exception the
+ * reference catches (:203-210); pose_out is then the identity and *n_inliers = 0.
+ * SSX_ERR_INVALID_ARG: M < 0, a null required pointer, max_iters outside [1, SSX_PNP_MAX_ITERS], reproj_px negative or NaN,
+ * a non-finite K4. */
+SSX_API ssx_status ssx_pnp_ransac(ssx_ctx* ctx, const double* K4, int32_t M, const double* xyz, const double* uv,
+                                  int32_t max_iters, double reproj_px, uint32_t seed, double* pose_out, uint8_t* inlier_out,
+                                  int32_t* n_inliers, int32_t* best_hypothesis, int32_t* found);
+/* OptimizeCurrentPose: pose_io = corrected_current_pose_ in and out, inlier_out[i] (nullable) = 1 when pair i survives,
+ * *n_inliers (nullable) = their number.  Reference: chi2_th 5.991, huber_delta 1.0. */
+SSX_API ssx_status ssx_loop_pose_opt(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz,
+                                     const double* uv, double chi2_th, double huber_delta, uint8_t* inlier_out,
+                                     int32_t* n_inliers);
+
+typedef enum ssx_loop_verdict {
+  SSX_LOOP_OK = 0,               /* ComputeCorrectPose returns true */
+  SSX_LOOP_FEW_MAP_POINTS = 1,   /* fewer than 10 pairs with a live map point (:193) */
+  SSX_LOOP_NO_POSE = 2,          /* the RANSAC found nothing (:203-210) */
+  SSX_LOOP_FEW_INLIERS = 3       /* fewer than 10 pairs survive the optimisation (:219) */
+} ssx_loop_verdict;
+typedef struct ssx_loop_pose_result {
+  int32_t verdict;               /* ssx_loop_verdict */
+  int32_t n_with_point;          /* pairs whose map point is alive */
+  int32_t n_ransac_inliers;      /* inliers of the RANSAC's winner; best_hypothesis = its 4 h + s (-1: none) */
+  int32_t best_hypothesis;
+  int32_t n_inliers;             /* cnt_inliner: pairs that survive OptimizeCurrentPose */
+  int32_t need_correct;          /* need_correct_loop_pose_ = error > 1 && error < 15 */
+  double error;                  /* |log(T_cur * corrected_pose^-1)| */
+  double corrected_pose[7];      /* corrected_current_pose_: written for SSX_LOOP_OK and SSX_LOOP_FEW_INLIERS (the
+                                  * optimisation ran), the identity for the other two verdicts */
+  double relative_to_loop[7];    /* relative_pose_to_loop_KF_ = corrected_pose * T_loop^-1 */
+} ssx_loop_pose_result;
+/* The whole of ComputeCorrectPose for the n_pairs pairs of ssx_kfdb_match_features: two launches (the RANSAC, the
+ * optimisation, which takes the RANSAC's pose where it lies in device memory) and one synchronisation.
+ *   loop_xyz n_pairs x 3   the map point of the loop keyframe's feature of each pair (ignored where has_point[i] == 0)
+ *   has_point n_pairs      0 = the feature's map_point_ has expired: the pair is erased (:170-173)
+ *   cur_uv n_pairs x 2     the current keyframe's pixel of each pair
+ *   T_cur, T_loop          the poses of the current and of the loop keyframe
+ *   kept n_pairs           set_valid_feature_matches_ afterwards: 1 = the pair is still in it
+ * RANSAC threshold 5.991 px, chi2_th 5.991 and Huber delta 1.0 are the reference's.  error, need_correct and
+ * relative_to_loop are written for SSX_LOOP_OK only (the reference returns before it computes them otherwise).
+ * SSX_ERR_INVALID_ARG as for ssx_pnp_ransac. */
+SSX_API ssx_status ssx_loop_compute_pose(ssx_ctx* ctx, int32_t n_pairs, const double* loop_xyz, const uint8_t* has_point,
+                                         const double* cur_uv, const double* T_cur, const double* T_loop, const double* K4,
+                                         int32_t max_iters, uint32_t seed, uint8_t* kept, ssx_loop_pose_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@
 //   ssx::calcOpticalFlowPyrLK    cv::calcOpticalFlowPyrLK as frontend.cpp:156-166 / :374-384 call it
 //   ssx::ORBVocabulary           DBoW2 vocabulary: loadFromTextFile / transform / score (loopclosing.cpp:33-41, :84, :633)
 //   ssx::KeyframeDatabase        key_frame_database_ with AddToKeyframeDatabase / DetectLoop / MatchFeatures (loopclosing.cpp:72-145, :646)
+//   ssx::ComputeCorrectPose      LoopClosing::ComputeCorrectPose / OptimizeCurrentPose (loopclosing.cpp:147-351)
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -334,5 +335,74 @@ class KeyframeDatabase {
   Context& ctx_;
   ssx_kf_database* db_ = nullptr;
 };
+
+// What LoopClosing::ComputeCorrectPose reads of one entry of set_valid_feature_matches_: the pair itself, the position of
+// loop_keyframe_->features_left_[loop_feature_id]->map_point_ (has_map_point = false when the weak_ptr has expired) and
+// current_keyframe_->features_left_[current_feature_id]->kp_position_.pt
+struct LoopMatch {
+  int current_feature_id, loop_feature_id;
+  bool has_map_point;
+  double map_point[3];
+  float pt_x, pt_y;
+};
+
+// bool LoopClosing::ComputeCorrectPose() (loopclosing.cpp:147-243) with the OptimizeCurrentPose it calls: solvePnPRansac(100 iterations,
+// 5.991 px) under the contract of ssx_pnp_ransac, then g2o over all pairs.  The members the reference writes come back as fields:
+struct CorrectPoseResult {
+  bool ok = false;                                     // the return value
+  ssx_loop_verdict verdict = SSX_LOOP_FEW_MAP_POINTS;  // why not
+  std::set<std::pair<int, int>> set_valid_feature_matches;   // after the two erasures (:172, :338-344)
+  double corrected_current_pose[7] = {0, 0, 0, 1, 0, 0, 0};
+  bool need_correct_loop_pose = false;
+  double error = 0.0;                                  // the "Loop Error" the reference logs
+  double relative_pose_to_loop_KF[7] = {0, 0, 0, 1, 0, 0, 0};
+  int cnt_inliner = 0;
+};
+inline CorrectPoseResult ComputeCorrectPose(Context& ctx, const std::vector<LoopMatch>& matches, const double current_pose[7], const double loop_pose[7],
+                                            const double K4[4], int iterations = 100, uint32_t seed = 0)
+{
+  const size_t n = matches.size();
+  std::vector<double> xyz(3 * n), uv(2 * n);
+  std::vector<uint8_t> has(n), kept(n);
+  for (size_t i = 0; i < n; ++i) {
+    has[i] = matches[i].has_map_point ? 1 : 0;
+    for (int k = 0; k < 3; ++k) xyz[3 * i + k] = matches[i].has_map_point ? matches[i].map_point[k] : 0.0;
+    uv[2 * i] = matches[i].pt_x; uv[2 * i + 1] = matches[i].pt_y;
+  }
+  ssx_loop_pose_result r;
+  ctx.check(ssx_loop_compute_pose(ctx.get(), (int32_t)n, xyz.data(), has.data(), uv.data(), current_pose, loop_pose, K4, iterations, seed, kept.data(), &r));
+  CorrectPoseResult out;
+  out.verdict = (ssx_loop_verdict)r.verdict;
+  out.ok = r.verdict == SSX_LOOP_OK;
+  for (size_t i = 0; i < n; ++i)
+    if (kept[i]) out.set_valid_feature_matches.emplace(matches[i].current_feature_id, matches[i].loop_feature_id);
+  std::copy(r.corrected_pose, r.corrected_pose + 7, out.corrected_current_pose);
+  std::copy(r.relative_to_loop, r.relative_to_loop + 7, out.relative_pose_to_loop_KF);
+  out.need_correct_loop_pose = r.need_correct != 0;
+  out.error = r.error;
+  out.cnt_inliner = r.n_inliers;
+  return out;
+}
+
+// int LoopClosing::OptimizeCurrentPose() (loopclosing.cpp:245-351) on its own: every match must have its map point.
+// corrected_current_pose is refined in place, the matches that end as outliers are erased; returns what is left (cnt_inliner).
+inline int OptimizeCurrentPose(Context& ctx, std::vector<LoopMatch>& matches, double corrected_current_pose[7], const double K4[4])
+{
+  const size_t n = matches.size();
+  std::vector<double> xyz(3 * n), uv(2 * n);
+  std::vector<uint8_t> in(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (!matches[i].has_map_point) throw std::invalid_argument("OptimizeCurrentPose: a match without a map point");
+    for (int k = 0; k < 3; ++k) xyz[3 * i + k] = matches[i].map_point[k];
+    uv[2 * i] = matches[i].pt_x; uv[2 * i + 1] = matches[i].pt_y;
+  }
+  int32_t cnt = 0;
+  ctx.check(ssx_loop_pose_opt(ctx.get(), corrected_current_pose, K4, (int32_t)n, xyz.data(), uv.data(), 5.991, 1.0, in.data(), &cnt));
+  size_t w = 0;
+  for (size_t i = 0; i < n; ++i)
+    if (in[i]) matches[w++] = matches[i];
+  matches.resize(w);
+  return cnt;
+}
 
 }  // namespace ssx

@@ -89,6 +89,13 @@ SSX_API ssx_status ssx_lk_stage_level(ssx_ctx* ctx, int32_t which, int32_t level
 SSX_API ssx_status ssx_lk_stage_deriv(ssx_ctx* ctx, int32_t level, int16_t* out, int32_t out_cap, int32_t* rows,
                                       int32_t* cols);
 
+/* tests hooks of the P3P-RANSAC (csrc/pnp.hip, model: tools/pnp_model.py): the sample triples of (seed, M >= 3, H) as the kernel's
+ * device function draws them (triples_out H x 3), and the best inlier count of each of the max_iters hypotheses of an
+ * ssx_pnp_ransac call with the same arguments (counts_out max_iters) */
+SSX_API ssx_status ssx_pnp_debug_samples(ssx_ctx* ctx, uint32_t seed, int32_t M, int32_t H, int32_t* triples_out);
+SSX_API ssx_status ssx_pnp_debug_counts(ssx_ctx* ctx, const double* K4, int32_t M, const double* xyz, const double* uv,
+                                        int32_t max_iters, double reproj_px, uint32_t seed, int32_t* counts_out);
+
 #ifdef __cplusplus
 }
 #endif

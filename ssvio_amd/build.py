@@ -32,6 +32,7 @@ PER_FILE = {
     "stereo.hip": ["-ffp-contract=off"],
     "lk.hip": ["-ffp-contract=off"],
     "loop.hip": ["-ffp-contract=off"],
+    "pnp.hip": ["-ffp-contract=off"],        # the P3P of a hypothesis rounds like tools/pnp_model.py, operation by operation
 }
 
 

@@ -73,6 +73,8 @@ void ssx_ctx_destroy(ssx_ctx* ctx)
   if (ctx->lk && ctx->lk_free) ctx->lk_free(ctx->lk);
   ctx->po_arena.release();
   ctx->po_stage.release();
+  ctx->pnp_arena.release();
+  ctx->pnp_stage.release();
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }

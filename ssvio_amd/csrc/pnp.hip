@@ -1,0 +1,648 @@
+// ssvio_amd/csrc/pnp.hip -- the pose correction of loop closing: P3P-RANSAC and its refinement, on the device.
+//
+// LoopClosing::ComputeCorrectPose (src/ssvio/loopclosing.cpp:147-243) hands the matched (map point of the loop keyframe, pixel of the
+// current keyframe) pairs to cv::solvePnPRansac(..., 100 iterations, 5.991 px, 0.99), takes ONLY the pose from it (never the inliers)
+// and refines that pose over all pairs in OptimizeCurrentPose (:245-351).  OpenCV's sampler and sequential early exit cannot be
+// restated to the bit, so the RANSAC here is a contract of its own, stated once more in tools/pnp_model.py; the refinement is g2o's,
+// which pose_only.hip already restates (one warm-up pass, then the four classified rounds).
+//
+// k_pnp_ransac   one wavefront per hypothesis, four per workgroup.  Hypothesis h samples three distinct points as a pure function of
+//                (seed, h, M) -- a counter-based mixer, multiply-high draws from [0, M), [0, M-1), [0, M-2), each lifted past the earlier
+//                picks -- so the result does not depend on the launch.  Every lane solves the P3P of the triple (up to four poses; the
+//                solver is described in tools/pnp_model.py and uses + - * / sqrt only, with fixed numbers of Newton steps), then the
+//                lanes stride over the M points per solution: inlier = positive depth and ex^2 + ey^2 <= thr^2 (thr in PIXELS: the
+//                reference passes its chi-square constant as OpenCV's pixel threshold), counted by ballot + popcount.  A degenerate
+//                triple yields no solution and scores 0: validity is decided by finiteness tests, no NaN reaches a comparison.
+//                ALL max_iters hypotheses are scored: the confidence-driven early exit of OpenCV's loop is a sequential notion, a
+//                launch has no use for it.
+//                Selection: max over (count << 32) | ~(4 h + s) -- the most inliers, then the lowest hypothesis, then the lowest
+//                solution, what a sequential loop with `>` keeps -- folded through LDS, one 64-bit atomicMax per workgroup behind a
+//                read.  The LAST workgroup to finish (a ticket) solves the winner's triple again and writes its pose
+//                (qx qy qz qw tx ty tz, normalised, qw >= 0), its inlier mask and the header: they stay in device memory, where
+//                the refinement (k_pose_only*, gated by the header's `found`) picks the pose up.
+//
+// This file is compiled with -ffp-contract=off: every operation rounds as the model's does.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "ctx.hpp"
+#include "pose_only.hpp"
+#include "se3.hpp"
+#include "../../include/ssx_test_hooks.h"
+
+namespace {
+
+constexpr int kNewtonSteps = 16;    // on the cubic
+constexpr int kGnSteps = 3;         // on the three quadrics
+constexpr int kMinInliers = 4;      // a hypothesis explains its own three points: a pose needs one more
+
+struct PnpHdr {                     // results of k_pnp_ransac, in device memory
+  double pose[7];
+  int32_t found, n_inliers, best, pad;
+};
+
+struct PnpDev {
+  int M, H;
+  uint32_t seed;
+  double fx, fy, cx, cy, thr2;
+  const double* xyz;
+  const double* uv;
+  unsigned long long* best;         // zero before the launch
+  unsigned int* ticket;             // zero before the launch
+  PnpHdr* hdr;
+  uint8_t* inlier;                  // M
+  int32_t* hyp_counts;              // nullable (tap): the best count of each hypothesis
+};
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x)
+{
+  x ^= x >> 16; x *= 0x7feb352du;
+  x ^= x >> 15; x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// three distinct indices of [0, M), M >= 3
+__device__ __forceinline__ void sample_triple(uint32_t seed, int h, int M, int* tri)
+{
+  const uint32_t r0 = mix32(seed ^ mix32(3u * (uint32_t)h + 1u)), r1 = mix32(seed ^ mix32(3u * (uint32_t)h + 2u)),
+                 r2 = mix32(seed ^ mix32(3u * (uint32_t)h + 3u));
+  const int a = (int)(((uint64_t)r0 * (uint32_t)M) >> 32);
+  int b = (int)(((uint64_t)r1 * (uint32_t)(M - 1)) >> 32);
+  int c = (int)(((uint64_t)r2 * (uint32_t)(M - 2)) >> 32);
+  b += b >= a ? 1 : 0;
+  const int lo = min(a, b), hi = max(a, b);
+  c += c >= lo ? 1 : 0;
+  c += c >= hi ? 1 : 0;
+  tri[0] = a; tri[1] = b; tri[2] = c;
+}
+
+// symmetric 3x3 as (m00 m01 m02 m11 m12 m22)
+__device__ __forceinline__ void adj_sym(const double* m, double* o)
+{
+  o[0] = m[3] * m[5] - m[4] * m[4];
+  o[1] = m[2] * m[4] - m[1] * m[5];
+  o[2] = m[1] * m[4] - m[2] * m[3];
+  o[3] = m[0] * m[5] - m[2] * m[2];
+  o[4] = m[1] * m[2] - m[0] * m[4];
+  o[5] = m[0] * m[3] - m[1] * m[1];
+}
+__device__ __forceinline__ double dot_sym(const double* a, const double* b)
+{
+  return a[0] * b[0] + a[3] * b[3] + a[5] * b[5] + 2.0 * (a[1] * b[1] + a[2] * b[2] + a[4] * b[4]);
+}
+__device__ __forceinline__ double quad_sym(const double* q, const double* u, const double* v)
+{
+  return u[0] * (q[0] * v[0] + q[1] * v[1] + q[2] * v[2]) + u[1] * (q[1] * v[0] + q[3] * v[1] + q[4] * v[2]) +
+         u[2] * (q[2] * v[0] + q[4] * v[1] + q[5] * v[2]);
+}
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* o)
+{
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// a real root of r^3 + b r^2 + c r + d (finite b, c, d): a start beyond the turning points, from where Newton's iteration is monotone.
+// Where an intermediate overflows, that non-finite value is returned before it is compared; the caller tests the result.
+__device__ __forceinline__ double cubic_root(double b, double c, double d)
+{
+  const double disc = b * b - 3.0 * c;
+  if (!isfinite(disc)) return disc;
+  double r;
+  if (disc > 0.0) {
+    const double v = sqrt(disc);
+    const double t1 = (-b - v) / 3.0;
+    double k = ((t1 + b) * t1 + c) * t1 + d;
+    if (!isfinite(k)) return k;
+    if (k > 0.0) {                                            // the local maximum is above the axis: the root left of it
+      r = t1 - sqrt(k / v);
+    } else {                                                  // else the root right of the local minimum
+      const double t2 = (-b + v) / 3.0;
+      k = ((t2 + b) * t2 + c) * t2 + d;
+      r = t2 + sqrt(-k / v);
+    }
+  } else {                                                    // monotone: from the inflection
+    r = -b / 3.0;
+    if (fabs((3.0 * r + 2.0 * b) * r + c) < 1e-4) r = r + 1.0;
+  }
+  for (int it = 0; it < kNewtonSteps; ++it) {
+    const double fx = ((r + b) * r + c) * r + d;
+    const double fp = (3.0 * r + 2.0 * b) * r + c;
+    r = r - fx / fp;
+  }
+  return r;
+}
+
+__device__ __forceinline__ bool fin3(const double* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
+
+struct P3P {
+  bool valid[4];
+  double R[4][9], t[4][3];          // solution 2 p + r is root r of plane p
+};
+
+// the P3P of points X[3][3] seen at pixels z[3][2]; tools/pnp_model.py::_p3p, line by line
+__device__ __forceinline__ void p3p_solve(const PnpDev& d, const double (*X)[3], const double (*z)[2], P3P& out)
+{
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out.valid[k] = false;
+  double y[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double bx = (z[i][0] - d.cx) / d.fx, by = (z[i][1] - d.cy) / d.fy;
+    const double n = sqrt(bx * bx + by * by + 1.0);
+    y[i][0] = bx / n; y[i][1] = by / n; y[i][2] = 1.0 / n;
+  }
+  auto d2 = [](const double* p, const double* q) {
+    const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+    return dx * dx + dy * dy + dz * dz;
+  };
+  auto dot = [](const double* p, const double* q) { return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]; };
+  const double A12 = d2(X[0], X[1]), A13 = d2(X[0], X[2]), A23 = d2(X[1], X[2]);
+  const double S = A12 + A13 + A23;
+  if (!(isfinite(S) && S > 0.0)) return;
+  const double a12 = A12 / S, a13 = A13 / S, a23 = A23 / S;
+  const double b12 = -2.0 * dot(y[0], y[1]), b13 = -2.0 * dot(y[0], y[2]), b23 = -2.0 * dot(y[1], y[2]);
+  const double h12 = 0.5 * b12, h13 = 0.5 * b13, h23 = 0.5 * b23;
+  const double D1[6] = {a23, a23 * h12, 0.0, a23 - a12, -(a12 * h23), -a12};
+  const double D2[6] = {a23, 0.0, a23 * h13, -a13, -(a13 * h23), a23 - a13};
+  double J1[6], J2[6];
+  adj_sym(D1, J1);
+  adj_sym(D2, J2);
+  const double det1 = D1[0] * J1[0] + D1[1] * J1[1] + D1[2] * J1[2];
+  const double det2 = D2[0] * J2[0] + D2[1] * J2[1] + D2[2] * J2[2];
+  if (!(isfinite(det1) && isfinite(det2))) return;
+  const bool keep = fabs(det2) >= fabs(det1);                 // the cubic is made monic by the larger determinant
+  double Da[6], Db[6], Ja[6], Jb[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    Da[k] = keep ? D1[k] : D2[k]; Db[k] = keep ? D2[k] : D1[k];
+    Ja[k] = keep ? J1[k] : J2[k]; Jb[k] = keep ? J2[k] : J1[k];
+  }
+  const double deta = keep ? det1 : det2, detb = keep ? det2 : det1;
+  if (!(fabs(detb) > 0.0)) return;
+  const double cb = dot_sym(Da, Jb) / detb, cc = dot_sym(Ja, Db) / detb, cd = deta / detb;   // (a tiny detb can make them infinite)
+  if (!(isfinite(cb) && isfinite(cc) && isfinite(cd))) return;
+  const double g = cubic_root(cb, cc, cd);
+  if (!isfinite(g)) return;
+  double C[6], Q[6];
+  const bool q_b = fabs(g) <= 1.0;                            // on the planes Da = -g Db: the one that is not small there
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { C[k] = Da[k] + g * Db[k]; Q[k] = q_b ? Db[k] : Da[k]; }
+  // C = l m' + m l' with p = l x m: -adj(C) = p p', and C + [p]x = 2 m l'
+  double Jc[6], B[6];
+  adj_sym(C, Jc);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) B[k] = -Jc[k];
+  if (!(fin3(B) && fin3(B + 3))) return;
+  double bii, p[3];
+  if (B[0] >= B[3] && B[0] >= B[5]) { bii = B[0]; p[0] = B[0]; p[1] = B[1]; p[2] = B[2]; }
+  else if (B[3] >= B[5]) { bii = B[3]; p[0] = B[1]; p[1] = B[3]; p[2] = B[4]; }
+  else { bii = B[5]; p[0] = B[2]; p[1] = B[4]; p[2] = B[5]; }
+  if (!(bii > 0.0)) return;
+  const double beta = sqrt(bii);
+  p[0] = p[0] / beta; p[1] = p[1] / beta; p[2] = p[2] / beta;
+  const double N[3][3] = {{C[0], C[1] - p[2], C[2] + p[1]}, {C[1] + p[2], C[3], C[4] - p[0]}, {C[2] - p[1], C[4] + p[0], C[5]}};
+  if (!(fin3(N[0]) && fin3(N[1]) && fin3(N[2]))) return;
+  double best = -1.0;
+  double row[3] = {0.0, 0.0, 0.0}, col[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (fabs(N[j][k]) > best) {
+        best = fabs(N[j][k]);
+        row[0] = N[j][0]; row[1] = N[j][1]; row[2] = N[j][2];
+        col[0] = N[0][k]; col[1] = N[1][k]; col[2] = N[2][k];
+      }
+    }
+  }
+  const double sqS = sqrt(S);
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    const double n[3] = {pl == 0 ? row[0] : col[0], pl == 0 ? row[1] : col[1], pl == 0 ? row[2] : col[2]};
+    const double u[3] = {n[1] - n[2], n[2] - n[0], n[0] - n[1]};   // n x (1, 1, 1): never zero for a plane that meets the positive octant
+    double v[3];
+    cross3(n, u, v);
+    const double qa = quad_sym(Q, u, u), qb = quad_sym(Q, u, v), qc = quad_sym(Q, v, v);
+    const double disc = qb * qb - qa * qc;
+    if (!(isfinite(disc) && disc >= 0.0)) continue;
+    const double sq = sqrt(disc);
+    const double q = qb >= 0.0 ? -(qb + sq) : -(qb - sq);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const double s = r == 0 ? q : qc, t = r == 0 ? qa : q;     // the two roots (s : t) of qa s^2 + 2 qb s t + qc t^2
+      double l1 = s * u[0] + t * v[0], l2 = s * u[1] + t * v[1], l3 = s * u[2] + t * v[2];
+      const double w = 2.0 * (l1 * l1 + l2 * l2 + l3 * l3) + b12 * (l1 * l2) + b13 * (l1 * l3) + b23 * (l2 * l3);   // = a12 + a13 + a23 = 1
+      if (!(isfinite(w) && w > 0.0)) continue;
+      double sc = 1.0 / sqrt(w);
+      if (l1 < 0.0) sc = -sc;
+      l1 = l1 * sc; l2 = l2 * sc; l3 = l3 * sc;
+      for (int it = 0; it < kGnSteps; ++it) {
+        const double r0 = l1 * l1 + l2 * l2 + b12 * (l1 * l2) - a12;
+        const double r1 = l1 * l1 + l3 * l3 + b13 * (l1 * l3) - a13;
+        const double r2 = l2 * l2 + l3 * l3 + b23 * (l2 * l3) - a23;
+        const double j00 = 2.0 * l1 + b12 * l2, j01 = 2.0 * l2 + b12 * l1;
+        const double j10 = 2.0 * l1 + b13 * l3, j12 = 2.0 * l3 + b13 * l1;
+        const double j21 = 2.0 * l2 + b23 * l3, j22 = 2.0 * l3 + b23 * l2;
+        const double det = -(j00 * (j12 * j21)) - j01 * (j10 * j22);
+        // Cramer for [[j00 j01 0] [j10 0 j12] [0 j21 j22]]
+        const double e1 = (r0 * (-(j12 * j21)) - j01 * (r1 * j22 - j12 * r2)) / det;
+        const double e2 = (j00 * (r1 * j22 - j12 * r2) - r0 * (j10 * j22)) / det;
+        const double e3 = (j00 * (-(r1 * j21)) - j01 * (j10 * r2) + r0 * (j10 * j21)) / det;
+        l1 = l1 - e1; l2 = l2 - e2; l3 = l3 - e3;
+      }
+      if (!(isfinite(l1) && isfinite(l2) && isfinite(l3) && l1 > 0.0 && l2 > 0.0 && l3 > 0.0)) continue;
+      l1 = l1 * sqS; l2 = l2 * sqS; l3 = l3 * sqS;
+      const double Y[3][3] = {{l1 * y[0][0], l1 * y[0][1], l1 * y[0][2]}, {l2 * y[1][0], l2 * y[1][1], l2 * y[1][2]}, {l3 * y[2][0], l3 * y[2][1], l3 * y[2][2]}};
+      const double p1[3] = {X[1][0] - X[0][0], X[1][1] - X[0][1], X[1][2] - X[0][2]};
+      const double p2[3] = {X[2][0] - X[0][0], X[2][1] - X[0][1], X[2][2] - X[0][2]};
+      const double q1[3] = {Y[1][0] - Y[0][0], Y[1][1] - Y[0][1], Y[1][2] - Y[0][2]};
+      const double q2[3] = {Y[2][0] - Y[0][0], Y[2][1] - Y[0][1], Y[2][2] - Y[0][2]};
+      double p3[3], q3[3], w1[3], w2[3];
+      cross3(p1, p2, p3);
+      cross3(q1, q2, q3);
+      const double det = p3[0] * p3[0] + p3[1] * p3[1] + p3[2] * p3[2];
+      if (!(isfinite(det) && det > 0.0)) continue;
+      cross3(p2, p3, w1);                                     // rows of the inverse of [p1 p2 p3], times det
+      cross3(p3, p1, w2);
+      const int k = 2 * pl + r;
+      bool ok = true;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out.R[k][a * 3 + c] = (q1[a] * w1[c] + q2[a] * w2[c] + q3[a] * p3[c]) / det;
+        out.t[k][a] = Y[0][a] - (out.R[k][a * 3] * X[0][0] + out.R[k][a * 3 + 1] * X[0][1] + out.R[k][a * 3 + 2] * X[0][2]);
+        ok = ok && fin3(&out.R[k][a * 3]) && isfinite(out.t[k][a]);
+      }
+      out.valid[k] = ok;
+    }
+  }
+}
+
+__device__ __forceinline__ void load_triple(const PnpDev& d, int h, double (*X)[3], double (*z)[2])
+{
+  int tri[3];
+  sample_triple(d.seed, h, d.M, tri);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    X[i][0] = d.xyz[3 * tri[i]]; X[i][1] = d.xyz[3 * tri[i] + 1]; X[i][2] = d.xyz[3 * tri[i] + 2];
+    z[i][0] = d.uv[2 * tri[i]]; z[i][1] = d.uv[2 * tri[i] + 1];
+  }
+}
+
+__device__ __forceinline__ bool is_inlier(const PnpDev& d, const double* R, const double* t, int i)
+{
+  const double x = d.xyz[3 * i], y = d.xyz[3 * i + 1], z = d.xyz[3 * i + 2];
+  const double px = R[0] * x + R[1] * y + R[2] * z + t[0];
+  const double py = R[3] * x + R[4] * y + R[5] * z + t[1];
+  const double pz = R[6] * x + R[7] * y + R[8] * z + t[2];
+  const double ex = d.fx * (px / pz) + d.cx - d.uv[2 * i];
+  const double ey = d.fy * (py / pz) + d.cy - d.uv[2 * i + 1];
+  const double e2 = ex * ex + ey * ey;
+  return isfinite(pz) && pz > 0.0 && isfinite(e2) && e2 <= d.thr2;
+}
+
+__device__ __forceinline__ void rot_to_quat(const double* R, double* q)
+{
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0.0) {
+    const double s = sqrt(tr + 1.0) * 2.0;
+    q[0] = (R[7] - R[5]) / s; q[1] = (R[2] - R[6]) / s; q[2] = (R[3] - R[1]) / s; q[3] = 0.25 * s;
+  } else if (R[0] > R[4] && R[0] > R[8]) {
+    const double s = sqrt(1.0 + R[0] - R[4] - R[8]) * 2.0;
+    q[0] = 0.25 * s; q[1] = (R[1] + R[3]) / s; q[2] = (R[2] + R[6]) / s; q[3] = (R[7] - R[5]) / s;
+  } else if (R[4] > R[8]) {
+    const double s = sqrt(1.0 + R[4] - R[0] - R[8]) * 2.0;
+    q[0] = (R[1] + R[3]) / s; q[1] = 0.25 * s; q[2] = (R[5] + R[7]) / s; q[3] = (R[2] - R[6]) / s;
+  } else {
+    const double s = sqrt(1.0 + R[8] - R[0] - R[4]) * 2.0;
+    q[0] = (R[2] + R[6]) / s; q[1] = (R[5] + R[7]) / s; q[2] = 0.25 * s; q[3] = (R[3] - R[1]) / s;
+  }
+  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double sg = q[3] < 0.0 ? -n : n;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = q[k] / sg;
+}
+
+__global__ __launch_bounds__(256) void k_pnp_ransac(PnpDev d)
+{
+  __shared__ unsigned long long s_best[4];
+  __shared__ int s_last;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int h = blockIdx.x * 4 + wave;
+  unsigned long long best_key = 0;
+  if (h < d.H) {
+    double X[3][3], z[3][2];
+    load_triple(d, h, X, z);
+    P3P sol;
+    p3p_solve(d, X, z, sol);
+    int hyp_best = 0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      int count = 0;
+      if (sol.valid[s]) {                                     // (uniform: every lane solved the same triple)
+        for (int base = 0; base < d.M; base += 64) {
+          const int i = base + lane;
+          const bool in = i < d.M && is_inlier(d, sol.R[s], sol.t[s], i);
+          count += __popcll(__ballot(in));
+        }
+      }
+      hyp_best = max(hyp_best, count);
+      best_key = max(best_key, ((unsigned long long)(unsigned)count << 32) | (unsigned)~(4 * h + s));
+    }
+    if (d.hyp_counts && lane == 0) d.hyp_counts[h] = hyp_best;
+  }
+  if (lane == 0) s_best[wave] = best_key;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // one atomic per workgroup, and none when the word already holds a larger key (it only ever grows)
+    const unsigned long long k = max(max(s_best[0], s_best[1]), max(s_best[2], s_best[3]));
+    if (k > __hip_atomic_load(d.best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d.best, k);
+    // the ticket releases this workgroup's key and, in the last workgroup, acquires everybody's
+    const unsigned int prev = __hip_atomic_fetch_add(d.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = prev + 1u == gridDim.x;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // ---- finish: the winner's pose, mask and header ----
+  const unsigned long long key = __hip_atomic_load(d.best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int n_best = (int)(key >> 32);
+  const int id = (int)~(unsigned)key;                         // 4 h + s
+  const bool found = n_best >= kMinInliers;
+  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
+  if (found) {
+    double X[3][3], z[3][2];
+    load_triple(d, id >> 2, X, z);
+    P3P sol;
+    p3p_solve(d, X, z, sol);
+    const int s = id & 3;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k == s) {
+#pragma unroll
+        for (int a = 0; a < 9; ++a) R[a] = sol.R[k][a];
+        t[0] = sol.t[k][0]; t[1] = sol.t[k][1]; t[2] = sol.t[k][2];
+      }
+    }
+  }
+  for (int i = threadIdx.x; i < d.M; i += blockDim.x) d.inlier[i] = found && is_inlier(d, R, t, i) ? 1 : 0;
+  if (threadIdx.x == 0) {
+    double q[4];
+    rot_to_quat(R, q);
+    d.hdr->pose[0] = q[0]; d.hdr->pose[1] = q[1]; d.hdr->pose[2] = q[2]; d.hdr->pose[3] = q[3];
+    d.hdr->pose[4] = t[0]; d.hdr->pose[5] = t[1]; d.hdr->pose[6] = t[2];
+    d.hdr->found = found ? 1 : 0;
+    d.hdr->n_inliers = found ? n_best : 0;
+    d.hdr->best = found ? id : -1;
+    d.hdr->pad = 0;
+  }
+}
+
+__global__ void k_pnp_samples(uint32_t seed, int M, int H, int32_t* out)
+{
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= H) return;
+  int tri[3];
+  sample_triple(seed, h, M, tri);
+  out[3 * h] = tri[0]; out[3 * h + 1] = tri[1]; out[3 * h + 2] = tri[2];
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+
+bool finite4(const double* K4) { return std::isfinite(K4[0]) && std::isfinite(K4[1]) && std::isfinite(K4[2]) && std::isfinite(K4[3]); }
+
+// One arena for the whole of ComputeCorrectPose:  [best | ticket | xyz | uv | pose in]  go up in one copy,
+// [RANSAC header | refined pose | inlier count | RANSAC mask | outlier flags] come back in one copy.
+struct PnpPlan {
+  int M = 0, H = 0;
+  size_t o_best = 0, o_xyz = 0, o_uv = 0, o_pose = 0, in_bytes = 0;
+  size_t o_hdr = 0, o_pose_out = 0, o_n = 0, o_mask = 0, o_out = 0, out_end = 0;
+  size_t o_err = 0, o_level = 0, o_counts = 0, bytes = 0;
+};
+
+PnpPlan plan_pnp(int M, int H, bool tap)
+{
+  PnpPlan p;
+  p.M = M; p.H = H;
+  Layout lay;
+  p.o_best = lay.take(16);
+  p.o_xyz = lay.take(sizeof(double) * 3 * (size_t)M);
+  p.o_uv = lay.take(sizeof(double) * 2 * (size_t)M);
+  p.o_pose = lay.take(sizeof(double) * 8);
+  p.in_bytes = lay.off;
+  p.o_hdr = lay.take(sizeof(PnpHdr));
+  p.o_pose_out = lay.take(sizeof(double) * 8);
+  p.o_n = lay.take(sizeof(int32_t) * 2);
+  p.o_mask = lay.take((size_t)M);
+  p.o_out = lay.take((size_t)M);
+  p.out_end = lay.off;
+  const bool generic = M > po_register_edges();
+  p.o_err = lay.take(generic ? sizeof(double) * 2 * (size_t)M : 0);
+  p.o_level = lay.take(generic ? (size_t)M : 0);
+  p.o_counts = lay.take(tap ? sizeof(int32_t) * (size_t)H : 0);
+  p.bytes = lay.off;
+  return p;
+}
+
+// stage the inputs (pose7 nullable) and send them up
+ssx_status pnp_upload(ssx_ctx* ctx, const PnpPlan& p, const double* xyz, const double* uv, const double* pose7)
+{
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(p.bytes));
+  SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(p.bytes));
+  char* hs = ctx->pnp_stage.as<char>();
+  memset(hs + p.o_best, 0, 16);
+  memcpy(hs + p.o_xyz, xyz, sizeof(double) * 3 * (size_t)p.M);
+  memcpy(hs + p.o_uv, uv, sizeof(double) * 2 * (size_t)p.M);
+  if (pose7) memcpy(hs + p.o_pose, pose7, sizeof(double) * 7);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(ctx->pnp_arena.p, hs, p.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  return SSX_OK;
+}
+
+ssx_status pnp_launch_ransac(ssx_ctx* ctx, const PnpPlan& p, const double* K4, double reproj_px, uint32_t seed, bool tap)
+{
+  char* base = ctx->pnp_arena.as<char>();
+  PnpDev d;
+  d.M = p.M; d.H = p.H; d.seed = seed;
+  d.fx = K4[0]; d.fy = K4[1]; d.cx = K4[2]; d.cy = K4[3]; d.thr2 = reproj_px * reproj_px;
+  d.xyz = (const double*)(base + p.o_xyz); d.uv = (const double*)(base + p.o_uv);
+  d.best = (unsigned long long*)(base + p.o_best); d.ticket = (unsigned int*)(base + p.o_best + 8);
+  d.hdr = (PnpHdr*)(base + p.o_hdr); d.inlier = (uint8_t*)(base + p.o_mask);
+  d.hyp_counts = tap ? (int32_t*)(base + p.o_counts) : nullptr;
+  SSX_PROF(ctx, KID_PNP_RANSAC, hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)((p.H + 3) / 4)), dim3(256), 0, ctx->stream, d));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  return SSX_OK;
+}
+
+// OptimizeCurrentPose from the pose at pose_in (device): one warm-up optimize(10), then 4 rounds x optimize(10)
+ssx_status pnp_launch_refine(ssx_ctx* ctx, const PnpPlan& p, const double* K4, const double* pose_in, const int32_t* gate, double chi2_th, double huber_delta)
+{
+  char* base = ctx->pnp_arena.as<char>();
+  PoDeviceJob j;
+  j.M = p.M; j.warmup = 1; j.rounds = 4; j.iters = 10; j.chi2_th = chi2_th; j.huber_delta = huber_delta;
+  for (int k = 0; k < 4; ++k) j.K4[k] = K4[k];
+  j.xyz = (const double*)(base + p.o_xyz); j.uv = (const double*)(base + p.o_uv);
+  j.pose_in = pose_in; j.gate = gate;
+  j.err = (double*)(base + p.o_err); j.level = (uint8_t*)(base + p.o_level);
+  j.outlier = (uint8_t*)(base + p.o_out); j.pose_out = (double*)(base + p.o_pose_out); j.n_inliers = (int32_t*)(base + p.o_n);
+  SSX_HIP_TRY(ctx, po_launch_device(ctx, j));
+  return SSX_OK;
+}
+
+// everything between o_hdr and out_end, and the synchronisation of the call
+ssx_status pnp_download(ssx_ctx* ctx, const PnpPlan& p, size_t extra_off = 0, size_t extra_bytes = 0)
+{
+  char* hs = ctx->pnp_stage.as<char>();
+  char* base = ctx->pnp_arena.as<char>();
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + p.o_hdr, base + p.o_hdr, p.out_end - p.o_hdr, hipMemcpyDeviceToHost, ctx->stream));
+  if (extra_bytes) SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + extra_off, base + extra_off, extra_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return SSX_OK;
+}
+
+bool pnp_args_ok(ssx_ctx* ctx, const double* K4, int32_t M, const double* xyz, const double* uv, int32_t max_iters)
+{
+  return ctx && K4 && M >= 0 && (M == 0 || (xyz && uv)) && max_iters >= 1 && max_iters <= SSX_PNP_MAX_ITERS && finite4(K4);
+}
+
+const double kIdentity[7] = {0, 0, 0, 1, 0, 0, 0};
+
+}  // namespace
+
+extern "C" {
+
+ssx_status ssx_pnp_ransac(ssx_ctx* ctx, const double* K4, int32_t M, const double* xyz, const double* uv, int32_t max_iters, double reproj_px,
+                          uint32_t seed, double* pose_out, uint8_t* inlier_out, int32_t* n_inliers, int32_t* best_hypothesis, int32_t* found)
+{
+  if (!pnp_args_ok(ctx, K4, M, xyz, uv, max_iters) || !pose_out || !n_inliers || !found || !(reproj_px >= 0.0)) return SSX_ERR_INVALID_ARG;
+  *found = 0; *n_inliers = 0;
+  if (best_hypothesis) *best_hypothesis = -1;
+  memcpy(pose_out, kIdentity, sizeof(kIdentity));
+  if (inlier_out && M > 0) memset(inlier_out, 0, (size_t)M);
+  if (M < 3) return SSX_OK;                                   // no triple to sample
+  const PnpPlan p = plan_pnp(M, max_iters, false);
+  ssx_status st = pnp_upload(ctx, p, xyz, uv, nullptr);
+  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, reproj_px, seed, false);
+  if (st == SSX_OK) st = pnp_download(ctx, p);
+  if (st != SSX_OK) return st;
+  const char* hs = ctx->pnp_stage.as<char>();
+  PnpHdr hdr;
+  memcpy(&hdr, hs + p.o_hdr, sizeof(hdr));
+  *found = hdr.found; *n_inliers = hdr.n_inliers;
+  if (best_hypothesis) *best_hypothesis = hdr.best;
+  memcpy(pose_out, hdr.pose, sizeof(double) * 7);
+  if (inlier_out) memcpy(inlier_out, hs + p.o_mask, (size_t)M);
+  return SSX_OK;
+}
+
+ssx_status ssx_loop_pose_opt(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz, const double* uv, double chi2_th,
+                             double huber_delta, uint8_t* inlier_out, int32_t* n_inliers)
+{
+  if (!ctx || !pose_io || !K4 || M < 0 || (M > 0 && (!xyz || !uv)) || !finite4(K4)) return SSX_ERR_INVALID_ARG;
+  if (n_inliers) *n_inliers = 0;
+  if (M == 0) return SSX_OK;
+  const PnpPlan p = plan_pnp(M, 0, false);
+  ssx_status st = pnp_upload(ctx, p, xyz, uv, pose_io);
+  if (st == SSX_OK) st = pnp_launch_refine(ctx, p, K4, (const double*)(ctx->pnp_arena.as<char>() + p.o_pose), nullptr, chi2_th, huber_delta);
+  if (st == SSX_OK) st = pnp_download(ctx, p);
+  if (st != SSX_OK) return st;
+  const char* hs = ctx->pnp_stage.as<char>();
+  memcpy(pose_io, hs + p.o_pose_out, sizeof(double) * 7);
+  if (n_inliers) memcpy(n_inliers, hs + p.o_n, sizeof(int32_t));
+  if (inlier_out) for (int32_t i = 0; i < M; ++i) inlier_out[i] = !reinterpret_cast<const uint8_t*>(hs + p.o_out)[i];
+  return SSX_OK;
+}
+
+ssx_status ssx_loop_compute_pose(ssx_ctx* ctx, int32_t n_pairs, const double* loop_xyz, const uint8_t* has_point, const double* cur_uv,
+                                 const double* T_cur, const double* T_loop, const double* K4, int32_t max_iters, uint32_t seed, uint8_t* kept,
+                                 ssx_loop_pose_result* out)
+{
+  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!loop_xyz || !has_point || !cur_uv || !kept)) || !T_cur || !T_loop || !K4 || !out || max_iters < 1 ||
+      max_iters > SSX_PNP_MAX_ITERS || !finite4(K4))
+    return SSX_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  out->best_hypothesis = -1;
+  memcpy(out->corrected_pose, kIdentity, sizeof(kIdentity));
+  memcpy(out->relative_to_loop, kIdentity, sizeof(kIdentity));
+  // the pairs whose map point is alive (loopclosing.cpp:153-174; the others are erased from the set)
+  std::vector<double> xyz, uv;
+  std::vector<int32_t> src;
+  for (int32_t i = 0; i < n_pairs; ++i) {
+    kept[i] = has_point[i] ? 1 : 0;
+    if (!has_point[i]) continue;
+    src.push_back(i);
+    xyz.insert(xyz.end(), loop_xyz + 3 * (size_t)i, loop_xyz + 3 * (size_t)i + 3);
+    uv.insert(uv.end(), cur_uv + 2 * (size_t)i, cur_uv + 2 * (size_t)i + 2);
+  }
+  const int32_t M = (int32_t)src.size();
+  out->n_with_point = M;
+  if (M < 10) { out->verdict = SSX_LOOP_FEW_MAP_POINTS; return SSX_OK; }           // :193
+  const double thr = 5.991, chi2_th = 5.991, huber_delta = 1.0;                   // :206, :301, g2o's RobustKernelHuber
+  const PnpPlan p = plan_pnp(M, max_iters, false);
+  ssx_status st = pnp_upload(ctx, p, xyz.data(), uv.data(), nullptr);
+  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, thr, seed, false);
+  const PnpHdr* dh = (const PnpHdr*)(ctx->pnp_arena.as<char>() + p.o_hdr);
+  if (st == SSX_OK) st = pnp_launch_refine(ctx, p, K4, dh->pose, &dh->found, chi2_th, huber_delta);
+  if (st == SSX_OK) st = pnp_download(ctx, p);
+  if (st != SSX_OK) return st;
+  const char* hs = ctx->pnp_stage.as<char>();
+  PnpHdr hdr;
+  memcpy(&hdr, hs + p.o_hdr, sizeof(hdr));
+  out->n_ransac_inliers = hdr.n_inliers;
+  out->best_hypothesis = hdr.best;
+  if (!hdr.found) { out->verdict = SSX_LOOP_NO_POSE; return SSX_OK; }              // the exception of :203-210
+  memcpy(out->corrected_pose, hs + p.o_pose_out, sizeof(double) * 7);
+  int32_t n_in = 0;
+  memcpy(&n_in, hs + p.o_n, sizeof(int32_t));
+  out->n_inliers = n_in;
+  const uint8_t* outl = reinterpret_cast<const uint8_t*>(hs + p.o_out);
+  for (int32_t k = 0; k < M; ++k) kept[src[k]] = outl[k] ? 0 : 1;                  // the erase of :338-344
+  if (n_in < 10) { out->verdict = SSX_LOOP_FEW_INLIERS; return SSX_OK; }           // :219
+  double inv[7], rel[7], lg[6];
+  ssx::se3_inverse(out->corrected_pose, inv);
+  ssx::se3_mul(T_cur, inv, rel);
+  ssx::se3_log(rel, lg);
+  double n2 = 0.0;
+  for (int k = 0; k < 6; ++k) n2 += lg[k] * lg[k];
+  out->error = std::sqrt(n2);                                                     // :224-225
+  out->need_correct = (out->error > 1 && out->error < 15) ? 1 : 0;                 // :226
+  ssx::se3_inverse(T_loop, inv);
+  ssx::se3_mul(out->corrected_pose, inv, out->relative_to_loop);                   // :237-238
+  out->verdict = SSX_LOOP_OK;
+  return SSX_OK;
+}
+
+#ifndef SSX_NO_TEST_HOOKS
+ssx_status ssx_pnp_debug_samples(ssx_ctx* ctx, uint32_t seed, int32_t M, int32_t H, int32_t* triples_out)
+{
+  if (!ctx || M < 3 || H < 1 || H > SSX_PNP_MAX_ITERS || !triples_out) return SSX_ERR_INVALID_ARG;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(int32_t) * 3 * (size_t)H;
+  SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(bytes));
+  SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(bytes));
+  hipLaunchKernelGGL(k_pnp_samples, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, seed, M, H, ctx->pnp_arena.as<int32_t>());
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(ctx->pnp_stage.p, ctx->pnp_arena.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(triples_out, ctx->pnp_stage.p, bytes);
+  return SSX_OK;
+}
+
+ssx_status ssx_pnp_debug_counts(ssx_ctx* ctx, const double* K4, int32_t M, const double* xyz, const double* uv, int32_t max_iters, double reproj_px,
+                                uint32_t seed, int32_t* counts_out)
+{
+  if (!pnp_args_ok(ctx, K4, M, xyz, uv, max_iters) || M < 3 || !counts_out) return SSX_ERR_INVALID_ARG;
+  const PnpPlan p = plan_pnp(M, max_iters, true);
+  ssx_status st = pnp_upload(ctx, p, xyz, uv, nullptr);
+  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, reproj_px, seed, true);
+  if (st == SSX_OK) st = pnp_download(ctx, p, p.o_counts, sizeof(int32_t) * (size_t)max_iters);
+  if (st != SSX_OK) return st;
+  memcpy(counts_out, ctx->pnp_stage.as<char>() + p.o_counts, sizeof(int32_t) * (size_t)max_iters);
+  return SSX_OK;
+}
+#endif
+
+}  // extern "C"

@@ -15,9 +15,15 @@
 // (thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:58-175) redundantly on identical values -- no
 // broadcast, no second barrier.  k_pose_only_generic (any M) is the same procedure with the edges in global memory
 // and an LDS tree reduction.
+//
+// LoopClosing::OptimizeCurrentPose (src/ssvio/loopclosing.cpp:245-351) is the same procedure behind one extra optimize(10) over all
+// edges (:305-306), and g2o restarts lambda and ni at iteration 0 of every optimize(): PoDev::warmup counts such passes (no
+// classification behind them, the robust kernel on).  Its initial pose is the result of a kernel (pnp.hip), so PoDev::pose may be
+// device memory and PoDev::gate a device word that calls the whole launch off (po_launch_device, pose_only.hpp).
 #include <cmath>
 
 #include "ctx.hpp"
+#include "pose_only.hpp"
 #include "se3.hpp"
 
 namespace {
@@ -34,9 +40,11 @@ struct PoDev {
   double* err;         // M x 2 (last computed error of each edge, like g2o's _error)
   uint8_t* level;      // M: 1 = outlier level (not optimised)
   uint8_t* outlier;    // M: features[i]->is_outlier_
-  double* pose;        // 7 in (the generic kernel also writes its result here)
+  const double* pose;  // 7 in (never written: it may be another kernel's result, pose_only.hpp)
   double* pose_out;    // 7 out
   int* n_inliers;
+  int warmup;          // optimize(iters) passes over all edges before the classified rounds (0: EstimateCurrentPose)
+  const int* gate;     // nullable: *gate == 0 ends the launch before it writes anything
 };
 
 __device__ __forceinline__ void po_error(const double* T, const PoDev& d, int i, double* e, double* pc)
@@ -68,6 +76,7 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
   __shared__ double sCtl[8];      // 0 lambda, 1 ni, 2 currentChi, 3 rho, 4 qmax, 5 stop flag, 6 accepted
   __shared__ int sUseKernel;
   const int t = threadIdx.x;
+  if (d.gate && *d.gate == 0) return;
   if (t < 7) sT[t] = d.pose[t];
   if (t == 0) sUseKernel = 1;
   for (int i = t; i < d.M; i += PT) { d.level[i] = 0; d.outlier[i] = 0; d.err[2 * i] = 0.0; d.err[2 * i + 1] = 0.0; }
@@ -94,7 +103,7 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
   };
 
   int cnt_outliers = 0;
-  for (int round = 0; round < d.rounds; ++round) {
+  for (int round = -d.warmup; round < d.rounds; ++round) {   // round < 0: a warm-up pass
     // initializeOptimization(0): only level-0 edges are active
     int mine = 0;
     for (int i = t; i < d.M; i += PT) mine += !d.level[i];
@@ -230,6 +239,7 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
       __syncthreads();
     }
     __syncthreads();
+    if (round < 0) continue;
     // frontend.cpp:243-268: recompute the error only for features flagged outlier, classify, set levels
     {
       double T[7];
@@ -412,6 +422,7 @@ template <int EPT>
 __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
 {
   const PoDev d = dv[blockIdx.x];
+  if (d.gate && *d.gate == 0) return;
   __shared__ double sPart[2][NRED][NW];
   __shared__ double sT[27][PT];
   __shared__ double sTot[27];
@@ -459,7 +470,7 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
   };
 
   int cnt_outliers = 0;
-  for (int round = 0; round < d.rounds; ++round) {
+  for (int round = -d.warmup; round < d.rounds; ++round) {   // round < 0: a warm-up pass
     double na = 0.0;
 #pragma unroll
     for (int k = 0; k < EPT; ++k) na += (valid[k] && !level[k]) ? 1.0 : 0.0;
@@ -544,6 +555,7 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
       }
       if (stop) break;                                         // Terminate: optimize() stops iterating
     }
+    if (round < 0) continue;
     // frontend.cpp:243-268: recompute the error only for features flagged outlier, classify, set levels
     double co = 0.0;
 #pragma unroll
@@ -601,7 +613,7 @@ ssx_status pose_only_generic(ssx_ctx* ctx, double* pose_io, const double* K4, in
   char* base = arena.as<char>();
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   PoDev d;
-  d.M = M; d.rounds = rounds; d.iters = iters; d.chi2_th = chi2_th; d.huber_delta = huber_delta;
+  d.M = M; d.rounds = rounds; d.iters = iters; d.chi2_th = chi2_th; d.huber_delta = huber_delta; d.warmup = 0; d.gate = nullptr;
   d.K = ssx::Cam{K4[0], K4[1], K4[2], K4[3]};
   d.xyz = (const double*)(base + o_xyz); d.uv = (const double*)(base + o_uv);
   d.err = (double*)(base + o_err); d.level = (uint8_t*)(base + o_level); d.outlier = (uint8_t*)(base + o_out);
@@ -617,6 +629,29 @@ ssx_status pose_only_generic(ssx_ctx* ctx, double* pose_io, const double* K4, in
 }
 
 }  // namespace
+
+int po_register_edges() { return PT * 6; }
+
+hipError_t po_launch_device(ssx_ctx* ctx, const PoDeviceJob& j)
+{
+  PoDev d;
+  d.M = j.M; d.rounds = j.rounds; d.iters = j.iters; d.chi2_th = j.chi2_th; d.huber_delta = j.huber_delta; d.warmup = j.warmup; d.gate = j.gate;
+  d.K = ssx::Cam{j.K4[0], j.K4[1], j.K4[2], j.K4[3]};
+  d.xyz = j.xyz; d.uv = j.uv; d.err = j.err; d.level = j.level; d.outlier = j.outlier;
+  d.pose = j.pose_in; d.pose_out = j.pose_out; d.n_inliers = j.n_inliers;
+  if (j.M > PT * 6) {
+    SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic, dim3(1), dim3(PT), 0, ctx->stream, d));
+    return hipGetLastError();
+  }
+  // the register-resident kernels read their descriptor from memory (one per workgroup): the pinned block, as the batch does
+  hipError_t e = ctx->po_stage.reserve(sizeof(PoDev), 2.0);
+  if (e != hipSuccess) return e;
+  PoDev* dv = ctx->po_stage.as<PoDev>();
+  *dv = d;
+  if (j.M <= PT * 2) SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<2>, dim3(1), dim3(PT), 0, ctx->stream, (const PoDev*)dv));
+  else SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<6>, dim3(1), dim3(PT), 0, ctx->stream, (const PoDev*)dv));
+  return hipGetLastError();
+}
 
 // n problems in one call (one frame of each of n streams: FrontEnd::EstimateCurrentPose, frontend.cpp:184-300): one workgroup per
 // problem, ONE launch per register class of the kernel.  Per problem the bits of ssx_pose_only_opt (which is a batch of one).
@@ -664,7 +699,7 @@ extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx
         memcpy(in + 3 * M, q.uv, sizeof(double) * 2 * M);
         memcpy(in + 5 * M, q.pose_io, sizeof(double) * 7);
         PoDev& d = dv[k];
-        d.M = q.M; d.rounds = q.rounds; d.iters = q.iters; d.chi2_th = q.chi2_th; d.huber_delta = q.huber_delta;
+        d.M = q.M; d.rounds = q.rounds; d.iters = q.iters; d.chi2_th = q.chi2_th; d.huber_delta = q.huber_delta; d.warmup = 0; d.gate = nullptr;
         d.K = ssx::Cam{q.K4[0], q.K4[1], q.K4[2], q.K4[3]};
         d.xyz = in; d.uv = in + 3 * M; d.pose = in + 5 * M;
         d.err = nullptr; d.level = nullptr;                          // (the register-resident kernels keep both in registers)

@@ -1,12 +1,18 @@
-"""The keyframe database of LoopClosing, resident on the device -- ssx_kfdb_* of include/ssx.h: AddToKeyframeDatabase, DetectLoop
-and MatchFeatures (reference: src/ssvio/loopclosing.cpp:646-649, :72-103, :105-145)."""
+"""Loop closing on the device -- include/ssx.h.
+
+KeyframeDatabase       ssx_kfdb_*: AddToKeyframeDatabase, DetectLoop and MatchFeatures (reference: src/ssvio/loopclosing.cpp:646-649,
+                       :72-103, :105-145)
+pnp_ransac             ssx_pnp_ransac: the cv::solvePnPRansac call of ComputeCorrectPose (:205-206) under the contract of
+                       tools/pnp_model.py
+loop_pose_opt          ssx_loop_pose_opt: OptimizeCurrentPose (:245-351)
+compute_correct_pose   ssx_loop_compute_pose: ComputeCorrectPose (:147-243) as a whole"""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import SSX_ERR_CAPACITY, Context, dbl_p, i32_p, u8_p
+from ._lib import SSX_ERR_CAPACITY, Context, dbl_p, i32_p, ptr, u8_p
 
 i64_p = C.POINTER(C.c_int64)
 
@@ -100,3 +106,82 @@ class KeyframeDatabase:
                 e.n_pairs = n.value
             raise
         return pairs[:n.value].copy(), md.value
+
+
+# ---- the pose correction: ComputeCorrectPose / OptimizeCurrentPose ---------------------------------------------------------------
+LOOP_OK, LOOP_FEW_MAP_POINTS, LOOP_NO_POSE, LOOP_FEW_INLIERS = 0, 1, 2, 3      # ssx_loop_verdict
+PNP_MAX_ITERS = 4096                                                           # SSX_PNP_MAX_ITERS
+
+
+class LoopPoseResult(C.Structure):
+    """ssx_loop_pose_result"""
+    _fields_ = [("verdict", C.c_int32), ("n_with_point", C.c_int32), ("n_ransac_inliers", C.c_int32), ("best_hypothesis", C.c_int32),
+                ("n_inliers", C.c_int32), ("need_correct", C.c_int32), ("error", C.c_double), ("corrected_pose", C.c_double * 7),
+                ("relative_to_loop", C.c_double * 7)]
+
+
+def _bind_pose(lib):
+    if getattr(lib, "_loop_pose_bound", False):
+        return
+    lib.ssx_pnp_ransac.argtypes = [C.c_void_p, dbl_p, C.c_int32, dbl_p, dbl_p, C.c_int32, C.c_double, C.c_uint32, dbl_p, u8_p, i32_p, i32_p, i32_p]
+    lib.ssx_loop_pose_opt.argtypes = [C.c_void_p, dbl_p, dbl_p, C.c_int32, dbl_p, dbl_p, C.c_double, C.c_double, u8_p, i32_p]
+    lib.ssx_loop_compute_pose.argtypes = [C.c_void_p, C.c_int32, dbl_p, u8_p, dbl_p, dbl_p, dbl_p, dbl_p, C.c_int32, C.c_uint32, u8_p,
+                                          C.POINTER(LoopPoseResult)]
+    lib._loop_pose_bound = True
+
+
+def _f64(a, cols):
+    return np.ascontiguousarray(a, dtype=np.float64).reshape(-1, cols)
+
+
+def pnp_ransac(ctx: Context, K, xyz, uv, max_iters=100, reproj_px=5.991, seed=0):
+    """-> dict(found, pose (qx qy qz qw tx ty tz), inliers uint8 [M], n_inliers, best = 4 h + s of the winner or -1).  All
+    max_iters hypotheses are scored; the same arguments give the same bytes."""
+    _bind_pose(ctx.lib)
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    xyz, uv = _f64(xyz, 3), _f64(uv, 2)
+    if len(xyz) != len(uv) or K.size != 4:
+        raise ValueError("one pixel per point, K = (fx, fy, cx, cy)")
+    M = len(xyz)
+    pose, inl = np.zeros(7), np.zeros(max(M, 1), np.uint8)
+    n, best, found = C.c_int32(), C.c_int32(), C.c_int32()
+    ctx.check(ctx.lib.ssx_pnp_ransac(ctx.handle, ptr(K, dbl_p), M, ptr(xyz, dbl_p), ptr(uv, dbl_p), int(max_iters), float(reproj_px),
+                                     int(seed) & 0xFFFFFFFF, ptr(pose, dbl_p), ptr(inl, u8_p), C.byref(n), C.byref(best), C.byref(found)))
+    return dict(found=bool(found.value), pose=pose, inliers=inl[:M], n_inliers=n.value, best=best.value)
+
+
+def loop_pose_opt(ctx: Context, pose, K, xyz, uv, chi2_th=5.991, huber_delta=1.0):
+    """OptimizeCurrentPose from `pose` over all pairs -> dict(pose, inliers uint8 [M], n_inliers)"""
+    _bind_pose(ctx.lib)
+    pose = np.ascontiguousarray(pose, dtype=np.float64).copy()
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    xyz, uv = _f64(xyz, 3), _f64(uv, 2)
+    if len(xyz) != len(uv) or K.size != 4 or pose.size != 7:
+        raise ValueError("one pixel per point, K = (fx, fy, cx, cy), pose = 7 doubles")
+    M = len(xyz)
+    inl = np.zeros(max(M, 1), np.uint8)
+    n = C.c_int32()
+    ctx.check(ctx.lib.ssx_loop_pose_opt(ctx.handle, ptr(pose, dbl_p), ptr(K, dbl_p), M, ptr(xyz, dbl_p), ptr(uv, dbl_p), float(chi2_th),
+                                        float(huber_delta), ptr(inl, u8_p), C.byref(n)))
+    return dict(pose=pose, inliers=inl[:M], n_inliers=n.value)
+
+
+def compute_correct_pose(ctx: Context, loop_xyz, has_point, cur_uv, T_cur, T_loop, K, max_iters=100, seed=0):
+    """ComputeCorrectPose for the pairs of KeyframeDatabase.match_features: loop_xyz [n, 3] the loop keyframe's map point of each pair
+    (any value where has_point [n] is 0), cur_uv [n, 2] the current keyframe's pixel.  -> dict(verdict (LOOP_*), ok, kept uint8 [n],
+    corrected_pose, error, need_correct, relative_to_loop, n_with_point, n_ransac_inliers, n_inliers, best)"""
+    _bind_pose(ctx.lib)
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    xyz, uv = _f64(loop_xyz, 3), _f64(cur_uv, 2)
+    has = np.ascontiguousarray(has_point, dtype=np.uint8).reshape(-1)
+    T_cur, T_loop = np.ascontiguousarray(T_cur, dtype=np.float64), np.ascontiguousarray(T_loop, dtype=np.float64)
+    if not (len(xyz) == len(uv) == len(has)) or K.size != 4 or T_cur.size != 7 or T_loop.size != 7:
+        raise ValueError("one map point, flag and pixel per pair; K = (fx, fy, cx, cy); poses = 7 doubles")
+    n = len(has)
+    kept = np.zeros(max(n, 1), np.uint8)
+    r = LoopPoseResult()
+    ctx.check(ctx.lib.ssx_loop_compute_pose(ctx.handle, n, ptr(xyz, dbl_p), ptr(has, u8_p), ptr(uv, dbl_p), ptr(T_cur, dbl_p), ptr(T_loop, dbl_p),
+                                            ptr(K, dbl_p), int(max_iters), int(seed) & 0xFFFFFFFF, ptr(kept, u8_p), C.byref(r)))
+    return dict(verdict=r.verdict, ok=r.verdict == LOOP_OK, kept=kept[:n], corrected_pose=np.array(r.corrected_pose), error=r.error,
+                need_correct=bool(r.need_correct), relative_to_loop=np.array(r.relative_to_loop), n_with_point=r.n_with_point,
+                n_ransac_inliers=r.n_ransac_inliers, n_inliers=r.n_inliers, best=r.best_hypothesis)
