@@ -89,6 +89,48 @@ SSX_API ssx_status ssx_lk_stage_level(ssx_ctx* ctx, int32_t which, int32_t level
 SSX_API ssx_status ssx_lk_stage_deriv(ssx_ctx* ctx, int32_t level, int16_t* out, int32_t out_cap, int32_t* rows,
                                       int32_t* cols);
 
+/* tests / tools hooks: one LK call as the host side plans it (csrc/lk.hip: build_geom, build_call) -- what ssx_lk_track /
+ * ssx_lk_track_next / ssx_lk_track_batch would do, without doing it.
+ *   status / error   what the entry point would return and ssx_last_error() would show; the rest is filled for SSX_OK only
+ *   levels .. deriv_words   the geometry of the key (rows, cols, win, max_level): per level rows, cols, pitch, byte offset inside a
+ *                    pyramid, word offset inside the derivative images
+ *   fused_ok         k_lk_pyramid can build this geometry's pyramids; use_fused: this call uses it; scharr_now: this call runs k_lk_scharr
+ *   intake           how the level-0 images reach the device: SSX_LK_STAGED host images through the pinned io block, SSX_LK_ARENA one DMA
+ *                    copy of a pinned arena (arena_bytes), SSX_LK_EACH one DMA copy per host image, SSX_LK_IN_PLACE read where they lie
+ *   span_off / _bytes  the io block in memory order: job table, staged images, previous points, next points, status, error, device
+ *                    images; [0, in_bytes) is sent, [next points, host_end) comes back, io_bytes is the whole block
+ *   launch           the launches in order: kernel (SSX_LK_K_*), grid, which / level (-1: the kernel takes none)
+ *   slot_flags       per job (the first SSX_LK_MAX_INFO_JOBS), the slot's state after a successful call: bit 0 have_next, bit 1
+ *                    have_next_deriv, bit 2 flip; job_roles: which of the slot's two buffers the job's table names as bit 0 pyr[0],
+ *                    bit 1 pyr[1], bit 2 deriv, bit 3 deriv1 */
+enum { SSX_LK_STAGED = 0, SSX_LK_ARENA = 1, SSX_LK_EACH = 2, SSX_LK_IN_PLACE = 3 };
+enum { SSX_LK_K_PYRAMID = 0, SSX_LK_K_PAD_LEVEL0 = 1, SSX_LK_K_PYR_DOWN = 2, SSX_LK_K_SCHARR = 3, SSX_LK_K_TRACK = 4 };
+enum { SSX_LK_SPANS = 7, SSX_LK_MAX_LAUNCHES = 32, SSX_LK_MAX_INFO_JOBS = 256 };
+typedef struct ssx_lk_call_info {
+  int32_t status;
+  char error[256];
+  int32_t levels, win, pad, rows[8], cols[8], pitch[8];
+  uint64_t off[8], doff[8], pyr_bytes, deriv_words;
+  int32_t fused_ok, use_fused, scharr_now, intake;
+  uint64_t span_off[7], span_bytes[7], in_bytes, host_end, io_bytes, arena_bytes;
+  int32_t n_launches, n_jobs;
+  struct { int32_t kernel, grid[3], which, level; } launch[32];
+  uint8_t slot_flags[256], job_roles[256];
+} ssx_lk_call_info;
+/* a job as ssx_lk_debug_plan needs it: next_off = its `next` pointer minus jobs[0].next, in bytes */
+typedef struct ssx_lk_job_facts {
+  int32_t slot, fresh, n, prev_stride, next_stride, reserved;
+  int64_t next_off;
+} ssx_lk_job_facts;
+/* needs no GPU.  planned_key: rows, cols, win, max_level of the context's last successful call (NULL: those of this call);
+ * slot_flags: per job its slot's state before the call, bits as above; next0_is_host: jobs[0].next is host memory (looked at only
+ * where the entry points would ask the runtime).  Returns out->status. */
+SSX_API ssx_status ssx_lk_debug_plan(int32_t rows, int32_t cols, int32_t win, int32_t max_level, const int32_t* planned_key, int32_t n_jobs,
+                                     const ssx_lk_job_facts* jobs, const uint8_t* slot_flags, int32_t images_on_device, int32_t next0_is_host,
+                                     ssx_lk_call_info* out);
+/* the same struct for the last successful LK call of ctx (status SSX_OK, no error text) */
+SSX_API ssx_status ssx_lk_debug_last_call(ssx_ctx* ctx, ssx_lk_call_info* out);
+
 /* tests hooks of the P3P-RANSAC (csrc/pnp.hip, model: tools/pnp_model.py): the sample triples of (seed, M >= 3, H) as the kernel's
  * device function draws them (triples_out H x 3), and the best inlier count of each of the max_iters hypotheses of an
  * ssx_pnp_ransac call with the same arguments (counts_out max_iters) */

@@ -59,23 +59,66 @@ struct LkJob {
   int n, pt0;
 };
 
+// A slot's memory: two pyramids and two sets of derivative images.  Which of the two holds the previous and which the next image is the
+// slot's `flip`: a chained job turns it over instead of copying anything (LkRoles).
+struct LkSlotState {
+  bool flip = false;                     // previous image in buf[flip] / der[flip], next image in buf[!flip] / der[!flip]
+  bool have_next = false;                // buf[!flip] holds the pyramid of the slot's last `next` image
+  bool have_next_deriv = false;          // ... and der[!flip] its derivative images (fused pyramid kernel)
+};
 struct LkSlot {
   DevBuf mem;
-  uint8_t* pyr[2] = {nullptr, nullptr};
-  uint32_t* deriv = nullptr, *deriv1 = nullptr;
-  bool have_next = false;                // pyr[1] holds the pyramid of the slot's last `next` image
-  bool have_next_deriv = false;          // ... and deriv1 its derivative images (fused pyramid kernel)
+  uint8_t* buf[2] = {nullptr, nullptr};  // carved from mem; null: not carved under the workspace's geometry
+  uint32_t* der[2] = {nullptr, nullptr};
+  LkSlotState st;
+};
+struct LkRoles { int pyr[2], deriv, deriv1; };                         // LkJob's four slot pointers as indices into LkSlot::buf / ::der
+inline LkRoles lk_roles(bool flip) { return LkRoles{{flip, !flip}, flip, !flip}; }
+
+// ---- the host side's values: what a plan depends on, the geometry of a key, one call (built by build_geom / build_call below) ----
+struct LkKey {
+  int rows = 0, cols = 0, win = 0, max_level = -1;
+  bool operator==(const LkKey& o) const { return rows == o.rows && cols == o.cols && win == o.win && max_level == o.max_level; }
+};
+struct LkGeom {
+  LkDev dev{};                           // the geometry scalars; tracking parameters and pointers are the call's (wire_dev); levels == 0: no geometry yet
+  size_t pyr_bytes = 0, deriv_words = 0;
+  bool fused_ok = false;                 // k_lk_pyramid can build the pyramids (<= 4 levels, border <= 16)
+};
+
+enum LkIntake { LK_STAGED = 0, LK_ARENA, LK_EACH, LK_IN_PLACE };      // how the level-0 images reach the device (choose_intake)
+enum LkKernel { LK_K_PYRAMID = 0, LK_K_PAD_LEVEL0, LK_K_PYR_DOWN, LK_K_SCHARR, LK_K_TRACK };
+struct LkLaunch { LkKernel kernel; unsigned grid[3]; int which, level; };   // which / level: -1 where the kernel takes none
+struct Span { size_t off = 0, n = 0; };                               // a buffer of the io block: its offset and its bytes
+constexpr size_t LK_IN_CALLER = ~size_t(0);                            // LkCallJob::img_off: the kernel reads the caller's pointer (null: chained)
+
+struct LkCallJob {
+  bool fresh;                            // both images given; else chained to the slot's last job
+  LkSlotState after;                     // the slot's state once the call has succeeded; after.flip gives the job's LkRoles
+  size_t img_off[2];                     // level-0 sources [0] previous, [1] next inside the io block, or LK_IN_CALLER
+  int pt0;                               // first point of the job among the call's
+};
+struct LkCall {
+  std::vector<LkCallJob> jobs;
+  bool use_fused = false, scharr_now = false;
+  LkIntake intake = LK_STAGED;
+  size_t arena_bytes = 0;                // LK_ARENA: bytes of the one copy that starts at jobs[0].next
+  size_t n_pts = 0;
+  // the io block in memory order: [0, in_bytes) goes to the device in one copy, [next_pts.off, host_end) comes back in one, the rest
+  // (dev_images: the arena's or the per-image copies' landing place) exists on the device only
+  Span tab, images, prev_pts, next_pts, status, err, dev_images;
+  size_t in_bytes = 0, host_end = 0, io_bytes = 0;
+  std::vector<LkLaunch> launches;       // in order
 };
 
 struct LkWorkspace {
   std::vector<LkSlot> slots;
   DevBuf io;
   HostBuf stage;
-  LkDev dev{};
-  size_t pyr_bytes = 0, deriv_words = 0;
-  int rows = 0, cols = 0, win = 0, max_level = -1;
-  bool planned = false;
-  bool fused = false;                    // k_lk_pyramid builds the pyramids (<= 4 levels, border <= 16)
+  LkKey key;
+  LkGeom geom;
+  LkCall last;                           // the last call that succeeded (ssx_lk_debug_last_call)
+  bool planned(const LkKey& k) const { return geom.dev.levels > 0 && key == k; }
 };
 
 void lk_ws_free(void* p)
@@ -524,249 +567,325 @@ __global__ __launch_bounds__(256) void k_lk_track(LkDev d, const LkJob* __restri
   }
 }
 
-ssx_status lk_plan(ssx_ctx* ctx, int rows, int cols, const ssx_lk_params& prm)
+// ---- host side.  key -> geometry (build_geom) and (geometry, jobs, slot states, facts) -> call (build_call) are arithmetic on plain
+// values: no HIP call, no workspace (ssx_lk_debug_plan runs them without a device).  lk_run() is the list of steps around them. ----
+constexpr int LK_ERR = 256;              // bytes of the text that says why a call is refused
+template <class... A> ssx_status lk_fail(char* err, ssx_status st, const char* fmt, A... a) { snprintf(err, LK_ERR, fmt, a...); return st; }
+
+ssx_status build_geom(const LkKey& k, LkGeom& g, char* err)
 {
-  LkWorkspace* ws = lk_ws(ctx);
-  if (prm.win < 3 || prm.win > LK_MAX_WIN || (prm.win & 1) == 0 || prm.max_level < 0 || prm.max_level >= LK_MAX_LEVELS) {
-    ctx->set_error("ssx_lk: unsupported window %d (odd, 3..%d) or max_level %d (0..%d)", prm.win, LK_MAX_WIN, prm.max_level, LK_MAX_LEVELS - 1);
-    return SSX_ERR_INVALID_ARG;
-  }
-  if (rows < 2 || cols < 2 || rows > 8192 || cols > 8192) {
-    ctx->set_error("ssx_lk: image %dx%d outside the supported range", cols, rows);
-    return SSX_ERR_INVALID_ARG;
-  }
-  if (ws->planned && ws->rows == rows && ws->cols == cols && ws->win == prm.win && ws->max_level == prm.max_level) return SSX_OK;
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  LkDev d{};
-  d.win = prm.win; d.pad = prm.win + 1;
-  // buildOpticalFlowPyramid: a level not larger than the window ends the pyramid
-  d.levels = 1;
-  d.rows[0] = rows; d.cols[0] = cols;
-  for (int l = 1; l <= prm.max_level; ++l) {
+  if (k.win < 3 || k.win > LK_MAX_WIN || (k.win & 1) == 0 || k.max_level < 0 || k.max_level >= LK_MAX_LEVELS)
+    return lk_fail(err, SSX_ERR_INVALID_ARG, "ssx_lk: unsupported window %d (odd, 3..%d) or max_level %d (0..%d)", k.win, LK_MAX_WIN, k.max_level, LK_MAX_LEVELS - 1);
+  if (k.rows < 2 || k.cols < 2 || k.rows > 8192 || k.cols > 8192)
+    return lk_fail(err, SSX_ERR_INVALID_ARG, "ssx_lk: image %dx%d outside the supported range", k.cols, k.rows);
+  g = LkGeom{};
+  LkDev& d = g.dev;
+  d.win = k.win; d.pad = k.win + 1; d.levels = 1; d.rows[0] = k.rows; d.cols[0] = k.cols;
+  for (int l = 1; l <= k.max_level; ++l) {                             // buildOpticalFlowPyramid: a level not larger than the window ends the pyramid
     const int w = (d.cols[l - 1] + 1) / 2, h = (d.rows[l - 1] + 1) / 2;
-    if (w <= prm.win || h <= prm.win) break;
+    if (w <= k.win || h <= k.win) break;
     d.rows[l] = h; d.cols[l] = w; d.levels = l + 1;
   }
-  size_t off = 0, doff = 0;
+  size_t off = 0;
   for (int l = 0; l < d.levels; ++l) {
     d.pitch[l] = (d.cols[l] + 2 * d.pad + 63) & ~63;
-    d.off[l] = off; d.doff[l] = doff;
+    d.off[l] = d.doff[l] = off;                                        // (bytes of a pyramid, words of the derivative images: the same padded geometry)
     off += (size_t)d.pitch[l] * (d.rows[l] + 2 * d.pad) + 64;
-    doff += (size_t)d.pitch[l] * (d.rows[l] + 2 * d.pad) + 64;
   }
-  ws->pyr_bytes = (off + 255) & ~size_t(255);
-  ws->deriv_words = doff;
-  ws->dev = d;
+  g.pyr_bytes = (off + 255) & ~size_t(255); g.deriv_words = off;
   // k_lk_pyramid: at most four levels in LDS, and every level at least border + 2 pixels a side (one fold per coordinate)
   static const bool unfused = getenv("SSX_LK_UNFUSED") != nullptr;     // (A/B: the per-level kernels)
-  ws->fused = !unfused && d.levels <= FUSED_MAX_LEVELS && std::min(d.rows[d.levels - 1], d.cols[d.levels - 1]) >= d.pad + 2;
-  ws->rows = rows; ws->cols = cols; ws->win = prm.win; ws->max_level = prm.max_level;
-  ws->planned = true;
-  for (LkSlot& sl : ws->slots) { sl.have_next = sl.have_next_deriv = false; sl.pyr[0] = sl.pyr[1] = nullptr; sl.deriv = sl.deriv1 = nullptr; }   // (their memory is re-carved on use)
+  g.fused_ok = !unfused && d.levels <= FUSED_MAX_LEVELS && std::min(d.rows[d.levels - 1], d.cols[d.levels - 1]) >= d.pad + 2;
   return SSX_OK;
 }
 
-// the slot's two pyramids and its derivative images, carved from a buffer of its own
-ssx_status lk_slot(ssx_ctx* ctx, LkWorkspace* ws, int slot, LkSlot** out)
+// What the jobs of a call are refused for, job by job; of several reasons the first is reported, and all of them come before those of
+// build_geom (parameters, then the image size).  before[j]: the state of job j's slot; prev_required: ssx_lk_track.
+ssx_status check_jobs(int nj, const ssx_lk_job* jobs, const LkKey& key, bool key_planned, const LkSlotState* before, bool prev_required, char* err)
 {
-  if (slot < 0 || slot >= 4096) { ctx->set_error("ssx_lk: slot %d outside 0..4095", slot); return SSX_ERR_INVALID_ARG; }
-  if ((size_t)slot >= ws->slots.size()) ws->slots.resize((size_t)slot + 1);
-  LkSlot& sl = ws->slots[slot];
-  if (!sl.pyr[0]) {
+  for (int j = 0; j < nj; ++j) {
+    const ssx_lk_job& q = jobs[j];
+    if ((prev_required && !q.prev) || !q.next || q.n < 0 || (q.n > 0 && (!q.prev_pts || !q.next_pts || !q.status))) return SSX_ERR_INVALID_ARG;
+    if ((q.prev && q.prev_stride < key.cols) || q.next_stride < key.cols) return lk_fail(err, SSX_ERR_INVALID_ARG, "%s", "ssx_lk: stride smaller than the image width");
+    if (q.slot < 0 || q.slot >= 4096) return lk_fail(err, SSX_ERR_INVALID_ARG, "ssx_lk: slot %d outside 0..4095", q.slot);
+    for (int k = 0; k < j; ++k)
+      if (jobs[k].slot == q.slot) return lk_fail(err, SSX_ERR_INVALID_ARG, "ssx_lk_track_batch: slot %d twice in one call", q.slot);
+    if (!q.prev && !(key_planned && before[j].have_next))
+      return lk_fail(err, SSX_ERR_INVALID_ARG, "ssx_lk_track_next: no previous ssx_lk_track call with the same image size, window and max_level on this context (slot %d)", q.slot);
+  }
+  return SSX_OK;
+}
+
+// k_lk_pyramid (one launch per image) for calls of a few jobs, whose frame is a chain of dependent launches; in a call of many jobs the
+// per-level kernels are wide launches already and do less work per pixel (profiles/r06/lk_pyramid_ab.txt)
+bool lk_use_fused(const LkGeom& g, int nj) { return g.fused_ok && nj <= FUSED_MAX_JOBS; }
+size_t image_span(const LkKey& k, int stride) { return (size_t)(k.rows - 1) * (size_t)stride + (size_t)k.cols; }
+
+// How the level-0 images reach the device, from the strides, the distances of the `next` pointers and whether jobs[0].next is host memory:
+// LK_STAGED   host images: rows packed into the pinned io block, which goes over in one copy with the table and the points
+// LK_ARENA    the `next` images lie at a constant distance (one pinned arena, a slice per stream: host/stream_batcher.cpp; gaps: streams
+//             that sit this call out): ONE copy of *arena_bytes from jobs[0].next on the DMA engine, instead of reads through PCIe
+// LK_EACH     host memory (pinned, no arena) in front of k_lk_pyramid, which reads level 0 about 2.5 times: one DMA copy per image
+// LK_IN_PLACE otherwise: read where they lie
+LkIntake choose_intake(const LkKey& k, int nj, const ssx_lk_job* jobs, bool images_on_device, bool use_fused, bool next0_is_host, size_t* arena_bytes)
+{
+  *arena_bytes = 0;
+  if (!images_on_device) return LK_STAGED;
+  const size_t span = image_span(k, jobs[0].next_stride);
+  bool ok = nj >= 2;                                                   // (one job: LK_EACH, if the image is in host memory)
+  for (int j = 1; ok && j < nj; ++j)
+    ok = jobs[j].next_stride == jobs[0].next_stride && jobs[j].next > jobs[j - 1].next && (size_t)(jobs[j].next - jobs[j - 1].next) >= span;
+  const size_t range = ok ? (size_t)(jobs[nj - 1].next - jobs[0].next) + span : 0;
+  if (ok && range <= 2 * (size_t)nj * span) { *arena_bytes = range; return LK_ARENA; }
+  return use_fused && next0_is_host ? LK_EACH : LK_IN_PLACE;
+}
+
+// the io block, each span stated once: [job table | (staged images) | prev points | next points] | status | err | (device images)
+void plan_io(const LkKey& key, int nj, const ssx_lk_job* jobs, LkCall& c)
+{
+  Layout lay;
+  auto take = [&](size_t n) { return Span{lay.take(n), n}; };
+  const size_t img_bytes = (size_t)key.rows * key.cols, pts = std::max<size_t>(c.n_pts, 1);
+  size_t each_span = 0;
+  c.tab = take(sizeof(LkJob) * (size_t)nj);
+  c.images.off = lay.off;
+  for (int j = 0; j < nj; ++j) {
+    LkCallJob& cj = c.jobs[j];
+    cj.img_off[1] = c.intake == LK_STAGED ? lay.take(img_bytes) : LK_IN_CALLER;
+    cj.img_off[0] = c.intake == LK_STAGED && cj.fresh ? lay.take(img_bytes) : LK_IN_CALLER;
+    each_span = std::max(each_span, std::max(image_span(key, jobs[j].next_stride), cj.fresh ? image_span(key, jobs[j].prev_stride) : (size_t)0));
+  }
+  c.images.n = lay.off - c.images.off;
+  c.prev_pts = take(sizeof(float) * 2 * pts); c.next_pts = take(sizeof(float) * 2 * pts);
+  c.in_bytes = lay.off;
+  c.status = take(pts); c.err = take(sizeof(float) * pts);
+  c.host_end = lay.off;                                                // (what has a pinned mirror: inputs by copy + results)
+  each_span = (each_span + 63) & ~size_t(63);
+  c.dev_images = take(c.intake == LK_ARENA ? c.arena_bytes + 16 : c.intake == LK_EACH ? 2 * (size_t)nj * each_span : 0);
+  c.io_bytes = lay.off;
+  for (int j = 0; j < nj; ++j) {
+    LkCallJob& cj = c.jobs[j];
+    if (c.intake == LK_ARENA) cj.img_off[1] = c.dev_images.off + (size_t)(jobs[j].next - jobs[0].next);
+    if (c.intake == LK_EACH) cj.img_off[1] = c.dev_images.off + (size_t)(2 * j) * each_span;
+    if (c.intake == LK_EACH && cj.fresh) cj.img_off[0] = c.dev_images.off + (size_t)(2 * j + 1) * each_span;
+  }
+}
+
+// The launches in order.  Pyramids: k_lk_pyramid once for all images (z = job x {previous, next}), or per `which` (the previous images
+// only if a job is fresh) the per-level kernels; k_lk_scharr when scharr_now; k_lk_track (four points a workgroup) when there are points.
+void plan_launches(const LkDev& d, int nj, bool any_fresh, int max_n, LkCall& c)
+{
+  auto level = [&](LkKernel k, int which, int l) { c.launches.push_back({k, {(unsigned)(d.cols[l] + 2 * d.pad + 255) / 256, (unsigned)(d.rows[l] + 2 * d.pad), (unsigned)nj}, which, l}); };
+  const int top = d.levels - 1;
+  if (c.use_fused) c.launches.push_back({LK_K_PYRAMID, {(unsigned)(d.cols[top] + 2 * d.pad + FT - 1) / FT, (unsigned)(d.rows[top] + 2 * d.pad + FT - 1) / FT, 2u * nj}, -1, -1});
+  else
+    for (int which = any_fresh ? 0 : 1; which < 2; ++which) {
+      level(LK_K_PAD_LEVEL0, which, 0);
+      for (int l = 1; l < d.levels; ++l) level(LK_K_PYR_DOWN, which, l);
+    }
+  if (c.scharr_now)
+    for (int l = 0; l < d.levels; ++l) level(LK_K_SCHARR, -1, l);
+  if (c.n_pts > 0) c.launches.push_back({LK_K_TRACK, {(unsigned)(max_n + 3) / 4, (unsigned)nj, 1u}, -1, -1});
+}
+
+// One tracking CALL of nj jobs (ssx_lk_job) as a value.  A job with prev == nullptr is chained: its previous image is the next image of
+// its slot's last job, whose pyramid is still there -- the slot's two pyramids swap roles (after.flip) and only the new image is read
+// and reduced.  A fresh job overwrites both pyramids, so it takes the slot as carved (flip = false) whatever the slot held.
+LkCall build_call(const LkKey& key, const LkGeom& g, int nj, const ssx_lk_job* jobs, const LkSlotState* before, bool images_on_device, bool next0_is_host)
+{
+  LkCall c;
+  c.use_fused = lk_use_fused(g, nj);
+  c.scharr_now = !c.use_fused;                                         // (the derivative images of the previous image: per-level kernel, this call)
+  c.intake = choose_intake(key, nj, jobs, images_on_device, c.use_fused, next0_is_host, &c.arena_bytes);
+  c.jobs.resize(nj);
+  bool any_fresh = false;
+  int max_n = 0;
+  for (int j = 0; j < nj; ++j) {
+    LkCallJob& cj = c.jobs[j];
+    cj.fresh = jobs[j].prev != nullptr;
+    cj.after = LkSlotState{!cj.fresh && !before[j].flip, true, c.use_fused};
+    if (!cj.fresh && !before[j].have_next_deriv) c.scharr_now = true;  // its last call was a wide one: no derivative images were kept
+    any_fresh |= cj.fresh;
+    cj.pt0 = (int)c.n_pts;
+    c.n_pts += (size_t)jobs[j].n; max_n = std::max(max_n, jobs[j].n);
+  }
+  plan_io(key, nj, jobs, c);
+  plan_launches(g.dev, nj, any_fresh, max_n, c);
+  return c;
+}
+
+// step 2: the workspace's geometry if the key is the planned one; else a new one, the device drained and every slot invalidated
+ssx_status lk_geometry(ssx_ctx* ctx, LkWorkspace* ws, const LkKey& key, char* err)
+{
+  if (ws->planned(key)) return SSX_OK;
+  LkGeom g;
+  const ssx_status st = build_geom(key, g, err);
+  if (st != SSX_OK) return st;                                         // (the previous geometry stays in force)
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ws->key = key; ws->geom = g;
+  for (LkSlot& sl : ws->slots) { sl.st = LkSlotState{}; sl.buf[0] = sl.buf[1] = nullptr; sl.der[0] = sl.der[1] = nullptr; }   // (their memory is re-carved on use)
+  return SSX_OK;
+}
+
+// step 3: is jobs[0].next host memory?  The one question to the runtime, asked only where the answer decides the intake.
+bool lk_next0_is_host(const LkKey& key, const LkGeom& g, int nj, const ssx_lk_job* jobs, bool images_on_device)
+{
+  size_t arena = 0;
+  if (!lk_use_fused(g, nj) || choose_intake(key, nj, jobs, images_on_device, true, false, &arena) != LK_IN_PLACE) return false;
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, jobs[0].next) == hipSuccess) return at.type == hipMemoryTypeHost;
+  (void)hipGetLastError();
+  return false;
+}
+
+// step 5: the slots' two pyramids and derivative images, each slot carved from a buffer of its own; the io block and its pinned mirror
+ssx_status lk_reserve(ssx_ctx* ctx, LkWorkspace* ws, int nj, const ssx_lk_job* jobs, const LkCall& c)
+{
+  int top = 0;
+  for (int j = 0; j < nj; ++j) top = std::max(top, jobs[j].slot);
+  if ((size_t)top >= ws->slots.size()) ws->slots.resize((size_t)top + 1);
+  for (int j = 0; j < nj; ++j) {
+    LkSlot& sl = ws->slots[jobs[j].slot];
+    if (sl.buf[0]) continue;
     Layout lay;
-    const size_t o_p0 = lay.take(ws->pyr_bytes), o_p1 = lay.take(ws->pyr_bytes), o_g = lay.take(sizeof(uint32_t) * ws->deriv_words);
-    const size_t o_g1 = lay.take(sizeof(uint32_t) * ws->deriv_words);
+    const size_t pyr = ws->geom.pyr_bytes, der = sizeof(uint32_t) * ws->geom.deriv_words, o[4] = {lay.take(pyr), lay.take(pyr), lay.take(der), lay.take(der)};
     SSX_HIP_TRY(ctx, sl.mem.reserve(lay.off, 1.0));
     char* base = sl.mem.as<char>();
-    sl.pyr[0] = (uint8_t*)(base + o_p0); sl.pyr[1] = (uint8_t*)(base + o_p1); sl.deriv = (uint32_t*)(base + o_g); sl.deriv1 = (uint32_t*)(base + o_g1);
-    sl.have_next = sl.have_next_deriv = false;
+    sl.buf[0] = (uint8_t*)(base + o[0]); sl.buf[1] = (uint8_t*)(base + o[1]); sl.der[0] = (uint32_t*)(base + o[2]); sl.der[1] = (uint32_t*)(base + o[3]);
+    sl.st = LkSlotState{};
   }
-  *out = &sl;
+  SSX_HIP_TRY(ctx, ws->io.reserve(c.io_bytes, 1.5));
+  SSX_HIP_TRY(ctx, ws->stage.reserve(c.host_end, 1.5));
   return SSX_OK;
 }
 
-// One tracking CALL of nj jobs (ssx_lk_job).  A job with prev == nullptr is chained: its previous image is the next image of its
-// slot's last job, whose pyramid is still in pyr[1] -- the two pyramid pointers of the slot swap roles and only the new image is
-// read and reduced.  images_on_device: the image pointers are readable by the GPU (device memory, or pinned host memory that the
-// level-0 kernel then reads over PCIe): nothing is staged; else they go through pinned staging and one copy, with the points.
-ssx_status lk_run(ssx_ctx* ctx, int nj, const ssx_lk_job* jobs, int32_t rows, int32_t cols, const ssx_lk_params* prm_in, bool images_on_device,
-                  int32_t* top_level)
+// step 6: the pinned mirror of the io block: the job table, the rows of staged images, the points
+void lk_fill(LkWorkspace* ws, int nj, const ssx_lk_job* jobs, const LkCall& c)
 {
-  ssx_lk_params prm;
-  if (prm_in) prm = *prm_in; else ssx_lk_default_params(&prm);
-  LkWorkspace* w0 = lk_ws(ctx);
-  bool any_chained = false, any_fresh = false;
-  for (int j = 0; j < nj; ++j) {
-    const ssx_lk_job& q = jobs[j];
-    if (!q.next || q.n < 0 || (q.n > 0 && (!q.prev_pts || !q.next_pts || !q.status))) return SSX_ERR_INVALID_ARG;
-    if ((q.prev && q.prev_stride < cols) || q.next_stride < cols) { ctx->set_error("ssx_lk: stride smaller than the image width"); return SSX_ERR_INVALID_ARG; }
-    if (q.slot < 0 || q.slot >= 4096) { ctx->set_error("ssx_lk: slot %d outside 0..4095", q.slot); return SSX_ERR_INVALID_ARG; }   // (before any slot is touched)
-    for (int k = 0; k < j; ++k) if (jobs[k].slot == q.slot) { ctx->set_error("ssx_lk_track_batch: slot %d twice in one call", q.slot); return SSX_ERR_INVALID_ARG; }
-    if (!q.prev) {
-      any_chained = true;
-      const bool ok = w0->planned && w0->rows == rows && w0->cols == cols && w0->win == prm.win && w0->max_level == prm.max_level && q.slot >= 0 &&
-                      (size_t)q.slot < w0->slots.size() && w0->slots[q.slot].pyr[0] && w0->slots[q.slot].have_next;
-      if (!ok) {
-        ctx->set_error("ssx_lk_track_next: no previous ssx_lk_track call with the same image size, window and max_level on this context (slot %d)", q.slot);
-        return SSX_ERR_INVALID_ARG;
-      }
-    } else any_fresh = true;
-  }
-  (void)any_chained;
-  ssx_status st = lk_plan(ctx, rows, cols, prm);
-  if (st != SSX_OK) return st;
-  LkWorkspace* ws = lk_ws(ctx);
-  std::vector<LkSlot*> slot(nj);
-  {
-    int top = -1;
-    for (int j = 0; j < nj; ++j) top = std::max(top, jobs[j].slot);
-    if (top >= 0 && top < 4096 && (size_t)top >= ws->slots.size()) ws->slots.resize((size_t)top + 1);   // (before any pointer into it is taken)
-  }
-  // One launch per image (k_lk_pyramid) for calls of a few jobs -- a single stream's frame is a chain of dependent launches, and the
-  // fused kernel replaces eight of them (chained call 0.158 -> 0.122 ms, two fresh images 0.242 -> 0.151 ms); in a call of many jobs
-  // the per-level kernels are wide launches already and do less work per pixel (64 jobs: 0.53 against 0.75 ms): they stay for those
-  // (profiles/r06/lk_pyramid_ab.txt).
-  const bool use_fused = ws->fused && nj <= FUSED_MAX_JOBS;
-  bool scharr_now = !use_fused;                                       // (the derivative images of the previous image: per-level kernel, this call)
-  for (int j = 0; j < nj; ++j) {
-    st = lk_slot(ctx, ws, jobs[j].slot, &slot[j]);
-    if (st != SSX_OK) return st;
-    if (!jobs[j].prev) {
-      if (!slot[j]->have_next_deriv) scharr_now = true;               // its last call was a wide one: no derivative images were kept
-      std::swap(slot[j]->pyr[0], slot[j]->pyr[1]); std::swap(slot[j]->deriv, slot[j]->deriv1);
-    }
-    slot[j]->have_next = slot[j]->have_next_deriv = false;
-  }
-  LkDev d = ws->dev;
-  hipStream_t s = ctx->stream;
-  // one pinned block: [job table | (staged images) | prev points | next points] -> one copy -> device; results come back in one
-  const size_t img_bytes = (size_t)rows * cols;
-  size_t n_pts = 0;
-  int max_n = 0;
-  for (int j = 0; j < nj; ++j) { n_pts += (size_t)jobs[j].n; max_n = std::max(max_n, jobs[j].n); }
-  Layout io;
-  const size_t o_tab = io.take(sizeof(LkJob) * (size_t)nj);
-  std::vector<size_t> o_img0(nj, 0), o_img1(nj, 0);
-  if (!images_on_device)
-    for (int j = 0; j < nj; ++j) { o_img1[j] = io.take(img_bytes); if (jobs[j].prev) o_img0[j] = io.take(img_bytes); }
-  const size_t o_pp = io.take(sizeof(float) * 2 * std::max<size_t>(n_pts, 1));
-  const size_t o_np = io.take(sizeof(float) * 2 * std::max<size_t>(n_pts, 1));
-  const size_t in_bytes = io.off;
-  const size_t o_st = io.take(std::max<size_t>(n_pts, 1));
-  const size_t o_er = io.take(sizeof(float) * std::max<size_t>(n_pts, 1));
-  const size_t host_end = io.off;                                    // (what has a pinned mirror: inputs by copy + results)
-  // images_on_device: when the callers' `next` images lie at a constant distance from each other (one pinned arena, a slice per stream:
-  // ssvio_amd/host/stream_batcher.cpp) ONE copy on the DMA engine brings them into a staging block in HBM -- 54 GB/s, against 32 GB/s for
-  // the level-0 kernel reading the host pixels itself (0.95 ms of a 1.4 ms call for 64 frames; a kernel with 16-byte loads: no better --
-  // profiles/r06/c5_kernel_stats.txt).  Images elsewhere are read where they lie.
-  auto span = [&](int stride) { return (size_t)(rows - 1) * (size_t)stride + (size_t)cols; };
-  size_t arena_bytes = 0, o_arena = 0;                              // the range [jobs[0].next, last job's end) when it is worth one copy
-  if (images_on_device && nj >= 2) {                                 // (one job: stage_each below, if the image is in host memory)
-    bool ok = true;
-    for (int j = 1; ok && j < nj; ++j)
-      ok = jobs[j].next_stride == jobs[0].next_stride && jobs[j].next > jobs[j - 1].next && (size_t)(jobs[j].next - jobs[j - 1].next) >= span(jobs[0].next_stride);
-    const size_t range = ok ? (size_t)(jobs[nj - 1].next - jobs[0].next) + span(jobs[0].next_stride) : 0;
-    if (ok && range <= 2 * (size_t)nj * span(jobs[0].next_stride)) { arena_bytes = range; o_arena = io.take(range + 16); }   // (gaps: streams that sit this call out)
-  }
-  // k_lk_pyramid reads its patches with a halo (level 0 about 2.5 times): images that lie in HOST memory (pinned, not in one arena) come
-  // over by one DMA copy each instead of being read through PCIe by the kernel
-  bool stage_each = false;
-  size_t o_each = 0, each_span = 0;
-  if (images_on_device && use_fused && !arena_bytes) {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, jobs[0].next) == hipSuccess) stage_each = at.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();
-    if (stage_each) {
-      for (int j = 0; j < nj; ++j) each_span = std::max(each_span, std::max(span(jobs[j].next_stride), jobs[j].prev ? span(jobs[j].prev_stride) : (size_t)0));
-      each_span = (each_span + 63) & ~size_t(63);
-      o_each = io.take(2 * (size_t)nj * each_span);
-    }
-  }
-  SSX_HIP_TRY(ctx, ws->io.reserve(io.off, 1.5));
-  SSX_HIP_TRY(ctx, ws->stage.reserve(host_end, 1.5));
   char* hs = ws->stage.as<char>();
   char* db = ws->io.as<char>();
-  LkJob* tab = reinterpret_cast<LkJob*>(hs + o_tab);
-  size_t pt0 = 0;
+  const int rows = ws->key.rows, cols = ws->key.cols;
   for (int j = 0; j < nj; ++j) {
     const ssx_lk_job& q = jobs[j];
-    LkJob& t = tab[j];
-    t.pyr[0] = slot[j]->pyr[0]; t.pyr[1] = slot[j]->pyr[1]; t.deriv = slot[j]->deriv; t.deriv1 = slot[j]->deriv1;
-    if (images_on_device) {
-      t.img[0] = q.prev; t.img[1] = q.next; t.stride[0] = q.prev_stride; t.stride[1] = q.next_stride;
-      if (arena_bytes) t.img[1] = (const uint8_t*)(db + o_arena) + (size_t)(q.next - jobs[0].next);
-      if (stage_each) {
-        t.img[1] = (const uint8_t*)(db + o_each + (size_t)(2 * j) * each_span);
-        if (q.prev) t.img[0] = (const uint8_t*)(db + o_each + (size_t)(2 * j + 1) * each_span);
-      }
-    } else {
-      for (int y = 0; y < rows; ++y) {
-        if (q.prev) memcpy(hs + o_img0[j] + (size_t)y * cols, q.prev + (size_t)y * q.prev_stride, cols);
-        memcpy(hs + o_img1[j] + (size_t)y * cols, q.next + (size_t)y * q.next_stride, cols);
-      }
-      t.img[0] = q.prev ? (const uint8_t*)(db + o_img0[j]) : nullptr; t.img[1] = (const uint8_t*)(db + o_img1[j]);
-      t.stride[0] = t.stride[1] = cols;
+    const LkCallJob& cj = c.jobs[j];
+    const LkSlot& sl = ws->slots[q.slot];
+    const LkRoles r = lk_roles(cj.after.flip);
+    LkJob& t = reinterpret_cast<LkJob*>(hs + c.tab.off)[j];
+    t.pyr[0] = sl.buf[r.pyr[0]]; t.pyr[1] = sl.buf[r.pyr[1]]; t.deriv = sl.der[r.deriv]; t.deriv1 = sl.der[r.deriv1];
+    const uint8_t* src[2] = {q.prev, q.next};
+    const int src_stride[2] = {q.prev_stride, q.next_stride};
+    for (int w = 0; w < 2; ++w) {
+      t.img[w] = cj.img_off[w] == LK_IN_CALLER ? src[w] : (const uint8_t*)(db + cj.img_off[w]);
+      t.stride[w] = c.intake == LK_STAGED ? cols : src_stride[w];
+      if (c.intake == LK_STAGED && src[w])
+        for (int y = 0; y < rows; ++y) memcpy(hs + cj.img_off[w] + (size_t)y * cols, src[w] + (size_t)y * src_stride[w], cols);
     }
-    t.n = q.n; t.pt0 = (int)pt0;
-    if (q.n > 0) {
-      memcpy(hs + o_pp + sizeof(float) * 2 * pt0, q.prev_pts, sizeof(float) * 2 * q.n);
-      memcpy(hs + o_np + sizeof(float) * 2 * pt0, q.next_pts, sizeof(float) * 2 * q.n);
-    }
-    pt0 += (size_t)q.n;
+    t.n = q.n; t.pt0 = cj.pt0;
+    if (q.n > 0) memcpy(hs + c.prev_pts.off + sizeof(float) * 2 * cj.pt0, q.prev_pts, sizeof(float) * 2 * q.n);
+    if (q.n > 0) memcpy(hs + c.next_pts.off + sizeof(float) * 2 * cj.pt0, q.next_pts, sizeof(float) * 2 * q.n);
   }
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(db, hs, in_bytes, hipMemcpyHostToDevice, s));
-  const LkJob* dtab = reinterpret_cast<const LkJob*>(db + o_tab);
-  if (arena_bytes) SSX_HIP_TRY(ctx, hipMemcpyAsync(db + o_arena, jobs[0].next, arena_bytes, hipMemcpyDefault, s));
-  if (stage_each)
+}
+
+// k_lk_track's LkDev: the geometry + the tracking parameters and the points' places in the io block
+LkDev wire_dev(const LkDev& g, const ssx_lk_params& prm, const LkCall& c, char* db)
+{
+  LkDev d = g;
+  d.max_iters = std::min(std::max(prm.max_iters, 0), 100);             // TermCriteria clamps of calcOpticalFlowPyrLK
+  const double e = std::min(std::max(prm.eps, 0.), 10.);
+  d.eps2 = e * e; d.min_eig = prm.min_eig_threshold; d.use_initial_flow = prm.use_initial_flow;
+  d.prev_pts = (const float*)(db + c.prev_pts.off); d.next_pts = (float*)(db + c.next_pts.off);
+  d.status = (uint8_t*)(db + c.status.off); d.err = (float*)(db + c.err.off);
+  return d;
+}
+
+// step 7: the io block in one copy, the images of LK_ARENA (one copy) or LK_EACH (one per image: next, then previous), the launch list,
+// the results' way back.  The slot of a FRESH job loses its chain in front of the first launch: its kept pyramid is about to be
+// overwritten (see lk_commit).
+ssx_status lk_enqueue(ssx_ctx* ctx, LkWorkspace* ws, int nj, const ssx_lk_job* jobs, const ssx_lk_params& prm, const LkCall& c)
+{
+  char* hs = ws->stage.as<char>();
+  char* db = ws->io.as<char>();
+  hipStream_t s = ctx->stream;
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(db, hs, c.in_bytes, hipMemcpyHostToDevice, s));
+  if (c.intake == LK_ARENA) SSX_HIP_TRY(ctx, hipMemcpyAsync(db + c.dev_images.off, jobs[0].next, c.arena_bytes, hipMemcpyDefault, s));
+  if (c.intake == LK_EACH)
     for (int j = 0; j < nj; ++j) {
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(db + o_each + (size_t)(2 * j) * each_span, jobs[j].next, span(jobs[j].next_stride), hipMemcpyHostToDevice, s));
-      if (jobs[j].prev) SSX_HIP_TRY(ctx, hipMemcpyAsync(db + o_each + (size_t)(2 * j + 1) * each_span, jobs[j].prev, span(jobs[j].prev_stride), hipMemcpyHostToDevice, s));
+      SSX_HIP_TRY(ctx, hipMemcpyAsync(db + c.jobs[j].img_off[1], jobs[j].next, image_span(ws->key, jobs[j].next_stride), hipMemcpyHostToDevice, s));
+      if (jobs[j].prev) SSX_HIP_TRY(ctx, hipMemcpyAsync(db + c.jobs[j].img_off[0], jobs[j].prev, image_span(ws->key, jobs[j].prev_stride), hipMemcpyHostToDevice, s));
     }
-  if (use_fused) {
-    const int top = d.levels - 1;
-    const dim3 g((d.cols[top] + 2 * d.pad + FT - 1) / FT, (d.rows[top] + 2 * d.pad + FT - 1) / FT, 2 * nj);   // z = job x {previous, next} image
-    hipLaunchKernelGGL(k_lk_pyramid, g, dim3(256), 0, s, d, dtab);
-  }
-  for (int which = use_fused ? 2 : any_fresh ? 0 : 1; which < 2; ++which) {
-    const dim3 g0((d.cols[0] + 2 * d.pad + 255) / 256, d.rows[0] + 2 * d.pad, nj);
-    hipLaunchKernelGGL(k_lk_pad_level0, g0, dim3(256), 0, s, d, dtab, which);
-    for (int l = 1; l < d.levels; ++l) {
-      const dim3 g((d.cols[l] + 2 * d.pad + 255) / 256, d.rows[l] + 2 * d.pad, nj);
-      hipLaunchKernelGGL(k_lk_pyr_down, g, dim3(256), 0, s, d, dtab, which, l);
+  for (int j = 0; j < nj; ++j)
+    if (c.jobs[j].fresh) ws->slots[jobs[j].slot].st.have_next = ws->slots[jobs[j].slot].st.have_next_deriv = false;
+  const LkDev& g = ws->geom.dev;
+  const LkDev d = wire_dev(g, prm, c, db);
+  const LkJob* dtab = reinterpret_cast<const LkJob*>(db + c.tab.off);
+  for (const LkLaunch& l : c.launches) {
+    const dim3 grid(l.grid[0], l.grid[1], l.grid[2]);
+    switch (l.kernel) {
+      case LK_K_PYRAMID: hipLaunchKernelGGL(k_lk_pyramid, grid, dim3(256), 0, s, g, dtab); break;
+      case LK_K_PAD_LEVEL0: hipLaunchKernelGGL(k_lk_pad_level0, grid, dim3(256), 0, s, g, dtab, l.which); break;
+      case LK_K_PYR_DOWN: hipLaunchKernelGGL(k_lk_pyr_down, grid, dim3(256), 0, s, g, dtab, l.which, l.level); break;
+      case LK_K_SCHARR: hipLaunchKernelGGL(k_lk_scharr, grid, dim3(256), 0, s, g, dtab, l.level); break;
+      case LK_K_TRACK: hipLaunchKernelGGL(k_lk_track, grid, dim3(256), 0, s, d, dtab); break;
     }
   }
-  for (int l = scharr_now ? 0 : d.levels; l < d.levels; ++l) {
-    const dim3 g((d.cols[l] + 2 * d.pad + 255) / 256, d.rows[l] + 2 * d.pad, nj);
-    hipLaunchKernelGGL(k_lk_scharr, g, dim3(256), 0, s, d, dtab, l);
-  }
-  if (n_pts > 0) {
-    d.max_iters = std::min(std::max(prm.max_iters, 0), 100);          // TermCriteria clamps of calcOpticalFlowPyrLK
-    const double e = std::min(std::max(prm.eps, 0.), 10.);
-    d.eps2 = e * e;
-    d.min_eig = prm.min_eig_threshold;
-    d.use_initial_flow = prm.use_initial_flow;
-    d.prev_pts = (const float*)(db + o_pp); d.next_pts = (float*)(db + o_np);
-    d.status = (uint8_t*)(db + o_st); d.err = (float*)(db + o_er);
-    hipLaunchKernelGGL(k_lk_track, dim3((max_n + 3) / 4, nj), dim3(256), 0, s, d, dtab);
+  if (c.n_pts > 0) {
     SSX_HIP_TRY(ctx, hipGetLastError());
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_np, db + o_np, host_end - o_np, hipMemcpyDeviceToHost, s));
+    SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + c.next_pts.off, db + c.next_pts.off, c.host_end - c.next_pts.off, hipMemcpyDeviceToHost, s));
   }
   SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  pt0 = 0;
+  return SSX_OK;
+}
+
+// step 9: every job's results from the pinned mirror to the caller's arrays
+void lk_scatter(const LkWorkspace* ws, int nj, const ssx_lk_job* jobs, const LkCall& c)
+{
+  const char* hs = ws->stage.as<char>();
   for (int j = 0; j < nj; ++j) {
     const ssx_lk_job& q = jobs[j];
-    slot[j]->have_next = true;
-    slot[j]->have_next_deriv = use_fused;
-    if (q.n > 0) {
-      memcpy(q.next_pts, hs + o_np + sizeof(float) * 2 * pt0, sizeof(float) * 2 * q.n);
-      memcpy(q.status, hs + o_st + pt0, (size_t)q.n);
-      if (q.err) memcpy(q.err, hs + o_er + sizeof(float) * pt0, sizeof(float) * q.n);
-    }
-    pt0 += (size_t)q.n;
+    const size_t pt0 = (size_t)c.jobs[j].pt0;
+    if (q.n > 0) memcpy(q.next_pts, hs + c.next_pts.off + sizeof(float) * 2 * pt0, sizeof(float) * 2 * q.n);
+    if (q.n > 0) memcpy(q.status, hs + c.status.off + pt0, (size_t)q.n);
+    if (q.n > 0 && q.err) memcpy(q.err, hs + c.err.off + sizeof(float) * pt0, sizeof(float) * q.n);
   }
-  if (top_level) *top_level = d.levels - 1;
+}
+
+// step 10, after the synchronisation has succeeded: the ONLY place where a slot gains a chain or turns over.  A call that fails before
+// its first launch leaves every slot as it found it (but for a change of key, which invalidates all slots in step 2); a call that
+// fails later leaves chained slots chainable -- their kept pyramid was only read, their derivative images only read or rewritten with
+// the same values -- and fresh slots without a chain (lk_enqueue).
+void lk_commit(LkWorkspace* ws, int nj, const ssx_lk_job* jobs, LkCall&& c)
+{
+  for (int j = 0; j < nj; ++j) ws->slots[jobs[j].slot].st = c.jobs[j].after;
+  ws->last = std::move(c);
+}
+
+// check, geometry, facts, build_call, reserve, fill, enqueue, synchronise, scatter, commit.  images_on_device: the image pointers are
+// readable by the GPU (device memory, or pinned host memory); else they go through pinned staging.
+ssx_status lk_run(ssx_ctx* ctx, int nj, const ssx_lk_job* jobs, int32_t rows, int32_t cols, const ssx_lk_params* prm_in, bool images_on_device,
+                  bool prev_required, int32_t* top_level)
+{
+  if (!ctx || nj < 0 || (nj > 0 && !jobs)) return SSX_ERR_INVALID_ARG;
+  if (nj == 0) return SSX_OK;
+  ssx_lk_params prm;
+  if (prm_in) prm = *prm_in; else ssx_lk_default_params(&prm);
+  LkWorkspace* ws = lk_ws(ctx);
+  const LkKey key{rows, cols, prm.win, prm.max_level};
+  std::vector<LkSlotState> before(nj);                                 // (a slot that does not exist yet: the default state)
+  for (int j = 0; j < nj; ++j) if (jobs[j].slot >= 0 && (size_t)jobs[j].slot < ws->slots.size()) before[j] = ws->slots[jobs[j].slot].st;
+  char err[LK_ERR] = {0};
+  ssx_status st = check_jobs(nj, jobs, key, ws->planned(key), before.data(), prev_required, err);
+  if (st == SSX_OK) st = lk_geometry(ctx, ws, key, err);               // (a new geometry: no job is chained, and `before` no longer matters)
+  if (st != SSX_OK) { if (err[0]) ctx->set_error("%s", err); return st; }
+  const bool next0_is_host = lk_next0_is_host(key, ws->geom, nj, jobs, images_on_device);
+  LkCall call = build_call(key, ws->geom, nj, jobs, before.data(), images_on_device, next0_is_host);
+  if ((st = lk_reserve(ctx, ws, nj, jobs, call)) != SSX_OK) return st;
+  lk_fill(ws, nj, jobs, call);
+  if ((st = lk_enqueue(ctx, ws, nj, jobs, prm, call)) != SSX_OK) return st;
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  lk_scatter(ws, nj, jobs, call);
+  lk_commit(ws, nj, jobs, std::move(call));
+  if (top_level) *top_level = ws->geom.dev.levels - 1;
   return SSX_OK;
 }
 
@@ -785,18 +904,16 @@ ssx_status ssx_lk_track(ssx_ctx* ctx, const uint8_t* prev, int32_t prev_stride, 
                         int32_t rows, int32_t cols, int32_t n, const float* prev_pts, float* next_pts, uint8_t* status,
                         float* err, const ssx_lk_params* prm_in, int32_t* top_level)
 {
-  if (!ctx || !prev || !next || n < 0 || (n > 0 && (!prev_pts || !next_pts || !status))) return SSX_ERR_INVALID_ARG;
   const ssx_lk_job q{0, prev, prev_stride, next, next_stride, n, prev_pts, next_pts, status, err};
-  return lk_run(ctx, 1, &q, rows, cols, prm_in, false, top_level);
+  return lk_run(ctx, 1, &q, rows, cols, prm_in, false, true, top_level);
 }
 
 ssx_status ssx_lk_track_next(ssx_ctx* ctx, const uint8_t* next, int32_t next_stride, int32_t rows, int32_t cols, int32_t n,
                              const float* prev_pts, float* next_pts, uint8_t* status, float* err,
                              const ssx_lk_params* prm_in, int32_t* top_level)
 {
-  if (!ctx || !next || n < 0 || (n > 0 && (!prev_pts || !next_pts || !status))) return SSX_ERR_INVALID_ARG;
   const ssx_lk_job q{0, nullptr, 0, next, next_stride, n, prev_pts, next_pts, status, err};
-  return lk_run(ctx, 1, &q, rows, cols, prm_in, false, top_level);
+  return lk_run(ctx, 1, &q, rows, cols, prm_in, false, false, top_level);
 }
 
 // n_jobs tracking problems in one call (one frame of each of n_jobs streams: FrontEnd::TrackLastFrame, frontend.cpp:130-182): every
@@ -804,24 +921,22 @@ ssx_status ssx_lk_track_next(ssx_ctx* ctx, const uint8_t* next, int32_t next_str
 ssx_status ssx_lk_track_batch(ssx_ctx* ctx, int32_t n_jobs, const ssx_lk_job* jobs, int32_t rows, int32_t cols, const ssx_lk_params* prm_in,
                               int32_t images_on_device)
 {
-  if (!ctx || n_jobs < 0 || (n_jobs > 0 && !jobs)) return SSX_ERR_INVALID_ARG;
-  if (n_jobs == 0) return SSX_OK;
-  return lk_run(ctx, n_jobs, jobs, rows, cols, prm_in, images_on_device != 0, nullptr);
+  return lk_run(ctx, n_jobs, jobs, rows, cols, prm_in, images_on_device != 0, false, nullptr);
 }
 
-#ifndef SSX_NO_TEST_HOOKS   // kernel taps of the parity tests (include/ssx_test_hooks.h)
+#ifndef SSX_NO_TEST_HOOKS   // kernel taps of the parity tests and the plan of a call (include/ssx_test_hooks.h)
 // test / debug access to the pyramid and derivative images of the last ssx_lk_track call
 ssx_status ssx_lk_stage_level(ssx_ctx* ctx, int32_t which, int32_t level, uint8_t* out, int32_t out_cap, int32_t* rows, int32_t* cols)
 {
   if (!ctx || !ctx->lk || !rows || !cols) return SSX_ERR_INVALID_ARG;
   LkWorkspace* ws = static_cast<LkWorkspace*>(ctx->lk);
-  if (!ws->planned || which < 0 || which > 1 || level < 0 || level >= ws->dev.levels) return SSX_ERR_INVALID_ARG;
-  const LkDev& d = ws->dev;
+  const LkDev& d = ws->geom.dev;
+  if (which < 0 || which > 1 || level < 0 || level >= d.levels) return SSX_ERR_INVALID_ARG;
   *rows = d.rows[level]; *cols = d.cols[level];
   if (!out) return SSX_OK;
   if (out_cap < d.rows[level] * d.cols[level]) return SSX_ERR_CAPACITY;
-  if (ws->slots.empty() || !ws->slots[0].pyr[0]) return SSX_ERR_INVALID_ARG;
-  const uint8_t* src = ws->slots[0].pyr[which] + d.off[level] + (size_t)d.pad * d.pitch[level] + d.pad;
+  if (ws->slots.empty() || !ws->slots[0].buf[0]) return SSX_ERR_INVALID_ARG;
+  const uint8_t* src = ws->slots[0].buf[lk_roles(ws->slots[0].st.flip).pyr[which]] + d.off[level] + (size_t)d.pad * d.pitch[level] + d.pad;
   SSX_HIP_TRY(ctx, hipMemcpy2DAsync(out, d.cols[level], src, d.pitch[level], d.cols[level], d.rows[level], hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return SSX_OK;
@@ -831,16 +946,83 @@ ssx_status ssx_lk_stage_deriv(ssx_ctx* ctx, int32_t level, int16_t* out, int32_t
 {
   if (!ctx || !ctx->lk || !rows || !cols) return SSX_ERR_INVALID_ARG;
   LkWorkspace* ws = static_cast<LkWorkspace*>(ctx->lk);
-  if (!ws->planned || level < 0 || level >= ws->dev.levels) return SSX_ERR_INVALID_ARG;
-  const LkDev& d = ws->dev;
+  const LkDev& d = ws->geom.dev;
+  if (level < 0 || level >= d.levels) return SSX_ERR_INVALID_ARG;
   *rows = d.rows[level]; *cols = d.cols[level];
   if (!out) return SSX_OK;
   if (out_cap < 2 * d.rows[level] * d.cols[level]) return SSX_ERR_CAPACITY;
-  if (ws->slots.empty() || !ws->slots[0].deriv) return SSX_ERR_INVALID_ARG;
-  const uint32_t* src = ws->slots[0].deriv + d.doff[level] + (size_t)d.pad * d.pitch[level] + d.pad;
+  if (ws->slots.empty() || !ws->slots[0].buf[0]) return SSX_ERR_INVALID_ARG;
+  const uint32_t* src = ws->slots[0].der[lk_roles(ws->slots[0].st.flip).deriv] + d.doff[level] + (size_t)d.pad * d.pitch[level] + d.pad;
   SSX_HIP_TRY(ctx, hipMemcpy2DAsync(out, (size_t)d.cols[level] * 4, src, (size_t)d.pitch[level] * 4, (size_t)d.cols[level] * 4, d.rows[level],
                                     hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return SSX_OK;
+}
+
+// a geometry and a call as ssx_lk_call_info (status and error are the caller's)
+static void lk_fill_info(const LkGeom& g, const LkCall& c, ssx_lk_call_info* out)
+{
+  const LkDev& d = g.dev;
+  out->levels = d.levels; out->win = d.win; out->pad = d.pad;
+  for (int l = 0; l < d.levels; ++l) {
+    out->rows[l] = d.rows[l]; out->cols[l] = d.cols[l]; out->pitch[l] = d.pitch[l];
+    out->off[l] = d.off[l]; out->doff[l] = d.doff[l];
+  }
+  out->pyr_bytes = g.pyr_bytes; out->deriv_words = g.deriv_words;
+  out->fused_ok = g.fused_ok; out->use_fused = c.use_fused; out->scharr_now = c.scharr_now; out->intake = c.intake;
+  const Span* spans[SSX_LK_SPANS] = {&c.tab, &c.images, &c.prev_pts, &c.next_pts, &c.status, &c.err, &c.dev_images};
+  for (int i = 0; i < SSX_LK_SPANS; ++i) { out->span_off[i] = spans[i]->off; out->span_bytes[i] = spans[i]->n; }
+  out->in_bytes = c.in_bytes; out->host_end = c.host_end; out->io_bytes = c.io_bytes; out->arena_bytes = c.arena_bytes;
+  out->n_launches = (int32_t)c.launches.size();
+  for (size_t i = 0; i < c.launches.size() && i < SSX_LK_MAX_LAUNCHES; ++i) {
+    const LkLaunch& l = c.launches[i];
+    out->launch[i].kernel = l.kernel; out->launch[i].which = l.which; out->launch[i].level = l.level;
+    for (int k = 0; k < 3; ++k) out->launch[i].grid[k] = (int32_t)l.grid[k];
+  }
+  out->n_jobs = (int32_t)c.jobs.size();
+  for (size_t j = 0; j < c.jobs.size() && j < SSX_LK_MAX_INFO_JOBS; ++j) {
+    const LkCallJob& cj = c.jobs[j];
+    const LkRoles r = lk_roles(cj.after.flip);
+    out->slot_flags[j] = (uint8_t)((cj.after.have_next ? 1 : 0) | (cj.after.have_next_deriv ? 2 : 0) | (cj.after.flip ? 4 : 0));
+    out->job_roles[j] = (uint8_t)(r.pyr[0] | r.pyr[1] << 1 | r.deriv << 2 | r.deriv1 << 3);
+  }
+}
+
+ssx_status ssx_lk_debug_plan(int32_t rows, int32_t cols, int32_t win, int32_t max_level, const int32_t* planned_key, int32_t n_jobs,
+                             const ssx_lk_job_facts* facts, const uint8_t* slot_flags, int32_t images_on_device, int32_t next0_is_host,
+                             ssx_lk_call_info* out)
+{
+  if (!out || n_jobs < 1 || !facts || !slot_flags) return SSX_ERR_INVALID_ARG;
+  *out = ssx_lk_call_info{};
+  static_assert(sizeof(out->error) == LK_ERR, "ssx_lk_call_info::error holds the refusal's text");
+  const LkKey key{rows, cols, win, max_level};
+  const bool planned = !planned_key || key == LkKey{planned_key[0], planned_key[1], planned_key[2], planned_key[3]};
+  // jobs whose pointers say what the facts say and are never followed: check_jobs and build_call only compare and subtract them
+  const uint8_t* const img = reinterpret_cast<const uint8_t*>(uintptr_t(1) << 40);
+  float* const pts = reinterpret_cast<float*>(uintptr_t(1) << 41);
+  std::vector<ssx_lk_job> jobs(n_jobs);
+  std::vector<LkSlotState> before(n_jobs);
+  for (int j = 0; j < n_jobs; ++j) {
+    const ssx_lk_job_facts& q = facts[j];
+    jobs[j] = ssx_lk_job{q.slot, q.fresh ? img - (uintptr_t(1) << 39) : nullptr, q.prev_stride, img + q.next_off, q.next_stride, q.n, pts, pts, (uint8_t*)pts, pts};
+    before[j] = LkSlotState{(slot_flags[j] & 4) != 0, (slot_flags[j] & 1) != 0, (slot_flags[j] & 2) != 0};
+  }
+  LkGeom g;
+  ssx_status st = check_jobs(n_jobs, jobs.data(), key, planned, before.data(), false, out->error);
+  if (st == SSX_OK) st = build_geom(key, g, out->error);
+  out->status = st;
+  if (st != SSX_OK) return st;
+  lk_fill_info(g, build_call(key, g, n_jobs, jobs.data(), before.data(), images_on_device != 0, next0_is_host != 0), out);
+  return SSX_OK;
+}
+
+ssx_status ssx_lk_debug_last_call(ssx_ctx* ctx, ssx_lk_call_info* out)
+{
+  if (!ctx || !ctx->lk || !out) return SSX_ERR_INVALID_ARG;
+  const LkWorkspace* ws = static_cast<const LkWorkspace*>(ctx->lk);
+  if (ws->last.jobs.empty()) return SSX_ERR_INVALID_ARG;
+  *out = ssx_lk_call_info{};
+  lk_fill_info(ws->geom, ws->last, out);
   return SSX_OK;
 }
 

@@ -65,6 +65,28 @@ class LkJob(C.Structure):
                 ("prev_pts", f32_p), ("next_pts", f32_p), ("status", u8_p), ("err", f32_p)]
 
 
+def _batch_fn(lib):
+    """ssx_lk_track_batch with its C signature, declared in one place"""
+    fn = lib.ssx_lk_track_batch
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LkJob), C.c_int32, C.c_int32, C.POINTER(LkParams), C.c_int32]
+    return fn
+
+
+def _fill_job(a, j, next_ptr, next_stride, prev_ptr=None, prev_stride=0):
+    """one ssx_lk_job from a job dict (slot, prev_pts, next_pts or None) and its image pointers -> (prev_pts, guess, outputs): the
+    arrays the struct points into"""
+    pp = np.ascontiguousarray(j["prev_pts"], dtype=np.float32).reshape(-1, 2)
+    guess = np.ascontiguousarray(j["next_pts"], dtype=np.float32).reshape(-1, 2).copy() if j.get("next_pts") is not None else pp.copy()
+    npts = guess.copy(); st = np.zeros(len(pp), np.uint8); er = np.zeros(len(pp), np.float32)
+    a.slot = int(j["slot"])
+    a.prev = prev_ptr; a.prev_stride = prev_stride
+    a.next = next_ptr; a.next_stride = next_stride
+    a.n = len(pp); a.prev_pts = pp.ctypes.data_as(f32_p); a.next_pts = npts.ctypes.data_as(f32_p)
+    a.status = st.ctypes.data_as(u8_p); a.err = er.ctypes.data_as(f32_p)
+    return pp, guess, (npts, st, er)
+
+
 class PreparedTrackBatch:
     """ssx_lk_track_batch with everything a C caller holds between frames prepared once: the job structs, the points, and the images in
     PINNED memory (ssx_host_alloc) handed over with images_on_device = 1 -- what ssvio_amd/host/stream_batcher.cpp does per frame.
@@ -87,24 +109,16 @@ class PreparedTrackBatch:
                 raise MemoryError("ssx_host_alloc")
             C.memmove(pin, nxt.ctypes.data, nxt.size)
             self.pins.append(pin)
-            pp = np.ascontiguousarray(j["prev_pts"], dtype=np.float32).reshape(-1, 2)
-            g = np.ascontiguousarray(j["next_pts"], dtype=np.float32).reshape(-1, 2).copy() if j.get("next_pts") is not None else pp.copy()
-            npts = g.copy(); st = np.zeros(len(pp), np.uint8); er = np.zeros(len(pp), np.float32)
-            a = self.arr[i]
-            a.slot = int(j["slot"]); a.prev = None; a.prev_stride = 0
-            a.next = C.cast(pin, u8_p); a.next_stride = self.cols
-            a.n = len(pp); a.prev_pts = pp.ctypes.data_as(f32_p); a.next_pts = npts.ctypes.data_as(f32_p)
-            a.status = st.ctypes.data_as(u8_p); a.err = er.ctypes.data_as(f32_p)
-            self.keep.append(pp); self.outs.append((npts, st, er)); self.guess.append(g)
+            pp, g, out = _fill_job(self.arr[i], j, C.cast(pin, u8_p), self.cols)
+            self.keep.append(pp); self.outs.append(out); self.guess.append(g)
         self.n = n
         self.prm = LkParams(int(winSize), int(maxLevel), int(maxCount), float(epsilon), float(minEigThreshold), int(use_init))
-        lib.ssx_lk_track_batch.restype = C.c_int
-        lib.ssx_lk_track_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LkJob), C.c_int32, C.c_int32, C.POINTER(LkParams), C.c_int32]
+        self.fn = _batch_fn(lib)
 
     def run(self):
         for (npts, _, _), g in zip(self.outs, self.guess):
             npts[:] = g
-        self.ctx.check(self.ctx.lib.ssx_lk_track_batch(self.ctx.handle, self.n, self.arr, self.rows, self.cols, C.byref(self.prm), 1))
+        self.ctx.check(self.fn(self.ctx.handle, self.n, self.arr, self.rows, self.cols, C.byref(self.prm), 1))
         return self.outs
 
     def close(self):
@@ -125,21 +139,79 @@ def track_batch(ctx: Context, jobs, winSize=11, maxLevel=3, maxCount=30, epsilon
     for i, j in enumerate(jobs):
         nxt = _img(j["next"]); prev = None if j.get("prev") is None else _img(j["prev"])
         rows, cols = nxt.shape
-        pp = np.ascontiguousarray(j["prev_pts"], dtype=np.float32).reshape(-1, 2)
-        npts = np.ascontiguousarray(j["next_pts"], dtype=np.float32).reshape(-1, 2).copy() if j.get("next_pts") is not None else pp.copy()
-        st = np.zeros(len(pp), np.uint8); er = np.zeros(len(pp), np.float32)
-        a = arr[i]
-        a.slot = int(j["slot"])
-        a.prev = None if prev is None else prev.ctypes.data_as(u8_p); a.prev_stride = 0 if prev is None else prev.strides[0]
-        a.next = nxt.ctypes.data_as(u8_p); a.next_stride = nxt.strides[0]
-        a.n = len(pp); a.prev_pts = pp.ctypes.data_as(f32_p); a.next_pts = npts.ctypes.data_as(f32_p)
-        a.status = st.ctypes.data_as(u8_p); a.err = er.ctypes.data_as(f32_p)
-        keep.append((nxt, prev, pp)); outs.append((npts, st, er))
+        pp, _, out = _fill_job(arr[i], j, nxt.ctypes.data_as(u8_p), nxt.strides[0], None if prev is None else prev.ctypes.data_as(u8_p),
+                               0 if prev is None else prev.strides[0])
+        keep.append((nxt, prev, pp)); outs.append(out)
     prm = LkParams(int(winSize), int(maxLevel), int(maxCount), float(epsilon), float(minEigThreshold), int(use_init))
-    ctx.lib.ssx_lk_track_batch.restype = C.c_int
-    ctx.lib.ssx_lk_track_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LkJob), C.c_int32, C.c_int32, C.POINTER(LkParams), C.c_int32]
-    ctx.check(ctx.lib.ssx_lk_track_batch(ctx.handle, n, arr, rows, cols, C.byref(prm), 1 if images_on_device else 0))
+    ctx.check(_batch_fn(ctx.lib)(ctx.handle, n, arr, rows, cols, C.byref(prm), 1 if images_on_device else 0))
     return outs
+
+
+def track_batch_ptrs(ctx: Context, jobs, rows, cols, winSize=11, maxLevel=3, maxCount=30, epsilon=0.01, minEigThreshold=1e-4):
+    """ssx_lk_track_batch with images_on_device = 1 on images the caller holds in memory the GPU can read: jobs = [dict(slot, prev
+    (address or None), next (address), stride, prev_pts, next_pts or None)].  -> [(next_pts, status, err)] per job."""
+    arr = (LkJob * len(jobs))()
+    use_init = any(j.get("next_pts") is not None for j in jobs)
+    filled = [_fill_job(arr[i], j, C.cast(j["next"], u8_p), j["stride"], None if j.get("prev") is None else C.cast(j["prev"], u8_p),
+                        0 if j.get("prev") is None else j["stride"]) for i, j in enumerate(jobs)]
+    prm = LkParams(int(winSize), int(maxLevel), int(maxCount), float(epsilon), float(minEigThreshold), int(use_init))
+    ctx.check(_batch_fn(ctx.lib)(ctx.handle, len(jobs), arr, rows, cols, C.byref(prm), 1))
+    return [f[2] for f in filled]
+
+
+# ---- the plan of a call (include/ssx_test_hooks.h: ssx_lk_debug_plan needs no GPU, ssx_lk_debug_last_call reports the last call) ----
+STAGED, ARENA, EACH, IN_PLACE = range(4)
+KERNELS = ("k_lk_pyramid", "k_lk_pad_level0", "k_lk_pyr_down", "k_lk_scharr", "k_lk_track")
+SPANS = ("tab", "images", "prev_pts", "next_pts", "status", "err", "dev_images")
+
+
+class LkLaunch(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("grid", C.c_int32 * 3), ("which", C.c_int32), ("level", C.c_int32)]
+
+
+class LkCallInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("error", C.c_char * 256), ("levels", C.c_int32), ("win", C.c_int32), ("pad", C.c_int32),
+                ("rows", C.c_int32 * 8), ("cols", C.c_int32 * 8), ("pitch", C.c_int32 * 8), ("off", C.c_uint64 * 8), ("doff", C.c_uint64 * 8),
+                ("pyr_bytes", C.c_uint64), ("deriv_words", C.c_uint64), ("fused_ok", C.c_int32), ("use_fused", C.c_int32),
+                ("scharr_now", C.c_int32), ("intake", C.c_int32), ("span_off", C.c_uint64 * 7), ("span_bytes", C.c_uint64 * 7),
+                ("in_bytes", C.c_uint64), ("host_end", C.c_uint64), ("io_bytes", C.c_uint64), ("arena_bytes", C.c_uint64),
+                ("n_launches", C.c_int32), ("n_jobs", C.c_int32), ("launch", LkLaunch * 32), ("slot_flags", C.c_uint8 * 256),
+                ("job_roles", C.c_uint8 * 256)]
+
+
+class LkJobFacts(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("fresh", C.c_int32), ("n", C.c_int32), ("prev_stride", C.c_int32), ("next_stride", C.c_int32),
+                ("reserved", C.c_int32), ("next_off", C.c_int64)]
+
+
+def debug_plan(lib, rows, cols, jobs, slot_flags=None, win=11, max_level=3, planned_key=None, images_on_device=0, next0_is_host=0):
+    """ssx_lk_debug_plan: jobs = [dict(slot, fresh, n, prev_stride, next_stride, next_off)] (strides default to cols, next_off to
+    job index x rows x cols); slot_flags per job (default: 3 for a chained job, 0 for a fresh one) -> LkCallInfo"""
+    n = len(jobs)
+    arr = (LkJobFacts * n)()
+    for i, j in enumerate(jobs):
+        arr[i] = LkJobFacts(j["slot"], int(j["fresh"]), j.get("n", 0), j.get("prev_stride", cols if j["fresh"] else 0),
+                            j.get("next_stride", cols), 0, j.get("next_off", i * rows * cols))
+    if slot_flags is None:
+        slot_flags = [0 if j["fresh"] else 3 for j in jobs]
+    out = LkCallInfo()
+    key = None if planned_key is None else (C.c_int32 * 4)(*planned_key)
+    lib.ssx_lk_debug_plan.restype = C.c_int
+    lib.ssx_lk_debug_plan.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(LkJobFacts), C.POINTER(C.c_uint8), C.c_int32,
+                                                        C.c_int32, C.POINTER(LkCallInfo)]
+    st = lib.ssx_lk_debug_plan(rows, cols, win, max_level, key, n, arr, (C.c_uint8 * n)(*slot_flags), int(images_on_device), int(next0_is_host),
+                               C.byref(out))
+    assert st == out.status
+    return out
+
+
+def last_call(ctx: Context):
+    """ssx_lk_debug_last_call -> LkCallInfo of the last successful LK call of ctx"""
+    out = LkCallInfo()
+    ctx.lib.ssx_lk_debug_last_call.restype = C.c_int
+    ctx.lib.ssx_lk_debug_last_call.argtypes = [C.c_void_p, C.POINTER(LkCallInfo)]
+    ctx.check(ctx.lib.ssx_lk_debug_last_call(ctx.handle, C.byref(out)))
+    return out
 
 
 def stage_level(ctx: Context, which, level):

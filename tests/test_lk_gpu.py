@@ -233,3 +233,37 @@ def test_wide_and_narrow_calls_interleave(ctx, po):
     call(range(S), False)                  # wide, chained: slots 0 .. 3 come from a narrow call, the others from the first wide one
     call(range(few, 2 * few), False)       # narrow after wide for other slots
     c.close()
+
+
+@pytest.mark.parametrize("h,w,max_level,nj", [(120, 168, 3, 3), (120, 168, 3, 17), (240, 400, 4, 3), (240, 400, 4, 17)])
+def test_every_image_intake_gives_the_same_bits(po, h, w, max_level, nj):
+    """The four ways an image reaches the device (csrc/lk.hip: choose_intake) give, per job, the bytes of the staged path in points,
+    status and error: one pinned block sliced at a constant distance (one DMA copy), the same with a slice left out, a pinned block per
+    image and a device buffer per image (both listed in descending address order, so that no arena is seen) -- for k_lk_pyramid (3 jobs
+    at four levels) and the per-level kernels (17 jobs, or five levels), a fresh call and then a chained one through the same intake, one
+    job without points.  Which intake and which pyramid kernel a call took is asserted through ssx_lk_debug_last_call."""
+    import lk_call_cases as cc
+    from ssvio_amd import Context
+    from tools.lk_call_trace import Replay
+    cases = {c["name"]: c for c in cc.CASES}
+    c = Context(0)
+    ref = []
+    host = Replay(c, cases[f"intake-{h}x{w}-{nj}jobs-{cc.HOST}"])
+    for k in host.c["calls"]:
+        ref.append(host.run(k))
+        info = lk.last_call(c)
+        assert (info.intake, bool(info.use_fused)) == (cc.STAGED, host.c["use_fused"])
+        if nj == 3:
+            prm = po.lk_params(max_level=max_level)
+            for s_, (prev, nxt), p, g in zip(k["slots"], host.pairs, host.pts, ref[-1]):
+                o = po.lk_track(host.frames[s_][host.cur[s_] - 1] if prev is None else prev, nxt, p, p, prm=prm)
+                assert _same(g[0], o[0]) and _same(g[1], o[1]) and _same(g[2], o[2]), (s_, k["fresh"])
+    for layout in (cc.ARENA, cc.ARENA_SKIP, cc.SEPARATE_HOST, cc.DEVICE):
+        r = Replay(c, cases[f"intake-{h}x{w}-{nj}jobs-{layout}"])
+        for k, want in zip(r.c["calls"], ref):
+            got = r.run(k)
+            info = lk.last_call(c)
+            assert (info.intake, bool(info.use_fused)) == (r.c["intake"], r.c["use_fused"]), layout
+            for j, (g, o) in enumerate(zip(got, want)):
+                assert _same(g[0], o[0]) and _same(g[1], o[1]) and _same(g[2], o[2]), (layout, k["fresh"], j)
+    c.close()
