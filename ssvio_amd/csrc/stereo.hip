@@ -1,9 +1,11 @@
 // ssvio_amd/csrc/stereo.hip -- stereo association and triangulation on gfx950.
 //
 //   k_row_bucket     counting sort of the right keypoints by image row (LDS histogram + scan)
-//   k_match          ROW-BAND Hamming matcher, one wave per left keypoint: only the right keypoints whose row lies
-//                    in the band are visited; 256-bit XOR + 4 x popcount per candidate; wave-wide min-reduce on
-//                    (distance << 16 | right index) = minimum distance, lowest index wins ties
+//   k_match          ROW-BAND Hamming matcher, one wave per left keypoint: only the row buckets floorf(y - band) ..
+//                    floorf(y + band) are visited, one more below where y - band lies within rounding of an integer row: a
+//                    superset of what the exact float predicate inside the loop accepts (see the kernel); 256-bit XOR +
+//                    4 x popcount per candidate; wave-wide min-reduce on (distance << 16 | right index) = minimum distance,
+//                    lowest index wins ties
 //                    (the semantics of OpenCV BruteForce-Hamming match(), /root/reference/src/ssvio/loopclosing.cpp:24,108)
 //   k_bf_match       the unrestricted brute-force matcher of loop closing (loopclosing.cpp:105-110)
 //   k_triangulate    ssvio::triangulation (/root/reference/include/ssvio/algorithm.hpp:23-45): DLT rows of the two 3x4
@@ -109,7 +111,14 @@ __global__ __launch_bounds__(256) void k_match(MatchDev m)
   const int ol = a.octave < 0 ? 0 : (a.octave > 31 ? 31 : a.octave);
   const float band = m.mp.band_px * m.scale[ol];
   const int R = m.rows + 1;
-  int r0 = (int)floorf(a.y - band), r1 = (int)floorf(a.y + band);
+  // The visited buckets must hold every right keypoint the predicate below accepts.  floorf(a.y - band) alone does not: a.y - band
+  // can round UP to (or just past) an integer k while a b.y a few ulps under k (float is finer there than near a.y) still gives
+  // a.y - b.y == band after rounding -- accepted, but bucketed in row k - 1.  That needs lo - k < (ulp(band) + ulp(lo)) / 2
+  // <= (band + |lo|) * 2^-24; with a margin of four, such a window starts one row earlier (a b.y under k - 1 is a whole row outside
+  // the band).  The upper edge has no such case: a.y + band rounds to k whenever it is within half an ulp of it.
+  // tests/stereo_cases.py (window_model) restates this window and tests/test_stereo_cases.py sweeps it against the predicate.
+  const float lo = a.y - band, flo = floorf(lo);
+  int r0 = (int)flo - ((lo - flo < (band + fabsf(lo)) * 0x1p-22f) ? 1 : 0), r1 = (int)floorf(a.y + band);
   r0 = r0 < 0 ? 0 : (r0 >= R ? R - 1 : r0);
   r1 = r1 < 0 ? 0 : (r1 >= R ? R - 1 : r1);
   const int c0 = (nR > 0) ? row_ptr[r0] : 0, c1 = (nR > 0) ? row_ptr[r1 + 1] : 0;
