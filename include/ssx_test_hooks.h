@@ -137,6 +137,12 @@ SSX_API ssx_status ssx_lk_debug_last_call(ssx_ctx* ctx, ssx_lk_call_info* out);
 SSX_API ssx_status ssx_pnp_debug_samples(ssx_ctx* ctx, uint32_t seed, int32_t M, int32_t H, int32_t* triples_out);
 SSX_API ssx_status ssx_pnp_debug_counts(ssx_ctx* ctx, const double* K4, int32_t M, const double* xyz, const double* uv,
                                         int32_t max_iters, double reproj_px, uint32_t seed, int32_t* counts_out);
+/* the minimal solver alone: n triples (xyz n x 3 x 3, uv n x 3 x 2), one thread each, p3p_solve and rot_to_quat as k_pnp_ransac calls
+ * them -> per triple and slot (solution 2 p + r is root r of plane p) valid_out n x 4, R_out n x 4 x 9 (row-major), t_out n x 4 x 3 and
+ * pose_out n x 4 x 7 (qx qy qz qw tx ty tz); a slot that is not valid is all zeros.  n = 0 does nothing.  Reference:
+ * tests/golden/p3p_hp.npz */
+SSX_API ssx_status ssx_pnp_debug_p3p(ssx_ctx* ctx, const double* K4, int32_t n, const double* xyz, const double* uv, int32_t* valid_out,
+                                     double* R_out, double* t_out, double* pose_out);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,11 @@
 //                solver is described in tools/pnp_model.py and uses + - * / sqrt only, with fixed numbers of Newton steps), then the
 //                lanes stride over the M points per solution: inlier = positive depth and ex^2 + ey^2 <= thr^2 (thr in PIXELS: the
 //                reference passes its chi-square constant as OpenCV's pixel threshold), counted by ballot + popcount.  A degenerate
-//                triple yields no solution and scores 0: validity is decided by finiteness tests, no NaN reaches a comparison.
+//                triple yields no solution and scores 0: validity is decided by finiteness tests, no NaN reaches a comparison, and a
+//                solution is handed on only if it satisfies the three quadrics (kResidCut) and spans a triangle of the area of the
+//                points' (kAreaCut: the sides of a needle hold to rounding while R is stretched along its normal) -- both cut-offs are
+//                stated against the 60-digit reference tests/golden/p3p_hp.npz in tools/pnp_model.py.  Two plane pairs for D1 and D2
+//                (both determinants 0: an equilateral triangle on the axis) need no cubic: g = 0.
 //                ALL max_iters hypotheses are scored: the confidence-driven early exit of OpenCV's loop is a sequential notion, a
 //                launch has no use for it.
 //                Selection: max over (count << 32) | ~(4 h + s) -- the most inliers, then the lowest hypothesis, then the lowest
@@ -21,7 +25,8 @@
 //                (qx qy qz qw tx ty tz, normalised, qw >= 0), its inlier mask and the header: they stay in device memory, where
 //                the refinement (k_pose_only*, gated by the header's `found`) picks the pose up.
 //
-// This file is compiled with -ffp-contract=off: every operation rounds as the model's does.
+// This file is compiled with -ffp-contract=off: every operation rounds as the model's does (tests/test_p3p_gpu.py: R, t and the pose of
+// every slot of ssx_pnp_debug_p3p are the model's bytes).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -36,6 +41,8 @@ namespace {
 
 constexpr int kNewtonSteps = 16;    // on the cubic
 constexpr int kGnSteps = 3;         // on the three quadrics
+constexpr double kResidCut = 5.9e-9;    // on the three quadrics, relative to l1^2 + l2^2 + l3^2 (tools/pnp_model.py: RESID_CUT)
+constexpr double kAreaCut = 1e-6;       // on |q1 x q2|^2 / |p1 x p2|^2 - 1 (AREA_CUT)
 constexpr int kMinInliers = 4;      // a hypothesis explains its own three points: a pose needs one more
 
 struct PnpHdr {                     // results of k_pnp_ransac, in device memory
@@ -182,11 +189,13 @@ __device__ __forceinline__ void p3p_solve(const PnpDev& d, const double (*X)[3],
     Ja[k] = keep ? J1[k] : J2[k]; Jb[k] = keep ? J2[k] : J1[k];
   }
   const double deta = keep ? det1 : det2, detb = keep ? det2 : det1;
-  if (!(fabs(detb) > 0.0)) return;
-  const double cb = dot_sym(Da, Jb) / detb, cc = dot_sym(Ja, Db) / detb, cd = deta / detb;   // (a tiny detb can make them infinite)
-  if (!(isfinite(cb) && isfinite(cc) && isfinite(cd))) return;
-  const double g = cubic_root(cb, cc, cd);
-  if (!isfinite(g)) return;
+  double g = 0.0;                                             // detb = 0, hence deta = 0: Da is a plane pair itself (a12 = a23 and b12 = b23, say)
+  if (fabs(detb) > 0.0) {
+    const double cb = dot_sym(Da, Jb) / detb, cc = dot_sym(Ja, Db) / detb, cd = deta / detb;   // (a tiny detb can make them infinite)
+    if (!(isfinite(cb) && isfinite(cc) && isfinite(cd))) return;
+    g = cubic_root(cb, cc, cd);
+    if (!isfinite(g)) return;
+  }
   double C[6], Q[6];
   const bool q_b = fabs(g) <= 1.0;                            // on the planes Da = -g Db: the one that is not small there
 #pragma unroll
@@ -255,6 +264,15 @@ __device__ __forceinline__ void p3p_solve(const PnpDev& d, const double (*X)[3],
         l1 = l1 - e1; l2 = l2 - e2; l3 = l3 - e3;
       }
       if (!(isfinite(l1) && isfinite(l2) && isfinite(l3) && l1 > 0.0 && l2 > 0.0 && l3 > 0.0)) continue;
+      {
+        // a solution satisfies the three quadrics: where the iteration has not arrived (a plane pair that is none, a multiple root)
+        // there is no pose to hand on
+        const double r0 = l1 * l1 + l2 * l2 + b12 * (l1 * l2) - a12;
+        const double r1 = l1 * l1 + l3 * l3 + b13 * (l1 * l3) - a13;
+        const double r2 = l2 * l2 + l3 * l3 + b23 * (l2 * l3) - a23;
+        const double cut = kResidCut * (l1 * l1 + l2 * l2 + l3 * l3);
+        if (!(isfinite(r0) && isfinite(r1) && isfinite(r2) && isfinite(cut) && fabs(r0) <= cut && fabs(r1) <= cut && fabs(r2) <= cut)) continue;
+      }
       l1 = l1 * sqS; l2 = l2 * sqS; l3 = l3 * sqS;
       const double Y[3][3] = {{l1 * y[0][0], l1 * y[0][1], l1 * y[0][2]}, {l2 * y[1][0], l2 * y[1][1], l2 * y[1][2]}, {l3 * y[2][0], l3 * y[2][1], l3 * y[2][2]}};
       const double p1[3] = {X[1][0] - X[0][0], X[1][1] - X[0][1], X[1][2] - X[0][2]};
@@ -266,6 +284,11 @@ __device__ __forceinline__ void p3p_solve(const PnpDev& d, const double (*X)[3],
       cross3(q1, q2, q3);
       const double det = p3[0] * p3[0] + p3[1] * p3[1] + p3[2] * p3[2];
       if (!(isfinite(det) && det > 0.0)) continue;
+      // ... and spans a triangle congruent to the points': a needle's height is lost in the rounding of its sides, and the frames below
+      // would stretch R along the normal by the ratio of the two areas
+      const double area = q3[0] * q3[0] + q3[1] * q3[1] + q3[2] * q3[2];
+      const double acut = kAreaCut * det;
+      if (!(isfinite(area) && isfinite(acut) && fabs(area - det) <= acut)) continue;
       cross3(p2, p3, w1);                                     // rows of the inverse of [p1 p2 p3], times det
       cross3(p3, p1, w2);
       const int k = 2 * pl + r;
@@ -398,6 +421,37 @@ __global__ __launch_bounds__(256) void k_pnp_ransac(PnpDev d)
     d.hdr->n_inliers = found ? n_best : 0;
     d.hdr->best = found ? id : -1;
     d.hdr->pad = 0;
+  }
+}
+
+// tap: one thread per triple, the solver and the quaternion as k_pnp_ransac calls them; slots that are not valid are zeros
+__global__ void k_pnp_p3p_tap(PnpDev d, int n, int32_t* valid, double* R, double* t, double* pose)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double X[3][3], z[3][2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    X[k][0] = d.xyz[9 * (size_t)i + 3 * k]; X[k][1] = d.xyz[9 * (size_t)i + 3 * k + 1]; X[k][2] = d.xyz[9 * (size_t)i + 3 * k + 2];
+    z[k][0] = d.uv[6 * (size_t)i + 2 * k]; z[k][1] = d.uv[6 * (size_t)i + 2 * k + 1];
+  }
+  P3P sol;
+  p3p_solve(d, X, z, sol);
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const size_t o = 4 * (size_t)i + s;
+    const bool ok = sol.valid[s];
+    double q[4] = {0.0, 0.0, 0.0, 0.0};
+    if (ok) rot_to_quat(sol.R[s], q);
+    valid[o] = ok ? 1 : 0;
+#pragma unroll
+    for (int a = 0; a < 9; ++a) R[9 * o + a] = ok ? sol.R[s][a] : 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[3 * o + a] = ok ? sol.t[s][a] : 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) pose[7 * o + a] = q[a];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) pose[7 * o + 4 + a] = ok ? sol.t[s][a] : 0.0;
   }
 }
 
@@ -641,6 +695,39 @@ ssx_status ssx_pnp_debug_counts(ssx_ctx* ctx, const double* K4, int32_t M, const
   if (st == SSX_OK) st = pnp_download(ctx, p, p.o_counts, sizeof(int32_t) * (size_t)max_iters);
   if (st != SSX_OK) return st;
   memcpy(counts_out, ctx->pnp_stage.as<char>() + p.o_counts, sizeof(int32_t) * (size_t)max_iters);
+  return SSX_OK;
+}
+
+ssx_status ssx_pnp_debug_p3p(ssx_ctx* ctx, const double* K4, int32_t n, const double* xyz, const double* uv, int32_t* valid_out, double* R_out,
+                             double* t_out, double* pose_out)
+{
+  if (!ctx || !K4 || n < 0 || !finite4(K4) || (n > 0 && (!xyz || !uv || !valid_out || !R_out || !t_out || !pose_out))) return SSX_ERR_INVALID_ARG;
+  if (n == 0) return SSX_OK;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t N = (size_t)n;
+  Layout lay;
+  const size_t o_xyz = lay.take(sizeof(double) * 9 * N), o_uv = lay.take(sizeof(double) * 6 * N), in_bytes = lay.off;
+  const size_t o_R = lay.take(sizeof(double) * 36 * N), o_t = lay.take(sizeof(double) * 12 * N), o_pose = lay.take(sizeof(double) * 28 * N);
+  const size_t o_valid = lay.take(sizeof(int32_t) * 4 * N), bytes = lay.off;
+  SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(bytes));
+  SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(bytes));
+  char* hs = ctx->pnp_stage.as<char>();
+  char* base = ctx->pnp_arena.as<char>();
+  memcpy(hs + o_xyz, xyz, sizeof(double) * 9 * N);
+  memcpy(hs + o_uv, uv, sizeof(double) * 6 * N);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  PnpDev d = {};
+  d.fx = K4[0]; d.fy = K4[1]; d.cx = K4[2]; d.cy = K4[3];
+  d.xyz = (const double*)(base + o_xyz); d.uv = (const double*)(base + o_uv);
+  hipLaunchKernelGGL(k_pnp_p3p_tap, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, ctx->stream, d, n, (int32_t*)(base + o_valid), (double*)(base + o_R),
+                     (double*)(base + o_t), (double*)(base + o_pose));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_R, base + o_R, bytes - o_R, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(R_out, hs + o_R, sizeof(double) * 36 * N);
+  memcpy(t_out, hs + o_t, sizeof(double) * 12 * N);
+  memcpy(pose_out, hs + o_pose, sizeof(double) * 28 * N);
+  memcpy(valid_out, hs + o_valid, sizeof(int32_t) * 4 * N);
   return SSX_OK;
 }
 #endif

@@ -3,8 +3,9 @@ cv::solvePnPRansac call of LoopClosing::ComputeCorrectPose (reference: src/ssvio
 cannot be pinned (its sampler and its early exit belong to one build of one library), so the contract is this file: the
 same counter-based sampler, the same minimal solver written operation by operation as the kernel writes it, the same inlier
 rule and the same selection.  Every scalar is a numpy float64 and every operation is one IEEE operation (the kernel is built
-with -ffp-contract=off), so the kernel and this file agree to the bit; tests/test_pnp_model.py checks the model against
-ground truth, tests/test_loop_pose_gpu.py the kernel against the model.
+with -ffp-contract=off), so the kernel and this file agree to the bit: tests/test_p3p_gpu.py asserts it on R, t and the pose of
+every slot over tests/golden/p3p_hp.npz.  tests/test_pnp_model.py checks the model against ground truth, tests/test_p3p_cases.py its
+minimal solver against a 60-digit reference (complete, accurate, sound), tests/test_loop_pose_gpu.py the kernel against the model.
 
 sample_triple   three distinct indices of [0, M) as a pure function of (seed, h, M)
 p3p             up to four (R, t) for three bearings and three points
@@ -20,12 +21,30 @@ three Gauss-Newton steps on the three quadrics, and turned into (R, t) by the fr
 + - * / and sqrt are used.  (The construction follows Persson & Nordberg, "Lambda Twist: An Accurate Fast Robust
 Perspective Three Point (P3P) Solver", ECCV 2018; the splitting of the degenerate cone is the classical one of projective
 geometry.)
+
+Where both D1 and D2 are plane pairs themselves (det D1 = det D2 = 0 in double: an equilateral triangle seen on its axis, a12 = a23 and
+b12 = b23) there is no cubic to solve: g = 0, the member is Da.  (Before, this returned nothing where the reference has four poses.)
+
+What makes a slot valid.  Finite and positive depths are not enough: a slot is a hypothesis that is scored with R and whose
+rot_to_quat(R) is handed to the refinement, so it has to be a pose.  Two conditions, both measured against the 60-digit reference
+(tests/golden/make_p3p_hp.py; over its well-posed cases, at the reference's depths rounded to double, in this file's arithmetic):
+  RESID_CUT  the three quadrics hold to 5.9e-9 (l1^2 + l2^2 + l3^2) = 2^24 x the reference's worst, 3.52e-16.  Three Gauss-Newton steps
+             end at 1e-16 except next to a double root, where they leave a continuum of residuals r whose poses miss their own pixels by
+             about 2e3 r px (40 000 random triples: r up to 6e-9); the cut keeps that under 2e-5 px and every hypothesis of
+             tests/loop_pose_cases.py (largest 4.6e-12) as it was.
+  AREA_CUT   the triangle of the solution has the area of the points' triangle: | |q1 x q2|^2 / |p1 x p2|^2 - 1 | <= 1e-6 = 7.8e5 x the
+             reference's worst, 1.28e-12 (a 1 cm triangle at 50 m, where this file's own depths leave 1.6e-8).  The sides of a needle
+             (height 1e-6 of its length) hold to rounding while its height is off by percents; the frames then stretch R along the
+             normal by that ratio, and R is no rotation (|R R' - I| of 0.02 and 0.06 were returned as valid).  1e-6 is a stretch of 5e-7:
+             under 1e-3 px at any bearing the camera has.
 """
 import numpy as np
 
 F = np.float64
 NEWTON_STEPS = 16      # on the cubic
 GN_STEPS = 3           # on the three quadrics
+RESID_CUT = 5.9e-9     # on the three quadrics, relative to l1^2 + l2^2 + l3^2
+AREA_CUT = 1e-6        # on |q1 x q2|^2 / |p1 x p2|^2 - 1
 MIN_INLIERS = 4        # a hypothesis explains its own three points: a pose needs one more
 MAX_ITERS = 4096       # SSX_PNP_MAX_ITERS
 
@@ -113,13 +132,15 @@ def _fin(*v):
     return all(np.isfinite(x) for x in v)
 
 
-def p3p(K, X, uv):
-    """X [3, 3] points, uv [3, 2] pixels -> (valid [4] bool, R [4, 3, 3], t [4, 3]).  Solution 2 p + r is root r of plane p."""
+def p3p(K, X, uv, trace=None):
+    """X [3, 3] points, uv [3, 2] pixels -> (valid [4] bool, R [4, 3, 3], t [4, 3]).  Solution 2 p + r is root r of plane p.
+    trace: a list that receives (slot, largest |quadric residual| / (l1^2 + l2^2 + l3^2)) of every candidate that reaches that cut-off, and (4 + slot, the relative
+    difference of the two squared areas) of every one that reaches the second."""
     with np.errstate(all="ignore"):
-        return _p3p(K, X, uv)
+        return _p3p(K, X, uv, trace)
 
 
-def _p3p(K, X, uv):
+def _p3p(K, X, uv, trace=None):
     fx, fy, cx, cy = (F(v) for v in K)
     valid = np.zeros(4, bool)
     Rs = np.zeros((4, 3, 3))
@@ -158,14 +179,14 @@ def _p3p(K, X, uv):
         Da, Db, Ja, Jb, deta, detb = D1, D2, J1, J2, det1, det2
     else:
         Da, Db, Ja, Jb, deta, detb = D2, D1, J2, J1, det2, det1
-    if not abs(detb) > 0:
-        return valid, Rs, ts
-    cb, cc, cd = _dot_sym(Da, Jb) / detb, _dot_sym(Ja, Db) / detb, deta / detb   # (a tiny detb can make them infinite)
-    if not _fin(cb, cc, cd):
-        return valid, Rs, ts
-    g = _cubic_root(cb, cc, cd)
-    if not _fin(g):
-        return valid, Rs, ts
+    g = F(0.0)                                       # detb = 0, hence deta = 0: Da is a plane pair itself (a12 = a23 and b12 = b23, say)
+    if abs(detb) > 0:
+        cb, cc, cd = _dot_sym(Da, Jb) / detb, _dot_sym(Ja, Db) / detb, deta / detb   # (a tiny detb can make them infinite)
+        if not _fin(cb, cc, cd):
+            return valid, Rs, ts
+        g = _cubic_root(cb, cc, cd)
+        if not _fin(g):
+            return valid, Rs, ts
     C = tuple(Da[k] + g * Db[k] for k in range(6))
     Q = Db if abs(g) <= 1 else Da                    # on the planes Da = -g Db: the one that is not small there
     # C = l m' + m l' with p = l x m: -adj(C) = p p', and C + [p]x = 2 m l'
@@ -228,6 +249,16 @@ def _p3p(K, X, uv):
                 l1, l2, l3 = l1 - e1, l2 - e2, l3 - e3
             if not (_fin(l1, l2, l3) and l1 > 0 and l2 > 0 and l3 > 0):
                 continue
+            # a solution satisfies the three quadrics: where the iteration has not arrived (a plane pair that is none, a multiple root)
+            # there is no pose to hand on
+            r0 = l1 * l1 + l2 * l2 + b12 * (l1 * l2) - a12
+            r1 = l1 * l1 + l3 * l3 + b13 * (l1 * l3) - a13
+            r2 = l2 * l2 + l3 * l3 + b23 * (l2 * l3) - a23
+            cut = F(RESID_CUT) * (l1 * l1 + l2 * l2 + l3 * l3)
+            if trace is not None:
+                trace.append((2 * pl + r, max(abs(r0), abs(r1), abs(r2)) / (l1 * l1 + l2 * l2 + l3 * l3)))
+            if not (_fin(r0, r1, r2, cut) and abs(r0) <= cut and abs(r1) <= cut and abs(r2) <= cut):
+                continue
             l1, l2, l3 = l1 * sqS, l2 * sqS, l3 * sqS
             Y = [(l1 * y[0][0], l1 * y[0][1], l1 * y[0][2]), (l2 * y[1][0], l2 * y[1][1], l2 * y[1][2]), (l3 * y[2][0], l3 * y[2][1], l3 * y[2][2])]
             p1 = (X[1][0] - X[0][0], X[1][1] - X[0][1], X[1][2] - X[0][2])
@@ -239,6 +270,14 @@ def _p3p(K, X, uv):
             det = p3[0] * p3[0] + p3[1] * p3[1] + p3[2] * p3[2]
             if not (_fin(det) and det > 0):
                 continue
+            # ... and spans a triangle congruent to the points': a needle's height is lost in the rounding of its sides, and the frames
+            # below would stretch R along the normal by the ratio of the two areas
+            area = q3[0] * q3[0] + q3[1] * q3[1] + q3[2] * q3[2]
+            acut = F(AREA_CUT) * det
+            if trace is not None:
+                trace.append((4 + 2 * pl + r, abs(area - det) / det))
+            if not (_fin(area, acut) and abs(area - det) <= acut):
+                continue
             w1, w2 = _cross(p2, p3), _cross(p3, p1)              # rows of the inverse of [p1 p2 p3], times det
             R = [[(q1[a] * w1[c] + q2[a] * w2[c] + q3[a] * p3[c]) / det for c in range(3)] for a in range(3)]
             t = [Y[0][a] - (R[a][0] * X[0][0] + R[a][1] * X[0][1] + R[a][2] * X[0][2]) for a in range(3)]
@@ -249,6 +288,40 @@ def _p3p(K, X, uv):
             Rs[k] = np.array(R, dtype=np.float64)
             ts[k] = np.array(t, dtype=np.float64)
     return valid, Rs, ts
+
+
+def solution_checks(K, X, uv, l):
+    """what _p3p asks of a solution before it hands it on, at the normalised depths l (= depths / sqrt(A12 + A13 + A23)) and in _p3p's
+    operations -> (the three quadrics [3], |q1 x q2|^2 / |p1 x p2|^2 - 1: the squared areas of the two triangles)"""
+    fx, fy, cx, cy = (F(v) for v in K)
+    y = []
+    for i in range(3):
+        bx = (F(uv[i][0]) - cx) / fx
+        by = (F(uv[i][1]) - cy) / fy
+        n = np.sqrt(bx * bx + by * by + F(1.0))
+        y.append((bx / n, by / n, F(1.0) / n))
+    X = [[F(X[i][k]) for k in range(3)] for i in range(3)]
+
+    def d2(p, q):
+        dx, dy, dz = p[0] - q[0], p[1] - q[1], p[2] - q[2]
+        return dx * dx + dy * dy + dz * dz
+
+    def dot(p, q):
+        return p[0] * q[0] + p[1] * q[1] + p[2] * q[2]
+
+    A12, A13, A23 = d2(X[0], X[1]), d2(X[0], X[2]), d2(X[1], X[2])
+    S = A12 + A13 + A23
+    a12, a13, a23 = A12 / S, A13 / S, A23 / S
+    b12, b13, b23 = F(-2.0) * dot(y[0], y[1]), F(-2.0) * dot(y[0], y[2]), F(-2.0) * dot(y[1], y[2])
+    l1, l2, l3 = (F(v) for v in l)
+    res = np.array([l1 * l1 + l2 * l2 + b12 * (l1 * l2) - a12, l1 * l1 + l3 * l3 + b13 * (l1 * l3) - a13,
+                    l2 * l2 + l3 * l3 + b23 * (l2 * l3) - a23])
+    sqS = np.sqrt(S)
+    l1, l2, l3 = l1 * sqS, l2 * sqS, l3 * sqS
+    Y = [(l1 * y[0][0], l1 * y[0][1], l1 * y[0][2]), (l2 * y[1][0], l2 * y[1][1], l2 * y[1][2]), (l3 * y[2][0], l3 * y[2][1], l3 * y[2][2])]
+    p3 = _cross([X[1][k] - X[0][k] for k in range(3)], [X[2][k] - X[0][k] for k in range(3)])
+    q3 = _cross([Y[1][k] - Y[0][k] for k in range(3)], [Y[2][k] - Y[0][k] for k in range(3)])
+    return res, dot(q3, q3) / dot(p3, p3) - F(1.0)
 
 
 def reproj_sq(K, R, t, xyz, uv):

@@ -169,16 +169,20 @@ def make_pose_only_problem(M=200, seed=3, frac_gross=0.1, K=KITTI_K):
                 uv=np.ascontiguousarray(uv))
 
 
-def make_loop_pose_problem(M=200, seed=3, frac_gross=0.3, noise_px=0.0, K=KITTI_K):
+def make_loop_pose_problem(M=200, seed=3, frac_gross=0.3, noise_px=0.0, K=KITTI_K, gt_pose=None):
     """The matched pairs of LoopClosing::ComputeCorrectPose (loopclosing.cpp:147-243): M map points of the loop keyframe and the
     pixels of the current keyframe they were matched to.  Unlike make_pose_only_problem there is no initial pose: the ground-truth
     pose is a few metres and a few degrees from identity, and a share frac_gross of the pixels is a wrong match, displaced by
-    30-200 px.  Pixels are float32 values (cv::KeyPoint::pt, loopclosing.cpp:163).  inlier = the ground-truth mask."""
+    30-200 px.  Pixels are float32 values (cv::KeyPoint::pt, loopclosing.cpp:163).  inlier = the ground-truth mask.
+    gt_pose (qx qy qz qw tx ty tz, T_cw) replaces the drawn pose -- a loop closes anywhere in the world, at any heading -- and leaves every
+    other draw of the seed as it is."""
     rng = np.random.default_rng(seed)
     fx, fy, cx, cy = K
     w = rng.uniform(0.03, 0.08, 3) * rng.choice([-1.0, 1.0], 3)          # 3-8 degrees in all
     dq = small_rot_quat(w)
     gt = np.concatenate([dq / np.linalg.norm(dq), rng.uniform(1.0, 3.0, 3) * rng.choice([-1.0, 1.0], 3)])
+    if gt_pose is not None:
+        gt = np.array(gt_pose, dtype=np.float64)
     uv = np.stack([rng.uniform(20, KITTI_W - 20, M), rng.uniform(20, KITTI_H - 20, M)], 1)
     depth = rng.uniform(6, 45, M)
     pc = np.stack([(uv[:, 0] - cx) / fx * depth, (uv[:, 1] - cy) / fy * depth, depth], 1)
