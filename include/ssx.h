@@ -706,6 +706,50 @@ SSX_API ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_
                                            const int32_t* cur_class_id, int32_t cap, int32_t* pairs_out, int32_t* n_pairs,
                                            int32_t* min_distance);
 
+/* The per-keyframe step of LoopClosingThread (src/ssvio/loopclosing.cpp:39-70) as ONE call: ProcessNewKeyframe (:596-634:
+ * the left features replicated over the pyramid levels :607-619, ScreenAndComputeKPsParams + CalcDescriptors :622-629,
+ * dbow2_vocabulary_->transform :633), DetectLoop (:72-103) when more than min_db_size keyframes are stored (:48), and
+ * MatchFeatures (:105-145) against the winner.  Only the image and the features go up; only this result and the pairs
+ * come down (one synchronisation, two when a loop was found).  The keyframe's pyramid keypoints, descriptors, class ids
+ * and BowVector stay on the device as the PENDING keyframe of the database, for ssx_kfdb_add_pending. */
+typedef struct ssx_kfdb_step_result {
+  int32_t n_pyramid;     /* pyramid keypoints that survive ScreenAndComputeKPsParams = descriptors of the keyframe */
+  int32_t n_bow;         /* entries of its BowVector */
+  int32_t detect_ran;    /* stored keyframes > min_db_size (loopclosing.cpp:48) */
+  int32_t n_scored;      /* eligible stored keyframes, as ssx_kfdb_detect_loop; 0 when detection did not run */
+  int32_t found;         /* DetectLoop's verdict */
+  float   score;         /* the winner's float score (found only) */
+  int64_t loop_kf_id;    /* (found only) */
+  int32_t n_pairs;       /* set_valid_feature_matches_.size(); 0 when !found */
+  int32_t min_distance;  /* as ssx_kfdb_match_features; -1 when !found or no match exists */
+} ssx_kfdb_step_result;
+/* features[i] = features_left_[i]->kp_position_; pyramid keypoint i * pyramid_levels + level is a copy of it with
+ * octave = level, response = -1, class_id = i.  Every result is, bit for bit, what ssx_orb_describe_at on that list,
+ * ssx_voc_transform of its descriptors, ssx_kfdb_detect_loop(kf_id, that BowVector, min_id_gap, threshold) and
+ * ssx_kfdb_match_features(the winner, those descriptors and class ids) return.  pairs_out (pairs_cap x 2) as there:
+ * SSX_ERR_CAPACITY when pairs_cap is smaller than res->n_pairs, with the first pairs_cap pairs written and the keyframe
+ * still pending.  The "fewer than 10 pairs" verdict (:139) is the caller's.  SSX_ERR_UNSUPPORTED when n_features *
+ * pyramid_levels > 65535; SSX_ERR_INVALID_ARG when voc and db belong to different contexts or the winner was stored
+ * without descriptors.  An empty vocabulary, no features or no surviving keypoint: an empty BowVector, nothing found, and
+ * the keyframe can still be committed.  A call that fails otherwise leaves the stored keyframes as they were and nothing
+ * pending. */
+SSX_API ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary* voc, int64_t kf_id, const uint8_t* img,
+                                             int32_t stride, int32_t rows, int32_t cols, const ssx_orb_params* prm,
+                                             int32_t n_features, const ssx_keypoint* features, int32_t pyramid_levels,
+                                             int32_t min_db_size, int32_t min_id_gap, float threshold, int32_t pairs_cap,
+                                             int32_t* pairs_out, ssx_kfdb_step_result* res);
+/* AddToKeyframeDatabase (:646-649) for the keyframe of the last successful ssx_kfdb_process_keyframe: stored exactly as
+ * ssx_kfdb_add(kf_id, its BowVector, its descriptors, its class ids) would store it, device to device.  The same
+ * id-must-ascend rule; SSX_ERR_INVALID_ARG when nothing is pending (a keyframe is committed once).  ssx_kfdb_add and
+ * the growth of the database between the two calls leave the pending keyframe intact. */
+SSX_API ssx_status ssx_kfdb_add_pending(ssx_kf_database* db);
+/* Download the pending keyframe (ORBDescriptors_, pyramid_key_points_, bow2_vec_ of :622-633).  Every output is nullable;
+ * kps_out / desc_out / class_id_out hold kps_cap entries, ids_out / vals_out bow_cap (SSX_ERR_CAPACITY when smaller than
+ * the counts, which are written first).  SSX_ERR_INVALID_ARG when nothing is pending. */
+SSX_API ssx_status ssx_kfdb_pending(ssx_kf_database* db, int64_t* kf_id, int32_t kps_cap, ssx_keypoint* kps_out,
+                                    uint8_t* desc_out, int32_t* class_id_out, int32_t* n_pyramid, int32_t bow_cap,
+                                    int32_t* ids_out, double* vals_out, int32_t* n_bow);
+
 /* ------------------------------------------------------------------------------------------------
  * The pose correction of loop closing -- replaces LoopClosing::ComputeCorrectPose (src/ssvio/loopclosing.cpp:147-243)
  * with its cv::solvePnPRansac call (:205-206) and LoopClosing::OptimizeCurrentPose (:245-351).

@@ -260,6 +260,7 @@ class ORBVocabulary {
   {
     return ssx_bow_score_l1((int32_t)a.ids.size(), a.ids.data(), a.values.data(), (int32_t)b.ids.size(), b.ids.data(), b.values.data());
   }
+  ssx_vocabulary* get() const { return voc_; }               // null until loadFromTextFile has succeeded
 
  private:
   Context& ctx_;
@@ -322,6 +323,49 @@ class KeyframeDatabase {
     std::set<std::pair<int, int>> out;
     for (int32_t i = 0; i < n; ++i) out.emplace_hint(out.end(), pairs[2 * i], pairs[2 * i + 1]);
     return out;
+  }
+
+  // What one pass of LoopClosingThread's loop body decides (loopclosing.cpp:44-66) up to the "fewer than 10 pairs" verdict
+  struct KeyframeStep {
+    ssx_kfdb_step_result result;                             // counts, DetectLoop's verdict, loop_kf_id, score, min_distance
+    std::set<std::pair<int, int>> set_valid_feature_matches; // MatchFeatures' set; empty when no loop was detected
+  };
+
+  // ProcessNewKeyframe() (:596-634) + DetectLoop() when key_frame_database_.size() > min_db_size (:48) + MatchFeatures(), one call.  image =
+  // current_keyframe_->image_left_, features[i] = features_left_[i]->kp_position_.  Nothing of the keyframe comes back: its
+  // pyramid_key_points_, ORBDescriptors_ and bow2_vec_ stay on the device as the pending keyframe (Pending() downloads them).
+  KeyframeStep ProcessNewKeyframe(const ORBVocabulary& voc, unsigned long key_frame_id, const uint8_t* image, int stride, int rows, int cols,
+                                  const ORBextractor& extractor, const std::vector<ssx_keypoint>& features, float loop_threshold_heigher, int pyramid_levels = 8,
+                                  int min_db_size = 50, int min_id_gap = 20)
+  {
+    if (!voc.get()) throw std::invalid_argument("ProcessNewKeyframe: no vocabulary loaded");
+    KeyframeStep out{};
+    std::vector<int32_t> pairs(2 * std::max<size_t>(4096, features.size() * (size_t)pyramid_levels));
+    auto call = [&]() {
+      return ssx_kfdb_process_keyframe(db_, voc.get(), (int64_t)key_frame_id, image, stride, rows, cols, &extractor.params(), (int32_t)features.size(),
+                                       features.data(), pyramid_levels, min_db_size, min_id_gap, loop_threshold_heigher, (int32_t)(pairs.size() / 2),
+                                       pairs.data(), &out.result);
+    };
+    ssx_status st = call();
+    if (st == SSX_ERR_CAPACITY) {                            // a larger loop keyframe: the count is known now
+      pairs.resize((size_t)out.result.n_pairs * 2);
+      st = call();
+    }
+    ctx_.check(st);
+    for (int32_t i = 0; i < out.result.n_pairs; ++i) out.set_valid_feature_matches.emplace_hint(out.set_valid_feature_matches.end(), pairs[2 * i], pairs[2 * i + 1]);
+    return out;
+  }
+
+  // AddToKeyframeDatabase() (:646-649) for the keyframe ProcessNewKeyframe left on the device: no byte crosses PCIe
+  void AddToKeyframeDatabase() { ctx_.check(ssx_kfdb_add_pending(db_)); }
+
+  // current_keyframe_->pyramid_key_points_ / ORBDescriptors_ (n x 32) / bow2_vec_ of the pending keyframe, for a caller that keeps them
+  void Pending(std::vector<ssx_keypoint>& pyramid_key_points, std::vector<uint8_t>& descriptors, BowVector& bow)
+  {
+    int32_t n = 0, nb = 0;
+    ctx_.check(ssx_kfdb_pending(db_, nullptr, 0, nullptr, nullptr, nullptr, &n, 0, nullptr, nullptr, &nb));
+    pyramid_key_points.resize((size_t)n); descriptors.resize((size_t)n * 32); bow.ids.resize((size_t)nb); bow.values.resize((size_t)nb);
+    ctx_.check(ssx_kfdb_pending(db_, nullptr, n, pyramid_key_points.data(), descriptors.data(), nullptr, nullptr, nb, bow.ids.data(), bow.values.data(), nullptr));
   }
 
   int size() const

@@ -24,6 +24,20 @@
 // k_kfdb_pairs   one workgroup after k_bf_match: minimum distance, the screen dist <= max(2 min, 30), the kept pairs
 //                (current class_id, loop class_id) packed into order-preserving 64-bit keys, a bitonic sort (in LDS up
 //                to 4096 keys, else in a global scratch), and the unique keys written in order = the std::set.
+//
+// The per-keyframe step of the loop-closing thread (ssx_kfdb_process_keyframe: ProcessNewKeyframe, DetectLoop, MatchFeatures of
+// loopclosing.cpp:596-634, :72-103, :105-145) chains the describe kernels of orb.hip, k_voc_words of voc.hip and the two kernels above
+// with three of its own, and leaves the keyframe in the PENDING slot: kps | descriptors | class ids | BowVector ids | values, each at
+// the capacity n_features * pyramid_levels, the two counts known to the host.  ssx_kfdb_add_pending moves it into the arena.
+//
+// k_kf_compact   one workgroup: the kept pyramid keypoints, their descriptors and class ids in push_back order (orbextractor.cpp:893)
+//                by a prefix sum over the keep flags; the count to device memory.
+// k_kf_bow       one workgroup: the BowVector of the per-feature (word, weight) exactly as voc.hip builds it on the host.  The keys
+//                (word << 32) | feature are unique, so a bitonic sort orders every word's features; the head of a run adds its run's weights
+//                in feature order (TF_IDF, TF) or keeps the first (IDF, BINARY); the L1 norm is ONE chain over the words in ascending order,
+//                lane by lane over 64-entry chunks like the chain of k_kfdb_score.  Both sums are doubles whose value depends on the order
+//                of the additions, so neither is a tree.
+// k_kfdb_commit  the pending arrays into a blob of the arena and its row into the table.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -31,6 +45,8 @@
 
 #include "ctx.hpp"
 #include "orb_ws.hpp"
+#include "voc.hpp"
+#include "../../include/ssx_test_hooks.h"
 
 namespace {
 
@@ -60,9 +76,10 @@ __device__ __forceinline__ double readlane_f64(double v, int l)
 // scores[row] = L1Scoring::score(query, row) for the first n_rows keyframes; *best = max over rows of (float bits << 32) | ~row
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_kfdb_score(const char* arena, const KfRow* rows, int n_rows, const int32_t* q_ids, const double* q_vals, int nq,
-                                                    double* scores, unsigned long long* best)
+                                                    const int32_t* nq_dev, double* scores, unsigned long long* best)
 {
   extern __shared__ double smem[];                            // [nq] values, then [nq] ids
+  if (nq_dev) nq = *nq_dev;                                   // the query was built on the device: `nq` was its bound (it sized the LDS)
   const int32_t* qi = q_ids;
   const double* qv = q_vals;
   if (LDS) {
@@ -237,7 +254,136 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const int* idx, co
     sort_unique_pairs(gkeys, n_valid, npad, thr, idx, dist, n_loop, loop_class, cur_class, &s_fill, wave_sums, hdr, pairs, min_d);
 }
 
+
+// the kept keypoints of k_describe_at, their descriptors and class ids, in input order; *count = how many
+__global__ __launch_bounds__(kPairsThreads) void k_kf_compact(const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep, int n, ssx_keypoint* okps,
+                                                              uint8_t* odesc, int32_t* ocls, int32_t* count)
+{
+  __shared__ int wave_sums[kPairsThreads / 64];
+  const int tid = threadIdx.x;
+  const int seg = (n + kPairsThreads - 1) / kPairsThreads;    // a thread takes a contiguous piece
+  const int i0 = min(tid * seg, n), i1 = min(i0 + seg, n);
+  int mine = 0;
+  for (int i = i0; i < i1; ++i) mine += keep[i] ? 1 : 0;
+  int total = 0;
+  int pos = block_scan_excl(mine, wave_sums, &total);
+  for (int i = i0; i < i1; ++i) {
+    if (!keep[i]) continue;
+    const ssx_keypoint kp = kps[i];
+    const uint4* d4 = reinterpret_cast<const uint4*>(desc + (size_t)32 * i);
+    uint4* o4 = reinterpret_cast<uint4*>(odesc + (size_t)32 * pos);
+    okps[pos] = kp;
+    o4[0] = d4[0]; o4[1] = d4[1];
+    ocls[pos] = kp.class_id;
+    ++pos;
+  }
+  if (tid == 0) *count = total;
+}
+
+// The BowVector of n features from their (word, weight), as ssx_voc_transform assembles it (TemplatedVocabulary.h:1083-1124,
+// BowVector.cpp:62-84).  Called once with the LDS array and once with the global scratch, like sort_unique_pairs.
+__device__ __forceinline__ void bow_assemble(unsigned long long* keys, int n, int n_valid, int npad, const int32_t* word, const double* weight, bool add,
+                                             int* s_fill, int* wave_sums, double* s_norm, int32_t* ids, double* vals, int32_t* n_bow_out)
+{
+  const int tid = threadIdx.x;
+  for (int f = tid; f < n; f += kPairsThreads)
+    if (word[f] >= 0 && weight[f] > 0) keys[atomicAdd(s_fill, 1)] = ((unsigned long long)(unsigned)word[f] << 32) | (unsigned)f;   // any order: sorted next
+  for (int i = n_valid + tid; i < npad; i += kPairsThreads) keys[i] = ~0ull;
+  __syncthreads();
+  for (int k = 2; k <= npad; k <<= 1) {                       // bitonic sort of npad = 2^m keys; they are unique
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (npad >> 1); t += kPairsThreads) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const unsigned long long a = keys[i], b = keys[i | j];
+        if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[i | j] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  // keys [0, n_valid): ascending word, and inside a word ascending feature.  A thread takes a contiguous piece; the head of a run is an entry
+  const int seg = (n_valid + kPairsThreads - 1) / kPairsThreads;
+  const int i0 = min(tid * seg, n_valid), i1 = min(i0 + seg, n_valid);
+  int heads = 0;
+  for (int i = i0; i < i1; ++i) heads += (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1 : 0;
+  int n_bow = 0;
+  int pos = block_scan_excl(heads, wave_sums, &n_bow);
+  for (int i = i0; i < i1; ++i) {
+    const unsigned long long key = keys[i];
+    const unsigned w = (unsigned)(key >> 32);
+    if (i > 0 && (unsigned)(keys[i - 1] >> 32) == w) continue;
+    double v = weight[(unsigned)key];                         // the first occurrence inserts its weight ...
+    if (add)                                                  // ... and TF_IDF / TF add the later ones in feature order: one chain per word
+      for (int j = i + 1; j < n_valid && (unsigned)(keys[j] >> 32) == w; ++j) v += weight[(unsigned)keys[j]];
+    ids[pos] = (int32_t)w;
+    vals[pos] = v;
+    ++pos;
+  }
+  __syncthreads();
+  if (tid < 64) {                                             // the L1 norm: sum of fabs in ascending word order, ONE chain
+    double s = 0.0;
+    for (int base = 0; base < n_bow; base += 64) {
+      const int k = base + tid;
+      const double v = k < n_bow ? fabs(vals[k]) : 0.0;
+      const int cnt = min(64, n_bow - base);
+      for (int l = 0; l < cnt; ++l) s += readlane_f64(v, l);
+    }
+    if (tid == 0) *s_norm = s;
+  }
+  __syncthreads();
+  const double norm = *s_norm;
+  if (norm > 0.0)
+    for (int k = tid; k < n_bow; k += kPairsThreads) vals[k] /= norm;
+  if (tid == 0) *n_bow_out = n_bow;
+}
+
+// ids / vals / *n_bow = the BowVector of the first *n_dev features; *best_zero = 0 for the k_kfdb_score that follows
+__global__ __launch_bounds__(kPairsThreads) void k_kf_bow(const int32_t* word, const double* weight, const int32_t* n_dev, int weighting, unsigned long long* gkeys,
+                                                          int32_t* ids, double* vals, int32_t* n_bow, unsigned long long* best_zero)
+{
+  __shared__ unsigned long long skeys[kSortLds];
+  __shared__ int wave_sums[kPairsThreads / 64];
+  __shared__ int s_fill;
+  __shared__ double s_norm;
+  const int tid = threadIdx.x;
+  const int n = *n_dev;
+  if (tid == 0) { s_fill = 0; s_norm = 0.0; if (best_zero) *best_zero = 0; }
+  int mine = 0;
+  for (int f = tid; f < n; f += kPairsThreads) mine += (word[f] >= 0 && weight[f] > 0) ? 1 : 0;   // stopped words (weight 0) are skipped
+  int n_valid = 0;
+  block_scan_excl(mine, wave_sums, &n_valid);                 // (its barriers publish s_fill)
+  int npad = 1;
+  while (npad < n_valid) npad <<= 1;
+  const bool add = weighting == 0 || weighting == 1;          // TF_IDF, TF
+  if (npad <= kSortLds)
+    bow_assemble(skeys, n, n_valid, npad, word, weight, add, &s_fill, wave_sums, &s_norm, ids, vals, n_bow);
+  else                                                        // gkeys holds the next power of two of the feature bound
+    bow_assemble(gkeys, n, n_valid, npad, word, weight, add, &s_fill, wave_sums, &s_norm, ids, vals, n_bow);
+}
+
+// the pending keyframe into its blob (layout at the top of the file, padding zeroed) and its row into the table
+__global__ __launch_bounds__(256) void k_kfdb_commit(char* blob, const int32_t* ids, const double* vals, const int32_t* cls, const uint8_t* desc, int n_bow,
+                                                     int n_desc, KfRow* row_out, KfRow row)
+{
+  const size_t o_v = blob_vals(n_bow), o_c = blob_class(n_bow), o_d = blob_desc(n_bow, n_desc), words = blob_bytes(n_bow, n_desc) / 4;
+  const uint32_t* v32 = reinterpret_cast<const uint32_t*>(vals);
+  const uint32_t* d32 = reinterpret_cast<const uint32_t*>(desc);
+  uint32_t* out = reinterpret_cast<uint32_t*>(blob);
+  for (size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x; w < words; w += (size_t)gridDim.x * blockDim.x) {
+    const size_t off = w * 4;
+    uint32_t x = 0;
+    if (off < (size_t)n_bow * 4) x = (uint32_t)ids[w];
+    else if (off >= o_v && off < o_c) x = v32[(off - o_v) / 4];
+    else if (off >= o_c && off < o_c + (size_t)n_desc * 4) x = (uint32_t)cls[(off - o_c) / 4];
+    else if (off >= o_d && off < o_d + (size_t)n_desc * 32) x = d32[(off - o_d) / 4];
+    out[w] = x;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *row_out = row;
+}
+
 }  // namespace
+
+// what the last ssx_kfdb_process_keyframe issued (ssx_kfdb_debug_last_step)
+struct KfStepStats { int32_t launches = 0, syncs = 0; int64_t bytes_up = 0, bytes_down = 0; };
 
 struct ssx_kf_database {
   ssx_ctx* ctx = nullptr;
@@ -247,9 +393,22 @@ struct ssx_kf_database {
   HostBuf stage;
   size_t used = 0;                // bytes of the arena in use
   int64_t n_bow = 0, n_desc = 0;
+  // the pending keyframe: arrays of capacity `cap` entries each in `pend` (pend_arrays), the counts known to the host
+  DevBuf pend;
+  struct Pending { bool valid = false; int64_t kf_id = 0; int cap = 0, n_pyr = 0, n_bow = 0; } pending;
+  KfStepStats last;
 };
 
 namespace {
+
+struct PendArrays { ssx_keypoint* kps; uint8_t* desc; int32_t* cls; int32_t* ids; double* vals; };
+// the pending slot for `cap` pyramid keypoints; base null: the bytes only
+size_t pend_arrays(char* base, int cap, PendArrays& a)
+{
+  return ssxorb::carve(base, [&](auto&& f) {
+    f(a.kps, sizeof(ssx_keypoint) * (size_t)cap); f(a.desc, (size_t)32 * cap); f(a.cls, (size_t)4 * cap); f(a.ids, (size_t)4 * cap); f(a.vals, (size_t)8 * cap);
+  });
+}
 
 // DevBuf::reserve drops the contents: grow to at least `need` bytes keeping the first `keep`
 hipError_t grow_keep(ssx_ctx* ctx, DevBuf& b, size_t keep, size_t need)
@@ -266,6 +425,70 @@ hipError_t grow_keep(ssx_ctx* ctx, DevBuf& b, size_t keep, size_t need)
   if (b.p) (void)hipFree(b.p);
   b.p = np; b.cap = want;
   return hipSuccess;
+}
+
+// k_kfdb_score over the first n_elig stored keyframes.  The query lies on the device; nq is its length, or with nq_dev its bound (the length
+// is then read there): the bound sizes the LDS stage, and above kQueryLds the query is searched in global memory.
+void launch_score(ssx_kf_database* db, int n_elig, const int32_t* q_ids, const double* q_vals, int nq, const int32_t* nq_dev, double* scores,
+                  unsigned long long* best)
+{
+  ssx_ctx* ctx = db->ctx;
+  const int blocks = std::min((n_elig + 3) / 4, 1024);   // four workgroups per CU; a wavefront takes every 4096th row
+  const char* arena = db->arena.as<char>();
+  const KfRow* rows = db->table.as<KfRow>();
+  if (nq <= kQueryLds)
+    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score<true>, dim3(blocks), dim3(256), (size_t)nq * 12, ctx->stream, arena, rows, n_elig,
+                                                     q_ids, q_vals, nq, nq_dev, scores, best));
+  else
+    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score<false>, dim3(blocks), dim3(256), 0, ctx->stream, arena, rows, n_elig, q_ids, q_vals,
+                                                     nq, nq_dev, scores, best));
+}
+
+// DetectLoop's verdict from the key k_kfdb_score left: no score above 0 keeps max_score 0 (loopclosing.cpp:74,85); below the threshold: none (:93)
+bool winner_of(unsigned long long key, float threshold, uint32_t* row, float* score)
+{
+  if (key == 0) return false;
+  const uint32_t bits = (uint32_t)(key >> 32);
+  float f = 0.f;
+  memcpy(&f, &bits, 4);
+  if (f < threshold) return false;
+  *row = ~(uint32_t)key; *score = f;
+  return true;
+}
+
+// the device scratch of MatchFeatures against a stored keyframe of nl descriptors
+struct MatchScratch { int* idx; int* dist; unsigned long long* keys; };
+template <class F> void match_scratch(F&& f, MatchScratch& m, int nl)
+{
+  size_t npad = 1;
+  while (npad < (size_t)nl) npad *= 2;
+  f(m.idx, (size_t)nl * 4); f(m.dist, (size_t)nl * 4); f(m.keys, nl > kSortLds ? npad * 8 : 0);
+}
+
+// cv::BFMatcher::match(loop, current) + the screen and the set: query = the resident loop descriptors of `row`, train = the n_cur current ones
+// on the device; hdr (pair count, minimum distance) and the pairs go where the caller says
+hipError_t launch_match(ssx_kf_database* db, const KfRow& row, const uint8_t* cur_desc, int n_cur, const int32_t* cur_class, const MatchScratch& m, int32_t* hdr,
+                        int32_t* pairs)
+{
+  ssx_ctx* ctx = db->ctx;
+  const int nl = row.n_desc;
+  const char* blob = db->arena.as<char>() + row.off;
+  SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match(ctx->stream, (const uint8_t*)(blob + blob_desc(row.n_bow, nl)), nl, cur_desc, n_cur, m.idx, m.dist));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs, dim3(1), dim3(kPairsThreads), 0, ctx->stream, m.idx, m.dist, nl,
+                                                   (const int32_t*)(blob + blob_class(row.n_bow)), cur_class, m.keys, hdr, pairs));
+  return hipGetLastError();
+}
+
+// the id-must-ascend rule of AddToKeyframeDatabase's two entry points (the std::map of the reference is walked as a prefix, :79)
+ssx_status check_next_id(ssx_kf_database* db, const char* who, int64_t kf_id)
+{
+  if (!db->ids.empty() && kf_id <= db->ids.back()) {
+    db->ctx->set_error("%s: keyframe id %lld after %lld (ids must ascend)", who, (long long)kf_id, (long long)db->ids.back());
+    return SSX_ERR_INVALID_ARG;
+  }
+  return SSX_OK;
 }
 
 }  // namespace
@@ -297,7 +520,7 @@ ssx_status ssx_kfdb_create(ssx_ctx* ctx, int32_t keyframes_hint, ssx_kf_database
 void ssx_kfdb_destroy(ssx_kf_database* db)
 {
   if (!db) return;
-  db->arena.release(); db->table.release(); db->io.release(); db->stage.release();
+  db->arena.release(); db->table.release(); db->io.release(); db->pend.release(); db->stage.release();
   delete db;
 }
 
@@ -315,10 +538,7 @@ ssx_status ssx_kfdb_add(ssx_kf_database* db, int64_t kf_id, int32_t n_bow, const
 {
   if (!db || n_bow < 0 || n_desc < 0 || (n_bow > 0 && (!ids || !vals)) || (n_desc > 0 && (!desc || !class_id))) return SSX_ERR_INVALID_ARG;
   ssx_ctx* ctx = db->ctx;
-  if (!db->ids.empty() && kf_id <= db->ids.back()) {
-    ctx->set_error("ssx_kfdb_add: keyframe id %lld after %lld (ids must ascend)", (long long)kf_id, (long long)db->ids.back());
-    return SSX_ERR_INVALID_ARG;
-  }
+  if (ssx_status st = check_next_id(db, "ssx_kfdb_add", kf_id)) return st;
   for (int32_t i = 1; i < n_bow; ++i)
     if (ids[i] <= ids[i - 1]) { ctx->set_error("ssx_kfdb_add: word ids must ascend (entry %d)", i); return SSX_ERR_INVALID_ARG; }
   if (db->ids.size() >= (size_t)0x7fffffff) { ctx->set_error("ssx_kfdb_add: the database is full"); return SSX_ERR_CAPACITY; }
@@ -373,19 +593,7 @@ ssx_status ssx_kfdb_detect_loop(ssx_kf_database* db, int64_t query_kf_id, int32_
   memcpy(hs + o_i, ids, (size_t)n_bow * 4);
   memset(hs + o_best, 0, 8);
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const int blocks = std::min((n_elig + 3) / 4, 1024);   // four workgroups per CU; a wavefront takes every 4096th row
-  const char* arena = db->arena.as<char>();
-  const KfRow* rows = db->table.as<KfRow>();
-  const int32_t* q_ids = (const int32_t*)(base + o_i);
-  const double* q_vals = (const double*)(base + o_v);
-  double* scores = (double*)(base + o_s);
-  unsigned long long* best = (unsigned long long*)(base + o_best);
-  if (n_bow <= kQueryLds)
-    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score<true>, dim3(blocks), dim3(256), (size_t)n_bow * 12, ctx->stream, arena, rows, n_elig,
-                                                     q_ids, q_vals, n_bow, scores, best));
-  else
-    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score<false>, dim3(blocks), dim3(256), 0, ctx->stream, arena, rows, n_elig, q_ids, q_vals,
-                                                     n_bow, scores, best));
+  launch_score(db, n_elig, (const int32_t*)(base + o_i), (const double*)(base + o_v), n_bow, nullptr, (double*)(base + o_s), (unsigned long long*)(base + o_best));
   SSX_HIP_TRY(ctx, hipGetLastError());
   // the winner's key and, when asked for, the scores right behind it: one copy, one synchronisation
   SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_best, base + o_best, scores_out ? lay.off - o_best : 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -393,11 +601,9 @@ ssx_status ssx_kfdb_detect_loop(ssx_kf_database* db, int64_t query_kf_id, int32_
   if (scores_out) memcpy(scores_out, hs + o_s, (size_t)n_elig * 8);
   unsigned long long key = 0;
   memcpy(&key, hs + o_best, 8);
-  if (key == 0) return SSX_OK;                                // no score above 0: max_score stays 0 (loopclosing.cpp:74,85)
-  const uint32_t bits = (uint32_t)(key >> 32), row = ~(uint32_t)key;
+  uint32_t row = 0;
   float f = 0.f;
-  memcpy(&f, &bits, 4);
-  if (f < threshold) return SSX_OK;                           // loopclosing.cpp:93
+  if (!winner_of(key, threshold, &row, &f)) return SSX_OK;
   *found = 1;
   if (best_kf_id) *best_kf_id = db->ids[row];
   if (best_score) *best_score = f;
@@ -419,30 +625,24 @@ ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int3
   const int nl = row.n_desc;
   if (nl == 0 || n_cur == 0) return SSX_OK;                   // no match exists: no pairs (the reference dereferences end() here)
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  size_t npad = 1;
-  while (npad < (size_t)nl) npad *= 2;
   const int n_down = std::min(nl, cap);
   Layout lay;
   const size_t o_d = lay.take((size_t)n_cur * 32), o_c = lay.take((size_t)n_cur * 4);
   const size_t in_bytes = lay.off;
-  const size_t o_idx = lay.take((size_t)nl * 4), o_dist = lay.take((size_t)nl * 4), o_keys = lay.take(nl > kSortLds ? npad * 8 : 0);
+  MatchScratch m{};
+  size_t o_m[3]; int k = 0;
+  match_scratch([&](auto*&, size_t bytes) { o_m[k++] = lay.take(bytes); }, m, nl);
   const size_t o_hdr = lay.take(8), o_pairs = lay.take((size_t)nl * 8);
   SSX_HIP_TRY(ctx, db->io.reserve(lay.off));
   SSX_HIP_TRY(ctx, db->stage.reserve(lay.off));
   char* hs = db->stage.as<char>();
   char* base = db->io.as<char>();
+  k = 0;
+  match_scratch([&](auto*& ptr, size_t) { ssxorb::wire(ptr, base, o_m[k++]); }, m, nl);
   memcpy(hs + o_d, cur_desc, (size_t)n_cur * 32);
   memcpy(hs + o_c, cur_class_id, (size_t)n_cur * 4);
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const char* blob = db->arena.as<char>() + row.off;
-  // cv::BFMatcher::match(loop, current): query = the resident loop descriptors, train = the current ones
-  SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match(ctx->stream, (const uint8_t*)(blob + blob_desc(row.n_bow, nl)), nl, (const uint8_t*)(base + o_d), n_cur,
-                                                        (int*)(base + o_idx), (int*)(base + o_dist)));
-  SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs, dim3(1), dim3(kPairsThreads), 0, ctx->stream, (const int*)(base + o_idx), (const int*)(base + o_dist),
-                                                   nl, (const int32_t*)(blob + blob_class(row.n_bow)), (const int32_t*)(base + o_c),
-                                                   (unsigned long long*)(base + o_keys), (int32_t*)(base + o_hdr), (int32_t*)(base + o_pairs)));
-  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, launch_match(db, row, (const uint8_t*)(base + o_d), n_cur, (const int32_t*)(base + o_c), m, (int32_t*)(base + o_hdr), (int32_t*)(base + o_pairs)));
   SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_hdr, base + o_hdr, (o_pairs - o_hdr) + (size_t)n_down * 8, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   int32_t hdr[2];
@@ -453,5 +653,238 @@ ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int3
   if (hdr[0] > cap) { ctx->set_error("ssx_kfdb_match_features: %d pairs but capacity %d", hdr[0], cap); return SSX_ERR_CAPACITY; }
   return SSX_OK;
 }
+
+}  // extern "C"
+
+// ---- the per-keyframe step ----------------------------------------------------------------------------------------------------------
+namespace {
+
+struct StepHdr { int32_t n_pyr, n_bow; unsigned long long best; };   // what the first synchronisation brings down
+
+// steps 3-4 on descriptors that lie on the device: words, then the BowVector; scratch for `bound` features
+struct BowScratch { int32_t* word; double* weight; unsigned long long* keys; };
+template <class F> void bow_scratch(F&& f, BowScratch& b, int bound)
+{
+  size_t npad = 1;
+  while (npad < (size_t)bound) npad *= 2;
+  f(b.word, (size_t)bound * 4); f(b.weight, (size_t)bound * 8); f(b.keys, bound > kSortLds ? npad * 8 : 0);
+}
+hipError_t launch_bow(ssx_ctx* ctx, const ssx_vocabulary* voc, const uint8_t* desc, int bound, const int32_t* n_dev, const BowScratch& b, int32_t* ids,
+                      double* vals, int32_t* n_bow, unsigned long long* best_zero)
+{
+  SSX_PROF(ctx, KID_LOOP_WORDS, ssxvoc::launch_words(ctx->stream, voc, desc, bound, n_dev, b.word, b.weight));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  SSX_PROF(ctx, KID_LOOP_BOW, hipLaunchKernelGGL(k_kf_bow, dim3(1), dim3(kPairsThreads), 0, ctx->stream, b.word, b.weight, n_dev, voc->weighting, b.keys, ids, vals,
+                                                 n_bow, best_zero));
+  return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary* voc, int64_t kf_id, const uint8_t* img, int32_t stride, int32_t rows, int32_t cols,
+                                     const ssx_orb_params* prm, int32_t n_features, const ssx_keypoint* features, int32_t pyramid_levels, int32_t min_db_size,
+                                     int32_t min_id_gap, float threshold, int32_t pairs_cap, int32_t* pairs_out, ssx_kfdb_step_result* res)
+{
+  if (!db) return SSX_ERR_INVALID_ARG;
+  db->pending.valid = false;                                  // a call that fails leaves nothing pending
+  db->last = KfStepStats{};
+  if (!voc || !res || !prm || !img || rows <= 0 || cols <= 0 || stride < cols || n_features < 0 || (n_features > 0 && !features) || pyramid_levels < 1 ||
+      pyramid_levels > ssxorb::MAX_LEVELS || pairs_cap < 0 || (pairs_cap > 0 && !pairs_out))
+    return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = db->ctx;
+  if (voc->ctx != ctx) { ctx->set_error("ssx_kfdb_process_keyframe: the vocabulary belongs to another context"); return SSX_ERR_INVALID_ARG; }
+  if ((int64_t)n_features * pyramid_levels > 65535) {
+    ctx->set_error("ssx_kfdb_process_keyframe: %d features x %d levels: more than 65535 pyramid keypoints", n_features, pyramid_levels);
+    return SSX_ERR_UNSUPPORTED;
+  }
+  *res = ssx_kfdb_step_result{};
+  res->min_distance = -1;
+  const int N = n_features * pyramid_levels;
+  // DetectLoop runs when enough keyframes are stored (loopclosing.cpp:48) and scores the prefix that is old enough (:79)
+  const bool detect = (int64_t)db->ids.size() > (int64_t)min_db_size;
+  const int n_elig = detect ? (int)(std::upper_bound(db->ids.begin(), db->ids.end(), kf_id - (int64_t)min_id_gap) - db->ids.begin()) : 0;
+  res->detect_ran = detect ? 1 : 0;
+  res->n_scored = n_elig;
+  KfStepStats st{};
+  StepHdr hdr{0, 0, 0};
+  PendArrays pa{};
+  if (N > 0) {
+    SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ssxorb::Described d;
+    ssx_status s = ssxorb::describe_enqueue(ctx, img, stride, rows, cols, *prm, features, n_features, pyramid_levels, &d);
+    if (s != SSX_OK) return s;
+    st.launches += d.launches; st.syncs += d.syncs; st.bytes_up += (int64_t)d.bytes_up;
+    SSX_HIP_TRY(ctx, db->pend.reserve(pend_arrays(nullptr, N, pa)));
+    pend_arrays(db->pend.as<char>(), N, pa);
+    StepHdr* dh;
+    BowScratch b{};
+    double* scores;
+    auto scratch = [&](auto&& f) { f(dh, sizeof(StepHdr)); bow_scratch(f, b, N); f(scores, (size_t)n_elig * 8); };
+    SSX_HIP_TRY(ctx, db->io.reserve(ssxorb::carve(nullptr, scratch)));
+    SSX_HIP_TRY(ctx, db->stage.reserve(256));
+    ssxorb::carve(db->io.as<char>(), scratch);
+    SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact, dim3(1), dim3(kPairsThreads), 0, ctx->stream, d.kps, d.desc, d.keep, N, pa.kps, pa.desc, pa.cls,
+                                                       &dh->n_pyr));
+    SSX_HIP_TRY(ctx, hipGetLastError());
+    SSX_HIP_TRY(ctx, launch_bow(ctx, voc, pa.desc, N, &dh->n_pyr, b, pa.ids, pa.vals, &dh->n_bow, &dh->best));
+    st.launches += 3;
+    if (n_elig > 0) {                                         // the query where k_kf_bow left it, its length read on the device
+      launch_score(db, n_elig, pa.ids, pa.vals, N, &dh->n_bow, scores, &dh->best);
+      SSX_HIP_TRY(ctx, hipGetLastError());
+      ++st.launches;
+    }
+    SSX_HIP_TRY(ctx, hipMemcpyAsync(db->stage.p, dh, sizeof(StepHdr), hipMemcpyDeviceToHost, ctx->stream));
+    SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ++st.syncs; st.bytes_down += (int64_t)sizeof(StepHdr);
+    memcpy(&hdr, db->stage.p, sizeof(StepHdr));
+  }
+  res->n_pyramid = hdr.n_pyr; res->n_bow = hdr.n_bow;
+  uint32_t row_i = 0;
+  float f = 0.f;
+  int n_pairs = 0;
+  if (n_elig > 0 && winner_of(hdr.best, threshold, &row_i, &f)) {
+    res->found = 1; res->score = f; res->loop_kf_id = db->ids[row_i];
+    const KfRow row = db->rows[row_i];
+    if (row.n_desc < 0) {
+      ctx->set_error("ssx_kfdb_process_keyframe: the loop keyframe %lld was added without descriptors", (long long)db->ids[row_i]);
+      return SSX_ERR_INVALID_ARG;
+    }
+    const int nl = row.n_desc;
+    if (nl > 0 && hdr.n_pyr > 0) {                            // else no match exists: no pairs
+      // MatchFeatures: the pending descriptors and class ids are the current side.  The pair count and the pairs are written straight into
+      // the pinned block (mapped into the device's address space): what crosses is the 8-byte header and 8 bytes per pair
+      MatchScratch m{};
+      SSX_HIP_TRY(ctx, db->io.reserve(ssxorb::carve(nullptr, [&](auto&& g) { match_scratch(g, m, nl); })));
+      ssxorb::carve(db->io.as<char>(), [&](auto&& g) { match_scratch(g, m, nl); });
+      SSX_HIP_TRY(ctx, db->stage.reserve(256 + (size_t)nl * 8));
+      int32_t* hm = db->stage.as<int32_t>();
+      hm[0] = 0; hm[1] = -1;
+      void* dm = nullptr;
+      SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dm, hm, 0));
+      SSX_HIP_TRY(ctx, launch_match(db, row, pa.desc, hdr.n_pyr, pa.cls, m, (int32_t*)dm, (int32_t*)((char*)dm + 256)));
+      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+      st.launches += 2; ++st.syncs;
+      n_pairs = hm[0];
+      res->min_distance = hm[1];
+      st.bytes_down += 8 + (int64_t)n_pairs * 8;
+      if (pairs_cap > 0) memcpy(pairs_out, (const char*)hm + 256, (size_t)std::min(n_pairs, pairs_cap) * 8);
+    }
+  }
+  res->n_pairs = n_pairs;
+  // every synchronisation has succeeded: the keyframe is pending
+  db->pending.valid = true; db->pending.kf_id = kf_id; db->pending.cap = N; db->pending.n_pyr = hdr.n_pyr; db->pending.n_bow = hdr.n_bow;
+  db->last = st;
+  if (n_pairs > pairs_cap) { ctx->set_error("ssx_kfdb_process_keyframe: %d pairs but capacity %d", n_pairs, pairs_cap); return SSX_ERR_CAPACITY; }
+  return SSX_OK;
+}
+
+ssx_status ssx_kfdb_add_pending(ssx_kf_database* db)
+{
+  if (!db) return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = db->ctx;
+  if (!db->pending.valid) { ctx->set_error("ssx_kfdb_add_pending: no keyframe is pending"); return SSX_ERR_INVALID_ARG; }
+  const ssx_kf_database::Pending pe = db->pending;
+  if (ssx_status st = check_next_id(db, "ssx_kfdb_add_pending", pe.kf_id)) return st;
+  if (db->ids.size() >= (size_t)0x7fffffff) { ctx->set_error("ssx_kfdb_add_pending: the database is full"); return SSX_ERR_CAPACITY; }
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = blob_bytes(pe.n_bow, pe.n_pyr), n = db->ids.size();
+  SSX_HIP_TRY(ctx, grow_keep(ctx, db->arena, db->used, db->used + bytes));
+  SSX_HIP_TRY(ctx, grow_keep(ctx, db->table, n * sizeof(KfRow), (n + 1) * sizeof(KfRow)));
+  PendArrays pa{};
+  pend_arrays(db->pend.as<char>(), pe.cap, pa);              // (cap == 0: an empty keyframe, nothing is read)
+  const KfRow row{(int64_t)db->used, pe.n_bow, pe.n_pyr};
+  const int blocks = (int)std::min<size_t>(std::max<size_t>((bytes / 4 + 255) / 256, 1), 1024);
+  SSX_PROF(ctx, KID_LOOP_COMMIT, hipLaunchKernelGGL(k_kfdb_commit, dim3(blocks), dim3(256), 0, ctx->stream, db->arena.as<char>() + db->used, pa.ids, pa.vals, pa.cls,
+                                                    pa.desc, pe.n_bow, pe.n_pyr, db->table.as<KfRow>() + n, row));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  db->ids.push_back(pe.kf_id); db->rows.push_back(row);
+  db->used += bytes; db->n_bow += pe.n_bow; db->n_desc += pe.n_pyr;
+  db->pending.valid = false;                                  // a keyframe is committed once
+  return SSX_OK;
+}
+
+ssx_status ssx_kfdb_pending(ssx_kf_database* db, int64_t* kf_id, int32_t kps_cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* class_id_out,
+                            int32_t* n_pyramid, int32_t bow_cap, int32_t* ids_out, double* vals_out, int32_t* n_bow)
+{
+  if (!db || kps_cap < 0 || bow_cap < 0) return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = db->ctx;
+  if (!db->pending.valid) { ctx->set_error("ssx_kfdb_pending: no keyframe is pending"); return SSX_ERR_INVALID_ARG; }
+  const ssx_kf_database::Pending pe = db->pending;
+  if (kf_id) *kf_id = pe.kf_id;
+  if (n_pyramid) *n_pyramid = pe.n_pyr;
+  if (n_bow) *n_bow = pe.n_bow;
+  const bool want_kps = kps_out || desc_out || class_id_out, want_bow = ids_out || vals_out;
+  if ((want_kps && kps_cap < pe.n_pyr) || (want_bow && bow_cap < pe.n_bow)) {
+    ctx->set_error("ssx_kfdb_pending: %d keypoints and %d words but capacities %d and %d", pe.n_pyr, pe.n_bow, kps_cap, bow_cap);
+    return SSX_ERR_CAPACITY;
+  }
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PendArrays pa{};
+  pend_arrays(db->pend.as<char>(), pe.cap, pa);
+  hipStream_t s = ctx->stream;
+  if (pe.n_pyr > 0) {
+    if (kps_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(kps_out, pa.kps, sizeof(ssx_keypoint) * (size_t)pe.n_pyr, hipMemcpyDeviceToHost, s));
+    if (desc_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(desc_out, pa.desc, (size_t)32 * pe.n_pyr, hipMemcpyDeviceToHost, s));
+    if (class_id_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(class_id_out, pa.cls, (size_t)4 * pe.n_pyr, hipMemcpyDeviceToHost, s));
+  }
+  if (pe.n_bow > 0) {
+    if (ids_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(ids_out, pa.ids, (size_t)4 * pe.n_bow, hipMemcpyDeviceToHost, s));
+    if (vals_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(vals_out, pa.vals, (size_t)8 * pe.n_bow, hipMemcpyDeviceToHost, s));
+  }
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  return SSX_OK;
+}
+
+#ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h
+ssx_status ssx_kfdb_debug_last_step(const ssx_kf_database* db, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
+{
+  if (!db) return SSX_ERR_INVALID_ARG;
+  if (launches) *launches = db->last.launches;
+  if (synchronisations) *synchronisations = db->last.syncs;
+  if (bytes_up) *bytes_up = db->last.bytes_up;
+  if (bytes_down) *bytes_down = db->last.bytes_down;
+  return SSX_OK;
+}
+
+ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t cap, int32_t* ids_out, double* vals_out, int32_t* n_entries)
+{
+  if (!voc || n < 0 || (n > 0 && !desc) || cap < 0 || (cap > 0 && (!ids_out || !vals_out)) || !n_entries) return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = voc->ctx;
+  *n_entries = 0;
+  if (n == 0) return SSX_OK;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t* feat; int32_t* cnt; int32_t* ids; double* vals;
+  BowScratch b{};
+  // one block, on the device and (pinned) on the host: [descriptors | count in, count out] go up, [ids | values] and the counts come back
+  auto bufs = [&](auto&& f) { f(feat, (size_t)32 * n); f(cnt, 8); bow_scratch(f, b, n); f(ids, (size_t)4 * n); f(vals, (size_t)8 * n); };
+  const size_t total = ssxorb::carve(nullptr, bufs);
+  SSX_HIP_TRY(ctx, voc->io.reserve(total));
+  SSX_HIP_TRY(ctx, voc->stage.reserve(total));
+  char* base = voc->io.as<char>();
+  ssxorb::carve(base, bufs);
+  const size_t o_in = (size_t)((char*)b.word - base), o_out = (size_t)((char*)ids - base);
+  char* hs = voc->stage.as<char>();
+  memcpy(hs, desc, (size_t)32 * n);
+  int32_t hc[2] = {n, 0};
+  memcpy(hs + ((char*)cnt - base), hc, 8);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, o_in, hipMemcpyHostToDevice, ctx->stream));
+  SSX_HIP_TRY(ctx, launch_bow(ctx, voc, feat, n, cnt, b, ids, vals, cnt + 1, nullptr));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + ((char*)cnt - base), cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_out, base + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(hc, hs + ((char*)cnt - base), 8);
+  *n_entries = hc[1];
+  if (hc[1] > cap) { ctx->set_error("ssx_kfdb_debug_bow: %d words but capacity %d", hc[1], cap); return SSX_ERR_CAPACITY; }
+  if (hc[1] > 0) {
+    memcpy(ids_out, hs + ((char*)ids - base), (size_t)4 * hc[1]);
+    memcpy(vals_out, hs + ((char*)vals - base), (size_t)8 * hc[1]);
+  }
+  return SSX_OK;
+}
+#endif
 
 }  // extern "C"

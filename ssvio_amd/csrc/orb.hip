@@ -1353,8 +1353,9 @@ ssx_status plan(ssx_ctx* ctx, int rows, int cols, int I, const ssx_orb_params& p
 }
 
 // pyramid (ComputePyramid, orbextractor.cpp:993-1027): level l from level l-1, images (and masks) of the batch
-static void launch_pyramid(ssx_ctx* ctx, const OrbDev& d, hipStream_t s, int images)
+static int launch_pyramid(ssx_ctx* ctx, const OrbDev& d, hipStream_t s, int images)
 {
+  int launches = 0;
   for (int l = 1; l < d.nlevels; ++l) {
     if (d.lvl_cols[l] <= 0 || d.lvl_rows[l] <= 0) break;     // a tiny image runs out of pixels before it runs out of levels: nothing there
     const int loops = images > 8 ? RS_LOOP : 1;
@@ -1364,8 +1365,10 @@ static void launch_pyramid(ssx_ctx* ctx, const OrbDev& d, hipStream_t s, int ima
       uint8_t* pyr = m ? d.maskpyr : d.pyr;
       SSX_PROF(ctx, KID_ORB_RESIZE, hipLaunchKernelGGL(kern, grid, dim3(64, 4), 0, s, pyr + d.lvl_off[l - 1], pyr + d.lvl_off[l], d.pyr_bytes,
                          d.lvl_pitch[l - 1], d.lvl_rows[l], d.lvl_cols[l], d.lvl_pitch[l], d.rs_xtab + d.rs_xoff[l], d.rs_ytab + d.rs_yoff[l], loops));
+      ++launches;
     }
   }
+  return launches;
 }
 
 ssx_status stage_level0(ssx_ctx* ctx, const uint8_t* imgs_dev, int stride, size_t img_bytes, const uint8_t* masks_dev, int mask_stride, size_t mask_bytes)
@@ -1492,6 +1495,59 @@ ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, 
       SSX_HIP_TRY(ctx, hipMemcpyAsync(desc_out, d.out_desc + (size_t)image * d.out_cap * 32, (size_t)32 * hn[0], hipMemcpyDeviceToHost, ctx->stream));
     SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return SSX_OK;
+}
+
+// ScreenAndComputeKPsParams + CalcDescriptors enqueued, nothing fetched (the host side of ssx_orb_describe_at, and of the keyframe
+// step of loop.hip).  One block, on the device and (pinned) on the host: [image | keypoints in] go up in one copy, [keypoints out |
+// descriptors | keep flags] stay where the kernel wrote them.
+ssx_status describe_enqueue(ssx_ctx* ctx, const uint8_t* img, int stride, int rows, int cols, const ssx_orb_params& prm, const ssx_keypoint* kps, int n_kps,
+                            int levels, Described* out)
+{
+  OrbWorkspace* ws = get_ws(ctx);
+  const PlanKey key{rows, cols, 1, prm.nlevels, prm.nfeatures, prm.ini_th_fast, prm.min_th_fast, 0, 0, prm.scale_factor};
+  const bool planned = ws->planned && ws->key == key;
+  ssx_status st = plan(ctx, rows, cols, 1, prm, false, false);
+  if (st != SSX_OK) return st;
+  const OrbDev& d = ws->dev;
+  const int n_in = levels > 0 ? n_kps * levels : n_kps;
+  DescribeAt a;
+  const uint8_t* image;
+  auto buffers = [&](auto&& f) {
+    f(image, (size_t)rows * cols); f(a.in, sizeof(ssx_keypoint) * (size_t)n_in);
+    f(a.out, sizeof(ssx_keypoint) * (size_t)n_in); f(a.desc, (size_t)32 * n_in); f(a.keep, (size_t)n_in);
+  };
+  const size_t total = carve(nullptr, buffers);
+  SSX_HIP_TRY(ctx, ws->input.reserve(total));
+  SSX_HIP_TRY(ctx, ws->stage.reserve(total));
+  char* base = ws->input.as<char>();
+  carve(base, buffers); a.n_in = n_in;
+  ssx_keypoint* hk = (ssx_keypoint*)(ws->stage.as<char>() + ((const char*)a.in - base));   // the keypoints' place in the pinned block
+  if (levels > 0) {
+    // every feature once per level: octave = level, response = -1, class_id = the feature (loopclosing.cpp:607-619)
+    for (int i = 0; i < n_kps; ++i)
+      for (int l = 0; l < levels; ++l) {
+        ssx_keypoint kp = kps[i];
+        kp.octave = l; kp.response = -1.f; kp.class_id = i;
+        hk[(size_t)i * levels + l] = kp;
+      }
+  } else if (n_in > 0) {
+    memcpy(hk, kps, sizeof(ssx_keypoint) * n_in);
+  }
+  const size_t up = (const char*)a.out - base;
+  st = host_image_to_level0(ctx, img, stride, rows, cols, nullptr, 0, up);
+  if (st != SSX_OK) return st;
+  hipStream_t s = ctx->stream;
+  int launches = 1 + launch_pyramid(ctx, d, s, 1);   // ComputePyramid(image), orbextractor.cpp:1012-1027
+  SSX_PROF(ctx, KID_ORB_GAUSS, hipLaunchKernelGGL(k_gauss7, dim3(d.gauss_tile0[d.nlevels], 1), dim3(256), 0, s, d));
+  ++launches;
+  if (n_in > 0) {
+    SSX_PROF(ctx, KID_ORB_BRIEF, hipLaunchKernelGGL(k_describe_at, dim3((n_in + 3) / 4), dim3(256), 0, s, d, a));
+    ++launches;
+  }
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  out->base = base; out->total = total; out->kps = a.out; out->desc = a.desc; out->keep = a.keep; out->n_in = n_in;
+  out->launches = launches; out->syncs = planned ? 0 : 2; out->bytes_up = up;
   return SSX_OK;
 }
 
@@ -1679,37 +1735,18 @@ ssx_status ssx_orb_describe_at(ssx_ctx* ctx, const uint8_t* img, int32_t stride,
     ctx->set_error("ssx_orb_describe_at: stride smaller than the image width or no output arrays");
     return SSX_ERR_INVALID_ARG;
   }
-  ssx_status st = plan(ctx, rows, cols, 1, *prm, false, false);
+  Described d;
+  ssx_status st = describe_enqueue(ctx, img, stride, rows, cols, *prm, kps_in, n_in, 0, &d);
   if (st != SSX_OK) return st;
   OrbWorkspace* ws = get_ws(ctx);
-  const OrbDev& d = ws->dev;
-  // one block, on the device and (pinned) on the host: [image | keypoints in] go up, [keypoints out | descriptors | keep flags] come back
-  DescribeAt a;
-  const uint8_t* image;
-  auto buffers = [&](auto&& f) {
-    f(image, (size_t)rows * cols); f(a.in, sizeof(ssx_keypoint) * (size_t)n_in);
-    f(a.out, sizeof(ssx_keypoint) * (size_t)n_in); f(a.desc, (size_t)32 * n_in); f(a.keep, (size_t)n_in);
-  };
-  const size_t total = carve(nullptr, buffers);
-  SSX_HIP_TRY(ctx, ws->input.reserve(total));
-  SSX_HIP_TRY(ctx, ws->stage.reserve(total));
-  char* base = ws->input.as<char>();
-  carve(base, buffers); a.n_in = n_in;
-  auto host = [&](const void* dev) { return ws->stage.as<char>() + ((const char*)dev - base); };   // a buffer's place in the pinned block
-  memcpy(host(a.in), kps_in, sizeof(ssx_keypoint) * n_in);
-  st = host_image_to_level0(ctx, img, stride, rows, cols, nullptr, 0, (const char*)a.out - base);
-  if (st != SSX_OK) return st;
-  hipStream_t s = ctx->stream;
-  launch_pyramid(ctx, d, s, 1);           // ComputePyramid(image), orbextractor.cpp:1012-1027
-  SSX_PROF(ctx, KID_ORB_GAUSS, hipLaunchKernelGGL(k_gauss7, dim3(d.gauss_tile0[d.nlevels], 1), dim3(256), 0, s, d));
-  SSX_PROF(ctx, KID_ORB_BRIEF, hipLaunchKernelGGL(k_describe_at, dim3((n_in + 3) / 4), dim3(256), 0, s, d, a));
-  SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(host(a.out), a.out, total - ((const char*)a.out - base), hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  // [keypoints out | descriptors | keep flags] come back into the pinned twin of the block
+  auto host = [&](const void* dev) { return ws->stage.as<char>() + ((const char*)dev - d.base); };
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(host(d.kps), d.kps, d.total - ((const char*)d.kps - d.base), hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // order-preserving compaction of the kept keypoints (out_keypoints.push_back order, :893)
-  const ssx_keypoint* ok = (const ssx_keypoint*)host(a.out);
-  const uint8_t* od = (const uint8_t*)host(a.desc);
-  const uint8_t* keep = (const uint8_t*)host(a.keep);
+  const ssx_keypoint* ok = (const ssx_keypoint*)host(d.kps);
+  const uint8_t* od = (const uint8_t*)host(d.desc);
+  const uint8_t* keep = (const uint8_t*)host(d.keep);
   int m = 0;
   for (int i = 0; i < n_in; ++i) {
     if (!keep[i]) continue;

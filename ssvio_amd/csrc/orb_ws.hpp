@@ -146,6 +146,18 @@ ssx_status run_pipeline(ssx_ctx* ctx);
 ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n);
 // the brute-force matcher k_bf_match (stereo.hip) on device arrays: idx[i] / dist[i] = nearest of the nt <= 65535 train descriptors to query i
 void launch_bf_match(hipStream_t stream, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist);
+// what describe_enqueue leaves on the device: per input keypoint the output keypoint and descriptor (valid where keep), inside the block at
+// `base` of `total` bytes; and what it issued: launches, synchronisations (a new plan's two), bytes sent up
+struct Described {
+  char* base = nullptr; size_t total = 0;
+  const ssx_keypoint* kps = nullptr; const uint8_t* desc = nullptr; const uint8_t* keep = nullptr;
+  int n_in = 0, launches = 0, syncs = 0;
+  size_t bytes_up = 0;
+};
+// ScreenAndComputeKPsParams + CalcDescriptors of `kps` on a host image, enqueued on the ctx stream (orb.hip).  levels > 0: every keypoint is
+// replicated over that many pyramid levels first (octave = level, response = -1, class_id = its index); levels == 0: taken as they are
+ssx_status describe_enqueue(ssx_ctx* ctx, const uint8_t* img, int stride, int rows, int cols, const ssx_orb_params& prm, const ssx_keypoint* kps, int n_kps,
+                            int levels, Described* out);
 // a buffer's pointer, whatever its type, from the base of its block and its offset
 template <class T> void wire(T*& ptr, char* base, size_t off) { ptr = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off); }
 // The buffers of one block, each stated ONCE: `each(f)` calls f(pointer, bytes) for every buffer in memory order.  Wires the pointers

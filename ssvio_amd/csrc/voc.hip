@@ -20,25 +20,16 @@
 #include <string>
 #include <vector>
 
-#include "ctx.hpp"
+#include "voc.hpp"
 
-struct ssx_vocabulary {
-  ssx_ctx* ctx = nullptr;
-  int k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;
-  DevBuf arena, io;
-  HostBuf stage;
-  const uint8_t* d_desc = nullptr;      // [n_nodes][32]
-  const double* d_weight = nullptr;     // [n_nodes]
-  const int32_t* d_child_ptr = nullptr; // [n_nodes + 1]
-  const int32_t* d_child = nullptr;     // [n_nodes - 1] children of every node, id order
-  const int32_t* d_word = nullptr;      // [n_nodes] word id of a leaf, -1 otherwise
-};
 
 namespace {
 
 __global__ __launch_bounds__(256) void k_voc_words(const uint8_t* desc, const double* weight, const int32_t* child_ptr, const int32_t* child,
-                                                   const int32_t* word_of, const uint8_t* feat, int n, int32_t* word_out, double* weight_out)
+                                                   const int32_t* word_of, const uint8_t* feat, int n, const int32_t* n_dev, int32_t* word_out,
+                                                   double* weight_out)
 {
+  if (n_dev) n = *n_dev;                                     // the count lies on the device (the keyframe step of loop.hip): the grid covers its bound
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= n) return;
   const uint4* q4 = reinterpret_cast<const uint4*>(feat + 32 * (size_t)f);
@@ -64,6 +55,14 @@ __global__ __launch_bounds__(256) void k_voc_words(const uint8_t* desc, const do
 }
 
 }  // namespace
+
+namespace ssxvoc {
+void launch_words(hipStream_t stream, const ssx_vocabulary* v, const uint8_t* feat, int n_bound, const int32_t* n_dev, int32_t* word_out, double* weight_out)
+{
+  hipLaunchKernelGGL(k_voc_words, dim3((n_bound + 255) / 256), dim3(256), 0, stream, v->d_desc, v->d_weight, v->d_child_ptr, v->d_child, v->d_word, feat,
+                     n_bound, n_dev, word_out, weight_out);
+}
+}  // namespace ssxvoc
 
 extern "C" {
 
@@ -189,8 +188,7 @@ ssx_status ssx_voc_transform(ssx_vocabulary* v, const uint8_t* desc, int32_t n, 
   char* db = v->io.as<char>();
   memcpy(hs + o_f, desc, (size_t)32 * n);
   SSX_HIP_TRY(ctx, hipMemcpyAsync(db, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_voc_words, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, v->d_desc, v->d_weight, v->d_child_ptr, v->d_child, v->d_word,
-                     (const uint8_t*)(db + o_f), n, (int32_t*)(db + o_word), (double*)(db + o_w));
+  ssxvoc::launch_words(ctx->stream, v, (const uint8_t*)(db + o_f), n, nullptr, (int32_t*)(db + o_word), (double*)(db + o_w));
   SSX_HIP_TRY(ctx, hipGetLastError());
   SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_word, db + o_word, lay.off - o_word, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

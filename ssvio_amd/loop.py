@@ -1,7 +1,8 @@
 """Loop closing on the device -- include/ssx.h.
 
 KeyframeDatabase       ssx_kfdb_*: AddToKeyframeDatabase, DetectLoop and MatchFeatures (reference: src/ssvio/loopclosing.cpp:646-649,
-                       :72-103, :105-145)
+                       :72-103, :105-145), and the per-keyframe step of LoopClosingThread as one call (process_keyframe / add_pending /
+                       pending: ProcessNewKeyframe :596-634 + DetectLoop + MatchFeatures, the keyframe left on the device)
 pnp_ransac             ssx_pnp_ransac: the cv::solvePnPRansac call of ComputeCorrectPose (:205-206) under the contract of
                        tools/pnp_model.py
 loop_pose_opt          ssx_loop_pose_opt: OptimizeCurrentPose (:245-351)
@@ -12,14 +13,27 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import SSX_ERR_CAPACITY, Context, dbl_p, i32_p, ptr, u8_p
+from ._lib import KP_DTYPE, SSX_ERR_CAPACITY, Context, OrbParams, dbl_p, i32_p, ptr, u8_p
 
 i64_p = C.POINTER(C.c_int64)
+
+
+class StepResult(C.Structure):
+    """ssx_kfdb_step_result"""
+    _fields_ = [("n_pyramid", C.c_int32), ("n_bow", C.c_int32), ("detect_ran", C.c_int32), ("n_scored", C.c_int32), ("found", C.c_int32),
+                ("score", C.c_float), ("loop_kf_id", C.c_int64), ("n_pairs", C.c_int32), ("min_distance", C.c_int32)]
 
 
 def _bind(lib):
     if getattr(lib, "_kfdb_bound", False):
         return
+    lib.ssx_kfdb_process_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, u8_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, i32_p, C.POINTER(StepResult)]
+    lib.ssx_kfdb_add_pending.argtypes = [C.c_void_p]
+    lib.ssx_kfdb_pending.argtypes = [C.c_void_p, i64_p, C.c_int32, C.c_void_p, u8_p, i32_p, i32_p, C.c_int32, i32_p, dbl_p, i32_p]
+    if hasattr(lib, "ssx_kfdb_debug_last_step"):              # include/ssx_test_hooks.h: absent from a product build
+        lib.ssx_kfdb_debug_last_step.argtypes = [C.c_void_p, i32_p, i32_p, i64_p, i64_p]
+        lib.ssx_kfdb_debug_bow.argtypes = [C.c_void_p, u8_p, C.c_int32, C.c_int32, i32_p, dbl_p, i32_p]
     lib.ssx_kfdb_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
     lib.ssx_kfdb_destroy.argtypes = [C.c_void_p]
     lib.ssx_kfdb_destroy.restype = None
@@ -106,6 +120,67 @@ class KeyframeDatabase:
                 e.n_pairs = n.value
             raise
         return pairs[:n.value].copy(), md.value
+
+
+    def process_keyframe(self, voc, kf_id, image, features, prm, threshold, pyramid_levels=8, min_db_size=0, min_id_gap=20, pairs_cap=None):
+        """The per-keyframe step in one call: ProcessNewKeyframe (features [n] KP_DTYPE = the left features' kp_position_, replicated over
+        pyramid_levels), DetectLoop when more than min_db_size keyframes are stored, MatchFeatures against the winner.  -> dict of
+        ssx_kfdb_step_result's fields (loop_kf_id / score None when nothing was found) and pairs [n_pairs, 2].  The keyframe stays on the
+        device as the pending one: add_pending() stores it, pending() downloads it.  SsxError with status SSX_ERR_CAPACITY carries .result
+        (the first pairs_cap pairs in it) when pairs_cap is too small; the keyframe is pending all the same."""
+        image = np.asarray(image)
+        if image.ndim != 2 or image.dtype != np.uint8 or image.strides[1] != 1:
+            image = np.ascontiguousarray(image, dtype=np.uint8)
+        features = np.ascontiguousarray(features, dtype=KP_DTYPE)
+        if pairs_cap is None:
+            pairs_cap = len(features) * int(pyramid_levels)       # a std::set of (current class_id, loop class_id): bounded by the stored
+            pairs_cap = max(pairs_cap, self.size()[2])            # keyframe's descriptors
+        pairs = np.zeros((max(pairs_cap, 1), 2), np.int32)
+        r = StepResult()
+        st = self.ctx.lib.ssx_kfdb_process_keyframe(self.handle, voc.handle, int(kf_id), ptr(image, u8_p), image.strides[0], image.shape[0], image.shape[1],
+                                                    C.byref(prm), len(features), features.ctypes.data_as(C.c_void_p), int(pyramid_levels),
+                                                    int(min_db_size), int(min_id_gap), float(threshold), int(pairs_cap), ptr(pairs, i32_p), C.byref(r))
+        out = dict(n_pyramid=r.n_pyramid, n_bow=r.n_bow, detect_ran=bool(r.detect_ran), n_scored=r.n_scored, found=bool(r.found),
+                   score=np.float32(r.score) if r.found else None, loop_kf_id=r.loop_kf_id if r.found else None, n_pairs=r.n_pairs,
+                   min_distance=r.min_distance, pairs=pairs[:min(r.n_pairs, pairs_cap)].copy())
+        try:
+            self.ctx.check(st)
+        except Exception as e:
+            if st == SSX_ERR_CAPACITY:
+                e.result = out
+            raise
+        return out
+
+    def add_pending(self):
+        """AddToKeyframeDatabase for the keyframe of the last process_keyframe, device to device"""
+        self.ctx.check(self.ctx.lib.ssx_kfdb_add_pending(self.handle))
+
+    def pending(self):
+        """-> dict(kf_id, keypoints [n] KP_DTYPE, desc [n, 32], class_id [n], bow = (ids, values)): the pending keyframe, downloaded"""
+        lib = self.ctx.lib
+        kf, n, nb = C.c_int64(), C.c_int32(), C.c_int32()
+        self.ctx.check(lib.ssx_kfdb_pending(self.handle, C.byref(kf), 0, None, None, None, C.byref(n), 0, None, None, C.byref(nb)))
+        kps = np.zeros(max(n.value, 1), KP_DTYPE); desc = np.zeros((max(n.value, 1), 32), np.uint8); cls = np.zeros(max(n.value, 1), np.int32)
+        ids = np.zeros(max(nb.value, 1), np.int32); vals = np.zeros(max(nb.value, 1), np.float64)
+        self.ctx.check(lib.ssx_kfdb_pending(self.handle, None, n.value, kps.ctypes.data_as(C.c_void_p), ptr(desc, u8_p), ptr(cls, i32_p), None,
+                                            nb.value, ptr(ids, i32_p), ptr(vals, dbl_p), None))
+        return dict(kf_id=kf.value, keypoints=kps[:n.value], desc=desc[:n.value], class_id=cls[:n.value], bow=(ids[:nb.value], vals[:nb.value]))
+
+    def debug_last_step(self):
+        """tests / tools hook -> dict(launches, syncs, bytes_up, bytes_down) of the last process_keyframe"""
+        a, b, c, d = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.ssx_kfdb_debug_last_step(self.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(launches=a.value, syncs=b.value, bytes_up=c.value, bytes_down=d.value)
+
+
+def debug_bow(voc, desc):
+    """tests hook -> (ids, values): the BowVector of desc [n, 32] as the step's device kernels assemble it"""
+    _bind(voc.ctx.lib)
+    desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 32)
+    n = len(desc)
+    ids = np.zeros(max(n, 1), np.int32); vals = np.zeros(max(n, 1), np.float64); m = C.c_int32()
+    voc.ctx.check(voc.ctx.lib.ssx_kfdb_debug_bow(voc.handle, ptr(desc, u8_p), n, max(n, 1), ptr(ids, i32_p), ptr(vals, dbl_p), C.byref(m)))
+    return ids[:m.value].copy(), vals[:m.value].copy()
 
 
 # ---- the pose correction: ComputeCorrectPose / OptimizeCurrentPose ---------------------------------------------------------------
