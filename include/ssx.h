@@ -363,6 +363,7 @@ SSX_API ssx_status ssx_ba_window_solve_batch(int32_t n, ssx_ba_window* const* wi
  *   pose_io: initial estimate in, result out;  xyz: M x 3 map points;  uv: M x 2 measured pixels (cv::Point2f
  *   widened to double);  inlier_out[i] = 1 if the feature ends as inlier;  *n_inliers = features.size() - outliers.
  *   Reference defaults: rounds 4, iters 10, chi2_th 5.991, huber_delta 1.0.
+ *   Every input value must be finite and no map point may coincide with the camera centre (0 / 0): behaviour on NaN or infinity is undefined.
  * ------------------------------------------------------------------------------------------------ */
 SSX_API ssx_status ssx_pose_only_opt(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz,
                                      const double* uv, int32_t rounds, int32_t iters, double chi2_th,

@@ -131,6 +131,23 @@ SSX_API ssx_status ssx_lk_debug_plan(int32_t rows, int32_t cols, int32_t win, in
 /* the same struct for the last successful LK call of ctx (status SSX_OK, no error text) */
 SSX_API ssx_status ssx_lk_debug_last_call(ssx_ctx* ctx, ssx_lk_call_info* out);
 
+/* tests hook of the pose-only Levenberg kernels (csrc/pose_only.hip): ssx_pose_only_opt_batch -- jobs of any size in one call, so
+ * k_pose_only<2> (M <= 512), k_pose_only<6> (M <= 1536) and k_pose_only_generic are all reached -- behind `warmup` optimize(iters)
+ * passes over all edges (0: ssx_pose_only_opt; 1: ssx_loop_pose_opt), run by TRACED instantiations of the same three kernel bodies.
+ * They fill what g2o exposes in postIteration, which is also what oracle/ref_driver.cpp's ref_pose_only_trace and the oracle's
+ * orc_pose_only_trace record, so that every Levenberg decision of a run can be held against the compiled reference and not only
+ * its end (tests/test_pose_only_edges_gpu.py, tests/golden/ref_po_trace.npz):
+ *   per LM iteration   it_chi2 = the robust chi2 of the edges' current errors (the TRIAL state when the last trial was rejected: pop()
+ *                      restores vertices only), it_lambda = lambda after the iteration, it_trials = its trials (levenbergIteration())
+ *   per optimize()     round_rec, 4 ints: active edges at its start, iterations run, 1 = its last iteration returned Terminate (ten
+ *                      trials, rho == 0 or a non-finite lambda), outliers after the classification (-1 behind a warm-up pass)
+ * Layout: job after job, R_j = warmup + jobs[j].rounds optimize() calls each: R_j * iters_j slots in the three it_* arrays (slot
+ * r * iters_j + it; slots of iterations that did not run are 0), R_j * 4 ints in round_rec.  A job with M = 0 records zeros.
+ * The job's outputs (pose_io, inlier_out, n_inliers) are written as ssx_pose_only_opt_batch writes them and, for warmup = 0, equal
+ * its bytes: the shipped instantiations take no record argument and compile to the code they had before the hook existed. */
+SSX_API ssx_status ssx_pose_only_debug_trace(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, double* it_chi2,
+                                             double* it_lambda, int32_t* it_trials, int32_t* round_rec);
+
 /* tests hooks of the P3P-RANSAC (csrc/pnp.hip, model: tools/pnp_model.py): the sample triples of (seed, M >= 3, H) as the kernel's
  * device function draws them (triples_out H x 3), and the best inlier count of each of the max_iters hypotheses of an
  * ssx_pnp_ransac call with the same arguments (counts_out max_iters) */

@@ -194,6 +194,30 @@ def pose_only(pr, which="oracle", rounds=4, iters=10, chi2_th=5.991, huber_delta
     return dict(pose=pose, inliers=inl, n_inliers=n)
 
 
+def pose_only_trace(pr, which="oracle", rounds=4, iters=10, chi2_th=5.991, huber_delta=1.0, lib=None):
+    """pose_only + the record g2o exposes in postIteration.  -> dict(pose, inliers, n_inliers, chi2 / lam / trials [rounds, iters]
+    (zero beyond the iterations a round ran), active / iters_run / terminated / outliers [rounds]).  lib: another build of the oracle."""
+    pose = np.ascontiguousarray(pr["pose"], dtype=np.float64).copy()
+    M = pr["M"]
+    inl = np.zeros(M, dtype=np.uint8)
+    xyz = np.ascontiguousarray(pr["xyz"]); uv = np.ascontiguousarray(pr["uv"]); K = np.ascontiguousarray(pr["K"])
+    chi = np.zeros((rounds, iters)); lam = np.zeros((rounds, iters)); tr = np.zeros((rounds, iters), dtype=np.int32)
+    rr = np.zeros((rounds, 4), dtype=np.int32)
+    if which == "ref":
+        assert huber_delta == 1.0                            # RobustKernelHuber's default, as the reference constructs it
+        f = ref_lib().ref_pose_only_trace
+        f.restype = C.c_int
+        n = f(_p(pose, dbl_p), _p(K, dbl_p), M, _p(xyz, dbl_p), _p(uv, dbl_p), rounds, iters, C.c_double(chi2_th), _p(inl, u8_p),
+              _p(chi, dbl_p), _p(lam, dbl_p), _p(tr, i32_p), _p(rr, i32_p))
+    else:
+        f = (lib or oracle_lib()).orc_pose_only_trace
+        f.restype = C.c_int
+        n = f(_p(pose, dbl_p), _p(K, dbl_p), M, _p(xyz, dbl_p), _p(uv, dbl_p), rounds, iters, C.c_double(chi2_th),
+              C.c_double(huber_delta), _p(inl, u8_p), _p(chi, dbl_p), _p(lam, dbl_p), _p(tr, i32_p), _p(rr, i32_p))
+    return dict(pose=pose, inliers=inl, n_inliers=n, chi2=chi, lam=lam, trials=tr, active=rr[:, 0].copy(), iters_run=rr[:, 1].copy(),
+                terminated=rr[:, 2].copy(), outliers=rr[:, 3].copy())
+
+
 def triangulate(uvL, uvR, K, baseline, T_wc=None, which="oracle"):
     uvL = np.ascontiguousarray(uvL, dtype=np.float64); uvR = np.ascontiguousarray(uvR, dtype=np.float64)
     n = uvL.shape[0]

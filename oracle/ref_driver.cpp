@@ -10,7 +10,7 @@
 //   ref_ba_solve      graph assembly + outer robust loop of Backend::OptimizeActiveMap
 //                     (/root/reference/src/ssvio/backend.cpp:78-203) on a flat problem.
 //   ref_pose_only     FrontEnd::EstimateCurrentPose optimisation core
-//                     (/root/reference/src/ssvio/frontend.cpp:184-270).
+//                     (/root/reference/src/ssvio/frontend.cpp:184-270); ref_pose_only_trace: the same with g2o's per-iteration record.
 //   ref_triangulate   ssvio::triangulation (/root/reference/include/ssvio/algorithm.hpp:23-45) with the
 //                     stereo rig of System::GenerateSteroCamera (src/ssvio/system.cpp:54-113) and the
 //                     acceptance test of FrontEnd::BuidInitMap (src/ssvio/frontend.cpp:466).
@@ -79,6 +79,19 @@ struct IterRecorder : public g2o::HyperGraphAction
     lambda.push_back(lm->currentLambda());
     trials.push_back(lm->levenbergIteration());
     return this;
+  }
+};
+
+// The reference's Levenberg algorithm, its arithmetic untouched: solve() is forwarded and its verdict kept, because optimize() folds
+// "Terminate" and "ran all iterations" into the same return value when the last iteration is the one that terminates.
+struct ResultKeepingLevenberg : public g2o::OptimizationAlgorithmLevenberg
+{
+  using g2o::OptimizationAlgorithmLevenberg::OptimizationAlgorithmLevenberg;
+  SolverResult last = OK;
+  SolverResult solve(int iteration, bool online = false) override
+  {
+    last = g2o::OptimizationAlgorithmLevenberg::solve(iteration, online);
+    return last;
   }
 };
 
@@ -179,15 +192,26 @@ int ref_ba_solve(int P, double* poses, const unsigned char* pose_fixed, int L, d
 }
 
 // Pose-only optimisation, frontend.cpp:184-270.  inlier_out[m] = 1 if the feature ends as inlier.
-int ref_pose_only(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
-                  int rounds, int iters, double chi2_th, unsigned char* inlier_out)
+// The record (every pointer nullable; nothing is attached to the optimizer when all are NULL):
+//   per LM iteration, slot round * iters + it: what IterRecorder sees in postIteration -- the robust chi2 of the edges' current
+//     _error (the TRIAL state after a rejected last trial), lambda, the trials of that iteration (levenbergIteration())
+//   per round, 4 ints: active edges after initializeOptimization(), iterations run (postIteration calls), 1 when the last solve()
+//     returned Terminate, outliers after the classification
+static int pose_only_impl(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                          int rounds, int iters, double chi2_th, unsigned char* inlier_out,
+                          double* it_chi2, double* it_lambda, int* it_trials, int* round_rec)
 {
   typedef g2o::BlockSolver_6_3 BlockSolverType;
   typedef g2o::LinearSolverDense<BlockSolverType::PoseMatrixType> LinearSolverType;
-  auto solver = new g2o::OptimizationAlgorithmLevenberg(
+  auto solver = new ResultKeepingLevenberg(
       g2o::make_unique<BlockSolverType>(g2o::make_unique<LinearSolverType>()));
   g2o::SparseOptimizer optimizer;
   optimizer.setAlgorithm(solver);
+  const bool trace = it_chi2 || it_lambda || it_trials || round_rec;
+  IterRecorder rec;
+  rec.opt = &optimizer;
+  rec.lm = solver;
+  if (trace) optimizer.addPostIterationAction(&rec);
 
   VertexPose* vertex_pose = new VertexPose();
   vertex_pose->setId(0);
@@ -211,6 +235,8 @@ int ref_pose_only(double* pose7, const double* K4, int M, const double* xyz, con
   int cnt_outliers = 0;
   for (int iteration = 0; iteration < rounds; iteration++) {
     optimizer.initializeOptimization();
+    rec.chi2.clear(); rec.lambda.clear(); rec.trials.clear();
+    solver->last = g2o::OptimizationAlgorithm::OK;
     optimizer.optimize(iters);
     cnt_outliers = 0;
     for (int i = 0; i < M; ++i) {
@@ -226,11 +252,41 @@ int ref_pose_only(double* pose7, const double* K4, int M, const double* xyz, con
       }
       if (iteration == rounds - 2) e->setRobustKernel(nullptr);
     }
+    if (trace) {
+      const int n = (int)rec.chi2.size();
+      for (int k = 0; k < n && k < iters; ++k) {
+        if (it_chi2) it_chi2[iteration * iters + k] = rec.chi2[k];
+        if (it_lambda) it_lambda[iteration * iters + k] = rec.lambda[k];
+        if (it_trials) it_trials[iteration * iters + k] = rec.trials[k];
+      }
+      if (round_rec) {
+        // (the active set is still the one optimize() ran on: the levels set above take effect at the next initializeOptimization())
+        round_rec[4 * iteration] = (int)optimizer.activeEdges().size();
+        round_rec[4 * iteration + 1] = n;
+        round_rec[4 * iteration + 2] = (n > 0 && solver->last == g2o::OptimizationAlgorithm::Terminate) ? 1 : 0;
+        round_rec[4 * iteration + 3] = cnt_outliers;
+      }
+    }
   }
+  if (trace) optimizer.removePostIterationAction(&rec);
   pose_to(vertex_pose->estimate(), pose7);
   if (inlier_out)
     for (int i = 0; i < M; ++i) inlier_out[i] = !is_outlier[i];
   return M - cnt_outliers;
+}
+
+int ref_pose_only(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                  int rounds, int iters, double chi2_th, unsigned char* inlier_out)
+{
+  return pose_only_impl(pose7, K4, M, xyz, uv, rounds, iters, chi2_th, inlier_out, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ref_pose_only + its per-iteration and per-round record: it_* hold rounds * iters values, round_rec rounds * 4 (zero-filled by the caller)
+int ref_pose_only_trace(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                        int rounds, int iters, double chi2_th, unsigned char* inlier_out,
+                        double* it_chi2, double* it_lambda, int* it_trials, int* round_rec)
+{
+  return pose_only_impl(pose7, K4, M, xyz, uv, rounds, iters, chi2_th, inlier_out, it_chi2, it_lambda, it_trials, round_rec);
 }
 
 // Stereo triangulation with the rig of system.cpp:63,71 (left = I, right = (I, (-baseline,0,0))).

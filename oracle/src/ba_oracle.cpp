@@ -582,8 +582,13 @@ int orc_ba_linearize(int P, const double* poses, const uint8_t* pose_fixed, int 
 
 // FrontEnd::EstimateCurrentPose core, src/ssvio/frontend.cpp:184-270, with EdgeProjectionPoseOnly
 // (g2otypes.hpp:67-110: analytic Jacobian, Zinv = 1/(Z+1e-18)) and LinearSolverDense.
-int orc_pose_only(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
-                  int rounds, int iters, double chi2_th, double huber_delta, uint8_t* inlier_out)
+// The record (every pointer nullable) is the one of ref_pose_only_trace (oracle/ref_driver.cpp): per LM iteration, slot
+// round * iters + it, the robust chi2 of the edges' current errors (the trial state after a rejected last trial), lambda and the
+// trials of that iteration; per round 4 ints: active edges, iterations run, 1 = the last iteration terminated, outliers after
+// the classification.
+static int pose_only_impl(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                          int rounds, int iters, double chi2_th, double huber_delta, uint8_t* inlier_out,
+                          double* it_chi2, double* it_lambda, int* it_trials, int* round_rec)
 {
   const Cam K = cam_from(K4);
   std::vector<uint8_t> level(M, 0), is_outlier(M, 0);
@@ -614,6 +619,7 @@ int orc_pose_only(double* pose7, const double* K4, int M, const double* xyz, con
     int n_active = 0;
     for (int i = 0; i < M; ++i) n_active += !level[i];
     double lambda = -1, ni = 2;
+    int its_run = 0, terminated = 0;
     for (int it = 0; it < iters && n_active > 0; ++it) {
       for (int i = 0; i < M; ++i) if (!level[i]) compute_error(i);
       double currentChi = robust_chi2(), tempChi = currentChi;
@@ -667,7 +673,12 @@ int orc_pose_only(double* pose7, const double* K4, int M, const double* xyz, con
         }
         qmax++;
       } while (rho < 0 && qmax < 10);
-      if (qmax == 10 || rho == 0 || lambda_bad) break;
+      // postIteration: the edges' errors are those of the last trial, accepted or not
+      ++its_run;
+      if (it_chi2) it_chi2[round * iters + it] = robust_chi2();
+      if (it_lambda) it_lambda[round * iters + it] = lambda;
+      if (it_trials) it_trials[round * iters + it] = qmax;
+      if (qmax == 10 || rho == 0 || lambda_bad) { terminated = 1; break; }
     }
     // NB: after a rejected last trial g2o leaves _error of the active edges at the TRIAL state
     // (computeActiveErrors ran after update(); pop() restores vertices only).  frontend.cpp:247-251
@@ -678,10 +689,27 @@ int orc_pose_only(double* pose7, const double* K4, int M, const double* xyz, con
       if (chi2_of(i) > chi2_th) { is_outlier[i] = 1; level[i] = 1; cnt_outliers++; }
       else { is_outlier[i] = 0; level[i] = 0; }
     }
+    if (round_rec) {
+      round_rec[4 * round] = n_active; round_rec[4 * round + 1] = its_run;
+      round_rec[4 * round + 2] = terminated; round_rec[4 * round + 3] = cnt_outliers;
+    }
     if (round == rounds - 2) use_kernel = false;
   }
   if (inlier_out) for (int i = 0; i < M; ++i) inlier_out[i] = !is_outlier[i];
   return M - cnt_outliers;
+}
+
+int orc_pose_only(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                  int rounds, int iters, double chi2_th, double huber_delta, uint8_t* inlier_out)
+{
+  return pose_only_impl(pose7, K4, M, xyz, uv, rounds, iters, chi2_th, huber_delta, inlier_out, nullptr, nullptr, nullptr, nullptr);
+}
+
+int orc_pose_only_trace(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                        int rounds, int iters, double chi2_th, double huber_delta, uint8_t* inlier_out,
+                        double* it_chi2, double* it_lambda, int* it_trials, int* round_rec)
+{
+  return pose_only_impl(pose7, K4, M, xyz, uv, rounds, iters, chi2_th, huber_delta, inlier_out, it_chi2, it_lambda, it_trials, round_rec);
 }
 
 }  // extern "C"

@@ -60,6 +60,11 @@ void orc_edge_eval(const double* pose7, const double* p3, const double* uv2, con
 /* Pose-only (A11).  Returns number of inliers. */
 int orc_pose_only(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
                   int rounds, int iters, double chi2_th, double huber_delta, uint8_t* inlier_out);
+/* ... with the per-iteration record g2o exposes in postIteration (it_*: rounds * iters values, slot round * iters + it) and the
+ * per-round record (round_rec: rounds * 4 = active edges, iterations run, terminated, outliers); any of them may be NULL. */
+int orc_pose_only_trace(double* pose7, const double* K4, int M, const double* xyz, const double* uv,
+                        int rounds, int iters, double chi2_th, double huber_delta, uint8_t* inlier_out,
+                        double* it_chi2, double* it_lambda, int* it_trials, int* round_rec);
 
 /* ---------------- Triangulation (A10) ---------------- */
 void orc_triangulate(int n, const double* uvL, const double* uvR, double fx, double fy, double cx,

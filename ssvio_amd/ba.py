@@ -506,3 +506,40 @@ class BaWindow:
             self.close()
         except Exception:                                   # noqa: BLE001
             pass
+
+
+def pose_only_trace(ctx: Context, problems, settings, warmup=0, chi2_th=5.991, huber_delta=1.0):
+    """include/ssx_test_hooks.h: ssx_pose_only_debug_trace (absent from a product build).  problems = [dict(pose, K, xyz, uv)], settings =
+    [(rounds, iters)] per problem, all in ONE call -> per problem dict(pose, inliers, n_inliers, chi2 / lam / trials [R, iters], active /
+    iters_run / terminated / outliers [R]) with R = warmup + rounds."""
+    n = len(problems)
+    arr = (PoseOnlyJob * max(n, 1))()
+    keep, outs = [], []
+    for i, (pr, (rounds, iters)) in enumerate(zip(problems, settings)):
+        pose = np.ascontiguousarray(pr["pose"], dtype=np.float64).copy()
+        K = np.ascontiguousarray(pr["K"], dtype=np.float64)
+        xyz = np.ascontiguousarray(pr["xyz"], dtype=np.float64).reshape(-1, 3)
+        uv = np.ascontiguousarray(pr["uv"], dtype=np.float64).reshape(-1, 2)
+        inl = np.zeros(len(xyz), dtype=np.uint8)
+        cnt = (C.c_int32 * 1)(0)
+        a = arr[i]
+        a.pose_io = ptr(pose, dbl_p); a.K4 = ptr(K, dbl_p); a.M = len(xyz); a.xyz = ptr(xyz, dbl_p); a.uv = ptr(uv, dbl_p)
+        a.rounds = rounds; a.iters = iters; a.chi2_th = chi2_th; a.huber_delta = huber_delta
+        a.inlier_out = ptr(inl, u8_p); a.n_inliers = C.cast(cnt, C.POINTER(C.c_int32))
+        keep.append((K, xyz, uv)); outs.append((pose, inl, cnt))
+    n_it = sum((warmup + r) * i for r, i in settings)
+    n_rd = sum(warmup + r for r, _ in settings)
+    chi = np.zeros(max(n_it, 1)); lam = np.zeros(max(n_it, 1)); tr = np.zeros(max(n_it, 1), dtype=np.int32); rr = np.zeros((max(n_rd, 1), 4), dtype=np.int32)
+    f = ctx.lib.ssx_pose_only_debug_trace
+    f.restype = C.c_int32
+    f.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PoseOnlyJob), C.c_int32, dbl_p, dbl_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    ctx.check(f(ctx.handle, n, arr, warmup, ptr(chi, dbl_p), ptr(lam, dbl_p), tr.ctypes.data_as(C.POINTER(C.c_int32)), rr.ctypes.data_as(C.POINTER(C.c_int32))))
+    res, o_it, o_rd = [], 0, 0
+    for (p_, i_, c_), (rounds, iters) in zip(outs, settings):
+        R = warmup + rounds
+        it = lambda a: a[o_it:o_it + R * iters].reshape(R, iters).copy()      # noqa: E731
+        r4 = rr[o_rd:o_rd + R]
+        res.append(dict(pose=p_, inliers=i_, n_inliers=int(c_[0]), chi2=it(chi), lam=it(lam), trials=it(tr), active=r4[:, 0].copy(),
+                        iters_run=r4[:, 1].copy(), terminated=r4[:, 2].copy(), outliers=r4[:, 3].copy()))
+        o_it += R * iters; o_rd += R
+    return res

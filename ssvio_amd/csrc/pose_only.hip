@@ -25,6 +25,7 @@
 #include "ctx.hpp"
 #include "pose_only.hpp"
 #include "se3.hpp"
+#include "../../include/ssx_test_hooks.h"
 
 namespace {
 
@@ -45,6 +46,17 @@ struct PoDev {
   int* n_inliers;
   int warmup;          // optimize(iters) passes over all edges before the classified rounds (0: EstimateCurrentPose)
   const int* gate;     // nullable: *gate == 0 ends the launch before it writes anything
+};
+
+// The record of the traced instantiations (include/ssx_test_hooks.h: ssx_pose_only_debug_trace; never part of a product build and
+// never an argument of the shipped kernels).  What g2o exposes in postIteration, slot (warmup + round) * iters + it: the robust chi2
+// of the edges' current errors (the trial state after a rejected last trial), lambda, the trials of the iteration; per optimize()
+// 4 ints: active edges, iterations run, 1 = its last iteration terminated, outliers after the classification (-1: a warm-up pass).
+struct PoTrace {
+  double* chi2;
+  double* lambda;
+  int* trials;
+  int* round_rec;
 };
 
 __device__ __forceinline__ void po_error(const double* T, const PoDev& d, int i, double* e, double* pc)
@@ -69,8 +81,18 @@ __device__ __forceinline__ void tree_reduce(double (*sRed)[PT], int n)
   }
 }
 
-__global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
+// the record of a traced instantiation (the one element of the kernel's parameter pack), nothing for a shipped one
+__device__ __forceinline__ const PoTrace* po_trace_of() { return nullptr; }
+__device__ __forceinline__ const PoTrace* po_trace_of(const PoTrace& tr) { return &tr; }
+__device__ __forceinline__ const PoTrace* po_trace_at(const PoTrace* tv, unsigned problem) { return tv + problem; }
+
+// TR: empty for the shipped kernel -- its parameters and its code are what they were before the record existed --, PoTrace for the
+// traced instantiation of the test hook
+template <class... TR>
+__global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d, TR... trace)
 {
+  constexpr bool TRACE = sizeof...(TR) > 0;
+  [[maybe_unused]] const PoTrace* tr = po_trace_of(trace...);
   __shared__ double sRed[NRED][PT];
   __shared__ double sT[7], sTbak[7], sX[6];
   __shared__ double sCtl[8];      // 0 lambda, 1 ni, 2 currentChi, 3 rho, 4 qmax, 5 stop flag, 6 accepted
@@ -111,6 +133,8 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
     tree_reduce(sRed, 1);
     const int n_active = (int)sRed[0][0];
     __syncthreads();
+    int its_run = 0;
+    bool terminated = false;
     for (int it = 0; it < d.iters && n_active > 0; ++it) {
       const double chi_now = errors_and_chi2();
       __syncthreads();
@@ -160,6 +184,7 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
       }
       __syncthreads();
       // ---- LM trials ----
+      [[maybe_unused]] double last_chi = 0.0;
       while (true) {
         if (t == 0) {
           for (int k = 0; k < 7; ++k) sTbak[k] = sT[k];
@@ -205,6 +230,7 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
         __syncthreads();
         // the H/b in sRed[0..26][0] must survive the chi2 reduction: it only touches row 27
         double tempChi = errors_and_chi2();
+        if constexpr (TRACE) last_chi = tempChi;
         if (t == 0) {
           if (sCtl[6] == 0.0) tempChi = 1.7976931348623157e308;
           double rho = sCtl[2] - tempChi;
@@ -235,10 +261,24 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
         __syncthreads();
         if (sCtl[3] == 0.0) break;
       }
+      if constexpr (TRACE) {
+        ++its_run;
+        terminated = sCtl[5] != 0.0;
+        if (t == 0) {
+          const int slot = (round + d.warmup) * d.iters + it;
+          tr->chi2[slot] = last_chi; tr->lambda[slot] = sCtl[0]; tr->trials[slot] = (int)sCtl[4];
+        }
+      }
       if (sCtl[5] != 0.0) break;   // Terminate: optimize() stops iterating
       __syncthreads();
     }
     __syncthreads();
+    if constexpr (TRACE) {
+      if (t == 0) {
+        int* rr = tr->round_rec + 4 * (round + d.warmup);
+        rr[0] = n_active; rr[1] = its_run; rr[2] = terminated ? 1 : 0; rr[3] = -1;
+      }
+    }
     if (round < 0) continue;
     // frontend.cpp:243-268: recompute the error only for features flagged outlier, classify, set levels
     {
@@ -259,6 +299,9 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d)
       tree_reduce(sRed, 1);
       cnt_outliers = (int)sRed[0][0];
       __syncthreads();
+      if constexpr (TRACE) {
+        if (t == 0) tr->round_rec[4 * (round + d.warmup) + 3] = cnt_outliers;
+      }
       if (t == 0 && round == d.rounds - 2) sUseKernel = 0;   // e->setRobustKernel(nullptr)
       __syncthreads();
     }
@@ -418,11 +461,15 @@ __device__ __forceinline__ bool solve6(const double* Hb, double lambda, double* 
 // dv: one descriptor per problem of the batch (blockIdx.x = problem); ssx_pose_only_opt is a batch of one.  The descriptors
 // and a problem's inputs live in a pinned host block the kernel reads DIRECTLY (each value once, at the top), its results go
 // straight back into that block: one launch and one synchronisation per batch, no copy in either direction.
-template <int EPT>
-__global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
+// TR: as for k_pose_only_generic; a traced launch passes one `const PoTrace*`, the records of its problems
+template <int EPT, class... TR>
+__global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv, TR... trace_v)
 {
+  constexpr bool TRACE = sizeof...(TR) > 0;
   const PoDev d = dv[blockIdx.x];
   if (d.gate && *d.gate == 0) return;
+  [[maybe_unused]] const PoTrace* tr = nullptr;
+  if constexpr (TRACE) tr = po_trace_at(trace_v..., blockIdx.x);
   __shared__ double sPart[2][NRED][NW];
   __shared__ double sT[27][PT];
   __shared__ double sTot[27];
@@ -477,6 +524,8 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
     block_sum<1>(&na, sPart, buf);
     const bool any_active = na > 0.0;                       // initializeOptimization(0): only level-0 edges are active
     double lambda = 0.0, ni = 2.0, current_chi = 0.0;
+    [[maybe_unused]] int its_run = 0;
+    [[maybe_unused]] bool terminated = false;
     for (int it = 0; it < d.iters && any_active; ++it) {
       // solve() starts with computeActiveErrors() + activeRobustChi2(); after an accepted trial (the only way to get
       // here with it > 0) the errors and the chi2 of that trial ARE those values -- no second pass over the edges
@@ -516,6 +565,7 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
       // ---- LM trials ----
       int qmax = 0;
       bool stop = false;
+      [[maybe_unused]] double last_chi = 0.0;
       while (true) {
         double Tbak[7];
 #pragma unroll
@@ -527,6 +577,7 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
 #pragma unroll
         for (int k = 0; k < 7; ++k) T[k] = Tn[k];
         double temp_chi = errors_and_chi2();
+        if constexpr (TRACE) last_chi = temp_chi;
         if (!ok) temp_chi = 1.7976931348623157e308;
         double scale = 0.0;
 #pragma unroll
@@ -553,7 +604,21 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
         stop = (qmax == 10 || rho == 0 || lambda_bad);
         if (!(!lambda_bad && rho < 0 && qmax < 10)) break;
       }
+      if constexpr (TRACE) {
+        ++its_run;
+        terminated = stop;
+        if (t == 0) {
+          const int slot = (round + d.warmup) * d.iters + it;
+          tr->chi2[slot] = last_chi; tr->lambda[slot] = lambda; tr->trials[slot] = qmax;
+        }
+      }
       if (stop) break;                                         // Terminate: optimize() stops iterating
+    }
+    if constexpr (TRACE) {
+      if (t == 0) {
+        int* rr = tr->round_rec + 4 * (round + d.warmup);
+        rr[0] = (int)na; rr[1] = its_run; rr[2] = terminated ? 1 : 0; rr[3] = -1;
+      }
     }
     if (round < 0) continue;
     // frontend.cpp:243-268: recompute the error only for features flagged outlier, classify, set levels
@@ -573,6 +638,9 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv)
     }
     block_sum<1>(&co, sPart, buf);
     cnt_outliers = (int)co;
+    if constexpr (TRACE) {
+      if (t == 0) tr->round_rec[4 * (round + d.warmup) + 3] = cnt_outliers;
+    }
     if (round == d.rounds - 2) use_kernel = false;             // e->setRobustKernel(nullptr)
   }
 #pragma unroll
@@ -589,8 +657,10 @@ struct PoWorkspace { DevBuf arena; HostBuf stage; };
 namespace {
 
 // the generic kernel (M > 6 x 256 edges: never a front-end's frame) keeps its edges in device memory: one problem per call
+// (warmup, tr: the test hook's -- 0 and nullptr from the entry points; tr's pointers are memory the device can write)
 ssx_status pose_only_generic(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz, const double* uv, int32_t rounds,
-                             int32_t iters, double chi2_th, double huber_delta, uint8_t* inlier_out, int32_t* n_inliers)
+                             int32_t iters, double chi2_th, double huber_delta, uint8_t* inlier_out, int32_t* n_inliers, int32_t warmup,
+                             const PoTrace* tr)
 {
   DevBuf& arena = ctx->po_arena;
   HostBuf& stage = ctx->po_stage;
@@ -613,12 +683,16 @@ ssx_status pose_only_generic(ssx_ctx* ctx, double* pose_io, const double* K4, in
   char* base = arena.as<char>();
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   PoDev d;
-  d.M = M; d.rounds = rounds; d.iters = iters; d.chi2_th = chi2_th; d.huber_delta = huber_delta; d.warmup = 0; d.gate = nullptr;
+  d.M = M; d.rounds = rounds; d.iters = iters; d.chi2_th = chi2_th; d.huber_delta = huber_delta; d.warmup = warmup; d.gate = nullptr;
   d.K = ssx::Cam{K4[0], K4[1], K4[2], K4[3]};
   d.xyz = (const double*)(base + o_xyz); d.uv = (const double*)(base + o_uv);
   d.err = (double*)(base + o_err); d.level = (uint8_t*)(base + o_level); d.outlier = (uint8_t*)(base + o_out);
   d.pose = (double*)(base + o_pose); d.pose_out = (double*)(base + o_pose_out); d.n_inliers = (int*)(base + o_n);
-  SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic, dim3(1), dim3(PT), 0, ctx->stream, d));
+#ifndef SSX_NO_TEST_HOOKS
+  if (tr) hipLaunchKernelGGL((k_pose_only_generic<PoTrace>), dim3(1), dim3(PT), 0, ctx->stream, d, *tr);
+  else
+#endif
+  SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic<>, dim3(1), dim3(PT), 0, ctx->stream, d));
   SSX_HIP_TRY(ctx, hipGetLastError());
   SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_res, base + o_res, sizeof(double) * 8 + sizeof(int) * 2 + (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -627,6 +701,9 @@ ssx_status pose_only_generic(ssx_ctx* ctx, double* pose_io, const double* K4, in
   if (n_inliers) *n_inliers = *reinterpret_cast<int*>(hs + o_n);
   return SSX_OK;
 }
+
+// the batch behind ssx_pose_only_opt_batch (warmup = 0, trace = nullptr) and behind the test hook (trace[j]: the record of job j)
+ssx_status po_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, const PoTrace* trace);
 
 }  // namespace
 
@@ -640,7 +717,7 @@ hipError_t po_launch_device(ssx_ctx* ctx, const PoDeviceJob& j)
   d.xyz = j.xyz; d.uv = j.uv; d.err = j.err; d.level = j.level; d.outlier = j.outlier;
   d.pose = j.pose_in; d.pose_out = j.pose_out; d.n_inliers = j.n_inliers;
   if (j.M > PT * 6) {
-    SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic, dim3(1), dim3(PT), 0, ctx->stream, d));
+    SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic<>, dim3(1), dim3(PT), 0, ctx->stream, d));
     return hipGetLastError();
   }
   // the register-resident kernels read their descriptor from memory (one per workgroup): the pinned block, as the batch does
@@ -656,6 +733,13 @@ hipError_t po_launch_device(ssx_ctx* ctx, const PoDeviceJob& j)
 // n problems in one call (one frame of each of n streams: FrontEnd::EstimateCurrentPose, frontend.cpp:184-300): one workgroup per
 // problem, ONE launch per register class of the kernel.  Per problem the bits of ssx_pose_only_opt (which is a batch of one).
 extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs)
+{
+  return po_batch(ctx, n, jobs, 0, nullptr);
+}
+
+namespace {
+
+ssx_status po_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, const PoTrace* trace)
 {
   if (!ctx || n < 0 || (n > 0 && !jobs)) return SSX_ERR_INVALID_ARG;
   for (int j = 0; j < n; ++j) {
@@ -685,6 +769,7 @@ extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx
         o_out[k] = lay.take(sizeof(double) * 8 + sizeof(int) * 2 + M);
         ++k;
       }
+    const size_t o_tv = lay.take(trace ? sizeof(PoTrace) * nb : 0);   // (nothing for the entry points: their block is as it was)
     HostBuf& stage = ctx->po_stage;
     SSX_HIP_TRY(ctx, stage.reserve(lay.off, 2.0));
     char* hs = stage.as<char>();
@@ -699,8 +784,9 @@ extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx
         memcpy(in + 3 * M, q.uv, sizeof(double) * 2 * M);
         memcpy(in + 5 * M, q.pose_io, sizeof(double) * 7);
         PoDev& d = dv[k];
-        d.M = q.M; d.rounds = q.rounds; d.iters = q.iters; d.chi2_th = q.chi2_th; d.huber_delta = q.huber_delta; d.warmup = 0; d.gate = nullptr;
+        d.M = q.M; d.rounds = q.rounds; d.iters = q.iters; d.chi2_th = q.chi2_th; d.huber_delta = q.huber_delta; d.warmup = warmup; d.gate = nullptr;
         d.K = ssx::Cam{q.K4[0], q.K4[1], q.K4[2], q.K4[3]};
+        if (trace) reinterpret_cast<PoTrace*>(hs + o_tv)[k] = trace[j];
         d.xyz = in; d.uv = in + 3 * M; d.pose = in + 5 * M;
         d.err = nullptr; d.level = nullptr;                          // (the register-resident kernels keep both in registers)
         d.pose_out = reinterpret_cast<double*>(hs + o_out[k]);
@@ -708,10 +794,22 @@ extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx
         d.outlier = reinterpret_cast<uint8_t*>(hs + o_out[k] + sizeof(double) * 8 + sizeof(int) * 2);
         ++k;
       }
+#ifndef SSX_NO_TEST_HOOKS
+    if (trace) {
+      const PoTrace* tv = reinterpret_cast<const PoTrace*>(hs + o_tv);
+      if (!order[0].empty())
+        hipLaunchKernelGGL((k_pose_only<2, const PoTrace*>), dim3((unsigned)order[0].size()), dim3(PT), 0, ctx->stream, (const PoDev*)dv, tv);
+      if (!order[1].empty())
+        hipLaunchKernelGGL((k_pose_only<6, const PoTrace*>), dim3((unsigned)order[1].size()), dim3(PT), 0, ctx->stream, (const PoDev*)(dv + order[0].size()),
+                           tv + order[0].size());
+    } else
+#endif
+    {
     if (!order[0].empty())
       SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<2>, dim3((unsigned)order[0].size()), dim3(PT), 0, ctx->stream, (const PoDev*)dv));
     if (!order[1].empty())
       SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<6>, dim3((unsigned)order[1].size()), dim3(PT), 0, ctx->stream, (const PoDev*)(dv + order[0].size())));
+    }
     SSX_HIP_TRY(ctx, hipGetLastError());
     SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     k = 0;
@@ -729,11 +827,14 @@ extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx
   for (int j = 0; j < n; ++j) {
     const ssx_pose_only_job& q = jobs[j];
     if (q.M <= PT * 6) continue;
-    const ssx_status st = pose_only_generic(ctx, q.pose_io, q.K4, q.M, q.xyz, q.uv, q.rounds, q.iters, q.chi2_th, q.huber_delta, q.inlier_out, q.n_inliers);
+    const ssx_status st = pose_only_generic(ctx, q.pose_io, q.K4, q.M, q.xyz, q.uv, q.rounds, q.iters, q.chi2_th, q.huber_delta, q.inlier_out, q.n_inliers,
+                                            warmup, trace ? trace + j : nullptr);
     if (st != SSX_OK) return st;
   }
   return SSX_OK;
 }
+
+}  // namespace
 
 extern "C" ssx_status ssx_pose_only_opt(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz,
                                         const double* uv, int32_t rounds, int32_t iters, double chi2_th, double huber_delta,
@@ -745,3 +846,44 @@ extern "C" ssx_status ssx_pose_only_opt(ssx_ctx* ctx, double* pose_io, const dou
   q.inlier_out = inlier_out; q.n_inliers = n_inliers;
   return ssx_pose_only_opt_batch(ctx, 1, &q);
 }
+
+#ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h
+// The record lives in one pinned block of this call's own (the kernels write it in place, as they write their results), laid out job
+// after job: (warmup + rounds) * iters slots of chi2, lambda and trials, (warmup + rounds) * 4 ints per job.
+extern "C" ssx_status ssx_pose_only_debug_trace(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, double* it_chi2,
+                                                double* it_lambda, int32_t* it_trials, int32_t* round_rec)
+{
+  if (!ctx || n < 0 || (n > 0 && !jobs) || warmup < 0 || !it_chi2 || !it_lambda || !it_trials || !round_rec) return SSX_ERR_INVALID_ARG;
+  size_t n_it = 0, n_rd = 0;
+  for (int j = 0; j < n; ++j) {
+    if (jobs[j].rounds < 0 || jobs[j].iters < 0) return SSX_ERR_INVALID_ARG;
+    n_it += (size_t)(warmup + jobs[j].rounds) * (size_t)jobs[j].iters;
+    n_rd += (size_t)(warmup + jobs[j].rounds);
+  }
+  if (n == 0) return SSX_OK;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  Layout lay;
+  const size_t o_chi = lay.take(sizeof(double) * n_it), o_lam = lay.take(sizeof(double) * n_it), o_tr = lay.take(sizeof(int) * n_it);
+  const size_t o_rd = lay.take(sizeof(int) * 4 * n_rd);
+  HostBuf rec;
+  hipError_t e = rec.reserve(lay.off + 256);
+  if (e != hipSuccess) { SSX_HIP_TRY(ctx, e); }
+  char* hb = rec.as<char>();
+  memset(hb, 0, lay.off);
+  std::vector<PoTrace> tv((size_t)n);
+  size_t k_it = 0, k_rd = 0;
+  for (int j = 0; j < n; ++j) {
+    tv[j].chi2 = reinterpret_cast<double*>(hb + o_chi) + k_it; tv[j].lambda = reinterpret_cast<double*>(hb + o_lam) + k_it;
+    tv[j].trials = reinterpret_cast<int*>(hb + o_tr) + k_it; tv[j].round_rec = reinterpret_cast<int*>(hb + o_rd) + 4 * k_rd;
+    k_it += (size_t)(warmup + jobs[j].rounds) * (size_t)jobs[j].iters;
+    k_rd += (size_t)(warmup + jobs[j].rounds);
+  }
+  const ssx_status st = po_batch(ctx, n, jobs, warmup, tv.data());        // (synchronises the stream before it returns)
+  if (st == SSX_OK) {
+    memcpy(it_chi2, hb + o_chi, sizeof(double) * n_it); memcpy(it_lambda, hb + o_lam, sizeof(double) * n_it);
+    memcpy(it_trials, hb + o_tr, sizeof(int) * n_it); memcpy(round_rec, hb + o_rd, sizeof(int) * 4 * n_rd);
+  }
+  rec.release();
+  return st;
+}
+#endif  // SSX_NO_TEST_HOOKS
