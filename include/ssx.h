@@ -816,6 +816,64 @@ SSX_API ssx_status ssx_loop_compute_pose(ssx_ctx* ctx, int32_t n_pairs, const do
                                          const double* cur_uv, const double* T_cur, const double* T_loop, const double* K4,
                                          int32_t max_iters, uint32_t seed, uint8_t* kept, ssx_loop_pose_result* out);
 
+/* ------------------------------------------------------------------------------------------------
+ * The geometry of LoopClosing::LoopCorrect (reference: src/ssvio/loopclosing.cpp:353-594) as one call: what the thread does
+ * with need_correct, corrected_pose and relative_to_loop of ssx_loop_compute_pose.  One upload, three short kernel passes around
+ * the optimiser of ssx_pose_graph_opt, one download.  Keyframes and map points are flat arrays; the caller gathers indices for
+ * the reference's pointers.  The pointer-level map fusion of :427-453 moves no number and stays with the caller.
+ *
+ * Stage 1, CorrectActivateKeyframeAndMappoint (:378-425):
+ *   an active keyframe a != cur_kf gets T'_a = (T_a * T_cur^-1) * corrected_pose, grouped as :394-397 group it; T'_cur =
+ *   corrected_pose (:384-385); keyframes that are not active keep their bits (:387 visits the active ones only).
+ *   An active point whose anchor is an active keyframe a gets p' = T'_a^-1 * (T_a * p) (:417-419).  An active point whose anchor
+ *   is -1 or not active is left alone (:413-415).
+ * Stage 2, PoseGraphOptimization (:458-533): exactly ssx_pose_graph_opt(iterations) on the poses stage 1 left, with
+ *   pose_fixed[i] = kf_active[i] | (i == loop_kf) | (i == initial_kf) (:482-486).  When nothing can be optimised -- no free
+ *   keyframe, no edge, iterations <= 0 -- stages 1 and 3 still run, pg.n_iters = 0, and edge_err_out and the statistics are
+ *   not written.
+ * Stage 3 (:537-591): every point with point_active == 0 and anchor a >= 0 gets p' = T_opt_a^-1 * (T_stage1_a * p) (:562-565);
+ *   T_stage1_a is the pose after stage 1 (getPose() at :562), T_opt_a the vertex estimate (:564).  The two-step product is applied
+ *   where the vertex was fixed as well, so such points move by rounding, as the reference's do.  A point with anchor -1 is left
+ *   alone (:556-561).
+ * Poses returned: every keyframe gets the optimiser's estimate (:588) except keep_kf, the front-end's reference keyframe, which
+ *   gets its stage-1 pose (:572-587) while its points were re-anchored with the estimate.
+ * Every product, inverse and action is Sophus' (SE3 operator*, inverse(), operator* on a point: the quaternion re-normalised after
+ * a product and an inverse); T'^-1 is computed once per keyframe, not once per point -- the same function, the same bits.
+ *
+ * SSX_ERR_INVALID_ARG: a null array that is needed (points, point_anchor, point_active may be null when n_points == 0, the edge
+ *   arrays when n_edges == 0), n_keyframes < 1, cur_kf or loop_kf outside [0, n_keyframes), initial_kf or keep_kf outside
+ *   [-1, n_keyframes), an edge index or a point_anchor out of range, and kf_active[cur_kf] == 0: the reference sets poses for
+ *   active keyframes only (:422-425), and a current keyframe outside the window is not a case ssvio produces.
+ * SSX_ERR_UNSUPPORTED: more than 2048 free keyframes, as for ssx_pose_graph_opt.
+ * On any failure poses, points and the optional outputs are untouched: they are written after the final synchronisation only.
+ * Inputs must be finite.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct ssx_loop_correct_problem {
+  int32_t n_keyframes, n_edges, n_points;
+  int32_t cur_kf, loop_kf;        /* indices into poses: current_keyframe_, loop_keyframe_ */
+  int32_t initial_kf;             /* keyframe id 0 (:483), -1 = none */
+  int32_t keep_kf;                /* the front-end's reference keyframe (:568-572), -1 = none */
+  double* poses;                  /* n_keyframes x 7 (qx qy qz qw tx ty tz, T_cw), in/out */
+  const uint8_t* kf_active;       /* n_keyframes: in Map::GetActiveKeyFrames() */
+  const double* corrected_pose;   /* 7: corrected_current_pose_ */
+  const int32_t* edge_i; const int32_t* edge_j; const double* edge_meas;   /* as ssx_pose_graph_problem (:492-529) */
+  double* points;                 /* n_points x 3, in/out */
+  const int32_t* point_anchor;    /* n_points: keyframe index the point is re-anchored to, -1 = leave the point alone.
+                                     Active point: GetActiveObservations().front() (:408); other: GetObservations().front() (:554) */
+  const uint8_t* point_active;    /* n_points: in Map::GetActiveMapPoints() (:402, :543-547) */
+  double* stage1_poses_out;       /* optional n_keyframes x 7: the poses after CorrectActivateKeyframeAndMappoint (:422-425) */
+  double* edge_err_out; int32_t stats_cap; double* stats_chi2; double* stats_lambda; int32_t* stats_trials;  /* as the pose graph's */
+} ssx_loop_correct_problem;
+typedef struct ssx_loop_correct_result {
+  ssx_pose_graph_result pg;       /* stage 2 */
+  int32_t n_active_kf;            /* keyframes moved by stage 1 */
+  int32_t n_active_points_moved;  /* stage 1 (:417-419) */
+  int32_t n_other_points_moved;   /* stage 3 (:562-565) */
+  int32_t n_points_skipped;       /* left alone by both stages (:413-415, :556-561): n_points minus the two above */
+} ssx_loop_correct_result;
+SSX_API ssx_status ssx_loop_correct(ssx_ctx* ctx, const ssx_loop_correct_problem* prob, int32_t iterations,
+                                    ssx_loop_correct_result* res);
+
 #ifdef __cplusplus
 }
 #endif

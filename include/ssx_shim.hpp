@@ -428,6 +428,40 @@ inline CorrectPoseResult ComputeCorrectPose(Context& ctx, const std::vector<Loop
   return out;
 }
 
+// void LoopClosing::LoopCorrect() (loopclosing.cpp:353-594) without its pointer-level map fusion (:427-453, which moves no number):
+// CorrectActivateKeyframeAndMappoint, PoseGraphOptimization and the re-anchoring of every map point, over ssx_loop_correct.
+// The caller gathers indices for the reference's pointers: a row per keyframe of Map::GetAllKeyFrames() and a row per map point of
+// Map::GetAllMapPoints().  poses and points are corrected in place; the caller writes them back with SetPose / SetPosition.
+struct LoopCorrectInput {
+  std::vector<double> poses;            // 7 per keyframe: getPose().data()
+  std::vector<uint8_t> kf_active;       // Map::GetActiveKeyFrames().count(id)
+  int cur_kf = -1, loop_kf = -1;        // rows of current_keyframe_, loop_keyframe_
+  int initial_kf = -1;                  // row of key_frame_id_ == 0 (:483), -1 when it is not in the map
+  int keep_kf = -1;                     // row of frontend_->getReferenceKF() (:568), -1 when it is not in the map
+  double corrected_current_pose[7] = {0, 0, 0, 1, 0, 0, 0};
+  std::vector<int32_t> edge_i, edge_j;  // as for ssx_pose_graph_opt (:492-529)
+  std::vector<double> edge_meas;        // 7 per edge
+  std::vector<double> points;           // 3 per map point: getPosition()
+  std::vector<int32_t> point_anchor;    // row of GetActiveObservations().front()'s keyframe for an active point (:408), of
+                                        // GetObservations().front()'s otherwise (:554); -1 when that keyframe has no row (:556-561)
+  std::vector<uint8_t> point_active;    // Map::GetActiveMapPoints().count(id)
+};
+inline ssx_loop_correct_result LoopCorrect(Context& ctx, LoopCorrectInput& in, int iterations = 20)
+{
+  const size_t n = in.kf_active.size(), e = in.edge_i.size(), m = in.point_anchor.size();
+  if (in.poses.size() != 7 * n || in.edge_j.size() != e || in.edge_meas.size() != 7 * e || in.points.size() != 3 * m || in.point_active.size() != m)
+    throw std::invalid_argument("LoopCorrect: array sizes disagree");
+  ssx_loop_correct_problem p{};
+  p.n_keyframes = (int32_t)n; p.n_edges = (int32_t)e; p.n_points = (int32_t)m;
+  p.cur_kf = in.cur_kf; p.loop_kf = in.loop_kf; p.initial_kf = in.initial_kf; p.keep_kf = in.keep_kf;
+  p.poses = in.poses.data(); p.kf_active = in.kf_active.data(); p.corrected_pose = in.corrected_current_pose;
+  p.edge_i = in.edge_i.data(); p.edge_j = in.edge_j.data(); p.edge_meas = in.edge_meas.data();
+  p.points = in.points.data(); p.point_anchor = in.point_anchor.data(); p.point_active = in.point_active.data();
+  ssx_loop_correct_result r;
+  ctx.check(ssx_loop_correct(ctx.get(), &p, iterations, &r));
+  return r;
+}
+
 // int LoopClosing::OptimizeCurrentPose() (loopclosing.cpp:245-351) on its own: every match must have its map point.
 // corrected_current_pose is refined in place, the matches that end as outliers are erased; returns what is left (cnt_inliner).
 inline int OptimizeCurrentPose(Context& ctx, std::vector<LoopMatch>& matches, double corrected_current_pose[7], const double K4[4])

@@ -166,47 +166,55 @@ __global__ __launch_bounds__(CH) void k_pg_reduce(BaDev d, PgDev g, int slot, in
   }
 }
 
-}  // namespace
+// ---- the host side of a pose graph, shared by ssx_pose_graph_opt and ssx_loop_correct (loop_correct.inc) ----
+// pg_plan      the block lists of the graph and the offsets of its inputs in the staging blob; a caller with inputs of its own takes
+//              them from `in` afterwards, so that everything goes up in ONE copy
+// pg_layout    the working buffers behind the inputs (`all`; a caller takes its own behind them)
+// pg_stage     the inputs into the pinned staging blob
+// pg_wire      device pointers (no stream operation)
+// pg_lm_loop   the solver's lists, then OptimizationAlgorithmLevenberg::solve per iteration; returns the buffer the state lies in
+struct PgPlan {
+  int P = 0, E = 0, nP = 0, nBlk = 0, band_w = 1, n = 0, n_pad = 0;
+  bool use_bcr = false;
+  std::vector<int> pose_free, blk_pa, blk_pb, blk_ptr, blk_item, g_ptr, g_item;
+  std::vector<uint8_t> active;
+  BcrPlan bcrp;
+  size_t sb_count = 0;
+  Layout in, all;
+  size_t in_bytes = 0;
+  size_t o_pose0, o_meas, o_pf, o_ei, o_ej, o_act, o_bpa, o_bpb, o_bptr, o_bit, o_gptr, o_git, o_bcr_p0, o_bcr_elim;
+  size_t o_pose1, o_eblk, o_err, o_maxd, o_iter, o_S, o_x, o_Sb, o_bcr_mem, o_Ld, o_invd, o_Ninv, o_sp, o_xp, o_scal;
+};
+struct PgRun {
+  BaDev d{};
+  PgDev g{};
+  BigDev bd{};
+  BandDev bnd{};
+};
+struct PgStats {                      // where the per-iteration statistics go (each nullable)
+  int cap = 0;
+  double* chi2 = nullptr; double* lambda = nullptr; int32_t* trials = nullptr;
+};
 
-extern "C" {
-
-ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, int32_t iterations, ssx_pose_graph_result* res)
+// host lists: non-zero blocks (diagonal first) with their contributing (edge, kind) in edge order.  pose_fixed [P]; nP >= 1, E >= 1
+static void pg_plan(PgPlan& pl, int P, int E, const uint8_t* pose_fixed, const int32_t* edge_i, const int32_t* edge_j)
 {
-  if (!ctx || !prob || !res || prob->n_poses < 1 || prob->n_edges < 0 || !prob->poses || !prob->pose_fixed ||
-      (prob->n_edges > 0 && (!prob->edge_i || !prob->edge_j || !prob->edge_meas)))
-    return SSX_ERR_INVALID_ARG;
-  const int P = prob->n_poses, E = prob->n_edges;
-  std::vector<int> pose_free(P, -1);
+  pl.P = P; pl.E = E;
+  pl.pose_free.assign(P, -1);
   int nP = 0;
-  for (int i = 0; i < P; ++i) if (!prob->pose_fixed[i]) pose_free[i] = nP++;
-  res->n_iters = 0; res->chi2_initial = 0.0; res->chi2_final = 0.0; res->stats_n = 0;
-  for (int k = 0; k < E; ++k)
-    if (prob->edge_i[k] < 0 || prob->edge_i[k] >= P || prob->edge_j[k] < 0 || prob->edge_j[k] >= P) {
-      ctx->set_error("ssx_pose_graph_opt: edge %d references a keyframe outside [0, %d)", k, P);
-      return SSX_ERR_INVALID_ARG;
-    }
-  if (nP == 0 || E == 0) return SSX_OK;                        // nothing to optimise (g2o: optimize() returns -1)
-  if (nP > 2048) { ctx->set_error("ssx_pose_graph_opt: %d free keyframes exceed the supported 2048", nP); return SSX_ERR_UNSUPPORTED; }
-  BaWorkspace* ws = ba_workspace(ctx);
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // ---- host lists: non-zero blocks (diagonal first) with their contributing (edge, kind) in edge order ----
-  std::vector<uint8_t> active(E);
-  std::vector<int> blk_pa, blk_pb;
+  for (int i = 0; i < P; ++i) if (!pose_fixed[i]) pl.pose_free[i] = nP++;
+  pl.nP = nP;
+  const std::vector<int>& pose_free = pl.pose_free;
+  std::vector<uint8_t>& active = pl.active;
+  std::vector<int>& blk_pa = pl.blk_pa; std::vector<int>& blk_pb = pl.blk_pb;
+  active.assign(E, 0);
   for (int p = 0; p < nP; ++p) { blk_pa.push_back(p); blk_pb.push_back(p); }
   std::vector<std::vector<int>> items(nP), gitems(nP);
-  std::vector<long long> offkey;                               // pa * nP + pb -> block id, kept sorted by creation
-  std::vector<int> offid;
-  auto find_block = [&](int pa, int pb) -> int {
-    const long long key = (long long)pa * nP + pb;
-    for (size_t k = 0; k < offkey.size(); ++k) if (offkey[k] == key) return offid[k];
-    return -1;
-  };
   // (a keyframe has at most a handful of edges, but a linear search over all off-diagonal blocks would be
   //  quadratic: index them per smaller pose instead)
   std::vector<std::vector<std::pair<int, int>>> off_of(nP);   // pa -> (pb, block id)
-  (void)find_block;
   for (int k = 0; k < E; ++k) {
-    const int a = pose_free[prob->edge_i[k]], c = pose_free[prob->edge_j[k]];
+    const int a = pose_free[edge_i[k]], c = pose_free[edge_j[k]];
     active[k] = (a >= 0 || c >= 0);
     if (a >= 0) { items[a].push_back(k * 4 + 0); gitems[a].push_back(k * 2 + 0); }
     if (c >= 0) { items[c].push_back(k * 4 + 1); gitems[c].push_back(k * 2 + 1); }
@@ -226,81 +234,102 @@ ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, 
       items[a].push_back(k * 4 + 2); items[a].push_back(k * 4 + 3);
     }
   }
-  const int nBlk = (int)blk_pa.size();
-  std::vector<int> blk_ptr(nBlk + 1, 0), blk_item, g_ptr(nP + 1, 0), g_item;
-  for (int q = 0; q < nBlk; ++q) { for (int it : items[q]) blk_item.push_back(it); blk_ptr[q + 1] = (int)blk_item.size(); }
-  for (int p = 0; p < nP; ++p) { for (int it : gitems[p]) g_item.push_back(it); g_ptr[p + 1] = (int)g_item.size(); }
+  const int nBlk = pl.nBlk = (int)blk_pa.size();
+  pl.blk_ptr.assign(nBlk + 1, 0); pl.g_ptr.assign(nP + 1, 0);
+  for (int q = 0; q < nBlk; ++q) { for (int it : items[q]) pl.blk_item.push_back(it); pl.blk_ptr[q + 1] = (int)pl.blk_item.size(); }
+  for (int p = 0; p < nP; ++p) { for (int it : gitems[p]) pl.g_item.push_back(it); pl.g_ptr[p + 1] = (int)pl.g_item.size(); }
   // the band of the free keyframes' couplings: <= BAND_WMAX positions -> block cyclic reduction (SSX_PG_TILES: the tile solver, for A/B)
   int band_w = 1;
   for (int q = nP; q < nBlk; ++q) band_w = std::max(band_w, blk_pb[q] - blk_pa[q]);
-  BcrPlan bcrp;
+  pl.band_w = band_w;
   static const bool pg_tiles_env = getenv("SSX_PG_TILES") != nullptr;
-  if (band_w <= BAND_WMAX && !pg_tiles_env) plan_bcr(nP, band_w, bcrp);
-  const bool use_bcr = bcrp.on != 0;
-  // ---- device memory ----
-  const int n = 6 * nP, n_pad = ((n + NB - 1) / NB) * NB;
-  Layout in;
-  const size_t o_pose0 = in.take(sizeof(double) * 7 * P), o_meas = in.take(sizeof(double) * 7 * (size_t)E);
-  const size_t o_pf = in.take(sizeof(int) * P), o_ei = in.take(sizeof(int) * E), o_ej = in.take(sizeof(int) * E);
-  const size_t o_act = in.take((size_t)E);
-  const size_t o_bpa = in.take(sizeof(int) * nBlk), o_bpb = in.take(sizeof(int) * nBlk), o_bptr = in.take(sizeof(int) * (nBlk + 1));
-  const size_t o_bit = in.take(sizeof(int) * (blk_item.size() + 1)), o_gptr = in.take(sizeof(int) * (nP + 1)), o_git = in.take(sizeof(int) * (g_item.size() + 1));
-  const size_t o_bcr_p0 = in.take(use_bcr ? sizeof(int) * (bcrp.p0.size() + 1) : 0), o_bcr_elim = in.take(use_bcr ? sizeof(int) * (bcrp.elim.size() + 4) : 0);
-  const size_t in_bytes = in.off;
-  Layout all = in;
-  const size_t o_pose1 = all.take(sizeof(double) * 7 * P);
-  const size_t o_eblk = all.take(sizeof(double) * PG_EBLK * (size_t)E), o_err = all.take(sizeof(double) * 6 * (size_t)E);
-  const size_t o_maxd = all.take(sizeof(double) * nP), o_iter = all.take(sizeof(double) * ((size_t)nP * 27 + 8));
-  const size_t o_S = all.take(use_bcr ? 256 : sizeof(double) * (size_t)(n_pad + NB) * n_pad), o_x = all.take(sizeof(double) * (n_pad + 8));
-  const size_t sb_count = use_bcr ? band_rhs_doubles(nP, band_w) : 0;
-  const size_t o_Sb = all.take(sizeof(double) * (sb_count + 1)), o_bcr_mem = all.take(use_bcr ? sizeof(double) * (bcr_mem_doubles(bcrp.N, bcrp.m) + 8) : 256);
-  const size_t o_Ld = all.take(sizeof(double) * NB * NB), o_invd = all.take(sizeof(double) * (n_pad + 8)), o_Ninv = all.take(sizeof(double) * 4 * 256);
-  const size_t o_sp = all.take(sizeof(double) * 64), o_xp = all.take(sizeof(double) * (n + 1)), o_scal = all.take(sizeof(double) * SC_N);
-  SSX_HIP_TRY(ctx, ws->arena.reserve(all.off));
-  SSX_HIP_TRY(ctx, ws->stage.reserve(std::max(in_bytes, sizeof(double) * (7 * (size_t)P + 6 * (size_t)E))));
-  SSX_HIP_TRY(ctx, ws->scal.reserve(sizeof(double) * SC_N));
-  char* hs = ws->stage.as<char>();
-  memcpy(hs + o_pose0, prob->poses, sizeof(double) * 7 * P);
-  memcpy(hs + o_meas, prob->edge_meas, sizeof(double) * 7 * (size_t)E);
-  memcpy(hs + o_pf, pose_free.data(), sizeof(int) * P);
-  memcpy(hs + o_ei, prob->edge_i, sizeof(int) * E); memcpy(hs + o_ej, prob->edge_j, sizeof(int) * E);
-  memcpy(hs + o_act, active.data(), (size_t)E);
-  memcpy(hs + o_bpa, blk_pa.data(), sizeof(int) * nBlk); memcpy(hs + o_bpb, blk_pb.data(), sizeof(int) * nBlk);
-  memcpy(hs + o_bptr, blk_ptr.data(), sizeof(int) * (nBlk + 1)); memcpy(hs + o_bit, blk_item.data(), sizeof(int) * blk_item.size());
-  memcpy(hs + o_gptr, g_ptr.data(), sizeof(int) * (nP + 1)); memcpy(hs + o_git, g_item.data(), sizeof(int) * g_item.size());
-  if (use_bcr) { memcpy(hs + o_bcr_p0, bcrp.p0.data(), sizeof(int) * bcrp.p0.size()); memcpy(hs + o_bcr_elim, bcrp.elim.data(), sizeof(int) * bcrp.elim.size()); }
-  char* base = ws->arena.as<char>();
-  hipStream_t s = ctx->stream;
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, s));
-  BaDev d{};
+  if (band_w <= BAND_WMAX && !pg_tiles_env) plan_bcr(nP, band_w, pl.bcrp);
+  pl.use_bcr = pl.bcrp.on != 0;
+  pl.n = 6 * nP; pl.n_pad = ((pl.n + NB - 1) / NB) * NB;
+  Layout& in = pl.in;
+  pl.o_pose0 = in.take(sizeof(double) * 7 * P); pl.o_meas = in.take(sizeof(double) * 7 * (size_t)E);
+  pl.o_pf = in.take(sizeof(int) * P); pl.o_ei = in.take(sizeof(int) * E); pl.o_ej = in.take(sizeof(int) * E);
+  pl.o_act = in.take((size_t)E);
+  pl.o_bpa = in.take(sizeof(int) * nBlk); pl.o_bpb = in.take(sizeof(int) * nBlk); pl.o_bptr = in.take(sizeof(int) * (nBlk + 1));
+  pl.o_bit = in.take(sizeof(int) * (pl.blk_item.size() + 1)); pl.o_gptr = in.take(sizeof(int) * (nP + 1)); pl.o_git = in.take(sizeof(int) * (pl.g_item.size() + 1));
+  pl.o_bcr_p0 = in.take(pl.use_bcr ? sizeof(int) * (pl.bcrp.p0.size() + 1) : 0); pl.o_bcr_elim = in.take(pl.use_bcr ? sizeof(int) * (pl.bcrp.elim.size() + 4) : 0);
+}
+
+static void pg_layout(PgPlan& pl)
+{
+  const int P = pl.P, E = pl.E, nP = pl.nP, n = pl.n, n_pad = pl.n_pad;
+  const bool use_bcr = pl.use_bcr;
+  pl.in_bytes = pl.in.off;
+  pl.all = pl.in;
+  Layout& all = pl.all;
+  pl.o_pose1 = all.take(sizeof(double) * 7 * P);
+  pl.o_eblk = all.take(sizeof(double) * PG_EBLK * (size_t)E); pl.o_err = all.take(sizeof(double) * 6 * (size_t)E);
+  pl.o_maxd = all.take(sizeof(double) * nP); pl.o_iter = all.take(sizeof(double) * ((size_t)nP * 27 + 8));
+  pl.o_S = all.take(use_bcr ? 256 : sizeof(double) * (size_t)(n_pad + NB) * n_pad); pl.o_x = all.take(sizeof(double) * (n_pad + 8));
+  pl.sb_count = use_bcr ? band_rhs_doubles(nP, pl.band_w) : 0;
+  pl.o_Sb = all.take(sizeof(double) * (pl.sb_count + 1)); pl.o_bcr_mem = all.take(use_bcr ? sizeof(double) * (bcr_mem_doubles(pl.bcrp.N, pl.bcrp.m) + 8) : 256);
+  pl.o_Ld = all.take(sizeof(double) * NB * NB); pl.o_invd = all.take(sizeof(double) * (n_pad + 8)); pl.o_Ninv = all.take(sizeof(double) * 4 * 256);
+  pl.o_sp = all.take(sizeof(double) * 64); pl.o_xp = all.take(sizeof(double) * (n + 1)); pl.o_scal = all.take(sizeof(double) * SC_N);
+}
+
+static void pg_stage(const PgPlan& pl, char* hs, const double* poses, const int32_t* edge_i, const int32_t* edge_j, const double* edge_meas)
+{
+  const int P = pl.P, E = pl.E, nP = pl.nP, nBlk = pl.nBlk;
+  memcpy(hs + pl.o_pose0, poses, sizeof(double) * 7 * P);
+  memcpy(hs + pl.o_meas, edge_meas, sizeof(double) * 7 * (size_t)E);
+  memcpy(hs + pl.o_pf, pl.pose_free.data(), sizeof(int) * P);
+  memcpy(hs + pl.o_ei, edge_i, sizeof(int) * E); memcpy(hs + pl.o_ej, edge_j, sizeof(int) * E);
+  memcpy(hs + pl.o_act, pl.active.data(), (size_t)E);
+  memcpy(hs + pl.o_bpa, pl.blk_pa.data(), sizeof(int) * nBlk); memcpy(hs + pl.o_bpb, pl.blk_pb.data(), sizeof(int) * nBlk);
+  memcpy(hs + pl.o_bptr, pl.blk_ptr.data(), sizeof(int) * (nBlk + 1)); memcpy(hs + pl.o_bit, pl.blk_item.data(), sizeof(int) * pl.blk_item.size());
+  memcpy(hs + pl.o_gptr, pl.g_ptr.data(), sizeof(int) * (nP + 1)); memcpy(hs + pl.o_git, pl.g_item.data(), sizeof(int) * pl.g_item.size());
+  if (pl.use_bcr) { memcpy(hs + pl.o_bcr_p0, pl.bcrp.p0.data(), sizeof(int) * pl.bcrp.p0.size()); memcpy(hs + pl.o_bcr_elim, pl.bcrp.elim.data(), sizeof(int) * pl.bcrp.elim.size()); }
+}
+
+static void pg_wire(const PgPlan& pl, char* base, PgRun& r)
+{
+  const int P = pl.P, E = pl.E, nP = pl.nP;
+  BaDev& d = r.d;
   d.P = P; d.nP = nP;
-  d.pose_free = (const int*)(base + o_pf);
-  d.pose[0] = (double*)(base + o_pose0); d.pose[1] = (double*)(base + o_pose1);
-  d.iter_comm = (double*)(base + o_iter); d.xp = (double*)(base + o_xp); d.scal = (double*)(base + o_scal);
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(d.pose[1], d.pose[0], sizeof(double) * 7 * P, hipMemcpyDeviceToDevice, s));   // fixed keyframes
-  PgDev g{};
-  g.P = P; g.E = E; g.nP = nP; g.nBlk = nBlk;
-  g.ei = (const int*)(base + o_ei); g.ej = (const int*)(base + o_ej); g.meas = (const double*)(base + o_meas);
-  g.active = (const uint8_t*)(base + o_act);
-  g.eblk = (double*)(base + o_eblk); g.err = (double*)(base + o_err); g.maxd = (double*)(base + o_maxd);
-  g.blk_pa = (const int*)(base + o_bpa); g.blk_pb = (const int*)(base + o_bpb); g.blk_ptr = (const int*)(base + o_bptr);
-  g.blk_item = (const int*)(base + o_bit); g.g_ptr = (const int*)(base + o_gptr); g.g_item = (const int*)(base + o_git);
-  BigDev bd{};
-  bd.n = n; bd.n_pad = n_pad; bd.ld = n_pad; bd.T = n_pad / NB;
-  bd.S = (double*)(base + o_S); bd.x = (double*)(base + o_x); bd.Ld = (double*)(base + o_Ld);
-  bd.invd = (double*)(base + o_invd); bd.Ninv = (double*)(base + o_Ninv); bd.scale_part = (double*)(base + o_sp);
+  d.pose_free = (const int*)(base + pl.o_pf);
+  d.pose[0] = (double*)(base + pl.o_pose0); d.pose[1] = (double*)(base + pl.o_pose1);
+  d.iter_comm = (double*)(base + pl.o_iter); d.xp = (double*)(base + pl.o_xp); d.scal = (double*)(base + pl.o_scal);
+  PgDev& g = r.g;
+  g.P = P; g.E = E; g.nP = nP; g.nBlk = pl.nBlk;
+  g.ei = (const int*)(base + pl.o_ei); g.ej = (const int*)(base + pl.o_ej); g.meas = (const double*)(base + pl.o_meas);
+  g.active = (const uint8_t*)(base + pl.o_act);
+  g.eblk = (double*)(base + pl.o_eblk); g.err = (double*)(base + pl.o_err); g.maxd = (double*)(base + pl.o_maxd);
+  g.blk_pa = (const int*)(base + pl.o_bpa); g.blk_pb = (const int*)(base + pl.o_bpb); g.blk_ptr = (const int*)(base + pl.o_bptr);
+  g.blk_item = (const int*)(base + pl.o_bit); g.g_ptr = (const int*)(base + pl.o_gptr); g.g_item = (const int*)(base + pl.o_git);
+  BigDev& bd = r.bd;
+  bd.n = pl.n; bd.n_pad = pl.n_pad; bd.ld = pl.n_pad; bd.T = pl.n_pad / NB;
+  bd.S = (double*)(base + pl.o_S); bd.x = (double*)(base + pl.o_x); bd.Ld = (double*)(base + pl.o_Ld);
+  bd.invd = (double*)(base + pl.o_invd); bd.Ninv = (double*)(base + pl.o_Ninv); bd.scale_part = (double*)(base + pl.o_sp);
+  BandDev& bnd = r.bnd;
+  if (pl.use_bcr) {
+    bnd.on = 1; bnd.w = pl.band_w; bnd.K = 1; bnd.nP = nP;
+    bnd.Sb = (double*)(base + pl.o_Sb); bnd.bsv = bnd.Sb + band_doubles(nP, pl.band_w);
+    bnd.bcr.p0 = (const int*)(base + pl.o_bcr_p0); bnd.bcr.elim = (const int4*)(base + pl.o_bcr_elim);
+    bcr_carve(bnd.bcr, (double*)(base + pl.o_bcr_mem), pl.bcrp.N, pl.bcrp.m);
+  }
+}
+
+// the state is r.d.pose[0] with its copy in r.d.pose[1] (the fixed keyframes); *cur_out = the buffer the accepted state lies in
+static ssx_status pg_lm_loop(ssx_ctx* ctx, BaWorkspace* ws, const PgPlan& pl, PgRun& run, int iterations, const PgStats& so,
+                             ssx_pose_graph_result* res, int* cur_out)
+{
+  const int P = pl.P, E = pl.E, nBlk = pl.nBlk;
+  const bool use_bcr = pl.use_bcr;
+  const BcrPlan& bcrp = pl.bcrp;
+  const size_t sb_count = pl.sb_count;
+  BaDev& d = run.d; PgDev& g = run.g; BigDev& bd = run.bd; BandDev& bnd = run.bnd;
+  hipStream_t s = ctx->stream;
   Comm cm;                                                    // single GPU: the graph is tiny next to a BA
   std::vector<int> tl_row_cnt, tl_pair_cnt;
   std::vector<uint8_t> tl_next_diag;
   ssx_status st = SSX_OK;
-  BandDev bnd{};
-  if (use_bcr) {
-    bnd.on = 1; bnd.w = band_w; bnd.K = 1; bnd.nP = nP;
-    bnd.Sb = (double*)(base + o_Sb); bnd.bsv = bnd.Sb + band_doubles(nP, band_w);
-    bnd.bcr.p0 = (const int*)(base + o_bcr_p0); bnd.bcr.elim = (const int4*)(base + o_bcr_elim);
-    bcr_carve(bnd.bcr, (double*)(base + o_bcr_mem), bcrp.N, bcrp.m);
-  } else {
-    st = build_tile_lists(ctx, ws, blk_pa, blk_pb, cm, bd, tl_row_cnt, tl_pair_cnt, tl_next_diag);
+  if (!use_bcr) {
+    st = build_tile_lists(ctx, ws, pl.blk_pa, pl.blk_pb, cm, bd, tl_row_cnt, tl_pair_cnt, tl_next_diag);
     if (st != SSX_OK) return st;
   }
   double* hscal = ws->scal.as<double>();
@@ -390,19 +419,64 @@ ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, 
       qmax++;
     } while (rho < 0 && qmax < 10);
     res->n_iters = it + 1;
-    if (res->stats_n < prob->stats_cap) {
+    if (res->stats_n < so.cap) {
       const int k = res->stats_n;
-      if (prob->stats_chi2) prob->stats_chi2[k] = hscal[SC_TEMP_CHI];   // chi2 of the last evaluation, as g2o reports it
-      if (prob->stats_lambda) prob->stats_lambda[k] = lambda;
-      if (prob->stats_trials) prob->stats_trials[k] = qmax;
+      if (so.chi2) so.chi2[k] = hscal[SC_TEMP_CHI];   // chi2 of the last evaluation, as g2o reports it
+      if (so.lambda) so.lambda[k] = lambda;
+      if (so.trials) so.trials[k] = qmax;
       res->stats_n = k + 1;
     }
     res->chi2_final = currentChi;
     if (qmax == 10 || rho == 0 || lambda_bad) break;
   }
+  *cur_out = cur;
+  return SSX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+ssx_status ssx_pose_graph_opt(ssx_ctx* ctx, const ssx_pose_graph_problem* prob, int32_t iterations, ssx_pose_graph_result* res)
+{
+  if (!ctx || !prob || !res || prob->n_poses < 1 || prob->n_edges < 0 || !prob->poses || !prob->pose_fixed ||
+      (prob->n_edges > 0 && (!prob->edge_i || !prob->edge_j || !prob->edge_meas)))
+    return SSX_ERR_INVALID_ARG;
+  const int P = prob->n_poses, E = prob->n_edges;
+  int nP = 0;
+  for (int i = 0; i < P; ++i) if (!prob->pose_fixed[i]) nP++;
+  res->n_iters = 0; res->chi2_initial = 0.0; res->chi2_final = 0.0; res->stats_n = 0;
+  for (int k = 0; k < E; ++k)
+    if (prob->edge_i[k] < 0 || prob->edge_i[k] >= P || prob->edge_j[k] < 0 || prob->edge_j[k] >= P) {
+      ctx->set_error("ssx_pose_graph_opt: edge %d references a keyframe outside [0, %d)", k, P);
+      return SSX_ERR_INVALID_ARG;
+    }
+  if (nP == 0 || E == 0) return SSX_OK;                        // nothing to optimise (g2o: optimize() returns -1)
+  if (nP > 2048) { ctx->set_error("ssx_pose_graph_opt: %d free keyframes exceed the supported 2048", nP); return SSX_ERR_UNSUPPORTED; }
+  BaWorkspace* ws = ba_workspace(ctx);
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  PgPlan pl;
+  pg_plan(pl, P, E, prob->pose_fixed, prob->edge_i, prob->edge_j);
+  pg_layout(pl);
+  SSX_HIP_TRY(ctx, ws->arena.reserve(pl.all.off));
+  SSX_HIP_TRY(ctx, ws->stage.reserve(std::max(pl.in_bytes, sizeof(double) * (7 * (size_t)P + 6 * (size_t)E))));
+  SSX_HIP_TRY(ctx, ws->scal.reserve(sizeof(double) * SC_N));
+  char* hs = ws->stage.as<char>();
+  pg_stage(pl, hs, prob->poses, prob->edge_i, prob->edge_j, prob->edge_meas);
+  char* base = ws->arena.as<char>();
+  hipStream_t s = ctx->stream;
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, pl.in_bytes, hipMemcpyHostToDevice, s));
+  PgRun run;
+  pg_wire(pl, base, run);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(run.d.pose[1], run.d.pose[0], sizeof(double) * 7 * P, hipMemcpyDeviceToDevice, s));   // fixed keyframes
+  PgStats so;
+  so.cap = prob->stats_cap; so.chi2 = prob->stats_chi2; so.lambda = prob->stats_lambda; so.trials = prob->stats_trials;
+  int cur = 0;
+  const ssx_status st = pg_lm_loop(ctx, ws, pl, run, iterations, so, res, &cur);
+  if (st != SSX_OK) return st;
   // results: the accepted state, and the edges' errors of the last evaluation (what g2o leaves in _error)
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs, d.pose[cur], sizeof(double) * 7 * P, hipMemcpyDeviceToHost, s));
-  if (prob->edge_err_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + sizeof(double) * 7 * P, g.err, sizeof(double) * 6 * (size_t)E, hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs, run.d.pose[cur], sizeof(double) * 7 * P, hipMemcpyDeviceToHost, s));
+  if (prob->edge_err_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + sizeof(double) * 7 * P, run.g.err, sizeof(double) * 6 * (size_t)E, hipMemcpyDeviceToHost, s));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
   memcpy(prob->poses, hs, sizeof(double) * 7 * P);
   if (prob->edge_err_out) memcpy(prob->edge_err_out, hs + sizeof(double) * 7 * P, sizeof(double) * 6 * (size_t)E);

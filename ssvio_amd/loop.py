@@ -6,7 +6,10 @@ KeyframeDatabase       ssx_kfdb_*: AddToKeyframeDatabase, DetectLoop and MatchFe
 pnp_ransac             ssx_pnp_ransac: the cv::solvePnPRansac call of ComputeCorrectPose (:205-206) under the contract of
                        tools/pnp_model.py
 loop_pose_opt          ssx_loop_pose_opt: OptimizeCurrentPose (:245-351)
-compute_correct_pose   ssx_loop_compute_pose: ComputeCorrectPose (:147-243) as a whole"""
+compute_correct_pose   ssx_loop_compute_pose: ComputeCorrectPose (:147-243) as a whole
+loop_correct           ssx_loop_correct: the geometry of LoopCorrect (:353-594) -- the active window moved with the corrected current
+                       keyframe, the pose-graph optimisation, every map point re-anchored -- under the contract of
+                       tools/loop_correct_model.py"""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import KP_DTYPE, SSX_ERR_CAPACITY, Context, OrbParams, dbl_p, i32_p, ptr, u8_p
+from .ba import PoseGraphResult
 
 i64_p = C.POINTER(C.c_int64)
 
@@ -260,3 +264,62 @@ def compute_correct_pose(ctx: Context, loop_xyz, has_point, cur_uv, T_cur, T_loo
     return dict(verdict=r.verdict, ok=r.verdict == LOOP_OK, kept=kept[:n], corrected_pose=np.array(r.corrected_pose), error=r.error,
                 need_correct=bool(r.need_correct), relative_to_loop=np.array(r.relative_to_loop), n_with_point=r.n_with_point,
                 n_ransac_inliers=r.n_ransac_inliers, n_inliers=r.n_inliers, best=r.best_hypothesis)
+
+
+class LoopCorrectProblem(C.Structure):
+    """ssx_loop_correct_problem"""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_edges", C.c_int32), ("n_points", C.c_int32), ("cur_kf", C.c_int32), ("loop_kf", C.c_int32),
+                ("initial_kf", C.c_int32), ("keep_kf", C.c_int32), ("poses", dbl_p), ("kf_active", u8_p), ("corrected_pose", dbl_p),
+                ("edge_i", i32_p), ("edge_j", i32_p), ("edge_meas", dbl_p), ("points", dbl_p), ("point_anchor", i32_p), ("point_active", u8_p),
+                ("stage1_poses_out", dbl_p), ("edge_err_out", dbl_p), ("stats_cap", C.c_int32), ("stats_chi2", dbl_p), ("stats_lambda", dbl_p),
+                ("stats_trials", i32_p)]
+
+
+class LoopCorrectResult(C.Structure):
+    """ssx_loop_correct_result"""
+    _fields_ = [("pg", PoseGraphResult), ("n_active_kf", C.c_int32), ("n_active_points_moved", C.c_int32), ("n_other_points_moved", C.c_int32),
+                ("n_points_skipped", C.c_int32)]
+
+
+def loop_correct_struct(pr, iters=20):
+    """the ctypes problem for pr (see loop_correct) -> (struct, arrays): arrays holds every buffer the struct points into, the in/out ones
+    under "poses" and "points", the outputs under "stage1_poses", "edge_err", "chi2", "lambdas", "trials" """
+    a = dict(poses=np.ascontiguousarray(pr["poses"], dtype=np.float64).reshape(-1, 7).copy(),
+             kf_active=np.ascontiguousarray(pr["kf_active"], dtype=np.uint8).reshape(-1),
+             corrected=np.ascontiguousarray(pr["corrected_pose"], dtype=np.float64).reshape(-1),
+             ei=np.ascontiguousarray(pr["ei"], dtype=np.int32).reshape(-1), ej=np.ascontiguousarray(pr["ej"], dtype=np.int32).reshape(-1),
+             meas=np.ascontiguousarray(pr["meas"], dtype=np.float64).reshape(-1, 7),
+             points=np.ascontiguousarray(pr["points"], dtype=np.float64).reshape(-1, 3).copy(),
+             point_anchor=np.ascontiguousarray(pr["point_anchor"], dtype=np.int32).reshape(-1),
+             point_active=np.ascontiguousarray(pr["point_active"], dtype=np.uint8).reshape(-1))
+    P, E, N = len(a["poses"]), len(a["ei"]), len(a["points"])
+    if not (len(a["kf_active"]) == P and a["corrected"].size == 7 and len(a["ej"]) == E and len(a["meas"]) == E and
+            len(a["point_anchor"]) == N and len(a["point_active"]) == N):
+        raise ValueError("one flag per keyframe, 7 doubles of corrected pose, one (i, j, measurement) per edge, one anchor and flag per point")
+    cap = max(int(iters), 0) + 2
+    a.update(stage1_poses=np.zeros((P, 7)), edge_err=np.zeros((max(E, 1), 6)), chi2=np.zeros(cap), lambdas=np.zeros(cap), trials=np.zeros(cap, np.int32))
+    nz = lambda arr, t: ptr(arr, t) if arr.size else None       # an empty array has no address worth passing
+    prob = LoopCorrectProblem(P, E, N, int(pr["cur_kf"]), int(pr["loop_kf"]), int(pr.get("initial_kf", -1)), int(pr.get("keep_kf", -1)),
+                              ptr(a["poses"], dbl_p), ptr(a["kf_active"], u8_p), ptr(a["corrected"], dbl_p), nz(a["ei"], i32_p), nz(a["ej"], i32_p),
+                              nz(a["meas"], dbl_p), nz(a["points"], dbl_p), nz(a["point_anchor"], i32_p), nz(a["point_active"], u8_p),
+                              ptr(a["stage1_poses"], dbl_p), ptr(a["edge_err"], dbl_p), cap, ptr(a["chi2"], dbl_p), ptr(a["lambdas"], dbl_p),
+                              ptr(a["trials"], i32_p))
+    return prob, a
+
+
+def loop_correct(ctx: Context, pr, iters=20):
+    """The geometry of LoopClosing::LoopCorrect (:353-594) on a flat problem:
+    pr = dict(poses [P, 7] T_cw, kf_active [P], cur_kf, loop_kf, initial_kf (-1: none), keep_kf (-1: none), corrected_pose [7],
+              ei [E], ej [E], meas [E, 7], points [N, 3], point_anchor [N] (-1: leave alone), point_active [N]).
+    -> dict(poses, points, stage1_poses, edge_err, n_iters, chi2, lambdas, trials, chi2_initial, chi2_final, n_active_kf,
+            n_active_points_moved, n_other_points_moved, n_points_skipped); the inputs are not modified."""
+    prob, a = loop_correct_struct(pr, iters)
+    res = LoopCorrectResult()
+    ctx.lib.ssx_loop_correct.restype = C.c_int
+    ctx.lib.ssx_loop_correct.argtypes = [C.c_void_p, C.POINTER(LoopCorrectProblem), C.c_int32, C.POINTER(LoopCorrectResult)]
+    ctx.check(ctx.lib.ssx_loop_correct(ctx.handle, C.byref(prob), int(iters), C.byref(res)))
+    k, E = res.pg.stats_n, len(a["ei"])
+    return dict(poses=a["poses"], points=a["points"], stage1_poses=a["stage1_poses"], edge_err=a["edge_err"][:E], n_iters=res.pg.n_iters,
+                chi2=a["chi2"][:k].copy(), lambdas=a["lambdas"][:k].copy(), trials=a["trials"][:k].copy(), chi2_initial=res.pg.chi2_initial,
+                chi2_final=res.pg.chi2_final, n_active_kf=res.n_active_kf, n_active_points_moved=res.n_active_points_moved,
+                n_other_points_moved=res.n_other_points_moved, n_points_skipped=res.n_points_skipped)
