@@ -349,6 +349,39 @@ SSX_API ssx_status ssx_ba_window_solve(ssx_ba_window* win, ssx_ba_result* res);
  * concurrent streams of BASELINE configs[4], or of a batch of stereo pairs.  Per window the bits of ssx_ba_window_solve.
  * The options of the first window apply. */
 SSX_API ssx_status ssx_ba_window_solve_batch(int32_t n, ssx_ba_window* const* wins, ssx_ba_result* results);
+/* A loop correction applied to the window where it lies: LoopClosing::CorrectActivateKeyframeAndMappoint (loopclosing.cpp:378-453)
+ * on what the window holds -- every keyframe of a window is active, so this is stage 1 of ssx_loop_correct on the resident state,
+ * followed by the fusion of :427-453, which for a window is a removal (below).  One small upload, one download, one synchronisation.
+ *   Poses:  T'_cur = corrected_pose7; every other keyframe a gets T'_a = (T_a * T_cur^-1) * corrected_pose7, grouped as :394-397
+ *           group it.  pose_fixed is unchanged.
+ *   Points: every landmark somebody observes gets p' = T'_a^-1 * (T_a * p); its anchor a is the keyframe of its first active
+ *           observation (:408) -- among its remaining observations the keyframe that was PUSHED earliest (not the lowest id;
+ *           observations removed as outliers do not count).  Fixed landmarks move as well (the reference moves every active map
+ *           point); the fixed flags are unchanged.  A landmark nobody observes is left alone.
+ *   Fusion: :439-448 appends the current map point's observations to the loop map point with AddObservation only and calls
+ *           Map::RemoveMapPoint(current_mp) (map.cpp:162-173); the loop map point is not inserted into the active map.  So the
+ *           landmarks fused_lm_ids (the ids of the current keyframe's map points that had a loop map point to merge into) leave
+ *           with all their observations, exactly as ssx_ba_window_remove_landmarks removes them after the correction; ids the
+ *           window does not hold are skipped.  The loop map point enters later through an ordinary push with new_fixed = 1.
+ * The arithmetic is that of ssx_loop_correct (the same kernels): on the exported window with every keyframe and point active and
+ * these anchors, that call returns the same bits.  Afterwards both state buffers and the host mirror hold the corrected state: the
+ * next solve starts from it and ssx_ba_window_export returns it.  Edits still pending (a push not yet solved) are sent first.
+ * res (nullable), arrays nullable, in the order of ssx_ba_window_export of the window as the call found it:
+ *   poses_out n_keyframes x 7, points_out n_landmarks x 3 (the fused ones still among them), anchor_kf_out n_landmarks = the id of
+ *   the keyframe each landmark was re-anchored to (-1: nobody observes it).
+ * SSX_ERR_INVALID_ARG: win or corrected_pose7 null, n_fused < 0 or n_fused > 0 with null ids, an empty window, cur_kf_id not in
+ * the window, a corrected pose that is not finite or whose quaternion is zero.  All are refused before anything is launched; on
+ * any failure the window, its mirror and res are unchanged. */
+typedef struct ssx_ba_window_loop_result {
+  int32_t n_keyframes, n_landmarks;   /* the window when the call began (= ssx_ba_window_size) */
+  int32_t n_points_moved;             /* landmarks re-anchored (:417-419) */
+  int32_t n_fused_removed;            /* landmarks that left (:447) */
+  double* poses_out;
+  double* points_out;
+  int64_t* anchor_kf_out;
+} ssx_ba_window_loop_result;
+SSX_API ssx_status ssx_ba_window_loop_correct(ssx_ba_window* win, int64_t cur_kf_id, const double* corrected_pose7, int32_t n_fused,
+                                              const int64_t* fused_lm_ids, ssx_ba_window_loop_result* res);
 
 /* (test and tools hooks -- ssx_ba_window_selftest, ssx_debug_*, ssx_ba_debug_*, the kernel taps ssx_ba_linearize / ssx_orb_stage_* /
  * ssx_lk_stage_* -- are NOT part of this ABI: include/ssx_test_hooks.h,

@@ -462,6 +462,27 @@ inline ssx_loop_correct_result LoopCorrect(Context& ctx, LoopCorrectInput& in, i
   return r;
 }
 
+// CorrectActivateKeyframeAndMappoint (loopclosing.cpp:378-453) for the backend's resident window, over ssx_ba_window_loop_correct:
+// after LoopCorrect has corrected the map, the window's keyframes and landmarks get the same bits where they lie.  fused_map_point_ids:
+// the ids of the current keyframe's map points that :439-448 merged into a loop map point (Map::RemoveMapPoint): they leave the window;
+// the loop map points come back through an ordinary push with new_fixed = 1.  poses / points / anchor_keyframe_ids receive the
+// corrected window in export order when given.
+inline ssx_ba_window_loop_result CorrectActiveWindow(ssx_ba_window* win, int64_t current_keyframe_id, const double corrected_current_pose[7],
+                                                     const std::vector<int64_t>& fused_map_point_ids = {}, std::vector<double>* poses = nullptr,
+                                                     std::vector<double>* points = nullptr, std::vector<int64_t>* anchor_keyframe_ids = nullptr)
+{
+  int32_t n_kf = 0, n_lm = 0;
+  if (ssx_ba_window_size(win, &n_kf, &n_lm, nullptr) != SSX_OK) throw std::invalid_argument("CorrectActiveWindow: no window");
+  ssx_ba_window_loop_result r{};
+  if (poses) { poses->assign(7 * (size_t)n_kf, 0.0); r.poses_out = poses->data(); }
+  if (points) { points->assign(3 * (size_t)n_lm, 0.0); r.points_out = points->data(); }
+  if (anchor_keyframe_ids) { anchor_keyframe_ids->assign((size_t)n_lm, -1); r.anchor_kf_out = anchor_keyframe_ids->data(); }
+  const ssx_status st = ssx_ba_window_loop_correct(win, current_keyframe_id, corrected_current_pose, (int32_t)fused_map_point_ids.size(),
+                                                   fused_map_point_ids.empty() ? nullptr : fused_map_point_ids.data(), &r);
+  if (st != SSX_OK) throw std::runtime_error("ssx_ba_window_loop_correct failed with status " + std::to_string((int)st));
+  return r;
+}
+
 // int LoopClosing::OptimizeCurrentPose() (loopclosing.cpp:245-351) on its own: every match must have its map point.
 // corrected_current_pose is refined in place, the matches that end as outliers are erased; returns what is left (cnt_inliner).
 inline int OptimizeCurrentPose(Context& ctx, std::vector<LoopMatch>& matches, double corrected_current_pose[7], const double K4[4])

@@ -15,6 +15,9 @@ extern "C" {
  * rule 1), its contents, order and fixed flags checked against a plain model after every step, and two twin windows that receive the same edits through ssx_ba_window_update_batch (two windows per call: the
  * threaded path) against the window itself; 0 = all steps agree, else the first step that does not */
 SSX_API int32_t ssx_ba_window_selftest(uint32_t seed, int32_t steps);
+/* test hook: how often the window's observation storage has been rewritten without its dead entries (tests that need dead entries
+ * before and after a rewrite ask it which state they built); -1 = no window */
+SSX_API int32_t ssx_ba_window_debug_rewrites(const ssx_ba_window* win);
 
 /* tools hook, needs no GPU: dynamic LDS bytes a BA kernel is launched with (-1: depends on the problem); the compiler's
  * resource report and rocprofv3's dispatch rows only know static __shared__ arrays (tools/kernel_resources.py) */

@@ -284,6 +284,12 @@ class BaBatch:
 i64_p = C.POINTER(C.c_int64)
 
 
+class BaWindowLoopResult(C.Structure):
+    """ssx_ba_window_loop_result"""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_landmarks", C.c_int32), ("n_points_moved", C.c_int32), ("n_fused_removed", C.c_int32),
+                ("poses_out", dbl_p), ("points_out", dbl_p), ("anchor_kf_out", i64_p)]
+
+
 class BaWindow:
     """A sliding local-BA window resident in HBM -- ssx_ba_window (include/ssx.h): push / pop keyframes, solve in place.
     What Backend::OptimizeActiveMap sees at consecutive keyframes (backend.cpp:88-169, map.cpp:27-56, 89-160)."""
@@ -381,6 +387,30 @@ class BaWindow:
     def set_landmark(self, lm_id, xyz=None, fixed=-1):
         xyz = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).ravel()
         self.ctx.check(self.ctx.lib.ssx_ba_window_set_landmark(self.handle, int(lm_id), ptr(xyz, dbl_p), int(fixed)))
+
+    def loop_correct(self, cur_kf_id, corrected_pose, fused_lm_ids=()):
+        """ssx_ba_window_loop_correct: CorrectActivateKeyframeAndMappoint on the resident window -- the keyframes move rigidly with
+        the corrected current keyframe, every observed landmark is re-anchored to its earliest-pushed observer, then the landmarks
+        fused_lm_ids leave (the fusion of loopclosing.cpp:427-453 is a removal for the window).  -> dict(kf_ids, lm_ids, poses,
+        points, anchors (keyframe id per landmark, -1: unobserved), n_points_moved, n_fused_removed), in export order of the window
+        as the call found it."""
+        lib = self.ctx.lib
+        lib.ssx_ba_window_loop_correct.restype = C.c_int32
+        lib.ssx_ba_window_loop_correct.argtypes = [C.c_void_p, C.c_int64, dbl_p, C.c_int32, i64_p, C.POINTER(BaWindowLoopResult)]
+        pose = np.ascontiguousarray(corrected_pose, dtype=np.float64).ravel()
+        if pose.size != 7:
+            raise ValueError("corrected_pose = 7 doubles (qx qy qz qw tx ty tz)")
+        fused = np.ascontiguousarray(fused_lm_ids, dtype=np.int64).ravel()
+        before = self.export()
+        P, L = before["P"], before["L"]
+        poses, points, anchors = np.zeros((P, 7)), np.zeros((L, 3)), np.full(L, -1, np.int64)
+        res = BaWindowLoopResult()
+        res.poses_out = ptr(poses, dbl_p); res.points_out = ptr(points, dbl_p); res.anchor_kf_out = ptr(anchors, i64_p)
+        self.ctx.check(lib.ssx_ba_window_loop_correct(self.handle, int(cur_kf_id), ptr(pose, dbl_p), len(fused), ptr(fused, i64_p) if len(fused) else None,
+                                                      C.byref(res)))
+        assert res.n_keyframes == P and res.n_landmarks == L
+        return dict(kf_ids=before["kf_ids"], lm_ids=before["lm_ids"], poses=poses, points=points, anchors=anchors,
+                    n_points_moved=res.n_points_moved, n_fused_removed=res.n_fused_removed)
 
     def size(self):
         a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)

@@ -2794,3 +2794,4 @@ int32_t ssx_ba_debug_upload_format(const ssx_ba_problem* prob)
 #include "ba_window.inc"
 #include "pg.inc"
 #include "loop_correct.inc"
+#include "ba_window_loop.inc"

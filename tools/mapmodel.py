@@ -11,7 +11,8 @@ re-marshalled map after every keyframe.
 Nothing here computes: `ActiveMap.problem()` lists the graph the reference would hand to g2o (keyframes and map points ascending
 by id, as g2o orders its vertices), `ActiveMap.apply()` writes a result back the way backend.cpp:205-244 does, and every change
 of the window between two optimisations is recorded as an edit (`ActiveMap.take_edits()`) that `apply_edits` replays on a
-`ssvio_amd.ba.BaWindow`.  `make_window_scenario` generates a synthetic drive (no GPU, no oracle, no reference).
+`ssvio_amd.ba.BaWindow`.  `ActiveMap.loop_correct` restates LoopClosing::CorrectActivateKeyframeAndMappoint
+(reference: src/ssvio/loopclosing.cpp:378-456) on the same map.  `make_window_scenario` generates a synthetic drive (no GPU, no oracle, no reference).
 """
 from __future__ import annotations
 
@@ -178,13 +179,78 @@ class ActiveMap:
         if removed:
             self._edits.append(("remove_obs", removed))
 
+    # ---- loop closing side ----------------------------------------------------------------------------------------------
+    def _lock(self, f):
+        """feature->map_point_.lock(): None when the feature carries no map point or the map deleted it"""
+        return self.mps.get(f.lm) if f.lm is not None else None
+
+    def loop_correct(self, cur_kf_id, corrected_pose, matches, loop_kf_id):
+        """LoopClosing::CorrectActivateKeyframeAndMappoint (reference: src/ssvio/loopclosing.cpp:378-456).
+        matches: [(current feature index, loop feature index)] into the two keyframes' feature lists (set_valid_feature_matches_).
+        Stage 1 (:382-425) goes through tools/loop_correct_model.py over the active keyframes and ALL active map points, condemned
+        ones included (the map still holds them, a window does not); the fusion (:427-453) is restated pointer by pointer.  Records
+        the edit ("loop_correct", dict(cur, corrected, fused)): for a window the fused current map points leave (Map::RemoveMapPoint,
+        map.cpp:162-173) and the loop map points are NOT inserted -- they come back with the next insert_keyframe that observes them.
+        -> dict(kf_ids, lm_ids, poses, points, anchors, fused): what stage 1 wrote, rows in ascending id order."""
+        from tools import loop_correct_model as lcm
+        assert cur_kf_id in self.active_kfs
+        corrected = np.array(corrected_pose, dtype=np.float64).reshape(7)
+        kf_ids = sorted(self.active_kfs)
+        row = {k: i for i, k in enumerate(kf_ids)}
+        lm_ids = sorted(self.active_mps)
+        anchors = []
+        for l in lm_ids:
+            mp = self.active_mps[l]
+            assert mp.active_obs                                                      # :405
+            anchors.append(row.get(mp.active_obs[0].kf, -1))                          # :408, :413-415
+        pr = dict(poses=np.array([self.kfs[k]["pose"] for k in kf_ids]).reshape(-1, 7), kf_active=np.ones(len(kf_ids), np.uint8),
+                  cur_kf=row[cur_kf_id], corrected_pose=corrected, points=np.array([self.active_mps[l].pos for l in lm_ids]).reshape(-1, 3),
+                  point_anchor=np.array(anchors, dtype=np.int64), point_active=np.ones(len(lm_ids), np.uint8))
+        s1, pts, _ = lcm.stage1(pr)
+        for l, x in zip(lm_ids, pts):                                                 # :419 SetPosition
+            self.active_mps[l].pos = np.array(x, dtype=np.float64)
+        for k, T in zip(kf_ids, s1):                                                  # :422-425 SetPose
+            self.kfs[k]["pose"] = np.array(T, dtype=np.float64)
+        # :427-453
+        cur_feats, loop_feats = self.kfs[cur_kf_id]["feats"], self.kfs[loop_kf_id]["feats"]
+        fused = []
+        for ci, li in matches:
+            loop_mp = self._lock(loop_feats[li])
+            current_mp = self._lock(cur_feats[ci])
+            if current_mp is not None and loop_mp is not None:
+                assert current_mp is not loop_mp, "the reference appends to the list it iterates: it would never return"
+                for f in list(current_mp.obs):                                        # :441-446
+                    loop_mp.obs.append(f)                                             # AddObservation (not AddActiveObservation)
+                    f.lm = loop_mp.id
+                self.mps.pop(current_mp.id, None)                                     # :447 Map::RemoveMapPoint
+                self.active_mps.pop(current_mp.id, None)
+                fused.append(current_mp.id)
+            else:
+                cur_feats[ci].lm = loop_mp.id if loop_mp is not None else None         # :451
+        self.stats["fused"] = self.stats.get("fused", 0) + len(fused)
+        self.in_window.difference_update(fused)
+        self._edits.append(("loop_correct", dict(cur=cur_kf_id, corrected=corrected.copy(), fused=np.array(fused, dtype=np.int64))))
+        return dict(kf_ids=kf_ids, lm_ids=lm_ids, poses=s1, points=pts, anchors=[kf_ids[a] if a >= 0 else -1 for a in anchors], fused=fused)
+
+    def adopt(self, kf_ids, poses, lm_ids, points):
+        """overwrite estimates with what a window computed (a device differs from numpy by FMA contraction): keyframes and map points
+        the map no longer holds are skipped"""
+        for k, p in zip(kf_ids, poses):
+            if int(k) in self.kfs:
+                self.kfs[int(k)]["pose"] = np.array(p, dtype=np.float64)
+        for l, x in zip(lm_ids, points):
+            if int(l) in self.mps:
+                self.mps[int(l)].pos = np.array(x, dtype=np.float64)
+
     def take_edits(self):
         e, self._edits = self._edits, []
         return e
 
 
 def apply_edits(win, edits):
-    """replay ActiveMap.take_edits() on a ssvio_amd.ba.BaWindow (created with fix_rule=1)"""
+    """replay ActiveMap.take_edits() on a ssvio_amd.ba.BaWindow (created with fix_rule=1); returns what the window's loop corrections
+    returned, in order (BaWindow.loop_correct's dicts)"""
+    corrections = []
     for kind, arg in edits:
         if kind == "push":
             win.push(arg["kf_id"], arg["pose"], new_ids=arg["new_ids"], new_xyz=arg["new_xyz"], new_fixed=arg["new_fixed"], obs_lm=arg["obs_lm"],
@@ -199,8 +265,11 @@ def apply_edits(win, edits):
                 by_kf.setdefault(kf, []).append((lm, cam))
             for kf, lst in by_kf.items():
                 win.remove_observations(kf, [l for l, _ in lst], [c for _, c in lst])
+        elif kind == "loop_correct":
+            corrections.append(win.loop_correct(arg["cur"], arg["corrected"], arg["fused"]))
         else:
             raise ValueError(kind)
+    return corrections
 
 
 def make_window_scenario(n_kf=14, n_active=5, new_per_kf=140, track_len=7, seed=0, frac_gross=0.04, pix_sigma=0.4, step=0.8,
