@@ -151,6 +151,32 @@ SSX_API ssx_status ssx_lk_debug_last_call(ssx_ctx* ctx, ssx_lk_call_info* out);
 SSX_API ssx_status ssx_pose_only_debug_trace(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, double* it_chi2,
                                              double* it_lambda, int32_t* it_trials, int32_t* round_rec);
 
+/* tests / tools hook, needs no GPU: the host side of the pose-only and loop-pose calls as plain plans (csrc/pose_only.hpp: PoProblem;
+ * csrc/pose_only.hip: po_plan_batch; csrc/pnp.hip: plan_pnp).  Either output may be NULL.
+ * out: what ssx_pose_only_opt_batch (traced != 0: ssx_pose_only_debug_trace) would do with n <= SSX_PO_MAX_INFO_JOBS jobs of M[j] edges.
+ *   job[j]     cls 0 = k_pose_only<2>, 1 = k_pose_only<6>, 2 = k_pose_only_generic, 3 = empty (no block: -1); the block it lies in; offset
+ *              and bytes of its buffers there in memory order: xyz, uv, pose in, err, level, result (record + M flags)
+ *   block[b]   block 0 is the pinned block of the register classes when there is such a job (read and written in place: nothing sent,
+ *              nothing returned; desc_* its descriptor table, trace_* the record table of a traced batch), then one block per generic job
+ *              in job order (device arena + pinned mirror: [0, sent) goes up, [ret_off, ret_off + ret_bytes) comes back)
+ *   launch[i]  in order: class, workgroups, block, index of its first descriptor in the block's table (-1: handed over by value)
+ * pnp_out: the one block of ssx_pnp_ransac / ssx_loop_pose_opt / ssx_loop_compute_pose (tap: ssx_pnp_debug_counts) for pnp_M pairs and
+ * pnp_H hypotheses; spans in memory order: best + ticket, xyz, uv, pose in, err, level, result, RANSAC header, RANSAC mask, tap counts,
+ * the refinement's descriptor (used in the pinned mirror only); sent / ret_* as above; refine_cls as job[].cls */
+enum { SSX_PO_SPANS = 6, SSX_PO_MAX_INFO_JOBS = 16, SSX_PNP_SPANS = 11 };
+typedef struct ssx_po_plan_info {
+  int32_t n_jobs, n_blocks, n_launches, reserved;
+  struct { int32_t cls, block; uint64_t span_off[6], span_bytes[6]; } job[16];
+  struct { uint64_t bytes, sent, ret_off, ret_bytes, desc_off, desc_bytes, trace_off, trace_bytes; } block[16];
+  struct { int32_t cls, grid, block, first_desc; } launch[16];
+} ssx_po_plan_info;
+typedef struct ssx_pnp_plan_info {
+  uint64_t span_off[11], span_bytes[11], bytes, sent, ret_off, ret_bytes;
+  int32_t refine_cls, reserved;
+} ssx_pnp_plan_info;
+SSX_API ssx_status ssx_po_debug_plan(int32_t n, const int32_t* M, int32_t traced, ssx_po_plan_info* out, int32_t pnp_M, int32_t pnp_H,
+                                     int32_t pnp_tap, ssx_pnp_plan_info* pnp_out);
+
 /* tests hooks of the P3P-RANSAC (csrc/pnp.hip, model: tools/pnp_model.py): the sample triples of (seed, M >= 3, H) as the kernel's
  * device function draws them (triples_out H x 3), and the best inlier count of each of the max_iters hypotheses of an
  * ssx_pnp_ransac call with the same arguments (counts_out max_iters) */

@@ -110,25 +110,31 @@ class PoseOnlyJob(C.Structure):
                 ("chi2_th", C.c_double), ("huber_delta", C.c_double), ("inlier_out", u8_p), ("n_inliers", C.POINTER(C.c_int32))]
 
 
-def pose_only_opt_batch(ctx: Context, problems, rounds=4, iters=10, chi2_th=5.991, huber_delta=1.0, prepared=False):
-    """ssx_pose_only_opt_batch: problems = [dict(pose, K, xyz, uv)] -> [dict(pose, inliers, n_inliers)], one launch for all.
-    prepared=True: -> a callable that restores the initial poses and makes the library call alone (the job structs built once, as a C
-    caller holds them)."""
-    n = len(problems)
-    arr = (PoseOnlyJob * n)()
+def _pose_only_jobs(problems, settings, chi2_th, huber_delta):
+    """problems = [dict(pose, K, xyz, uv)], settings = [(rounds, iters)] per problem -> the ssx_pose_only_job array, the input arrays it
+    points into, and per problem (pose, inliers, count): the arrays the call writes"""
+    arr = (PoseOnlyJob * max(len(problems), 1))()
     keep, outs = [], []
-    for i, pr in enumerate(problems):
+    for a, pr, (rounds, iters) in zip(arr, problems, settings):
         pose = np.ascontiguousarray(pr["pose"], dtype=np.float64).copy()
         K = np.ascontiguousarray(pr["K"], dtype=np.float64)
         xyz = np.ascontiguousarray(pr["xyz"], dtype=np.float64).reshape(-1, 3)
         uv = np.ascontiguousarray(pr["uv"], dtype=np.float64).reshape(-1, 2)
         inl = np.zeros(len(xyz), dtype=np.uint8)
         cnt = (C.c_int32 * 1)(0)
-        a = arr[i]
         a.pose_io = ptr(pose, dbl_p); a.K4 = ptr(K, dbl_p); a.M = len(xyz); a.xyz = ptr(xyz, dbl_p); a.uv = ptr(uv, dbl_p)
         a.rounds = rounds; a.iters = iters; a.chi2_th = chi2_th; a.huber_delta = huber_delta
         a.inlier_out = ptr(inl, u8_p); a.n_inliers = C.cast(cnt, C.POINTER(C.c_int32))
         keep.append((K, xyz, uv)); outs.append((pose, inl, cnt))
+    return arr, keep, outs
+
+
+def pose_only_opt_batch(ctx: Context, problems, rounds=4, iters=10, chi2_th=5.991, huber_delta=1.0, prepared=False):
+    """ssx_pose_only_opt_batch: problems = [dict(pose, K, xyz, uv)] -> [dict(pose, inliers, n_inliers)], one launch for all.
+    prepared=True: -> a callable that restores the initial poses and makes the library call alone (the job structs built once, as a C
+    caller holds them)."""
+    n = len(problems)
+    arr, keep, outs = _pose_only_jobs(problems, [(rounds, iters)] * n, chi2_th, huber_delta)
     ctx.lib.ssx_pose_only_opt_batch.restype = C.c_int32
     ctx.lib.ssx_pose_only_opt_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PoseOnlyJob)]
     if prepared:
@@ -543,20 +549,7 @@ def pose_only_trace(ctx: Context, problems, settings, warmup=0, chi2_th=5.991, h
     [(rounds, iters)] per problem, all in ONE call -> per problem dict(pose, inliers, n_inliers, chi2 / lam / trials [R, iters], active /
     iters_run / terminated / outliers [R]) with R = warmup + rounds."""
     n = len(problems)
-    arr = (PoseOnlyJob * max(n, 1))()
-    keep, outs = [], []
-    for i, (pr, (rounds, iters)) in enumerate(zip(problems, settings)):
-        pose = np.ascontiguousarray(pr["pose"], dtype=np.float64).copy()
-        K = np.ascontiguousarray(pr["K"], dtype=np.float64)
-        xyz = np.ascontiguousarray(pr["xyz"], dtype=np.float64).reshape(-1, 3)
-        uv = np.ascontiguousarray(pr["uv"], dtype=np.float64).reshape(-1, 2)
-        inl = np.zeros(len(xyz), dtype=np.uint8)
-        cnt = (C.c_int32 * 1)(0)
-        a = arr[i]
-        a.pose_io = ptr(pose, dbl_p); a.K4 = ptr(K, dbl_p); a.M = len(xyz); a.xyz = ptr(xyz, dbl_p); a.uv = ptr(uv, dbl_p)
-        a.rounds = rounds; a.iters = iters; a.chi2_th = chi2_th; a.huber_delta = huber_delta
-        a.inlier_out = ptr(inl, u8_p); a.n_inliers = C.cast(cnt, C.POINTER(C.c_int32))
-        keep.append((K, xyz, uv)); outs.append((pose, inl, cnt))
+    arr, keep, outs = _pose_only_jobs(problems, settings, chi2_th, huber_delta)
     n_it = sum((warmup + r) * i for r, i in settings)
     n_rd = sum(warmup + r for r, _ in settings)
     chi = np.zeros(max(n_it, 1)); lam = np.zeros(max(n_it, 1)); tr = np.zeros(max(n_it, 1), dtype=np.int32); rr = np.zeros((max(n_rd, 1), 4), dtype=np.int32)
@@ -573,3 +566,45 @@ def pose_only_trace(ctx: Context, problems, settings, warmup=0, chi2_th=5.991, h
                         iters_run=r4[:, 1].copy(), terminated=r4[:, 2].copy(), outliers=r4[:, 3].copy()))
         o_it += R * iters; o_rd += R
     return res
+
+
+class _PoJobInfo(C.Structure):
+    _fields_ = [("cls", C.c_int32), ("block", C.c_int32), ("span_off", C.c_uint64 * 6), ("span_bytes", C.c_uint64 * 6)]
+
+
+class _PoBlockInfo(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("bytes", "sent", "ret_off", "ret_bytes", "desc_off", "desc_bytes", "trace_off", "trace_bytes")]
+
+
+class _PoLaunchInfo(C.Structure):
+    _fields_ = [("cls", C.c_int32), ("grid", C.c_int32), ("block", C.c_int32), ("first_desc", C.c_int32)]
+
+
+class PoPlanInfo(C.Structure):
+    """ssx_po_plan_info (include/ssx_test_hooks.h)"""
+    _fields_ = [("n_jobs", C.c_int32), ("n_blocks", C.c_int32), ("n_launches", C.c_int32), ("reserved", C.c_int32),
+                ("job", _PoJobInfo * 16), ("block", _PoBlockInfo * 16), ("launch", _PoLaunchInfo * 16)]
+
+
+class PnpPlanInfo(C.Structure):
+    """ssx_pnp_plan_info"""
+    _fields_ = [("span_off", C.c_uint64 * 11), ("span_bytes", C.c_uint64 * 11), ("bytes", C.c_uint64), ("sent", C.c_uint64),
+                ("ret_off", C.c_uint64), ("ret_bytes", C.c_uint64), ("refine_cls", C.c_int32), ("reserved", C.c_int32)]
+
+
+PO_SPANS = ("xyz", "uv", "pose_in", "err", "level", "result")
+PNP_SPANS = ("best",) + PO_SPANS + ("header", "mask", "counts", "descriptor")
+
+
+def po_debug_plan(lib, Ms=None, traced=False, pnp=None):
+    """ssx_po_debug_plan, no GPU: -> (PoPlanInfo of a batch of jobs of Ms edges, or None; PnpPlanInfo of pnp = (M, H, tap), or None)"""
+    lib.ssx_po_debug_plan.restype = C.c_int32
+    lib.ssx_po_debug_plan.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(PoPlanInfo), C.c_int32, C.c_int32, C.c_int32, C.POINTER(PnpPlanInfo)]
+    info = PoPlanInfo() if Ms is not None else None
+    pinfo = PnpPlanInfo() if pnp is not None else None
+    m = (C.c_int32 * max(len(Ms or ()), 1))(*(Ms or ()))
+    M, H, tap = pnp or (0, 0, 0)
+    st = lib.ssx_po_debug_plan(len(Ms or ()), m, int(traced), C.byref(info) if info is not None else None, M, H, int(tap), C.byref(pinfo) if pinfo is not None else None)
+    if st != 0:
+        raise ValueError(f"ssx_po_debug_plan: status {st}")
+    return info, pinfo

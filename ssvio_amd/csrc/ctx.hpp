@@ -90,6 +90,11 @@ struct Layout {
   size_t off = 0;
   size_t take(size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
 };
+// a buffer's pointer, whatever its type, from the base of its block and its offset
+template <class T> void wire(T*& ptr, char* base, size_t off) { ptr = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off); }
+// The buffers of one block, each stated ONCE: `each(f)` calls f(pointer, bytes) for every buffer in memory order.  Wires the pointers
+// from `base` (null: offsets only, to size the block before it is reserved) and returns the bytes the block takes.
+template <class Each> size_t carve(char* base, Each&& each) { Layout lay; each([&](auto*& ptr, size_t bytes) { wire(ptr, base, lay.take(bytes)); }); return lay.off; }
 
 // ---- per-kernel timing with HIP events on the ctx stream (ssx_profile_begin / ssx_profile_end) ----
 enum SsxKernelId {

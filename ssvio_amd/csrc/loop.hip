@@ -405,7 +405,7 @@ struct PendArrays { ssx_keypoint* kps; uint8_t* desc; int32_t* cls; int32_t* ids
 // the pending slot for `cap` pyramid keypoints; base null: the bytes only
 size_t pend_arrays(char* base, int cap, PendArrays& a)
 {
-  return ssxorb::carve(base, [&](auto&& f) {
+  return carve(base, [&](auto&& f) {
     f(a.kps, sizeof(ssx_keypoint) * (size_t)cap); f(a.desc, (size_t)32 * cap); f(a.cls, (size_t)4 * cap); f(a.ids, (size_t)4 * cap); f(a.vals, (size_t)8 * cap);
   });
 }
@@ -638,7 +638,7 @@ ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int3
   char* hs = db->stage.as<char>();
   char* base = db->io.as<char>();
   k = 0;
-  match_scratch([&](auto*& ptr, size_t) { ssxorb::wire(ptr, base, o_m[k++]); }, m, nl);
+  match_scratch([&](auto*& ptr, size_t) { wire(ptr, base, o_m[k++]); }, m, nl);
   memcpy(hs + o_d, cur_desc, (size_t)n_cur * 32);
   memcpy(hs + o_c, cur_class_id, (size_t)n_cur * 4);
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -723,9 +723,9 @@ ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary* voc, i
     BowScratch b{};
     double* scores;
     auto scratch = [&](auto&& f) { f(dh, sizeof(StepHdr)); bow_scratch(f, b, N); f(scores, (size_t)n_elig * 8); };
-    SSX_HIP_TRY(ctx, db->io.reserve(ssxorb::carve(nullptr, scratch)));
+    SSX_HIP_TRY(ctx, db->io.reserve(carve(nullptr, scratch)));
     SSX_HIP_TRY(ctx, db->stage.reserve(256));
-    ssxorb::carve(db->io.as<char>(), scratch);
+    carve(db->io.as<char>(), scratch);
     SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact, dim3(1), dim3(kPairsThreads), 0, ctx->stream, d.kps, d.desc, d.keep, N, pa.kps, pa.desc, pa.cls,
                                                        &dh->n_pyr));
     SSX_HIP_TRY(ctx, hipGetLastError());
@@ -757,8 +757,8 @@ ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary* voc, i
       // MatchFeatures: the pending descriptors and class ids are the current side.  The pair count and the pairs are written straight into
       // the pinned block (mapped into the device's address space): what crosses is the 8-byte header and 8 bytes per pair
       MatchScratch m{};
-      SSX_HIP_TRY(ctx, db->io.reserve(ssxorb::carve(nullptr, [&](auto&& g) { match_scratch(g, m, nl); })));
-      ssxorb::carve(db->io.as<char>(), [&](auto&& g) { match_scratch(g, m, nl); });
+      SSX_HIP_TRY(ctx, db->io.reserve(carve(nullptr, [&](auto&& g) { match_scratch(g, m, nl); })));
+      carve(db->io.as<char>(), [&](auto&& g) { match_scratch(g, m, nl); });
       SSX_HIP_TRY(ctx, db->stage.reserve(256 + (size_t)nl * 8));
       int32_t* hm = db->stage.as<int32_t>();
       hm[0] = 0; hm[1] = -1;
@@ -861,11 +861,11 @@ ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t 
   BowScratch b{};
   // one block, on the device and (pinned) on the host: [descriptors | count in, count out] go up, [ids | values] and the counts come back
   auto bufs = [&](auto&& f) { f(feat, (size_t)32 * n); f(cnt, 8); bow_scratch(f, b, n); f(ids, (size_t)4 * n); f(vals, (size_t)8 * n); };
-  const size_t total = ssxorb::carve(nullptr, bufs);
+  const size_t total = carve(nullptr, bufs);
   SSX_HIP_TRY(ctx, voc->io.reserve(total));
   SSX_HIP_TRY(ctx, voc->stage.reserve(total));
   char* base = voc->io.as<char>();
-  ssxorb::carve(base, bufs);
+  carve(base, bufs);
   const size_t o_in = (size_t)((char*)b.word - base), o_out = (size_t)((char*)ids - base);
   char* hs = voc->stage.as<char>();
   memcpy(hs, desc, (size_t)32 * n);

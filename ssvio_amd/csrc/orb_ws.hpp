@@ -158,11 +158,6 @@ struct Described {
 // replicated over that many pyramid levels first (octave = level, response = -1, class_id = its index); levels == 0: taken as they are
 ssx_status describe_enqueue(ssx_ctx* ctx, const uint8_t* img, int stride, int rows, int cols, const ssx_orb_params& prm, const ssx_keypoint* kps, int n_kps,
                             int levels, Described* out);
-// a buffer's pointer, whatever its type, from the base of its block and its offset
-template <class T> void wire(T*& ptr, char* base, size_t off) { ptr = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(base) + off); }
-// The buffers of one block, each stated ONCE: `each(f)` calls f(pointer, bytes) for every buffer in memory order.  Wires the pointers
-// from `base` (null: offsets only, to size the block before it is reserved) and returns the bytes the block takes.
-template <class Each> size_t carve(char* base, Each&& each) { Layout lay; each([&](auto*& ptr, size_t bytes) { wire(ptr, base, lay.take(bytes)); }); return lay.off; }
 // rows of `cols` bytes from the caller's pitch to the staging copy's
 inline void copy_rows(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t src_pitch, int rows, int cols)
 {

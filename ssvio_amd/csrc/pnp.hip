@@ -468,91 +468,89 @@ __global__ void k_pnp_samples(uint32_t seed, int M, int H, int32_t* out)
 
 bool finite4(const double* K4) { return std::isfinite(K4[0]) && std::isfinite(K4[1]) && std::isfinite(K4[2]) && std::isfinite(K4[3]); }
 
-// One arena for the whole of ComputeCorrectPose:  [best | ticket | xyz | uv | pose in]  go up in one copy,
-// [RANSAC header | refined pose | inlier count | RANSAC mask | outlier flags] come back in one copy.
+// One block for the whole of ComputeCorrectPose, each buffer stated once and in memory order: the RANSAC's best key and ticket (16
+// bytes, zero before the launch), the refinement's problem (pose_only.hpp), the RANSAC's header and mask, the tap's counts, and the
+// refinement's descriptor, which only the pinned mirror uses.  [best .. pose in] go up in one copy, [result .. mask] come back in one.
+struct PnpBlock {
+  unsigned long long* best = nullptr;
+  PoProblem po;
+  PnpHdr* hdr = nullptr;
+  uint8_t* mask = nullptr;
+  int32_t* counts = nullptr;
+  PoDev* refine = nullptr;
+};
+
 struct PnpPlan {
   int M = 0, H = 0;
-  size_t o_best = 0, o_xyz = 0, o_uv = 0, o_pose = 0, in_bytes = 0;
-  size_t o_hdr = 0, o_pose_out = 0, o_n = 0, o_mask = 0, o_out = 0, out_end = 0;
-  size_t o_err = 0, o_level = 0, o_counts = 0, bytes = 0;
+  bool tap = false;
+  size_t bytes = 0;
+  PnpBlock dev, host;               // the block in the arena and its mirror in the pinned block (wired by pnp_upload)
+  template <class F> void each(PnpBlock& b, F&& f)
+  {
+    f(b.best, 16);
+    b.po.each(f);
+    f(b.hdr, sizeof(PnpHdr)); f(b.mask, (size_t)M);
+    f(b.counts, tap ? sizeof(int32_t) * (size_t)H : 0);
+    f(b.refine, sizeof(PoDev));
+  }
+  size_t wire(PnpBlock& b, char* base) { return carve(base, [&](auto&& f) { each(b, f); }); }
+  size_t returned() const { return (size_t)(reinterpret_cast<const char*>(host.mask) + M - reinterpret_cast<const char*>(host.po.res)); }
 };
 
 PnpPlan plan_pnp(int M, int H, bool tap)
 {
   PnpPlan p;
-  p.M = M; p.H = H;
-  Layout lay;
-  p.o_best = lay.take(16);
-  p.o_xyz = lay.take(sizeof(double) * 3 * (size_t)M);
-  p.o_uv = lay.take(sizeof(double) * 2 * (size_t)M);
-  p.o_pose = lay.take(sizeof(double) * 8);
-  p.in_bytes = lay.off;
-  p.o_hdr = lay.take(sizeof(PnpHdr));
-  p.o_pose_out = lay.take(sizeof(double) * 8);
-  p.o_n = lay.take(sizeof(int32_t) * 2);
-  p.o_mask = lay.take((size_t)M);
-  p.o_out = lay.take((size_t)M);
-  p.out_end = lay.off;
-  const bool generic = M > po_register_edges();
-  p.o_err = lay.take(generic ? sizeof(double) * 2 * (size_t)M : 0);
-  p.o_level = lay.take(generic ? (size_t)M : 0);
-  p.o_counts = lay.take(tap ? sizeof(int32_t) * (size_t)H : 0);
-  p.bytes = lay.off;
+  p.M = M; p.H = H; p.tap = tap;
+  p.dev.po.M = p.host.po.M = M;
+  p.bytes = p.wire(p.host, nullptr);
   return p;
 }
 
 // stage the inputs (pose7 nullable) and send them up
-ssx_status pnp_upload(ssx_ctx* ctx, const PnpPlan& p, const double* xyz, const double* uv, const double* pose7)
+ssx_status pnp_upload(ssx_ctx* ctx, PnpPlan& p, const double* xyz, const double* uv, const double* pose7)
 {
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(p.bytes));
   SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(p.bytes));
   char* hs = ctx->pnp_stage.as<char>();
-  memset(hs + p.o_best, 0, 16);
-  memcpy(hs + p.o_xyz, xyz, sizeof(double) * 3 * (size_t)p.M);
-  memcpy(hs + p.o_uv, uv, sizeof(double) * 2 * (size_t)p.M);
-  if (pose7) memcpy(hs + p.o_pose, pose7, sizeof(double) * 7);
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(ctx->pnp_arena.p, hs, p.in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  p.wire(p.dev, ctx->pnp_arena.as<char>());
+  p.wire(p.host, hs);
+  memset(p.host.best, 0, 16);
+  p.host.po.stage(xyz, uv, pose7);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(ctx->pnp_arena.p, hs, (size_t)(p.host.po.sent() - hs), hipMemcpyHostToDevice, ctx->stream));
   return SSX_OK;
 }
 
-ssx_status pnp_launch_ransac(ssx_ctx* ctx, const PnpPlan& p, const double* K4, double reproj_px, uint32_t seed, bool tap)
+ssx_status pnp_launch_ransac(ssx_ctx* ctx, const PnpPlan& p, const double* K4, double reproj_px, uint32_t seed)
 {
-  char* base = ctx->pnp_arena.as<char>();
   PnpDev d;
   d.M = p.M; d.H = p.H; d.seed = seed;
   d.fx = K4[0]; d.fy = K4[1]; d.cx = K4[2]; d.cy = K4[3]; d.thr2 = reproj_px * reproj_px;
-  d.xyz = (const double*)(base + p.o_xyz); d.uv = (const double*)(base + p.o_uv);
-  d.best = (unsigned long long*)(base + p.o_best); d.ticket = (unsigned int*)(base + p.o_best + 8);
-  d.hdr = (PnpHdr*)(base + p.o_hdr); d.inlier = (uint8_t*)(base + p.o_mask);
-  d.hyp_counts = tap ? (int32_t*)(base + p.o_counts) : nullptr;
+  d.xyz = p.dev.po.xyz; d.uv = p.dev.po.uv;
+  d.best = p.dev.best; d.ticket = reinterpret_cast<unsigned int*>(p.dev.best + 1);
+  d.hdr = p.dev.hdr; d.inlier = p.dev.mask;
+  d.hyp_counts = p.tap ? p.dev.counts : nullptr;
   SSX_PROF(ctx, KID_PNP_RANSAC, hipLaunchKernelGGL(k_pnp_ransac, dim3((unsigned)((p.H + 3) / 4)), dim3(256), 0, ctx->stream, d));
   SSX_HIP_TRY(ctx, hipGetLastError());
   return SSX_OK;
 }
 
-// OptimizeCurrentPose from the pose at pose_in (device): one warm-up optimize(10), then 4 rounds x optimize(10)
-ssx_status pnp_launch_refine(ssx_ctx* ctx, const PnpPlan& p, const double* K4, const double* pose_in, const int32_t* gate, double chi2_th, double huber_delta)
+// OptimizeCurrentPose: one warm-up optimize(10), then 4 rounds x optimize(10), from the uploaded pose or, with hdr, from the pose the
+// RANSAC left in its header (device memory), called off where it found none
+ssx_status pnp_launch_refine(ssx_ctx* ctx, const PnpPlan& p, const double* K4, const PnpHdr* hdr, double chi2_th, double huber_delta)
 {
-  char* base = ctx->pnp_arena.as<char>();
-  PoDeviceJob j;
-  j.M = p.M; j.warmup = 1; j.rounds = 4; j.iters = 10; j.chi2_th = chi2_th; j.huber_delta = huber_delta;
-  for (int k = 0; k < 4; ++k) j.K4[k] = K4[k];
-  j.xyz = (const double*)(base + p.o_xyz); j.uv = (const double*)(base + p.o_uv);
-  j.pose_in = pose_in; j.gate = gate;
-  j.err = (double*)(base + p.o_err); j.level = (uint8_t*)(base + p.o_level);
-  j.outlier = (uint8_t*)(base + p.o_out); j.pose_out = (double*)(base + p.o_pose_out); j.n_inliers = (int32_t*)(base + p.o_n);
-  SSX_HIP_TRY(ctx, po_launch_device(ctx, j));
+  PoDev& d = *p.host.refine;
+  po_set_scalars(d, p.M, 1, 4, 10, chi2_th, huber_delta, K4, hdr ? &hdr->found : nullptr);
+  p.dev.po.wire(d, hdr ? hdr->pose : nullptr);
+  SSX_HIP_TRY(ctx, po_launch_device(ctx, &d));
   return SSX_OK;
 }
 
-// everything between o_hdr and out_end, and the synchronisation of the call
-ssx_status pnp_download(ssx_ctx* ctx, const PnpPlan& p, size_t extra_off = 0, size_t extra_bytes = 0)
+// the results, the tap's counts behind them, and the synchronisation of the call
+ssx_status pnp_download(ssx_ctx* ctx, const PnpPlan& p)
 {
-  char* hs = ctx->pnp_stage.as<char>();
-  char* base = ctx->pnp_arena.as<char>();
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + p.o_hdr, base + p.o_hdr, p.out_end - p.o_hdr, hipMemcpyDeviceToHost, ctx->stream));
-  if (extra_bytes) SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + extra_off, base + extra_off, extra_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(p.host.po.res, p.dev.po.res, p.returned(), hipMemcpyDeviceToHost, ctx->stream));
+  if (p.tap) SSX_HIP_TRY(ctx, hipMemcpyAsync(p.host.counts, p.dev.counts, sizeof(int32_t) * (size_t)p.H, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return SSX_OK;
 }
@@ -577,18 +575,16 @@ ssx_status ssx_pnp_ransac(ssx_ctx* ctx, const double* K4, int32_t M, const doubl
   memcpy(pose_out, kIdentity, sizeof(kIdentity));
   if (inlier_out && M > 0) memset(inlier_out, 0, (size_t)M);
   if (M < 3) return SSX_OK;                                   // no triple to sample
-  const PnpPlan p = plan_pnp(M, max_iters, false);
+  PnpPlan p = plan_pnp(M, max_iters, false);
   ssx_status st = pnp_upload(ctx, p, xyz, uv, nullptr);
-  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, reproj_px, seed, false);
+  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, reproj_px, seed);
   if (st == SSX_OK) st = pnp_download(ctx, p);
   if (st != SSX_OK) return st;
-  const char* hs = ctx->pnp_stage.as<char>();
-  PnpHdr hdr;
-  memcpy(&hdr, hs + p.o_hdr, sizeof(hdr));
+  const PnpHdr& hdr = *p.host.hdr;
   *found = hdr.found; *n_inliers = hdr.n_inliers;
   if (best_hypothesis) *best_hypothesis = hdr.best;
   memcpy(pose_out, hdr.pose, sizeof(double) * 7);
-  if (inlier_out) memcpy(inlier_out, hs + p.o_mask, (size_t)M);
+  if (inlier_out) memcpy(inlier_out, p.host.mask, (size_t)M);
   return SSX_OK;
 }
 
@@ -598,15 +594,12 @@ ssx_status ssx_loop_pose_opt(ssx_ctx* ctx, double* pose_io, const double* K4, in
   if (!ctx || !pose_io || !K4 || M < 0 || (M > 0 && (!xyz || !uv)) || !finite4(K4)) return SSX_ERR_INVALID_ARG;
   if (n_inliers) *n_inliers = 0;
   if (M == 0) return SSX_OK;
-  const PnpPlan p = plan_pnp(M, 0, false);
+  PnpPlan p = plan_pnp(M, 0, false);
   ssx_status st = pnp_upload(ctx, p, xyz, uv, pose_io);
-  if (st == SSX_OK) st = pnp_launch_refine(ctx, p, K4, (const double*)(ctx->pnp_arena.as<char>() + p.o_pose), nullptr, chi2_th, huber_delta);
+  if (st == SSX_OK) st = pnp_launch_refine(ctx, p, K4, nullptr, chi2_th, huber_delta);
   if (st == SSX_OK) st = pnp_download(ctx, p);
   if (st != SSX_OK) return st;
-  const char* hs = ctx->pnp_stage.as<char>();
-  memcpy(pose_io, hs + p.o_pose_out, sizeof(double) * 7);
-  if (n_inliers) memcpy(n_inliers, hs + p.o_n, sizeof(int32_t));
-  if (inlier_out) for (int32_t i = 0; i < M; ++i) inlier_out[i] = !reinterpret_cast<const uint8_t*>(hs + p.o_out)[i];
+  po_read_result(p.host.po.res, M, pose_io, inlier_out, n_inliers);
   return SSX_OK;
 }
 
@@ -635,26 +628,18 @@ ssx_status ssx_loop_compute_pose(ssx_ctx* ctx, int32_t n_pairs, const double* lo
   out->n_with_point = M;
   if (M < 10) { out->verdict = SSX_LOOP_FEW_MAP_POINTS; return SSX_OK; }           // :193
   const double thr = 5.991, chi2_th = 5.991, huber_delta = 1.0;                   // :206, :301, g2o's RobustKernelHuber
-  const PnpPlan p = plan_pnp(M, max_iters, false);
+  PnpPlan p = plan_pnp(M, max_iters, false);
   ssx_status st = pnp_upload(ctx, p, xyz.data(), uv.data(), nullptr);
-  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, thr, seed, false);
-  const PnpHdr* dh = (const PnpHdr*)(ctx->pnp_arena.as<char>() + p.o_hdr);
-  if (st == SSX_OK) st = pnp_launch_refine(ctx, p, K4, dh->pose, &dh->found, chi2_th, huber_delta);
+  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, thr, seed);
+  if (st == SSX_OK) st = pnp_launch_refine(ctx, p, K4, p.dev.hdr, chi2_th, huber_delta);
   if (st == SSX_OK) st = pnp_download(ctx, p);
   if (st != SSX_OK) return st;
-  const char* hs = ctx->pnp_stage.as<char>();
-  PnpHdr hdr;
-  memcpy(&hdr, hs + p.o_hdr, sizeof(hdr));
+  const PnpHdr& hdr = *p.host.hdr;
   out->n_ransac_inliers = hdr.n_inliers;
   out->best_hypothesis = hdr.best;
   if (!hdr.found) { out->verdict = SSX_LOOP_NO_POSE; return SSX_OK; }              // the exception of :203-210
-  memcpy(out->corrected_pose, hs + p.o_pose_out, sizeof(double) * 7);
-  int32_t n_in = 0;
-  memcpy(&n_in, hs + p.o_n, sizeof(int32_t));
-  out->n_inliers = n_in;
-  const uint8_t* outl = reinterpret_cast<const uint8_t*>(hs + p.o_out);
-  for (int32_t k = 0; k < M; ++k) kept[src[k]] = outl[k] ? 0 : 1;                  // the erase of :338-344
-  if (n_in < 10) { out->verdict = SSX_LOOP_FEW_INLIERS; return SSX_OK; }           // :219
+  po_read_result(p.host.po.res, M, out->corrected_pose, kept, &out->n_inliers, src.data());   // (kept: the erase of :338-344)
+  if (out->n_inliers < 10) { out->verdict = SSX_LOOP_FEW_INLIERS; return SSX_OK; } // :219
   double inv[7], rel[7], lg[6];
   ssx::se3_inverse(out->corrected_pose, inv);
   ssx::se3_mul(T_cur, inv, rel);
@@ -674,14 +659,17 @@ ssx_status ssx_pnp_debug_samples(ssx_ctx* ctx, uint32_t seed, int32_t M, int32_t
 {
   if (!ctx || M < 3 || H < 1 || H > SSX_PNP_MAX_ITERS || !triples_out) return SSX_ERR_INVALID_ARG;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = sizeof(int32_t) * 3 * (size_t)H;
+  int32_t *dev = nullptr, *host = nullptr;
+  const size_t tri_bytes = sizeof(int32_t) * 3 * (size_t)H, bytes = carve(nullptr, [&](auto&& f) { f(dev, tri_bytes); });
   SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(bytes));
   SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(bytes));
-  hipLaunchKernelGGL(k_pnp_samples, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, seed, M, H, ctx->pnp_arena.as<int32_t>());
+  carve(ctx->pnp_arena.as<char>(), [&](auto&& f) { f(dev, tri_bytes); });
+  carve(ctx->pnp_stage.as<char>(), [&](auto&& f) { f(host, tri_bytes); });
+  hipLaunchKernelGGL(k_pnp_samples, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, ctx->stream, seed, M, H, dev);
   SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(ctx->pnp_stage.p, ctx->pnp_arena.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(host, dev, tri_bytes, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(triples_out, ctx->pnp_stage.p, bytes);
+  memcpy(triples_out, host, tri_bytes);
   return SSX_OK;
 }
 
@@ -689,12 +677,12 @@ ssx_status ssx_pnp_debug_counts(ssx_ctx* ctx, const double* K4, int32_t M, const
                                 uint32_t seed, int32_t* counts_out)
 {
   if (!pnp_args_ok(ctx, K4, M, xyz, uv, max_iters) || M < 3 || !counts_out) return SSX_ERR_INVALID_ARG;
-  const PnpPlan p = plan_pnp(M, max_iters, true);
+  PnpPlan p = plan_pnp(M, max_iters, true);
   ssx_status st = pnp_upload(ctx, p, xyz, uv, nullptr);
-  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, reproj_px, seed, true);
-  if (st == SSX_OK) st = pnp_download(ctx, p, p.o_counts, sizeof(int32_t) * (size_t)max_iters);
+  if (st == SSX_OK) st = pnp_launch_ransac(ctx, p, K4, reproj_px, seed);
+  if (st == SSX_OK) st = pnp_download(ctx, p);
   if (st != SSX_OK) return st;
-  memcpy(counts_out, ctx->pnp_stage.as<char>() + p.o_counts, sizeof(int32_t) * (size_t)max_iters);
+  memcpy(counts_out, p.host.counts, sizeof(int32_t) * (size_t)max_iters);
   return SSX_OK;
 }
 
@@ -705,31 +693,52 @@ ssx_status ssx_pnp_debug_p3p(ssx_ctx* ctx, const double* K4, int32_t n, const do
   if (n == 0) return SSX_OK;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t N = (size_t)n;
-  Layout lay;
-  const size_t o_xyz = lay.take(sizeof(double) * 9 * N), o_uv = lay.take(sizeof(double) * 6 * N), in_bytes = lay.off;
-  const size_t o_R = lay.take(sizeof(double) * 36 * N), o_t = lay.take(sizeof(double) * 12 * N), o_pose = lay.take(sizeof(double) * 28 * N);
-  const size_t o_valid = lay.take(sizeof(int32_t) * 4 * N), bytes = lay.off;
+  // the triples go up, [R .. valid] come back
+  struct Block { double *xyz, *uv, *R, *t, *pose; int32_t* valid; } dev{}, host{};
+  auto wire_block = [&](Block& b, char* base) {
+    return carve(base, [&](auto&& f) {
+      f(b.xyz, sizeof(double) * 9 * N); f(b.uv, sizeof(double) * 6 * N);
+      f(b.R, sizeof(double) * 36 * N); f(b.t, sizeof(double) * 12 * N); f(b.pose, sizeof(double) * 28 * N); f(b.valid, sizeof(int32_t) * 4 * N);
+    });
+  };
+  const size_t bytes = wire_block(dev, nullptr);
   SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(bytes));
   SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(bytes));
   char* hs = ctx->pnp_stage.as<char>();
-  char* base = ctx->pnp_arena.as<char>();
-  memcpy(hs + o_xyz, xyz, sizeof(double) * 9 * N);
-  memcpy(hs + o_uv, uv, sizeof(double) * 6 * N);
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  wire_block(dev, ctx->pnp_arena.as<char>());
+  wire_block(host, hs);
+  memcpy(host.xyz, xyz, sizeof(double) * 9 * N);
+  memcpy(host.uv, uv, sizeof(double) * 6 * N);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(dev.xyz, hs, (size_t)(reinterpret_cast<char*>(host.R) - hs), hipMemcpyHostToDevice, ctx->stream));
   PnpDev d = {};
   d.fx = K4[0]; d.fy = K4[1]; d.cx = K4[2]; d.cy = K4[3];
-  d.xyz = (const double*)(base + o_xyz); d.uv = (const double*)(base + o_uv);
-  hipLaunchKernelGGL(k_pnp_p3p_tap, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, ctx->stream, d, n, (int32_t*)(base + o_valid), (double*)(base + o_R),
-                     (double*)(base + o_t), (double*)(base + o_pose));
+  d.xyz = dev.xyz; d.uv = dev.uv;
+  hipLaunchKernelGGL(k_pnp_p3p_tap, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, ctx->stream, d, n, dev.valid, dev.R, dev.t, dev.pose);
   SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_R, base + o_R, bytes - o_R, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(host.R, dev.R, (size_t)(hs + bytes - reinterpret_cast<char*>(host.R)), hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(R_out, hs + o_R, sizeof(double) * 36 * N);
-  memcpy(t_out, hs + o_t, sizeof(double) * 12 * N);
-  memcpy(pose_out, hs + o_pose, sizeof(double) * 28 * N);
-  memcpy(valid_out, hs + o_valid, sizeof(int32_t) * 4 * N);
+  memcpy(R_out, host.R, sizeof(double) * 36 * N);
+  memcpy(t_out, host.t, sizeof(double) * 12 * N);
+  memcpy(pose_out, host.pose, sizeof(double) * 28 * N);
+  memcpy(valid_out, host.valid, sizeof(int32_t) * 4 * N);
   return SSX_OK;
 }
 #endif
 
 }  // extern "C"
+
+#ifndef SSX_NO_TEST_HOOKS
+void pnp_describe_plan(int M, int H, bool tap, ssx_pnp_plan_info* out)
+{
+  memset(out, 0, sizeof(*out));
+  PnpPlan p = plan_pnp(M, H, tap);                            // (carved from a null base, the mirror's pointers are its offsets)
+  auto span = [&](int k, auto* ptr, size_t bytes) { out->span_off[k] = reinterpret_cast<uintptr_t>(ptr); out->span_bytes[k] = bytes; };
+  int k = 0;
+  p.each(p.host, [&](auto*& ptr, size_t bytes) { span(k++, ptr, bytes); });
+  out->bytes = p.bytes;
+  out->sent = reinterpret_cast<uintptr_t>(p.host.po.sent());
+  out->ret_off = reinterpret_cast<uintptr_t>(p.host.po.res);
+  out->ret_bytes = p.returned();
+  out->refine_cls = M ? po_class(M) : 3;
+}
+#endif

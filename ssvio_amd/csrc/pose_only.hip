@@ -30,23 +30,8 @@
 namespace {
 
 constexpr int PT = 256;
+static_assert(PT == kPoThreads, "po_class (pose_only.hpp) counts edges per thread of this workgroup");
 constexpr int NRED = 28;   // 21 (upper 6x6) + 6 (b) + 1 (chi2)
-
-struct PoDev {
-  int M, rounds, iters;
-  double chi2_th, huber_delta;
-  ssx::Cam K;
-  const double* xyz;   // M x 3
-  const double* uv;    // M x 2
-  double* err;         // M x 2 (last computed error of each edge, like g2o's _error)
-  uint8_t* level;      // M: 1 = outlier level (not optimised)
-  uint8_t* outlier;    // M: features[i]->is_outlier_
-  const double* pose;  // 7 in (never written: it may be another kernel's result, pose_only.hpp)
-  double* pose_out;    // 7 out
-  int* n_inliers;
-  int warmup;          // optimize(iters) passes over all edges before the classified rounds (0: EstimateCurrentPose)
-  const int* gate;     // nullable: *gate == 0 ends the launch before it writes anything
-};
 
 // The record of the traced instantiations (include/ssx_test_hooks.h: ssx_pose_only_debug_trace; never part of a product build and
 // never an argument of the shipped kernels).  What g2o exposes in postIteration, slot (warmup + round) * iters + it: the robust chi2
@@ -652,81 +637,150 @@ __global__ __launch_bounds__(PT) void k_pose_only(const PoDev* __restrict__ dv, 
 
 }  // namespace
 
-struct PoWorkspace { DevBuf arena; HostBuf stage; };
-
 namespace {
 
-// the generic kernel (M > 6 x 256 edges: never a front-end's frame) keeps its edges in device memory: one problem per call
-// (warmup, tr: the test hook's -- 0 and nullptr from the entry points; tr's pointers are memory the device can write)
-ssx_status pose_only_generic(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz, const double* uv, int32_t rounds,
-                             int32_t iters, double chi2_th, double huber_delta, uint8_t* inlier_out, int32_t* n_inliers, int32_t warmup,
-                             const PoTrace* tr)
+// The only launches of the three kernels: n problems of class cls (po_class) whose descriptors start at dv -- memory the device reads
+// for the register classes, one descriptor handed over by value for the generic kernel.  tv: the records of a traced launch (test
+// hook), null for the shipped kernels, which alone are profiled.
+void po_launch(ssx_ctx* ctx, int cls, unsigned n, const PoDev* dv, const PoTrace* tv)
 {
-  DevBuf& arena = ctx->po_arena;
-  HostBuf& stage = ctx->po_stage;
-  Layout lay;
-  const size_t o_xyz = lay.take(sizeof(double) * 3 * (size_t)M);
-  const size_t o_uv = lay.take(sizeof(double) * 2 * (size_t)M);
-  const size_t o_pose = lay.take(sizeof(double) * 8);
-  const size_t in_bytes = lay.off;
-  const size_t o_err = lay.take(sizeof(double) * 2 * (size_t)M);
-  const size_t o_level = lay.take((size_t)M);
-  // results, contiguous so that one copy brings them back: pose | inlier count | outlier flags
-  const size_t o_res = lay.take(sizeof(double) * 8 + sizeof(int) * 2 + (size_t)M);
-  const size_t o_pose_out = o_res, o_n = o_res + sizeof(double) * 8, o_out = o_n + sizeof(int) * 2;
-  SSX_HIP_TRY(ctx, arena.reserve(lay.off));
-  SSX_HIP_TRY(ctx, stage.reserve(lay.off));
-  char* hs = stage.as<char>();
-  memcpy(hs + o_xyz, xyz, sizeof(double) * 3 * M);
-  memcpy(hs + o_uv, uv, sizeof(double) * 2 * M);
-  memcpy(hs + o_pose, pose_io, sizeof(double) * 7);
-  char* base = arena.as<char>();
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  PoDev d;
-  d.M = M; d.rounds = rounds; d.iters = iters; d.chi2_th = chi2_th; d.huber_delta = huber_delta; d.warmup = warmup; d.gate = nullptr;
-  d.K = ssx::Cam{K4[0], K4[1], K4[2], K4[3]};
-  d.xyz = (const double*)(base + o_xyz); d.uv = (const double*)(base + o_uv);
-  d.err = (double*)(base + o_err); d.level = (uint8_t*)(base + o_level); d.outlier = (uint8_t*)(base + o_out);
-  d.pose = (double*)(base + o_pose); d.pose_out = (double*)(base + o_pose_out); d.n_inliers = (int*)(base + o_n);
+  const dim3 grid(n), block(PT);
+  if (cls == 2) {
 #ifndef SSX_NO_TEST_HOOKS
-  if (tr) hipLaunchKernelGGL((k_pose_only_generic<PoTrace>), dim3(1), dim3(PT), 0, ctx->stream, d, *tr);
-  else
+    if (tv) hipLaunchKernelGGL((k_pose_only_generic<PoTrace>), grid, block, 0, ctx->stream, *dv, *tv);
+    else
 #endif
-  SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic<>, dim3(1), dim3(PT), 0, ctx->stream, d));
+    SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic<>, grid, block, 0, ctx->stream, *dv));
+    return;
+  }
+  if (!tv) {
+    if (cls == 0) SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<2>, grid, block, 0, ctx->stream, dv));
+    else SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<6>, grid, block, 0, ctx->stream, dv));
+    return;
+  }
+#ifndef SSX_NO_TEST_HOOKS
+  if (cls == 0) hipLaunchKernelGGL((k_pose_only<2, const PoTrace*>), grid, block, 0, ctx->stream, dv, tv);
+  else hipLaunchKernelGGL((k_pose_only<6, const PoTrace*>), grid, block, 0, ctx->stream, dv, tv);
+#endif
+}
+
+// A batch as a plain value.  The jobs of the register classes share ONE pinned block, which the kernels read and write in place (no
+// copy in either direction):  [descriptors: class 0 first, then class 1, job order inside a class | the problem of each, in that
+// order | the record table of a traced batch (nothing for the entry points: their block is not enlarged for the hook)].
+// The generic jobs follow one by one, in job order (pose_only_generic); an empty job is in neither list.
+struct PoBatchPlan {
+  struct Job { int job; PoProblem p; };
+  struct Launch { int cls; unsigned grid; size_t first; };
+  std::vector<Job> reg;
+  size_t n2 = 0;                // the first n2 of reg are of class 0
+  std::vector<int> generic;
+  bool traced = false;
+  PoDev* dv = nullptr;
+  PoTrace* tv = nullptr;
+  template <class F> void each(F&& f)
+  {
+    f(dv, sizeof(PoDev) * reg.size());
+    for (Job& j : reg) j.p.each(f);
+    f(tv, traced ? sizeof(PoTrace) * reg.size() : 0);
+  }
+  // at most two launches over the block's descriptors
+  int launches(Launch* out) const
+  {
+    int k = 0;
+    if (n2) out[k++] = Launch{0, (unsigned)n2, 0};
+    if (reg.size() > n2) out[k++] = Launch{1, (unsigned)(reg.size() - n2), n2};
+    return k;
+  }
+};
+
+template <class MOf> PoBatchPlan po_plan_batch(int n, MOf&& M_of, bool traced)
+{
+  PoBatchPlan pl;
+  pl.traced = traced;
+  pl.reg.reserve((size_t)n);
+  for (int c = 0; c < 3; ++c) {
+    for (int j = 0; j < n; ++j) {
+      const int M = M_of(j);
+      if (M == 0 || po_class(M) != c) continue;
+      if (c < 2) pl.reg.push_back({j, PoProblem{M}}); else pl.generic.push_back(j);
+    }
+    if (c == 0) pl.n2 = pl.reg.size();
+  }
+  return pl;
+}
+
+bool po_job_ok(const ssx_pose_only_job& q)
+{
+  return q.pose_io && q.K4 && q.M >= 0 && (q.M == 0 || (q.xyz && q.uv)) && q.rounds >= 0 && q.iters >= 0;
+}
+
+// the generic kernel (M > 6 x 256 edges: never a front-end's frame) keeps its edges in device memory, one problem per call: the
+// block in the arena and its mirror in the pinned block, the inputs sent up in one copy, the result brought back in one
+// (warmup, tr: the test hook's -- 0 and nullptr from the entry points; tr's pointers are memory the device can write)
+ssx_status pose_only_generic(ssx_ctx* ctx, const ssx_pose_only_job& q, int32_t warmup, const PoTrace* tr)
+{
+  PoProblem dev{q.M}, host{q.M};
+  const size_t bytes = carve(nullptr, [&](auto&& f) { dev.each(f); });
+  SSX_HIP_TRY(ctx, ctx->po_arena.reserve(bytes));
+  SSX_HIP_TRY(ctx, ctx->po_stage.reserve(bytes));
+  char* hs = ctx->po_stage.as<char>();
+  carve(ctx->po_arena.as<char>(), [&](auto&& f) { dev.each(f); });
+  carve(hs, [&](auto&& f) { host.each(f); });
+  host.stage(q.xyz, q.uv, q.pose_io);
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(ctx->po_arena.p, hs, (size_t)(host.sent() - hs), hipMemcpyHostToDevice, ctx->stream));
+  PoDev d;
+  po_set_scalars(d, q.M, warmup, q.rounds, q.iters, q.chi2_th, q.huber_delta, q.K4, nullptr);
+  dev.wire(d);
+  po_launch(ctx, 2, 1, &d, tr);
   SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_res, base + o_res, sizeof(double) * 8 + sizeof(int) * 2 + (size_t)M, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(host.res, dev.res, host.result_bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(pose_io, hs + o_pose_out, sizeof(double) * 7);
-  if (inlier_out) for (int i = 0; i < M; ++i) inlier_out[i] = !reinterpret_cast<uint8_t*>(hs + o_out)[i];
-  if (n_inliers) *n_inliers = *reinterpret_cast<int*>(hs + o_n);
+  po_read_result(host.res, q.M, q.pose_io, q.inlier_out, q.n_inliers);
   return SSX_OK;
 }
 
-// the batch behind ssx_pose_only_opt_batch (warmup = 0, trace = nullptr) and behind the test hook (trace[j]: the record of job j)
-ssx_status po_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, const PoTrace* trace);
+// the batch behind ssx_pose_only_opt_batch (warmup = 0, trace = nullptr) and behind the test hook (trace[j]: the record of job j).
+// Register classes: no copy, at most two launches, one synchronisation; then each generic job with its own upload, launch, download
+// and synchronisation.
+ssx_status po_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, const PoTrace* trace)
+{
+  if (!ctx || n < 0 || (n > 0 && !jobs)) return SSX_ERR_INVALID_ARG;
+  for (int j = 0; j < n; ++j)
+    if (!po_job_ok(jobs[j])) return SSX_ERR_INVALID_ARG;
+  if (n == 0) return SSX_OK;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  for (int j = 0; j < n; ++j)
+    if (jobs[j].M == 0 && jobs[j].n_inliers) *jobs[j].n_inliers = 0;      // (an empty job: no inliers, the pose as it came)
+  PoBatchPlan pl = po_plan_batch(n, [&](int j) { return jobs[j].M; }, trace != nullptr);
+  if (!pl.reg.empty()) {
+    SSX_HIP_TRY(ctx, ctx->po_stage.reserve(carve(nullptr, [&](auto&& f) { pl.each(f); }), 2.0));
+    carve(ctx->po_stage.as<char>(), [&](auto&& f) { pl.each(f); });
+    for (size_t k = 0; k < pl.reg.size(); ++k) {
+      const ssx_pose_only_job& q = jobs[pl.reg[k].job];
+      const PoProblem& p = pl.reg[k].p;
+      p.stage(q.xyz, q.uv, q.pose_io);
+      po_set_scalars(pl.dv[k], q.M, warmup, q.rounds, q.iters, q.chi2_th, q.huber_delta, q.K4, nullptr);
+      p.wire(pl.dv[k]);
+      if (trace) pl.tv[k] = trace[pl.reg[k].job];
+    }
+    PoBatchPlan::Launch ls[2];
+    for (int i = 0, nl = pl.launches(ls); i < nl; ++i) po_launch(ctx, ls[i].cls, ls[i].grid, pl.dv + ls[i].first, trace ? pl.tv + ls[i].first : nullptr);
+    SSX_HIP_TRY(ctx, hipGetLastError());
+    SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (const PoBatchPlan::Job& j : pl.reg) po_read_result(j.p.res, j.p.M, jobs[j.job].pose_io, jobs[j.job].inlier_out, jobs[j.job].n_inliers);
+  }
+  for (int j : pl.generic) {
+    const ssx_status st = pose_only_generic(ctx, jobs[j], warmup, trace ? trace + j : nullptr);
+    if (st != SSX_OK) return st;
+  }
+  return SSX_OK;
+}
 
 }  // namespace
 
-int po_register_edges() { return PT * 6; }
-
-hipError_t po_launch_device(ssx_ctx* ctx, const PoDeviceJob& j)
+hipError_t po_launch_device(ssx_ctx* ctx, const PoDev* d)
 {
-  PoDev d;
-  d.M = j.M; d.rounds = j.rounds; d.iters = j.iters; d.chi2_th = j.chi2_th; d.huber_delta = j.huber_delta; d.warmup = j.warmup; d.gate = j.gate;
-  d.K = ssx::Cam{j.K4[0], j.K4[1], j.K4[2], j.K4[3]};
-  d.xyz = j.xyz; d.uv = j.uv; d.err = j.err; d.level = j.level; d.outlier = j.outlier;
-  d.pose = j.pose_in; d.pose_out = j.pose_out; d.n_inliers = j.n_inliers;
-  if (j.M > PT * 6) {
-    SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic<>, dim3(1), dim3(PT), 0, ctx->stream, d));
-    return hipGetLastError();
-  }
-  // the register-resident kernels read their descriptor from memory (one per workgroup): the pinned block, as the batch does
-  hipError_t e = ctx->po_stage.reserve(sizeof(PoDev), 2.0);
-  if (e != hipSuccess) return e;
-  PoDev* dv = ctx->po_stage.as<PoDev>();
-  *dv = d;
-  if (j.M <= PT * 2) SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<2>, dim3(1), dim3(PT), 0, ctx->stream, (const PoDev*)dv));
-  else SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<6>, dim3(1), dim3(PT), 0, ctx->stream, (const PoDev*)dv));
+  po_launch(ctx, po_class(d->M), 1, d, nullptr);
   return hipGetLastError();
 }
 
@@ -737,114 +791,14 @@ extern "C" ssx_status ssx_pose_only_opt_batch(ssx_ctx* ctx, int32_t n, const ssx
   return po_batch(ctx, n, jobs, 0, nullptr);
 }
 
-namespace {
-
-ssx_status po_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int32_t warmup, const PoTrace* trace)
-{
-  if (!ctx || n < 0 || (n > 0 && !jobs)) return SSX_ERR_INVALID_ARG;
-  for (int j = 0; j < n; ++j) {
-    const ssx_pose_only_job& q = jobs[j];
-    if (!q.pose_io || !q.K4 || q.M < 0 || (q.M && (!q.xyz || !q.uv)) || q.rounds < 0 || q.iters < 0) return SSX_ERR_INVALID_ARG;
-  }
-  if (n == 0) return SSX_OK;
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  // classes: 0 = up to 2 edges per thread, 1 = up to 6 (the register-resident kernels), 2 = generic, 3 = empty
-  std::vector<int> order[2];
-  for (int j = 0; j < n; ++j) {
-    const int M = jobs[j].M;
-    if (M == 0) { if (jobs[j].n_inliers) *jobs[j].n_inliers = 0; continue; }
-    if (M <= PT * 2) order[0].push_back(j); else if (M <= PT * 6) order[1].push_back(j);
-  }
-  const size_t nb = order[0].size() + order[1].size();
-  if (nb) {
-    // one pinned block: [descriptors | per problem: xyz, uv, pose in | pose out, inlier count, outlier flags]
-    Layout lay;
-    const size_t o_desc = lay.take(sizeof(PoDev) * nb);
-    std::vector<size_t> o_in(nb), o_out(nb);
-    size_t k = 0;
-    for (int c = 0; c < 2; ++c)
-      for (int j : order[c]) {
-        const size_t M = (size_t)jobs[j].M;
-        o_in[k] = lay.take(sizeof(double) * (5 * M + 8));
-        o_out[k] = lay.take(sizeof(double) * 8 + sizeof(int) * 2 + M);
-        ++k;
-      }
-    const size_t o_tv = lay.take(trace ? sizeof(PoTrace) * nb : 0);   // (nothing for the entry points: their block is as it was)
-    HostBuf& stage = ctx->po_stage;
-    SSX_HIP_TRY(ctx, stage.reserve(lay.off, 2.0));
-    char* hs = stage.as<char>();
-    PoDev* dv = reinterpret_cast<PoDev*>(hs + o_desc);
-    k = 0;
-    for (int c = 0; c < 2; ++c)
-      for (int j : order[c]) {
-        const ssx_pose_only_job& q = jobs[j];
-        const size_t M = (size_t)q.M;
-        double* in = reinterpret_cast<double*>(hs + o_in[k]);
-        memcpy(in, q.xyz, sizeof(double) * 3 * M);
-        memcpy(in + 3 * M, q.uv, sizeof(double) * 2 * M);
-        memcpy(in + 5 * M, q.pose_io, sizeof(double) * 7);
-        PoDev& d = dv[k];
-        d.M = q.M; d.rounds = q.rounds; d.iters = q.iters; d.chi2_th = q.chi2_th; d.huber_delta = q.huber_delta; d.warmup = warmup; d.gate = nullptr;
-        d.K = ssx::Cam{q.K4[0], q.K4[1], q.K4[2], q.K4[3]};
-        if (trace) reinterpret_cast<PoTrace*>(hs + o_tv)[k] = trace[j];
-        d.xyz = in; d.uv = in + 3 * M; d.pose = in + 5 * M;
-        d.err = nullptr; d.level = nullptr;                          // (the register-resident kernels keep both in registers)
-        d.pose_out = reinterpret_cast<double*>(hs + o_out[k]);
-        d.n_inliers = reinterpret_cast<int*>(hs + o_out[k] + sizeof(double) * 8);
-        d.outlier = reinterpret_cast<uint8_t*>(hs + o_out[k] + sizeof(double) * 8 + sizeof(int) * 2);
-        ++k;
-      }
-#ifndef SSX_NO_TEST_HOOKS
-    if (trace) {
-      const PoTrace* tv = reinterpret_cast<const PoTrace*>(hs + o_tv);
-      if (!order[0].empty())
-        hipLaunchKernelGGL((k_pose_only<2, const PoTrace*>), dim3((unsigned)order[0].size()), dim3(PT), 0, ctx->stream, (const PoDev*)dv, tv);
-      if (!order[1].empty())
-        hipLaunchKernelGGL((k_pose_only<6, const PoTrace*>), dim3((unsigned)order[1].size()), dim3(PT), 0, ctx->stream, (const PoDev*)(dv + order[0].size()),
-                           tv + order[0].size());
-    } else
-#endif
-    {
-    if (!order[0].empty())
-      SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<2>, dim3((unsigned)order[0].size()), dim3(PT), 0, ctx->stream, (const PoDev*)dv));
-    if (!order[1].empty())
-      SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only<6>, dim3((unsigned)order[1].size()), dim3(PT), 0, ctx->stream, (const PoDev*)(dv + order[0].size())));
-    }
-    SSX_HIP_TRY(ctx, hipGetLastError());
-    SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    k = 0;
-    for (int c = 0; c < 2; ++c)
-      for (int j : order[c]) {
-        const ssx_pose_only_job& q = jobs[j];
-        const char* o = hs + o_out[k];
-        memcpy(q.pose_io, o, sizeof(double) * 7);
-        const uint8_t* ol = reinterpret_cast<const uint8_t*>(o + sizeof(double) * 8 + sizeof(int) * 2);
-        if (q.inlier_out) for (int i = 0; i < q.M; ++i) q.inlier_out[i] = !ol[i];
-        if (q.n_inliers) *q.n_inliers = *reinterpret_cast<const int*>(o + sizeof(double) * 8);
-        ++k;
-      }
-  }
-  for (int j = 0; j < n; ++j) {
-    const ssx_pose_only_job& q = jobs[j];
-    if (q.M <= PT * 6) continue;
-    const ssx_status st = pose_only_generic(ctx, q.pose_io, q.K4, q.M, q.xyz, q.uv, q.rounds, q.iters, q.chi2_th, q.huber_delta, q.inlier_out, q.n_inliers,
-                                            warmup, trace ? trace + j : nullptr);
-    if (st != SSX_OK) return st;
-  }
-  return SSX_OK;
-}
-
-}  // namespace
-
 extern "C" ssx_status ssx_pose_only_opt(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz,
                                         const double* uv, int32_t rounds, int32_t iters, double chi2_th, double huber_delta,
                                         uint8_t* inlier_out, int32_t* n_inliers)
 {
-  if (!ctx || !pose_io || !K4 || M < 0 || (M && (!xyz || !uv)) || rounds < 0 || iters < 0) return SSX_ERR_INVALID_ARG;
   ssx_pose_only_job q;
   q.pose_io = pose_io; q.K4 = K4; q.M = M; q.xyz = xyz; q.uv = uv; q.rounds = rounds; q.iters = iters; q.chi2_th = chi2_th; q.huber_delta = huber_delta;
   q.inlier_out = inlier_out; q.n_inliers = n_inliers;
-  return ssx_pose_only_opt_batch(ctx, 1, &q);
+  return po_batch(ctx, 1, &q, 0, nullptr);
 }
 
 #ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h
@@ -862,28 +816,76 @@ extern "C" ssx_status ssx_pose_only_debug_trace(ssx_ctx* ctx, int32_t n, const s
   }
   if (n == 0) return SSX_OK;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  Layout lay;
-  const size_t o_chi = lay.take(sizeof(double) * n_it), o_lam = lay.take(sizeof(double) * n_it), o_tr = lay.take(sizeof(int) * n_it);
-  const size_t o_rd = lay.take(sizeof(int) * 4 * n_rd);
+  PoTrace all;                                                              // the four arrays, all jobs
+  auto arrays = [&](auto&& f) { f(all.chi2, sizeof(double) * n_it); f(all.lambda, sizeof(double) * n_it); f(all.trials, sizeof(int) * n_it); f(all.round_rec, sizeof(int) * 4 * n_rd); };
+  const size_t bytes = carve(nullptr, arrays);
   HostBuf rec;
-  hipError_t e = rec.reserve(lay.off + 256);
+  hipError_t e = rec.reserve(bytes + 256);
   if (e != hipSuccess) { SSX_HIP_TRY(ctx, e); }
-  char* hb = rec.as<char>();
-  memset(hb, 0, lay.off);
+  memset(rec.p, 0, bytes);
+  carve(rec.as<char>(), arrays);
   std::vector<PoTrace> tv((size_t)n);
   size_t k_it = 0, k_rd = 0;
   for (int j = 0; j < n; ++j) {
-    tv[j].chi2 = reinterpret_cast<double*>(hb + o_chi) + k_it; tv[j].lambda = reinterpret_cast<double*>(hb + o_lam) + k_it;
-    tv[j].trials = reinterpret_cast<int*>(hb + o_tr) + k_it; tv[j].round_rec = reinterpret_cast<int*>(hb + o_rd) + 4 * k_rd;
+    tv[j] = PoTrace{all.chi2 + k_it, all.lambda + k_it, all.trials + k_it, all.round_rec + 4 * k_rd};
     k_it += (size_t)(warmup + jobs[j].rounds) * (size_t)jobs[j].iters;
     k_rd += (size_t)(warmup + jobs[j].rounds);
   }
   const ssx_status st = po_batch(ctx, n, jobs, warmup, tv.data());        // (synchronises the stream before it returns)
   if (st == SSX_OK) {
-    memcpy(it_chi2, hb + o_chi, sizeof(double) * n_it); memcpy(it_lambda, hb + o_lam, sizeof(double) * n_it);
-    memcpy(it_trials, hb + o_tr, sizeof(int) * n_it); memcpy(round_rec, hb + o_rd, sizeof(int) * 4 * n_rd);
+    memcpy(it_chi2, all.chi2, sizeof(double) * n_it); memcpy(it_lambda, all.lambda, sizeof(double) * n_it);
+    memcpy(it_trials, all.trials, sizeof(int) * n_it); memcpy(round_rec, all.round_rec, sizeof(int) * 4 * n_rd);
   }
   rec.release();
   return st;
+}
+
+// what po_batch would do with jobs of M[0 .. n) edges, and what plan_pnp (pnp.hip) makes of (pnp_M, pnp_H, pnp_tap); no device
+extern "C" ssx_status ssx_po_debug_plan(int32_t n, const int32_t* M, int32_t traced, ssx_po_plan_info* out, int32_t pnp_M, int32_t pnp_H,
+                                        int32_t pnp_tap, ssx_pnp_plan_info* pnp_out)
+{
+  if (out) {
+    if (n < 0 || n > SSX_PO_MAX_INFO_JOBS || (n > 0 && !M)) return SSX_ERR_INVALID_ARG;
+    for (int j = 0; j < n; ++j)
+      if (M[j] < 0) return SSX_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    out->n_jobs = n;
+    for (int j = 0; j < n; ++j) { out->job[j].cls = M[j] ? po_class(M[j]) : 3; out->job[j].block = -1; }
+    PoBatchPlan pl = po_plan_batch(n, [&](int j) { return M[j]; }, traced != 0);
+    // (carved from a null base, a plan's pointers are its offsets)
+    auto spans = [&](PoProblem& p, int job) {
+      int k = 0;
+      p.each([&](auto*& ptr, size_t bytes) { out->job[job].span_off[k] = reinterpret_cast<uintptr_t>(ptr); out->job[job].span_bytes[k] = bytes; ++k; });
+      out->job[job].block = out->n_blocks;
+    };
+    if (!pl.reg.empty()) {
+      auto& b = out->block[out->n_blocks];
+      b.bytes = carve(nullptr, [&](auto&& f) { pl.each(f); });
+      b.desc_off = reinterpret_cast<uintptr_t>(pl.dv); b.desc_bytes = sizeof(PoDev) * pl.reg.size();
+      b.trace_off = reinterpret_cast<uintptr_t>(pl.tv); b.trace_bytes = pl.traced ? sizeof(PoTrace) * pl.reg.size() : 0;
+      for (PoBatchPlan::Job& j : pl.reg) spans(j.p, j.job);
+      PoBatchPlan::Launch ls[2];
+      for (int i = 0, nl = pl.launches(ls); i < nl; ++i) {
+        auto& l = out->launch[out->n_launches++];
+        l.cls = ls[i].cls; l.grid = (int32_t)ls[i].grid; l.block = out->n_blocks; l.first_desc = (int32_t)ls[i].first;
+      }
+      ++out->n_blocks;
+    }
+    for (int j : pl.generic) {
+      PoProblem p{M[j]};
+      auto& b = out->block[out->n_blocks];
+      b.bytes = carve(nullptr, [&](auto&& f) { p.each(f); });
+      b.sent = reinterpret_cast<uintptr_t>(p.sent()); b.ret_off = reinterpret_cast<uintptr_t>(p.res); b.ret_bytes = p.result_bytes();
+      spans(p, j);
+      auto& l = out->launch[out->n_launches++];
+      l.cls = 2; l.grid = 1; l.block = out->n_blocks; l.first_desc = -1;
+      ++out->n_blocks;
+    }
+  }
+  if (pnp_out) {
+    if (pnp_M < 0 || pnp_H < 0) return SSX_ERR_INVALID_ARG;
+    pnp_describe_plan(pnp_M, pnp_H, pnp_tap != 0, pnp_out);
+  }
+  return SSX_OK;
 }
 #endif  // SSX_NO_TEST_HOOKS

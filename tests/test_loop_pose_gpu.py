@@ -6,10 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from ssvio_amd import loop
+import ssvio_amd
+from ssvio_amd import ba, loop
 from ssvio_amd._lib import SSX_ERR_INVALID_ARG, dbl_p, i32_p, ptr, u8_p
 from tools import pnp_model as pm
-from tools.synth import make_loop_pose_problem, pose_inv, pose_mul
+from tools.synth import make_loop_pose_problem, make_pose_only_problem, pose_inv, pose_mul
 
 import loop_pose_cases as lc
 
@@ -151,6 +152,40 @@ def _compute_correct_pose_equals_the_chained_calls(ctx, po, pose):
         np.testing.assert_allclose(g["relative_to_loop"], rel, rtol=0, atol=1e-12 * far)
     again = loop.compute_correct_pose(ctx, xyz, has, uv, T_cur, T_loop, p["K"], lc.H, seed=6)
     assert all(np.asarray(again[k]).tobytes() == np.asarray(g[k]).tobytes() for k in g)
+
+
+def _frozen(r):
+    """a result (dict, or list of dicts) as bytes"""
+    if isinstance(r, list):
+        return [_frozen(x) for x in r]
+    return {k: np.asarray(v).tobytes() for k, v in r.items()}
+
+
+def test_alternating_calls_on_one_context_equal_first_calls_on_fresh_ones():
+    """The pose-only batch and the loop-pose calls keep their pinned blocks apart (the refinement's descriptor lies in the loop-pose
+    block, not in the batch's): in whatever order they alternate on one context, each returns the bytes it returns as the first call
+    of a fresh context."""
+    ident = np.array([0, 0, 0, 1.0, 0, 0, 0])
+    p40, has40, xyz40, uv40 = _pairs(35, 41, 5)                              # 40 pairs, 35 with a map point: k_pose_only<2> refines
+    p1600 = make_loop_pose_problem(M=1600, seed=42, frac_gross=0.3, noise_px=0.5)   # k_pose_only_generic refines
+    batch = [make_pose_only_problem(M=M, seed=50 + M, frac_gross=0.05) for M in (12, 513, 1537)]
+    batch.append(dict(pose=ident, K=batch[0]["K"], xyz=np.zeros((0, 3)), uv=np.zeros((0, 2))))
+    p200 = make_pose_only_problem(M=200, seed=43, frac_gross=0.05)
+    calls = [
+        lambda c: loop.compute_correct_pose(c, xyz40, has40, uv40, ident, ident, p40["K"], lc.H, seed=6),
+        lambda c: ba.pose_only_opt_batch(c, batch),
+        lambda c: loop.compute_correct_pose(c, p1600["xyz"], np.ones(1600, np.uint8), p1600["uv"], ident, ident, p1600["K"], 64, seed=6),
+        lambda c: ba.pose_only_opt(c, p200["pose"], p200["K"], p200["xyz"], p200["uv"]),
+    ]
+    first = []
+    for call in calls:
+        with ssvio_amd.Context(0) as fresh:
+            first.append(_frozen(call(fresh)))
+    assert first[0]["verdict"] == first[2]["verdict"] == np.asarray(loop.LOOP_OK).tobytes()       # both refinements ran
+    assert first[1][3]["n_inliers"] == np.asarray(0).tobytes() and first[1][3]["pose"] == ident.tobytes()
+    with ssvio_amd.Context(0) as one:
+        for k in [0, 1, 2, 3, 3, 2, 1, 0]:
+            assert _frozen(calls[k](one)) == first[k], k
 
 
 def test_compute_correct_pose_verdicts(ctx):
