@@ -1,6 +1,8 @@
 // ssvio_amd/host/backend.cpp -- see backend.hpp
 #include "backend.hpp"
 
+#include "loopclosing.hpp"
+
 #include <chrono>
 
 #include <algorithm>
@@ -59,6 +61,7 @@ void Backend::InsertKeyFrame(const KeyFramePtr& kf, bool optimization)
   if (!async_) {
     InsertIntoMap(kf);
     if (optimization) OptimizeActiveMap();
+    HandToLoopClosing(kf);
     return;
   }
   {
@@ -79,6 +82,34 @@ void Backend::WaitIdle()
   RethrowWorkerError();
 }
 
+void Backend::HandToLoopClosing(const KeyFramePtr& kf)
+{
+  if (loop_) loop_->InsertNewKeyFrame(kf);
+}
+
+void Backend::RequestPause()
+{
+  std::unique_lock<std::mutex> lk(queue_mutex_);
+  pause_requested_ = true;
+  queue_cv_.notify_all();
+  if (async_) pause_cv_.wait(lk, [this] { return paused_ || stop_; });
+}
+
+bool Backend::HasPaused()
+{
+  std::lock_guard<std::mutex> lk(queue_mutex_);
+  return pause_requested_ && (!async_ || paused_);
+}
+
+void Backend::Resume()
+{
+  {
+    std::lock_guard<std::mutex> lk(queue_mutex_);
+    pause_requested_ = false;
+  }
+  queue_cv_.notify_all();
+}
+
 // queue_mutex_ held.  The worker thread cannot let an exception escape (std::terminate): it parks it here and the
 // caller thread gets it from WaitIdle() / the next InsertKeyFrame(), like the synchronous mode through its call stack.
 void Backend::RethrowWorkerError()
@@ -97,7 +128,14 @@ void Backend::Worker()
     std::deque<std::pair<KeyFramePtr, bool>> batch;
     {
       std::unique_lock<std::mutex> lk(queue_mutex_);
-      queue_cv_.wait(lk, [this] { return stop_ || !queue_.empty(); });
+      queue_cv_.wait(lk, [this] { return stop_ || pause_requested_ || !queue_.empty(); });
+      if (pause_requested_ && !stop_) {                              // park between two batches until Resume
+        paused_ = true;
+        pause_cv_.notify_all();
+        queue_cv_.wait(lk, [this] { return stop_ || !pause_requested_; });
+        paused_ = false;
+        continue;
+      }
       if (queue_.empty()) return;                                    // stop requested and nothing left to do
       batch.swap(queue_);
       busy_ = true;
@@ -123,6 +161,10 @@ void Backend::Worker()
         Solve(w);                                                    // throws on a HIP / argument error of the BA call
         std::lock_guard<std::mutex> map_lock(map_->update_mutex);
         Apply(w);
+      }
+      if (loop_) {
+        std::lock_guard<std::mutex> map_lock(map_->update_mutex);
+        for (auto& item : batch) HandToLoopClosing(item.first);
       }
     } catch (...) {
       err = std::current_exception();
@@ -360,6 +402,23 @@ void Backend::WindowApply(WindowResult& r)
   map_->RemoveOldActiveMapPoints();
   const auto& active_mps = map_->GetActiveMapPoints();
   for (auto it = in_window_.begin(); it != in_window_.end();) it = active_mps.count(*it) ? std::next(it) : in_window_.erase(it);
+  if (window_check_) WindowCheckAgainstMap();
+}
+
+// The window after a loop correction of the map.  The fused map points left the map (Map::RemoveMapPoint) and leave the window with
+// all their observations, so they leave in_window_ and every keyframe's window_feats_ as well; the loop map points they were merged
+// into got plain observations only (not active ones) and enter later through an ordinary push.  Poses and positions: the window
+// applies to its own state the arithmetic ssx_loop_correct applied to the map (the same kernels, the same anchors), so
+// Backend.Window.Check finds the two graphs equal again.
+void Backend::LoopCorrectWindow(unsigned long cur_kf_id, const SE3& corrected_pose, const std::vector<unsigned long>& fused_ids)
+{
+  if (!window_) return;
+  std::vector<int64_t> ids(fused_ids.begin(), fused_ids.end());
+  window_->LoopCorrect((int64_t)cur_kf_id, corrected_pose.data(), (int)ids.size(), ids.data(), nullptr);
+  for (unsigned long id : fused_ids) {
+    in_window_.erase(id);
+    for (auto& kv : window_feats_) kv.second.erase(id);
+  }
   if (window_check_) WindowCheckAgainstMap();
 }
 

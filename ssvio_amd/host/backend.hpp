@@ -20,7 +20,12 @@
 // the per-frame logs and trajectory files byte for byte; Backend.Window.Check: 1 re-marshals the map beside the window at every
 // keyframe and throws when the two graphs differ.  An implementation without a resident window (the CPU oracle of the tests)
 // falls back to 0.
-// Loop closing is not attached.
+// Loop closing (loopclosing.hpp) is attached with SetLoopClosing: every keyframe is handed to it after the window optimisation it
+// triggered (backend.cpp:66 of the reference hands it over before; with the loop step inline that would correct a window the
+// optimisation then overwrites).  A loop correction edits the map and the resident window while the backend stands still:
+// RequestPause returns once the worker thread is parked between two batches (at once without Backend.Async: the backend then only
+// runs under the map mutex of its caller), Resume lets it go on; LoopCorrectWindow applies the correction to the resident window
+// and brings the mirrors of it kept here in line.
 #pragma once
 #include <condition_variable>
 #include <deque>
@@ -38,6 +43,8 @@
 
 namespace ssx::host {
 
+class LoopClosing;
+
 class Backend {
  public:
   Backend(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right);
@@ -50,6 +57,16 @@ class Backend {
   void WaitIdle();                          // asynchronous mode: returns when the queue is empty and the worker idle
   bool async() const { return async_; }
   bool resident_window() const { return window_ != nullptr; }
+
+  void SetLoopClosing(LoopClosing* loop) { loop_ = loop; }
+  // backend.cpp:253-266 without the polling: RequestPause blocks until the worker is parked (never call it from the worker itself
+  // or with the map mutex held: the worker needs that mutex to finish its batch)
+  void RequestPause();
+  bool HasPaused();
+  void Resume();
+  // paused, map mutex held, the map already corrected and fused: the same correction on the resident window (no-op without one).
+  // fused_ids: the map points Map::FuseLoopMapPoints removed.
+  void LoopCorrectWindow(unsigned long cur_kf_id, const SE3& corrected_pose, const std::vector<unsigned long>& fused_ids);
 
   struct Stats {
     long windows = 0, lm_iterations = 0, edges = 0, outlier_edges = 0;
@@ -90,6 +107,7 @@ class Backend {
   void WindowSolve(WindowResult& r);        // the GPU call               (no lock)
   void WindowApply(WindowResult& r);        // result -> map, outliers -> window and map
   void WindowCheckAgainstMap();             // Backend.Window.Check
+  void HandToLoopClosing(const KeyFramePtr& kf);   // map mutex held
 
   Compute& compute_;
   std::shared_ptr<Map> map_;
@@ -103,7 +121,9 @@ class Backend {
   bool async_ = false;
   std::thread worker_;
   std::mutex queue_mutex_;
-  std::condition_variable queue_cv_, idle_cv_;
+  std::condition_variable queue_cv_, idle_cv_, pause_cv_;
+  bool pause_requested_ = false, paused_ = false;   // queue_mutex_
+  LoopClosing* loop_ = nullptr;
   std::deque<std::pair<KeyFramePtr, bool>> queue_;
   bool stop_ = false, busy_ = false;
   std::exception_ptr worker_error_;         // first failure of the worker thread, handed to the caller thread

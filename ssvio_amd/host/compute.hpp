@@ -1,16 +1,19 @@
-// ssvio_amd/host/compute.hpp -- the five compute calls the reference's front-end and backend make, as one interface
+// ssvio_amd/host/compute.hpp -- the compute calls the reference's front-end, backend and loop closing make, as one interface
 // the host layer is written against:
 //   Detect          ORBextractor::Detect              (frontend.cpp:302-344 DetectFeatures)
 //   TrackLK         cv::calcOpticalFlowPyrLK          (frontend.cpp:156-166 TrackLastFrame, :374-384 FindFeaturesInRight)
 //   PoseOnly        the g2o part of EstimateCurrentPose (frontend.cpp:196-270)
 //   Triangulate     ssvio::triangulation + z > 0      (frontend.cpp:448-544)
 //   BundleAdjust    the g2o part of OptimizeActiveMap (backend.cpp:78-205)
+//   LoopCompute     the per-keyframe step, ComputeCorrectPose and LoopCorrect's geometry (loopclosing.cpp:39-70, 147-243, 353-594)
 // SsxCompute is the product implementation: the C ABI of libssx.so on an MI355X, nothing else (no CPU fallback; the
 // constructor throws without a gfx950 device).  The interface exists so tests can run the same host logic against
 // the CPU oracle and compare whole trajectories.
 #pragma once
 #include <cstdint>
 #include <memory>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../include/ssx.h"
@@ -35,6 +38,31 @@ class BaWindow {
   // ids ascending; edge_pose / edge_point index into them; point_fixed = the flags the next solve uses (any may be null)
   virtual void Export(int64_t* kf_ids, int64_t* lm_ids, uint8_t* point_fixed, int32_t* edge_pose, int32_t* edge_point, double* edge_uv) = 0;
   virtual void Solve(ssx_ba_result& res) = 0;                                   // res.* in the order of Export
+  // LoopClosing::CorrectActivateKeyframeAndMappoint on the window where it lies (ssx_ba_window_loop_correct): every keyframe moves
+  // with the corrected current one, every observed landmark is re-anchored, the fused landmarks leave with their observations.
+  // res may be null.  An implementation without it cannot take part in loop closing.
+  virtual void LoopCorrect(int64_t cur_kf_id, const double* corrected_pose7, int n_fused, const int64_t* fused_ids, ssx_ba_window_loop_result* res)
+  {
+    (void)cur_kf_id; (void)corrected_pose7; (void)n_fused; (void)fused_ids; (void)res;
+    throw std::logic_error("BaWindow::LoopCorrect: this window cannot apply a loop correction");
+  }
+};
+
+// The library calls of the loop-closing thread (loopclosing.cpp:39-70, 147-243, 353-594), one method per call.  An object owns the
+// vocabulary and the keyframe database of ONE stream.
+class LoopCompute {
+ public:
+  virtual ~LoopCompute() = default;
+  // ssx_kfdb_process_keyframe: ProcessNewKeyframe + DetectLoop + MatchFeatures.  pairs = res.n_pairs x (current feature, loop feature),
+  // ascending; the keyframe stays pending on the device until AddPending or the next ProcessKeyframe.
+  virtual void ProcessKeyframe(int64_t kf_id, const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels,
+                               int min_db_size, int min_id_gap, float threshold, ssx_kfdb_step_result& res, std::vector<int32_t>& pairs) = 0;
+  virtual void AddPending() = 0;                                                // ssx_kfdb_add_pending (AddToKeyframeDatabase)
+  // ssx_loop_compute_pose with the reference's 100 hypotheses: kept[i] = pair i is still in set_valid_feature_matches_
+  virtual void ComputePose(int n_pairs, const double* loop_xyz, const uint8_t* has_point, const double* cur_uv, const double* T_cur, const double* T_loop,
+                           const double* K4, uint8_t* kept, ssx_loop_pose_result& out) = 0;
+  // ssx_loop_correct with optimize(20): prob.poses / prob.points are corrected in place
+  virtual void LoopCorrect(const ssx_loop_correct_problem& prob, ssx_loop_correct_result& res) = 0;
 };
 
 class Compute {
@@ -69,9 +97,16 @@ class Compute {
     (void)K4; (void)cam_ext14; (void)opt;
     return nullptr;
   }
+  // the loop-closing calls on a context of their own, with the vocabulary of DBOW2.VOC.Path loaded (throws when it cannot be read),
+  // or null when the implementation has none (the CPU oracle of the tests: the system then runs without loop closing)
+  virtual std::unique_ptr<LoopCompute> MakeLoopCompute(const std::string& voc_path)
+  {
+    (void)voc_path;
+    return nullptr;
+  }
 };
 
-// device: GPU ordinal.  Three contexts (streams): per-frame work, the temporal LK chain, the backend.
+// device: GPU ordinal.  Three contexts (streams): per-frame work, the temporal LK chain, the backend; loop closing adds a fourth.
 std::unique_ptr<Compute> MakeSsxCompute(int device = 0);
 
 }  // namespace ssx::host

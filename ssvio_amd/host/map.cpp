@@ -53,6 +53,7 @@ KeyFramePtr Map::CreateKF(const FramePtr& frame)
   kf->frame_id = frame->frame_id;
   kf->timestamp = frame->timestamp;
   kf->features_left = frame->features_left;
+  if (keep_keyframe_images) kf->left_image = frame->left_image;
   for (auto& feat : kf->features_left) {
     feat->keyframe = (long)kf->key_frame_id;
     if (MapPointPtr mp = Lock(feat)) mp->AddObservation(feat);
@@ -129,6 +130,49 @@ void Map::RemoveMapPoint(const MapPointPtr& mp)
 {
   all_map_points_.erase(mp->id);
   active_map_points_.erase(mp->id);
+}
+
+// loopclosing.cpp:427-453, pointer for pointer (tools/mapmodel.py: ActiveMap.loop_correct is the same text in Python):
+//   both map points alive   every observation of the current map point is appended to the loop map point with AddObservation --
+//                           NOT AddActiveObservation: the loop map point does not enter the active map here -- and re-pointed at it;
+//                           the current map point leaves the map (RemoveMapPoint).  Its own lists are left as they are, like the
+//                           reference leaves them: nothing refers to it any more.
+//   otherwise               the current feature is pointed at the loop map point, which may be null (:451).
+// One deliberate deviation: when the current feature's map point IS the loop feature's map point (a track that lasted from the
+// loop keyframe to the current one), the reference appends to the very list it iterates (:441-446) and never returns.  Such a pair
+// is already fused: it is skipped and counted.
+// A second one: the reference lets two features of the current keyframe end up on ONE loop map point (two pairs that name the same
+// loop feature, or a loop map point another feature of the keyframe already tracks).  The next keyframe would then observe that map
+// point twice, which the backend's resident window cannot hold (one observation per keyframe, map point and camera; Backend refuses
+// such a keyframe).  The first feature keeps the map point; a later pair that would give it to a second feature is skipped and counted.
+Map::LoopFusion Map::FuseLoopMapPoints(const KeyFramePtr& current, const KeyFramePtr& loop, const std::vector<int32_t>& pairs)
+{
+  LoopFusion out;
+  std::unordered_map<unsigned long, const Feature*> holder;            // map point -> the feature of the current keyframe that names it
+  for (auto& feat : current->features_left)
+    if (MapPointPtr mp = Lock(feat)) holder.emplace(mp->id, feat.get());
+  for (size_t i = 0; i + 1 < pairs.size(); i += 2) {
+    const FeaturePtr& cur_feat = current->features_left.at((size_t)pairs[i]);
+    const FeaturePtr& loop_feat = loop->features_left.at((size_t)pairs[i + 1]);
+    MapPointPtr loop_mp = Lock(loop_feat), current_mp = Lock(cur_feat);
+    if (loop_mp) {
+      auto h = holder.find(loop_mp->id);
+      if (h != holder.end() && h->second != cur_feat.get()) { ++out.duplicate_skipped; continue; }
+      if (current_mp != loop_mp) holder[loop_mp->id] = cur_feat.get();
+    }
+    if (current_mp && loop_mp) {
+      if (current_mp == loop_mp) { ++out.same_point_skipped; continue; }
+      for (auto& feat : current_mp->observations) {
+        loop_mp->AddObservation(feat);
+        feat->map_point = (long)loop_mp->id;
+      }
+      RemoveMapPoint(current_mp);
+      out.removed.push_back(current_mp->id);
+    } else {
+      cur_feat->map_point = loop_mp ? (long)loop_mp->id : kNoMapPoint;
+    }
+  }
+  return out;
 }
 
 void Map::RemoveAllOutlierMapPoints()

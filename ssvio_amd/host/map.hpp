@@ -10,6 +10,7 @@
 // arrays of ssx_ba_problem without chasing pointers.  Keyframes and map points stay in std::unordered_map keyed by id
 // like the reference: Map::RemoveOldActiveKeyframe depends on that container's iteration order.
 #pragma once
+#include <cstdint>
 #include <list>
 #include <memory>
 #include <mutex>
@@ -63,6 +64,12 @@ struct KeyFrame {
   std::vector<FeaturePtr> features_left;
   long last_key_frame = -1;
   SE3 relative_pose_to_last_kf;
+  // loop closing (keyframe.hpp: image_left_, loop_key_frame_, relative_pose_to_loop_KF_).  The image is held only until the loop
+  // step has processed the keyframe (its descriptors then live in the keyframe database on the device) and is released there:
+  // the map does not keep the images of a sequence.  Null when loop closing is off.
+  ImagePtr left_image;
+  long loop_key_frame = -1;
+  SE3 relative_pose_to_loop_kf;
 };
 using KeyFramePtr = std::shared_ptr<KeyFrame>;
 
@@ -91,10 +98,22 @@ class Map {
   void AddOutlierMapPoint(unsigned long id) { outlier_map_points_.push_back(id); }
   void RemoveAllOutlierMapPoints();
 
+  // The map fusion of LoopClosing::CorrectActivateKeyframeAndMappoint (loopclosing.cpp:427-453): pairs = n x (current feature index,
+  // loop feature index) into the two keyframes' features_left.  Returns the ids of the current keyframe's map points that were merged
+  // into a loop map point and removed (Map::RemoveMapPoint), in pair order.
+  struct LoopFusion {
+    std::vector<unsigned long> removed;
+    int same_point_skipped = 0;      // pairs whose two features already name the same map point (see map.cpp)
+    int duplicate_skipped = 0;       // pairs that would put a second feature of the current keyframe on one map point (see map.cpp)
+  };
+  LoopFusion FuseLoopMapPoints(const KeyFramePtr& current, const KeyFramePtr& loop, const std::vector<int32_t>& pairs);
+
   // Map::mmutex_map_update_ of the reference (map.hpp:66): the front-end holds it while it tracks a frame, the
   // backend while it inserts a keyframe, reads the active window and writes an optimisation back.  Only contended
   // when the backend runs on its own thread (Backend.Async).
   std::mutex update_mutex;
+  // CreateKF hands the frame's left image to the keyframe (KeyFrame::left_image): set when loop closing is attached
+  bool keep_keyframe_images = false;
 
   const MapPointsType& GetAllMapPoints() const { return all_map_points_; }
   const KeyFramesType& GetAllKeyFrames() const { return all_key_frames_; }

@@ -3,7 +3,7 @@
 // save the keyframe trajectory in TUM format.  Same two flags (gflags spelling), plus a frame limit and an output path.
 //
 //   ssx_run_kitti --config_yaml_path=cfg.yaml --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=out.txt]
-//                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--warmup=1]
+//                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--warmup=1] [--loop_log=FILE]
 // The PNG pairs are decoded ahead of the tracker on worker threads (StereoPrefetcher); everything else is the
 // reference's single loop.  --streams=K runs K independent copies of the loop in K threads of this process (each with
 // its own System, GPU contexts and prefetcher) on the same sequence: a single stream is latency-bound, several fill the
@@ -15,6 +15,10 @@
 // --warmup=1 (default): System::Warmup before the first frame -- the library's kernels are loaded and its workspaces sized on a
 // synthetic frame, outside the frame loop and its clock (a stream's first window solve alone costs 15 - 20 ms cold, 0.5 ms warm);
 // the trajectory is the same with --warmup=0.
+// --loop_log=FILE (with Loop.Closing.Open: 1): one line per keyframe the loop step handled (stream k of --streams writes FILE.k):
+//   kf <id> db <database size> found <0|1> loop <id|-1> score <float, 9 digits> pairs <n> pose <ssx_loop_verdict|-1> with_point <n> inliers <n>
+//   error <17 digits> need_correct <0|1> corrected <0|1> fused <n> same_point <n> pg_iters <n> moved_active <n> moved_other <n> skipped <n> duplicate <n>
+// Loop closing is per stream; batching the loop step over streams does not exist, so --batched >= 1 with Loop.Closing.Open is refused.
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -23,6 +27,7 @@
 #include <cstring>
 #include <exception>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -42,20 +47,34 @@ bool flag(const char* arg, const char* name, std::string& out)
   return true;
 }
 
+void WriteLoopLog(ssx::host::System& sys, const std::string& path)
+{
+  if (path.empty() || !sys.loop_closing()) return;
+  sys.WaitIdle();
+  std::FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) throw std::runtime_error("--loop_log: cannot write " + path);
+  for (const auto& r : sys.loop_closing()->records())
+    std::fprintf(f, "kf %lu db %d found %d loop %ld score %.9g pairs %d pose %d with_point %d inliers %d error %.17g need_correct %d corrected %d fused %d same_point %d "
+                 "pg_iters %d moved_active %d moved_other %d skipped %d duplicate %d\n", r.kf_id, r.db_size, r.found, r.loop_kf_id, (double)r.score, r.pairs, r.verdict, r.with_point,
+                 r.inliers, r.error, r.need_correct, r.corrected, r.fused, r.same_point_skipped, r.pg_iterations, r.active_points_moved, r.other_points_moved,
+                 r.points_skipped, r.duplicate_skipped);
+  std::fclose(f);
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
-  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s;
+  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log;
   for (int i = 1; i < argc; ++i) {
     if (flag(argv[i], "config_yaml_path", config) || flag(argv[i], "kitti_dataset_path", dataset) || flag(argv[i], "max_frames", max_frames_s) ||
-        flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s))
+        flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s) || flag(argv[i], "loop_log", loop_log))
       continue;
     std::fprintf(stderr, "unknown argument %s\n", argv[i]);
     return 2;
   }
   if (config.empty() || dataset.empty()) {
-    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0]\n",
+    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--warmup=1] [--loop_log=<file>]\n",
                  argv[0]);
     return 2;
   }
@@ -86,6 +105,11 @@ int main(int argc, char** argv)
     std::printf("Num Images: %zu\n", num_images);
 
     const int streams = streams_s.empty() ? 1 : std::max(1, std::atoi(streams_s.c_str()));
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Loop.Closing.Open") != 0) {
+      std::fprintf(stderr, "--batched=%s with Loop.Closing.Open: 1 is not supported: the loop step is not batched over streams (run --streams unbatched, or switch loop closing off)\n",
+                   batched_s.c_str());
+      return 2;
+    }
     const bool warmup = warmup_s.empty() || std::atoi(warmup_s.c_str()) != 0;
     if (streams > 1) {
       const int device = device_s.empty() ? 0 : std::atoi(device_s.c_str());
@@ -140,13 +164,14 @@ int main(int argc, char** argv)
               if (pair.left->empty() || pair.right->empty()) throw std::runtime_error("Failed to load image " + sq.left_paths[ni]);
               sys.RunStep(pair.left, pair.right, sq.timestamps[ni]);
             }
-            sys.backend().WaitIdle();
+            sys.WaitIdle();
             t_end[k] = clk::now();
             seconds[k] = std::chrono::duration<double>(t_end[k] - t0).count();
             keyframes[k] = sys.map().GetAllKeyFrames().size();
             fin.b = nullptr;
             if (batcher) batcher->Finish(k);                                  // before the trajectory is written and the System is torn down
             if (!trajectory.empty()) sys.SaveTrajectoryTUM(trajectory + "." + std::to_string(k));
+            if (!loop_log.empty()) WriteLoopLog(sys, loop_log + "." + std::to_string(k));
           } catch (const std::exception& e) {
             errors[k] = e.what();
             arrive();
@@ -207,6 +232,7 @@ int main(int argc, char** argv)
       if (ni % 100 == 99) std::printf("Has processed %zu frames.\n", ni + 1);
     }
     system.SaveTrajectoryTUM(trajectory);
+    WriteLoopLog(system, loop_log);
 
     const StageTimes& st = system.frontend().times();
     const Backend::Stats& bs = system.backend().stats();
@@ -230,6 +256,14 @@ int main(int argc, char** argv)
     if (bs.windows)
       std::printf("  per window on the host side: map + window edits %.3f ms, export + solve call %.3f ms, write-back %.3f ms\n", 1e3 * bs.t_insert / bs.windows,
                   1e3 * bs.t_solve / bs.windows, 1e3 * bs.t_apply / bs.windows);
+    if (LoopClosing* lc = system.loop_closing()) {
+      const LoopClosing::Stats& ls = lc->stats();
+      long found = 0;
+      for (const auto& r : lc->records()) found += r.found;
+      std::printf("  loop closing%s: %ld steps, %.3f ms/step (corrections included), %ld keyframes dropped by the 5-id rule, %ld loops found, %ld corrections, %.3f ms/correction\n",
+                  lc->async() ? " (own thread)" : "", ls.steps, 1e3 * ls.t_step / std::max(1L, ls.steps), ls.dropped, found, ls.corrections,
+                  1e3 * ls.t_correct / std::max(1L, ls.corrections));
+    }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "fatal: %s\n", e.what());
     return 1;

@@ -1,4 +1,5 @@
 // ssvio_amd/host/ssx_compute.cpp -- Compute on libssx.so (see compute.hpp)
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -35,15 +36,70 @@ class SsxBaWindow final : public BaWindow {
     ctx_.check(ssx_ba_window_export(win_, kf_ids, nullptr, nullptr, lm_ids, nullptr, point_fixed, edge_pose, edge_point, edge_uv, nullptr));
   }
   void Solve(ssx_ba_result& res) override { ctx_.check(ssx_ba_window_solve(win_, &res)); }
+  void LoopCorrect(int64_t cur_kf_id, const double* corrected_pose7, int n_fused, const int64_t* fused_ids, ssx_ba_window_loop_result* res) override
+  {
+    ctx_.check(ssx_ba_window_loop_correct(win_, cur_kf_id, corrected_pose7, n_fused, n_fused > 0 ? fused_ids : nullptr, res));
+  }
 
  private:
   ssx::Context& ctx_;
   ssx_ba_window* win_ = nullptr;
 };
 
+// The loop-closing calls of one stream: a context of its own (the loop thread's), the vocabulary, the resident keyframe database.
+class SsxLoopCompute final : public LoopCompute {
+ public:
+  SsxLoopCompute(int device, const std::string& voc_path) : ctx_(device)
+  {
+    if (ssx_voc_load_text(ctx_.get(), voc_path.c_str(), &voc_) != SSX_OK)
+      throw std::runtime_error("DBOW2.VOC.Path: cannot read the vocabulary \"" + voc_path + "\": " + ssx_last_error(ctx_.get()));
+    const ssx_status st = ssx_kfdb_create(ctx_.get(), 256, &db_);
+    if (st != SSX_OK) {
+      ssx_voc_destroy(voc_);
+      ctx_.check(st);
+    }
+  }
+  ~SsxLoopCompute() override
+  {
+    ssx_kfdb_destroy(db_);
+    ssx_voc_destroy(voc_);
+  }
+  void ProcessKeyframe(int64_t kf_id, const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, int min_db_size,
+                       int min_id_gap, float threshold, ssx_kfdb_step_result& res, std::vector<int32_t>& pairs) override
+  {
+    pairs.resize(2 * std::max<size_t>(1024, features.size() * (size_t)std::max(pyramid_levels, 1)));
+    auto call = [&] {
+      return ssx_kfdb_process_keyframe(db_, voc_, kf_id, img.ptr(), img.cols, img.rows, img.cols, &prm, (int32_t)features.size(), features.data(), pyramid_levels,
+                                       min_db_size, min_id_gap, threshold, (int32_t)(pairs.size() / 2), pairs.data(), &res);
+    };
+    ssx_status st = call();
+    if (st == SSX_ERR_CAPACITY) {                                        // a larger loop keyframe: the count is known now
+      pairs.resize(2 * (size_t)res.n_pairs);
+      st = call();
+    }
+    ctx_.check(st);
+    pairs.resize(2 * (size_t)res.n_pairs);
+  }
+  void AddPending() override { ctx_.check(ssx_kfdb_add_pending(db_)); }
+  void ComputePose(int n_pairs, const double* loop_xyz, const uint8_t* has_point, const double* cur_uv, const double* T_cur, const double* T_loop,
+                   const double* K4, uint8_t* kept, ssx_loop_pose_result& out) override
+  {
+    ctx_.check(ssx_loop_compute_pose(ctx_.get(), n_pairs, loop_xyz, has_point, cur_uv, T_cur, T_loop, K4, 100, 0, kept, &out));   // :205-206: 100 iterations
+  }
+  void LoopCorrect(const ssx_loop_correct_problem& prob, ssx_loop_correct_result& res) override
+  {
+    ctx_.check(ssx_loop_correct(ctx_.get(), &prob, 20, &res));           // :533 optimize(20)
+  }
+
+ private:
+  ssx::Context ctx_;
+  ssx_vocabulary* voc_ = nullptr;
+  ssx_kf_database* db_ = nullptr;
+};
+
 class SsxCompute final : public Compute {
  public:
-  explicit SsxCompute(int device) : frame_(device), chain_(device), backend_(device) {}
+  explicit SsxCompute(int device) : device_(device), frame_(device), chain_(device), backend_(device) {}
 
   void Detect(const Image& img, const uint8_t* mask, const ssx_orb_params& prm, std::vector<ssx_keypoint>& kps) override
   {
@@ -122,7 +178,10 @@ class SsxCompute final : public Compute {
     return std::make_unique<SsxBaWindow>(backend_, K4, cam_ext14, opt);    // (the window must be destroyed before this Compute)
   }
 
+  std::unique_ptr<LoopCompute> MakeLoopCompute(const std::string& voc_path) override { return std::make_unique<SsxLoopCompute>(device_, voc_path); }
+
  private:
+  int device_;
   ssx::Context frame_, chain_, backend_;
   uint64_t chain_next_id_ = 0;
   int chain_rows_ = 0, chain_cols_ = 0;

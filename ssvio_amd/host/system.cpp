@@ -2,6 +2,7 @@
 #include "system.hpp"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
@@ -29,6 +30,40 @@ System::System(const std::string& config_file_path, std::unique_ptr<Compute> com
   backend_ = std::make_unique<Backend>(setting_, *compute_, map_, left_camera_, right_camera_);
   frontend_ = std::make_unique<FrontEnd>(setting_, *compute_, map_, left_camera_, right_camera_);
   frontend_->SetBackend(backend_.get());
+
+  // system.cpp:17-41
+  if (setting_.Get<int>("Loop.Closing.Open") != 0) {
+    const std::string voc_path = setting_.Get<std::string>("DBOW2.VOC.Path");
+    std::unique_ptr<LoopCompute> loop_compute;
+    try {
+      loop_compute = compute_->MakeLoopCompute(voc_path);
+    } catch (const std::exception& e) {
+      const std::string what = e.what();
+      throw std::runtime_error(what.find("DBOW2.VOC.Path") != std::string::npos ? what : "System: DBOW2.VOC.Path \"" + voc_path + "\": " + what);
+    }
+    if (!loop_compute) {
+      std::fprintf(stderr, "warning: Loop.Closing.Open is set, but this Compute has no loop closing: running without it\n");
+    } else {
+      loop_closing_ = std::make_unique<LoopClosing>(setting_, std::move(loop_compute), map_, left_camera_);
+      loop_closing_->SetBackend(backend_.get());
+      FrontEnd* fe = frontend_.get();
+      loop_closing_->SetReferenceKeyFrame([fe] { return fe->reference_kf() ? (long)fe->reference_kf()->key_frame_id : -1L; });
+      map_->keep_keyframe_images = true;                              // each until the loop step has processed its keyframe
+      backend_->SetLoopClosing(loop_closing_.get());
+    }
+  }
+}
+
+// the two threads come to rest in the order of the data flow (frontend -> backend -> loop closing) before any member goes
+System::~System()
+{
+  try { WaitIdle(); } catch (...) {}
+}
+
+void System::WaitIdle()
+{
+  if (backend_) backend_->WaitIdle();
+  if (loop_closing_) loop_closing_->WaitIdle();
 }
 
 bool System::RunStep(ImagePtr left, ImagePtr right, double timestamp)
@@ -148,6 +183,7 @@ void System::Warmup(int rows, int cols)
 void System::SaveTrajectoryTUM(const std::string& path_in) const
 {
   backend_->WaitIdle();                                               // asynchronous backend: let the last windows finish
+  if (loop_closing_) loop_closing_->WaitIdle();                       // and the loop thread its last keyframes
   std::lock_guard<std::mutex> map_lock(map_->update_mutex);
   const std::string path = path_in.empty() ? setting_.Get<std::string>("Trajectory.Save.Path") : path_in;
   std::ofstream out(path, std::ios_base::out | std::ios_base::trunc);

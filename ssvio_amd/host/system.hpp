@@ -1,6 +1,7 @@
 // ssvio_amd/host/system.hpp -- ssvio::System without the viewer (/root/reference/src/ssvio/system.cpp:9-128):
 // reads the settings file, builds the stereo rig (GenerateSteroCamera :54-113), the two extractor settings
-// (GenerateORBextractor :115-128), Map, Backend, FrontEnd; RunStep = FrontEnd::GrabSteroImage (:46-52).
+// (GenerateORBextractor :115-128), Map, Backend, FrontEnd and -- with Loop.Closing.Open set -- LoopClosing (:17-41);
+// RunStep = FrontEnd::GrabSteroImage (:46-52).
 // SaveTrajectoryTUM is the trajectory writer the reference keeps in its viewer
 // (/root/reference/src/ui/pangolin_window_impl.cpp:362-395): every keyframe in id order,
 // "timestamp tx ty tz qx qy qz qw" of T_wc, fixed notation with 6 decimals.
@@ -11,6 +12,7 @@
 #include "backend.hpp"
 #include "compute.hpp"
 #include "frontend.hpp"
+#include "loopclosing.hpp"
 #include "map.hpp"
 #include "setting.hpp"
 
@@ -19,7 +21,11 @@ namespace ssx::host {
 class System {
  public:
   // compute: the implementation to run on; null = MakeSsxCompute(device)
+  // Loop.Closing.Open != 0: LoopClosing is built on Compute::MakeLoopCompute(DBOW2.VOC.Path) and attached to the backend; throws,
+  // naming the key, when the vocabulary cannot be read.  A Compute without loop closing (MakeLoopCompute returns null: the CPU
+  // oracle of the tests) gets one warning line and a system without it.
   explicit System(const std::string& config_file_path, std::unique_ptr<Compute> compute = nullptr, int device = 0);
+  ~System();
 
   bool RunStep(ImagePtr left, ImagePtr right, double timestamp);
   // One synthetic keyframe + two tracked frames of rows x cols through every compute call the loop makes (masked detection, stereo
@@ -33,6 +39,8 @@ class System {
   Map& map() { return *map_; }
   FrontEnd& frontend() { return *frontend_; }
   Backend& backend() { return *backend_; }
+  LoopClosing* loop_closing() { return loop_closing_.get(); }              // null: loop closing is off
+  void WaitIdle();                                                         // the backend's thread, then the loop thread
 
  private:
   Setting setting_;
@@ -41,6 +49,7 @@ class System {
   std::shared_ptr<Map> map_;
   std::unique_ptr<Backend> backend_;
   std::unique_ptr<FrontEnd> frontend_;
+  std::unique_ptr<LoopClosing> loop_closing_;
 };
 
 }  // namespace ssx::host

@@ -329,11 +329,15 @@ def fast9_density(img, t=20):
     return float((arc(ring > c + t) | arc(ring < c - t)).mean())
 
 
-def make_lateral_sequence(n_frames=12, step=0.12, seed=0, h=KITTI_H, w=KITTI_W, n_blobs=4000, bf=KITTI_BF, baseline=KITTI_BASELINE):
+def make_lateral_sequence(n_frames=12, step=0.12, seed=0, h=KITTI_H, w=KITTI_W, n_blobs=4000, bf=KITTI_BF, baseline=KITTI_BASELINE, alphas=None,
+                          right_alpha=1.0):
     """A stereo SEQUENCE of the make_stereo_pair scene seen from a rig that moves sideways (along +x, the direction of
     the right camera) by `step` baselines per frame: a camera at lateral offset a * baseline sees the texture shifted
     by a * disparity, so frame k is left = base(u + a_k d), right = base(u + (a_k + 1) d).  Returns
-    (frames [(left, right)], T_cw [n,7] ground-truth poses with world = camera 0, disp)."""
+    (frames [(left, right)], T_cw [n,7] ground-truth poses with world = camera 0, disp).
+    alphas: the lateral offsets in baselines, frame by frame, instead of step * k (n_frames is then their number).
+    right_alpha: the right camera sits this many baselines beside the left one (1 = the rig the poses and `bf` describe; any other
+    value renders a rig whose baseline the settings do not state)."""
     base, _, disp = make_stereo_pair(seed=seed, h=h, w=w, n_blobs=n_blobs, bf=bf)
     rng = np.random.default_rng(5000 + seed)
     lf = base.astype(np.float32)
@@ -348,9 +352,9 @@ def make_lateral_sequence(n_frames=12, step=0.12, seed=0, h=KITTI_H, w=KITTI_W, 
         img += rng.normal(0, 1.5, img.shape).astype(np.float32)
         return np.clip(np.rint(img), 0, 255).astype(np.uint8)
     frames, poses = [], []
-    for k in range(n_frames):
-        a = step * k
-        frames.append((render(a), render(a + 1.0)))
+    offsets = [step * k for k in range(n_frames)] if alphas is None else [float(a) for a in alphas]
+    for a in offsets:
+        frames.append((render(a), render(a + right_alpha)))
         poses.append(np.array([0, 0, 0, 1, -a * baseline, 0, 0], dtype=np.float64))       # T_cw: camera centre at (+a b, 0, 0)
     return frames, np.array(poses), disp
 
