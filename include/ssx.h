@@ -772,6 +772,36 @@ SSX_API ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary
                                              int32_t n_features, const ssx_keypoint* features, int32_t pyramid_levels,
                                              int32_t min_db_size, int32_t min_id_gap, float threshold, int32_t pairs_cap,
                                              int32_t* pairs_out, ssx_kfdb_step_result* res);
+/* The same step for n databases of ONE context in one call (one keyframe of each of n streams): one launch chain and one
+ * synchronisation for all jobs, and one more launch pair and a second synchronisation when at least one job found a loop;
+ * neither number depends on n.  Every job has a database of its own; all of them and the vocabulary belong to one
+ * context, the images share rows, cols and stride.  commit_pending != 0: ssx_kfdb_add_pending(db) first, inside the same
+ * chain (growing that database's arena or table adds that growth's own synchronisation).  Per job, *res, pairs_out and the
+ * keyframe left pending in job.db are bit for bit what ssx_kfdb_add_pending (when asked for) + ssx_kfdb_process_keyframe
+ * leave, whatever n is and wherever the job stands in the table; afterwards the single-database entry points work on every
+ * database as before.  images_on_device != 0: the images are read where they lie (device or pinned host memory).
+ * Rejected before anything is touched, pending keyframes included: n < 0, a missing db / res / status_out / image, two jobs
+ * with one database, a database of another context, differing strides, commit_pending with nothing pending or an id that
+ * does not ascend (SSX_ERR_INVALID_ARG), n_features * pyramid_levels > 65535 (SSX_ERR_UNSUPPORTED).  n == 0: SSX_OK.
+ * What depends on the data goes to the job's *status_out -- SSX_ERR_CAPACITY when pairs_cap is too small (the keyframe
+ * still pending), SSX_ERR_INVALID_ARG when the winner was stored without descriptors (nothing pending) -- while the other
+ * jobs complete; the call returns the first status that is not SSX_OK, so a return value that no job's status carries is a
+ * failure of the whole call.  A HIP error (SSX_ERR_HIP) leaves the stored keyframes of every database as they were and, unless
+ * it struck while an arena or table was grown before the call began on the databases, nothing pending. */
+typedef struct ssx_kfdb_step_job {
+  ssx_kf_database* db;
+  int64_t kf_id;
+  const uint8_t* img; int32_t stride;
+  int32_t n_features; const ssx_keypoint* features;
+  int32_t commit_pending;
+  int32_t pairs_cap; int32_t* pairs_out;
+  ssx_kfdb_step_result* res;
+  int32_t* status_out;            /* this job's ssx_status */
+} ssx_kfdb_step_job;
+SSX_API ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const ssx_kfdb_step_job* jobs, int32_t rows,
+                                                   int32_t cols, const ssx_orb_params* prm, int32_t pyramid_levels,
+                                                   int32_t min_db_size, int32_t min_id_gap, float threshold,
+                                                   int32_t images_on_device);
 /* AddToKeyframeDatabase (:646-649) for the keyframe of the last successful ssx_kfdb_process_keyframe: stored exactly as
  * ssx_kfdb_add(kf_id, its BowVector, its descriptors, its class ids) would store it, device to device.  The same
  * id-must-ascend rule; SSX_ERR_INVALID_ARG when nothing is pending (a keyframe is committed once).  ssx_kfdb_add and

@@ -374,11 +374,61 @@ class KeyframeDatabase {
     ssx_kfdb_size(db_, &n, nullptr, nullptr);
     return n;
   }
+  ssx_kf_database* get() const { return db_; }
+  Context& context() const { return ctx_; }
 
  private:
   Context& ctx_;
   ssx_kf_database* db_ = nullptr;
 };
+
+// One keyframe of each of several streams: KeyframeDatabase::ProcessNewKeyframe for every entry in ONE call (ssx_kfdb_process_keyframe_batch:
+// one launch chain and one synchronisation for all of them, two when a loop was found).  The databases and the vocabulary belong to one
+// Context, the images share rows, cols and stride.  add_to_database_first: AddToKeyframeDatabase() of the keyframe the database's last
+// step left pending, inside the same call.  Per entry the bytes of the single call.
+struct KeyframeStepRequest {
+  KeyframeDatabase* database;
+  unsigned long key_frame_id;
+  const uint8_t* image;
+  const std::vector<ssx_keypoint>* features;
+  bool add_to_database_first;
+};
+inline std::vector<KeyframeDatabase::KeyframeStep> ProcessNewKeyframes(const ORBVocabulary& voc, const KeyframeStepRequest* requests, size_t n, int stride, int rows,
+                                                                       int cols, const ORBextractor& extractor, float loop_threshold_heigher, int pyramid_levels = 8,
+                                                                       int min_db_size = 50, int min_id_gap = 20)
+{
+  if (!voc.get()) throw std::invalid_argument("ProcessNewKeyframes: no vocabulary loaded");
+  std::vector<KeyframeDatabase::KeyframeStep> out(n);
+  if (n == 0) return out;
+  std::vector<std::vector<int32_t>> pairs(n);
+  std::vector<int32_t> status(n, SSX_OK);
+  std::vector<ssx_kfdb_step_job> jobs(n);
+  for (size_t j = 0; j < n; ++j) {
+    const KeyframeStepRequest& q = requests[j];
+    if (!q.database || !q.features) throw std::invalid_argument("ProcessNewKeyframes: a request without database or features");
+    pairs[j].resize(2 * std::max<size_t>(4096, q.features->size() * (size_t)pyramid_levels));
+    jobs[j] = ssx_kfdb_step_job{q.database->get(), (int64_t)q.key_frame_id, q.image, stride, (int32_t)q.features->size(), q.features->data(),
+                                q.add_to_database_first ? 1 : 0, (int32_t)(pairs[j].size() / 2), pairs[j].data(), &out[j].result, &status[j]};
+  }
+  Context& ctx = requests[0].database->context();
+  ssx_status st = ssx_kfdb_process_keyframe_batch(voc.get(), (int32_t)n, jobs.data(), rows, cols, &extractor.params(), pyramid_levels, min_db_size, min_id_gap,
+                                                  loop_threshold_heigher, 0);
+  for (size_t j = 0; j < n && st == SSX_ERR_CAPACITY; ++j) {
+    if (status[j] != SSX_ERR_CAPACITY) continue;             // a larger loop keyframe: the count is known now, that step once more (its commit is done)
+    pairs[j].resize((size_t)out[j].result.n_pairs * 2);
+    jobs[j].commit_pending = 0; jobs[j].pairs_cap = out[j].result.n_pairs; jobs[j].pairs_out = pairs[j].data();
+    const ssx_status again = ssx_kfdb_process_keyframe_batch(voc.get(), 1, &jobs[j], rows, cols, &extractor.params(), pyramid_levels, min_db_size, min_id_gap,
+                                                             loop_threshold_heigher, 0);
+    if (again != SSX_OK) ctx.check(again);
+  }
+  for (size_t j = 0; j < n; ++j)
+    if (status[j] != SSX_OK) ctx.check((ssx_status)status[j]);
+  if (st != SSX_OK && st != SSX_ERR_CAPACITY) ctx.check(st);
+  for (size_t j = 0; j < n; ++j)
+    for (int32_t i = 0; i < out[j].result.n_pairs; ++i)
+      out[j].set_valid_feature_matches.emplace_hint(out[j].set_valid_feature_matches.end(), pairs[j][2 * i], pairs[j][2 * i + 1]);
+  return out;
+}
 
 // What LoopClosing::ComputeCorrectPose reads of one entry of set_valid_feature_matches_: the pair itself, the position of
 // loop_keyframe_->features_left_[loop_feature_id]->map_point_ (has_map_point = false when the weak_ptr has expired) and

@@ -195,6 +195,9 @@ SSX_API ssx_status ssx_pnp_debug_p3p(ssx_ctx* ctx, const double* K4, int32_t n, 
  * (the pairs are written by the kernel into mapped pinned memory: 8 bytes of header and 8 per pair).  Any output may be NULL. */
 SSX_API ssx_status ssx_kfdb_debug_last_step(const ssx_kf_database* db, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up,
                                             int64_t* bytes_down);
+/* the same for the context's last ssx_kfdb_process_keyframe_batch (all zero after a call that failed before its first synchronisation);
+ * the match table of the found jobs, read by the device from pinned memory, counts as bytes sent up */
+SSX_API ssx_status ssx_kfdb_debug_last_batch(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down);
 /* k_voc_words + k_kf_bow alone: the BowVector of n descriptors as the step assembles it on the device (ids ascending, values);
  * *n_entries = its size, SSX_ERR_CAPACITY when cap is smaller */
 SSX_API ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t cap, int32_t* ids_out, double* vals_out,

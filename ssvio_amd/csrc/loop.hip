@@ -38,12 +38,18 @@
 //                lane by lane over 64-entry chunks like the chain of k_kfdb_score.  Both sums are doubles whose value depends on the order
 //                of the additions, so neither is a tree.
 // k_kfdb_commit  the pending arrays into a blob of the arena and its row into the table.
+//
+// ssx_kfdb_process_keyframe_batch is that step for one keyframe of each of n databases of one context (the streams of a batched cohort) as
+// ONE launch chain: k_*_jobs are the same kernels indexed by a device job table (kf_batch.hpp) -- a workgroup (or a grid row) per job, the
+// counts read from the job's step header -- and call the very __device__ bodies of the single-call kernels, so the ordered double chains
+// are the same code.  A job may commit its previous pending keyframe first, inside the chain.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "ctx.hpp"
+#include "kf_batch.hpp"
 #include "orb_ws.hpp"
 #include "voc.hpp"
 #include "../../include/ssx_test_hooks.h"
@@ -73,21 +79,11 @@ __device__ __forceinline__ double readlane_f64(double v, int l)
   return __hiloint2double(hi, lo);
 }
 
-// scores[row] = L1Scoring::score(query, row) for the first n_rows keyframes; *best = max over rows of (float bits << 32) | ~row
-template <bool LDS>
-__global__ __launch_bounds__(256) void k_kfdb_score(const char* arena, const KfRow* rows, int n_rows, const int32_t* q_ids, const double* q_vals, int nq,
-                                                    const int32_t* nq_dev, double* scores, unsigned long long* best)
+// The rows blockIdx.x * 4 + wave + gridDim.x * 4 k of the first n_rows keyframes against the query (qi, qv) of nq words.  Called once with
+// the query in LDS and once with it in global memory, so that after inlining each copy addresses one known memory.
+__device__ __forceinline__ void score_rows(const char* arena, const KfRow* rows, int n_rows, const int32_t* qi, const double* qv, int nq, double* scores,
+                                           unsigned long long* best)
 {
-  extern __shared__ double smem[];                            // [nq] values, then [nq] ids
-  if (nq_dev) nq = *nq_dev;                                   // the query was built on the device: `nq` was its bound (it sized the LDS)
-  const int32_t* qi = q_ids;
-  const double* qv = q_vals;
-  if (LDS) {
-    int32_t* si = reinterpret_cast<int32_t*>(smem + nq);
-    for (int k = threadIdx.x; k < nq; k += blockDim.x) { smem[k] = q_vals[k]; si[k] = q_ids[k]; }
-    __syncthreads();
-    qi = si; qv = smem;
-  }
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int top = nq > 0 ? 1 << (31 - __clz(nq)) : 0;          // the largest power of two <= nq
   unsigned long long best_key = 0;
@@ -146,6 +142,29 @@ __global__ __launch_bounds__(256) void k_kfdb_score(const char* arena, const KfR
   if (threadIdx.x == 0) {
     const unsigned long long k = max(max(s_best[0], s_best[1]), max(s_best[2], s_best[3]));
     if (k > *reinterpret_cast<volatile unsigned long long*>(best)) atomicMax(best, k);
+  }
+}
+
+// the query into LDS: [nq] values, then [nq] ids
+__device__ __forceinline__ void stage_query(double* smem, const int32_t* q_ids, const double* q_vals, int nq)
+{
+  int32_t* si = reinterpret_cast<int32_t*>(smem + nq);
+  for (int k = threadIdx.x; k < nq; k += blockDim.x) { smem[k] = q_vals[k]; si[k] = q_ids[k]; }
+  __syncthreads();
+}
+
+// scores[row] = L1Scoring::score(query, row) for the first n_rows keyframes; *best = max over rows of (float bits << 32) | ~row
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_kfdb_score(const char* arena, const KfRow* rows, int n_rows, const int32_t* q_ids, const double* q_vals, int nq,
+                                                    const int32_t* nq_dev, double* scores, unsigned long long* best)
+{
+  extern __shared__ double smem[];                            // [nq] values, then [nq] ids
+  if (nq_dev) nq = *nq_dev;                                   // the query was built on the device: `nq` was its bound (it sized the LDS)
+  if (LDS) {
+    stage_query(smem, q_ids, q_vals, nq);
+    score_rows(arena, rows, n_rows, reinterpret_cast<const int32_t*>(smem + nq), smem, nq, scores, best);
+  } else {
+    score_rows(arena, rows, n_rows, q_ids, q_vals, nq, scores, best);
   }
 }
 
@@ -225,8 +244,8 @@ __device__ __forceinline__ void sort_unique_pairs(unsigned long long* keys, int 
 }
 
 // hdr[0] = number of unique pairs, hdr[1] = minimum distance; pairs[2 k], pairs[2 k + 1] = (current class_id, loop class_id) ascending
-__global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const int* idx, const int* dist, int n_loop, const int32_t* loop_class, const int32_t* cur_class,
-                                                              unsigned long long* gkeys, int32_t* hdr, int32_t* pairs)
+__device__ __forceinline__ void pairs_block(const int* idx, const int* dist, int n_loop, const int32_t* loop_class, const int32_t* cur_class,
+                                            unsigned long long* gkeys, int32_t* hdr, int32_t* pairs)
 {
   __shared__ unsigned long long skeys[kSortLds];
   __shared__ int wave_sums[kPairsThreads / 64];
@@ -254,10 +273,24 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const int* idx, co
     sort_unique_pairs(gkeys, n_valid, npad, thr, idx, dist, n_loop, loop_class, cur_class, &s_fill, wave_sums, hdr, pairs, min_d);
 }
 
+__global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const int* idx, const int* dist, int n_loop, const int32_t* loop_class, const int32_t* cur_class,
+                                                              unsigned long long* gkeys, int32_t* hdr, int32_t* pairs)
+{
+  pairs_block(idx, dist, n_loop, loop_class, cur_class, gkeys, hdr, pairs);
+}
+
+// one workgroup per found loop of a batch of keyframe steps
+// (jobs == null: the one job of the launch is `one`)
+__global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs_jobs(const KfMatchJob* jobs, KfMatchJob one)
+{
+  const KfMatchJob j = jobs ? jobs[blockIdx.x] : one;
+  pairs_block(j.idx, j.dist, j.nl, j.loop_cls, j.cur_cls, j.keys, j.hdr, j.pairs);
+}
+
 
 // the kept keypoints of k_describe_at, their descriptors and class ids, in input order; *count = how many
-__global__ __launch_bounds__(kPairsThreads) void k_kf_compact(const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep, int n, ssx_keypoint* okps,
-                                                              uint8_t* odesc, int32_t* ocls, int32_t* count)
+__device__ __forceinline__ void compact_block(const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep, int n, ssx_keypoint* okps,
+                                              uint8_t* odesc, int32_t* ocls, int32_t* count)
 {
   __shared__ int wave_sums[kPairsThreads / 64];
   const int tid = threadIdx.x;
@@ -278,6 +311,12 @@ __global__ __launch_bounds__(kPairsThreads) void k_kf_compact(const ssx_keypoint
     ++pos;
   }
   if (tid == 0) *count = total;
+}
+
+__global__ __launch_bounds__(kPairsThreads) void k_kf_compact(const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep, int n, ssx_keypoint* okps,
+                                                              uint8_t* odesc, int32_t* ocls, int32_t* count)
+{
+  compact_block(kps, desc, keep, n, okps, odesc, ocls, count);
 }
 
 // The BowVector of n features from their (word, weight), as ssx_voc_transform assembles it (TemplatedVocabulary.h:1083-1124,
@@ -337,8 +376,8 @@ __device__ __forceinline__ void bow_assemble(unsigned long long* keys, int n, in
 }
 
 // ids / vals / *n_bow = the BowVector of the first *n_dev features; *best_zero = 0 for the k_kfdb_score that follows
-__global__ __launch_bounds__(kPairsThreads) void k_kf_bow(const int32_t* word, const double* weight, const int32_t* n_dev, int weighting, unsigned long long* gkeys,
-                                                          int32_t* ids, double* vals, int32_t* n_bow, unsigned long long* best_zero)
+__device__ __forceinline__ void bow_block(const int32_t* word, const double* weight, const int32_t* n_dev, int weighting, unsigned long long* gkeys,
+                                          int32_t* ids, double* vals, int32_t* n_bow, unsigned long long* best_zero)
 {
   __shared__ unsigned long long skeys[kSortLds];
   __shared__ int wave_sums[kPairsThreads / 64];
@@ -360,9 +399,15 @@ __global__ __launch_bounds__(kPairsThreads) void k_kf_bow(const int32_t* word, c
     bow_assemble(gkeys, n, n_valid, npad, word, weight, add, &s_fill, wave_sums, &s_norm, ids, vals, n_bow);
 }
 
+__global__ __launch_bounds__(kPairsThreads) void k_kf_bow(const int32_t* word, const double* weight, const int32_t* n_dev, int weighting, unsigned long long* gkeys,
+                                                          int32_t* ids, double* vals, int32_t* n_bow, unsigned long long* best_zero)
+{
+  bow_block(word, weight, n_dev, weighting, gkeys, ids, vals, n_bow, best_zero);
+}
+
 // the pending keyframe into its blob (layout at the top of the file, padding zeroed) and its row into the table
-__global__ __launch_bounds__(256) void k_kfdb_commit(char* blob, const int32_t* ids, const double* vals, const int32_t* cls, const uint8_t* desc, int n_bow,
-                                                     int n_desc, KfRow* row_out, KfRow row)
+__device__ __forceinline__ void commit_blob(char* blob, const int32_t* ids, const double* vals, const int32_t* cls, const uint8_t* desc, int n_bow, int n_desc,
+                                            KfRow* row_out, KfRow row)
 {
   const size_t o_v = blob_vals(n_bow), o_c = blob_class(n_bow), o_d = blob_desc(n_bow, n_desc), words = blob_bytes(n_bow, n_desc) / 4;
   const uint32_t* v32 = reinterpret_cast<const uint32_t*>(vals);
@@ -378,6 +423,59 @@ __global__ __launch_bounds__(256) void k_kfdb_commit(char* blob, const int32_t* 
     out[w] = x;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) *row_out = row;
+}
+
+__global__ __launch_bounds__(256) void k_kfdb_commit(char* blob, const int32_t* ids, const double* vals, const int32_t* cls, const uint8_t* desc, int n_bow,
+                                                     int n_desc, KfRow* row_out, KfRow row)
+{
+  commit_blob(blob, ids, vals, cls, desc, n_bow, n_desc, row_out, row);
+}
+
+// ---- the job-indexed forms of a batch of keyframe steps (ssx_kfdb_process_keyframe_batch; the job table: kf_batch.hpp) ----
+struct StepHdr { int32_t n_pyr, n_bow; unsigned long long best; };   // what the first synchronisation brings down, per keyframe step
+
+// grid (blocks, job): the jobs that commit move their previous pending keyframe into its blob, before anything overwrites it
+__global__ __launch_bounds__(256) void k_kfdb_commit_jobs(const KfJobDev* jobs)
+{
+  const KfJobDev& j = jobs[blockIdx.y];
+  if (!j.commit) return;
+  commit_blob(j.c_blob, j.c_ids, j.c_vals, j.c_cls, j.c_desc, j.c_n_bow, j.c_n_desc, static_cast<KfRow*>(j.c_row_out), KfRow{j.c_off, j.c_n_bow, j.c_n_desc});
+}
+
+// one workgroup per job: k_describe_at_jobs' outputs of the job into its pending arrays, the count into its header
+__global__ __launch_bounds__(kPairsThreads) void k_kf_compact_jobs(const KfJobDev* jobs, const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep,
+                                                                   StepHdr* hdr)
+{
+  const KfJobDev& j = jobs[blockIdx.x];
+  compact_block(kps + j.kp0, desc + (size_t)32 * j.kp0, keep + j.kp0, j.n_in, j.p_kps, j.p_desc, j.p_cls, &hdr[blockIdx.x].n_pyr);
+}
+
+// one workgroup per job: its BowVector from its slice of the concatenated words and weights, the count read from its header
+__global__ __launch_bounds__(kPairsThreads) void k_kf_bow_jobs(const KfJobDev* jobs, const int32_t* word, const double* weight, int weighting, StepHdr* hdr)
+{
+  const KfJobDev& j = jobs[blockIdx.x];
+  StepHdr* h = hdr + blockIdx.x;
+  bow_block(word + j.kp0, weight + j.kp0, &h->n_pyr, weighting, j.bow_keys, j.p_ids, j.p_vals, &h->n_bow, &h->best);
+}
+
+// grid (blocks, job): every job scores its own eligible prefix of its own database against the BowVector in its pending arrays.  The dynamic
+// LDS holds lds_cap query words (the call's largest bound, at most kQueryLds); a longer query is searched in global memory.
+__global__ __launch_bounds__(256) void k_kfdb_score_jobs(const KfJobDev* jobs, StepHdr* hdr, int lds_cap)
+{
+  extern __shared__ double smem[];
+  const KfJobDev& j = jobs[blockIdx.y];
+  const int n_rows = j.n_elig;
+  if ((int)blockIdx.x * 4 >= n_rows) return;                  // nothing eligible, or fewer rows than the largest job has
+  StepHdr* h = hdr + blockIdx.y;
+  const int nq = h->n_bow;
+  const char* arena = j.arena;
+  const KfRow* rows = static_cast<const KfRow*>(j.rows);
+  if (nq <= lds_cap) {
+    stage_query(smem, j.p_ids, j.p_vals, nq);
+    score_rows(arena, rows, n_rows, reinterpret_cast<const int32_t*>(smem + nq), smem, nq, j.scores, &h->best);
+  } else {
+    score_rows(arena, rows, n_rows, j.p_ids, j.p_vals, nq, j.scores, &h->best);
+  }
 }
 
 }  // namespace
@@ -659,8 +757,6 @@ ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int3
 // ---- the per-keyframe step ----------------------------------------------------------------------------------------------------------
 namespace {
 
-struct StepHdr { int32_t n_pyr, n_bow; unsigned long long best; };   // what the first synchronisation brings down
-
 // steps 3-4 on descriptors that lie on the device: words, then the BowVector; scratch for `bound` features
 struct BowScratch { int32_t* word; double* weight; unsigned long long* keys; };
 template <class F> void bow_scratch(F&& f, BowScratch& b, int bound)
@@ -839,7 +935,264 @@ ssx_status ssx_kfdb_pending(ssx_kf_database* db, int64_t* kf_id, int32_t kps_cap
   return SSX_OK;
 }
 
+// The keyframe steps of n databases of one context as ONE launch chain (the job-indexed kernels above and in orb.hip / voc.hip /
+// stereo.hip): validate everything, grow what the commits need, enqueue phase 1 for all jobs, one synchronisation, and phase 2 (match and
+// pairs of the found jobs) behind a second one.  The host mirrors of the databases change only after the first synchronisation succeeded.
+ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const ssx_kfdb_step_job* jobs, int32_t rows, int32_t cols, const ssx_orb_params* prm,
+                                           int32_t pyramid_levels, int32_t min_db_size, int32_t min_id_gap, float threshold, int32_t images_on_device)
+{
+  if (n < 0) return SSX_ERR_INVALID_ARG;
+  if (n == 0) return SSX_OK;
+  if (!voc || !jobs || !prm || rows <= 0 || cols <= 0 || pyramid_levels < 1 || pyramid_levels > ssxorb::MAX_LEVELS) return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = voc->ctx;
+  // ---- nothing is touched before every job has passed ----
+  std::vector<const ssx_kf_database*> seen;
+  for (int j = 0; j < n; ++j) {
+    const ssx_kfdb_step_job& q = jobs[j];
+    if (!q.db || !q.res || !q.status_out || !q.img || q.stride < cols || q.n_features < 0 || (q.n_features > 0 && !q.features) || q.pairs_cap < 0 ||
+        (q.pairs_cap > 0 && !q.pairs_out)) {
+      ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: a missing database / result / status / image / array, a stride below the width or a negative count", j);
+      return SSX_ERR_INVALID_ARG;
+    }
+    if (q.db->ctx != ctx) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: the database and the vocabulary belong to different contexts", j); return SSX_ERR_INVALID_ARG; }
+    if (q.stride != jobs[0].stride) { ctx->set_error("ssx_kfdb_process_keyframe_batch: the images of a call share one stride"); return SSX_ERR_INVALID_ARG; }
+    if (std::find(seen.begin(), seen.end(), q.db) != seen.end()) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d names the database of an earlier job", j); return SSX_ERR_INVALID_ARG; }
+    seen.push_back(q.db);
+    if ((int64_t)q.n_features * pyramid_levels > 65535) {
+      ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: %d features x %d levels: more than 65535 pyramid keypoints", j, q.n_features, pyramid_levels);
+      return SSX_ERR_UNSUPPORTED;
+    }
+    if (q.commit_pending) {
+      if (!q.db->pending.valid) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: commit_pending but no keyframe is pending", j); return SSX_ERR_INVALID_ARG; }
+      if (ssx_status st = check_next_id(q.db, "ssx_kfdb_process_keyframe_batch", q.db->pending.kf_id)) return st;
+      if (q.db->ids.size() >= (size_t)0x7fffffff) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: the database is full", j); return SSX_ERR_CAPACITY; }
+    }
+  }
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ssx_ctx::KfBatchStats st{};
+  ctx->kf_batch = st;
+  // ---- what every job is, as if its commit had happened ----
+  struct Job { ssx_kf_database::Pending pe; bool commit; int N, n_elig; size_t blob; bool detect; };
+  std::vector<Job> J(n);
+  int total = 0, max_N = 0, max_elig = 0;
+  bool any_commit = false;
+  for (int j = 0; j < n; ++j) {
+    const ssx_kfdb_step_job& q = jobs[j];
+    ssx_kf_database* db = q.db;
+    Job& a = J[j];
+    a.commit = q.commit_pending != 0; a.pe = db->pending; a.N = q.n_features * pyramid_levels;
+    a.blob = a.commit ? blob_bytes(a.pe.n_bow, a.pe.n_pyr) : 0;
+    const size_t stored = db->ids.size() + (a.commit ? 1 : 0);
+    a.detect = (int64_t)stored > (int64_t)min_db_size;       // loopclosing.cpp:48
+    const int64_t newest = q.kf_id - (int64_t)min_id_gap;    // the prefix that is old enough (:79); the committed keyframe is the last of the map
+    a.n_elig = a.detect ? (int)(std::upper_bound(db->ids.begin(), db->ids.end(), newest) - db->ids.begin()) + ((a.commit && a.pe.kf_id <= newest) ? 1 : 0) : 0;
+    total += a.N; max_N = std::max(max_N, a.N); max_elig = std::max(max_elig, a.N > 0 ? a.n_elig : 0);
+    any_commit = any_commit || a.commit;
+    if (a.commit) {                                           // the growth a commit needs, with its own synchronisation as in ssx_kfdb_add_pending
+      const size_t cap_a = db->arena.cap, cap_t = db->table.cap, rows_n = db->ids.size();
+      SSX_HIP_TRY(ctx, grow_keep(ctx, db->arena, db->used, db->used + a.blob));
+      SSX_HIP_TRY(ctx, grow_keep(ctx, db->table, rows_n * sizeof(KfRow), (rows_n + 1) * sizeof(KfRow)));
+      st.syncs += (db->arena.cap != cap_a ? 1 : 0) + (db->table.cap != cap_t ? 1 : 0);
+    }
+  }
+  // ---- the describe block (the job table at its head), the scratch, the pending buffers: every allocation before the first enqueue ----
+  std::vector<ssxorb::DescribeJob> dj(n);
+  for (int j = 0; j < n; ++j) dj[j] = ssxorb::DescribeJob{jobs[j].img, jobs[j].features, jobs[j].n_features};
+  ssxorb::DescribedBatch d;
+  if (ssx_status s = ssxorb::describe_batch_prepare(ctx, n, dj.data(), jobs[0].stride, rows, cols, *prm, pyramid_levels, images_on_device != 0,
+                                                    sizeof(KfJobDev) * (size_t)n, &d))
+    return s;
+  st.syncs += d.syncs;
+  StepHdr* dh; int32_t* word; double* weight;
+  std::vector<unsigned long long*> keys(n, nullptr);
+  std::vector<double*> scores(n, nullptr);
+  auto scratch = [&](auto&& f) {
+    f(dh, sizeof(StepHdr) * (size_t)n); f(word, (size_t)4 * total); f(weight, (size_t)8 * total);
+    for (int j = 0; j < n; ++j) {
+      size_t npad = 1;
+      while (npad < (size_t)J[j].N) npad *= 2;
+      f(keys[j], J[j].N > kSortLds ? npad * 8 : 0); f(scores[j], (size_t)J[j].n_elig * 8);
+    }
+  };
+  SSX_HIP_TRY(ctx, voc->io.reserve(carve(nullptr, scratch)));
+  SSX_HIP_TRY(ctx, voc->stage.reserve(sizeof(StepHdr) * (size_t)n + 256));
+  carve(voc->io.as<char>(), scratch);
+  // A job that commits reads its previous pending arrays in the chain below: a buffer that has to grow is replaced, and the old one is
+  // freed only after the synchronisation (DevBuf::reserve would free it now)
+  struct Retired { std::vector<void*> p; ~Retired() { for (void* q : p) (void)hipFree(q); } } retired;
+  KfJobDev* tab = reinterpret_cast<KfJobDev*>(d.host_extra);
+  int kp0 = 0;
+  // from here on the databases are touched: whatever way the call fails, nothing is left pending
+  struct DropPending {
+    const ssx_kfdb_step_job* jobs; int n; bool armed;
+    ~DropPending() { if (armed) for (int j = 0; j < n; ++j) jobs[j].db->pending.valid = false; }
+  } drop{jobs, n, true};
+  for (int j = 0; j < n; ++j) {
+    const ssx_kfdb_step_job& q = jobs[j];
+    ssx_kf_database* db = q.db;
+    const Job& a = J[j];
+    KfJobDev t{};
+    PendArrays old{}, pa{};
+    if (a.commit) pend_arrays(db->pend.as<char>(), a.pe.cap, old);      // (cap == 0: an empty keyframe, nothing is read)
+    if (a.N > 0) {
+      const size_t need = pend_arrays(nullptr, a.N, pa);
+      if (a.commit && need > db->pend.cap) {
+        const size_t want = (size_t)((double)need * 1.25) + 256;
+        void* np = nullptr;
+        SSX_HIP_TRY(ctx, hipMalloc(&np, want));
+        if (db->pend.p) retired.p.push_back(db->pend.p);
+        db->pend.p = np; db->pend.cap = want;
+      } else {
+        SSX_HIP_TRY(ctx, db->pend.reserve(need));
+      }
+      pend_arrays(db->pend.as<char>(), a.N, pa);
+    }
+    db->pending.valid = false;                                          // a call that fails from here on leaves nothing pending
+    db->last = KfStepStats{};
+    t.kp0 = kp0; t.n_in = a.N; t.n_elig = a.N > 0 ? a.n_elig : 0; t.commit = a.commit ? 1 : 0;
+    t.p_kps = pa.kps; t.p_desc = pa.desc; t.p_cls = pa.cls; t.p_ids = pa.ids; t.p_vals = pa.vals;
+    t.bow_keys = keys[j]; t.arena = db->arena.as<char>(); t.rows = db->table.p; t.scores = scores[j];
+    if (a.commit) {
+      t.c_ids = old.ids; t.c_vals = old.vals; t.c_cls = old.cls; t.c_desc = old.desc;
+      t.c_blob = db->arena.as<char>() + db->used; t.c_row_out = db->table.as<KfRow>() + db->ids.size();
+      t.c_off = (int64_t)db->used; t.c_n_bow = a.pe.n_bow; t.c_n_desc = a.pe.n_pyr;
+    }
+    tab[j] = t;
+    kp0 += a.N;
+    *q.res = ssx_kfdb_step_result{};
+    q.res->min_distance = -1; q.res->detect_ran = a.detect ? 1 : 0; q.res->n_scored = a.n_elig;
+    *q.status_out = SSX_OK;
+  }
+  // ---- phase 1: one enqueue for all jobs ----
+  const KfJobDev* dtab = reinterpret_cast<const KfJobDev*>(d.dev_extra);
+  hipStream_t s = ctx->stream;
+  if (ssx_status e = ssxorb::describe_batch_launch(ctx, n, dtab, max_N, &d)) return e;
+  st.launches += d.launches; st.bytes_up += (int64_t)d.bytes_up;
+  if (any_commit) {
+    size_t most = 0;
+    for (const Job& a : J) most = std::max(most, a.blob);
+    const int blocks = (int)std::min<size_t>(std::max<size_t>((most / 4 + 255) / 256, 1), 1024);
+    SSX_PROF(ctx, KID_LOOP_COMMIT, hipLaunchKernelGGL(k_kfdb_commit_jobs, dim3(blocks, n), dim3(256), 0, s, dtab));
+    ++st.launches;
+  }
+  SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact_jobs, dim3(n), dim3(kPairsThreads), 0, s, dtab, d.kps, d.desc, d.keep, dh));
+  SSX_PROF(ctx, KID_LOOP_WORDS, ssxvoc::launch_words_jobs(s, voc, dtab, n, &dh->n_pyr, (int)(sizeof(StepHdr) / 4), total, word, weight));
+  SSX_PROF(ctx, KID_LOOP_BOW, hipLaunchKernelGGL(k_kf_bow_jobs, dim3(n), dim3(kPairsThreads), 0, s, dtab, word, weight, voc->weighting, dh));
+  st.launches += 3;
+  if (max_elig > 0) {
+    const int blocks = std::min((max_elig + 3) / 4, 1024), lds_cap = std::min(max_N, kQueryLds);
+    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score_jobs, dim3(blocks, n), dim3(256), (size_t)lds_cap * 12, s, dtab, dh, lds_cap));
+    ++st.launches;
+  }
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(voc->stage.p, dh, sizeof(StepHdr) * (size_t)n, hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  ++st.syncs; st.bytes_down += (int64_t)(sizeof(StepHdr) * (size_t)n);
+  std::vector<StepHdr> hdr(n);
+  memcpy(hdr.data(), voc->stage.p, sizeof(StepHdr) * (size_t)n);
+  // ---- the commits have happened: the host mirrors follow ----
+  for (int j = 0; j < n; ++j) {
+    if (!J[j].commit) continue;
+    ssx_kf_database* db = jobs[j].db;
+    const Job& a = J[j];
+    db->ids.push_back(a.pe.kf_id); db->rows.push_back(KfRow{(int64_t)db->used, a.pe.n_bow, a.pe.n_pyr});
+    db->used += a.blob; db->n_bow += a.pe.n_bow; db->n_desc += a.pe.n_pyr;
+  }
+  // ---- DetectLoop's verdicts; the jobs whose winner has something to match go to phase 2 ----
+  ssx_status first = SSX_OK;
+  auto fail = [&](int j, ssx_status e) { *jobs[j].status_out = e; if (first == SSX_OK) first = e; };
+  struct Found { int j; KfRow row; };
+  std::vector<Found> found;
+  for (int j = 0; j < n; ++j) {
+    const ssx_kfdb_step_job& q = jobs[j];
+    ssx_kf_database* db = q.db;
+    q.res->n_pyramid = hdr[j].n_pyr; q.res->n_bow = hdr[j].n_bow;
+    uint32_t row_i = 0;
+    float f = 0.f;
+    if (J[j].N > 0 && J[j].n_elig > 0 && winner_of(hdr[j].best, threshold, &row_i, &f)) {
+      q.res->found = 1; q.res->score = f; q.res->loop_kf_id = db->ids[row_i];
+      const KfRow row = db->rows[row_i];
+      if (row.n_desc < 0) {
+        ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: the loop keyframe %lld was added without descriptors", j, (long long)db->ids[row_i]);
+        fail(j, SSX_ERR_INVALID_ARG);
+        continue;                                             // (nothing pending, as the single call leaves it)
+      }
+      if (row.n_desc > 0 && hdr[j].n_pyr > 0) found.push_back(Found{j, row});   // else no match exists: no pairs
+    }
+    db->pending.valid = true; db->pending.kf_id = q.kf_id; db->pending.cap = J[j].N; db->pending.n_pyr = hdr[j].n_pyr; db->pending.n_bow = hdr[j].n_bow;
+  }
+  if (!found.empty()) {
+    // ---- phase 2: MatchFeatures of the found jobs, one match launch and one pairs launch.  The match table lies in mapped pinned memory and is
+    // read from there; the pair counts and the pairs are written there: 8 bytes of header and 8 per pair cross. ----
+    const int nf = (int)found.size();
+    std::vector<MatchScratch> m(nf);
+    auto mscratch = [&](auto&& g) { for (int k = 0; k < nf; ++k) match_scratch(g, m[k], found[k].row.n_desc); };
+    SSX_HIP_TRY(ctx, voc->io.reserve(carve(nullptr, mscratch)));
+    carve(voc->io.as<char>(), mscratch);
+    KfMatchJob* mt;
+    std::vector<int32_t*> out(nf, nullptr);
+    auto pinned = [&](auto&& g) { g(mt, sizeof(KfMatchJob) * (size_t)nf); for (int k = 0; k < nf; ++k) g(out[k], 256 + (size_t)found[k].row.n_desc * 8); };
+    SSX_HIP_TRY(ctx, voc->stage.reserve(carve(nullptr, pinned)));
+    char* hp = voc->stage.as<char>();
+    carve(hp, pinned);
+    void* dp = nullptr;
+    SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dp, hp, 0));
+    auto on_device = [&](void* host) { return (char*)dp + ((char*)host - hp); };
+    int max_nl = 0;
+    for (int k = 0; k < nf; ++k) {
+      const Found& fd = found[k];
+      ssx_kf_database* db = jobs[fd.j].db;
+      const char* blob = db->arena.as<char>() + fd.row.off;
+      PendArrays pa{};
+      pend_arrays(db->pend.as<char>(), J[fd.j].N, pa);
+      out[k][0] = 0; out[k][1] = -1;
+      KfMatchJob t{};
+      t.loop_desc = (const uint8_t*)(blob + blob_desc(fd.row.n_bow, fd.row.n_desc)); t.loop_cls = (const int32_t*)(blob + blob_class(fd.row.n_bow));
+      t.cur_desc = pa.desc; t.cur_cls = pa.cls; t.idx = m[k].idx; t.dist = m[k].dist; t.keys = m[k].keys;
+      t.hdr = (int32_t*)on_device(out[k]); t.pairs = (int32_t*)(on_device(out[k]) + 256);
+      t.nl = fd.row.n_desc; t.n_cur = hdr[fd.j].n_pyr;
+      mt[k] = t;
+      max_nl = std::max(max_nl, t.nl);
+    }
+    // (one found job: its entry travels as a kernel argument, as the single call's pointers do, and no workgroup reads host memory for it)
+    const KfMatchJob* dmt = nf > 1 ? (const KfMatchJob*)on_device(mt) : nullptr;
+    SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match_jobs(s, dmt, mt[0], nf, max_nl));
+    SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs_jobs, dim3(nf), dim3(kPairsThreads), 0, s, dmt, mt[0]));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      ctx->set_error("ssx_kfdb_process_keyframe_batch: the match phase failed: %s", hipGetErrorString(e));
+      return SSX_ERR_HIP;
+    }
+    st.launches += 2; ++st.syncs; st.bytes_up += (int64_t)(sizeof(KfMatchJob) * (size_t)nf);   // (nf == 1: as kernel arguments)
+    for (int k = 0; k < nf; ++k) {
+      const ssx_kfdb_step_job& q = jobs[found[k].j];
+      const int n_pairs = out[k][0];
+      q.res->n_pairs = n_pairs; q.res->min_distance = out[k][1];
+      st.bytes_down += 8 + (int64_t)n_pairs * 8;
+      if (q.pairs_cap > 0) memcpy(q.pairs_out, (const char*)out[k] + 256, (size_t)std::min(n_pairs, q.pairs_cap) * 8);
+      if (n_pairs > q.pairs_cap) {
+        ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: %d pairs but capacity %d", found[k].j, n_pairs, q.pairs_cap);
+        fail(found[k].j, SSX_ERR_CAPACITY);
+      }
+    }
+  }
+  ctx->kf_batch = st;
+  drop.armed = false;                                         // the call ran: every job's keyframe is pending (but for a winner without descriptors)
+  return first;
+}
+
 #ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h
+ssx_status ssx_kfdb_debug_last_batch(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
+{
+  if (!ctx) return SSX_ERR_INVALID_ARG;
+  if (launches) *launches = ctx->kf_batch.launches;
+  if (synchronisations) *synchronisations = ctx->kf_batch.syncs;
+  if (bytes_up) *bytes_up = ctx->kf_batch.bytes_up;
+  if (bytes_down) *bytes_down = ctx->kf_batch.bytes_down;
+  return SSX_OK;
+}
+
 ssx_status ssx_kfdb_debug_last_step(const ssx_kf_database* db, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
 {
   if (!db) return SSX_ERR_INVALID_ARG;

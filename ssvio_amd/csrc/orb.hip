@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "kf_batch.hpp"
 #include "orb_ws.hpp"
 #include "../../include/ssx_test_hooks.h"
 
@@ -961,7 +962,8 @@ struct DescribeAt {
   int n_in;
 };
 
-__global__ __launch_bounds__(256) void k_describe_at(OrbDev o, DescribeAt a)
+// keypoint blockIdx.x * 4 + wave of `a` on the pyramid at byte offset `img_off` of the plan's (image 0 of a plan for one image)
+__device__ __forceinline__ void describe_at_wave(const OrbDev& o, const DescribeAt& a, size_t img_off)
 {
   __shared__ uint32_t sPatch[4][PATCH_LDS_DW];
   __shared__ IcTables sIc;
@@ -985,7 +987,7 @@ __global__ __launch_bounds__(256) void k_describe_at(OrbDev o, DescribeAt a)
               kp.x + EDGE_THRESHOLD < cols);
     cx = __float2int_rn(kp.x); cy = __float2int_rn(kp.y);     // cvRound
   }
-  const uint8_t* lvl = o.pyr + o.lvl_off[level];
+  const uint8_t* lvl = o.pyr + img_off + o.lvl_off[level];
   const int pitch = o.lvl_pitch[level];
   if (active) active = fast_score(lvl + (size_t)cy * pitch + cx, pitch, min(max(o.min_th, 0), 255)) >= 0;   // isFastCorner
   uint32_t* sp = sPatch[wave];
@@ -999,7 +1001,7 @@ __global__ __launch_bounds__(256) void k_describe_at(OrbDev o, DescribeAt a)
   float ox = kp.x * sc, oy = kp.y * sc;                        // kps.pt *= scale  (the output coordinates)
   const float dx = ox / sc, dy = oy / sc;
   const int bx = __float2int_rn(dx), by = __float2int_rn(dy);
-  const uint8_t* blur = o.blur + o.lvl_off[level];
+  const uint8_t* blur = o.blur + img_off + o.lvl_off[level];
   int off_b = 0;
   if (active) off_b = stage_patch<BP, BP_NDW, 205, 11>(sp + 31 * OP_NDW, blur, pitch, bx - BR, by - BR, lane);
   __syncthreads();
@@ -1017,6 +1019,21 @@ __global__ __launch_bounds__(256) void k_describe_at(OrbDev o, DescribeAt a)
     a.out[k] = okp;
     a.keep[k] = 1;
   }
+}
+
+__global__ __launch_bounds__(256) void k_describe_at(OrbDev o, DescribeAt a)
+{
+  describe_at_wave(o, a, 0);
+}
+
+// the same for a batch of keyframe steps (kf_batch.hpp): grid.y is the job, its image is image grid.y of the plan, its keypoints are the
+// n_in entries from kp0 of the concatenated arrays in `a`; the grid covers the largest n_in
+__global__ __launch_bounds__(256) void k_describe_at_jobs(OrbDev o, DescribeAt a, const KfJobDev* jobs)
+{
+  const int kp0 = jobs[blockIdx.y].kp0;
+  a.in += kp0; a.out += kp0; a.desc += (size_t)32 * kp0; a.keep += kp0;
+  a.n_in = jobs[blockIdx.y].n_in;
+  describe_at_wave(o, a, (size_t)blockIdx.y * o.pyr_bytes);
 }
 
 // ORBextractor::Detect output: octree selection of level 0 + border, size 7, angle -1, octave 0 (cv::FAST keypoints)
@@ -1548,6 +1565,84 @@ ssx_status describe_enqueue(ssx_ctx* ctx, const uint8_t* img, int stride, int ro
   SSX_HIP_TRY(ctx, hipGetLastError());
   out->base = base; out->total = total; out->kps = a.out; out->desc = a.desc; out->keep = a.keep; out->n_in = n_in;
   out->launches = launches; out->syncs = planned ? 0 : 2; out->bytes_up = up;
+  return SSX_OK;
+}
+
+// describe_enqueue for n images in one chain (the keyframe steps of n streams, ssx_kfdb_process_keyframe_batch), in two halves: the caller
+// writes its job table into the head of the pinned block between them, so that one copy takes everything up.
+ssx_status describe_batch_prepare(ssx_ctx* ctx, int n, const DescribeJob* jobs, int stride, int rows, int cols, const ssx_orb_params& prm, int levels,
+                                  bool images_on_device, size_t extra_bytes, DescribedBatch* out)
+{
+  OrbWorkspace* ws = get_ws(ctx);
+  int cap_I = 1;
+  while (cap_I < n) cap_I *= 2;
+  const PlanKey want{rows, cols, cap_I, prm.nlevels, prm.nfeatures, prm.ini_th_fast, prm.min_th_fast, 0, 0, prm.scale_factor};
+  PlanKey have = ws->key;
+  have.I = cap_I;
+  const bool planned = ws->planned && have == want && ws->key.I >= n;   // (a smaller batch runs on the larger plan)
+  if (planned) cap_I = ws->key.I;
+  ssx_status st = plan(ctx, rows, cols, cap_I, prm, false, false);
+  if (st != SSX_OK) return st;
+  int total = 0;
+  for (int j = 0; j < n; ++j) total += jobs[j].n_feats * levels;
+  const size_t bytes = (size_t)rows * cols, extra = (extra_bytes + 7) & ~size_t(7);
+  const size_t o_ptr = extra, o_in = o_ptr + sizeof(void*) * (size_t)n, o_img = o_in + sizeof(ssx_keypoint) * (size_t)total;
+  const size_t up = o_img + (images_on_device ? 0 : bytes * (size_t)n);
+  ssx_keypoint* okps; uint8_t* odesc; uint8_t* okeep;
+  auto outputs = [&](auto&& f) { f(okps, sizeof(ssx_keypoint) * (size_t)total); f(odesc, (size_t)32 * total); f(okeep, (size_t)total); };
+  const size_t o_out = (up + 255) & ~size_t(255), block = o_out + carve(nullptr, outputs);
+  SSX_HIP_TRY(ctx, ws->input.reserve(block + 16, 1.5));   // (k_copy_level0_ptrs reads whole dwords)
+  SSX_HIP_TRY(ctx, ws->stage.reserve(up + 16, 1.5));
+  char* hs = ws->stage.as<char>();
+  char* base = ws->input.as<char>();
+  carve(base + o_out, outputs);
+  const uint8_t** ptrs = reinterpret_cast<const uint8_t**>(hs + o_ptr);
+  ssx_keypoint* hk = reinterpret_cast<ssx_keypoint*>(hs + o_in);
+  size_t k0 = 0;
+  for (int j = 0; j < n; ++j) {
+    const DescribeJob& q = jobs[j];
+    if (images_on_device) ptrs[j] = q.img;
+    else {
+      copy_rows(reinterpret_cast<uint8_t*>(hs + o_img) + bytes * (size_t)j, cols, q.img, stride, rows, cols);
+      ptrs[j] = reinterpret_cast<const uint8_t*>(base + o_img) + bytes * (size_t)j;
+    }
+    // every feature once per level: octave = level, response = -1, class_id = the feature (loopclosing.cpp:607-619)
+    for (int i = 0; i < q.n_feats; ++i)
+      for (int l = 0; l < levels; ++l) {
+        ssx_keypoint kp = q.feats[i];
+        kp.octave = l; kp.response = -1.f; kp.class_id = i;
+        hk[k0 + (size_t)i * levels + l] = kp;
+      }
+    k0 += (size_t)q.n_feats * levels;
+  }
+  out->host_extra = hs; out->dev_extra = base;
+  out->kps = okps; out->desc = odesc; out->keep = okeep;
+  out->launches = 0; out->syncs = planned ? 0 : 2; out->bytes_up = up;
+  out->o_ptr = o_ptr; out->o_in = o_in; out->stride = images_on_device ? stride : cols; out->total = total;
+  return SSX_OK;
+}
+
+ssx_status describe_batch_launch(ssx_ctx* ctx, int n, const KfJobDev* table, int max_n_in, DescribedBatch* io)
+{
+  OrbWorkspace* ws = get_ws(ctx);
+  OrbDev d = ws->dev;
+  d.I = n;                                              // (the plan may hold more images)
+  hipStream_t s = ctx->stream;
+  char* base = ws->input.as<char>();
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(base, ws->stage.p, io->bytes_up, hipMemcpyHostToDevice, s));
+  const dim3 grid((d.lvl_cols[0] + 511) / 512, (d.lvl_rows[0] + 3) / 4, n);
+  SSX_PROF(ctx, KID_ORB_MISC, hipLaunchKernelGGL(k_copy_level0_ptrs, grid, dim3(64, 4), 0, s, reinterpret_cast<const uint8_t* const*>(base + io->o_ptr), io->stride,
+                                                 d.pyr, d.pyr_bytes, d.lvl_rows[0], d.lvl_cols[0], d.lvl_pitch[0]));
+  int launches = 1 + launch_pyramid(ctx, d, s, n);
+  SSX_PROF(ctx, KID_ORB_GAUSS, hipLaunchKernelGGL(k_gauss7, dim3(d.gauss_tile0[d.nlevels], n), dim3(256), 0, s, d));
+  ++launches;
+  DescribeAt a;
+  a.in = reinterpret_cast<const ssx_keypoint*>(base + io->o_in);
+  a.out = const_cast<ssx_keypoint*>(io->kps); a.desc = const_cast<uint8_t*>(io->desc); a.keep = const_cast<uint8_t*>(io->keep); a.n_in = 0;
+  SSX_PROF(ctx, KID_ORB_BRIEF, hipLaunchKernelGGL(k_describe_at_jobs, dim3(std::max((max_n_in + 3) / 4, 1), n), dim3(256), 0, s, d, a, table));
+  ++launches;
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  io->launches = launches;
   return SSX_OK;
 }
 

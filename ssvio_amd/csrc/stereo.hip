@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "kf_batch.hpp"
 #include "orb_ws.hpp"
 
 namespace ssxorb {
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256) void k_match(MatchDev m)
 }
 
 // generic brute force: query block x all train descriptors (host-array entry point ssx_bf_match)
-__global__ __launch_bounds__(256) void k_bf_match(const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist)
+__device__ __forceinline__ void bf_match_query(const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist)
 {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // wave index in an SGPR: everything derived from it is scalar
   const int i = blockIdx.x * 4 + wave;
@@ -168,6 +169,19 @@ __global__ __launch_bounds__(256) void k_bf_match(const uint8_t* dq, int nq, con
     dist[i] = d;
     idx[i] = d <= 256 ? (int)(best & 0xFFFFu) : -1;
   }
+}
+
+__global__ __launch_bounds__(256) void k_bf_match(const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist)
+{
+  bf_match_query(dq, nq, dt, nt, idx, dist);
+}
+
+// the same for every found loop of a batch of keyframe steps (kf_batch.hpp): grid.y is the job, each with its own query count
+// (jobs == null: the one job of the launch is `one`, a kernel argument)
+__global__ __launch_bounds__(256) void k_bf_match_jobs(const KfMatchJob* jobs, KfMatchJob one)
+{
+  const KfMatchJob j = jobs ? jobs[blockIdx.y] : one;
+  bf_match_query(j.loop_desc, j.nl, j.cur_desc, j.n_cur, j.idx, j.dist);
 }
 
 // ---- 4x4 SVD by one-sided (Hestenes) Jacobi, everything in registers (loops fully unrolled: static indices) ----
@@ -518,6 +532,10 @@ ssx_status fetch_frame_fast(ssx_ctx* ctx, const FrameSlots& o, ssx_stereo_frame_
 void launch_bf_match(hipStream_t stream, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist)
 {
   hipLaunchKernelGGL(k_bf_match, dim3((nq + 3) / 4), dim3(256), 0, stream, dq, nq, dt, nt, idx, dist);
+}
+void launch_bf_match_jobs(hipStream_t stream, const KfMatchJob* jobs, const KfMatchJob& one, int n_jobs, int max_nl)
+{
+  hipLaunchKernelGGL(k_bf_match_jobs, dim3((max_nl + 3) / 4, n_jobs), dim3(256), 0, stream, jobs, one);
 }
 }  // namespace ssxorb
 

@@ -11,6 +11,7 @@
 // object.  The BowVector itself (a sorted map with weights summed in feature order and an L1 normalisation in word order,
 // TemplatedVocabulary.h:1065-1124, BowVector.cpp:62-84) is a few hundred entries and is assembled on the host in
 // exactly that order; L1Scoring::score (ScoringObject.cpp:23-68) is a host function.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -20,23 +21,21 @@
 #include <string>
 #include <vector>
 
+#include "kf_batch.hpp"
 #include "voc.hpp"
 
 
 namespace {
 
-__global__ __launch_bounds__(256) void k_voc_words(const uint8_t* desc, const double* weight, const int32_t* child_ptr, const int32_t* child,
-                                                   const int32_t* word_of, const uint8_t* feat, int n, const int32_t* n_dev, int32_t* word_out,
-                                                   double* weight_out)
+// the descent of one feature: its leaf's word and weight (word -1, weight 0 with an empty vocabulary)
+__device__ __forceinline__ void voc_descend(const uint8_t* desc, const double* weight, const int32_t* child_ptr, const int32_t* child, const int32_t* word_of,
+                                            const uint8_t* q, int32_t* word_out, double* weight_out)
 {
-  if (n_dev) n = *n_dev;                                     // the count lies on the device (the keyframe step of loop.hip): the grid covers its bound
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= n) return;
-  const uint4* q4 = reinterpret_cast<const uint4*>(feat + 32 * (size_t)f);
+  const uint4* q4 = reinterpret_cast<const uint4*>(q);
   const uint4 qa = q4[0], qb = q4[1];
   int id = 0;
   int c0 = child_ptr[0], c1 = child_ptr[1];
-  if (c1 == c0) { word_out[f] = -1; weight_out[f] = 0.0; return; }
+  if (c1 == c0) { *word_out = -1; *weight_out = 0.0; return; }
   while (c1 > c0) {
     int best = 0x7fffffff, bid = 0;
     for (int c = c0; c < c1; ++c) {
@@ -50,8 +49,35 @@ __global__ __launch_bounds__(256) void k_voc_words(const uint8_t* desc, const do
     id = bid;
     c0 = child_ptr[id]; c1 = child_ptr[id + 1];
   }
-  word_out[f] = word_of[id];
-  weight_out[f] = weight[id];
+  *word_out = word_of[id];
+  *weight_out = weight[id];
+}
+
+__global__ __launch_bounds__(256) void k_voc_words(const uint8_t* desc, const double* weight, const int32_t* child_ptr, const int32_t* child,
+                                                   const int32_t* word_of, const uint8_t* feat, int n, const int32_t* n_dev, int32_t* word_out,
+                                                   double* weight_out)
+{
+  if (n_dev) n = *n_dev;                                     // the count lies on the device (the keyframe step of loop.hip): the grid covers its bound
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n) return;
+  voc_descend(desc, weight, child_ptr, child, word_of, feat + 32 * (size_t)f, word_out + f, weight_out + f);
+}
+
+// the same over the concatenated bound of a batch of keyframe steps (kf_batch.hpp): a thread finds its job by bisection of the table
+__global__ __launch_bounds__(256) void k_voc_words_jobs(const uint8_t* desc, const double* weight, const int32_t* child_ptr, const int32_t* child,
+                                                        const int32_t* word_of, const KfJobDev* jobs, int n_jobs, const int32_t* counts, int count_stride,
+                                                        int total, int32_t* word_out, double* weight_out)
+{
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  int lo = 0, hi = n_jobs - 1;                                // the last job with kp0 <= t (empty jobs share the kp0 of the one behind them)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].kp0 <= t) lo = mid; else hi = mid - 1;
+  }
+  const int f = t - jobs[lo].kp0;
+  if (f >= counts[(size_t)count_stride * lo]) return;
+  voc_descend(desc, weight, child_ptr, child, word_of, jobs[lo].p_desc + 32 * (size_t)f, word_out + t, weight_out + t);
 }
 
 }  // namespace
@@ -61,6 +87,12 @@ void launch_words(hipStream_t stream, const ssx_vocabulary* v, const uint8_t* fe
 {
   hipLaunchKernelGGL(k_voc_words, dim3((n_bound + 255) / 256), dim3(256), 0, stream, v->d_desc, v->d_weight, v->d_child_ptr, v->d_child, v->d_word, feat,
                      n_bound, n_dev, word_out, weight_out);
+}
+void launch_words_jobs(hipStream_t stream, const ssx_vocabulary* v, const KfJobDev* jobs, int n_jobs, const int32_t* counts, int count_stride, int total,
+                       int32_t* word_out, double* weight_out)
+{
+  hipLaunchKernelGGL(k_voc_words_jobs, dim3(std::max((total + 255) / 256, 1)), dim3(256), 0, stream, v->d_desc, v->d_weight, v->d_child_ptr, v->d_child, v->d_word, jobs,
+                     n_jobs, counts, count_stride, total, word_out, weight_out);
 }
 }  // namespace ssxvoc
 

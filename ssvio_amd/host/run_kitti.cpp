@@ -3,7 +3,7 @@
 // save the keyframe trajectory in TUM format.  Same two flags (gflags spelling), plus a frame limit and an output path.
 //
 //   ssx_run_kitti --config_yaml_path=cfg.yaml --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=out.txt]
-//                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--warmup=1] [--loop_log=FILE]
+//                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--warmup=1] [--loop_log=FILE]
 // The PNG pairs are decoded ahead of the tracker on worker threads (StereoPrefetcher); everything else is the
 // reference's single loop.  --streams=K runs K independent copies of the loop in K threads of this process (each with
 // its own System, GPU contexts and prefetcher) on the same sequence: a single stream is latency-bound, several fill the
@@ -18,7 +18,9 @@
 // --loop_log=FILE (with Loop.Closing.Open: 1): one line per keyframe the loop step handled (stream k of --streams writes FILE.k):
 //   kf <id> db <database size> found <0|1> loop <id|-1> score <float, 9 digits> pairs <n> pose <ssx_loop_verdict|-1> with_point <n> inliers <n>
 //   error <17 digits> need_correct <0|1> corrected <0|1> fused <n> same_point <n> pg_iters <n> moved_active <n> moved_other <n> skipped <n> duplicate <n>
-// Loop closing is per stream; batching the loop step over streams does not exist, so --batched >= 1 with Loop.Closing.Open is refused.
+// Loop closing is per stream.  --batched >= 1 with Loop.Closing.Open: 1 is refused unless --loop_batched=1 is given: the streams of a cohort
+// then share one loop context and one vocabulary, and their inline keyframe steps go to the GPU as ssx_kfdb_process_keyframe_batch calls
+// (every stream still writes the bytes of its single-stream run).  The loop thread (Loop.Closing.Async: 1) is not batched: refused with it.
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -65,16 +67,16 @@ void WriteLoopLog(ssx::host::System& sys, const std::string& path)
 
 int main(int argc, char** argv)
 {
-  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log;
+  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log, loop_batched_s;
   for (int i = 1; i < argc; ++i) {
     if (flag(argv[i], "config_yaml_path", config) || flag(argv[i], "kitti_dataset_path", dataset) || flag(argv[i], "max_frames", max_frames_s) ||
-        flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s) || flag(argv[i], "loop_log", loop_log))
+        flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s) || flag(argv[i], "loop_log", loop_log) || flag(argv[i], "loop_batched", loop_batched_s))
       continue;
     std::fprintf(stderr, "unknown argument %s\n", argv[i]);
     return 2;
   }
   if (config.empty() || dataset.empty()) {
-    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--warmup=1] [--loop_log=<file>]\n",
+    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--warmup=1] [--loop_log=<file>]\n",
                  argv[0]);
     return 2;
   }
@@ -105,9 +107,14 @@ int main(int argc, char** argv)
     std::printf("Num Images: %zu\n", num_images);
 
     const int streams = streams_s.empty() ? 1 : std::max(1, std::atoi(streams_s.c_str()));
-    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Loop.Closing.Open") != 0) {
-      std::fprintf(stderr, "--batched=%s with Loop.Closing.Open: 1 is not supported: the loop step is not batched over streams (run --streams unbatched, or switch loop closing off)\n",
-                   batched_s.c_str());
+    const bool loop_batched = !loop_batched_s.empty() && std::atoi(loop_batched_s.c_str()) != 0;
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Loop.Closing.Open") != 0 && !loop_batched) {
+      std::fprintf(stderr, "--batched=%s with Loop.Closing.Open: 1 is not supported without --loop_batched=1 (the loop step batched over the streams); "
+                   "or run --streams unbatched, or switch loop closing off\n", batched_s.c_str());
+      return 2;
+    }
+    if (loop_batched && Setting(config).Get<int>("Loop.Closing.Open") != 0 && Setting(config).Get<int>("Loop.Closing.Async") != 0) {
+      std::fprintf(stderr, "--loop_batched=1 with Loop.Closing.Async: 1 is not supported: the batched loop step is the inline one (no third thread per stream)\n");
       return 2;
     }
     const bool warmup = warmup_s.empty() || std::atoi(warmup_s.c_str()) != 0;
@@ -202,6 +209,10 @@ int main(int argc, char** argv)
                     1e3 * bs.lk_s, 1e3 * bs.lk_s / std::max(1L, bs.lk_calls), 1e3 * bs.po_s, 1e3 * bs.po_s / std::max(1L, bs.po_calls), 1e3 * bs.ba_s,
                     1e3 * bs.ba_s / std::max(1L, bs.ba_calls), bs.kf_calls, bs.kf_jobs / std::max(1.0, (double)bs.kf_calls), 1e3 * bs.kf_s,
                     1e3 * bs.kf_s / std::max(1L, bs.kf_calls), 1e3 * bs.wait_s);
+        if (bs.loop_calls || bs.single_calls)
+          std::printf("batched loop steps: loop_calls %ld loop_jobs %ld loop_s %.6f (%.3f ms per call, %.1f jobs each); a correction's single calls %ld, %.1f ms\n",
+                      bs.loop_calls, bs.loop_jobs, bs.loop_s, 1e3 * bs.loop_s / std::max(1L, bs.loop_calls), bs.loop_jobs / std::max(1.0, (double)bs.loop_calls),
+                      bs.single_calls, 1e3 * bs.single_s);
       }
       return 0;
     }

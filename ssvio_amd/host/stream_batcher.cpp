@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 
 #include "../../include/ssx_shim.hpp"
@@ -11,7 +12,9 @@
 namespace ssx::host {
 
 namespace {
-enum class St { RUNNING, PENDING_LK, PENDING_PO, PENDING_DET, PENDING_LKS, PENDING_TRI, PENDING_BA, INFLIGHT, LONGOP, DONE, IDLE };
+enum class St { RUNNING, PENDING_LK, PENDING_PO, PENDING_DET, PENDING_LKS, PENDING_TRI, PENDING_BA, PENDING_LOOP, PENDING_CALL, INFLIGHT, LONGOP, DONE, IDLE };
+// one keyframe step of loop closing as a stream files it (ssx_kfdb_process_keyframe_batch): the job and what a call's jobs must share
+struct LoopReq { ssx_kfdb_step_job job{}; ssx_orb_params prm{}; int rows = 0, cols = 0, levels = 0, min_db = 0, min_gap = 0; float threshold = 0.f; int32_t status = 0; };
 }
 
 struct StreamBatcher::Impl {
@@ -21,7 +24,8 @@ struct StreamBatcher::Impl {
   Impl(int device_, int streams) : device(device_), S(streams), lk_ctx(device_), po_ctx(device_), ba_ctx(device_), det_ctx(device_), lks_ctx(device_),
                                    tri_ctx(device_), state(2 * (size_t)streams, St::RUNNING), lk_req(streams), lk_rows(streams, 0), lk_cols(streams, 0),
                                    po_req(streams), det_req(streams), det_prm(streams), tri_req(streams), ba_win(2 * (size_t)streams, nullptr),
-                                   ba_res(2 * (size_t)streams, nullptr), error(2 * (size_t)streams)
+                                   ba_res(2 * (size_t)streams, nullptr), loop_req(2 * (size_t)streams), call_req(2 * (size_t)streams, nullptr),
+                                   error(2 * (size_t)streams)
   {
     n_in[(int)St::RUNNING] = streams;
     n_in[(int)St::IDLE] = streams;
@@ -39,7 +43,28 @@ struct StreamBatcher::Impl {
     cv_disp.notify_all();
     if (disp.joinable()) disp.join();
     if (ba_disp.joinable()) ba_disp.join();
+    if (voc) ssx_voc_destroy(voc);                  // (the streams' databases went with their Systems)
     ssx_host_free(pin_arena);
+  }
+
+  // The cohort's loop context and its ONE vocabulary, loaded when the first stream asks for them (128 streams with a vocabulary each
+  // would hold 128 copies of ORBvoc in HBM); every stream's keyframe database lives on that context.
+  ssx_kf_database* MakeLoopDatabase(const std::string& voc_path)
+  {
+    std::lock_guard<std::mutex> lk(loop_mu);
+    if (!loop_ctx) {
+      auto ctx = std::make_unique<ssx::Context>(device);
+      ssx_vocabulary* v = nullptr;
+      if (ssx_voc_load_text(ctx->get(), voc_path.c_str(), &v) != SSX_OK)
+        throw std::runtime_error("DBOW2.VOC.Path: cannot read the vocabulary \"" + voc_path + "\": " + ssx_last_error(ctx->get()));
+      loop_ctx = std::move(ctx); voc = v; loop_voc_path = voc_path;
+    } else if (voc_path != loop_voc_path) {
+      throw std::runtime_error("DBOW2.VOC.Path: the streams of a batched cohort share one vocabulary, \"" + loop_voc_path + "\" is loaded and \"" + voc_path +
+                               "\" was asked for");
+    }
+    ssx_kf_database* db = nullptr;
+    loop_ctx->check(ssx_kfdb_create(loop_ctx->get(), 256, &db));
+    return db;
   }
 
   // The streams' pinned image buffers are slices of ONE arena: buffer `which` of stream k at (which * S + k) * slice.  The `next`
@@ -196,7 +221,9 @@ struct StreamBatcher::Impl {
   {
     std::unique_lock<std::mutex> lk(m);
     std::vector<int> who;
-    auto n_kf = [&] { return count(St::PENDING_DET) + count(St::PENDING_LKS) + count(St::PENDING_TRI) + count(St::PENDING_BA); };
+    auto n_kf = [&] {
+      return count(St::PENDING_DET) + count(St::PENDING_LKS) + count(St::PENDING_TRI) + count(St::PENDING_BA) + count(St::PENDING_LOOP) + count(St::PENDING_CALL);
+    };
     for (;;) {
       // (streams in a call of their own -- LONGOP -- are about to file the next request of this path: wait for them)
       const bool at_rest = cv_disp.wait_for(lk, std::chrono::milliseconds(2), [&] { return quit || (n_kf() > 0 && count(St::RUNNING) == 0 && count(St::LONGOP) == 0); });
@@ -205,11 +232,13 @@ struct StreamBatcher::Impl {
         // An asynchronous backend's window solve has waited 2 ms for the front-ends to come to rest -- they may be waiting for IT
         // (Backend::WaitIdle at the end of a sequence, the map mutex): it is served with what has gathered so far.
         bool backend_waits = false;
-        for (int k = S; k < 2 * S; ++k) backend_waits = backend_waits || state[k] == St::PENDING_BA;
+        for (int k = S; k < 2 * S; ++k) backend_waits = backend_waits || state[k] == St::PENDING_BA || state[k] == St::PENDING_LOOP || state[k] == St::PENDING_CALL;
         if (!backend_waits) continue;
       }
+      // (the loop step follows the window solve inside the backend: served after it, the streams that solved a little later merge into
+      // one loop call; the rare single calls of a correction come last)
       const St kind = count(St::PENDING_DET) > 0 ? St::PENDING_DET : count(St::PENDING_LKS) > 0 ? St::PENDING_LKS : count(St::PENDING_TRI) > 0 ? St::PENDING_TRI
-                                                                                                                                              : St::PENDING_BA;
+                      : count(St::PENDING_BA) > 0 ? St::PENDING_BA : count(St::PENDING_LOOP) > 0 ? St::PENDING_LOOP : St::PENDING_CALL;
       who.clear();
       for (int k = 0; k < 2 * S; ++k) if (state[k] == kind) { who.push_back(k); Move(k, St::INFLIGHT); }
       lk.unlock();
@@ -219,7 +248,48 @@ struct StreamBatcher::Impl {
       const auto tb0 = std::chrono::steady_clock::now();
       std::vector<size_t> all(who.size());
       for (size_t i = 0; i < all.size(); ++i) all[i] = i;
-      if (kind == St::PENDING_BA) {
+      if (kind == St::PENDING_CALL) {
+        // ComputeCorrectPose, LoopCorrect and the window's loop correction: one at a time, here, so that none runs on the loop context or
+        // the window context beside a batched call of this dispatcher
+        for (size_t i = 0; i < who.size(); ++i) {
+          try { (*call_req[who[i]])(); } catch (const std::exception& e) { errs[i] = e.what(); }
+        }
+      } else if (kind == St::PENDING_LOOP) {
+        auto same = [&](size_t a, size_t b) {
+          const LoopReq &x = loop_req[who[a]], &y = loop_req[who[b]];
+          return x.rows == y.rows && x.cols == y.cols && x.job.stride == y.job.stride && std::memcmp(&x.prm, &y.prm, sizeof(ssx_orb_params)) == 0 &&
+                 x.levels == y.levels && x.min_db == y.min_db && x.min_gap == y.min_gap && x.threshold == y.threshold;
+        };
+        for (const auto& g : Groups(who.size(), same))
+          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
+            std::vector<ssx_kfdb_step_job> jobs;
+            for (size_t i : sub) { LoopReq& r = loop_req[who[i]]; r.status = SSX_OK; r.job.status_out = &r.status; jobs.push_back(r.job); }
+            const LoopReq& r0 = loop_req[who[sub[0]]];
+            const ssx_status rc = ssx_kfdb_process_keyframe_batch(voc, (int32_t)jobs.size(), jobs.data(), r0.rows, r0.cols, &r0.prm, r0.levels, r0.min_db, r0.min_gap,
+                                                                  r0.threshold, 1);
+            if (rc == SSX_OK) return;
+            // The call returns the first job status that is not SSX_OK: a return value that one of the jobs carries is that job's own
+            // outcome, the other jobs are complete (SSX_ERR_CAPACITY: the stream asks again with the room the count names).  Any other
+            // value is a failure of the whole call.
+            bool per_job = false;
+            for (size_t i : sub) per_job = per_job || loop_req[who[i]].status == (int32_t)rc;
+            const std::string why = ssx_last_error(loop_ctx->get());
+            if (per_job) {
+              for (size_t i : sub) {
+                const int32_t js = loop_req[who[i]].status;
+                if (js != SSX_OK && js != SSX_ERR_CAPACITY) errs[i] = "ssx_kfdb_process_keyframe_batch: job status " + std::to_string(js) + ": " + why;
+              }
+              return;
+            }
+            // a HIP error: the library had begun (commits may be lost, nothing is pending any more), so no job of the call has a result and
+            // none is tried again; every stream of the call gets the error, and its AddPending stays unserved
+            if (rc == SSX_ERR_HIP) {
+              for (size_t i : sub) errs[i] = "ssx_kfdb_process_keyframe_batch: " + why;
+              return;
+            }
+            loop_ctx->check(rc);                    // rejected before anything was touched: Isolated tries the jobs one by one
+          });
+      } else if (kind == St::PENDING_BA) {
         Isolated(all, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
           std::vector<ssx_ba_window*> wins;
           std::vector<ssx_ba_result> res;
@@ -257,6 +327,8 @@ struct StreamBatcher::Impl {
       const double dtb = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count();
       lk.lock();
       if (kind == St::PENDING_BA) { ++st.ba_calls; st.ba_jobs += (long)who.size(); st.ba_s += dtb; }
+      else if (kind == St::PENDING_LOOP) { st.loop_calls += d_calls; st.loop_jobs += d_jobs; st.loop_s += dtb; }
+      else if (kind == St::PENDING_CALL) { st.single_calls += (long)who.size(); st.single_s += dtb; }
       else { ++st.kf_calls; st.kf_jobs += (long)who.size(); st.kf_s += dtb; }
       Release(who, errs);
       lk.unlock();
@@ -284,6 +356,12 @@ struct StreamBatcher::Impl {
   std::vector<ssx_triangulate_job> tri_req;
   std::vector<ssx_ba_window*> ba_win;
   std::vector<ssx_ba_result*> ba_res;
+  std::mutex loop_mu;                               // the making of the loop context, the vocabulary and the databases
+  std::unique_ptr<ssx::Context> loop_ctx;
+  ssx_vocabulary* voc = nullptr;
+  std::string loop_voc_path;
+  std::vector<LoopReq> loop_req;
+  std::vector<std::function<void()>*> call_req;
   std::vector<std::string> error;
   StreamBatcher::Stats st;
   bool quit = false;
@@ -333,6 +411,14 @@ class BatchedBaWindow final : public BaWindow {
     im_.ba_win[slot] = win_; im_.ba_res[slot] = &res;
     im_.SubmitAndWait(slot, St::PENDING_BA);
   }
+  void LoopCorrect(int64_t cur_kf_id, const double* corrected_pose7, int n_fused, const int64_t* fused_ids, ssx_ba_window_loop_result* res) override
+  {
+    // (the windows of a cohort share ba_ctx: the keyframe dispatcher makes the call, never beside one of its batched solves)
+    std::function<void()> call = [&] { im_.ba_ctx.check(ssx_ba_window_loop_correct(win_, cur_kf_id, corrected_pose7, n_fused, n_fused > 0 ? fused_ids : nullptr, res)); };
+    const int slot = std::this_thread::get_id() == owner_ ? k_ : im_.S + k_;
+    im_.call_req[slot] = &call;
+    im_.SubmitAndWait(slot, St::PENDING_CALL);
+  }
 
  private:
   // (these calls only edit the window's host mirror; the shared context's error text may belong to another stream's call, so the
@@ -342,6 +428,74 @@ class BatchedBaWindow final : public BaWindow {
   int k_;
   std::thread::id owner_;                            // the stream's thread (it makes the window: Backend's constructor)
   ssx_ba_window* win_ = nullptr;
+};
+
+// The loop-closing calls of one stream of a cohort: its keyframe database on the cohort's loop context.  The keyframe step is filed
+// like a window solve and served as one job of ssx_kfdb_process_keyframe_batch; the rare calls of a correction go to the keyframe
+// dispatcher one at a time.
+class BatchedLoopCompute final : public LoopCompute {
+ public:
+  BatchedLoopCompute(StreamBatcher::Impl& im, int k, const std::string& voc_path) : im_(im), k_(k), owner_(std::this_thread::get_id()), db_(im.MakeLoopDatabase(voc_path)) {}
+  ~BatchedLoopCompute() override
+  {
+    ssx_kfdb_destroy(db_);
+    ssx_host_free(pin_);
+  }
+  void ProcessKeyframe(int64_t kf_id, const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, int min_db_size,
+                       int min_id_gap, float threshold, ssx_kfdb_step_result& res, std::vector<int32_t>& pairs) override
+  {
+    const int slot = Slot();
+    const size_t bytes = (size_t)img.rows * img.cols;
+    if (bytes > pin_bytes_) {                       // the keyframe's image in a pinned buffer of the stream's own, read there by the GPU
+      ssx_host_free(pin_);
+      pin_ = static_cast<uint8_t*>(ssx_host_alloc(bytes));
+      if (!pin_) throw std::runtime_error("StreamBatcher: no pinned memory for the loop step's image");
+      pin_bytes_ = bytes;
+    }
+    std::memcpy(pin_, img.ptr(), bytes);
+    pairs.resize(2 * std::max<size_t>(1024, features.size() * (size_t)std::max(pyramid_levels, 1)));
+    LoopReq& r = im_.loop_req[slot];
+    for (int attempt = 0;; ++attempt) {
+      r = LoopReq{};
+      r.job.db = db_; r.job.kf_id = kf_id; r.job.img = pin_; r.job.stride = img.cols; r.job.n_features = (int32_t)features.size(); r.job.features = features.data();
+      r.job.commit_pending = commit_next_ ? 1 : 0; r.job.pairs_cap = (int32_t)(pairs.size() / 2); r.job.pairs_out = pairs.data(); r.job.res = &res;
+      r.prm = prm; r.rows = img.rows; r.cols = img.cols; r.levels = pyramid_levels; r.min_db = min_db_size; r.min_gap = min_id_gap; r.threshold = threshold;
+      im_.SubmitAndWait(slot, St::PENDING_LOOP);
+      commit_next_ = false;                         // (the call ran: the keyframe of AddPending is stored)
+      if (r.status != SSX_ERR_CAPACITY || attempt > 0) break;
+      pairs.resize(2 * (size_t)res.n_pairs);        // a larger loop keyframe: the count is known now, the step once more
+    }
+    if (r.status != SSX_OK) throw std::runtime_error("ssx_kfdb_process_keyframe_batch: job status " + std::to_string(r.status));
+    pairs.resize(2 * (size_t)res.n_pairs);
+  }
+  // nothing is launched: the stream's next step carries commit_pending, and the keyframe is read no earlier than that
+  void AddPending() override { commit_next_ = true; }
+  void ComputePose(int n_pairs, const double* loop_xyz, const uint8_t* has_point, const double* cur_uv, const double* T_cur, const double* T_loop,
+                   const double* K4, uint8_t* kept, ssx_loop_pose_result& out) override
+  {
+    Single([&] { im_.loop_ctx->check(ssx_loop_compute_pose(im_.loop_ctx->get(), n_pairs, loop_xyz, has_point, cur_uv, T_cur, T_loop, K4, 100, 0, kept, &out)); });
+  }
+  void LoopCorrect(const ssx_loop_correct_problem& prob, ssx_loop_correct_result& res) override
+  {
+    Single([&] { im_.loop_ctx->check(ssx_loop_correct(im_.loop_ctx->get(), &prob, 20, &res)); });
+  }
+
+ private:
+  // the stream's thread, or the worker of its asynchronous backend (the rule of BatchedBaWindow::Solve)
+  int Slot() const { return std::this_thread::get_id() == owner_ ? k_ : im_.S + k_; }
+  void Single(std::function<void()> call)
+  {
+    const int slot = Slot();
+    im_.call_req[slot] = &call;
+    im_.SubmitAndWait(slot, St::PENDING_CALL);
+  }
+  StreamBatcher::Impl& im_;
+  int k_;
+  std::thread::id owner_;                            // the stream's thread (it makes the System)
+  ssx_kf_database* db_ = nullptr;
+  uint8_t* pin_ = nullptr;
+  size_t pin_bytes_ = 0;
+  bool commit_next_ = false;
 };
 
 class BatchedCompute final : public Compute {
@@ -456,6 +610,8 @@ class BatchedCompute final : public Compute {
     return std::make_unique<BatchedBaWindow>(im_, k_, K4, cam_ext14, opt);
   }
 
+  std::unique_ptr<LoopCompute> MakeLoopCompute(const std::string& voc_path) override { return std::make_unique<BatchedLoopCompute>(im_, k_, voc_path); }
+
  private:
   // the image in the stream's pinned buffer `which` (copied by this thread unless it is there already)
   // (keep: a buffer this call must not overwrite -- the other image of a two-image request)
@@ -533,6 +689,7 @@ StreamBatcher::Stats StreamBatcher::stats()
     const Stats& a = im->st;
     t.lk_calls += a.lk_calls; t.lk_jobs += a.lk_jobs; t.po_calls += a.po_calls; t.po_jobs += a.po_jobs; t.ba_calls += a.ba_calls; t.ba_jobs += a.ba_jobs;
     t.kf_calls += a.kf_calls; t.kf_jobs += a.kf_jobs; t.lk_s += a.lk_s; t.po_s += a.po_s; t.ba_s += a.ba_s; t.kf_s += a.kf_s; t.wait_s += a.wait_s;
+    t.loop_calls += a.loop_calls; t.loop_jobs += a.loop_jobs; t.loop_s += a.loop_s; t.single_calls += a.single_calls; t.single_s += a.single_s;
   }
   return t;
 }

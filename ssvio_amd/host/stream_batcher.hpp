@@ -14,7 +14,10 @@
 // single-stream run, whatever S and whatever the interleaving (tests/test_host_gpu.py).  The keyframe path of a stream (masked
 // detection, stereo LK, triangulation: ssx_orb_detect_boxes_batch / ssx_lk_track_batch / ssx_triangulate_batch) is batched by a
 // second dispatcher on contexts of its own, beside the per-frame batches; a stream's images are read by the GPU from the stream's
-// pinned buffers (filled by the stream's own thread), nothing is staged inside the batched calls.
+// pinned buffers (filled by the stream's own thread), nothing is staged inside the batched calls.  Loop closing's keyframe step
+// (LoopCompute::ProcessKeyframe) is one more request kind of that dispatcher: the streams of a cohort share one loop context and ONE
+// vocabulary, each has its keyframe database there, and their steps go out as ssx_kfdb_process_keyframe_batch; the calls of a
+// correction are rare and are made by the dispatcher one at a time.
 //
 // Dispatch order: pose-only before LK.  A stream that comes back from a keyframe is half a frame out of phase with the cohort; with
 // the pose-only batch served first the cohort arrives at its next LK request while the straggler still waits there, and they merge.
@@ -49,6 +52,10 @@ class StreamBatcher {
     long lk_calls = 0, lk_jobs = 0, po_calls = 0, po_jobs = 0, ba_calls = 0, ba_jobs = 0, kf_calls = 0, kf_jobs = 0;   // kf: detection, stereo LK, triangulation
     double lk_s = 0, po_s = 0, ba_s = 0, kf_s = 0;  // seconds inside the batched library calls
     double wait_s = 0;                               // seconds the per-frame dispatcher waited for the streams' host code
+    long loop_calls = 0, loop_jobs = 0;              // loop closing's keyframe step: ssx_kfdb_process_keyframe_batch calls and their jobs
+    double loop_s = 0;
+    long single_calls = 0;                           // a correction's calls (ComputeCorrectPose, LoopCorrect, the window's), one at a time
+    double single_s = 0;
   };
   Stats stats();
   void ResetStats();                                 // (after the streams' warm-up: the counters then describe the frames alone)

@@ -3,6 +3,7 @@
 KeyframeDatabase       ssx_kfdb_*: AddToKeyframeDatabase, DetectLoop and MatchFeatures (reference: src/ssvio/loopclosing.cpp:646-649,
                        :72-103, :105-145), and the per-keyframe step of LoopClosingThread as one call (process_keyframe / add_pending /
                        pending: ProcessNewKeyframe :596-634 + DetectLoop + MatchFeatures, the keyframe left on the device)
+process_keyframe_batch ssx_kfdb_process_keyframe_batch: that step for one keyframe of each of several databases, one launch chain
 pnp_ransac             ssx_pnp_ransac: the cv::solvePnPRansac call of ComputeCorrectPose (:205-206) under the contract of
                        tools/pnp_model.py
 loop_pose_opt          ssx_loop_pose_opt: OptimizeCurrentPose (:245-351)
@@ -28,9 +29,20 @@ class StepResult(C.Structure):
                 ("score", C.c_float), ("loop_kf_id", C.c_int64), ("n_pairs", C.c_int32), ("min_distance", C.c_int32)]
 
 
+class StepJob(C.Structure):
+    """ssx_kfdb_step_job"""
+    _fields_ = [("db", C.c_void_p), ("kf_id", C.c_int64), ("img", C.c_void_p), ("stride", C.c_int32), ("n_features", C.c_int32),
+                ("features", C.c_void_p), ("commit_pending", C.c_int32), ("pairs_cap", C.c_int32), ("pairs_out", i32_p),
+                ("res", C.POINTER(StepResult)), ("status_out", i32_p)]
+
+
 def _bind(lib):
     if getattr(lib, "_kfdb_bound", False):
         return
+    lib.ssx_kfdb_process_keyframe_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(StepJob), C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_float, C.c_int32]
+    if hasattr(lib, "ssx_kfdb_debug_last_batch"):
+        lib.ssx_kfdb_debug_last_batch.argtypes = [C.c_void_p, i32_p, i32_p, i64_p, i64_p]
     lib.ssx_kfdb_process_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, u8_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32,
                                               C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, i32_p, C.POINTER(StepResult)]
     lib.ssx_kfdb_add_pending.argtypes = [C.c_void_p]
@@ -144,9 +156,7 @@ class KeyframeDatabase:
         st = self.ctx.lib.ssx_kfdb_process_keyframe(self.handle, voc.handle, int(kf_id), ptr(image, u8_p), image.strides[0], image.shape[0], image.shape[1],
                                                     C.byref(prm), len(features), features.ctypes.data_as(C.c_void_p), int(pyramid_levels),
                                                     int(min_db_size), int(min_id_gap), float(threshold), int(pairs_cap), ptr(pairs, i32_p), C.byref(r))
-        out = dict(n_pyramid=r.n_pyramid, n_bow=r.n_bow, detect_ran=bool(r.detect_ran), n_scored=r.n_scored, found=bool(r.found),
-                   score=np.float32(r.score) if r.found else None, loop_kf_id=r.loop_kf_id if r.found else None, n_pairs=r.n_pairs,
-                   min_distance=r.min_distance, pairs=pairs[:min(r.n_pairs, pairs_cap)].copy())
+        out = _step_dict(r, pairs, pairs_cap)
         try:
             self.ctx.check(st)
         except Exception as e:
@@ -175,6 +185,67 @@ class KeyframeDatabase:
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
         self.ctx.check(self.ctx.lib.ssx_kfdb_debug_last_step(self.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(launches=a.value, syncs=b.value, bytes_up=c.value, bytes_down=d.value)
+
+
+def _step_dict(r, pairs, pairs_cap):
+    return dict(n_pyramid=r.n_pyramid, n_bow=r.n_bow, detect_ran=bool(r.detect_ran), n_scored=r.n_scored, found=bool(r.found),
+                score=np.float32(r.score) if r.found else None, loop_kf_id=r.loop_kf_id if r.found else None, n_pairs=r.n_pairs,
+                min_distance=r.min_distance, pairs=pairs[:min(r.n_pairs, pairs_cap)].copy())
+
+
+def step_job_table(jobs):
+    """the ssx_kfdb_step_job table of process_keyframe_batch's jobs -> (table, results, statuses, per job (image, features, pairs, pairs_cap),
+    image shape); the arrays the table points into live as long as the returned objects"""
+    n = len(jobs)
+    table = (StepJob * max(n, 1))()
+    res, status, keep = (StepResult * max(n, 1))(), (C.c_int32 * max(n, 1))(), []
+    shape = None
+    for j, q in enumerate(jobs):
+        image = np.asarray(q["image"])
+        if image.ndim != 2 or image.dtype != np.uint8 or image.strides[1] != 1:
+            image = np.ascontiguousarray(image, dtype=np.uint8)
+        if shape is None:
+            shape = image.shape
+        elif image.shape != shape:
+            raise ValueError("the images of a call share one shape")
+        features = np.ascontiguousarray(q["features"], dtype=KP_DTYPE)
+        cap = q.get("pairs_cap")
+        if cap is None:                                           # a std::set of (current class_id, loop class_id): bounded by the winner's
+            cap = 65535                                           # descriptors, and a keyframe has no more than 65535
+        pairs = np.zeros((max(cap, 1), 2), np.int32)
+        keep.append((image, features, pairs, int(cap)))
+        table[j] = StepJob(q["db"].handle, int(q["kf_id"]), image.ctypes.data, image.strides[0], len(features), features.ctypes.data,
+                           1 if q.get("commit_pending") else 0, int(cap), ptr(pairs, i32_p), C.pointer(res[j]), C.cast(C.byref(status, 4 * j), i32_p))
+    return table, res, status, keep, shape if shape is not None else (0, 0)
+
+
+def process_keyframe_batch(voc, jobs, prm, threshold, pyramid_levels=8, min_db_size=0, min_id_gap=20, images_on_device=False):
+    """The per-keyframe step of several databases of voc's context in ONE call (ssx_kfdb_process_keyframe_batch).  jobs = dicts of
+    db (KeyframeDatabase), kf_id, image, features and optionally commit_pending (add_pending() first, inside the call) and pairs_cap;
+    the images share one shape and row stride.  -> one dict per job in process_keyframe's form plus status, the job's ssx_status.
+    SsxError carries .results (that list) when the call reports a job's status; a call that was rejected has touched nothing.
+    images_on_device: the image buffers are pinned or device memory and are read where they lie."""
+    ctx = voc.ctx
+    _bind(ctx.lib)
+    n = len(jobs)
+    table, res, status, keep, (rows, cols) = step_job_table(jobs)
+    st = ctx.lib.ssx_kfdb_process_keyframe_batch(voc.handle, n, table, rows, cols, C.byref(prm), int(pyramid_levels), int(min_db_size), int(min_id_gap),
+                                                 float(threshold), 1 if images_on_device else 0)
+    out = [dict(_step_dict(res[j], keep[j][2], keep[j][3]), status=status[j]) for j in range(n)]
+    try:
+        ctx.check(st)
+    except Exception as e:
+        e.results = out
+        raise
+    return out
+
+
+def debug_last_batch(ctx):
+    """tests / tools hook -> dict(launches, syncs, bytes_up, bytes_down) of the context's last process_keyframe_batch"""
+    _bind(ctx.lib)
+    a, b, c, d = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+    ctx.check(ctx.lib.ssx_kfdb_debug_last_batch(ctx.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+    return dict(launches=a.value, syncs=b.value, bytes_up=c.value, bytes_down=d.value)
 
 
 def debug_bow(voc, desc):
