@@ -814,6 +814,45 @@ SSX_API ssx_status ssx_kfdb_pending(ssx_kf_database* db, int64_t* kf_id, int32_t
                                     uint8_t* desc_out, int32_t* class_id_out, int32_t* n_pyramid, int32_t bow_cap,
                                     int32_t* ids_out, double* vals_out, int32_t* n_bow);
 
+/* The candidate query of relocalisation (the reference has a TODO there, src/ssvio/frontend.cpp:62-66): which stored
+ * keyframes a frame that lost tracking resembles, and its feature matches against each of them, in ONE call with ONE
+ * synchronisation (two more the first time an image shape is planned); neither the launches nor the synchronisations
+ * depend on max_candidates or on the number of stored keyframes.  The frame is described and its BowVector assembled as
+ * ssx_kfdb_process_keyframe does it; EVERY stored keyframe is scored (no id gap, no minimum size).  With f[row] the
+ * score narrowed to float and f_best the largest, the candidates are the rows with f > 0, f >= threshold and
+ * f >= ratio * f_best (a float product), ordered by f descending and then by row ascending (the lower id first), cut to
+ * max_candidates (tools/reloc_model.py): cand[0] is the winner of ssx_kfdb_detect_loop(INT64_MAX, that BowVector,
+ * min_id_gap 0, threshold).  Per candidate, n_pairs, min_distance and its slice pairs_out[c * pairs_cap * 2 ...] are bit
+ * for bit what ssx_kfdb_match_features(cand.kf_id, the frame's descriptors and class ids) returns; a candidate stored
+ * without descriptors has no_descriptors = 1, no pairs and min_distance -1 and is no error.  SSX_ERR_CAPACITY when some
+ * candidate has more than pairs_cap pairs: every count is true and the first pairs_cap pairs of each are written.
+ * The database is only read: the stored keyframes and the pending keyframe are as before the call.
+ * SSX_ERR_INVALID_ARG, before anything is touched: a null required pointer, max_candidates outside
+ * [1, SSX_RELOC_MAX_CANDIDATES], ratio not finite or outside [0, 1], threshold negative or NaN, a vocabulary of another
+ * context; SSX_ERR_UNSUPPORTED: n_features * pyramid_levels > 65535.  An empty database, no features, no surviving
+ * keypoint or an empty vocabulary: n_candidates = 0 and SSX_OK. */
+#define SSX_RELOC_MAX_CANDIDATES 8
+typedef struct ssx_reloc_candidate {
+  int64_t kf_id;
+  float   score;            /* f */
+  int32_t row;              /* its index among the stored keyframes, in id order */
+  int32_t no_descriptors;
+  int32_t n_pairs;
+  int32_t min_distance;
+} ssx_reloc_candidate;
+typedef struct ssx_reloc_query_result {
+  int32_t n_pyramid, n_bow; /* as ssx_kfdb_step_result */
+  int32_t n_scored;         /* stored keyframes */
+  int32_t n_candidates;
+  ssx_reloc_candidate cand[SSX_RELOC_MAX_CANDIDATES];   /* behind n_candidates: kf_id -1, row -1, min_distance -1 */
+} ssx_reloc_query_result;
+SSX_API ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, const uint8_t* img, int32_t stride,
+                                             int32_t rows, int32_t cols, const ssx_orb_params* prm, int32_t n_features,
+                                             const ssx_keypoint* features, int32_t pyramid_levels, int32_t max_candidates,
+                                             float threshold, float ratio, int32_t pairs_cap,
+                                             int32_t* pairs_out /* max_candidates x pairs_cap x 2 */,
+                                             ssx_reloc_query_result* res);
+
 /* ------------------------------------------------------------------------------------------------
  * The pose correction of loop closing -- replaces LoopClosing::ComputeCorrectPose (src/ssvio/loopclosing.cpp:147-243)
  * with its cv::solvePnPRansac call (:205-206) and LoopClosing::OptimizeCurrentPose (:245-351).
@@ -846,6 +885,20 @@ SSX_API ssx_status ssx_pnp_ransac(ssx_ctx* ctx, const double* K4, int32_t M, con
 SSX_API ssx_status ssx_loop_pose_opt(ssx_ctx* ctx, double* pose_io, const double* K4, int32_t M, const double* xyz,
                                      const double* uv, double chi2_th, double huber_delta, uint8_t* inlier_out,
                                      int32_t* n_inliers);
+/* n poses in ONE call (relocalisation: one per candidate keyframe): per job, bit for bit, ssx_pnp_ransac(K4, M, xyz, uv,
+ * max_iters, reproj_px, seed) and, where that found a pose, ssx_loop_pose_opt(chi2_th, huber_delta) started from it --
+ * pose_out, inlier_out and n_inliers are then the refinement's -- whatever n is and wherever the job stands in the table.
+ * A job with M < 3 or nothing found: found = 0, the identity, n_inliers = 0, inlier_out zeroed.  One upload, one download,
+ * one synchronisation; one launch of the RANSAC and at most one of the refinement per kernel class, independent of n.
+ * n in [0, SSX_PNP_BATCH_MAX] (0: SSX_OK); otherwise SSX_ERR_INVALID_ARG as ssx_pnp_ransac, before anything is written. */
+#define SSX_PNP_BATCH_MAX 64
+typedef struct ssx_pnp_pose_job {
+  int32_t M; const double* xyz; const double* uv; uint32_t seed;             /* in */
+  double pose_out[7]; uint8_t* inlier_out /* nullable, M */;                 /* out */
+  int32_t found, n_ransac_inliers, best_hypothesis, n_inliers;
+} ssx_pnp_pose_job;
+SSX_API ssx_status ssx_pnp_pose_batch(ssx_ctx* ctx, const double* K4, int32_t n, ssx_pnp_pose_job* jobs, int32_t max_iters,
+                                      double reproj_px, double chi2_th, double huber_delta);
 
 typedef enum ssx_loop_verdict {
   SSX_LOOP_OK = 0,               /* ComputeCorrectPose returns true */

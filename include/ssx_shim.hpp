@@ -356,6 +356,50 @@ class KeyframeDatabase {
     return out;
   }
 
+  // Relocalisation (the reference has a TODO at frontend.cpp:62-66): the stored keyframes a frame that lost tracking resembles, best first,
+  // and MatchFeatures against each of them, in ONE call (ssx_kfdb_relocalize_query).  features[i] = the frame's keypoints, as for
+  // ProcessNewKeyframe.  Candidates: float score > 0, >= threshold and >= ratio * the best, at most max_candidates.  The database and its
+  // pending keyframe are only read.
+  struct RelocCandidate {
+    unsigned long key_frame_id;
+    float score;
+    bool has_descriptors;
+    int min_distance;
+    std::set<std::pair<int, int>> set_valid_feature_matches;   // (feature of the frame, feature of the keyframe)
+  };
+  std::vector<RelocCandidate> RelocalizeQuery(const ORBVocabulary& voc, const uint8_t* image, int stride, int rows, int cols, const ORBextractor& extractor,
+                                              const std::vector<ssx_keypoint>& features, int max_candidates, float threshold, float ratio = 0.75f,
+                                              int pyramid_levels = 8, ssx_reloc_query_result* result = nullptr)
+  {
+    if (!voc.get()) throw std::invalid_argument("RelocalizeQuery: no vocabulary loaded");
+    const size_t K = (size_t)std::max(max_candidates, 1);
+    size_t cap = std::max<size_t>(4096, features.size() * (size_t)std::max(pyramid_levels, 1));
+    std::vector<int32_t> pairs(2 * K * cap);
+    ssx_reloc_query_result res{};
+    auto call = [&]() {
+      return ssx_kfdb_relocalize_query(db_, voc.get(), image, stride, rows, cols, &extractor.params(), (int32_t)features.size(), features.data(), pyramid_levels,
+                                       max_candidates, threshold, ratio, (int32_t)cap, pairs.data(), &res);
+    };
+    ssx_status st = call();
+    if (st == SSX_ERR_CAPACITY) {                            // a larger stored keyframe: the counts are known now
+      for (int32_t c = 0; c < res.n_candidates; ++c) cap = std::max(cap, (size_t)res.cand[c].n_pairs);
+      pairs.assign(2 * K * cap, 0);
+      st = call();
+    }
+    ctx_.check(st);
+    if (result) *result = res;
+    std::vector<RelocCandidate> out((size_t)res.n_candidates);
+    for (int32_t c = 0; c < res.n_candidates; ++c) {
+      const ssx_reloc_candidate& q = res.cand[c];
+      out[(size_t)c].key_frame_id = (unsigned long)q.kf_id; out[(size_t)c].score = q.score; out[(size_t)c].has_descriptors = q.no_descriptors == 0;
+      out[(size_t)c].min_distance = q.min_distance;
+      const int32_t* p = pairs.data() + 2 * (size_t)c * cap;
+      auto& set = out[(size_t)c].set_valid_feature_matches;
+      for (int32_t i = 0; i < q.n_pairs; ++i) set.emplace_hint(set.end(), p[2 * i], p[2 * i + 1]);
+    }
+    return out;
+  }
+
   // AddToKeyframeDatabase() (:646-649) for the keyframe ProcessNewKeyframe left on the device: no byte crosses PCIe
   void AddToKeyframeDatabase() { ctx_.check(ssx_kfdb_add_pending(db_)); }
 
@@ -428,6 +472,15 @@ inline std::vector<KeyframeDatabase::KeyframeStep> ProcessNewKeyframes(const ORB
     for (int32_t i = 0; i < out[j].result.n_pairs; ++i)
       out[j].set_valid_feature_matches.emplace_hint(out[j].set_valid_feature_matches.end(), pairs[j][2 * i], pairs[j][2 * i + 1]);
   return out;
+}
+
+// The pose of several candidates in ONE call (ssx_pnp_pose_batch): per job solvePnPRansac under the contract of ssx_pnp_ransac (100
+// iterations, 5.991 px as the reference passes them) and, where it found a pose, OptimizeCurrentPose over all pairs from it.  xyz / uv /
+// inlier_out of every job are the caller's arrays; the results are written into the jobs.
+inline void PnpPoseBatch(Context& ctx, const double K4[4], std::vector<ssx_pnp_pose_job>& jobs, int iterations = 100, double reproj_px = 5.991,
+                         double chi2_th = 5.991, double huber_delta = 1.0)
+{
+  ctx.check(ssx_pnp_pose_batch(ctx.get(), K4, (int32_t)jobs.size(), jobs.data(), iterations, reproj_px, chi2_th, huber_delta));
 }
 
 // What LoopClosing::ComputeCorrectPose reads of one entry of set_valid_feature_matches_: the pair itself, the position of

@@ -43,6 +43,13 @@
 // ONE launch chain: k_*_jobs are the same kernels indexed by a device job table (kf_batch.hpp) -- a workgroup (or a grid row) per job, the
 // counts read from the job's step header -- and call the very __device__ bodies of the single-call kernels, so the ordered double chains
 // are the same code.  A job may commit its previous pending keyframe first, inside the chain.
+//
+// ssx_kfdb_relocalize_query is the query of a frame that lost tracking: the same describe / compact / words / BowVector chain
+// into scratch of its own, k_kfdb_score over EVERY stored keyframe, then
+// k_kfdb_topk    one workgroup: the K <= 8 largest keys (float bits << 32) | ~row of the scores -- per thread in registers, merged in K
+//                rounds of a block-wide maximum -- screened by the threshold and by a share of the best, and the match job of every
+//                candidate filled on the device, so that k_bf_match_jobs + k_kfdb_pairs_jobs match all K behind it without a round trip.
+// The database and its pending keyframe are only read.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -284,6 +291,7 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const int* idx, co
 __global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs_jobs(const KfMatchJob* jobs, KfMatchJob one)
 {
   const KfMatchJob j = jobs ? jobs[blockIdx.x] : one;
+  if (j.nl <= 0) return;                                      // a table filled on the device (k_kfdb_topk) has empty entries: their header stays (0, -1)
   pairs_block(j.idx, j.dist, j.nl, j.loop_cls, j.cur_cls, j.keys, j.hdr, j.pairs);
 }
 
@@ -476,6 +484,97 @@ __global__ __launch_bounds__(256) void k_kfdb_score_jobs(const KfJobDev* jobs, S
   } else {
     score_rows(arena, rows, n_rows, j.p_ids, j.p_vals, nq, j.scores, &h->best);
   }
+}
+
+// ---- the candidate query of relocalisation (ssx_kfdb_relocalize_query; the rule: tools/reloc_model.py) ----
+constexpr int kTopK = SSX_RELOC_MAX_CANDIDATES;
+struct RelocDev {                    // what the query's one synchronisation brings down
+  StepHdr h;
+  int32_t n_cand, pad;
+  int32_t row[kTopK];                // the candidates in order; -1 behind the last
+  uint32_t fbits[kTopK];             // their float scores
+};
+// where candidate c's match job finds the frame's side and its slices of the scratch and of the mapped pinned output
+struct RelocMatch {
+  const uint8_t* cur_desc; const int32_t* cur_cls;
+  int* idx; int* dist; unsigned long long* keys;   // c * max_nl, c * max_nl, c * keys_stride (keys null: every sort fits the LDS)
+  int32_t* hdr; int32_t* pairs;                    // 2 c, 2 c * max_nl
+  int max_nl; size_t keys_stride;
+};
+
+// One workgroup after k_kfdb_score: the kTopK largest keys (float bits << 32) | ~row of the scores, i.e. f descending and then row
+// ascending.  A thread keeps the kTopK largest of rows tid + 1024 k in registers, sorted; kTopK rounds then take the block-wide maximum
+// of the threads' heads through LDS, and the thread that held it moves on to its next (keys of rows are unique, 0 = none).  No
+// floating-point arithmetic but the narrowing and the one product ratio * f_best, no atomics: a pure function of the scores.
+// Threads 0 .. max_cand - 1 then screen their candidate (f >= threshold, f >= ratio * f_best: both hold for a prefix of the order)
+// and fill its match job, with nl = 0 where there is nothing to match (no candidate, no descriptors on either side).
+__global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const double* scores, int n_rows, const char* arena, const KfRow* rows, int max_cand, float threshold,
+                                                             float ratio, RelocDev* out, KfMatchJob* jobs, RelocMatch mb)
+{
+  __shared__ unsigned long long s_wave[kPairsThreads / 64];
+  __shared__ unsigned long long s_top[kTopK];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long top[kTopK];
+#pragma unroll
+  for (int k = 0; k < kTopK; ++k) top[k] = 0;
+  for (int row = tid; row < n_rows; row += kPairsThreads) {
+    const float f = (float)scores[row];
+    if (!(f > 0.f)) continue;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(f) << 32) | (unsigned)~row;
+    if (key <= top[kTopK - 1]) continue;
+    top[kTopK - 1] = key;
+#pragma unroll
+    for (int k = kTopK - 1; k > 0; --k) {                     // one pass of a bubble: the array stays sorted descending
+      const unsigned long long a = top[k - 1], b = top[k];
+      top[k - 1] = max(a, b); top[k] = min(a, b);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kTopK; ++r) {
+    unsigned long long m = top[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned long long)__shfl_xor((long long)m, o));
+    if (lane == 0) s_wave[wave] = m;
+    __syncthreads();
+    unsigned long long win = 0;
+#pragma unroll
+    for (int w = 0; w < kPairsThreads / 64; ++w) win = max(win, s_wave[w]);
+    if (tid == 0) s_top[r] = win;
+    if (win != 0 && top[0] == win) {                          // exactly one thread: it moves on to its next key
+#pragma unroll
+      for (int k = 0; k + 1 < kTopK; ++k) top[k] = top[k + 1];
+      top[kTopK - 1] = 0;
+    }
+    __syncthreads();                                          // s_wave is rewritten by the next round; s_top is read below
+  }
+  if (tid >= 64) return;
+  const int c = tid;
+  const unsigned long long key = c < kTopK ? s_top[c] : 0;
+  const float f = __uint_as_float((unsigned)(key >> 32)), f_best = __uint_as_float((unsigned)(s_top[0] >> 32));
+  const bool ok = c < max_cand && key != 0 && f >= threshold && f >= ratio * f_best;
+  const int n_cand = __popcll(__ballot(ok));
+  if (c == 0) { out->n_cand = n_cand; out->pad = 0; }
+  if (c >= kTopK) return;
+  const int row = (int)~(unsigned)key;
+  out->row[c] = ok ? row : -1;
+  out->fbits[c] = ok ? (unsigned)(key >> 32) : 0u;
+  if (c >= max_cand) return;
+  const int n_cur = out->h.n_pyr;                             // (k_kf_compact's count, an earlier launch)
+  KfMatchJob j{};
+  j.cur_desc = mb.cur_desc; j.cur_cls = mb.cur_cls;
+  j.idx = mb.idx + (size_t)c * mb.max_nl; j.dist = mb.dist + (size_t)c * mb.max_nl;
+  j.keys = mb.keys ? mb.keys + (size_t)c * mb.keys_stride : nullptr;
+  j.hdr = mb.hdr + 2 * c; j.pairs = mb.pairs + (size_t)2 * c * mb.max_nl;
+  j.n_cur = n_cur;
+  if (ok) {
+    const KfRow r = rows[row];
+    if (r.n_desc > 0 && r.n_desc <= mb.max_nl && n_cur > 0) { // (n_desc <= max_nl by construction: the scratch is sized by the host mirror's largest)
+      const char* blob = arena + r.off;
+      j.loop_desc = (const uint8_t*)(blob + blob_desc(r.n_bow, r.n_desc)); j.loop_cls = (const int32_t*)(blob + blob_class(r.n_bow));
+      j.nl = r.n_desc;
+    }
+  }
+  jobs[c] = j;
 }
 
 }  // namespace
@@ -932,6 +1031,111 @@ ssx_status ssx_kfdb_pending(ssx_kf_database* db, int64_t* kf_id, int32_t kps_cap
     if (vals_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(vals_out, pa.vals, (size_t)8 * pe.n_bow, hipMemcpyDeviceToHost, s));
   }
   SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  return SSX_OK;
+}
+
+// The candidate query of relocalisation: describe -> k_kf_compact -> k_voc_words -> k_kf_bow -> k_kfdb_score (every stored keyframe) ->
+// k_kfdb_topk (the candidates and their match jobs, on the device) -> k_bf_match_jobs + k_kfdb_pairs_jobs with grid.y = max_candidates,
+// then ONE synchronisation.  The match grid and the scratch are sized by the host mirror's largest n_desc, so nothing has to come down
+// before the match is enqueued; a job without a candidate exits.  The frame's compacted arrays live in db->io, never in db->pend.
+ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, const uint8_t* img, int32_t stride, int32_t rows, int32_t cols,
+                                     const ssx_orb_params* prm, int32_t n_features, const ssx_keypoint* features, int32_t pyramid_levels, int32_t max_candidates,
+                                     float threshold, float ratio, int32_t pairs_cap, int32_t* pairs_out, ssx_reloc_query_result* res)
+{
+  if (!db || !voc || !res || !prm || !img || rows <= 0 || cols <= 0 || stride < cols || n_features < 0 || (n_features > 0 && !features) || pyramid_levels < 1 ||
+      pyramid_levels > ssxorb::MAX_LEVELS || pairs_cap < 0 || (pairs_cap > 0 && !pairs_out) || max_candidates < 1 || max_candidates > kTopK ||
+      !std::isfinite(ratio) || ratio < 0.f || ratio > 1.f || !(threshold >= 0.f))
+    return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = db->ctx;
+  if (voc->ctx != ctx) { ctx->set_error("ssx_kfdb_relocalize_query: the vocabulary belongs to another context"); return SSX_ERR_INVALID_ARG; }
+  if ((int64_t)n_features * pyramid_levels > 65535) {
+    ctx->set_error("ssx_kfdb_relocalize_query: %d features x %d levels: more than 65535 pyramid keypoints", n_features, pyramid_levels);
+    return SSX_ERR_UNSUPPORTED;
+  }
+  db->last = KfStepStats{};
+  *res = ssx_reloc_query_result{};
+  for (int c = 0; c < kTopK; ++c) { res->cand[c].kf_id = -1; res->cand[c].row = -1; res->cand[c].min_distance = -1; }
+  const int N = n_features * pyramid_levels, K = max_candidates, n_db = (int)db->ids.size();
+  res->n_scored = n_db;
+  if (N == 0) return SSX_OK;
+  int max_nl = 0;
+  for (const KfRow& r : db->rows) max_nl = std::max(max_nl, r.n_desc);
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  KfStepStats st{};
+  ssxorb::Described d;
+  if (ssx_status s = ssxorb::describe_enqueue(ctx, img, stride, rows, cols, *prm, features, n_features, pyramid_levels, &d)) return s;
+  st.launches += d.launches; st.syncs += d.syncs; st.bytes_up += (int64_t)d.bytes_up;
+  // the device scratch: the frame's compacted arrays (PendArrays' layout, in a buffer of the query's own), the result block, the BowVector's
+  // scratch, the scores, the match table and every job's match scratch
+  size_t keys_stride = 1;
+  while (keys_stride < (size_t)max_nl) keys_stride *= 2;
+  if (max_nl <= kSortLds) keys_stride = 0;
+  PendArrays pa{};
+  RelocDev* dh; BowScratch b{}; double* scores; KfMatchJob* jobs; RelocMatch mb{};
+  char* frame;
+  auto scratch = [&](auto&& f) {
+    f(frame, pend_arrays(nullptr, N, pa)); f(dh, sizeof(RelocDev)); bow_scratch(f, b, N); f(scores, (size_t)n_db * 8); f(jobs, sizeof(KfMatchJob) * (size_t)K);
+    f(mb.idx, (size_t)4 * K * max_nl); f(mb.dist, (size_t)4 * K * max_nl); f(mb.keys, (size_t)8 * K * keys_stride);
+  };
+  SSX_HIP_TRY(ctx, db->io.reserve(carve(nullptr, scratch)));
+  carve(db->io.as<char>(), scratch);
+  pend_arrays(frame, N, pa);
+  // the mapped pinned block: [the result block's copy | (pair count, minimum distance) per job | max_nl pairs per job]
+  RelocDev* hh; int32_t* hm; int32_t* hp;
+  auto pinned = [&](auto&& f) { f(hh, sizeof(RelocDev)); f(hm, (size_t)8 * kTopK); f(hp, (size_t)8 * K * max_nl); };
+  SSX_HIP_TRY(ctx, db->stage.reserve(carve(nullptr, pinned)));
+  char* hs = db->stage.as<char>();
+  carve(hs, pinned);
+  for (int c = 0; c < kTopK; ++c) { hm[2 * c] = 0; hm[2 * c + 1] = -1; }
+  void* dp = nullptr;
+  SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dp, hs, 0));
+  mb.cur_desc = pa.desc; mb.cur_cls = pa.cls; mb.max_nl = max_nl; mb.keys_stride = keys_stride;
+  if (keys_stride == 0) mb.keys = nullptr;
+  mb.hdr = (int32_t*)((char*)dp + ((char*)hm - hs)); mb.pairs = (int32_t*)((char*)dp + ((char*)hp - hs));
+  hipStream_t s = ctx->stream;
+  SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact, dim3(1), dim3(kPairsThreads), 0, s, d.kps, d.desc, d.keep, N, pa.kps, pa.desc, pa.cls, &dh->h.n_pyr));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, launch_bow(ctx, voc, pa.desc, N, &dh->h.n_pyr, b, pa.ids, pa.vals, &dh->h.n_bow, &dh->h.best));
+  st.launches += 3;
+  if (n_db > 0) {
+    launch_score(db, n_db, pa.ids, pa.vals, N, &dh->h.n_bow, scores, &dh->h.best);
+    SSX_HIP_TRY(ctx, hipGetLastError());
+    SSX_PROF(ctx, KID_LOOP_TOPK, hipLaunchKernelGGL(k_kfdb_topk, dim3(1), dim3(kPairsThreads), 0, s, scores, n_db, db->arena.as<char>(), db->table.as<KfRow>(), K,
+                                                    threshold, ratio, dh, jobs, mb));
+    SSX_HIP_TRY(ctx, hipGetLastError());
+    st.launches += 2;
+    if (max_nl > 0) {                                         // (else no stored keyframe has a descriptor: nothing can match)
+      SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match_jobs(s, jobs, KfMatchJob{}, K, max_nl));
+      SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs_jobs, dim3(K), dim3(kPairsThreads), 0, s, jobs, KfMatchJob{}));
+      SSX_HIP_TRY(ctx, hipGetLastError());
+      st.launches += 2;
+    }
+  }
+  // (n_db == 0: k_kfdb_topk did not run and n_cand, row and fbits of the block are not written; the host does not read them then)
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hh, dh, sizeof(RelocDev), hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  ++st.syncs; st.bytes_down += (int64_t)sizeof(RelocDev);
+  res->n_pyramid = hh->h.n_pyr; res->n_bow = hh->h.n_bow;
+  const int n_cand = n_db > 0 ? std::min(std::max(hh->n_cand, 0), K) : 0;
+  res->n_candidates = n_cand;
+  int over = -1;
+  for (int c = 0; c < n_cand; ++c) {
+    ssx_reloc_candidate& q = res->cand[c];
+    const int row = hh->row[c];
+    if (row < 0 || row >= n_db) { ctx->set_error("ssx_kfdb_relocalize_query: candidate %d names row %d of %d", c, row, n_db); return SSX_ERR_HIP; }
+    q.row = row; q.kf_id = db->ids[row];
+    memcpy(&q.score, &hh->fbits[c], 4);
+    q.no_descriptors = db->rows[row].n_desc < 0 ? 1 : 0;
+    q.n_pairs = hm[2 * c]; q.min_distance = hm[2 * c + 1];
+    st.bytes_down += 8 + (int64_t)q.n_pairs * 8;
+    if (pairs_cap > 0) memcpy(pairs_out + (size_t)2 * c * pairs_cap, hp + (size_t)2 * c * max_nl, (size_t)std::min(q.n_pairs, pairs_cap) * 8);
+    if (q.n_pairs > pairs_cap && over < 0) over = c;
+  }
+  db->last = st;
+  if (over >= 0) {
+    ctx->set_error("ssx_kfdb_relocalize_query: candidate %d has %d pairs but capacity %d", over, res->cand[over].n_pairs, pairs_cap);
+    return SSX_ERR_CAPACITY;
+  }
   return SSX_OK;
 }
 

@@ -25,6 +25,10 @@
 //                (qx qy qz qw tx ty tz, normalised, qw >= 0), its inlier mask and the header: they stay in device memory, where
 //                the refinement (k_pose_only*, gated by the header's `found`) picks the pose up.
 //
+// ssx_pnp_pose_batch (relocalisation: one pose per candidate keyframe) is n of these in one call: k_pnp_ransac_jobs is the same workgroup
+// body with the job as blockIdx.y -- a table of PnpDev, each with its own best / ticket words and header -- and the refinement one launch
+// per kernel class over a table of descriptors, each gated on its job's header.
+//
 // This file is compiled with -ffp-contract=off: every operation rounds as the model's does (tests/test_p3p_gpu.py: R, t and the pose of
 // every slot of ssx_pnp_debug_p3p are the model's bytes).
 #include <algorithm>
@@ -350,7 +354,8 @@ __device__ __forceinline__ void rot_to_quat(const double* R, double* q)
   for (int k = 0; k < 4; ++k) q[k] = q[k] / sg;
 }
 
-__global__ __launch_bounds__(256) void k_pnp_ransac(PnpDev d)
+// the workgroup blockIdx.x of the gridDim.x that score one problem's hypotheses: the body of k_pnp_ransac and k_pnp_ransac_jobs
+__device__ __forceinline__ void ransac_block(const PnpDev& d)
 {
   __shared__ unsigned long long s_best[4];
   __shared__ int s_last;
@@ -422,6 +427,19 @@ __global__ __launch_bounds__(256) void k_pnp_ransac(PnpDev d)
     d.hdr->best = found ? id : -1;
     d.hdr->pad = 0;
   }
+}
+
+__global__ __launch_bounds__(256) void k_pnp_ransac(PnpDev d)
+{
+  ransac_block(d);
+}
+
+// grid (ceil(H / 4), job): every job of ssx_pnp_pose_batch has its own problem, `best` / `ticket` words and header in the table; H is
+// shared, so the last workgroup of a grid row finishes that row's job
+__global__ __launch_bounds__(256) void k_pnp_ransac_jobs(const PnpDev* jobs)
+{
+  const PnpDev d = jobs[blockIdx.y];
+  ransac_block(d);
 }
 
 // tap: one thread per triple, the solver and the quaternion as k_pnp_ransac calls them; slots that are not valid are zeros
@@ -651,6 +669,101 @@ ssx_status ssx_loop_compute_pose(ssx_ctx* ctx, int32_t n_pairs, const double* lo
   ssx::se3_inverse(T_loop, inv);
   ssx::se3_mul(out->corrected_pose, inv, out->relative_to_loop);                   // :237-238
   out->verdict = SSX_LOOP_OK;
+  return SSX_OK;
+}
+
+// n times (ssx_pnp_ransac, then ssx_loop_pose_opt from the pose it found) in one block, one upload, one launch of k_pnp_ransac_jobs, one
+// launch of the refinement per kernel class, one download and one synchronisation.  The jobs with a triple to sample (M >= 3) are
+// ordered by class (po_class), in job order inside a class, so that each class's descriptors are one run of the table.
+ssx_status ssx_pnp_pose_batch(ssx_ctx* ctx, const double* K4, int32_t n, ssx_pnp_pose_job* jobs, int32_t max_iters, double reproj_px, double chi2_th,
+                              double huber_delta)
+{
+  if (!ctx || !K4 || n < 0 || n > SSX_PNP_BATCH_MAX || (n > 0 && !jobs) || max_iters < 1 || max_iters > SSX_PNP_MAX_ITERS || !finite4(K4) || !(reproj_px >= 0.0))
+    return SSX_ERR_INVALID_ARG;
+  for (int j = 0; j < n; ++j)
+    if (jobs[j].M < 0 || (jobs[j].M > 0 && (!jobs[j].xyz || !jobs[j].uv))) return SSX_ERR_INVALID_ARG;
+  std::vector<int> act;                                       // the jobs that run, in table order
+  int first[4] = {0, 0, 0, 0};                                // class c is act[first[c] .. first[c + 1])
+  for (int c = 0; c < 3; ++c) {
+    for (int j = 0; j < n; ++j)
+      if (jobs[j].M >= 3 && po_class(jobs[j].M) == c) act.push_back(j);
+    first[c + 1] = (int)act.size();
+  }
+  for (int j = 0; j < n; ++j) {
+    ssx_pnp_pose_job& q = jobs[j];
+    q.found = 0; q.n_ransac_inliers = 0; q.best_hypothesis = -1; q.n_inliers = 0;
+    memcpy(q.pose_out, kIdentity, sizeof(kIdentity));
+    if (q.inlier_out && q.M > 0) memset(q.inlier_out, 0, (size_t)q.M);
+  }
+  const size_t na = act.size();
+  if (na == 0) return SSX_OK;
+  struct Block {
+    unsigned long long* zero = nullptr;                       // (best, ticket) of every job: zero before the launch
+    PnpDev* rt = nullptr;                                     // the RANSAC's job table
+    PoDev* pt = nullptr;                                      // the refinement's descriptors
+    std::vector<PoProblem> po;
+    std::vector<PnpHdr*> hdr;
+    std::vector<uint8_t*> mask;
+    char *sent = nullptr, *ret = nullptr;                     // [start, sent) goes up, [ret, end) comes back
+  } dev, host;
+  auto wire_block = [&](Block& b, char* base) {
+    b.po.assign(na, PoProblem{}); b.hdr.assign(na, nullptr); b.mask.assign(na, nullptr);
+    return carve(base, [&](auto&& f) {
+      f(b.zero, 16 * na); f(b.rt, sizeof(PnpDev) * na); f(b.pt, sizeof(PoDev) * na);
+      for (size_t k = 0; k < na; ++k) {
+        PoProblem& p = b.po[k];
+        p.M = jobs[act[k]].M;
+        f(p.xyz, sizeof(double) * 3 * (size_t)p.M); f(p.uv, sizeof(double) * 2 * (size_t)p.M); f(p.pose_in, sizeof(double) * 8);
+      }
+      f(b.sent, 0);
+      for (size_t k = 0; k < na; ++k) {                       // what only the device uses: the generic kernel's scratch, the RANSAC's mask
+        PoProblem& p = b.po[k];
+        const size_t scratch = po_class(p.M) == 2 ? (size_t)p.M : 0;
+        f(p.err, sizeof(double) * 2 * scratch); f(p.level, scratch); f(b.mask[k], (size_t)p.M);
+      }
+      f(b.ret, 0);
+      for (size_t k = 0; k < na; ++k) { f(b.po[k].res, b.po[k].result_bytes()); f(b.hdr[k], sizeof(PnpHdr)); }
+    });
+  };
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = wire_block(host, nullptr);
+  SSX_HIP_TRY(ctx, ctx->pnp_arena.reserve(bytes));
+  SSX_HIP_TRY(ctx, ctx->pnp_stage.reserve(bytes));
+  char* hs = ctx->pnp_stage.as<char>();
+  char* ds = ctx->pnp_arena.as<char>();
+  wire_block(dev, ds);
+  wire_block(host, hs);
+  memset(host.zero, 0, 16 * na);
+  for (size_t k = 0; k < na; ++k) {
+    const ssx_pnp_pose_job& q = jobs[act[k]];
+    host.po[k].stage(q.xyz, q.uv, nullptr);
+    PnpDev& r = host.rt[k];
+    r.M = q.M; r.H = max_iters; r.seed = q.seed;
+    r.fx = K4[0]; r.fy = K4[1]; r.cx = K4[2]; r.cy = K4[3]; r.thr2 = reproj_px * reproj_px;
+    r.xyz = dev.po[k].xyz; r.uv = dev.po[k].uv;
+    r.best = dev.zero + 2 * k; r.ticket = reinterpret_cast<unsigned int*>(dev.zero + 2 * k + 1);
+    r.hdr = dev.hdr[k]; r.inlier = dev.mask[k]; r.hyp_counts = nullptr;
+    // OptimizeCurrentPose from the pose in the job's header, called off where the RANSAC found none (as pnp_launch_refine)
+    PoDev& d = host.pt[k];
+    po_set_scalars(d, q.M, 1, 4, 10, chi2_th, huber_delta, K4, &dev.hdr[k]->found);
+    dev.po[k].wire(d, dev.hdr[k]->pose);
+  }
+  hipStream_t s = ctx->stream;
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(ds, hs, (size_t)(host.sent - hs), hipMemcpyHostToDevice, s));
+  SSX_PROF(ctx, KID_PNP_RANSAC, hipLaunchKernelGGL(k_pnp_ransac_jobs, dim3((unsigned)((max_iters + 3) / 4), (unsigned)na), dim3(256), 0, s, dev.rt));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  for (int c = 0; c < 3; ++c)
+    if (first[c + 1] > first[c]) SSX_HIP_TRY(ctx, po_launch_device_table(ctx, c, (unsigned)(first[c + 1] - first[c]), dev.pt + first[c]));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(host.ret, dev.ret, bytes - (size_t)(host.ret - hs), hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  for (size_t k = 0; k < na; ++k) {
+    ssx_pnp_pose_job& q = jobs[act[k]];
+    const PnpHdr& hdr = *host.hdr[k];
+    q.n_ransac_inliers = hdr.n_inliers; q.best_hypothesis = hdr.best;
+    if (!hdr.found) continue;                                 // (the refinement was called off: its record holds nothing)
+    q.found = 1;
+    po_read_result(host.po[k].res, q.M, q.pose_out, q.inlier_out, &q.n_inliers);
+  }
   return SSX_OK;
 }
 

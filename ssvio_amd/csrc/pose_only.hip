@@ -71,13 +71,11 @@ __device__ __forceinline__ const PoTrace* po_trace_of() { return nullptr; }
 __device__ __forceinline__ const PoTrace* po_trace_of(const PoTrace& tr) { return &tr; }
 __device__ __forceinline__ const PoTrace* po_trace_at(const PoTrace* tv, unsigned problem) { return tv + problem; }
 
-// TR: empty for the shipped kernel -- its parameters and its code are what they were before the record existed --, PoTrace for the
-// traced instantiation of the test hook
-template <class... TR>
-__global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d, TR... trace)
+// one workgroup, one problem with its edges in device memory: the body of k_pose_only_generic and k_pose_only_generic_jobs.
+// TRACE: the traced instantiation of the test hook writes its record through tr
+template <bool TRACE>
+__device__ __forceinline__ void pose_only_generic_block(const PoDev& d, [[maybe_unused]] const PoTrace* tr)
 {
-  constexpr bool TRACE = sizeof...(TR) > 0;
-  [[maybe_unused]] const PoTrace* tr = po_trace_of(trace...);
   __shared__ double sRed[NRED][PT];
   __shared__ double sT[7], sTbak[7], sX[6];
   __shared__ double sCtl[8];      // 0 lambda, 1 ni, 2 currentChi, 3 rho, 4 qmax, 5 stop flag, 6 accepted
@@ -293,6 +291,21 @@ __global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d, TR... trace)
   }
   if (t < 7) d.pose_out[t] = sT[t];
   if (t == 0) *d.n_inliers = d.M - cnt_outliers;
+}
+
+// TR: empty for the shipped kernel -- its parameters and its code are what they were before the record existed --, PoTrace for the
+// traced instantiation of the test hook
+template <class... TR>
+__global__ __launch_bounds__(PT) void k_pose_only_generic(PoDev d, TR... trace)
+{
+  pose_only_generic_block<(sizeof...(TR) > 0)>(d, po_trace_of(trace...));
+}
+
+// the same for every problem of a table the device can read (blockIdx.x = problem): the generic jobs of ssx_pnp_pose_batch in one launch
+__global__ __launch_bounds__(PT) void k_pose_only_generic_jobs(const PoDev* dv)
+{
+  const PoDev d = dv[blockIdx.x];
+  pose_only_generic_block<false>(d, nullptr);
 }
 
 // ---- register-resident variant ------------------------------------------------------------------------------------
@@ -781,6 +794,13 @@ ssx_status po_batch(ssx_ctx* ctx, int32_t n, const ssx_pose_only_job* jobs, int3
 hipError_t po_launch_device(ssx_ctx* ctx, const PoDev* d)
 {
   po_launch(ctx, po_class(d->M), 1, d, nullptr);
+  return hipGetLastError();
+}
+
+hipError_t po_launch_device_table(ssx_ctx* ctx, int cls, unsigned n, const PoDev* dv)
+{
+  if (cls == 2) SSX_PROF(ctx, KID_POSE_ONLY, hipLaunchKernelGGL(k_pose_only_generic_jobs, dim3(n), dim3(PT), 0, ctx->stream, dv));
+  else po_launch(ctx, cls, n, dv, nullptr);
   return hipGetLastError();
 }
 

@@ -88,6 +88,9 @@ inline void po_read_result(const PoResult* r, int M, double* pose7, uint8_t* inl
 // One launch of the kernel of d->M > 0 edges on ctx->stream, no synchronisation.  d is a filled descriptor in pinned memory of the
 // caller's own, which stays as it is until the stream is idle (the register-resident kernels read it from there).
 hipError_t po_launch_device(ssx_ctx* ctx, const PoDev* d);
+// One launch for n > 0 problems that are all of class cls (po_class), one workgroup each: dv[0 .. n) are their descriptors in memory the
+// device can read, which stays as it is until the stream is idle.  No synchronisation.
+hipError_t po_launch_device_table(ssx_ctx* ctx, int cls, unsigned n, const PoDev* dv);
 
 #ifndef SSX_NO_TEST_HOOKS
 struct ssx_pnp_plan_info;

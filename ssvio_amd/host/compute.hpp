@@ -63,6 +63,21 @@ class LoopCompute {
                            const double* K4, uint8_t* kept, ssx_loop_pose_result& out) = 0;
   // ssx_loop_correct with optimize(20): prob.poses / prob.points are corrected in place
   virtual void LoopCorrect(const ssx_loop_correct_problem& prob, ssx_loop_correct_result& res) = 0;
+  // Relocalisation (LoopClosing::Relocalize).  ssx_kfdb_relocalize_query: the stored keyframes a frame resembles, best first, and its
+  // feature matches against each; pairs[c] = res.cand[c].n_pairs x (frame feature, keyframe feature), ascending.  The database and
+  // its pending keyframe are only read.
+  virtual void RelocalizeQuery(const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, int max_candidates,
+                               float threshold, float ratio, ssx_reloc_query_result& res, std::vector<std::vector<int32_t>>& pairs)
+  {
+    (void)img; (void)features; (void)prm; (void)pyramid_levels; (void)max_candidates; (void)threshold; (void)ratio; (void)res; (void)pairs;
+    throw std::logic_error("LoopCompute::RelocalizeQuery: this implementation cannot relocalise");
+  }
+  // ssx_pnp_pose_batch with the reference's 100 hypotheses, 5.991 px, chi2 5.991 and Huber 1.0: one pose per job
+  virtual void PosesBatch(const double* K4, std::vector<ssx_pnp_pose_job>& jobs)
+  {
+    (void)K4; (void)jobs;
+    throw std::logic_error("LoopCompute::PosesBatch: this implementation cannot relocalise");
+  }
 };
 
 class Compute {

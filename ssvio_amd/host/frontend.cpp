@@ -5,8 +5,10 @@
 #include <cmath>
 #include <cstdio>
 #include <stdexcept>
+#include <string>
 
 #include "backend.hpp"
+#include "loopclosing.hpp"
 
 namespace ssx::host {
 namespace {
@@ -61,7 +63,9 @@ bool FrontEnd::GrabSteroImage(ImagePtr left, ImagePtr right, double timestamp)
     case FrontendStatus::INITING: SteroInit(); break;
     case FrontendStatus::TRACKING_BAD:
     case FrontendStatus::TRACKING_GOOD: Track(); break;
-    case FrontendStatus::LOST: break;                                  // the reference has no relocalisation either
+    case FrontendStatus::LOST:                                         // the reference has a TODO here (frontend.cpp:62-66)
+      if (loop_ && loop_->relocalization()) Relocalize();
+      break;
   }
   last_frame_ = current_frame_;
   return true;
@@ -80,6 +84,11 @@ bool FrontEnd::Track()
   } else {
     track_status_ = FrontendStatus::LOST;
     std::fprintf(stderr, "[frontend] frame %lu: tracking lost with %d inliers\n", current_frame_->frame_id, inliers);
+    // With relocalisation on, the map is needed again.  A pose that explains next to nothing says nothing about the map points it
+    // calls outliers (one occluded frame would otherwise condemn every point the last keyframe saw, and leave the keyframe database
+    // pointing at a map that is about to be deleted): their condemnation is taken back.  Without relocalisation the run is over here,
+    // and the map stays as the reference leaves it.
+    if (loop_ && loop_->relocalization()) map_->RetractOutlierMapPoints(condemned_);
   }
   relative_motion_ = current_frame_->relative_pose_to_kf * last_frame_->relative_pose_to_kf.inverse();
   if (track_status_ == FrontendStatus::TRACKING_BAD) {                 // new features, new map points, new keyframe
@@ -88,6 +97,44 @@ bool FrontEnd::Track()
     TriangulateNewPoints();
     InsertKeyFrame();
   }
+  return true;
+}
+
+// State LOST with Relocalization.Open: 1.  Features of the whole image as at initialisation (no mask), LoopClosing::Relocalize over the
+// keyframe database, and on success the frame is a keyframe like one of TRACKING_BAD: its pose, the matched map points on its
+// features, then new features, their right-image partners, new map points, the keyframe.  On failure the frame stays LOST and the
+// next frame tries again.
+bool FrontEnd::Relocalize()
+{
+  const Image& img = *current_frame_->left_image;
+  std::vector<ssx_keypoint> kps;
+  {
+    Stopwatch sw(times_.detect, times_.n_detect);
+    compute_.DetectBoxes(img, std::vector<int32_t>(), orb_init_, kps);
+  }
+  std::vector<ssx_keypoint> feats(kps.size());
+  for (size_t i = 0; i < kps.size(); ++i) feats[i] = ssx_keypoint{kps[i].x, kps[i].y, 7.f, -1.f, 0.f, 0, (int32_t)i};
+  const double K4[4] = {left_camera_.fx, left_camera_.fy, left_camera_.cx, left_camera_.cy};
+  LoopClosing::RelocResult r;
+  const bool ok = reference_kf_ && loop_->Relocalize(current_frame_->frame_id, img, feats, K4, r);
+  std::fprintf(stderr, "[frontend] frame %lu: relocalisation %s: %zu features, %d candidates, %d pairs, %d inliers%s\n", current_frame_->frame_id,
+               ok ? "succeeded" : "failed", feats.size(), r.candidates, r.pairs, r.inliers, ok ? (" against keyframe " + std::to_string(r.kf_id)).c_str() : "");
+  if (!ok) return false;
+  current_frame_->pose = r.T_cw;
+  current_frame_->relative_pose_to_kf = r.T_cw * reference_kf_->pose.inverse();      // reference_kf_ stays
+  for (const auto& m : r.matches) {
+    auto f = std::make_shared<Feature>();
+    f->x = feats[(size_t)m.first].x; f->y = feats[(size_t)m.first].y;
+    f->map_point = m.second;
+    current_frame_->features_left.push_back(std::move(f));
+  }
+  // the tail of Track() for a frame that needs a keyframe
+  DetectFeatures();                                                    // (its boxes mask the attached features)
+  FindFeaturesInRight();
+  TriangulateNewPoints();
+  InsertKeyFrame();
+  relative_motion_ = SE3();
+  track_status_ = FrontendStatus::TRACKING_GOOD;
   return true;
 }
 
@@ -144,6 +191,7 @@ int FrontEnd::EstimateCurrentPose()
   const int M = (int)features.size();
   std::vector<uint8_t> inlier(M, 0);
   int n_inliers = 0;
+  condemned_.clear();
   if (M > 0) {
     Stopwatch sw(times_.pose_only, times_.n_pose_only);
     n_inliers = compute_.PoseOnly(est.data(), K4, M, xyz.data(), uv.data(), inlier.data());
@@ -157,6 +205,7 @@ int FrontEnd::EstimateCurrentPose()
       if (mp && current_frame_->frame_id - reference_kf_->frame_id <= 2) {
         mp->is_outlier = true;
         map_->AddOutlierMapPoint(mp->id);
+        condemned_.push_back(mp->id);
       }
       features[i]->map_point = kNoMapPoint;
       features[i]->is_outlier = false;

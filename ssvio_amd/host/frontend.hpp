@@ -3,6 +3,7 @@
 //   FrontEnd   /root/reference/src/ssvio/frontend.cpp:34-128 (GrabSteroImage / Track), :130-182 TrackLastFrame,
 //              :184-300 EstimateCurrentPose, :302-344 DetectFeatures, :346-428 FindFeaturesInRight, :430-446 SteroInit,
 //              :448-498 BuidInitMap, :500-544 TriangulateNewPoints, :546-580 InsertKeyFrame
+//              Relocalize: what the reference leaves as a TODO in state LOST (:62-66), behind Relocalization.Open
 // Every arithmetic step of those functions is a Compute call; what is restated here is the bookkeeping between them.
 // Not carried over: the viewer hooks (Pangolin), cv::imshow debugging, image undistortion (KITTI is rectified;
 // Camera.NeedUndistortion != 0 is refused), and the mutexes -- the headless runner is single-threaded.
@@ -23,6 +24,7 @@ struct Camera {
 };
 
 class Backend;
+class LoopClosing;
 
 enum class FrontendStatus { INITING, TRACKING_GOOD, TRACKING_BAD, LOST };
 
@@ -35,6 +37,9 @@ class FrontEnd {
  public:
   FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right);
   void SetBackend(Backend* backend) { backend_ = backend; }
+  // Relocalization.Open: 1 -- a LOST front-end asks the loop closing's keyframe database where it is (Relocalize below) instead of
+  // ignoring every later frame.  Without a LoopClosing the state LOST is final, as in the reference (frontend.cpp:62-66: a TODO).
+  void SetLoopClosing(LoopClosing* loop) { loop_ = loop; }
 
   bool GrabSteroImage(ImagePtr left, ImagePtr right, double timestamp);
 
@@ -47,6 +52,7 @@ class FrontEnd {
   bool SteroInit();
   bool BuidInitMap();
   bool Track();
+  bool Relocalize();
   int TrackLastFrame();
   int EstimateCurrentPose();
   int DetectFeatures();
@@ -57,6 +63,7 @@ class FrontEnd {
   Compute& compute_;
   std::shared_ptr<Map> map_;
   Backend* backend_ = nullptr;
+  LoopClosing* loop_ = nullptr;
   Camera left_camera_, right_camera_;
   ssx_orb_params orb_, orb_init_;
   ssx_stereo_rig rig_;
@@ -70,6 +77,7 @@ class FrontEnd {
   unsigned min_init_landmark_;
   bool open_backend_optimization_;
   std::vector<int32_t> boxes_;               // DetectFeatures: the mask's rectangles (x0, y0, x1, y1)
+  std::vector<unsigned long> condemned_;     // EstimateCurrentPose: the map points this frame condemned (taken back when it ends LOST and relocalisation is on)
   StageTimes times_;
 };
 

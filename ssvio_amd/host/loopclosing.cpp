@@ -1,6 +1,7 @@
 // ssvio_amd/host/loopclosing.cpp -- see loopclosing.hpp
 #include "loopclosing.hpp"
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <map>
@@ -36,6 +37,16 @@ LoopClosing::LoopClosing(const Setting& cfg, std::unique_ptr<LoopCompute> comput
   min_id_gap_ = cfg.Has("Loop.Min.Keyframe.Gap") ? cfg.Get<int>("Loop.Min.Keyframe.Gap") : 20;
   (void)cfg.Get<int>("Loop.Show.Closing.Result");                      // the headless system has nothing to show
   if (pyramid_levels_ < 1) throw std::runtime_error("LoopClosing: Pyramid.Level must be at least 1");
+  // relocalisation (the reference has a TODO at frontend.cpp:62-66): no constant of its own but the share of the best score
+  reloc_open_ = cfg.Get<int>("Relocalization.Open") != 0;
+  reloc_candidates_ = cfg.Has("Relocalization.Candidates") ? cfg.Get<int>("Relocalization.Candidates") : 4;
+  reloc_threshold_ = cfg.Has("Relocalization.Threshold") ? cfg.Get<float>("Relocalization.Threshold") : threshold_;
+  reloc_ratio_ = cfg.Has("Relocalization.Score.Ratio") ? cfg.Get<float>("Relocalization.Score.Ratio") : 0.75f;
+  // the bar: the reference's own boundary between LOST and TRACKING_BAD (frontend.cpp:99-110) unless the settings name another
+  reloc_min_inliers_ = cfg.Has("Relocalization.Min.Inliers") ? cfg.Get<int>("Relocalization.Min.Inliers") : cfg.Get<int>("numFeatures.trackingBad");
+  if (reloc_open_ && (reloc_candidates_ < 1 || reloc_candidates_ > SSX_RELOC_MAX_CANDIDATES || !(reloc_ratio_ >= 0.f && reloc_ratio_ <= 1.f) || !(reloc_threshold_ >= 0.f)))
+    throw std::runtime_error("LoopClosing: Relocalization.Candidates must lie in [1, " + std::to_string(SSX_RELOC_MAX_CANDIDATES) +
+                             "], Relocalization.Score.Ratio in [0, 1], and Relocalization.Threshold must not be negative");
   async_ = cfg.Get<int>("Loop.Closing.Async") != 0;
   if (async_) worker_ = std::thread([this] { Worker(); });
 }
@@ -132,7 +143,10 @@ void LoopClosing::Step(const KeyFramePtr& kf)
   for (size_t i = 0; i < feats.size(); ++i) feats[i] = ssx_keypoint{kf->features_left[i]->x, kf->features_left[i]->y, 7.f, -1.f, 0.f, 0, (int32_t)i};
   ssx_kfdb_step_result step{};
   std::vector<int32_t> pairs;
-  compute_->ProcessKeyframe((int64_t)kf->key_frame_id, *img, feats, orb_, pyramid_levels_, min_db_size_, min_id_gap_, threshold_, step, pairs);
+  {
+    std::lock_guard<std::mutex> compute_lock(compute_mutex_);
+    compute_->ProcessKeyframe((int64_t)kf->key_frame_id, *img, feats, orb_, pyramid_levels_, min_db_size_, min_id_gap_, threshold_, step, pairs);
+  }
   kf->left_image.reset();                                              // its descriptors are on the device now
   img.reset();
   rec.found = step.found ? 1 : 0;
@@ -164,7 +178,10 @@ void LoopClosing::Step(const KeyFramePtr& kf)
     }
     const double K4[4] = {camera_left_.fx, camera_left_.fy, camera_left_.cx, camera_left_.cy};
     ssx_loop_pose_result pose{};
-    compute_->ComputePose((int)n, xyz.data(), has.data(), uv.data(), T_cur.data(), T_loop.data(), K4, kept.data(), pose);
+    {
+      std::lock_guard<std::mutex> compute_lock(compute_mutex_);
+      compute_->ComputePose((int)n, xyz.data(), has.data(), uv.data(), T_cur.data(), T_loop.data(), K4, kept.data(), pose);
+    }
     rec.verdict = pose.verdict; rec.with_point = pose.n_with_point; rec.inliers = pose.n_inliers;
     std::vector<int32_t> valid;                                        // set_valid_feature_matches_ after :172 and :338-344
     for (size_t i = 0; i < n; ++i)
@@ -186,6 +203,7 @@ void LoopClosing::Step(const KeyFramePtr& kf)
     }
   }
   if (!confirmed) {                                                    // :62-65
+    std::lock_guard<std::mutex> compute_lock(compute_mutex_);
     compute_->AddPending();
     ++db_size_;
   }
@@ -258,7 +276,10 @@ void LoopClosing::LoopCorrect(const KeyFramePtr& cur, const KeyFramePtr& loop, c
 
   // (b) one call; poses and points back
   ssx_loop_correct_result res{};
-  compute_->LoopCorrect(prob, res);
+  {
+    std::lock_guard<std::mutex> compute_lock(compute_mutex_);      // (behind the map mutex: the order everywhere)
+    compute_->LoopCorrect(prob, res);
+  }
   for (size_t i = 0; i < kf_rows.size(); ++i) kf_rows[i]->pose = SE3(&poses[7 * i]);
   for (size_t j = 0; j < mp_rows.size(); ++j) std::memcpy(mp_rows[j]->position, &points[3 * j], 3 * sizeof(double));
 
@@ -277,6 +298,80 @@ void LoopClosing::LoopCorrect(const KeyFramePtr& cur, const KeyFramePtr& loop, c
   rec.active_points_moved = res.n_active_points_moved;
   rec.other_points_moved = res.n_other_points_moved;
   rec.points_skipped = res.n_points_skipped;
+}
+
+// The caller (the front-end, in state LOST) holds Map::update_mutex; the compute lock is taken behind it.  One query, one gather per
+// candidate as Step's for ComputePose, one pose batch, one verdict.
+bool LoopClosing::Relocalize(unsigned long frame_id, const Image& img, const std::vector<ssx_keypoint>& features, const double* K4, RelocResult& out)
+{
+  out = RelocResult{};
+  RelocRecord rec;
+  rec.frame_id = frame_id;
+  struct Job { int rank; KeyFramePtr kf; std::vector<double> xyz, uv; std::vector<int32_t> feat; std::vector<long> mp; std::vector<uint8_t> inlier; };
+  std::vector<Job> gathered;
+  std::vector<ssx_pnp_pose_job> jobs;
+  {
+    std::lock_guard<std::mutex> compute_lock(compute_mutex_);
+    ssx_reloc_query_result q{};
+    std::vector<std::vector<int32_t>> pairs;
+    compute_->RelocalizeQuery(img, features, orb_, pyramid_levels_, reloc_candidates_, reloc_threshold_, reloc_ratio_, q, pairs);
+    rec.candidates = q.n_candidates;
+    for (int c = 0; c < q.n_candidates; ++c) {
+      rec.pairs += q.cand[c].n_pairs;
+      auto it = map_->GetAllKeyFrames().find((unsigned long)q.cand[c].kf_id);
+      if (it == map_->GetAllKeyFrames().end()) throw std::logic_error("LoopClosing: the database named keyframe " + std::to_string(q.cand[c].kf_id) + ", which the map does not hold");
+      Job j;
+      j.rank = c; j.kf = it->second;
+      const std::vector<int32_t>& pr = pairs.at((size_t)c);
+      for (size_t i = 0; i + 1 < pr.size(); i += 2) {                  // the live, not condemned map point of the keyframe's feature of every pair
+        MapPointPtr mp = map_->Lock(j.kf->features_left.at((size_t)pr[i + 1]));
+        if (!mp || mp->is_outlier) continue;
+        const ssx_keypoint& kp = features.at((size_t)pr[i]);
+        j.xyz.insert(j.xyz.end(), mp->position, mp->position + 3);
+        j.uv.push_back(kp.x); j.uv.push_back(kp.y);
+        j.feat.push_back(pr[i]); j.mp.push_back((long)mp->id);
+      }
+      if (j.feat.size() < 10) continue;                                // loopclosing.cpp:193
+      j.inlier.assign(j.feat.size(), 0);
+      gathered.push_back(std::move(j));
+    }
+    jobs.resize(gathered.size());
+    for (size_t k = 0; k < gathered.size(); ++k) {
+      Job& j = gathered[k];
+      ssx_pnp_pose_job& p = jobs[k];
+      p = ssx_pnp_pose_job{};
+      p.M = (int32_t)j.feat.size(); p.xyz = j.xyz.data(); p.uv = j.uv.data(); p.inlier_out = j.inlier.data();
+      p.seed = 0u + (uint32_t)j.rank;                                  // ComputePose's seed (0) plus the candidate's rank
+    }
+    if (!jobs.empty()) compute_->PosesBatch(K4, jobs);
+  }
+  // the most refined inliers, the lower rank on a tie (the jobs are in rank order), and MORE than the bar (tools/reloc_model.py: accept)
+  int best = -1, best_n = reloc_min_inliers_;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    if (jobs[k].found) rec.inliers = std::max(rec.inliers, (int)jobs[k].n_inliers);
+    if (jobs[k].found && jobs[k].n_inliers > best_n) { best = (int)k; best_n = jobs[k].n_inliers; }
+  }
+  rec.poses = (int)jobs.size();
+  if (best >= 0) {
+    const Job& j = gathered[(size_t)best];
+    out.ok = true;
+    out.kf_id = (long)j.kf->key_frame_id;
+    out.T_cw = SE3(jobs[(size_t)best].pose_out);
+    out.inliers = jobs[(size_t)best].n_inliers;
+    // the surviving pairs: one map point per feature and one feature per map point (a keyframe observes a map point once), first come
+    std::unordered_map<long, int> taken_mp;
+    std::unordered_map<int32_t, int> taken_feat;
+    for (size_t i = 0; i < j.feat.size(); ++i) {
+      if (!j.inlier[i] || taken_mp.count(j.mp[i]) || taken_feat.count(j.feat[i])) continue;
+      taken_mp[j.mp[i]] = 1; taken_feat[j.feat[i]] = 1;
+      out.matches.emplace_back(j.feat[i], j.mp[i]);
+    }
+    rec.accepted = out.kf_id;
+  }
+  out.candidates = rec.candidates; out.pairs = rec.pairs;
+  if (!out.ok) out.inliers = rec.inliers;
+  reloc_records_.push_back(rec);
+  return out.ok;
 }
 
 }  // namespace ssx::host

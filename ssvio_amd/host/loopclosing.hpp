@@ -17,6 +17,8 @@
 //                            whole correction, after the backend has come to rest (RequestPause; the reference polls, and polls the
 //                            inverted condition).  A failure of the thread is parked and rethrown by the next InsertNewKeyFrame / WaitIdle,
 //                            like Backend::worker_error_.
+// Relocalisation settings: Relocalization.Open (absent = 0), Relocalization.Candidates (absent = 4), Relocalization.Threshold (absent =
+// Loop.Threshold.Heigher), Relocalization.Score.Ratio (absent = 0.75), Relocalization.Min.Inliers (absent = numFeatures.trackingBad).
 // Settings: Loop.Threshold.Heigher, Loop.Closig.Keyframe.Database.Min.Size, Pyramid.Level (the reference's keys and spelling),
 // Loop.Min.Keyframe.Gap (absent = 20, the constant of :79), Loop.Closing.Async (absent = 0); Loop.Show.Closing.Result is read and ignored.
 // The extractor parameters are those of :689-698 (ORBextractor.nNewFeatures).  The 1 / 15 gates of :226 are the library's.
@@ -28,6 +30,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "compute.hpp"
@@ -71,6 +74,27 @@ class LoopClosing {
 
   // called by the backend WITH Map::update_mutex held
   void InsertNewKeyFrame(const KeyFramePtr& kf);
+
+  // Relocalisation (Relocalization.Open: 1): where is a frame that lost tracking?  One candidate query over the whole keyframe database
+  // (LoopCompute::RelocalizeQuery), per candidate the live, not condemned map point of the keyframe's feature of every pair (fewer than
+  // 10: skipped, :193), ONE pose batch over the rest (LoopCompute::PosesBatch, seed = ComputePose's + the candidate's rank).  Accepted: the
+  // most refined inliers, the lower rank on a tie, and more than Relocalization.Min.Inliers (tools/reloc_model.py).  Called by the
+  // front-end WITH Map::update_mutex held; the compute lock is taken behind it.
+  struct RelocResult {
+    bool ok = false;
+    long kf_id = -1;                   // the accepted keyframe
+    SE3 T_cw;                          // the frame's pose
+    std::vector<std::pair<int32_t, long>> matches;   // (feature of the frame, map point) of the pairs that survive the refinement: each feature and each map point once
+    int candidates = 0, pairs = 0, inliers = 0;      // of the attempt: candidates named, their pairs in all, the most refined inliers
+  };
+  struct RelocRecord {                 // one per attempt, in order (the runner's --loop_log)
+    unsigned long frame_id = 0;
+    int candidates = 0, pairs = 0, poses = 0, inliers = 0;
+    long accepted = -1;
+  };
+  bool relocalization() const { return reloc_open_; }
+  bool Relocalize(unsigned long frame_id, const Image& img, const std::vector<ssx_keypoint>& features, const double* K4, RelocResult& out);
+  const std::vector<RelocRecord>& reloc_records() const { return reloc_records_; }   // read with the front-end at rest
   void WaitIdle();                     // asynchronous mode: returns when the queue is empty and the thread idle
   bool async() const { return async_; }
   // valid after WaitIdle (asynchronous mode: the thread appends)
@@ -92,6 +116,13 @@ class LoopClosing {
   int pyramid_levels_ = 0, min_db_size_ = 0, min_id_gap_ = 20;
   float threshold_ = 0;
   int db_size_ = 0;
+  bool reloc_open_ = false;
+  int reloc_candidates_ = 4, reloc_min_inliers_ = 0;
+  float reloc_threshold_ = 0, reloc_ratio_ = 0.75f;
+  std::vector<RelocRecord> reloc_records_;
+  // compute_ is one context, used by one thread at a time: the loop step (this thread or the loop thread) and Relocalize (the
+  // front-end's thread).  Lock order everywhere: Map::update_mutex, then this; nothing waits for the map mutex while holding it.
+  std::mutex compute_mutex_;
   std::vector<Record> records_;
   Stats stats_;
 

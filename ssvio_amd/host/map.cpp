@@ -175,6 +175,14 @@ Map::LoopFusion Map::FuseLoopMapPoints(const KeyFramePtr& current, const KeyFram
   return out;
 }
 
+void Map::RetractOutlierMapPoints(const std::vector<unsigned long>& ids)
+{
+  for (unsigned long id : ids) {
+    outlier_map_points_.remove(id);
+    if (MapPointPtr mp = Lock((long)id)) mp->is_outlier = false;
+  }
+}
+
 void Map::RemoveAllOutlierMapPoints()
 {
   for (unsigned long id : outlier_map_points_) {

@@ -97,6 +97,9 @@ class Map {
   void RemoveMapPoint(const MapPointPtr& mp);
   void AddOutlierMapPoint(unsigned long id) { outlier_map_points_.push_back(id); }
   void RemoveAllOutlierMapPoints();
+  // take back AddOutlierMapPoint for these ids and clear their flag (relocalisation: a frame on which tracking was lost is no witness
+  // against the map points it failed to explain)
+  void RetractOutlierMapPoints(const std::vector<unsigned long>& ids);
 
   // The map fusion of LoopClosing::CorrectActivateKeyframeAndMappoint (loopclosing.cpp:427-453): pairs = n x (current feature index,
   // loop feature index) into the two keyframes' features_left.  Returns the ids of the current keyframe's map points that were merged

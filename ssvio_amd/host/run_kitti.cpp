@@ -18,6 +18,9 @@
 // --loop_log=FILE (with Loop.Closing.Open: 1): one line per keyframe the loop step handled (stream k of --streams writes FILE.k):
 //   kf <id> db <database size> found <0|1> loop <id|-1> score <float, 9 digits> pairs <n> pose <ssx_loop_verdict|-1> with_point <n> inliers <n>
 //   error <17 digits> need_correct <0|1> corrected <0|1> fused <n> same_point <n> pg_iters <n> moved_active <n> moved_other <n> skipped <n> duplicate <n>
+//   and, with Relocalization.Open: 1, behind them one line per attempt of a lost front-end:
+//   reloc_frame <frame id> candidates <n> pairs <n> poses <n> inliers <n> accepted <keyframe id|-1>
+// Relocalization.Open: 1 works per stream of an unbatched --streams; with --batched >= 1 it is refused.
 // Loop closing is per stream.  --batched >= 1 with Loop.Closing.Open: 1 is refused unless --loop_batched=1 is given: the streams of a cohort
 // then share one loop context and one vocabulary, and their inline keyframe steps go to the GPU as ssx_kfdb_process_keyframe_batch calls
 // (every stream still writes the bytes of its single-stream run).  The loop thread (Loop.Closing.Async: 1) is not batched: refused with it.
@@ -60,6 +63,9 @@ void WriteLoopLog(ssx::host::System& sys, const std::string& path)
                  "pg_iters %d moved_active %d moved_other %d skipped %d duplicate %d\n", r.kf_id, r.db_size, r.found, r.loop_kf_id, (double)r.score, r.pairs, r.verdict, r.with_point,
                  r.inliers, r.error, r.need_correct, r.corrected, r.fused, r.same_point_skipped, r.pg_iterations, r.active_points_moved, r.other_points_moved,
                  r.points_skipped, r.duplicate_skipped);
+  // then one line per relocalisation attempt of the front-end (Relocalization.Open: 1), in the same key / value form
+  for (const auto& r : sys.loop_closing()->reloc_records())
+    std::fprintf(f, "reloc_frame %lu candidates %d pairs %d poses %d inliers %d accepted %ld\n", r.frame_id, r.candidates, r.pairs, r.poses, r.inliers, r.accepted);
   std::fclose(f);
 }
 
@@ -111,6 +117,11 @@ int main(int argc, char** argv)
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Loop.Closing.Open") != 0 && !loop_batched) {
       std::fprintf(stderr, "--batched=%s with Loop.Closing.Open: 1 is not supported without --loop_batched=1 (the loop step batched over the streams); "
                    "or run --streams unbatched, or switch loop closing off\n", batched_s.c_str());
+      return 2;
+    }
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Open") != 0) {
+      std::fprintf(stderr, "--batched=%s with Relocalization.Open: 1 is not supported: a batched stream's loop context belongs to the dispatcher's thread; "
+                   "run --streams unbatched, or switch relocalisation off\n", batched_s.c_str());
       return 2;
     }
     if (loop_batched && Setting(config).Get<int>("Loop.Closing.Open") != 0 && Setting(config).Get<int>("Loop.Closing.Async") != 0) {

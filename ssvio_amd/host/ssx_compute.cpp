@@ -90,6 +90,30 @@ class SsxLoopCompute final : public LoopCompute {
   {
     ctx_.check(ssx_loop_correct(ctx_.get(), &prob, 20, &res));           // :533 optimize(20)
   }
+  void RelocalizeQuery(const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, int max_candidates,
+                       float threshold, float ratio, ssx_reloc_query_result& res, std::vector<std::vector<int32_t>>& pairs) override
+  {
+    const size_t K = (size_t)std::max(max_candidates, 1);
+    size_t cap = std::max<size_t>(1024, features.size() * (size_t)std::max(pyramid_levels, 1));
+    std::vector<int32_t> flat(2 * K * cap);
+    auto call = [&] {
+      return ssx_kfdb_relocalize_query(db_, voc_, img.ptr(), img.cols, img.rows, img.cols, &prm, (int32_t)features.size(), features.data(), pyramid_levels,
+                                       max_candidates, threshold, ratio, (int32_t)cap, flat.data(), &res);
+    };
+    ssx_status st = call();
+    if (st == SSX_ERR_CAPACITY) {                                        // a larger stored keyframe: the counts are known now
+      for (int c = 0; c < res.n_candidates; ++c) cap = std::max(cap, (size_t)res.cand[c].n_pairs);
+      flat.assign(2 * K * cap, 0);
+      st = call();
+    }
+    ctx_.check(st);
+    pairs.assign((size_t)res.n_candidates, {});
+    for (int c = 0; c < res.n_candidates; ++c) pairs[c].assign(flat.begin() + 2 * c * cap, flat.begin() + 2 * (c * cap + (size_t)res.cand[c].n_pairs));
+  }
+  void PosesBatch(const double* K4, std::vector<ssx_pnp_pose_job>& jobs) override
+  {
+    ctx_.check(ssx_pnp_pose_batch(ctx_.get(), K4, (int32_t)jobs.size(), jobs.data(), 100, 5.991, 5.991, 1.0));   // :205-206, :301, g2o's Huber
+  }
 
  private:
   ssx::Context ctx_;

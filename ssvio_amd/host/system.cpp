@@ -50,8 +50,13 @@ System::System(const std::string& config_file_path, std::unique_ptr<Compute> com
       loop_closing_->SetReferenceKeyFrame([fe] { return fe->reference_kf() ? (long)fe->reference_kf()->key_frame_id : -1L; });
       map_->keep_keyframe_images = true;                              // each until the loop step has processed its keyframe
       backend_->SetLoopClosing(loop_closing_.get());
+      if (loop_closing_->relocalization()) frontend_->SetLoopClosing(loop_closing_.get());
     }
   }
+  // relocalisation asks the keyframe database of loop closing: without one a lost front-end stays lost, as in the reference
+  if (setting_.Get<int>("Relocalization.Open") != 0 && !loop_closing_)
+    std::fprintf(stderr, "warning: Relocalization.Open is set, but there is no loop closing to ask (Loop.Closing.Open: 1 on a Compute that has it): "
+                 "a lost front-end stays lost\n");
 }
 
 // the two threads come to rest in the order of the data flow (frontend -> backend -> loop closing) before any member goes

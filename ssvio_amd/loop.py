@@ -36,9 +36,26 @@ class StepJob(C.Structure):
                 ("res", C.POINTER(StepResult)), ("status_out", i32_p)]
 
 
+RELOC_MAX_CANDIDATES = 8                                       # SSX_RELOC_MAX_CANDIDATES
+
+
+class RelocCandidate(C.Structure):
+    """ssx_reloc_candidate"""
+    _fields_ = [("kf_id", C.c_int64), ("score", C.c_float), ("row", C.c_int32), ("no_descriptors", C.c_int32), ("n_pairs", C.c_int32),
+                ("min_distance", C.c_int32)]
+
+
+class RelocQueryResult(C.Structure):
+    """ssx_reloc_query_result"""
+    _fields_ = [("n_pyramid", C.c_int32), ("n_bow", C.c_int32), ("n_scored", C.c_int32), ("n_candidates", C.c_int32),
+                ("cand", RelocCandidate * RELOC_MAX_CANDIDATES)]
+
+
 def _bind(lib):
     if getattr(lib, "_kfdb_bound", False):
         return
+    lib.ssx_kfdb_relocalize_query.argtypes = [C.c_void_p, C.c_void_p, u8_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32, C.c_void_p,
+                                              C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, i32_p, C.POINTER(RelocQueryResult)]
     lib.ssx_kfdb_process_keyframe_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(StepJob), C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32,
                                                     C.c_int32, C.c_int32, C.c_float, C.c_int32]
     if hasattr(lib, "ssx_kfdb_debug_last_batch"):
@@ -165,6 +182,36 @@ class KeyframeDatabase:
             raise
         return out
 
+    def relocalize_query(self, voc, image, features, prm, max_candidates=4, threshold=0.0, ratio=0.75, pyramid_levels=8, pairs_cap=None):
+        """The candidate query of relocalisation (ssx_kfdb_relocalize_query): the stored keyframes a frame that lost tracking resembles,
+        best first, and its feature matches against each, in one call.  -> dict(n_pyramid, n_bow, n_scored, candidates = list of
+        dict(kf_id, score float32, row, no_descriptors, n_pairs, min_distance, pairs [n_pairs, 2] as match_features)).  The database and
+        its pending keyframe are not touched.  SsxError with status SSX_ERR_CAPACITY carries .result (the first pairs_cap pairs of each
+        candidate in it) when pairs_cap is too small."""
+        image = np.asarray(image)
+        if image.ndim != 2 or image.dtype != np.uint8 or image.strides[1] != 1:
+            image = np.ascontiguousarray(image, dtype=np.uint8)
+        features = np.ascontiguousarray(features, dtype=KP_DTYPE)
+        if pairs_cap is None:                                     # a std::set of (current class_id, stored class_id): bounded by the stored
+            pairs_cap = max(self.size()[2], 1)                    # keyframe's descriptors
+        K = int(max_candidates)
+        pairs = np.zeros((max(K, 1), max(pairs_cap, 1), 2), np.int32)
+        r = RelocQueryResult()
+        st = self.ctx.lib.ssx_kfdb_relocalize_query(self.handle, voc.handle, ptr(image, u8_p), image.strides[0], image.shape[0], image.shape[1], C.byref(prm),
+                                                    len(features), features.ctypes.data_as(C.c_void_p), int(pyramid_levels), K, float(threshold), float(ratio),
+                                                    int(pairs_cap), ptr(pairs, i32_p), C.byref(r))
+        cands = [dict(kf_id=q.kf_id, score=np.float32(q.score), row=q.row, no_descriptors=bool(q.no_descriptors), n_pairs=q.n_pairs,
+                      min_distance=q.min_distance, pairs=pairs[c, :min(q.n_pairs, pairs_cap)].copy())
+                 for c, q in enumerate(r.cand[:max(0, min(r.n_candidates, RELOC_MAX_CANDIDATES))])]
+        out = dict(n_pyramid=r.n_pyramid, n_bow=r.n_bow, n_scored=r.n_scored, candidates=cands)
+        try:
+            self.ctx.check(st)
+        except Exception as e:
+            if st == SSX_ERR_CAPACITY:
+                e.result = out
+            raise
+        return out
+
     def add_pending(self):
         """AddToKeyframeDatabase for the keyframe of the last process_keyframe, device to device"""
         self.ctx.check(self.ctx.lib.ssx_kfdb_add_pending(self.handle))
@@ -277,6 +324,7 @@ def _bind_pose(lib):
     lib.ssx_loop_pose_opt.argtypes = [C.c_void_p, dbl_p, dbl_p, C.c_int32, dbl_p, dbl_p, C.c_double, C.c_double, u8_p, i32_p]
     lib.ssx_loop_compute_pose.argtypes = [C.c_void_p, C.c_int32, dbl_p, u8_p, dbl_p, dbl_p, dbl_p, dbl_p, C.c_int32, C.c_uint32, u8_p,
                                           C.POINTER(LoopPoseResult)]
+    lib.ssx_pnp_pose_batch.argtypes = [C.c_void_p, dbl_p, C.c_int32, C.POINTER(PnpPoseJob), C.c_int32, C.c_double, C.c_double, C.c_double]
     lib._loop_pose_bound = True
 
 
@@ -314,6 +362,39 @@ def loop_pose_opt(ctx: Context, pose, K, xyz, uv, chi2_th=5.991, huber_delta=1.0
     ctx.check(ctx.lib.ssx_loop_pose_opt(ctx.handle, ptr(pose, dbl_p), ptr(K, dbl_p), M, ptr(xyz, dbl_p), ptr(uv, dbl_p), float(chi2_th),
                                         float(huber_delta), ptr(inl, u8_p), C.byref(n)))
     return dict(pose=pose, inliers=inl[:M], n_inliers=n.value)
+
+
+PNP_BATCH_MAX = 64                                                             # SSX_PNP_BATCH_MAX
+
+
+class PnpPoseJob(C.Structure):
+    """ssx_pnp_pose_job"""
+    _fields_ = [("M", C.c_int32), ("xyz", dbl_p), ("uv", dbl_p), ("seed", C.c_uint32), ("pose_out", C.c_double * 7), ("inlier_out", u8_p),
+                ("found", C.c_int32), ("n_ransac_inliers", C.c_int32), ("best_hypothesis", C.c_int32), ("n_inliers", C.c_int32)]
+
+
+def pnp_pose_batch(ctx: Context, K, jobs, max_iters=100, reproj_px=5.991, chi2_th=5.991, huber_delta=1.0):
+    """ssx_pnp_pose_batch: per job = dict(xyz [M, 3], uv [M, 2], seed) the bits of pnp_ransac and, where it found a pose, loop_pose_opt from
+    it, all jobs in one call.  -> one dict(found, pose, inliers uint8 [M], n_inliers, n_ransac_inliers, best) per job; pose, inliers and
+    n_inliers are the refinement's (the identity, zeros and 0 where nothing was found)."""
+    _bind_pose(ctx.lib)
+    K = np.ascontiguousarray(K, dtype=np.float64)
+    if K.size != 4:
+        raise ValueError("K = (fx, fy, cx, cy)")
+    n = len(jobs)
+    table = (PnpPoseJob * max(n, 1))()
+    keep = []
+    for j, q in enumerate(jobs):
+        xyz, uv = _f64(q["xyz"], 3), _f64(q["uv"], 2)
+        if len(xyz) != len(uv):
+            raise ValueError("one pixel per point")
+        inl = np.zeros(max(len(xyz), 1), np.uint8)
+        keep.append((xyz, uv, inl))
+        table[j].M, table[j].xyz, table[j].uv, table[j].seed = len(xyz), ptr(xyz, dbl_p), ptr(uv, dbl_p), int(q.get("seed", 0)) & 0xFFFFFFFF
+        table[j].inlier_out = ptr(inl, u8_p)
+    ctx.check(ctx.lib.ssx_pnp_pose_batch(ctx.handle, ptr(K, dbl_p), n, table, int(max_iters), float(reproj_px), float(chi2_th), float(huber_delta)))
+    return [dict(found=bool(table[j].found), pose=np.array(table[j].pose_out), inliers=keep[j][2][:len(keep[j][0])], n_inliers=table[j].n_inliers,
+                 n_ransac_inliers=table[j].n_ransac_inliers, best=table[j].best_hypothesis) for j in range(n)]
 
 
 def compute_correct_pose(ctx: Context, loop_xyz, has_point, cur_uv, T_cur, T_loop, K, max_iters=100, seed=0):
