@@ -124,6 +124,9 @@ struct SsxProf {
   }
 };
 
+// what one call of the keyframe database's chain (loop.hip) issued: of a step or a query in its database, of a batch in the context
+struct KfChainStats { int32_t launches = 0, syncs = 0; int64_t bytes_up = 0, bytes_down = 0; };
+
 struct BaWorkspace;   // ba.hip
 struct OrbWorkspace;  // orb.hip
 
@@ -164,7 +167,7 @@ struct ssx_ctx {
   HostBuf po_stage;
   DevBuf pnp_arena;                          // loop closing's pose correction (pnp.hip)
   HostBuf pnp_stage;
-  struct KfBatchStats { int32_t launches = 0, syncs = 0; int64_t bytes_up = 0, bytes_down = 0; } kf_batch;   // ssx_kfdb_debug_last_batch
+  KfChainStats kf_batch;                     // the last ssx_kfdb_process_keyframe_batch (ssx_kfdb_debug_last_batch)
 
   std::mutex err_mu;                         // worker threads of a batched call may report failures concurrently
 

@@ -1,5 +1,6 @@
-// ssvio_amd/csrc/kf_batch.hpp -- the device job tables of ssx_kfdb_process_keyframe_batch (loop.hip) and the job-indexed launches it
-// borrows from orb.hip (pyramid, blur, k_describe_at), voc.hip (k_voc_words) and stereo.hip (k_bf_match).
+// ssvio_amd/csrc/kf_batch.hpp -- the jobs of the keyframe database's chain (loop.hip): a device table of them for
+// ssx_kfdb_process_keyframe_batch, one by value as a kernel argument for the single calls; and the job-indexed launches the chain borrows
+// from orb.hip (pyramid, blur, k_describe_at), voc.hip (k_voc_words) and stereo.hip (k_bf_match).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -9,8 +9,7 @@
 //           descriptors uint8[n_desc][32]
 //   table   KfRow[n]: where a keyframe's blob starts and its two counts
 //
-// Both grow geometrically with a device-to-device copy.  ssx_kfdb_add stages the blob and its row once and copies
-// them up; it launches nothing.
+// Both grow geometrically with a device-to-device copy.  ssx_kfdb_add stages the blob and its row once and copies them up; it launches nothing.
 //
 // k_kfdb_score   one wavefront per stored keyframe.  The query's (id, value) pairs are in LDS when they fit (4096
 //                words), else they are read from global memory.  A lane takes the row's entries lane + 64 k (four
@@ -21,15 +20,9 @@
 //                The winner of DetectLoop is the arg-max of the scores narrowed to float with the lowest index on a
 //                tie: floats > 0 order like their bit patterns, so it is one 64-bit atomicMax of
 //                (float bits << 32) | ~index per workgroup.
-// k_kfdb_pairs   one workgroup after k_bf_match: minimum distance, the screen dist <= max(2 min, 30), the kept pairs
-//                (current class_id, loop class_id) packed into order-preserving 64-bit keys, a bitonic sort (in LDS up
+// k_kfdb_pairs   one workgroup after k_bf_match_jobs (stereo.hip): minimum distance, the screen dist <= max(2 min, 30), the kept
+//                pairs (current class_id, loop class_id) packed into order-preserving 64-bit keys, a bitonic sort (in LDS up
 //                to 4096 keys, else in a global scratch), and the unique keys written in order = the std::set.
-//
-// The per-keyframe step of the loop-closing thread (ssx_kfdb_process_keyframe: ProcessNewKeyframe, DetectLoop, MatchFeatures of
-// loopclosing.cpp:596-634, :72-103, :105-145) chains the describe kernels of orb.hip, k_voc_words of voc.hip and the two kernels above
-// with three of its own, and leaves the keyframe in the PENDING slot: kps | descriptors | class ids | BowVector ids | values, each at
-// the capacity n_features * pyramid_levels, the two counts known to the host.  ssx_kfdb_add_pending moves it into the arena.
-//
 // k_kf_compact   one workgroup: the kept pyramid keypoints, their descriptors and class ids in push_back order (orbextractor.cpp:893)
 //                by a prefix sum over the keep flags; the count to device memory.
 // k_kf_bow       one workgroup: the BowVector of the per-feature (word, weight) exactly as voc.hip builds it on the host.  The keys
@@ -38,20 +31,31 @@
 //                lane by lane over 64-entry chunks like the chain of k_kfdb_score.  Both sums are doubles whose value depends on the order
 //                of the additions, so neither is a tree.
 // k_kfdb_commit  the pending arrays into a blob of the arena and its row into the table.
-//
-// ssx_kfdb_process_keyframe_batch is that step for one keyframe of each of n databases of one context (the streams of a batched cohort) as
-// ONE launch chain: k_*_jobs are the same kernels indexed by a device job table (kf_batch.hpp) -- a workgroup (or a grid row) per job, the
-// counts read from the job's step header -- and call the very __device__ bodies of the single-call kernels, so the ordered double chains
-// are the same code.  A job may commit its previous pending keyframe first, inside the chain.
-//
-// ssx_kfdb_relocalize_query is the query of a frame that lost tracking: the same describe / compact / words / BowVector chain
-// into scratch of its own, k_kfdb_score over EVERY stored keyframe, then
 // k_kfdb_topk    one workgroup: the K <= 8 largest keys (float bits << 32) | ~row of the scores -- per thread in registers, merged in K
 //                rounds of a block-wide maximum -- screened by the threshold and by a share of the best, and the match job of every
-//                candidate filled on the device, so that k_bf_match_jobs + k_kfdb_pairs_jobs match all K behind it without a round trip.
-// The database and its pending keyframe are only read.
+//                candidate filled on the device, so that the match kernels run for all K behind it without a round trip.
+// One entry per stage: pairs, compact, bow and commit take (jobs, one) -- a workgroup or a grid row per job of a device table (kf_batch.hpp),
+// or with jobs == null the one job as a kernel argument -- and read their counts from the job's StepHdr in device memory.  The score kernel
+// alone keeps k_kfdb_score<LDS> for one query and k_kfdb_score_jobs for a table: merged it was measurably slower (launch_score).
+//
+// The host side is ONE chain, describe (orb.hip) -> [k_kfdb_commit] -> k_kf_compact -> k_voc_words (voc.hip) -> k_kf_bow -> [k_kfdb_score]
+// (chain_reserve, chain_enqueue), a verdict (step_verdict) and a match phase k_bf_match_jobs -> k_kfdb_pairs (match_phase).  Its callers:
+//   ssx_kfdb_process_keyframe        the per-keyframe step of the loop-closing thread (ProcessNewKeyframe, DetectLoop, MatchFeatures of
+//       loopclosing.cpp:596-634, :72-103, :105-145): the chain with one job by value, the verdict, the match phase with one entry.  It leaves
+//       the keyframe in the PENDING slot: kps | descriptors | class ids | BowVector ids | values, each at the capacity n_features *
+//       pyramid_levels, the two counts known to the host.  ssx_kfdb_add_pending moves it into the arena: k_kfdb_commit, one job by value.
+//   ssx_kfdb_process_keyframe_batch  that step for one keyframe of each of n databases of one context (the streams of a batched cohort): the
+//       chain over a job table that goes up with the describe block, a job's commit of its previous pending keyframe inside it, n verdicts,
+//       the match phase with the found jobs.
+//   ssx_kfdb_relocalize_query        the query of a frame that lost tracking: the chain with one job by value into scratch of
+//       its own and over EVERY stored keyframe, k_kfdb_topk, the match kernels over the table it filled, ONE synchronisation.  The database
+//       and its pending keyframe are only read.
+//   ssx_kfdb_detect_loop / ssx_kfdb_match_features / ssx_kfdb_debug_bow   one stage on a caller's arrays: the score launch, the match
+//       launch and the words + BowVector launch of the chain, each with one job by value.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -68,13 +72,15 @@ struct KfRow {
   int32_t n_bow;    // BowVector entries
   int32_t n_desc;   // descriptors; -1: the keyframe was added without any
 };
+// The counts of one job of the chain, in device memory: k_kf_compact writes n_pyr, k_kf_bow reads it and writes n_bow (and zeroes best),
+// k_kfdb_score reads n_bow and raises best.  It is what the first synchronisation brings down, per keyframe step.
+struct StepHdr { int32_t n_pyr, n_bow; unsigned long long best; };
 
 constexpr int kQueryLds = 4096;     // query words staged in LDS (12 bytes each)
 constexpr int kSortLds = 4096;      // keys sorted in LDS (8 bytes each)
 constexpr int kPairsThreads = 1024;
 constexpr int kChunks = 4;          // 64-entry chunks of a row a wavefront has in flight
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 __host__ __device__ inline size_t blob_vals(int n_bow) { return ((size_t)n_bow * 4 + 7) & ~size_t(7); }
 __host__ __device__ inline size_t blob_class(int n_bow) { return blob_vals(n_bow) + (size_t)n_bow * 8; }
 __host__ __device__ inline size_t blob_desc(int n_bow, int n_desc) { return (blob_class(n_bow) + (size_t)n_desc * 4 + 31) & ~size_t(31); }
@@ -160,7 +166,12 @@ __device__ __forceinline__ void stage_query(double* smem, const int32_t* q_ids, 
   __syncthreads();
 }
 
-// scores[row] = L1Scoring::score(query, row) for the first n_rows keyframes; *best = max over rows of (float bits << 32) | ~row
+// (jobs, one): with jobs == null the one job of the launch is `one`, a kernel argument, and no workgroup reads a table.  The body is called
+// once with either, so that each copy reads the job from one known memory with scalar loads (behind a chosen pointer, a flat one, its fields land in VGPRs).
+template <class Body> __device__ __forceinline__ void with_job(const KfJobDev* jobs, const KfJobDev& one, unsigned i, Body&& body) { if (jobs) body(jobs[i]); else body(one); }
+
+// The score kernel alone keeps a form per caller (launch_score says why).  The single calls: scores[row] = L1Scoring::score(query, row)
+// for the first n_rows keyframes; *best = max over rows of (float bits << 32) | ~row
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_kfdb_score(const char* arena, const KfRow* rows, int n_rows, const int32_t* q_ids, const double* q_vals, int nq,
                                                     const int32_t* nq_dev, double* scores, unsigned long long* best)
@@ -172,6 +183,26 @@ __global__ __launch_bounds__(256) void k_kfdb_score(const char* arena, const KfR
     score_rows(arena, rows, n_rows, reinterpret_cast<const int32_t*>(smem + nq), smem, nq, scores, best);
   } else {
     score_rows(arena, rows, n_rows, q_ids, q_vals, nq, scores, best);
+  }
+}
+
+// grid (blocks, job): every job scores its own eligible prefix of its own database against the BowVector in its pending arrays.  The dynamic
+// LDS holds lds_cap query words (the call's largest bound, at most kQueryLds); a longer query is searched in global memory.
+__global__ __launch_bounds__(256) void k_kfdb_score_jobs(const KfJobDev* jobs, StepHdr* hdr, int lds_cap)
+{
+  extern __shared__ double smem[];
+  const KfJobDev& j = jobs[blockIdx.y];
+  const int n_rows = j.n_elig;
+  if ((int)blockIdx.x * 4 >= n_rows) return;                  // nothing eligible, or fewer rows than the largest job has
+  StepHdr* h = hdr + blockIdx.y;
+  const int nq = h->n_bow;
+  const char* arena = j.arena;
+  const KfRow* rows = static_cast<const KfRow*>(j.rows);
+  if (nq <= lds_cap) {
+    stage_query(smem, j.p_ids, j.p_vals, nq);
+    score_rows(arena, rows, n_rows, reinterpret_cast<const int32_t*>(smem + nq), smem, nq, j.scores, &h->best);
+  } else {
+    score_rows(arena, rows, n_rows, j.p_ids, j.p_vals, nq, j.scores, &h->best);
   }
 }
 
@@ -203,18 +234,15 @@ __device__ __forceinline__ int block_scan_excl(int v, int* wave_sums, int* total
   return before + inc - v;
 }
 
-// The kept pairs as keys into `keys`, sorted, the first of every run written out.  Called once with the LDS array and once with the
-// global scratch, so that after inlining each copy addresses one known memory (no flat pointer to LDS).
-__device__ __forceinline__ void sort_unique_pairs(unsigned long long* keys, int n_valid, int npad, int thr, const int* idx, const int* dist, int n_loop,
-                                                  const int32_t* loop_class, const int32_t* cur_class, int* s_fill, int* wave_sums, int32_t* hdr,
-                                                  int32_t* pairs, int min_d)
+// keys[0, n_valid) ascending by a bitonic sort of npad = 2^m >= n_valid keys, the tail padded with ~0 (it sorts last).  Its callers are
+// each called once with the LDS array and once with the global scratch, so that after inlining each copy addresses one known memory (no
+// flat pointer to LDS).
+__device__ __forceinline__ void bitonic_sort_padded(unsigned long long* keys, int n_valid, int npad)
 {
   const int tid = threadIdx.x;
-  for (int i = tid; i < n_loop; i += kPairsThreads)
-    if (dist[i] <= thr) keys[atomicAdd(s_fill, 1)] = pair_key(cur_class[idx[i]], loop_class[i]);   // any order: sorted next
   for (int i = n_valid + tid; i < npad; i += kPairsThreads) keys[i] = ~0ull;
   __syncthreads();
-  for (int k = 2; k <= npad; k <<= 1) {                       // bitonic sort of npad = 2^m keys
+  for (int k = 2; k <= npad; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int t = tid; t < (npad >> 1); t += kPairsThreads) {
         const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
@@ -224,6 +252,18 @@ __device__ __forceinline__ void sort_unique_pairs(unsigned long long* keys, int 
       __syncthreads();
     }
   }
+}
+
+// The kept pairs as keys into `keys`, sorted, the first of every run written out.  Called once with the LDS array and once with the
+// global scratch (bitonic_sort_padded).
+__device__ __forceinline__ void sort_unique_pairs(unsigned long long* keys, int n_valid, int npad, int thr, const int* idx, const int* dist, int n_loop,
+                                                  const int32_t* loop_class, const int32_t* cur_class, int* s_fill, int* wave_sums, int32_t* hdr,
+                                                  int32_t* pairs, int min_d)
+{
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n_loop; i += kPairsThreads)
+    if (dist[i] <= thr) keys[atomicAdd(s_fill, 1)] = pair_key(cur_class[idx[i]], loop_class[i]);   // any order: sorted next
+  bitonic_sort_padded(keys, n_valid, npad);
   // the first n_valid keys are the kept pairs in order (padding sorts last); a thread takes a contiguous piece and keeps the first of every run
   const int seg = (n_valid + kPairsThreads - 1) / kPairsThreads;
   const int i0 = min(tid * seg, n_valid), i1 = min(i0 + seg, n_valid);
@@ -280,15 +320,8 @@ __device__ __forceinline__ void pairs_block(const int* idx, const int* dist, int
     sort_unique_pairs(gkeys, n_valid, npad, thr, idx, dist, n_loop, loop_class, cur_class, &s_fill, wave_sums, hdr, pairs, min_d);
 }
 
-__global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const int* idx, const int* dist, int n_loop, const int32_t* loop_class, const int32_t* cur_class,
-                                                              unsigned long long* gkeys, int32_t* hdr, int32_t* pairs)
-{
-  pairs_block(idx, dist, n_loop, loop_class, cur_class, gkeys, hdr, pairs);
-}
-
-// one workgroup per found loop of a batch of keyframe steps
-// (jobs == null: the one job of the launch is `one`)
-__global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs_jobs(const KfMatchJob* jobs, KfMatchJob one)
+// one workgroup per match job, behind k_bf_match_jobs (stereo.hip) over the same jobs
+__global__ __launch_bounds__(kPairsThreads) void k_kfdb_pairs(const KfMatchJob* jobs, KfMatchJob one)
 {
   const KfMatchJob j = jobs ? jobs[blockIdx.x] : one;
   if (j.nl <= 0) return;                                      // a table filled on the device (k_kfdb_topk) has empty entries: their header stays (0, -1)
@@ -321,10 +354,13 @@ __device__ __forceinline__ void compact_block(const ssx_keypoint* kps, const uin
   if (tid == 0) *count = total;
 }
 
-__global__ __launch_bounds__(kPairsThreads) void k_kf_compact(const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep, int n, ssx_keypoint* okps,
-                                                              uint8_t* odesc, int32_t* ocls, int32_t* count)
+// one workgroup per job: the describe kernel's outputs of the job (entries kp0 .. kp0 + n_in of the concatenated arrays) into its pending
+// arrays, the count into its header
+__global__ __launch_bounds__(kPairsThreads) void k_kf_compact(const KfJobDev* jobs, KfJobDev one, const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep,
+                                                              StepHdr* hdr)
 {
-  compact_block(kps, desc, keep, n, okps, odesc, ocls, count);
+  with_job(jobs, one, blockIdx.x, [&](const KfJobDev& j) __attribute__((always_inline)) {
+    compact_block(kps + j.kp0, desc + (size_t)32 * j.kp0, keep + j.kp0, j.n_in, j.p_kps, j.p_desc, j.p_cls, &hdr[blockIdx.x].n_pyr); });
 }
 
 // The BowVector of n features from their (word, weight), as ssx_voc_transform assembles it (TemplatedVocabulary.h:1083-1124,
@@ -335,18 +371,7 @@ __device__ __forceinline__ void bow_assemble(unsigned long long* keys, int n, in
   const int tid = threadIdx.x;
   for (int f = tid; f < n; f += kPairsThreads)
     if (word[f] >= 0 && weight[f] > 0) keys[atomicAdd(s_fill, 1)] = ((unsigned long long)(unsigned)word[f] << 32) | (unsigned)f;   // any order: sorted next
-  for (int i = n_valid + tid; i < npad; i += kPairsThreads) keys[i] = ~0ull;
-  __syncthreads();
-  for (int k = 2; k <= npad; k <<= 1) {                       // bitonic sort of npad = 2^m keys; they are unique
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (npad >> 1); t += kPairsThreads) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const unsigned long long a = keys[i], b = keys[i | j];
-        if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[i | j] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort_padded(keys, n_valid, npad);                   // (these keys are unique)
   // keys [0, n_valid): ascending word, and inside a word ascending feature.  A thread takes a contiguous piece; the head of a run is an entry
   const int seg = (n_valid + kPairsThreads - 1) / kPairsThreads;
   const int i0 = min(tid * seg, n_valid), i1 = min(i0 + seg, n_valid);
@@ -407,10 +432,12 @@ __device__ __forceinline__ void bow_block(const int32_t* word, const double* wei
     bow_assemble(gkeys, n, n_valid, npad, word, weight, add, &s_fill, wave_sums, &s_norm, ids, vals, n_bow);
 }
 
-__global__ __launch_bounds__(kPairsThreads) void k_kf_bow(const int32_t* word, const double* weight, const int32_t* n_dev, int weighting, unsigned long long* gkeys,
-                                                          int32_t* ids, double* vals, int32_t* n_bow, unsigned long long* best_zero)
+// one workgroup per job: its BowVector from its slice of the concatenated words and weights, the count read from its header
+__global__ __launch_bounds__(kPairsThreads) void k_kf_bow(const KfJobDev* jobs, KfJobDev one, const int32_t* word, const double* weight, int weighting, StepHdr* hdr)
 {
-  bow_block(word, weight, n_dev, weighting, gkeys, ids, vals, n_bow, best_zero);
+  StepHdr* h = hdr + blockIdx.x;
+  with_job(jobs, one, blockIdx.x, [&](const KfJobDev& j) __attribute__((always_inline)) {
+    bow_block(word + j.kp0, weight + j.kp0, &h->n_pyr, weighting, j.bow_keys, j.p_ids, j.p_vals, &h->n_bow, &h->best); });
 }
 
 // the pending keyframe into its blob (layout at the top of the file, padding zeroed) and its row into the table
@@ -433,57 +460,13 @@ __device__ __forceinline__ void commit_blob(char* blob, const int32_t* ids, cons
   if (blockIdx.x == 0 && threadIdx.x == 0) *row_out = row;
 }
 
-__global__ __launch_bounds__(256) void k_kfdb_commit(char* blob, const int32_t* ids, const double* vals, const int32_t* cls, const uint8_t* desc, int n_bow,
-                                                     int n_desc, KfRow* row_out, KfRow row)
-{
-  commit_blob(blob, ids, vals, cls, desc, n_bow, n_desc, row_out, row);
-}
-
-// ---- the job-indexed forms of a batch of keyframe steps (ssx_kfdb_process_keyframe_batch; the job table: kf_batch.hpp) ----
-struct StepHdr { int32_t n_pyr, n_bow; unsigned long long best; };   // what the first synchronisation brings down, per keyframe step
-
 // grid (blocks, job): the jobs that commit move their previous pending keyframe into its blob, before anything overwrites it
-__global__ __launch_bounds__(256) void k_kfdb_commit_jobs(const KfJobDev* jobs)
+__global__ __launch_bounds__(256) void k_kfdb_commit(const KfJobDev* jobs, KfJobDev one)
 {
-  const KfJobDev& j = jobs[blockIdx.y];
-  if (!j.commit) return;
-  commit_blob(j.c_blob, j.c_ids, j.c_vals, j.c_cls, j.c_desc, j.c_n_bow, j.c_n_desc, static_cast<KfRow*>(j.c_row_out), KfRow{j.c_off, j.c_n_bow, j.c_n_desc});
-}
-
-// one workgroup per job: k_describe_at_jobs' outputs of the job into its pending arrays, the count into its header
-__global__ __launch_bounds__(kPairsThreads) void k_kf_compact_jobs(const KfJobDev* jobs, const ssx_keypoint* kps, const uint8_t* desc, const uint8_t* keep,
-                                                                   StepHdr* hdr)
-{
-  const KfJobDev& j = jobs[blockIdx.x];
-  compact_block(kps + j.kp0, desc + (size_t)32 * j.kp0, keep + j.kp0, j.n_in, j.p_kps, j.p_desc, j.p_cls, &hdr[blockIdx.x].n_pyr);
-}
-
-// one workgroup per job: its BowVector from its slice of the concatenated words and weights, the count read from its header
-__global__ __launch_bounds__(kPairsThreads) void k_kf_bow_jobs(const KfJobDev* jobs, const int32_t* word, const double* weight, int weighting, StepHdr* hdr)
-{
-  const KfJobDev& j = jobs[blockIdx.x];
-  StepHdr* h = hdr + blockIdx.x;
-  bow_block(word + j.kp0, weight + j.kp0, &h->n_pyr, weighting, j.bow_keys, j.p_ids, j.p_vals, &h->n_bow, &h->best);
-}
-
-// grid (blocks, job): every job scores its own eligible prefix of its own database against the BowVector in its pending arrays.  The dynamic
-// LDS holds lds_cap query words (the call's largest bound, at most kQueryLds); a longer query is searched in global memory.
-__global__ __launch_bounds__(256) void k_kfdb_score_jobs(const KfJobDev* jobs, StepHdr* hdr, int lds_cap)
-{
-  extern __shared__ double smem[];
-  const KfJobDev& j = jobs[blockIdx.y];
-  const int n_rows = j.n_elig;
-  if ((int)blockIdx.x * 4 >= n_rows) return;                  // nothing eligible, or fewer rows than the largest job has
-  StepHdr* h = hdr + blockIdx.y;
-  const int nq = h->n_bow;
-  const char* arena = j.arena;
-  const KfRow* rows = static_cast<const KfRow*>(j.rows);
-  if (nq <= lds_cap) {
-    stage_query(smem, j.p_ids, j.p_vals, nq);
-    score_rows(arena, rows, n_rows, reinterpret_cast<const int32_t*>(smem + nq), smem, nq, j.scores, &h->best);
-  } else {
-    score_rows(arena, rows, n_rows, j.p_ids, j.p_vals, nq, j.scores, &h->best);
-  }
+  with_job(jobs, one, blockIdx.y, [&](const KfJobDev& j) __attribute__((always_inline)) {
+    if (!j.commit) return;
+    commit_blob(j.c_blob, j.c_ids, j.c_vals, j.c_cls, j.c_desc, j.c_n_bow, j.c_n_desc, static_cast<KfRow*>(j.c_row_out), KfRow{j.c_off, j.c_n_bow, j.c_n_desc});
+  });
 }
 
 // ---- the candidate query of relocalisation (ssx_kfdb_relocalize_query; the rule: tools/reloc_model.py) ----
@@ -498,9 +481,10 @@ struct RelocDev {                    // what the query's one synchronisation bri
 struct RelocMatch {
   const uint8_t* cur_desc; const int32_t* cur_cls;
   int* idx; int* dist; unsigned long long* keys;   // c * max_nl, c * max_nl, c * keys_stride (keys null: every sort fits the LDS)
-  int32_t* hdr; int32_t* pairs;                    // 2 c, 2 c * max_nl
+  char* out; size_t out_stride;                    // c * out_stride: the candidate's block of the mapped pinned output (match_out)
   int max_nl; size_t keys_stride;
 };
+constexpr size_t kMatchPairsOff = 256;             // a block of the match output: (pair count, minimum distance), and the pairs this far behind
 
 // One workgroup after k_kfdb_score: the kTopK largest keys (float bits << 32) | ~row of the scores, i.e. f descending and then row
 // ascending.  A thread keeps the kTopK largest of rows tid + 1024 k in registers, sorted; kTopK rounds then take the block-wide maximum
@@ -564,7 +548,7 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const double* score
   j.cur_desc = mb.cur_desc; j.cur_cls = mb.cur_cls;
   j.idx = mb.idx + (size_t)c * mb.max_nl; j.dist = mb.dist + (size_t)c * mb.max_nl;
   j.keys = mb.keys ? mb.keys + (size_t)c * mb.keys_stride : nullptr;
-  j.hdr = mb.hdr + 2 * c; j.pairs = mb.pairs + (size_t)2 * c * mb.max_nl;
+  j.hdr = reinterpret_cast<int32_t*>(mb.out + (size_t)c * mb.out_stride); j.pairs = j.hdr + kMatchPairsOff / 4;
   j.n_cur = n_cur;
   if (ok) {
     const KfRow r = rows[row];
@@ -579,9 +563,6 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const double* score
 
 }  // namespace
 
-// what the last ssx_kfdb_process_keyframe issued (ssx_kfdb_debug_last_step)
-struct KfStepStats { int32_t launches = 0, syncs = 0; int64_t bytes_up = 0, bytes_down = 0; };
-
 struct ssx_kf_database {
   ssx_ctx* ctx = nullptr;
   std::vector<int64_t> ids;       // keyframe ids, ascending
@@ -593,7 +574,7 @@ struct ssx_kf_database {
   // the pending keyframe: arrays of capacity `cap` entries each in `pend` (pend_arrays), the counts known to the host
   DevBuf pend;
   struct Pending { bool valid = false; int64_t kf_id = 0; int cap = 0, n_pyr = 0, n_bow = 0; } pending;
-  KfStepStats last;
+  KfChainStats last;              // what the last ssx_kfdb_process_keyframe / ssx_kfdb_relocalize_query issued (ssx_kfdb_debug_last_step)
 };
 
 namespace {
@@ -624,21 +605,171 @@ hipError_t grow_keep(ssx_ctx* ctx, DevBuf& b, size_t keep, size_t need)
   return hipSuccess;
 }
 
-// k_kfdb_score over the first n_elig stored keyframes.  The query lies on the device; nq is its length, or with nq_dev its bound (the length
-// is then read there): the bound sizes the LDS stage, and above kQueryLds the query is searched in global memory.
-void launch_score(ssx_kf_database* db, int n_elig, const int32_t* q_ids, const double* q_vals, int nq, const int32_t* nq_dev, double* scores,
-                  unsigned long long* best)
+// "job 3: " in the messages of a batch, nothing in those of a single call (job < 0)
+struct JobTag { char s[24] = ""; explicit JobTag(int job) { if (job >= 0) snprintf(s, sizeof s, "job %d: ", job); } };
+
+// the global scratch of a bitonic sort of up to `bound` keys: none while they fit the LDS
+size_t sort_scratch_bytes(int bound)
 {
-  ssx_ctx* ctx = db->ctx;
-  const int blocks = std::min((n_elig + 3) / 4, 1024);   // four workgroups per CU; a wavefront takes every 4096th row
-  const char* arena = db->arena.as<char>();
-  const KfRow* rows = db->table.as<KfRow>();
-  if (nq <= kQueryLds)
-    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score<true>, dim3(blocks), dim3(256), (size_t)nq * 12, ctx->stream, arena, rows, n_elig,
-                                                     q_ids, q_vals, nq, nq_dev, scores, best));
+  size_t npad = 1;
+  while (npad < (size_t)bound) npad *= 2;
+  return bound > kSortLds ? npad * 8 : 0;
+}
+
+// ---- the commit: a keyframe into the arena and the table (AddToKeyframeDatabase) --------------------------------------------------------
+// ids ascend (the std::map of the reference is walked as a prefix, loopclosing.cpp:79) and the table has room
+ssx_status check_commit(const ssx_kf_database* db, const char* who, int job, int64_t kf_id)
+{
+  if (!db->ids.empty() && kf_id <= db->ids.back()) {
+    db->ctx->set_error("%s: keyframe id %lld after %lld (ids must ascend)", who, (long long)kf_id, (long long)db->ids.back());
+    return SSX_ERR_INVALID_ARG;
+  }
+  if (db->ids.size() >= (size_t)0x7fffffff) { db->ctx->set_error("%s: %sthe database is full", who, JobTag(job).s); return SSX_ERR_CAPACITY; }
+  return SSX_OK;
+}
+// room for one more blob and one more row; *moved = the buffers that had to move (each with a synchronisation of its own)
+hipError_t grow_for_commit(ssx_kf_database* db, size_t blob, int* moved = nullptr)
+{
+  const size_t cap_a = db->arena.cap, cap_t = db->table.cap, n = db->ids.size();
+  hipError_t e = grow_keep(db->ctx, db->arena, db->used, db->used + blob);
+  if (e == hipSuccess) e = grow_keep(db->ctx, db->table, n * sizeof(KfRow), (n + 1) * sizeof(KfRow));
+  if (moved) *moved = (db->arena.cap != cap_a ? 1 : 0) + (db->table.cap != cap_t ? 1 : 0);
+  return e;
+}
+// the host mirrors follow a commit that has happened on the device
+void commit_mirror(ssx_kf_database* db, int64_t kf_id, const KfRow& row, size_t blob)
+{
+  db->ids.push_back(kf_id); db->rows.push_back(row);
+  db->used += blob; db->n_bow += row.n_bow; db->n_desc += std::max(row.n_desc, 0);
+}
+// the commit of the pending keyframe as k_kfdb_commit reads it from a job (after grow_for_commit: the blob and the row lie where they stay)
+void commit_job(KfJobDev& t, const ssx_kf_database* db)
+{
+  const ssx_kf_database::Pending& pe = db->pending;
+  PendArrays old{};
+  pend_arrays(db->pend.as<char>(), pe.cap, old);              // (cap == 0: an empty keyframe, nothing is read)
+  t.commit = 1;
+  t.c_ids = old.ids; t.c_vals = old.vals; t.c_cls = old.cls; t.c_desc = old.desc;
+  t.c_blob = db->arena.as<char>() + db->used; t.c_row_out = db->table.as<KfRow>() + db->ids.size();
+  t.c_off = (int64_t)db->used; t.c_n_bow = pe.n_bow; t.c_n_desc = pe.n_pyr;
+}
+
+// ---- the chain: [commit] -> compact -> words -> BowVector -> [score], for n jobs --------------------------------------------------------
+// The frame arguments of a keyframe step or a query.  Two checks: every caller has one of its own between them (the contexts of its
+// handles), and their order decides the error code of a call that is wrong twice.
+struct FrameArgs {
+  const uint8_t* img; int32_t stride, rows, cols; const ssx_orb_params* prm; int32_t n_features; const ssx_keypoint* features; int32_t pyramid_levels, pairs_cap; const int32_t* pairs_out;
+};
+bool frame_args_ok(const FrameArgs& a)
+{
+  return a.prm && a.img && a.rows > 0 && a.cols > 0 && a.stride >= a.cols && a.n_features >= 0 && (a.n_features == 0 || a.features) && a.pyramid_levels >= 1 &&
+         a.pyramid_levels <= ssxorb::MAX_LEVELS && a.pairs_cap >= 0 && (a.pairs_cap == 0 || a.pairs_out);
+}
+// (k_bf_match packs a train index into 16 bits, and the pyramid keypoints of a frame are the train side of its match)
+ssx_status check_pyramid_bound(ssx_ctx* ctx, const char* who, int job, const FrameArgs& a)
+{
+  if ((int64_t)a.n_features * a.pyramid_levels <= 65535) return SSX_OK;
+  ctx->set_error("%s: %s%d features x %d levels: more than 65535 pyramid keypoints", who, JobTag(job).s, a.n_features, a.pyramid_levels);
+  return SSX_ERR_UNSUPPORTED;
+}
+
+// One enqueue of the chain.  The caller states n, the jobs (n_in, n_elig, the pending arrays, the database, a commit), the describe outputs, the bound.
+struct Chain {
+  int n = 0; KfJobDev* jobs = nullptr;  // on the host: the table that goes up with the describe block, or the one job
+  const KfJobDev* dev_jobs = nullptr;   // the table on the device; null: jobs[0] travels as a kernel argument
+  const ssx_keypoint* kps = nullptr; const uint8_t* desc = nullptr; const uint8_t* keep = nullptr;   // the describe outputs, concatenated over the jobs
+  int bound = 0;                        // the query's bound, or the largest of the table's (launch_score)
+  StepHdr* hdr = nullptr; int32_t* word = nullptr; double* weight = nullptr; int total = 0;        // chain_reserve
+};
+
+// The device scratch of the chain in `io`: [header block | words | weights | per job: the BowVector's global sort scratch, the scores],
+// then what the caller adds to the same buffer (`more`, the carve idiom).  The header block is a StepHdr per job, or a caller's larger
+// block that begins with one.  `stage` takes the headers when they come down.
+template <class More>
+hipError_t chain_reserve(DevBuf& io, HostBuf& stage, Chain& c, size_t hdr_bytes, More&& more)
+{
+  c.total = 0;
+  for (int j = 0; j < c.n; ++j) c.total += c.jobs[j].n_in;
+  auto scratch = [&](auto&& f) {
+    f(c.hdr, hdr_bytes); f(c.word, (size_t)4 * c.total); f(c.weight, (size_t)8 * c.total);
+    for (int j = 0; j < c.n; ++j) { f(c.jobs[j].bow_keys, sort_scratch_bytes(c.jobs[j].n_in)); f(c.jobs[j].scores, (size_t)c.jobs[j].n_elig * 8); }
+    more(f);
+  };
+  hipError_t e = io.reserve(carve(nullptr, scratch));
+  if (e == hipSuccess) e = stage.reserve(sizeof(StepHdr) * (size_t)c.n + 256);
+  if (e == hipSuccess) carve(io.as<char>(), scratch);
+  return e;
+}
+const auto nothing_more = [](auto&&) {};
+// the frame side and the database of a job
+void job_arrays(KfJobDev& t, const PendArrays& pa, const ssx_kf_database* db)
+{
+  t.p_kps = pa.kps; t.p_desc = pa.desc; t.p_cls = pa.cls; t.p_ids = pa.ids; t.p_vals = pa.vals;
+  t.arena = db->arena.as<char>(); t.rows = db->table.p;
+}
+
+// k_voc_words + k_kf_bow: n_pyr descriptors of every job (its p_desc) into its BowVector (p_ids, p_vals, n_bow of its header)
+void launch_words_bow(ssx_ctx* ctx, const ssx_vocabulary* voc, const KfJobDev* tab, const KfJobDev& one, int n, int total, StepHdr* hdr, int32_t* word, double* weight)
+{
+  hipStream_t s = ctx->stream;
+  if (tab)
+    SSX_PROF(ctx, KID_LOOP_WORDS, ssxvoc::launch_words_jobs(s, voc, tab, n, &hdr->n_pyr, (int)(sizeof(StepHdr) / 4), total, word, weight));
   else
-    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score<false>, dim3(blocks), dim3(256), 0, ctx->stream, arena, rows, n_elig, q_ids, q_vals,
-                                                     nq, nq_dev, scores, best));
+    SSX_PROF(ctx, KID_LOOP_WORDS, ssxvoc::launch_words(s, voc, one.p_desc, one.n_in, &hdr->n_pyr, word, weight));
+  SSX_PROF(ctx, KID_LOOP_BOW, hipLaunchKernelGGL(k_kf_bow, dim3(n), dim3(kPairsThreads), 0, s, tab, one, word, weight, voc->weighting, hdr));
+}
+
+// The scores of n jobs, the largest of max_elig stored keyframes.  The query is staged in LDS or searched in global memory, and the
+// single calls and the batch choose differently: a single call stages by its BOUND (all of it when it fits kQueryLds, else nothing: such
+// a query is searched in global memory however short it came out), the batch stages by each job's LENGTH against the call's cap
+// min(largest bound, kQueryLds).  The scores are the same bits either way, the speed is not; making the two alike is a change of
+// behaviour that wants a measurement of its own.
+// This stage alone keeps the kernel of each: one kernel with both paths behind a job took 55.3 us where k_kfdb_score<true> takes 53.0 us
+// (a step against 100 keyframes of 1000 words, MI355X), at the same occupancy and without scratch.  `bound`: the query's bound (a single
+// call; its length is read from the header when `on_device`) or the largest bound of the call (a table).
+void launch_score(ssx_ctx* ctx, const KfJobDev* tab, const KfJobDev& one, int n, int max_elig, StepHdr* hdr, int bound, bool on_device)
+{
+  const int blocks = std::min((max_elig + 3) / 4, 1024), lds_cap = std::min(bound, kQueryLds);   // four workgroups per CU; a wavefront takes every 4096th row
+  const auto single = bound <= kQueryLds ? k_kfdb_score<true> : k_kfdb_score<false>;
+  if (tab)
+    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score_jobs, dim3(blocks, n), dim3(256), (size_t)lds_cap * 12, ctx->stream, tab, hdr, lds_cap));
+  else
+    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(single, dim3(blocks), dim3(256), bound <= kQueryLds ? (size_t)bound * 12 : 0, ctx->stream, one.arena,
+                                                     static_cast<const KfRow*>(one.rows), one.n_elig, one.p_ids, one.p_vals, bound, on_device ? &hdr->n_bow : nullptr,
+                                                     one.scores, &hdr->best));
+}
+int commit_blocks(size_t blob) { return (int)std::min<size_t>(std::max<size_t>((blob / 4 + 255) / 256, 1), 1024); }
+
+// `down`: the headers of the n jobs come down behind the chain, which is the first synchronisation of a step
+hipError_t chain_enqueue(ssx_ctx* ctx, const ssx_vocabulary* voc, HostBuf& stage, const Chain& c, StepHdr* down, KfChainStats& st)
+{
+  const KfJobDev* tab = c.dev_jobs; const KfJobDev& one = c.jobs[0];
+  bool any_commit = false; size_t most = 0, bytes = sizeof(StepHdr) * (size_t)c.n;
+  int max_elig = 0;
+  for (int j = 0; j < c.n; ++j) {
+    const KfJobDev& t = c.jobs[j];
+    if (t.commit) { any_commit = true; most = std::max(most, blob_bytes(t.c_n_bow, t.c_n_desc)); }
+    max_elig = std::max(max_elig, t.n_elig);
+  }
+  if (any_commit) {
+    SSX_PROF(ctx, KID_LOOP_COMMIT, hipLaunchKernelGGL(k_kfdb_commit, dim3(commit_blocks(most), c.n), dim3(256), 0, ctx->stream, tab, one));
+    ++st.launches;
+  }
+  SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact, dim3(c.n), dim3(kPairsThreads), 0, ctx->stream, tab, one, c.kps, c.desc, c.keep, c.hdr));
+  launch_words_bow(ctx, voc, tab, one, c.n, c.total, c.hdr, c.word, c.weight);
+  st.launches += 3;
+  if (max_elig > 0) {                                         // the queries where k_kf_bow left them, their lengths read on the device
+    launch_score(ctx, tab, one, c.n, max_elig, c.hdr, c.bound, true);
+    ++st.launches;
+  }
+  hipError_t e = hipGetLastError();
+  if (!down || e != hipSuccess) return e;
+  e = hipMemcpyAsync(stage.p, c.hdr, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return e;
+  ++st.syncs; st.bytes_down += (int64_t)bytes;
+  memcpy(down, stage.p, bytes);
+  return hipSuccess;
 }
 
 // DetectLoop's verdict from the key k_kfdb_score left: no score above 0 keeps max_score 0 (loopclosing.cpp:74,85); below the threshold: none (:93)
@@ -652,40 +783,94 @@ bool winner_of(unsigned long long key, float threshold, uint32_t* row, float* sc
   *row = ~(uint32_t)key; *score = f;
   return true;
 }
-
-// the device scratch of MatchFeatures against a stored keyframe of nl descriptors
-struct MatchScratch { int* idx; int* dist; unsigned long long* keys; };
-template <class F> void match_scratch(F&& f, MatchScratch& m, int nl)
+ssx_status no_descriptors(ssx_ctx* ctx, const char* who, int job, const char* which, int64_t kf_id)
 {
-  size_t npad = 1;
-  while (npad < (size_t)nl) npad *= 2;
-  f(m.idx, (size_t)nl * 4); f(m.dist, (size_t)nl * 4); f(m.keys, nl > kSortLds ? npad * 8 : 0);
+  ctx->set_error("%s: %s%skeyframe %lld was added without descriptors", who, JobTag(job).s, which, (long long)kf_id);
+  return SSX_ERR_INVALID_ARG;
+}
+// the verdict of a keyframe step whose header came down (`scored`: k_kfdb_score ran for it) into found / score / loop_kf_id of its
+// result; *match: the winner `row` and the keyframe both have descriptors, so MatchFeatures follows (else no match exists: no pairs)
+ssx_status step_verdict(const ssx_kf_database* db, const char* who, int job, const StepHdr& h, bool scored, float threshold, ssx_kfdb_step_result* res, KfRow* row, bool* match)
+{
+  *match = false;
+  uint32_t row_i = 0; float f = 0.f;
+  if (!scored || !winner_of(h.best, threshold, &row_i, &f)) return SSX_OK;
+  res->found = 1; res->score = f; res->loop_kf_id = db->ids[row_i];
+  *row = db->rows[row_i];
+  if (row->n_desc < 0) return no_descriptors(db->ctx, who, job, "the loop ", db->ids[row_i]);
+  *match = row->n_desc > 0 && h.n_pyr > 0;
+  return SSX_OK;
 }
 
-// cv::BFMatcher::match(loop, current) + the screen and the set: query = the resident loop descriptors of `row`, train = the n_cur current ones
-// on the device; hdr (pair count, minimum distance) and the pairs go where the caller says
-hipError_t launch_match(ssx_kf_database* db, const KfRow& row, const uint8_t* cur_desc, int n_cur, const int32_t* cur_class, const MatchScratch& m, int32_t* hdr,
-                        int32_t* pairs)
+// ---- the match phase: MatchFeatures ---------------------------------------------------------------------------------------------------
+// cv::BFMatcher::match(loop, current) + the screen and the set: query = the resident descriptors of `row`, train = the n_cur current ones
+// on the device.  The job but for its scratch (match_scratch) and for where its result goes.
+KfMatchJob match_job(const ssx_kf_database* db, const KfRow& row, const uint8_t* cur_desc, const int32_t* cur_cls, int n_cur)
 {
-  ssx_ctx* ctx = db->ctx;
-  const int nl = row.n_desc;
   const char* blob = db->arena.as<char>() + row.off;
-  SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match(ctx->stream, (const uint8_t*)(blob + blob_desc(row.n_bow, nl)), nl, cur_desc, n_cur, m.idx, m.dist));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs, dim3(1), dim3(kPairsThreads), 0, ctx->stream, m.idx, m.dist, nl,
-                                                   (const int32_t*)(blob + blob_class(row.n_bow)), cur_class, m.keys, hdr, pairs));
+  KfMatchJob t{};
+  t.loop_desc = (const uint8_t*)(blob + blob_desc(row.n_bow, row.n_desc)); t.loop_cls = (const int32_t*)(blob + blob_class(row.n_bow));
+  t.cur_desc = cur_desc; t.cur_cls = cur_cls; t.nl = row.n_desc; t.n_cur = n_cur;
+  return t;
+}
+template <class F> void match_scratch(F&& f, KfMatchJob& t) { f(t.idx, (size_t)t.nl * 4); f(t.dist, (size_t)t.nl * 4); f(t.keys, sort_scratch_bytes(t.nl)); }
+// k_bf_match_jobs + k_kfdb_pairs over n jobs, the largest of max_nl stored descriptors; tab null (n == 1): the job is `one`
+hipError_t launch_match_jobs(ssx_ctx* ctx, const KfMatchJob* tab, const KfMatchJob& one, int n, int max_nl)
+{
+  SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match_jobs(ctx->stream, tab, one, n, max_nl));
+  SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs, dim3(n), dim3(kPairsThreads), 0, ctx->stream, tab, one));
   return hipGetLastError();
 }
+// A job's result in pinned memory that is mapped into the device's address space: (pair count, minimum distance), and kMatchPairsOff
+// bytes behind them the pairs, written by k_kfdb_pairs straight from the device: what crosses is the 8-byte header and 8 bytes per pair.
+size_t match_out_bytes(int nl) { return kMatchPairsOff + (size_t)nl * 8; }
+void match_out_preset(int32_t* o) { o[0] = 0; o[1] = -1; }    // what a job that no workgroup runs for reads as
+struct MatchResult { int n_pairs, min_distance; const int32_t* pairs; };
+MatchResult match_out_read(const int32_t* o) { return MatchResult{o[0], o[1], o + kMatchPairsOff / 4}; }
+int64_t match_out_crossed(const MatchResult& r) { return 8 + (int64_t)r.n_pairs * 8; }
+void copy_pairs(const MatchResult& r, int32_t cap, int32_t* pairs_out) { if (cap > 0) memcpy(pairs_out, r.pairs, (size_t)std::min(r.n_pairs, cap) * 8); }
 
-// the id-must-ascend rule of AddToKeyframeDatabase's two entry points (the std::map of the reference is walked as a prefix, :79)
-ssx_status check_next_id(ssx_kf_database* db, const char* who, int64_t kf_id)
+// One entry of the match phase: a winner's row of its database against a current side on the device; `r` holds until `stage` is used again
+struct MatchEntry {
+  const ssx_kf_database* db; KfRow row; const uint8_t* cur_desc; const int32_t* cur_cls; int n_cur; int tag;   // (tag: the caller's, its job)
+  int32_t* out = nullptr; MatchResult r{0, -1, nullptr};
+};
+
+// MatchFeatures of n entries: two launches, one synchronisation.  The scratch in `io` (its contents are dropped), table and results in `stage`.
+hipError_t match_phase(ssx_ctx* ctx, DevBuf& io, HostBuf& stage, MatchEntry* e, int n, KfChainStats& st)
 {
-  if (!db->ids.empty() && kf_id <= db->ids.back()) {
-    db->ctx->set_error("%s: keyframe id %lld after %lld (ids must ascend)", who, (long long)kf_id, (long long)db->ids.back());
-    return SSX_ERR_INVALID_ARG;
+  KfMatchJob* mt;
+  auto pinned = [&](auto&& g) { g(mt, sizeof(KfMatchJob) * (size_t)n); for (int k = 0; k < n; ++k) g(e[k].out, match_out_bytes(e[k].row.n_desc)); };
+  hipError_t err = stage.reserve(carve(nullptr, pinned));
+  if (err != hipSuccess) return err;
+  char* hp = stage.as<char>();
+  carve(hp, pinned);
+  void* dp = nullptr;
+  if ((err = hipHostGetDevicePointer(&dp, hp, 0)) != hipSuccess) return err;
+  auto on_device = [&](void* host) { return (char*)dp + ((char*)host - hp); };
+  int max_nl = 0;
+  for (int k = 0; k < n; ++k) {
+    mt[k] = match_job(e[k].db, e[k].row, e[k].cur_desc, e[k].cur_cls, e[k].n_cur);
+    match_out_preset(e[k].out);
+    mt[k].hdr = (int32_t*)on_device(e[k].out); mt[k].pairs = mt[k].hdr + kMatchPairsOff / 4;
+    max_nl = std::max(max_nl, mt[k].nl);
   }
-  return SSX_OK;
+  auto scratch = [&](auto&& g) { for (int k = 0; k < n; ++k) match_scratch(g, mt[k]); };
+  if ((err = io.reserve(carve(nullptr, scratch))) != hipSuccess) return err;
+  carve(io.as<char>(), scratch);
+  // (one entry: it travels as a kernel argument, and no workgroup reads host memory for it)
+  err = launch_match_jobs(ctx, n > 1 ? (const KfMatchJob*)on_device(mt) : nullptr, mt[0], n, max_nl);
+  if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+  if (err != hipSuccess) return err;
+  st.launches += 2; ++st.syncs;
+  for (int k = 0; k < n; ++k) { e[k].r = match_out_read(e[k].out); st.bytes_down += match_out_crossed(e[k].r); }
+  return hipSuccess;
+}
+
+void report_stats(const KfChainStats& s, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
+{
+  if (launches) *launches = s.launches; if (synchronisations) *synchronisations = s.syncs;
+  if (bytes_up) *bytes_up = s.bytes_up; if (bytes_down) *bytes_down = s.bytes_down;
 }
 
 }  // namespace
@@ -735,15 +920,13 @@ ssx_status ssx_kfdb_add(ssx_kf_database* db, int64_t kf_id, int32_t n_bow, const
 {
   if (!db || n_bow < 0 || n_desc < 0 || (n_bow > 0 && (!ids || !vals)) || (n_desc > 0 && (!desc || !class_id))) return SSX_ERR_INVALID_ARG;
   ssx_ctx* ctx = db->ctx;
-  if (ssx_status st = check_next_id(db, "ssx_kfdb_add", kf_id)) return st;
+  if (ssx_status st = check_commit(db, "ssx_kfdb_add", -1, kf_id)) return st;
   for (int32_t i = 1; i < n_bow; ++i)
     if (ids[i] <= ids[i - 1]) { ctx->set_error("ssx_kfdb_add: word ids must ascend (entry %d)", i); return SSX_ERR_INVALID_ARG; }
-  if (db->ids.size() >= (size_t)0x7fffffff) { ctx->set_error("ssx_kfdb_add: the database is full"); return SSX_ERR_CAPACITY; }
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const bool with_desc = desc != nullptr;
   const size_t bytes = blob_bytes(n_bow, n_desc), n = db->ids.size();
-  SSX_HIP_TRY(ctx, grow_keep(ctx, db->arena, db->used, db->used + bytes));
-  SSX_HIP_TRY(ctx, grow_keep(ctx, db->table, n * sizeof(KfRow), (n + 1) * sizeof(KfRow)));
+  SSX_HIP_TRY(ctx, grow_for_commit(db, bytes));
   SSX_HIP_TRY(ctx, db->stage.reserve(bytes + sizeof(KfRow)));
   char* hs = db->stage.as<char>();
   memset(hs, 0, bytes);
@@ -754,8 +937,7 @@ ssx_status ssx_kfdb_add(ssx_kf_database* db, int64_t kf_id, int32_t n_bow, const
   if (bytes) SSX_HIP_TRY(ctx, hipMemcpyAsync(db->arena.as<char>() + db->used, hs, bytes, hipMemcpyHostToDevice, ctx->stream));
   SSX_HIP_TRY(ctx, hipMemcpyAsync(db->table.as<KfRow>() + n, hs + bytes, sizeof(KfRow), hipMemcpyHostToDevice, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // the staging buffer is free again, and a failed copy is reported here
-  db->ids.push_back(kf_id); db->rows.push_back(row);
-  db->used += bytes; db->n_bow += n_bow; db->n_desc += n_desc;
+  commit_mirror(db, kf_id, row, bytes);
   return SSX_OK;
 }
 
@@ -778,8 +960,9 @@ ssx_status ssx_kfdb_detect_loop(ssx_kf_database* db, int64_t query_kf_id, int32_
     return SSX_OK;
   }
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // one block, on the device and (pinned) on the host: [values | ids | header] go up, [header | scores] come back
   Layout lay;
-  const size_t o_v = lay.take((size_t)n_bow * 8), o_i = lay.take((size_t)n_bow * 4), o_best = lay.take(8);
+  const size_t o_v = lay.take((size_t)n_bow * 8), o_i = lay.take((size_t)n_bow * 4), o_hdr = lay.take(sizeof(StepHdr));
   const size_t in_bytes = lay.off;
   const size_t o_s = lay.take((size_t)n_elig * 8);
   SSX_HIP_TRY(ctx, db->io.reserve(lay.off));
@@ -788,25 +971,28 @@ ssx_status ssx_kfdb_detect_loop(ssx_kf_database* db, int64_t query_kf_id, int32_
   char* base = db->io.as<char>();
   memcpy(hs + o_v, vals, (size_t)n_bow * 8);
   memcpy(hs + o_i, ids, (size_t)n_bow * 4);
-  memset(hs + o_best, 0, 8);
+  StepHdr hdr{0, n_bow, 0};
+  memcpy(hs + o_hdr, &hdr, sizeof(StepHdr));
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  launch_score(db, n_elig, (const int32_t*)(base + o_i), (const double*)(base + o_v), n_bow, nullptr, (double*)(base + o_s), (unsigned long long*)(base + o_best));
+  KfJobDev one{};
+  one.n_elig = n_elig; one.arena = db->arena.as<char>(); one.rows = db->table.p;
+  one.p_ids = (int32_t*)(base + o_i); one.p_vals = (double*)(base + o_v); one.scores = (double*)(base + o_s);
+  launch_score(ctx, nullptr, one, 1, n_elig, (StepHdr*)(base + o_hdr), n_bow, false);
   SSX_HIP_TRY(ctx, hipGetLastError());
-  // the winner's key and, when asked for, the scores right behind it: one copy, one synchronisation
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_best, base + o_best, scores_out ? lay.off - o_best : 8, hipMemcpyDeviceToHost, ctx->stream));
+  // the header with the winner's key and, when asked for, the scores right behind it: one copy, one synchronisation
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_hdr, base + o_hdr, scores_out ? lay.off - o_hdr : sizeof(StepHdr), hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (scores_out) memcpy(scores_out, hs + o_s, (size_t)n_elig * 8);
-  unsigned long long key = 0;
-  memcpy(&key, hs + o_best, 8);
-  uint32_t row = 0;
-  float f = 0.f;
-  if (!winner_of(key, threshold, &row, &f)) return SSX_OK;
+  memcpy(&hdr, hs + o_hdr, sizeof(StepHdr));
+  uint32_t row = 0; float f = 0.f;
+  if (!winner_of(hdr.best, threshold, &row, &f)) return SSX_OK;
   *found = 1;
   if (best_kf_id) *best_kf_id = db->ids[row];
   if (best_score) *best_score = f;
   return SSX_OK;
 }
 
+// (the current side is uploaded and the result copied back; a keyframe step matches its pending arrays where they lie: match_phase)
 ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int32_t n_cur, const uint8_t* cur_desc, const int32_t* cur_class_id,
                                    int32_t cap, int32_t* pairs_out, int32_t* n_pairs, int32_t* min_distance)
 {
@@ -817,84 +1003,50 @@ ssx_status ssx_kfdb_match_features(ssx_kf_database* db, int64_t loop_kf_id, int3
   const auto it = std::lower_bound(db->ids.begin(), db->ids.end(), loop_kf_id);
   if (it == db->ids.end() || *it != loop_kf_id) { ctx->set_error("ssx_kfdb_match_features: keyframe %lld is not in the database", (long long)loop_kf_id); return SSX_ERR_INVALID_ARG; }
   const KfRow row = db->rows[it - db->ids.begin()];
-  if (row.n_desc < 0) { ctx->set_error("ssx_kfdb_match_features: keyframe %lld was added without descriptors", (long long)loop_kf_id); return SSX_ERR_INVALID_ARG; }
+  if (row.n_desc < 0) return no_descriptors(ctx, "ssx_kfdb_match_features", -1, "", loop_kf_id);
   if (n_cur > 65535) { ctx->set_error("ssx_kfdb_match_features: more than 65535 current descriptors"); return SSX_ERR_UNSUPPORTED; }
   const int nl = row.n_desc;
   if (nl == 0 || n_cur == 0) return SSX_OK;                   // no match exists: no pairs (the reference dereferences end() here)
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int n_down = std::min(nl, cap);
-  Layout lay;
-  const size_t o_d = lay.take((size_t)n_cur * 32), o_c = lay.take((size_t)n_cur * 4);
-  const size_t in_bytes = lay.off;
-  MatchScratch m{};
-  size_t o_m[3]; int k = 0;
-  match_scratch([&](auto*&, size_t bytes) { o_m[k++] = lay.take(bytes); }, m, nl);
-  const size_t o_hdr = lay.take(8), o_pairs = lay.take((size_t)nl * 8);
-  SSX_HIP_TRY(ctx, db->io.reserve(lay.off));
-  SSX_HIP_TRY(ctx, db->stage.reserve(lay.off));
+  // one block, on the device and (pinned) on the host: [descriptors | class ids] go up, [header | pairs] come back
+  uint8_t* d_desc; int32_t* d_cls; int32_t* d_out;
+  KfMatchJob t = match_job(db, row, nullptr, nullptr, n_cur);
+  auto bufs = [&](auto&& f) { f(d_desc, (size_t)n_cur * 32); f(d_cls, (size_t)n_cur * 4); match_scratch(f, t); f(d_out, match_out_bytes(nl)); };
+  const size_t total = carve(nullptr, bufs);
+  SSX_HIP_TRY(ctx, db->io.reserve(total));
+  SSX_HIP_TRY(ctx, db->stage.reserve(total));
   char* hs = db->stage.as<char>();
   char* base = db->io.as<char>();
-  k = 0;
-  match_scratch([&](auto*& ptr, size_t) { wire(ptr, base, o_m[k++]); }, m, nl);
-  memcpy(hs + o_d, cur_desc, (size_t)n_cur * 32);
-  memcpy(hs + o_c, cur_class_id, (size_t)n_cur * 4);
+  carve(base, bufs);
+  const size_t in_bytes = (size_t)((char*)t.idx - base), o_cls = (size_t)((char*)d_cls - base), o_out = (size_t)((char*)d_out - base);
+  t.cur_desc = d_desc; t.cur_cls = d_cls; t.hdr = d_out; t.pairs = d_out + kMatchPairsOff / 4;
+  memcpy(hs, cur_desc, (size_t)n_cur * 32);
+  memcpy(hs + o_cls, cur_class_id, (size_t)n_cur * 4);
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  SSX_HIP_TRY(ctx, launch_match(db, row, (const uint8_t*)(base + o_d), n_cur, (const int32_t*)(base + o_c), m, (int32_t*)(base + o_hdr), (int32_t*)(base + o_pairs)));
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_hdr, base + o_hdr, (o_pairs - o_hdr) + (size_t)n_down * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, launch_match_jobs(ctx, nullptr, t, 1, nl));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_out, d_out, kMatchPairsOff + (size_t)std::min(nl, cap) * 8, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  int32_t hdr[2];
-  memcpy(hdr, hs + o_hdr, 8);
-  *n_pairs = hdr[0];
-  if (min_distance) *min_distance = hdr[1];
-  if (cap > 0) memcpy(pairs_out, hs + o_pairs, (size_t)std::min(hdr[0], cap) * 8);
-  if (hdr[0] > cap) { ctx->set_error("ssx_kfdb_match_features: %d pairs but capacity %d", hdr[0], cap); return SSX_ERR_CAPACITY; }
+  const MatchResult r = match_out_read((const int32_t*)(hs + o_out));
+  *n_pairs = r.n_pairs;
+  if (min_distance) *min_distance = r.min_distance;
+  copy_pairs(r, cap, pairs_out);
+  if (r.n_pairs > cap) { ctx->set_error("ssx_kfdb_match_features: %d pairs but capacity %d", r.n_pairs, cap); return SSX_ERR_CAPACITY; }
   return SSX_OK;
 }
-
-}  // extern "C"
-
-// ---- the per-keyframe step ----------------------------------------------------------------------------------------------------------
-namespace {
-
-// steps 3-4 on descriptors that lie on the device: words, then the BowVector; scratch for `bound` features
-struct BowScratch { int32_t* word; double* weight; unsigned long long* keys; };
-template <class F> void bow_scratch(F&& f, BowScratch& b, int bound)
-{
-  size_t npad = 1;
-  while (npad < (size_t)bound) npad *= 2;
-  f(b.word, (size_t)bound * 4); f(b.weight, (size_t)bound * 8); f(b.keys, bound > kSortLds ? npad * 8 : 0);
-}
-hipError_t launch_bow(ssx_ctx* ctx, const ssx_vocabulary* voc, const uint8_t* desc, int bound, const int32_t* n_dev, const BowScratch& b, int32_t* ids,
-                      double* vals, int32_t* n_bow, unsigned long long* best_zero)
-{
-  SSX_PROF(ctx, KID_LOOP_WORDS, ssxvoc::launch_words(ctx->stream, voc, desc, bound, n_dev, b.word, b.weight));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  SSX_PROF(ctx, KID_LOOP_BOW, hipLaunchKernelGGL(k_kf_bow, dim3(1), dim3(kPairsThreads), 0, ctx->stream, b.word, b.weight, n_dev, voc->weighting, b.keys, ids, vals,
-                                                 n_bow, best_zero));
-  return hipGetLastError();
-}
-
-}  // namespace
-
-extern "C" {
 
 ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary* voc, int64_t kf_id, const uint8_t* img, int32_t stride, int32_t rows, int32_t cols,
                                      const ssx_orb_params* prm, int32_t n_features, const ssx_keypoint* features, int32_t pyramid_levels, int32_t min_db_size,
                                      int32_t min_id_gap, float threshold, int32_t pairs_cap, int32_t* pairs_out, ssx_kfdb_step_result* res)
 {
+  static const char* const who = "ssx_kfdb_process_keyframe";
   if (!db) return SSX_ERR_INVALID_ARG;
   db->pending.valid = false;                                  // a call that fails leaves nothing pending
-  db->last = KfStepStats{};
-  if (!voc || !res || !prm || !img || rows <= 0 || cols <= 0 || stride < cols || n_features < 0 || (n_features > 0 && !features) || pyramid_levels < 1 ||
-      pyramid_levels > ssxorb::MAX_LEVELS || pairs_cap < 0 || (pairs_cap > 0 && !pairs_out))
-    return SSX_ERR_INVALID_ARG;
+  db->last = KfChainStats{};
+  const FrameArgs fa{img, stride, rows, cols, prm, n_features, features, pyramid_levels, pairs_cap, pairs_out};
+  if (!voc || !res || !frame_args_ok(fa)) return SSX_ERR_INVALID_ARG;
   ssx_ctx* ctx = db->ctx;
-  if (voc->ctx != ctx) { ctx->set_error("ssx_kfdb_process_keyframe: the vocabulary belongs to another context"); return SSX_ERR_INVALID_ARG; }
-  if ((int64_t)n_features * pyramid_levels > 65535) {
-    ctx->set_error("ssx_kfdb_process_keyframe: %d features x %d levels: more than 65535 pyramid keypoints", n_features, pyramid_levels);
-    return SSX_ERR_UNSUPPORTED;
-  }
+  if (voc->ctx != ctx) { ctx->set_error("%s: the vocabulary belongs to another context", who); return SSX_ERR_INVALID_ARG; }
+  if (ssx_status s = check_pyramid_bound(ctx, who, -1, fa)) return s;
   *res = ssx_kfdb_step_result{};
   res->min_distance = -1;
   const int N = n_features * pyramid_levels;
@@ -903,76 +1055,34 @@ ssx_status ssx_kfdb_process_keyframe(ssx_kf_database* db, ssx_vocabulary* voc, i
   const int n_elig = detect ? (int)(std::upper_bound(db->ids.begin(), db->ids.end(), kf_id - (int64_t)min_id_gap) - db->ids.begin()) : 0;
   res->detect_ran = detect ? 1 : 0;
   res->n_scored = n_elig;
-  KfStepStats st{};
-  StepHdr hdr{0, 0, 0};
-  PendArrays pa{};
+  KfChainStats st{}; StepHdr hdr{0, 0, 0}; PendArrays pa{};
   if (N > 0) {
     SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
     ssxorb::Described d;
-    ssx_status s = ssxorb::describe_enqueue(ctx, img, stride, rows, cols, *prm, features, n_features, pyramid_levels, &d);
-    if (s != SSX_OK) return s;
+    if (ssx_status s = ssxorb::describe_enqueue(ctx, img, stride, rows, cols, *prm, features, n_features, pyramid_levels, &d)) return s;
     st.launches += d.launches; st.syncs += d.syncs; st.bytes_up += (int64_t)d.bytes_up;
     SSX_HIP_TRY(ctx, db->pend.reserve(pend_arrays(nullptr, N, pa)));
     pend_arrays(db->pend.as<char>(), N, pa);
-    StepHdr* dh;
-    BowScratch b{};
-    double* scores;
-    auto scratch = [&](auto&& f) { f(dh, sizeof(StepHdr)); bow_scratch(f, b, N); f(scores, (size_t)n_elig * 8); };
-    SSX_HIP_TRY(ctx, db->io.reserve(carve(nullptr, scratch)));
-    SSX_HIP_TRY(ctx, db->stage.reserve(256));
-    carve(db->io.as<char>(), scratch);
-    SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact, dim3(1), dim3(kPairsThreads), 0, ctx->stream, d.kps, d.desc, d.keep, N, pa.kps, pa.desc, pa.cls,
-                                                       &dh->n_pyr));
-    SSX_HIP_TRY(ctx, hipGetLastError());
-    SSX_HIP_TRY(ctx, launch_bow(ctx, voc, pa.desc, N, &dh->n_pyr, b, pa.ids, pa.vals, &dh->n_bow, &dh->best));
-    st.launches += 3;
-    if (n_elig > 0) {                                         // the query where k_kf_bow left it, its length read on the device
-      launch_score(db, n_elig, pa.ids, pa.vals, N, &dh->n_bow, scores, &dh->best);
-      SSX_HIP_TRY(ctx, hipGetLastError());
-      ++st.launches;
-    }
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(db->stage.p, dh, sizeof(StepHdr), hipMemcpyDeviceToHost, ctx->stream));
-    SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ++st.syncs; st.bytes_down += (int64_t)sizeof(StepHdr);
-    memcpy(&hdr, db->stage.p, sizeof(StepHdr));
+    KfJobDev one{}; one.n_in = N; one.n_elig = n_elig;
+    job_arrays(one, pa, db);
+    Chain c; c.n = 1; c.jobs = &one; c.kps = d.kps; c.desc = d.desc; c.keep = d.keep; c.bound = N;
+    SSX_HIP_TRY(ctx, chain_reserve(db->io, db->stage, c, sizeof(StepHdr), nothing_more));
+    SSX_HIP_TRY(ctx, chain_enqueue(ctx, voc, db->stage, c, &hdr, st));
   }
   res->n_pyramid = hdr.n_pyr; res->n_bow = hdr.n_bow;
-  uint32_t row_i = 0;
-  float f = 0.f;
-  int n_pairs = 0;
-  if (n_elig > 0 && winner_of(hdr.best, threshold, &row_i, &f)) {
-    res->found = 1; res->score = f; res->loop_kf_id = db->ids[row_i];
-    const KfRow row = db->rows[row_i];
-    if (row.n_desc < 0) {
-      ctx->set_error("ssx_kfdb_process_keyframe: the loop keyframe %lld was added without descriptors", (long long)db->ids[row_i]);
-      return SSX_ERR_INVALID_ARG;
-    }
-    const int nl = row.n_desc;
-    if (nl > 0 && hdr.n_pyr > 0) {                            // else no match exists: no pairs
-      // MatchFeatures: the pending descriptors and class ids are the current side.  The pair count and the pairs are written straight into
-      // the pinned block (mapped into the device's address space): what crosses is the 8-byte header and 8 bytes per pair
-      MatchScratch m{};
-      SSX_HIP_TRY(ctx, db->io.reserve(carve(nullptr, [&](auto&& g) { match_scratch(g, m, nl); })));
-      carve(db->io.as<char>(), [&](auto&& g) { match_scratch(g, m, nl); });
-      SSX_HIP_TRY(ctx, db->stage.reserve(256 + (size_t)nl * 8));
-      int32_t* hm = db->stage.as<int32_t>();
-      hm[0] = 0; hm[1] = -1;
-      void* dm = nullptr;
-      SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dm, hm, 0));
-      SSX_HIP_TRY(ctx, launch_match(db, row, pa.desc, hdr.n_pyr, pa.cls, m, (int32_t*)dm, (int32_t*)((char*)dm + 256)));
-      SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      st.launches += 2; ++st.syncs;
-      n_pairs = hm[0];
-      res->min_distance = hm[1];
-      st.bytes_down += 8 + (int64_t)n_pairs * 8;
-      if (pairs_cap > 0) memcpy(pairs_out, (const char*)hm + 256, (size_t)std::min(n_pairs, pairs_cap) * 8);
-    }
+  MatchEntry m{db, KfRow{}, pa.desc, pa.cls, hdr.n_pyr, 0};
+  bool match = false;
+  if (ssx_status s = step_verdict(db, who, -1, hdr, n_elig > 0, threshold, res, &m.row, &match)) return s;
+  if (match) {                                                // MatchFeatures: the pending descriptors and class ids are the current side
+    SSX_HIP_TRY(ctx, match_phase(ctx, db->io, db->stage, &m, 1, st));
+    res->min_distance = m.r.min_distance;
+    copy_pairs(m.r, pairs_cap, pairs_out);
   }
-  res->n_pairs = n_pairs;
+  const int n_pairs = res->n_pairs = m.r.n_pairs;
   // every synchronisation has succeeded: the keyframe is pending
   db->pending.valid = true; db->pending.kf_id = kf_id; db->pending.cap = N; db->pending.n_pyr = hdr.n_pyr; db->pending.n_bow = hdr.n_bow;
   db->last = st;
-  if (n_pairs > pairs_cap) { ctx->set_error("ssx_kfdb_process_keyframe: %d pairs but capacity %d", n_pairs, pairs_cap); return SSX_ERR_CAPACITY; }
+  if (n_pairs > pairs_cap) { ctx->set_error("%s: %d pairs but capacity %d", who, n_pairs, pairs_cap); return SSX_ERR_CAPACITY; }
   return SSX_OK;
 }
 
@@ -982,22 +1092,16 @@ ssx_status ssx_kfdb_add_pending(ssx_kf_database* db)
   ssx_ctx* ctx = db->ctx;
   if (!db->pending.valid) { ctx->set_error("ssx_kfdb_add_pending: no keyframe is pending"); return SSX_ERR_INVALID_ARG; }
   const ssx_kf_database::Pending pe = db->pending;
-  if (ssx_status st = check_next_id(db, "ssx_kfdb_add_pending", pe.kf_id)) return st;
-  if (db->ids.size() >= (size_t)0x7fffffff) { ctx->set_error("ssx_kfdb_add_pending: the database is full"); return SSX_ERR_CAPACITY; }
+  if (ssx_status st = check_commit(db, "ssx_kfdb_add_pending", -1, pe.kf_id)) return st;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = blob_bytes(pe.n_bow, pe.n_pyr), n = db->ids.size();
-  SSX_HIP_TRY(ctx, grow_keep(ctx, db->arena, db->used, db->used + bytes));
-  SSX_HIP_TRY(ctx, grow_keep(ctx, db->table, n * sizeof(KfRow), (n + 1) * sizeof(KfRow)));
-  PendArrays pa{};
-  pend_arrays(db->pend.as<char>(), pe.cap, pa);              // (cap == 0: an empty keyframe, nothing is read)
-  const KfRow row{(int64_t)db->used, pe.n_bow, pe.n_pyr};
-  const int blocks = (int)std::min<size_t>(std::max<size_t>((bytes / 4 + 255) / 256, 1), 1024);
-  SSX_PROF(ctx, KID_LOOP_COMMIT, hipLaunchKernelGGL(k_kfdb_commit, dim3(blocks), dim3(256), 0, ctx->stream, db->arena.as<char>() + db->used, pa.ids, pa.vals, pa.cls,
-                                                    pa.desc, pe.n_bow, pe.n_pyr, db->table.as<KfRow>() + n, row));
+  const size_t bytes = blob_bytes(pe.n_bow, pe.n_pyr);
+  SSX_HIP_TRY(ctx, grow_for_commit(db, bytes));
+  KfJobDev one{};
+  commit_job(one, db);
+  SSX_PROF(ctx, KID_LOOP_COMMIT, hipLaunchKernelGGL(k_kfdb_commit, dim3(commit_blocks(bytes), 1), dim3(256), 0, ctx->stream, (const KfJobDev*)nullptr, one));
   SSX_HIP_TRY(ctx, hipGetLastError());
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  db->ids.push_back(pe.kf_id); db->rows.push_back(row);
-  db->used += bytes; db->n_bow += pe.n_bow; db->n_desc += pe.n_pyr;
+  commit_mirror(db, pe.kf_id, KfRow{one.c_off, pe.n_bow, pe.n_pyr}, bytes);
   db->pending.valid = false;                                  // a keyframe is committed once
   return SSX_OK;
 }
@@ -1034,25 +1138,23 @@ ssx_status ssx_kfdb_pending(ssx_kf_database* db, int64_t* kf_id, int32_t kps_cap
   return SSX_OK;
 }
 
-// The candidate query of relocalisation: describe -> k_kf_compact -> k_voc_words -> k_kf_bow -> k_kfdb_score (every stored keyframe) ->
-// k_kfdb_topk (the candidates and their match jobs, on the device) -> k_bf_match_jobs + k_kfdb_pairs_jobs with grid.y = max_candidates,
-// then ONE synchronisation.  The match grid and the scratch are sized by the host mirror's largest n_desc, so nothing has to come down
-// before the match is enqueued; a job without a candidate exits.  The frame's compacted arrays live in db->io, never in db->pend.
+// The candidate query of relocalisation: the chain with n = 1 over EVERY stored keyframe -> k_kfdb_topk (the candidates and their match
+// jobs, on the device) -> k_bf_match_jobs + k_kfdb_pairs with one job per candidate slot, then ONE synchronisation.  The match grid and
+// the scratch are sized by the host mirror's largest n_desc, so nothing has to come down before the match is enqueued; a job without a
+// candidate exits.  The frame's compacted arrays live in db->io, never in db->pend.
 ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, const uint8_t* img, int32_t stride, int32_t rows, int32_t cols,
                                      const ssx_orb_params* prm, int32_t n_features, const ssx_keypoint* features, int32_t pyramid_levels, int32_t max_candidates,
                                      float threshold, float ratio, int32_t pairs_cap, int32_t* pairs_out, ssx_reloc_query_result* res)
 {
-  if (!db || !voc || !res || !prm || !img || rows <= 0 || cols <= 0 || stride < cols || n_features < 0 || (n_features > 0 && !features) || pyramid_levels < 1 ||
-      pyramid_levels > ssxorb::MAX_LEVELS || pairs_cap < 0 || (pairs_cap > 0 && !pairs_out) || max_candidates < 1 || max_candidates > kTopK ||
-      !std::isfinite(ratio) || ratio < 0.f || ratio > 1.f || !(threshold >= 0.f))
+  static const char* const who = "ssx_kfdb_relocalize_query";
+  const FrameArgs fa{img, stride, rows, cols, prm, n_features, features, pyramid_levels, pairs_cap, pairs_out};
+  if (!db || !voc || !res || !frame_args_ok(fa) || max_candidates < 1 || max_candidates > kTopK || !std::isfinite(ratio) || ratio < 0.f || ratio > 1.f ||
+      !(threshold >= 0.f))
     return SSX_ERR_INVALID_ARG;
   ssx_ctx* ctx = db->ctx;
-  if (voc->ctx != ctx) { ctx->set_error("ssx_kfdb_relocalize_query: the vocabulary belongs to another context"); return SSX_ERR_INVALID_ARG; }
-  if ((int64_t)n_features * pyramid_levels > 65535) {
-    ctx->set_error("ssx_kfdb_relocalize_query: %d features x %d levels: more than 65535 pyramid keypoints", n_features, pyramid_levels);
-    return SSX_ERR_UNSUPPORTED;
-  }
-  db->last = KfStepStats{};
+  if (voc->ctx != ctx) { ctx->set_error("%s: the vocabulary belongs to another context", who); return SSX_ERR_INVALID_ARG; }
+  if (ssx_status s = check_pyramid_bound(ctx, who, -1, fa)) return s;
+  db->last = KfChainStats{};
   *res = ssx_reloc_query_result{};
   for (int c = 0; c < kTopK; ++c) { res->cand[c].kf_id = -1; res->cand[c].row = -1; res->cand[c].min_distance = -1; }
   const int N = n_features * pyramid_levels, K = max_candidates, n_db = (int)db->ids.size();
@@ -1061,53 +1163,44 @@ ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, c
   int max_nl = 0;
   for (const KfRow& r : db->rows) max_nl = std::max(max_nl, r.n_desc);
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  KfStepStats st{};
+  KfChainStats st{};
   ssxorb::Described d;
   if (ssx_status s = ssxorb::describe_enqueue(ctx, img, stride, rows, cols, *prm, features, n_features, pyramid_levels, &d)) return s;
   st.launches += d.launches; st.syncs += d.syncs; st.bytes_up += (int64_t)d.bytes_up;
-  // the device scratch: the frame's compacted arrays (PendArrays' layout, in a buffer of the query's own), the result block, the BowVector's
-  // scratch, the scores, the match table and every job's match scratch
-  size_t keys_stride = 1;
-  while (keys_stride < (size_t)max_nl) keys_stride *= 2;
-  if (max_nl <= kSortLds) keys_stride = 0;
-  PendArrays pa{};
-  RelocDev* dh; BowScratch b{}; double* scores; KfMatchJob* jobs; RelocMatch mb{};
-  char* frame;
-  auto scratch = [&](auto&& f) {
-    f(frame, pend_arrays(nullptr, N, pa)); f(dh, sizeof(RelocDev)); bow_scratch(f, b, N); f(scores, (size_t)n_db * 8); f(jobs, sizeof(KfMatchJob) * (size_t)K);
+  // the device scratch: the chain's with the result block as its header, then the frame's compacted arrays, the match table and its jobs' scratch
+  static_assert(offsetof(RelocDev, h) == 0, "the chain's kernels take the result block for a step header");
+  const size_t keys_stride = sort_scratch_bytes(max_nl) / 8;
+  PendArrays pa{}; KfMatchJob* jobs; RelocMatch mb{}; char* frame;
+  KfJobDev one{}; one.n_in = N; one.n_elig = n_db;
+  Chain c; c.n = 1; c.jobs = &one; c.kps = d.kps; c.desc = d.desc; c.keep = d.keep; c.bound = N;
+  SSX_HIP_TRY(ctx, chain_reserve(db->io, db->stage, c, sizeof(RelocDev), [&](auto&& f) {
+    f(frame, pend_arrays(nullptr, N, pa)); f(jobs, sizeof(KfMatchJob) * (size_t)K);
     f(mb.idx, (size_t)4 * K * max_nl); f(mb.dist, (size_t)4 * K * max_nl); f(mb.keys, (size_t)8 * K * keys_stride);
-  };
-  SSX_HIP_TRY(ctx, db->io.reserve(carve(nullptr, scratch)));
-  carve(db->io.as<char>(), scratch);
-  pend_arrays(frame, N, pa);
-  // the mapped pinned block: [the result block's copy | (pair count, minimum distance) per job | max_nl pairs per job]
-  RelocDev* hh; int32_t* hm; int32_t* hp;
-  auto pinned = [&](auto&& f) { f(hh, sizeof(RelocDev)); f(hm, (size_t)8 * kTopK); f(hp, (size_t)8 * K * max_nl); };
+  }));
+  RelocDev* dh = reinterpret_cast<RelocDev*>(c.hdr);
+  pend_arrays(frame, N, pa); job_arrays(one, pa, db);
+  // the mapped pinned block: [the result block's copy | a match result per candidate slot, each for max_nl pairs]
+  const size_t out_stride = (match_out_bytes(max_nl) + 255) & ~size_t(255);
+  RelocDev* hh; char* ho;
+  auto pinned = [&](auto&& f) { f(hh, sizeof(RelocDev)); f(ho, out_stride * (size_t)K); };
   SSX_HIP_TRY(ctx, db->stage.reserve(carve(nullptr, pinned)));
   char* hs = db->stage.as<char>();
   carve(hs, pinned);
-  for (int c = 0; c < kTopK; ++c) { hm[2 * c] = 0; hm[2 * c + 1] = -1; }
+  for (int k = 0; k < K; ++k) match_out_preset((int32_t*)(ho + out_stride * (size_t)k));
   void* dp = nullptr;
   SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dp, hs, 0));
   mb.cur_desc = pa.desc; mb.cur_cls = pa.cls; mb.max_nl = max_nl; mb.keys_stride = keys_stride;
   if (keys_stride == 0) mb.keys = nullptr;
-  mb.hdr = (int32_t*)((char*)dp + ((char*)hm - hs)); mb.pairs = (int32_t*)((char*)dp + ((char*)hp - hs));
+  mb.out = (char*)dp + (ho - hs); mb.out_stride = out_stride;
   hipStream_t s = ctx->stream;
-  SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact, dim3(1), dim3(kPairsThreads), 0, s, d.kps, d.desc, d.keep, N, pa.kps, pa.desc, pa.cls, &dh->h.n_pyr));
-  SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, launch_bow(ctx, voc, pa.desc, N, &dh->h.n_pyr, b, pa.ids, pa.vals, &dh->h.n_bow, &dh->h.best));
-  st.launches += 3;
+  SSX_HIP_TRY(ctx, chain_enqueue(ctx, voc, db->stage, c, nullptr, st));
   if (n_db > 0) {
-    launch_score(db, n_db, pa.ids, pa.vals, N, &dh->h.n_bow, scores, &dh->h.best);
-    SSX_HIP_TRY(ctx, hipGetLastError());
-    SSX_PROF(ctx, KID_LOOP_TOPK, hipLaunchKernelGGL(k_kfdb_topk, dim3(1), dim3(kPairsThreads), 0, s, scores, n_db, db->arena.as<char>(), db->table.as<KfRow>(), K,
+    SSX_PROF(ctx, KID_LOOP_TOPK, hipLaunchKernelGGL(k_kfdb_topk, dim3(1), dim3(kPairsThreads), 0, s, one.scores, n_db, db->arena.as<char>(), db->table.as<KfRow>(), K,
                                                     threshold, ratio, dh, jobs, mb));
     SSX_HIP_TRY(ctx, hipGetLastError());
-    st.launches += 2;
+    ++st.launches;
     if (max_nl > 0) {                                         // (else no stored keyframe has a descriptor: nothing can match)
-      SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match_jobs(s, jobs, KfMatchJob{}, K, max_nl));
-      SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs_jobs, dim3(K), dim3(kPairsThreads), 0, s, jobs, KfMatchJob{}));
-      SSX_HIP_TRY(ctx, hipGetLastError());
+      SSX_HIP_TRY(ctx, launch_match_jobs(ctx, jobs, KfMatchJob{}, K, max_nl));
       st.launches += 2;
     }
   }
@@ -1119,32 +1212,33 @@ ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, c
   const int n_cand = n_db > 0 ? std::min(std::max(hh->n_cand, 0), K) : 0;
   res->n_candidates = n_cand;
   int over = -1;
-  for (int c = 0; c < n_cand; ++c) {
-    ssx_reloc_candidate& q = res->cand[c];
-    const int row = hh->row[c];
-    if (row < 0 || row >= n_db) { ctx->set_error("ssx_kfdb_relocalize_query: candidate %d names row %d of %d", c, row, n_db); return SSX_ERR_HIP; }
+  for (int k = 0; k < n_cand; ++k) {
+    ssx_reloc_candidate& q = res->cand[k];
+    const int row = hh->row[k];
+    if (row < 0 || row >= n_db) { ctx->set_error("%s: candidate %d names row %d of %d", who, k, row, n_db); return SSX_ERR_HIP; }
     q.row = row; q.kf_id = db->ids[row];
-    memcpy(&q.score, &hh->fbits[c], 4);
+    memcpy(&q.score, &hh->fbits[k], 4);
     q.no_descriptors = db->rows[row].n_desc < 0 ? 1 : 0;
-    q.n_pairs = hm[2 * c]; q.min_distance = hm[2 * c + 1];
-    st.bytes_down += 8 + (int64_t)q.n_pairs * 8;
-    if (pairs_cap > 0) memcpy(pairs_out + (size_t)2 * c * pairs_cap, hp + (size_t)2 * c * max_nl, (size_t)std::min(q.n_pairs, pairs_cap) * 8);
-    if (q.n_pairs > pairs_cap && over < 0) over = c;
+    const MatchResult r = match_out_read((const int32_t*)(ho + out_stride * (size_t)k));
+    q.n_pairs = r.n_pairs; q.min_distance = r.min_distance; st.bytes_down += match_out_crossed(r);
+    copy_pairs(r, pairs_cap, pairs_out + (size_t)2 * k * pairs_cap);
+    if (q.n_pairs > pairs_cap && over < 0) over = k;
   }
   db->last = st;
   if (over >= 0) {
-    ctx->set_error("ssx_kfdb_relocalize_query: candidate %d has %d pairs but capacity %d", over, res->cand[over].n_pairs, pairs_cap);
+    ctx->set_error("%s: candidate %d has %d pairs but capacity %d", who, over, res->cand[over].n_pairs, pairs_cap);
     return SSX_ERR_CAPACITY;
   }
   return SSX_OK;
 }
 
-// The keyframe steps of n databases of one context as ONE launch chain (the job-indexed kernels above and in orb.hip / voc.hip /
+// The keyframe steps of n databases of one context as ONE enqueue of the chain (and the job-indexed kernels of orb.hip / voc.hip /
 // stereo.hip): validate everything, grow what the commits need, enqueue phase 1 for all jobs, one synchronisation, and phase 2 (match and
 // pairs of the found jobs) behind a second one.  The host mirrors of the databases change only after the first synchronisation succeeded.
 ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const ssx_kfdb_step_job* jobs, int32_t rows, int32_t cols, const ssx_orb_params* prm,
                                            int32_t pyramid_levels, int32_t min_db_size, int32_t min_id_gap, float threshold, int32_t images_on_device)
 {
+  static const char* const who = "ssx_kfdb_process_keyframe_batch";
   if (n < 0) return SSX_ERR_INVALID_ARG;
   if (n == 0) return SSX_OK;
   if (!voc || !jobs || !prm || rows <= 0 || cols <= 0 || pyramid_levels < 1 || pyramid_levels > ssxorb::MAX_LEVELS) return SSX_ERR_INVALID_ARG;
@@ -1153,33 +1247,28 @@ ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const
   std::vector<const ssx_kf_database*> seen;
   for (int j = 0; j < n; ++j) {
     const ssx_kfdb_step_job& q = jobs[j];
-    if (!q.db || !q.res || !q.status_out || !q.img || q.stride < cols || q.n_features < 0 || (q.n_features > 0 && !q.features) || q.pairs_cap < 0 ||
-        (q.pairs_cap > 0 && !q.pairs_out)) {
-      ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: a missing database / result / status / image / array, a stride below the width or a negative count", j);
+    const FrameArgs fa{q.img, q.stride, rows, cols, prm, q.n_features, q.features, pyramid_levels, q.pairs_cap, q.pairs_out};
+    if (!q.db || !q.res || !q.status_out || !frame_args_ok(fa)) {
+      ctx->set_error("%s: job %d: a missing database / result / status / image / array, a stride below the width or a negative count", who, j);
       return SSX_ERR_INVALID_ARG;
     }
-    if (q.db->ctx != ctx) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: the database and the vocabulary belong to different contexts", j); return SSX_ERR_INVALID_ARG; }
-    if (q.stride != jobs[0].stride) { ctx->set_error("ssx_kfdb_process_keyframe_batch: the images of a call share one stride"); return SSX_ERR_INVALID_ARG; }
-    if (std::find(seen.begin(), seen.end(), q.db) != seen.end()) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d names the database of an earlier job", j); return SSX_ERR_INVALID_ARG; }
+    if (q.db->ctx != ctx) { ctx->set_error("%s: job %d: the database and the vocabulary belong to different contexts", who, j); return SSX_ERR_INVALID_ARG; }
+    if (q.stride != jobs[0].stride) { ctx->set_error("%s: the images of a call share one stride", who); return SSX_ERR_INVALID_ARG; }
+    if (std::find(seen.begin(), seen.end(), q.db) != seen.end()) { ctx->set_error("%s: job %d names the database of an earlier job", who, j); return SSX_ERR_INVALID_ARG; }
     seen.push_back(q.db);
-    if ((int64_t)q.n_features * pyramid_levels > 65535) {
-      ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: %d features x %d levels: more than 65535 pyramid keypoints", j, q.n_features, pyramid_levels);
-      return SSX_ERR_UNSUPPORTED;
-    }
+    if (ssx_status s = check_pyramid_bound(ctx, who, j, fa)) return s;
     if (q.commit_pending) {
-      if (!q.db->pending.valid) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: commit_pending but no keyframe is pending", j); return SSX_ERR_INVALID_ARG; }
-      if (ssx_status st = check_next_id(q.db, "ssx_kfdb_process_keyframe_batch", q.db->pending.kf_id)) return st;
-      if (q.db->ids.size() >= (size_t)0x7fffffff) { ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: the database is full", j); return SSX_ERR_CAPACITY; }
+      if (!q.db->pending.valid) { ctx->set_error("%s: job %d: commit_pending but no keyframe is pending", who, j); return SSX_ERR_INVALID_ARG; }
+      if (ssx_status s = check_commit(q.db, who, j, q.db->pending.kf_id)) return s;
     }
   }
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ssx_ctx::KfBatchStats st{};
+  KfChainStats st{};
   ctx->kf_batch = st;
   // ---- what every job is, as if its commit had happened ----
   struct Job { ssx_kf_database::Pending pe; bool commit; int N, n_elig; size_t blob; bool detect; };
   std::vector<Job> J(n);
-  int total = 0, max_N = 0, max_elig = 0;
-  bool any_commit = false;
+  int max_N = 0;
   for (int j = 0; j < n; ++j) {
     const ssx_kfdb_step_job& q = jobs[j];
     ssx_kf_database* db = q.db;
@@ -1190,13 +1279,11 @@ ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const
     a.detect = (int64_t)stored > (int64_t)min_db_size;       // loopclosing.cpp:48
     const int64_t newest = q.kf_id - (int64_t)min_id_gap;    // the prefix that is old enough (:79); the committed keyframe is the last of the map
     a.n_elig = a.detect ? (int)(std::upper_bound(db->ids.begin(), db->ids.end(), newest) - db->ids.begin()) + ((a.commit && a.pe.kf_id <= newest) ? 1 : 0) : 0;
-    total += a.N; max_N = std::max(max_N, a.N); max_elig = std::max(max_elig, a.N > 0 ? a.n_elig : 0);
-    any_commit = any_commit || a.commit;
+    max_N = std::max(max_N, a.N);
     if (a.commit) {                                           // the growth a commit needs, with its own synchronisation as in ssx_kfdb_add_pending
-      const size_t cap_a = db->arena.cap, cap_t = db->table.cap, rows_n = db->ids.size();
-      SSX_HIP_TRY(ctx, grow_keep(ctx, db->arena, db->used, db->used + a.blob));
-      SSX_HIP_TRY(ctx, grow_keep(ctx, db->table, rows_n * sizeof(KfRow), (rows_n + 1) * sizeof(KfRow)));
-      st.syncs += (db->arena.cap != cap_a ? 1 : 0) + (db->table.cap != cap_t ? 1 : 0);
+      int moved = 0;                                          // (counted: the batch's synchronisations stay exact)
+      SSX_HIP_TRY(ctx, grow_for_commit(db, a.blob, &moved));
+      st.syncs += moved;
     }
   }
   // ---- the describe block (the job table at its head), the scratch, the pending buffers: every allocation before the first enqueue ----
@@ -1207,25 +1294,16 @@ ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const
                                                     sizeof(KfJobDev) * (size_t)n, &d))
     return s;
   st.syncs += d.syncs;
-  StepHdr* dh; int32_t* word; double* weight;
-  std::vector<unsigned long long*> keys(n, nullptr);
-  std::vector<double*> scores(n, nullptr);
-  auto scratch = [&](auto&& f) {
-    f(dh, sizeof(StepHdr) * (size_t)n); f(word, (size_t)4 * total); f(weight, (size_t)8 * total);
-    for (int j = 0; j < n; ++j) {
-      size_t npad = 1;
-      while (npad < (size_t)J[j].N) npad *= 2;
-      f(keys[j], J[j].N > kSortLds ? npad * 8 : 0); f(scores[j], (size_t)J[j].n_elig * 8);
-    }
-  };
-  SSX_HIP_TRY(ctx, voc->io.reserve(carve(nullptr, scratch)));
-  SSX_HIP_TRY(ctx, voc->stage.reserve(sizeof(StepHdr) * (size_t)n + 256));
-  carve(voc->io.as<char>(), scratch);
+  KfJobDev* tab = reinterpret_cast<KfJobDev*>(d.host_extra);
+  for (int j = 0, kp0 = 0; j < n; kp0 += J[j].N, ++j) {
+    tab[j] = KfJobDev{};
+    tab[j].kp0 = kp0; tab[j].n_in = J[j].N; tab[j].n_elig = J[j].N > 0 ? J[j].n_elig : 0;
+  }
+  Chain c; c.n = n; c.jobs = tab; c.dev_jobs = reinterpret_cast<const KfJobDev*>(d.dev_extra); c.bound = max_N;
+  SSX_HIP_TRY(ctx, chain_reserve(voc->io, voc->stage, c, sizeof(StepHdr) * (size_t)n, nothing_more));
   // A job that commits reads its previous pending arrays in the chain below: a buffer that has to grow is replaced, and the old one is
   // freed only after the synchronisation (DevBuf::reserve would free it now)
   struct Retired { std::vector<void*> p; ~Retired() { for (void* q : p) (void)hipFree(q); } } retired;
-  KfJobDev* tab = reinterpret_cast<KfJobDev*>(d.host_extra);
-  int kp0 = 0;
   // from here on the databases are touched: whatever way the call fails, nothing is left pending
   struct DropPending {
     const ssx_kfdb_step_job* jobs; int n; bool armed;
@@ -1235,9 +1313,8 @@ ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const
     const ssx_kfdb_step_job& q = jobs[j];
     ssx_kf_database* db = q.db;
     const Job& a = J[j];
-    KfJobDev t{};
-    PendArrays old{}, pa{};
-    if (a.commit) pend_arrays(db->pend.as<char>(), a.pe.cap, old);      // (cap == 0: an empty keyframe, nothing is read)
+    if (a.commit) commit_job(tab[j], db);                               // (the arrays where they lie now, before the buffer is replaced)
+    PendArrays pa{};
     if (a.N > 0) {
       const size_t need = pend_arrays(nullptr, a.N, pa);
       if (a.commit && need > db->pend.cap) {
@@ -1252,132 +1329,53 @@ ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const
       pend_arrays(db->pend.as<char>(), a.N, pa);
     }
     db->pending.valid = false;                                          // a call that fails from here on leaves nothing pending
-    db->last = KfStepStats{};
-    t.kp0 = kp0; t.n_in = a.N; t.n_elig = a.N > 0 ? a.n_elig : 0; t.commit = a.commit ? 1 : 0;
-    t.p_kps = pa.kps; t.p_desc = pa.desc; t.p_cls = pa.cls; t.p_ids = pa.ids; t.p_vals = pa.vals;
-    t.bow_keys = keys[j]; t.arena = db->arena.as<char>(); t.rows = db->table.p; t.scores = scores[j];
-    if (a.commit) {
-      t.c_ids = old.ids; t.c_vals = old.vals; t.c_cls = old.cls; t.c_desc = old.desc;
-      t.c_blob = db->arena.as<char>() + db->used; t.c_row_out = db->table.as<KfRow>() + db->ids.size();
-      t.c_off = (int64_t)db->used; t.c_n_bow = a.pe.n_bow; t.c_n_desc = a.pe.n_pyr;
-    }
-    tab[j] = t;
-    kp0 += a.N;
+    db->last = KfChainStats{};
+    job_arrays(tab[j], pa, db);
     *q.res = ssx_kfdb_step_result{};
     q.res->min_distance = -1; q.res->detect_ran = a.detect ? 1 : 0; q.res->n_scored = a.n_elig;
     *q.status_out = SSX_OK;
   }
   // ---- phase 1: one enqueue for all jobs ----
-  const KfJobDev* dtab = reinterpret_cast<const KfJobDev*>(d.dev_extra);
-  hipStream_t s = ctx->stream;
-  if (ssx_status e = ssxorb::describe_batch_launch(ctx, n, dtab, max_N, &d)) return e;
+  if (ssx_status e = ssxorb::describe_batch_launch(ctx, n, c.dev_jobs, max_N, &d)) return e;
   st.launches += d.launches; st.bytes_up += (int64_t)d.bytes_up;
-  if (any_commit) {
-    size_t most = 0;
-    for (const Job& a : J) most = std::max(most, a.blob);
-    const int blocks = (int)std::min<size_t>(std::max<size_t>((most / 4 + 255) / 256, 1), 1024);
-    SSX_PROF(ctx, KID_LOOP_COMMIT, hipLaunchKernelGGL(k_kfdb_commit_jobs, dim3(blocks, n), dim3(256), 0, s, dtab));
-    ++st.launches;
-  }
-  SSX_PROF(ctx, KID_LOOP_COMPACT, hipLaunchKernelGGL(k_kf_compact_jobs, dim3(n), dim3(kPairsThreads), 0, s, dtab, d.kps, d.desc, d.keep, dh));
-  SSX_PROF(ctx, KID_LOOP_WORDS, ssxvoc::launch_words_jobs(s, voc, dtab, n, &dh->n_pyr, (int)(sizeof(StepHdr) / 4), total, word, weight));
-  SSX_PROF(ctx, KID_LOOP_BOW, hipLaunchKernelGGL(k_kf_bow_jobs, dim3(n), dim3(kPairsThreads), 0, s, dtab, word, weight, voc->weighting, dh));
-  st.launches += 3;
-  if (max_elig > 0) {
-    const int blocks = std::min((max_elig + 3) / 4, 1024), lds_cap = std::min(max_N, kQueryLds);
-    SSX_PROF(ctx, KID_LOOP_SCORE, hipLaunchKernelGGL(k_kfdb_score_jobs, dim3(blocks, n), dim3(256), (size_t)lds_cap * 12, s, dtab, dh, lds_cap));
-    ++st.launches;
-  }
-  SSX_HIP_TRY(ctx, hipGetLastError());
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(voc->stage.p, dh, sizeof(StepHdr) * (size_t)n, hipMemcpyDeviceToHost, s));
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  ++st.syncs; st.bytes_down += (int64_t)(sizeof(StepHdr) * (size_t)n);
+  c.kps = d.kps; c.desc = d.desc; c.keep = d.keep;
   std::vector<StepHdr> hdr(n);
-  memcpy(hdr.data(), voc->stage.p, sizeof(StepHdr) * (size_t)n);
+  SSX_HIP_TRY(ctx, chain_enqueue(ctx, voc, voc->stage, c, hdr.data(), st));
   // ---- the commits have happened: the host mirrors follow ----
-  for (int j = 0; j < n; ++j) {
-    if (!J[j].commit) continue;
-    ssx_kf_database* db = jobs[j].db;
-    const Job& a = J[j];
-    db->ids.push_back(a.pe.kf_id); db->rows.push_back(KfRow{(int64_t)db->used, a.pe.n_bow, a.pe.n_pyr});
-    db->used += a.blob; db->n_bow += a.pe.n_bow; db->n_desc += a.pe.n_pyr;
-  }
+  for (int j = 0; j < n; ++j)
+    if (J[j].commit) commit_mirror(jobs[j].db, J[j].pe.kf_id, KfRow{tab[j].c_off, J[j].pe.n_bow, J[j].pe.n_pyr}, J[j].blob);
   // ---- DetectLoop's verdicts; the jobs whose winner has something to match go to phase 2 ----
   ssx_status first = SSX_OK;
   auto fail = [&](int j, ssx_status e) { *jobs[j].status_out = e; if (first == SSX_OK) first = e; };
-  struct Found { int j; KfRow row; };
-  std::vector<Found> found;
+  std::vector<MatchEntry> found;
   for (int j = 0; j < n; ++j) {
     const ssx_kfdb_step_job& q = jobs[j];
     ssx_kf_database* db = q.db;
     q.res->n_pyramid = hdr[j].n_pyr; q.res->n_bow = hdr[j].n_bow;
-    uint32_t row_i = 0;
-    float f = 0.f;
-    if (J[j].N > 0 && J[j].n_elig > 0 && winner_of(hdr[j].best, threshold, &row_i, &f)) {
-      q.res->found = 1; q.res->score = f; q.res->loop_kf_id = db->ids[row_i];
-      const KfRow row = db->rows[row_i];
-      if (row.n_desc < 0) {
-        ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: the loop keyframe %lld was added without descriptors", j, (long long)db->ids[row_i]);
-        fail(j, SSX_ERR_INVALID_ARG);
-        continue;                                             // (nothing pending, as the single call leaves it)
-      }
-      if (row.n_desc > 0 && hdr[j].n_pyr > 0) found.push_back(Found{j, row});   // else no match exists: no pairs
+    MatchEntry m{db, KfRow{}, tab[j].p_desc, tab[j].p_cls, hdr[j].n_pyr, j};
+    bool match = false;
+    if (ssx_status s = step_verdict(db, who, j, hdr[j], tab[j].n_elig > 0, threshold, q.res, &m.row, &match)) {
+      fail(j, s);
+      continue;                                               // (nothing pending, as the single call leaves it)
     }
+    if (match) found.push_back(m);
     db->pending.valid = true; db->pending.kf_id = q.kf_id; db->pending.cap = J[j].N; db->pending.n_pyr = hdr[j].n_pyr; db->pending.n_bow = hdr[j].n_bow;
   }
   if (!found.empty()) {
-    // ---- phase 2: MatchFeatures of the found jobs, one match launch and one pairs launch.  The match table lies in mapped pinned memory and is
-    // read from there; the pair counts and the pairs are written there: 8 bytes of header and 8 per pair cross. ----
+    // ---- phase 2: MatchFeatures of the found jobs.  Their table lies in mapped pinned memory and is read from there ----
     const int nf = (int)found.size();
-    std::vector<MatchScratch> m(nf);
-    auto mscratch = [&](auto&& g) { for (int k = 0; k < nf; ++k) match_scratch(g, m[k], found[k].row.n_desc); };
-    SSX_HIP_TRY(ctx, voc->io.reserve(carve(nullptr, mscratch)));
-    carve(voc->io.as<char>(), mscratch);
-    KfMatchJob* mt;
-    std::vector<int32_t*> out(nf, nullptr);
-    auto pinned = [&](auto&& g) { g(mt, sizeof(KfMatchJob) * (size_t)nf); for (int k = 0; k < nf; ++k) g(out[k], 256 + (size_t)found[k].row.n_desc * 8); };
-    SSX_HIP_TRY(ctx, voc->stage.reserve(carve(nullptr, pinned)));
-    char* hp = voc->stage.as<char>();
-    carve(hp, pinned);
-    void* dp = nullptr;
-    SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dp, hp, 0));
-    auto on_device = [&](void* host) { return (char*)dp + ((char*)host - hp); };
-    int max_nl = 0;
-    for (int k = 0; k < nf; ++k) {
-      const Found& fd = found[k];
-      ssx_kf_database* db = jobs[fd.j].db;
-      const char* blob = db->arena.as<char>() + fd.row.off;
-      PendArrays pa{};
-      pend_arrays(db->pend.as<char>(), J[fd.j].N, pa);
-      out[k][0] = 0; out[k][1] = -1;
-      KfMatchJob t{};
-      t.loop_desc = (const uint8_t*)(blob + blob_desc(fd.row.n_bow, fd.row.n_desc)); t.loop_cls = (const int32_t*)(blob + blob_class(fd.row.n_bow));
-      t.cur_desc = pa.desc; t.cur_cls = pa.cls; t.idx = m[k].idx; t.dist = m[k].dist; t.keys = m[k].keys;
-      t.hdr = (int32_t*)on_device(out[k]); t.pairs = (int32_t*)(on_device(out[k]) + 256);
-      t.nl = fd.row.n_desc; t.n_cur = hdr[fd.j].n_pyr;
-      mt[k] = t;
-      max_nl = std::max(max_nl, t.nl);
-    }
-    // (one found job: its entry travels as a kernel argument, as the single call's pointers do, and no workgroup reads host memory for it)
-    const KfMatchJob* dmt = nf > 1 ? (const KfMatchJob*)on_device(mt) : nullptr;
-    SSX_PROF(ctx, KID_LOOP_MATCH, ssxorb::launch_bf_match_jobs(s, dmt, mt[0], nf, max_nl));
-    SSX_PROF(ctx, KID_LOOP_PAIRS, hipLaunchKernelGGL(k_kfdb_pairs_jobs, dim3(nf), dim3(kPairsThreads), 0, s, dmt, mt[0]));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      ctx->set_error("ssx_kfdb_process_keyframe_batch: the match phase failed: %s", hipGetErrorString(e));
+    if (hipError_t e = match_phase(ctx, voc->io, voc->stage, found.data(), nf, st)) {
+      ctx->set_error("%s: the match phase failed: %s", who, hipGetErrorString(e));
       return SSX_ERR_HIP;
     }
-    st.launches += 2; ++st.syncs; st.bytes_up += (int64_t)(sizeof(KfMatchJob) * (size_t)nf);   // (nf == 1: as kernel arguments)
-    for (int k = 0; k < nf; ++k) {
-      const ssx_kfdb_step_job& q = jobs[found[k].j];
-      const int n_pairs = out[k][0];
-      q.res->n_pairs = n_pairs; q.res->min_distance = out[k][1];
-      st.bytes_down += 8 + (int64_t)n_pairs * 8;
-      if (q.pairs_cap > 0) memcpy(q.pairs_out, (const char*)out[k] + 256, (size_t)std::min(n_pairs, q.pairs_cap) * 8);
-      if (n_pairs > q.pairs_cap) {
-        ctx->set_error("ssx_kfdb_process_keyframe_batch: job %d: %d pairs but capacity %d", found[k].j, n_pairs, q.pairs_cap);
-        fail(found[k].j, SSX_ERR_CAPACITY);
+    st.bytes_up += (int64_t)(sizeof(KfMatchJob) * (size_t)nf);   // (nf == 1: as kernel arguments; the single step does not count its one)
+    for (const MatchEntry& m : found) {
+      const ssx_kfdb_step_job& q = jobs[m.tag];
+      q.res->n_pairs = m.r.n_pairs; q.res->min_distance = m.r.min_distance;
+      copy_pairs(m.r, q.pairs_cap, q.pairs_out);
+      if (m.r.n_pairs > q.pairs_cap) {
+        ctx->set_error("%s: job %d: %d pairs but capacity %d", who, m.tag, m.r.n_pairs, q.pairs_cap);
+        fail(m.tag, SSX_ERR_CAPACITY);
       }
     }
   }
@@ -1390,23 +1388,18 @@ ssx_status ssx_kfdb_process_keyframe_batch(ssx_vocabulary* voc, int32_t n, const
 ssx_status ssx_kfdb_debug_last_batch(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
 {
   if (!ctx) return SSX_ERR_INVALID_ARG;
-  if (launches) *launches = ctx->kf_batch.launches;
-  if (synchronisations) *synchronisations = ctx->kf_batch.syncs;
-  if (bytes_up) *bytes_up = ctx->kf_batch.bytes_up;
-  if (bytes_down) *bytes_down = ctx->kf_batch.bytes_down;
+  report_stats(ctx->kf_batch, launches, synchronisations, bytes_up, bytes_down);
   return SSX_OK;
 }
 
 ssx_status ssx_kfdb_debug_last_step(const ssx_kf_database* db, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
 {
   if (!db) return SSX_ERR_INVALID_ARG;
-  if (launches) *launches = db->last.launches;
-  if (synchronisations) *synchronisations = db->last.syncs;
-  if (bytes_up) *bytes_up = db->last.bytes_up;
-  if (bytes_down) *bytes_down = db->last.bytes_down;
+  report_stats(db->last, launches, synchronisations, bytes_up, bytes_down);
   return SSX_OK;
 }
 
+// steps 3-4 of the chain alone, on a caller's descriptors
 ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t cap, int32_t* ids_out, double* vals_out, int32_t* n_entries)
 {
   if (!voc || n < 0 || (n > 0 && !desc) || cap < 0 || (cap > 0 && (!ids_out || !vals_out)) || !n_entries) return SSX_ERR_INVALID_ARG;
@@ -1414,31 +1407,36 @@ ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t 
   *n_entries = 0;
   if (n == 0) return SSX_OK;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint8_t* feat; int32_t* cnt; int32_t* ids; double* vals;
-  BowScratch b{};
-  // one block, on the device and (pinned) on the host: [descriptors | count in, count out] go up, [ids | values] and the counts come back
-  auto bufs = [&](auto&& f) { f(feat, (size_t)32 * n); f(cnt, 8); bow_scratch(f, b, n); f(ids, (size_t)4 * n); f(vals, (size_t)8 * n); };
+  StepHdr* dh; int32_t* word; double* weight;
+  KfJobDev one{}; one.n_in = n;
+  // one block, on the device and (pinned) on the host: [descriptors | header: count in, count out] go up, [ids | values] and the header come back
+  auto bufs = [&](auto&& f) {
+    f(one.p_desc, (size_t)32 * n); f(dh, sizeof(StepHdr)); f(word, (size_t)4 * n); f(weight, (size_t)8 * n); f(one.bow_keys, sort_scratch_bytes(n));
+    f(one.p_ids, (size_t)4 * n); f(one.p_vals, (size_t)8 * n);
+  };
   const size_t total = carve(nullptr, bufs);
   SSX_HIP_TRY(ctx, voc->io.reserve(total));
   SSX_HIP_TRY(ctx, voc->stage.reserve(total));
   char* base = voc->io.as<char>();
   carve(base, bufs);
-  const size_t o_in = (size_t)((char*)b.word - base), o_out = (size_t)((char*)ids - base);
+  const size_t o_hdr = (size_t)((char*)dh - base), o_in = (size_t)((char*)word - base), o_ids = (size_t)((char*)one.p_ids - base),
+               o_vals = (size_t)((char*)one.p_vals - base);
   char* hs = voc->stage.as<char>();
   memcpy(hs, desc, (size_t)32 * n);
-  int32_t hc[2] = {n, 0};
-  memcpy(hs + ((char*)cnt - base), hc, 8);
+  StepHdr hdr{n, 0, 0};
+  memcpy(hs + o_hdr, &hdr, sizeof(StepHdr));
   SSX_HIP_TRY(ctx, hipMemcpyAsync(base, hs, o_in, hipMemcpyHostToDevice, ctx->stream));
-  SSX_HIP_TRY(ctx, launch_bow(ctx, voc, feat, n, cnt, b, ids, vals, cnt + 1, nullptr));
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + ((char*)cnt - base), cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_out, base + o_out, total - o_out, hipMemcpyDeviceToHost, ctx->stream));
+  launch_words_bow(ctx, voc, nullptr, one, 1, n, dh, word, weight);
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_hdr, dh, sizeof(StepHdr), hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hs + o_ids, base + o_ids, total - o_ids, hipMemcpyDeviceToHost, ctx->stream));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(hc, hs + ((char*)cnt - base), 8);
-  *n_entries = hc[1];
-  if (hc[1] > cap) { ctx->set_error("ssx_kfdb_debug_bow: %d words but capacity %d", hc[1], cap); return SSX_ERR_CAPACITY; }
-  if (hc[1] > 0) {
-    memcpy(ids_out, hs + ((char*)ids - base), (size_t)4 * hc[1]);
-    memcpy(vals_out, hs + ((char*)vals - base), (size_t)8 * hc[1]);
+  memcpy(&hdr, hs + o_hdr, sizeof(StepHdr));
+  *n_entries = hdr.n_bow;
+  if (hdr.n_bow > cap) { ctx->set_error("ssx_kfdb_debug_bow: %d words but capacity %d", hdr.n_bow, cap); return SSX_ERR_CAPACITY; }
+  if (hdr.n_bow > 0) {
+    memcpy(ids_out, hs + o_ids, (size_t)4 * hdr.n_bow);
+    memcpy(vals_out, hs + o_vals, (size_t)8 * hdr.n_bow);
   }
   return SSX_OK;
 }

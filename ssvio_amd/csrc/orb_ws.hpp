@@ -145,6 +145,7 @@ ssx_status run_pipeline(ssx_ctx* ctx);
 // download the keypoints / descriptors of one image of the last run (synchronises the stream)
 ssx_status fetch_image(ssx_ctx* ctx, int image, int cap, ssx_keypoint* kps_out, uint8_t* desc_out, int32_t* n);
 // the brute-force matcher k_bf_match (stereo.hip) on device arrays: idx[i] / dist[i] = nearest of the nt <= 65535 train descriptors to query i
+// (ssx_bf_match's launch; the keyframe database matches through launch_bf_match_jobs, kf_batch.hpp)
 void launch_bf_match(hipStream_t stream, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist);
 // what describe_enqueue leaves on the device: per input keypoint the output keypoint and descriptor (valid where keep), inside the block at
 // `base` of `total` bytes; and what it issued: launches, synchronisations (a new plan's two), bytes sent up

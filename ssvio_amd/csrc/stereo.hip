@@ -528,7 +528,7 @@ ssx_status fetch_frame_fast(ssx_ctx* ctx, const FrameSlots& o, ssx_stereo_frame_
 
 }  // namespace
 
-// k_bf_match on device arrays, for the callers outside this file (loop.hip matches against descriptors that stay in HBM)
+// k_bf_match on device arrays (ssx_bf_match below), and its job form for loop.hip, which matches against descriptors that stay in HBM
 void launch_bf_match(hipStream_t stream, const uint8_t* dq, int nq, const uint8_t* dt, int nt, int* idx, int* dist)
 {
   hipLaunchKernelGGL(k_bf_match, dim3((nq + 3) / 4), dim3(256), 0, stream, dq, nq, dt, nt, idx, dist);
