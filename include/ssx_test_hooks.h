@@ -85,6 +85,24 @@ SSX_API ssx_status ssx_orb_stage_level(ssx_ctx* ctx, int32_t image, int32_t leve
 SSX_API ssx_status ssx_orb_stage_candidates(ssx_ctx* ctx, int32_t image, int32_t level, int32_t cap,
                                             ssx_keypoint* out, int32_t* n);
 
+/* tests hook: k_octree (csrc/octree.hip) on the CALLER'S candidates, no image involved (tests/test_octree_gpu.py,
+ * tests/octree_cases.py).  The key (rows, cols, images, prm, detect_only; no mask) is planned as the entry points plan it -- the
+ * same build_plan, the same arena, so the same one of the kernel's four builds and the same scratch stride -- and the n candidates,
+ * parallel int32 arrays (image, level, x, y, response) with x, y relative to the 16-px border as in cell_cand, are written into
+ * the cell lists as k_fast_cells would have left them: each into the one cell whose ROI, less its 3-px frame, holds it, in
+ * input order inside a cell.  status and every cell_count are zeroed first; then launch_octree runs as the pipeline calls it and
+ * the stream is synchronised.  Outputs (any may be NULL), L = the plan's levels (1 for detect_only):
+ *   lvl_ncand, sel_count   images x L (-1 where the kernel wrote nothing)
+ *   sel                    images x L x 4096 packed x | y << 12 | response << 24; the first sel_count entries, in list order
+ *   status                 per image (bit 0 candidates, bit 1 nodes, bit 2 outputs over capacity)
+ * SSX_ERR_INVALID_ARG with text, and nothing launched, for: an image or level out of range, a coordinate outside 0..4095, a
+ * response outside 1..255, a candidate in no cell, more than 256 candidates in a cell.  The key's own refusals are the plan's.
+ * Afterwards ssx_orb_stage_candidates returns the candidates in reference order, as after a run on an image. */
+SSX_API ssx_status ssx_orb_debug_octree(ssx_ctx* ctx, int32_t rows, int32_t cols, int32_t images, const ssx_orb_params* prm,
+                                        int32_t detect_only, int32_t n, const int32_t* image, const int32_t* level, const int32_t* x,
+                                        const int32_t* y, const int32_t* response, int32_t* lvl_ncand, int32_t* sel_count,
+                                        uint32_t* sel, int32_t* status);
+
 /* Test access to the pyramids (which = 0 previous, 1 next) and the Scharr images (int16 dx, dy interleaved) of
  * the last ssx_lk_track call. */
 SSX_API ssx_status ssx_lk_stage_level(ssx_ctx* ctx, int32_t which, int32_t level, uint8_t* out, int32_t out_cap,

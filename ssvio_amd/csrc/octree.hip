@@ -117,7 +117,7 @@ __device__ __forceinline__ int above1_4(u64 c) { return (f16(c, 0) > 1) + (f16(c
 
 // GLOBAL_TAB = false: node tables in dynamic LDS (OCT_NODE_BYTES * LN bytes); true: in the global scratch block.
 // GLOBAL_KEYS = false: per-key state (6 bytes per candidate, <= 16384 candidates per level) in LDS; true: in the
-// global scratch block (images above ~0.6 Mpx: up to 65536 candidates per level, 64 keys per thread).
+// global scratch block (images above ~0.6 Mpx: up to 65535 candidates per level, 64 keys per thread).
 template <bool GLOBAL_TAB, bool GLOBAL_KEYS>
 __global__ __launch_bounds__(OCT_THREADS) void k_octree(OrbDev d)
 {
@@ -133,23 +133,24 @@ __global__ __launch_bounds__(OCT_THREADS) void k_octree(OrbDev d)
   Tab tb;
   uint32_t* s_cellpos;                                                 // [cells of the level + 1], dynamic LDS
   const int CAP = d.oct_cand_cap;
+  const int SLOTS = oct_key_slots(CAP);                                // key slots: [slots per thread][T]
   uint8_t* scratch = d.oct + (size_t)il * d.oct_stride;                // [keys (GLOBAL_KEYS) | node tables (GLOBAL_TAB)]
   if constexpr (GLOBAL_TAB) {
-    tb = carve(scratch + (GLOBAL_KEYS ? 6 * (size_t)CAP : 0), LN);
+    tb = carve(scratch + (GLOBAL_KEYS ? 6 * (size_t)SLOTS : 0), LN);
     s_cellpos = reinterpret_cast<uint32_t*>(smem);
   } else {
     tb = carve(smem, LN);
     s_cellpos = reinterpret_cast<uint32_t*>(smem + (((size_t)OCT_NODE_BYTES * LN + 15) & ~size_t(15)));
   }
   // per-key state, slot k of thread t at [k * T + t]: packed candidate, and node id | quadrant << 14
-  uint32_t* s_kpk;                                                     // [CAP] x | y << 12 | score << 24
-  uint16_t* s_kn;                                                      // [CAP]
+  uint32_t* s_kpk;                                                     // [SLOTS] x | y << 12 | score << 24
+  uint16_t* s_kn;                                                      // [SLOTS]
   if constexpr (GLOBAL_KEYS) {
     s_kpk = reinterpret_cast<uint32_t*>(scratch);
-    s_kn = reinterpret_cast<uint16_t*>(s_kpk + CAP);
+    s_kn = reinterpret_cast<uint16_t*>(s_kpk + SLOTS);
   } else {
     s_kpk = s_cellpos + ((d.oct_max_cells + 1 + 3) & ~3);
-    s_kn = reinterpret_cast<uint16_t*>(s_kpk + CAP);
+    s_kn = reinterpret_cast<uint16_t*>(s_kpk + SLOTS);
   }
   const int N = d.feat[level];
   const int cell0 = d.lvl_cell0[level], cell1 = d.lvl_cell0[level + 1];
@@ -187,7 +188,8 @@ __global__ __launch_bounds__(OCT_THREADS) void k_octree(OrbDev d)
   const int minX = EDGE_THRESHOLD - 3, minY = minX;
   const int maxX = d.lvl_cols[level] - EDGE_THRESHOLD + 3, maxY = d.lvl_rows[level] - EDGE_THRESHOLD + 3;
   const int nIni = (int)roundf((float)(maxX - minX) / (float)(maxY - minY));
-  if (nIni < 1 || nIni > 64) { if (t == 0) *sel_count = 0; return; }
+  static_assert(OCT_MAX_ROOTS == 64, "the roots are placed by one wave, in s_root[64]");
+  if (nIni < 1 || nIni > OCT_MAX_ROOTS) { if (t == 0) *sel_count = 0; return; }   // (> OCT_MAX_ROOTS: build_plan refuses the key)
   const float hX = (float)(maxX - minX) / (float)nIni;
   // my candidates: the CONTIGUOUS range [p0, p0 + nk) of the reference order.  Neighbouring candidates mostly sit
   // in the same node, so a thread folds runs of equal targets in registers and issues one LDS atomic per run
@@ -444,7 +446,7 @@ void launch_octree(const OrbDev& o, hipStream_t s)
   // all level-0 workgroups first and spreads them over the whole chip.
   const dim3 grid(o.I, o.detect_only ? 1 : o.nlevels);
   const size_t tab = o.oct_global_tab ? 0 : (((size_t)OCT_NODE_BYTES * o.oct_ln + 15) & ~size_t(15));
-  const size_t lds = tab + 4 * (size_t)((o.oct_max_cells + 1 + 3) & ~3) + (o.oct_global_keys ? 0 : 6 * (size_t)o.oct_cand_cap);
+  const size_t lds = tab + 4 * (size_t)((o.oct_max_cells + 1 + 3) & ~3) + (o.oct_global_keys ? 0 : 6 * (size_t)oct_key_slots(o.oct_cand_cap));
   void (*kern)(OrbDev) = o.oct_global_tab ? (o.oct_global_keys ? k_octree<true, true> : k_octree<true, false>)
                                           : (o.oct_global_keys ? k_octree<false, true> : k_octree<false, false>);
   if (lds > 48 * 1024)

@@ -1193,6 +1193,17 @@ void plan_cells(OrbPlan& p)
 ssx_status plan_octree(OrbPlan& p, char* err)
 {
   OrbDev& d = p.dev;
+  // root nodes: k_octree keeps their counts in 64 LDS words and sizes its node table for a first round of 4 * 64 children.  A level
+  // with cells and more roots than that would come back empty, so its key is refused.  (nIni as the kernel computes it; a level
+  // taller than wide has nIni 0 and selects nothing, in the reference as here.)
+  for (int l = 0; l < (d.detect_only ? 1 : d.nlevels); ++l) {
+    const int bw = d.lvl_cols[l] - 2 * (EDGE_THRESHOLD - 3), bh = d.lvl_rows[l] - 2 * (EDGE_THRESHOLD - 3);
+    if (d.lvl_cell0[l + 1] == d.lvl_cell0[l]) continue;
+    const int n_ini = (int)roundf((float)bw / (float)bh);
+    if (n_ini > OCT_MAX_ROOTS)
+      return plan_fail(err, SSX_ERR_UNSUPPORTED, "ssx_orb: level %d (%dx%d) is %d times as wide as high: the octree takes at most %d root nodes", l,
+                       d.lvl_cols[l], d.lvl_rows[l], n_ini, OCT_MAX_ROOTS);
+  }
   // node-table capacity: a round of phase 1 never ends above N nodes (it is only entered while
   // size + 3 * expandable <= N) except the first one (<= 4 * nIni <= 256), phase 2 stops within N + 2
   int maxN = 256;
@@ -1203,11 +1214,11 @@ ssx_status plan_octree(OrbPlan& p, char* err)
   // per-key state: in LDS for images up to ~0.6 Mpx (16384 candidates per level), else in global scratch
   d.oct_global_keys = (size_t)d.lvl_rows[0] * d.lvl_cols[0] > 600000;
   d.oct_cand_cap = d.oct_global_keys ? CAND_CAP_BIG : CAND_CAP;
-  const size_t key_lds = d.oct_global_keys ? 0 : 6 * (size_t)CAND_CAP;
+  const size_t key_lds = d.oct_global_keys ? 0 : 6 * (size_t)oct_key_slots(CAND_CAP);
   if (4 * (size_t)(d.oct_max_cells + 8) + key_lds > (size_t)OCT_LDS_BUDGET)
     return plan_fail(err, SSX_ERR_UNSUPPORTED, "ssx_orb: %d grid cells on one level exceed the octree workgroup's LDS", d.oct_max_cells);
   d.oct_global_tab = (size_t)OCT_NODE_BYTES * d.oct_ln + 4 * (size_t)(d.oct_max_cells + 8) + key_lds > (size_t)OCT_LDS_BUDGET;
-  d.oct_stride = ((d.oct_global_keys ? 6 * (size_t)CAND_CAP_BIG : 0) + (d.oct_global_tab ? (size_t)OCT_NODE_BYTES * d.oct_ln : 0) + 255) & ~size_t(255);
+  d.oct_stride = ((d.oct_global_keys ? 6 * (size_t)oct_key_slots(CAND_CAP_BIG) : 0) + (d.oct_global_tab ? (size_t)OCT_NODE_BYTES * d.oct_ln : 0) + 255) & ~size_t(255);
   if (!d.oct_global_keys && !d.oct_global_tab) d.oct_stride = 0;
   return SSX_OK;
 }
@@ -1299,8 +1310,8 @@ void plan_arena(OrbPlan& p)
   p.arena_bytes = lay.off;
 }
 
-// The plan of a key.  Of several reasons to refuse a key the first in this order is reported: a level's budget, the octree's LDS,
-// the resize scale, a grid cell larger than the FAST tile.
+// The plan of a key.  Of several reasons to refuse a key the first in this order is reported: a level's budget, a level's root nodes,
+// the octree's LDS, the resize scale, a grid cell larger than the FAST tile.
 ssx_status build_plan(const PlanKey& k, OrbPlan& p, char* err)
 {
   ssx_status st = plan_levels(k, p, err);
@@ -1926,6 +1937,73 @@ ssx_status ssx_orb_stage_candidates(ssx_ctx* ctx, int32_t image, int32_t level, 
     }
   *n = m;
   return (out && m > cap) ? SSX_ERR_CAPACITY : SSX_OK;
+}
+
+// k_octree on the caller's candidates (include/ssx_test_hooks.h): the plan and the arena of the entry points, the cell lists written
+// as k_fast_cells would have left them, launch_octree as the pipeline calls it
+ssx_status ssx_orb_debug_octree(ssx_ctx* ctx, int32_t rows, int32_t cols, int32_t images, const ssx_orb_params* prm, int32_t detect_only, int32_t n,
+                                const int32_t* image, const int32_t* level, const int32_t* x, const int32_t* y, const int32_t* response,
+                                int32_t* lvl_ncand, int32_t* sel_count, uint32_t* sel, int32_t* status)
+{
+  if (!ctx) return SSX_ERR_INVALID_ARG;
+  if (!prm || n < 0 || (n > 0 && (!image || !level || !x || !y || !response))) {
+    ctx->set_error("ssx_orb_debug_octree: missing parameters or candidate arrays, or a negative count");
+    return SSX_ERR_INVALID_ARG;
+  }
+  ssx_status st = plan(ctx, rows, cols, images, *prm, false, detect_only != 0);
+  if (st != SSX_OK) return st;
+  const OrbDev& d = ctx->orb->dev;
+  const int nl = d.detect_only ? 1 : d.nlevels;
+  std::vector<Cell> cells;   // (the plan's own cell table: make_cells level by level, as plan_cells calls it)
+  for (int l = 0; l < d.nlevels; ++l) make_cells(d.lvl_rows[l], d.lvl_cols[l], l, cells);
+  const size_t n_slots = (size_t)d.I * std::max(d.n_cells, 1);
+  std::vector<int> cnt(n_slots, 0);
+  std::vector<uint32_t> cand(n_slots * CELL_CAP, 0u);
+  int last = 0;   // candidates come cell by cell: the previous candidate's cell is tried first
+  for (int i = 0; i < n; ++i) {
+    if (image[i] < 0 || image[i] >= d.I || level[i] < 0 || level[i] >= nl) {
+      ctx->set_error("ssx_orb_debug_octree: candidate %d: image %d / level %d out of range (%d images, %d levels)", i, image[i], level[i], d.I, nl);
+      return SSX_ERR_INVALID_ARG;
+    }
+    if (x[i] < 0 || x[i] > 4095 || y[i] < 0 || y[i] > 4095) {
+      ctx->set_error("ssx_orb_debug_octree: candidate %d: coordinate (%d, %d) outside 0..4095", i, x[i], y[i]);
+      return SSX_ERR_INVALID_ARG;
+    }
+    if (response[i] < 1 || response[i] > 255) { ctx->set_error("ssx_orb_debug_octree: candidate %d: response %d outside 1..255", i, response[i]); return SSX_ERR_INVALID_ARG; }
+    // k_fast_cells: a cell yields the pixels of its ROI but for a 3-px frame, at ROI-local coordinates + (ox, oy)
+    const int c0 = d.lvl_cell0[level[i]], c1 = d.lvl_cell0[level[i] + 1];
+    auto holds = [&](int c) {
+      const Cell& q = cells[c];
+      return x[i] >= q.ox + 3 && x[i] < q.ox + q.w - 3 && y[i] >= q.oy + 3 && y[i] < q.oy + q.h - 3;
+    };
+    int cell = -1;
+    if (last >= c0 && last < c1 && holds(last)) cell = last;
+    for (int c = c0; c < c1 && cell < 0; ++c) if (holds(c)) cell = c;
+    if (cell < 0) { ctx->set_error("ssx_orb_debug_octree: candidate %d: (%d, %d) lies in no grid cell of level %d", i, x[i], y[i], level[i]); return SSX_ERR_INVALID_ARG; }
+    last = cell;
+    const size_t slot = (size_t)image[i] * d.n_cells + cell;
+    if (cnt[slot] >= CELL_CAP) {
+      ctx->set_error("ssx_orb_debug_octree: candidate %d: more than %d candidates in cell %d of level %d", i, CELL_CAP, cell - c0, level[i]);
+      return SSX_ERR_INVALID_ARG;
+    }
+    cand[slot * CELL_CAP + cnt[slot]++] = (uint32_t)x[i] | ((uint32_t)y[i] << 12) | ((uint32_t)response[i] << 24);
+  }
+  hipStream_t s = ctx->stream;
+  const size_t IL = (size_t)d.I * d.nlevels;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SSX_HIP_TRY(ctx, hipMemsetAsync(d.status, 0, sizeof(int) * d.I, s));
+  SSX_HIP_TRY(ctx, hipMemsetAsync(d.lvl_ncand, 0xFF, sizeof(int) * IL, s));   // (-1: what the kernel leaves unwritten shows)
+  SSX_HIP_TRY(ctx, hipMemsetAsync(d.sel_count, 0xFF, sizeof(int) * IL, s));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(d.cell_count, cnt.data(), sizeof(int) * n_slots, hipMemcpyHostToDevice, s));
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(d.cell_cand, cand.data(), sizeof(uint32_t) * n_slots * CELL_CAP, hipMemcpyHostToDevice, s));
+  launch_octree(d, s);
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  if (lvl_ncand) SSX_HIP_TRY(ctx, hipMemcpyAsync(lvl_ncand, d.lvl_ncand, sizeof(int) * IL, hipMemcpyDeviceToHost, s));
+  if (sel_count) SSX_HIP_TRY(ctx, hipMemcpyAsync(sel_count, d.sel_count, sizeof(int) * IL, hipMemcpyDeviceToHost, s));
+  if (sel) SSX_HIP_TRY(ctx, hipMemcpyAsync(sel, d.sel, sizeof(uint32_t) * IL * SEL_CAP, hipMemcpyDeviceToHost, s));
+  if (status) SSX_HIP_TRY(ctx, hipMemcpyAsync(status, d.status, sizeof(int) * d.I, hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  return SSX_OK;
 }
 
 #endif  // SSX_NO_TEST_HOOKS

@@ -12,10 +12,13 @@ namespace ssxorb {
 constexpr int MAX_LEVELS = 8;
 constexpr int CELL_CAP = 256;      // candidates kept per grid cell (31x32 interior: NMS leaves < 250)
 constexpr int CAND_CAP = 16384;    // candidates per (image, level) the octree keeps in LDS (16 per thread)
-constexpr int CAND_CAP_BIG = 65536;  // ... and in global scratch for larger images (64 per thread)
+constexpr int CAND_CAP_BIG = 65535;  // ... and in global scratch for larger images (64 per thread): the most a 16-bit node count holds
 constexpr int SEL_CAP = 4096;      // selected keypoints per (image, level)
 constexpr int EDGE_THRESHOLD = 19; // orbextractor.cpp:13
 constexpr int OCT_THREADS = 1024;
+constexpr int OCT_MAX_ROOTS = 64;  // root nodes (nIni, a level's width / height rounded) of k_octree: one wave places them; more is refused by the plan
+// key slots behind a candidate capacity: whole slots-per-thread rows of the [slot][thread] layout (also keeps what follows the keys aligned)
+constexpr int oct_key_slots(int cap) { return (cap + OCT_THREADS - 1) / OCT_THREADS * OCT_THREADS; }
 
 struct Cell {
   int16_t x0, y0;   // ROI origin in the level image

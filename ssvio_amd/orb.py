@@ -134,6 +134,26 @@ class ORBextractor:
                                                              out.ctypes.data_as(C.c_void_p), C.byref(n)))
         return out[:n.value].copy()
 
+    def debug_octree(self, rows, cols, cand, images=1, detect_only=False):
+        """ssx_orb_debug_octree: k_octree on made candidates.  cand: int32 [n, 5] rows (image, level, x, y, response), x / y relative
+        to the 16-px border.  -> dict(lvl_ncand [images, L], sel_count [images, L], status [images], sel: per (image, level) an int
+        array [sel_count, 3] of (x, y, response) in list order), L = 1 for detect_only else nlevels."""
+        cand = np.ascontiguousarray(cand, dtype=np.int32).reshape(-1, 5)
+        cols5 = [np.ascontiguousarray(cand[:, k]) for k in range(5)]
+        L = 1 if detect_only else self.prm.nlevels
+        if not (1 <= images <= 1 << 16 and 1 <= L <= 8):   # (the plan refuses these; the output arrays below are sized by them)
+            raise ValueError("images / nlevels out of range")
+        ncand = np.zeros((images, L), np.int32); count = np.zeros((images, L), np.int32)
+        sel = np.zeros((images, L, 4096), np.uint32); status = np.zeros(images, np.int32)
+        f = self.ctx.lib.ssx_orb_debug_octree
+        f.restype = C.c_int32
+        f.argtypes = [C.c_void_p] + [C.c_int32] * 3 + [C.POINTER(OrbParams)] + [C.c_int32] * 2 + [i32_p] * 7 +[C.POINTER(C.c_uint32), i32_p]
+        self.ctx.check(f(self.ctx.handle, rows, cols, images, C.byref(self.prm), int(detect_only), len(cand), *[ptr(a, i32_p) for a in cols5],
+                         ptr(ncand, i32_p), ptr(count, i32_p), sel.ctypes.data_as(C.POINTER(C.c_uint32)), ptr(status, i32_p)))
+        lists = [[np.stack([s[:max(c, 0)] & 0xFFF, (s[:max(c, 0)] >> 12) & 0xFFF, s[:max(c, 0)] >> 24], axis=1).astype(np.int32)
+                  for s, c in zip(sel[i], count[i])] for i in range(images)]
+        return dict(lvl_ncand=ncand, sel_count=count, status=status, sel=lists)
+
 
 def match_params(band_px=2.0, min_disp=0.0, max_disp=120.0, max_dist=80, max_octave_diff=1, scale_factor=1.2):
     return MatchParams(band_px, min_disp, max_disp, max_dist, max_octave_diff, scale_factor)

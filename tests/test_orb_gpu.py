@@ -355,7 +355,7 @@ def test_matcher_and_triangulation_edge_cases(ctx, po, pair_small):
 
 def test_other_image_sizes(ctx, po):
     """641x479 (octree keys in LDS, <= 16384 candidates per level) and 1280x720 / 1920x1080 (keys in the global scratch
-    block, <= 65536 candidates per level) are all bit-exact"""
+    block, <= 65535 candidates per level) are all bit-exact"""
     for h, w, nb in ((479, 641, 1500), (720, 1280, 6000), (1080, 1920, 12000)):
         L = make_stereo_pair(seed=2, h=h, w=w, n_blobs=nb)[0]
         gk, gd = sorb.ORBextractor(ctx, nfeatures=2000).DetectAndCompute(L)

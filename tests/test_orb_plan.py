@@ -52,6 +52,27 @@ def test_plan_refusals_and_their_order(lib, which):
     assert all(d == 0 for d in p.digest) and p.arena_bytes == 0
 
 
+def test_plan_refuses_more_octree_roots_than_the_kernel_places(lib):
+    """k_octree places at most 64 root nodes (nIni = a level's (cols - 32) / (rows - 32), rounded); a level with grid cells and more
+    roots came back empty and silent, so the plan refuses the key, naming the level and its aspect.  62 rows leave 30: nIni 64 up to
+    1966 columns (1934 / 30 = 64.47), 65 from 1967 (64.5 rounds up), 66 at 2000.  A level WITHOUT cells (the pyramid's upper levels
+    here, 52 rows and less) refuses nothing, and a tall level (nIni 0: 300 x 45 of tests/test_orb_gpu.py::test_degenerate_small_images)
+    still plans and selects nothing, as in the reference."""
+    for cols, n_ini in ((1952, 64), (1966, 64), (1967, 65), (2000, 66)):
+        for kw in (dict(detect=1, nfeatures=100), dict(nfeatures=500, nlevels=8)):
+            p = plan_info(lib, case(62, cols, **kw))
+            if n_ini <= 64:
+                assert p.status == _lib.SSX_OK, p.error
+                assert 1 <= p.lvl_cell0[1] <= (cols - 32) // 30 and p.out_cap >= 4 * n_ini + 4
+                assert all(p.lvl_cell0[l] == p.lvl_cell0[1] for l in range(1, MAX_LEVELS + 1))        # cells on level 0 only
+            else:
+                assert p.status == _lib.SSX_ERR_UNSUPPORTED
+                assert p.error.decode() == "ssx_orb: level 0 (%dx62) is %d times as wide as high: the octree takes at most 64 root nodes" % (cols, n_ini)
+                assert all(d == 0 for d in p.digest) and p.arena_bytes == 0
+    assert plan_info(lib, case(300, 45, nlevels=6, nfeatures=300)).status == _lib.SSX_OK
+    assert plan_info(lib, case(45, 300, nlevels=6, nfeatures=300)).status == _lib.SSX_OK
+
+
 def test_plan_rejections_of_the_misuse_test(lib):
     """tests/test_misuse_gpu.py::test_orb_entry_points_reject_bad_arguments: 0 levels, scale < 1, a negative budget, too many levels
     (ssx_orb_extract on 100 x 160) and an absurd height (ssx_orb_detect)"""

@@ -50,13 +50,16 @@ FAILING = {
     "budget_big":   (case(100, 160, nfeatures=4089, nlevels=3), INVALID, "ssx_orb: unsupported parameters"),
     "images_0":     (case(100, 160, I=0), INVALID, "ssx_orb: unsupported parameters"),
     "level_cap":    (case(**K, nfeatures=20000, unchecked=1), UNSUPPORTED, "ssx_orb: 4343 features on level 0 exceed"),
+    "octree_roots": (case(62, 2000, detect=1, nfeatures=100), UNSUPPORTED, "ssx_orb: level 0 (2000x62) is 66 times as wide as high"),
     "octree_lds":   (case(8000, 8000, detect=1, nfeatures=100, unchecked=1), UNSUPPORTED, "ssx_orb: 66049 grid cells on one level exceed"),
     "resize_scale": (case(400, 4000, nlevels=2, scale=100.0), UNSUPPORTED, "ssx_orb: pyramid scale factor 100 is too large"),
     # two reasons at once: the earlier one in plan()'s order is reported
     "image+params":        (case(30, 160, nlevels=0), INVALID, "ssx_orb: image 160x30 outside"),
     "params+resize":       (case(400, 4000, nlevels=2, scale=100.0, nfeatures=0), INVALID, "ssx_orb: unsupported parameters"),
     "level_cap+octree":    (case(8000, 8000, nfeatures=20000, nlevels=2, unchecked=1), UNSUPPORTED, "ssx_orb: 10909 features on level 0 exceed"),
-    "level_cap+resize":    (case(400, 4000, nfeatures=20000, nlevels=2, scale=100.0, unchecked=1), UNSUPPORTED, "features on level 0 exceed"),
+    "level_cap+roots":     (case(62, 2000, nfeatures=20000, nlevels=2, unchecked=1), UNSUPPORTED, "features on level 0 exceed"),
+    "roots+resize":        (case(62, 2000, nlevels=2, scale=100.0), UNSUPPORTED, "times as wide as high"),
+    "level_cap+resize":   (case(400, 4000, nfeatures=20000, nlevels=2, scale=100.0, unchecked=1), UNSUPPORTED, "features on level 0 exceed"),
     "octree+resize":       (case(8000, 8000, nlevels=2, scale=100.0, unchecked=1), UNSUPPORTED, "grid cells on one level exceed"),
 }
 
