@@ -10,7 +10,13 @@
 namespace ssxorb {
 
 constexpr int MAX_LEVELS = 8;
-constexpr int CELL_CAP = 256;      // candidates kept per grid cell (31x32 interior: NMS leaves < 250)
+// candidates kept per grid cell.  No two survivors of the strict 3x3 NMS touch, so a cell whose FAST interior is iw x ih px keeps at
+// most ceil(iw / 2) * ceil(ih / 2): 256 for a 31 x 32 interior.  The grid allows more -- a cell is 30 .. 59 px a side (wCell =
+// ceil(width / floor(width / 30)): at most 45 once a level has two columns of cells, up to 59 with one), i.e. up to 30 * 30 -- but
+// images stay below 256 (uniform noise at threshold 0: 194 in a 32 x 44 cell, where the bound is 352; isolated pixels every 4 px, the
+// densest lattice of corners that do not suppress each other: one per 16 px, at most 225 in the largest cell).  A cell with more
+// raises the candidate bit of the status word (value 1) and the call returns SSX_ERR_CAPACITY: nothing is dropped silently.
+constexpr int CELL_CAP = 256;
 constexpr int CAND_CAP = 16384;    // candidates per (image, level) the octree keeps in LDS (16 per thread)
 constexpr int CAND_CAP_BIG = 65535;  // ... and in global scratch for larger images (64 per thread): the most a 16-bit node count holds
 constexpr int SEL_CAP = 4096;      // selected keypoints per (image, level)

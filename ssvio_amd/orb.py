@@ -16,10 +16,13 @@ from ._lib import KP_DTYPE, Context, MatchParams, OrbParams, StereoFrameOut, Ste
 
 
 def _img(a):
-    a = np.ascontiguousarray(a, dtype=np.uint8)
+    a = np.asarray(a)
     if a.ndim != 2:
         raise ValueError("CV_8UC1 image expected")   # the reference asserts image.type() == CV_8UC1
-    return a
+    # rows that lie pitched in a larger buffer (a cv::Mat with step > cols, a ROI) go to the library as they lie: it takes a row stride
+    if a.dtype == np.uint8 and a.strides[1] == 1 and a.strides[0] >= a.shape[1]:
+        return a
+    return np.ascontiguousarray(a, dtype=np.uint8)
 
 
 class ORBextractor:
@@ -74,8 +77,11 @@ class ORBextractor:
         arr = (Job * n)()
         keep, outs = [], []
         cap = self._cap()
+        images = [_img(im) for im in images]
+        if len({im.strides[0] for im in images}) > 1:   # the call takes one row stride for all its images
+            images = [np.ascontiguousarray(im) for im in images]
         for i, (im, bx) in enumerate(zip(images, boxes_list)):
-            im = _img(im); bx = np.ascontiguousarray(bx, dtype=np.int32).reshape(-1, 4)
+            bx = np.ascontiguousarray(bx, dtype=np.int32).reshape(-1, 4)
             kps = np.zeros(cap, dtype=KP_DTYPE); cnt = (C.c_int32 * 1)(0)
             a = arr[i]
             a.img = ptr(im, u8_p); a.stride = im.strides[0]; a.boxes = bx.ctypes.data_as(C.POINTER(C.c_int32)); a.n_boxes = len(bx)
@@ -244,6 +250,8 @@ class _FrameBuffers:
 def stereo_frame(ctx: Context, imgL, imgR, orb: OrbParams | None = None, mp=None, rig=None, T_wc=None):
     """extract L+R, row-band match, triangulate -- one call (ssx_stereo_frame)."""
     imgL = _img(imgL); imgR = _img(imgR)
+    if imgL.strides != imgR.strides:                 # one row stride for the pair
+        imgL = np.ascontiguousarray(imgL); imgR = np.ascontiguousarray(imgR)
     assert imgL.shape == imgR.shape and imgL.strides == imgR.strides
     orb = orb or OrbParams(2000, 1.2, 8, 20, 7)
     mp = mp or match_params(scale_factor=orb.scale_factor)
