@@ -613,15 +613,27 @@ SSX_API ssx_status ssx_lk_track(ssx_ctx* ctx, const uint8_t* prev, int32_t prev_
  * the previous image is the `next` image of the last ssx_lk_track / ssx_lk_track_next call on this context, whose
  * pyramid is still on the device -- only the new image is uploaded and reduced. Same results as ssx_lk_track on the
  * two images; SSX_ERR_INVALID_ARG when there is no such call or the size / window / max_level changed. A context
- * holds one chain: keep the left-right stereo LK calls of a keyframe on a second context. */
+ * holds one chain: keep the left-right stereo LK calls of a keyframe on a second context.
+ * A context holds chains for ONE key (rows, cols, win, max_level) at a time.  A successful call with another key re-plans the
+ * context for that key and DROPS EVERY CHAIN it held, on all slots: the next chained call with the earlier key is refused
+ * (SSX_ERR_INVALID_ARG, nothing is run, next_pts stays as passed) until a call with both images has started a new chain.
+ * Streams of different image sizes therefore need a context per size. */
 SSX_API ssx_status ssx_lk_track_next(ssx_ctx* ctx, const uint8_t* next, int32_t next_stride, int32_t rows,
                                      int32_t cols, int32_t n, const float* prev_pts, float* next_pts,
                                      uint8_t* status, float* err, const ssx_lk_params* prm, int32_t* top_level);
 /* n_jobs tracking problems in ONE call -- one frame of each of n_jobs streams (BASELINE configs[4]): every kernel of the tracker runs
  * once for all jobs.  A job names the SLOT of the context that holds its pyramids (0 .. 4095; ssx_lk_track / _next use slot 0; a
  * slot at most once per call); prev == NULL chains it to the slot's last job like ssx_lk_track_next.  All jobs share rows x cols
- * and prm.  images_on_device != 0: the image pointers are readable by the GPU -- device memory, or pinned host memory
- * (hipHostMalloc / hipHostRegister) that the level-0 kernel reads over PCIe -- and nothing is staged; 0: ordinary host memory.
+ * and prm -- the context's one key (see ssx_lk_track_next: a call with another size drops the chains of ALL slots, so the jobs of
+ * streams with different image sizes go to different contexts, not to one context in turn).
+ * images_on_device != 0: the image pointers are readable by the GPU -- device memory, or pinned host memory
+ * (hipHostMalloc / hipHostRegister) -- and nothing is staged; 0: ordinary host memory.  The images are then read where they lie,
+ * which asks of the caller: (1) every image, rows x stride bytes from its pointer up to the end of its last row, lies inside ONE
+ * allocation the HIP runtime knows (hipMalloc, hipHostMalloc / ssx_host_alloc, hipHostRegister), readable from this context's
+ * device; (2) it stays allocated and unchanged until the call returns.  The images of different jobs may be separate allocations
+ * anywhere.  When the `next` images ascend at a constant distance AND the runtime confirms that the first and the last lie in one
+ * allocation that covers the whole range (a pinned arena with a slice per stream), that range crosses PCIe in one copy, bytes
+ * between the images included; images allocated one by one are copied or read one by one, however close they lie.
  * Per job the bits of ssx_lk_track / ssx_lk_track_next. */
 typedef struct ssx_lk_job {
   int32_t slot;

@@ -144,11 +144,21 @@ typedef struct ssx_lk_job_facts {
   int64_t next_off;
 } ssx_lk_job_facts;
 /* needs no GPU.  planned_key: rows, cols, win, max_level of the context's last successful call (NULL: those of this call);
- * slot_flags: per job its slot's state before the call, bits as above; next0_is_host: jobs[0].next is host memory (looked at only
- * where the entry points would ask the runtime).  Returns out->status. */
+ * slot_flags: per job its slot's state before the call, bits as above; call_facts: what the entry points would learn from the
+ * runtime about the image pointers (each looked at only where they would ask) -- bit 0 jobs[0].next is host memory, bit 1 the
+ * `next` images do NOT lie in one allocation (so 0 and 1 mean what they meant when the argument was next0_is_host alone: pointers
+ * that pass the arena's arithmetic are one arena).  Returns out->status. */
+enum { SSX_LK_FACT_NEXT0_IS_HOST = 1, SSX_LK_FACT_SEVERAL_ALLOCATIONS = 2 };
 SSX_API ssx_status ssx_lk_debug_plan(int32_t rows, int32_t cols, int32_t win, int32_t max_level, const int32_t* planned_key, int32_t n_jobs,
-                                     const ssx_lk_job_facts* jobs, const uint8_t* slot_flags, int32_t images_on_device, int32_t next0_is_host,
+                                     const ssx_lk_job_facts* jobs, const uint8_t* slot_flags, int32_t images_on_device, int32_t call_facts,
                                      ssx_lk_call_info* out);
+/* which intake (SSX_LK_*) ssx_lk_track_batch would take for these jobs' REAL image pointers on this device; arena_arithmetic
+ * (optional): 1 when the `next` pointers pass the arena's arithmetic (ascending, equal strides, at least an image apart, within
+ * 2 x jobs images) -- then SSX_LK_ARENA or not is the runtime's answer about the allocation.  Only the `next` pointers and strides
+ * of the jobs are looked at.  Makes the runtime's pointer queries of the entry point and nothing else: no copy, no launch, and the
+ * context (its geometry, slots, last call) stays as it is. */
+SSX_API ssx_status ssx_lk_debug_intake(ssx_ctx* ctx, int32_t n_jobs, const ssx_lk_job* jobs, int32_t rows, int32_t cols, const ssx_lk_params* prm,
+                                       int32_t images_on_device, int32_t* intake, int32_t* arena_arithmetic);
 /* the same struct for the last successful LK call of ctx (status SSX_OK, no error text) */
 SSX_API ssx_status ssx_lk_debug_last_call(ssx_ctx* ctx, ssx_lk_call_info* out);
 

@@ -621,14 +621,26 @@ ssx_status check_jobs(int nj, const ssx_lk_job* jobs, const LkKey& key, bool key
 bool lk_use_fused(const LkGeom& g, int nj) { return g.fused_ok && nj <= FUSED_MAX_JOBS; }
 size_t image_span(const LkKey& k, int stride) { return (size_t)(k.rows - 1) * (size_t)stride + (size_t)k.cols; }
 
-// How the level-0 images reach the device, from the strides, the distances of the `next` pointers and whether jobs[0].next is host memory:
+// What the runtime knows about the caller's image pointers and arithmetic does not (lk_facts asks, and only where the answer decides;
+// ssx_lk_debug_plan is told):
+//   next0_is_host    jobs[0].next is host memory
+//   one_allocation   the `next` images, jobs[0].next up to the end of the last one, lie in ONE allocation
+struct LkFacts { bool next0_is_host = false, one_allocation = true; };
+
+// How the level-0 images reach the device, from the strides, the distances of the `next` pointers and the facts:
 // LK_STAGED   host images: rows packed into the pinned io block, which goes over in one copy with the table and the points
-// LK_ARENA    the `next` images lie at a constant distance (one pinned arena, a slice per stream: host/stream_batcher.cpp; gaps: streams
-//             that sit this call out): ONE copy of *arena_bytes from jobs[0].next on the DMA engine, instead of reads through PCIe
+// LK_ARENA    the `next` images lie at a constant distance IN ONE ALLOCATION (one pinned arena, a slice per stream:
+//             host/stream_batcher.cpp; gaps: streams that sit this call out): ONE copy of *arena_bytes from jobs[0].next on the DMA
+//             engine, instead of reads through PCIe.  Images allocated one by one can stand just like that -- ascending, equally
+//             spaced, close -- and one copy over them would cross whatever lies between two allocations: without the runtime's word
+//             (one_allocation) there is no arena.
 // LK_EACH     host memory (pinned, no arena) in front of k_lk_pyramid, which reads level 0 about 2.5 times: one DMA copy per image
 // LK_IN_PLACE otherwise: read where they lie
-LkIntake choose_intake(const LkKey& k, int nj, const ssx_lk_job* jobs, bool images_on_device, bool use_fused, bool next0_is_host, size_t* arena_bytes)
+// arena_arithmetic (optional): the pointers pass the arena's arithmetic, whatever the facts say
+LkIntake choose_intake(const LkKey& k, int nj, const ssx_lk_job* jobs, bool images_on_device, bool use_fused, const LkFacts& facts, size_t* arena_bytes,
+                       bool* arena_arithmetic = nullptr)
 {
+  if (arena_arithmetic) *arena_arithmetic = false;
   *arena_bytes = 0;
   if (!images_on_device) return LK_STAGED;
   const size_t span = image_span(k, jobs[0].next_stride);
@@ -636,8 +648,11 @@ LkIntake choose_intake(const LkKey& k, int nj, const ssx_lk_job* jobs, bool imag
   for (int j = 1; ok && j < nj; ++j)
     ok = jobs[j].next_stride == jobs[0].next_stride && jobs[j].next > jobs[j - 1].next && (size_t)(jobs[j].next - jobs[j - 1].next) >= span;
   const size_t range = ok ? (size_t)(jobs[nj - 1].next - jobs[0].next) + span : 0;
-  if (ok && range <= 2 * (size_t)nj * span) { *arena_bytes = range; return LK_ARENA; }
-  return use_fused && next0_is_host ? LK_EACH : LK_IN_PLACE;
+  if (ok && range <= 2 * (size_t)nj * span) {
+    if (arena_arithmetic) *arena_arithmetic = true;
+    if (facts.one_allocation) { *arena_bytes = range; return LK_ARENA; }
+  }
+  return use_fused && facts.next0_is_host ? LK_EACH : LK_IN_PLACE;
 }
 
 // the io block, each span stated once: [job table | (staged images) | prev points | next points] | status | err | (device images)
@@ -691,12 +706,12 @@ void plan_launches(const LkDev& d, int nj, bool any_fresh, int max_n, LkCall& c)
 // One tracking CALL of nj jobs (ssx_lk_job) as a value.  A job with prev == nullptr is chained: its previous image is the next image of
 // its slot's last job, whose pyramid is still there -- the slot's two pyramids swap roles (after.flip) and only the new image is read
 // and reduced.  A fresh job overwrites both pyramids, so it takes the slot as carved (flip = false) whatever the slot held.
-LkCall build_call(const LkKey& key, const LkGeom& g, int nj, const ssx_lk_job* jobs, const LkSlotState* before, bool images_on_device, bool next0_is_host)
+LkCall build_call(const LkKey& key, const LkGeom& g, int nj, const ssx_lk_job* jobs, const LkSlotState* before, bool images_on_device, const LkFacts& facts)
 {
   LkCall c;
   c.use_fused = lk_use_fused(g, nj);
   c.scharr_now = !c.use_fused;                                         // (the derivative images of the previous image: per-level kernel, this call)
-  c.intake = choose_intake(key, nj, jobs, images_on_device, c.use_fused, next0_is_host, &c.arena_bytes);
+  c.intake = choose_intake(key, nj, jobs, images_on_device, c.use_fused, facts, &c.arena_bytes);
   c.jobs.resize(nj);
   bool any_fresh = false;
   int max_n = 0;
@@ -728,15 +743,28 @@ ssx_status lk_geometry(ssx_ctx* ctx, LkWorkspace* ws, const LkKey& key, char* er
   return SSX_OK;
 }
 
-// step 3: is jobs[0].next host memory?  The one question to the runtime, asked only where the answer decides the intake.
-bool lk_next0_is_host(const LkKey& key, const LkGeom& g, int nj, const ssx_lk_job* jobs, bool images_on_device)
+// step 3: the questions to the runtime, each asked only where its answer decides the intake.  Do the `next` images lie in one
+// allocation?  Only where the pointers pass the arena's arithmetic: the allocation of the first image must be that of the last one and
+// reach to its end (a runtime that does not know the pointers: no arena).  Is jobs[0].next host memory?  Only where k_lk_pyramid runs
+// and there is no arena.  Both are look-ups in the runtime's table of allocations: no copy, no launch, no synchronisation.
+LkFacts lk_facts(const LkKey& key, const LkGeom& g, int nj, const ssx_lk_job* jobs, bool images_on_device)
 {
+  LkFacts f;
   size_t arena = 0;
-  if (!lk_use_fused(g, nj) || choose_intake(key, nj, jobs, images_on_device, true, false, &arena) != LK_IN_PLACE) return false;
+  if (choose_intake(key, nj, jobs, images_on_device, true, f, &arena) == LK_ARENA) {
+    const uint8_t* const last_end = jobs[nj - 1].next + image_span(key, jobs[nj - 1].next_stride);
+    hipDeviceptr_t base0 = nullptr, base1 = nullptr;
+    size_t size0 = 0, size1 = 0;
+    f.one_allocation = hipMemGetAddressRange(&base0, &size0, (hipDeviceptr_t)jobs[0].next) == hipSuccess &&
+                       hipMemGetAddressRange(&base1, &size1, (hipDeviceptr_t)jobs[nj - 1].next) == hipSuccess && base0 == base1 &&
+                       (const uint8_t*)base0 <= jobs[0].next && last_end <= (const uint8_t*)base0 + size0;
+    if (!f.one_allocation) (void)hipGetLastError();
+  }
+  if (!lk_use_fused(g, nj) || choose_intake(key, nj, jobs, images_on_device, true, f, &arena) != LK_IN_PLACE) return f;
   hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, jobs[0].next) == hipSuccess) return at.type == hipMemoryTypeHost;
-  (void)hipGetLastError();
-  return false;
+  if (hipPointerGetAttributes(&at, jobs[0].next) == hipSuccess) f.next0_is_host = at.type == hipMemoryTypeHost;
+  else (void)hipGetLastError();
+  return f;
 }
 
 // step 5: the slots' two pyramids and derivative images, each slot carved from a buffer of its own; the io block and its pinned mirror
@@ -877,8 +905,8 @@ ssx_status lk_run(ssx_ctx* ctx, int nj, const ssx_lk_job* jobs, int32_t rows, in
   ssx_status st = check_jobs(nj, jobs, key, ws->planned(key), before.data(), prev_required, err);
   if (st == SSX_OK) st = lk_geometry(ctx, ws, key, err);               // (a new geometry: no job is chained, and `before` no longer matters)
   if (st != SSX_OK) { if (err[0]) ctx->set_error("%s", err); return st; }
-  const bool next0_is_host = lk_next0_is_host(key, ws->geom, nj, jobs, images_on_device);
-  LkCall call = build_call(key, ws->geom, nj, jobs, before.data(), images_on_device, next0_is_host);
+  const LkFacts facts = lk_facts(key, ws->geom, nj, jobs, images_on_device);
+  LkCall call = build_call(key, ws->geom, nj, jobs, before.data(), images_on_device, facts);
   if ((st = lk_reserve(ctx, ws, nj, jobs, call)) != SSX_OK) return st;
   lk_fill(ws, nj, jobs, call);
   if ((st = lk_enqueue(ctx, ws, nj, jobs, prm, call)) != SSX_OK) return st;
@@ -989,7 +1017,7 @@ static void lk_fill_info(const LkGeom& g, const LkCall& c, ssx_lk_call_info* out
 }
 
 ssx_status ssx_lk_debug_plan(int32_t rows, int32_t cols, int32_t win, int32_t max_level, const int32_t* planned_key, int32_t n_jobs,
-                             const ssx_lk_job_facts* facts, const uint8_t* slot_flags, int32_t images_on_device, int32_t next0_is_host,
+                             const ssx_lk_job_facts* facts, const uint8_t* slot_flags, int32_t images_on_device, int32_t call_facts,
                              ssx_lk_call_info* out)
 {
   if (!out || n_jobs < 1 || !facts || !slot_flags) return SSX_ERR_INVALID_ARG;
@@ -1012,7 +1040,28 @@ ssx_status ssx_lk_debug_plan(int32_t rows, int32_t cols, int32_t win, int32_t ma
   if (st == SSX_OK) st = build_geom(key, g, out->error);
   out->status = st;
   if (st != SSX_OK) return st;
-  lk_fill_info(g, build_call(key, g, n_jobs, jobs.data(), before.data(), images_on_device != 0, next0_is_host != 0), out);
+  const LkFacts f{(call_facts & SSX_LK_FACT_NEXT0_IS_HOST) != 0, (call_facts & SSX_LK_FACT_SEVERAL_ALLOCATIONS) == 0};
+  lk_fill_info(g, build_call(key, g, n_jobs, jobs.data(), before.data(), images_on_device != 0, f), out);
+  return SSX_OK;
+}
+
+ssx_status ssx_lk_debug_intake(ssx_ctx* ctx, int32_t n_jobs, const ssx_lk_job* jobs, int32_t rows, int32_t cols, const ssx_lk_params* prm_in,
+                               int32_t images_on_device, int32_t* intake, int32_t* arena_arithmetic)
+{
+  if (!ctx || n_jobs < 1 || !jobs || !intake) return SSX_ERR_INVALID_ARG;
+  for (int j = 0; j < n_jobs; ++j) if (!jobs[j].next || jobs[j].next_stride < cols) return SSX_ERR_INVALID_ARG;
+  ssx_lk_params prm;
+  if (prm_in) prm = *prm_in; else ssx_lk_default_params(&prm);
+  const LkKey key{rows, cols, prm.win, prm.max_level};
+  LkGeom g;                                                            // (a geometry of the hook's own: the context's stays as it is)
+  char err[LK_ERR] = {0};
+  const ssx_status st = build_geom(key, g, err);
+  if (st != SSX_OK) return st;
+  const LkFacts f = lk_facts(key, g, n_jobs, jobs, images_on_device != 0);
+  size_t arena = 0;
+  bool arithmetic = false;
+  *intake = choose_intake(key, n_jobs, jobs, images_on_device != 0, lk_use_fused(g, n_jobs), f, &arena, &arithmetic);
+  if (arena_arithmetic) *arena_arithmetic = arithmetic;
   return SSX_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstring>
 #include <functional>
+#include <map>
 #include <stdexcept>
 
 #include "../../include/ssx_shim.hpp"
@@ -21,7 +22,7 @@ struct StreamBatcher::Impl {
   // Request slots: k < S is stream k's own thread (one request at a time); S + k is the worker thread of stream k's backend when the
   // backend is asynchronous (Backend.Async: 1 -- it files window solves while the stream's thread goes on tracking).  A backend slot
   // rests in IDLE, which no dispatcher waits for.
-  Impl(int device_, int streams) : device(device_), S(streams), lk_ctx(device_), po_ctx(device_), ba_ctx(device_), det_ctx(device_), lks_ctx(device_),
+  Impl(int device_, int streams) : device(device_), S(streams), po_ctx(device_), ba_ctx(device_), det_ctx(device_),
                                    tri_ctx(device_), state(2 * (size_t)streams, St::RUNNING), lk_req(streams), lk_rows(streams, 0), lk_cols(streams, 0),
                                    po_req(streams), det_req(streams), det_prm(streams), tri_req(streams), ba_win(2 * (size_t)streams, nullptr),
                                    ba_res(2 * (size_t)streams, nullptr), loop_req(2 * (size_t)streams), call_req(2 * (size_t)streams, nullptr),
@@ -67,8 +68,29 @@ struct StreamBatcher::Impl {
     return db;
   }
 
-  // The streams' pinned image buffers are slices of ONE arena: buffer `which` of stream k at (which * S + k) * slice.  The `next`
-  // images of a cohort's LK jobs then lie at a constant distance and cross PCIe in one DMA copy (ssx_lk_track_batch).
+  // The LK contexts of ONE image size: `lk` for the frame-to-frame chains, `lks` for the left-right calls of a keyframe, slot k of
+  // either for stream k.  An LK context holds chains for one (rows, cols, window, max_level) at a time and a call of another size
+  // drops them all (include/ssx.h, ssx_lk_track_next), so the streams of a cohort that differ in image size (KITTI 00 at 1241 x 376
+  // beside KITTI 04 at 1226 x 370) cannot take turns on one context: every size has a pair of its own, made when its first request
+  // is served.  A cohort of n sizes costs n LK calls per frame instead of one; the streams of one size still travel together.
+  struct SizeCtx {
+    explicit SizeCtx(int device) : lk(device), lks(device) {}
+    ssx::Context lk, lks;
+  };
+  SizeCtx& ForSize(int rows, int cols)
+  {
+    std::lock_guard<std::mutex> lk(size_mu);        // (both dispatchers come here)
+    std::unique_ptr<SizeCtx>& p = size_ctx[{rows, cols}];
+    if (!p) p = std::make_unique<SizeCtx>(device);
+    return *p;
+  }
+
+  // The streams' pinned image buffers are slices of ONE arena: buffer `which` of stream k at (which * S + k) * slice, the slice sized
+  // by the stream that pins first.  The `next` images of a cohort's LK jobs then lie at a constant distance in one allocation and
+  // cross PCIe in one DMA copy (ssx_lk_track_batch).  In a cohort of several image sizes a stream with SMALLER images than the
+  // first one uses its slice all the same (the images of its size are then further apart than the one-copy rule allows and are read
+  // one by one); a stream with LARGER images gets nullptr and keeps two pinned buffers of its own (BatchedCompute::Pinned), which
+  // the library takes one by one wherever the allocator put them.
   uint8_t* PinSlice(int k, int which, size_t bytes)
   {
     std::lock_guard<std::mutex> lk(pin_mu);
@@ -78,7 +100,7 @@ struct StreamBatcher::Impl {
       pin_arena = static_cast<uint8_t*>(ssx_host_alloc(pin_slice * 2 * (size_t)S));
       if (!pin_arena) throw std::runtime_error("StreamBatcher: no pinned memory for the streams' images");
     }
-    if (need > pin_slice) return nullptr;           // (a stream with larger images than the first one: it keeps buffers of its own)
+    if (need > pin_slice) return nullptr;
     return pin_arena + ((size_t)which * S + k) * pin_slice;
   }
 
@@ -199,9 +221,10 @@ struct StreamBatcher::Impl {
           po_ctx.check(ssx_pose_only_opt_batch(po_ctx.get(), (int32_t)jobs.size(), jobs.data()));
         });
       } else {
-        // (jobs of one call share the image size: streams of another size go in a call of their own)
+        // (jobs of one call share the image size: the streams of another size go in a call of their own, on that size's context --
+        // their chains live there)
         for (const auto& g : Groups(who.size(), [&](size_t a, size_t b) { return lk_rows[who[a]] == lk_rows[who[b]] && lk_cols[who[a]] == lk_cols[who[b]]; }))
-          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) { LkCall(lk_ctx, who, sub); });
+          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) { LkCall(ForSize(lk_rows[who[sub[0]]], lk_cols[who[sub[0]]]).lk, who, sub); });
       }
       const double dt = std::chrono::duration<double>(clk::now() - tc0).count();
       lk.lock();
@@ -305,7 +328,7 @@ struct StreamBatcher::Impl {
         });
       } else if (kind == St::PENDING_LKS) {
         for (const auto& g : Groups(who.size(), [&](size_t a, size_t b) { return lk_rows[who[a]] == lk_rows[who[b]] && lk_cols[who[a]] == lk_cols[who[b]]; }))
-          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) { LkCall(lks_ctx, who, sub); });
+          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) { LkCall(ForSize(lk_rows[who[sub[0]]], lk_cols[who[sub[0]]]).lks, who, sub); });
       } else {
         // detection: the jobs of a call share image size, stride and extractor settings
         auto same = [&](size_t a, size_t b) {
@@ -341,7 +364,9 @@ struct StreamBatcher::Impl {
   uint8_t* pin_arena = nullptr;
   size_t pin_slice = 0;
   int device, S;
-  ssx::Context lk_ctx, po_ctx, ba_ctx, det_ctx, lks_ctx, tri_ctx;
+  ssx::Context po_ctx, ba_ctx, det_ctx, tri_ctx;
+  std::mutex size_mu;
+  std::map<std::pair<int, int>, std::unique_ptr<SizeCtx>> size_ctx;   // (rows, cols) -> that size's LK contexts
   std::mutex m;
   std::condition_variable cv_disp;
   struct Sleeper { std::mutex mu; std::condition_variable cv; bool done = false; };
@@ -551,15 +576,15 @@ class BatchedCompute final : public Compute {
     q.n = n; q.prev_pts = prev_pts.data(); q.next_pts = next_pts.data(); q.status = status.data(); q.err = nullptr;
     im_.lk_rows[k_] = next.rows; im_.lk_cols[k_] = next.cols;
     if (!temporal) {
-      // FindFeaturesInRight (frontend.cpp:346-428): left -> right of one frame, both pyramids built afresh, on the stereo LK context's
-      // slot of this stream
+      // FindFeaturesInRight (frontend.cpp:346-428): left -> right of one frame, both pyramids built afresh, on this stream's slot of
+      // its image size's stereo LK context
       if (prev.rows != next.rows || prev.cols != next.cols) throw std::invalid_argument("TrackLK: image sizes differ");
       q.prev = Pinned(prev, 0); q.prev_stride = prev.cols;
       q.next = Pinned(next, 1, q.prev); q.next_stride = next.cols;
       im_.SubmitAndWait(k_, St::PENDING_LKS);
       return;
     }
-    // the frame-to-frame chain: this stream's slot of the shared LK context keeps the pyramid of its last `next` image.  The new
+    // the frame-to-frame chain: this stream's slot of its image size's LK context keeps the pyramid of its last `next` image.  The new
     // image goes into the stream's pinned buffer (this thread copies it: S streams copy side by side) and is read from there by the
     // GPU -- no staging inside the batched call.
     const bool chained = prev.id != 0 && prev.id == chain_next_id_ && prev.rows == chain_rows_ && prev.cols == chain_cols_ && next.rows == prev.rows &&
@@ -671,6 +696,14 @@ void StreamBatcher::Finish(int k)
 {
   const int C = (int)impls_.size();
   if (k >= 0 && k < n_streams_) impls_[k % C]->SetState(k / C, St::DONE);
+}
+
+size_t StreamBatcher::PinnedSliceBytes(int k)
+{
+  if (k < 0 || k >= n_streams_) return 0;
+  Impl& im = *impls_[k % (int)impls_.size()];
+  std::lock_guard<std::mutex> lk(im.pin_mu);
+  return im.pin_slice;
 }
 
 void StreamBatcher::ResetStats()

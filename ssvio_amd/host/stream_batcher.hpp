@@ -19,6 +19,9 @@
 // vocabulary, each has its keyframe database there, and their steps go out as ssx_kfdb_process_keyframe_batch; the calls of a
 // correction are rare and are made by the dispatcher one at a time.
 //
+// A cohort may mix image sizes: an LK context holds chains for one size, so the batcher keeps LK contexts per (rows, cols) and a frame
+// costs one LK call per size; the streams of one size still share it.
+//
 // Dispatch order: pose-only before LK.  A stream that comes back from a keyframe is half a frame out of phase with the cohort; with
 // the pose-only batch served first the cohort arrives at its next LK request while the straggler still waits there, and they merge.
 #pragma once
@@ -59,6 +62,10 @@ class StreamBatcher {
   };
   Stats stats();
   void ResetStats();                                 // (after the streams' warm-up: the counters then describe the frames alone)
+
+  // the slice of the pinned image arena of stream k's cohort, in bytes: 0 until the cohort's first stream has pinned its first image
+  // (that stream's image size sets it, see Impl::PinSlice -- tests order the streams' first calls by it)
+  size_t PinnedSliceBytes(int k);
 
   struct Impl;
 

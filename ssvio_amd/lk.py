@@ -89,8 +89,10 @@ def _fill_job(a, j, next_ptr, next_stride, prev_ptr=None, prev_stride=0):
 
 class PreparedTrackBatch:
     """ssx_lk_track_batch with everything a C caller holds between frames prepared once: the job structs, the points, and the images in
-    PINNED memory (ssx_host_alloc) handed over with images_on_device = 1 -- what ssvio_amd/host/stream_batcher.cpp does per frame.
-    run() is the library call alone; outputs in .outs [(next_pts, status, err)] (the guesses are restored before every run)."""
+    PINNED memory handed over with images_on_device = 1 -- ONE arena (ssx_host_alloc) with a slice per job, as
+    ssvio_amd/host/stream_batcher.cpp keeps its streams' images, so that they cross in one copy (a pinned allocation per image is never
+    one copy, however the allocator places them: include/ssx.h).  run() is the library call alone; outputs in .outs
+    [(next_pts, status, err)] (the guesses are restored before every run)."""
 
     def __init__(self, ctx: Context, jobs, winSize=11, maxLevel=3, maxCount=30, epsilon=0.01, minEigThreshold=1e-4):
         self.ctx = ctx
@@ -101,14 +103,18 @@ class PreparedTrackBatch:
         self.arr = (LkJob * n)()
         self.keep, self.outs, self.guess, self.pins = [], [], [], []
         use_init = any(j.get("next_pts") is not None for j in jobs)
-        for i, j in enumerate(jobs):
-            nxt = _img(j["next"])
-            self.rows, self.cols = nxt.shape
-            pin = lib.ssx_host_alloc(nxt.size)
-            if not pin:
-                raise MemoryError("ssx_host_alloc")
+        imgs = [_img(j["next"]) for j in jobs]
+        self.rows, self.cols = imgs[0].shape
+        slice_bytes = (imgs[0].size + 255) & ~255
+        arena = lib.ssx_host_alloc(n * slice_bytes)
+        if not arena:
+            raise MemoryError("ssx_host_alloc")
+        self.pins.append(arena)
+        for i, (j, nxt) in enumerate(zip(jobs, imgs)):
+            if nxt.shape != imgs[0].shape:
+                raise ValueError("PreparedTrackBatch: the jobs of a call share the image size")
+            pin = arena + i * slice_bytes
             C.memmove(pin, nxt.ctypes.data, nxt.size)
-            self.pins.append(pin)
             pp, g, out = _fill_job(self.arr[i], j, C.cast(pin, u8_p), self.cols)
             self.keep.append(pp); self.outs.append(out); self.guess.append(g)
         self.n = n
@@ -161,6 +167,7 @@ def track_batch_ptrs(ctx: Context, jobs, rows, cols, winSize=11, maxLevel=3, max
 
 # ---- the plan of a call (include/ssx_test_hooks.h: ssx_lk_debug_plan needs no GPU, ssx_lk_debug_last_call reports the last call) ----
 STAGED, ARENA, EACH, IN_PLACE = range(4)
+FACT_NEXT0_IS_HOST, FACT_SEVERAL_ALLOCATIONS = 1, 2
 KERNELS = ("k_lk_pyramid", "k_lk_pad_level0", "k_lk_pyr_down", "k_lk_scharr", "k_lk_track")
 SPANS = ("tab", "images", "prev_pts", "next_pts", "status", "err", "dev_images")
 
@@ -184,9 +191,10 @@ class LkJobFacts(C.Structure):
                 ("reserved", C.c_int32), ("next_off", C.c_int64)]
 
 
-def debug_plan(lib, rows, cols, jobs, slot_flags=None, win=11, max_level=3, planned_key=None, images_on_device=0, next0_is_host=0):
+def debug_plan(lib, rows, cols, jobs, slot_flags=None, win=11, max_level=3, planned_key=None, images_on_device=0, next0_is_host=0, one_allocation=1):
     """ssx_lk_debug_plan: jobs = [dict(slot, fresh, n, prev_stride, next_stride, next_off)] (strides default to cols, next_off to
-    job index x rows x cols); slot_flags per job (default: 3 for a chained job, 0 for a fresh one) -> LkCallInfo"""
+    job index x rows x cols); slot_flags per job (default: 3 for a chained job, 0 for a fresh one); next0_is_host, one_allocation:
+    what the runtime would answer about the image pointers -> LkCallInfo"""
     n = len(jobs)
     arr = (LkJobFacts * n)()
     for i, j in enumerate(jobs):
@@ -199,10 +207,25 @@ def debug_plan(lib, rows, cols, jobs, slot_flags=None, win=11, max_level=3, plan
     lib.ssx_lk_debug_plan.restype = C.c_int
     lib.ssx_lk_debug_plan.argtypes = [C.c_int32] * 4 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(LkJobFacts), C.POINTER(C.c_uint8), C.c_int32,
                                                         C.c_int32, C.POINTER(LkCallInfo)]
-    st = lib.ssx_lk_debug_plan(rows, cols, win, max_level, key, n, arr, (C.c_uint8 * n)(*slot_flags), int(images_on_device), int(next0_is_host),
-                               C.byref(out))
+    call_facts = (FACT_NEXT0_IS_HOST if next0_is_host else 0) | (0 if one_allocation else FACT_SEVERAL_ALLOCATIONS)
+    st = lib.ssx_lk_debug_plan(rows, cols, win, max_level, key, n, arr, (C.c_uint8 * n)(*slot_flags), int(images_on_device), call_facts, C.byref(out))
     assert st == out.status
     return out
+
+
+def debug_intake(ctx: Context, nexts, rows, cols, stride=None, winSize=11, maxLevel=3):
+    """ssx_lk_debug_intake: which intake ssx_lk_track_batch (images_on_device = 1) would take for jobs whose `next` images are at the
+    addresses `nexts` -> (intake, the pointers pass the arena's arithmetic).  Asks the runtime about the pointers, runs nothing."""
+    arr = (LkJob * len(nexts))()
+    for i, a in enumerate(nexts):
+        arr[i].slot = i; arr[i].next = C.cast(a, u8_p); arr[i].next_stride = cols if stride is None else stride
+    prm = LkParams(int(winSize), int(maxLevel), 30, 0.01, 1e-4, 1)
+    intake, arithmetic = C.c_int32(-1), C.c_int32(-1)
+    fn = ctx.lib.ssx_lk_debug_intake
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LkJob), C.c_int32, C.c_int32, C.POINTER(LkParams), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    ctx.check(fn(ctx.handle, len(nexts), arr, rows, cols, C.byref(prm), 1, C.byref(intake), C.byref(arithmetic)))
+    return intake.value, bool(arithmetic.value)
 
 
 def last_call(ctx: Context):

@@ -3,7 +3,15 @@
 // temporal LK calls, pose-only) on their own images; every result must be, byte for byte, what the same calls return one by one
 // through SsxCompute.  Then the same round with two streams filing requests the library rejects (a negative point count): those two
 // streams get the exception, the other streams of the same batched calls get their results.
-//   test_batcher_gpu [streams=6] [cohorts=1]
+//   test_batcher_gpu [streams=6] [cohorts=1] [mixed]
+// mixed: stream k has image size k % 2 of two (160 x 256 and 128 x 208: both keep a four-level pyramid at window 11), so a cohort
+// serves two sizes per frame -- each on LK contexts of its own, or the chain of the size served second would be gone when it is asked
+// for.  Both rounds run in both PIN ORDERS: which stream pins its images first sizes the slices of the cohort's pinned arena.
+//   small first   the streams of the large size do not fit and keep pinned buffers of their own: separate allocations, wherever the
+//                 allocator put them, handed to ssx_lk_track_batch as images_on_device
+//   large first   every stream is in the arena, the small images in slices larger than they are
+// With streams dealt to cohorts by k mod cohorts, an EVEN number of cohorts sorts the two sizes into different cohorts (each then serves
+// one size beside the other's); an odd number mixes them inside every cohort.
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -21,10 +29,10 @@ using namespace ssx::host;
 static int g_failed = 0;
 #define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #c); ++g_failed; } } while (0)
 
-static const int ROWS = 160, COLS = 256;
+static const int SIZES[2][2] = {{160, 256}, {128, 208}};      // rows, cols
 
 // a textured image: three octaves of bilinear value noise; (dx, dy) shifts the texture
-static Image make_image(uint32_t seed, double dx, double dy, uint64_t id)
+static Image make_image(int ROWS, int COLS, uint32_t seed, double dx, double dy, uint64_t id)
 {
   Image im;
   im.rows = ROWS; im.cols = COLS; im.id = id; im.data.resize((size_t)ROWS * COLS);
@@ -89,7 +97,7 @@ static void run_stream(Compute& c, const StreamData& d, Results& r, Fault fault)
   std::vector<double> uvL(2 * (size_t)n), uvR(2 * (size_t)n);
   for (int i = 0; i < 2 * n; ++i) { uvL[i] = pts[i]; uvR[i] = r.right_pts[i]; }
   ssx_stereo_rig rig{};
-  rig.fx = 300; rig.fy = 300; rig.cx = COLS / 2.0; rig.cy = ROWS / 2.0; rig.baseline = 0.5;
+  rig.fx = 300; rig.fy = 300; rig.cx = d.L0.cols / 2.0; rig.cy = d.L0.rows / 2.0; rig.baseline = 0.5;
   r.xyz.assign(3 * (size_t)n, 0.0); r.tri_ok.assign(n, 0);
   try {
     c.Triangulate(fault == BAD_TRIANGULATE ? -1 : n, uvL.data(), uvR.data(), rig, nullptr, r.xyz.data(), r.tri_ok.data());
@@ -116,15 +124,21 @@ static void run_stream(Compute& c, const StreamData& d, Results& r, Fault fault)
 int main(int argc, char** argv)
 {
   const int S = argc > 1 ? std::atoi(argv[1]) : 6, C = argc > 2 ? std::atoi(argv[2]) : 1;
+  const bool mixed = argc > 3 && std::string(argv[3]) == "mixed";
+  if (S < 1 || C < 1 || (argc > 3 && !mixed)) { std::fprintf(stderr, "usage: test_batcher_gpu [streams] [cohorts] [mixed]\n"); return 2; }
+  auto size_of = [&](int k) { return mixed ? k % 2 : 0; };
   std::vector<StreamData> data(S);
   uint64_t id = 1;
   for (int k = 0; k < S; ++k) {
     StreamData& d = data[k];
-    d.L0 = make_image(17 + k, 0, 0, id++);
-    d.R0 = make_image(17 + k, 7.0 + k % 3, 0, id++);       // a disparity of 7 - 9 px
-    d.L1 = make_image(17 + k, 1.5, 0.5, id++);
-    d.L2 = make_image(17 + k, 3.0, 1.0, id++);
-    d.boxes = {40 + k, 30, 90 + k, 70, 150, 60 + k, 200, 100};
+    const int rows = SIZES[size_of(k)][0], cols = SIZES[size_of(k)][1];
+    d.L0 = make_image(rows, cols, 17 + k, 0, 0, id++);
+    d.R0 = make_image(rows, cols, 17 + k, 7.0 + k % 3, 0, id++);       // a disparity of 7 - 9 px
+    d.L1 = make_image(rows, cols, 17 + k, 1.5, 0.5, id++);
+    d.L2 = make_image(rows, cols, 17 + k, 3.0, 1.0, id++);
+    // (two boxes inside the smaller image, clear of the extractor's border)
+    if (size_of(k) == 0) d.boxes = {40 + k, 30, 90 + k, 70, 150, 60 + k, 200, 100};
+    else d.boxes = {30 + k, 24, 80 + k, 64, 118, 48 + k, 168, 88};
   }
   // one by one, each stream on a Compute of its own
   std::vector<Results> ref(S);
@@ -135,7 +149,18 @@ int main(int argc, char** argv)
     int tracked = 0;
     for (uint8_t s_ : ref[k].st2) tracked += s_;
     CHECK(tracked > (int)ref[k].kps.size() / 2);
+    if (g_failed) std::fprintf(stderr, "reference of stream %d (%d x %d): %zu keypoints, %d tracked\n", k, data[k].L0.cols, data[k].L0.rows, ref[k].kps.size(), tracked);
   }
+  // LK calls of one frame, all cohorts together: a cohort makes one per image size among its streams
+  long calls_per_frame = 0;
+  for (int c = 0; c < std::min(C, S); ++c) {
+    bool has[2] = {false, false};
+    for (int k = c; k < S; k += std::min(C, S)) has[size_of(k)] = true;
+    calls_per_frame += (long)has[0] + (long)has[1];
+  }
+  // pin order: -1 as the threads come (one size: there is no order); else the streams of that size pin first, one per cohort
+  const std::vector<int> orders = mixed ? std::vector<int>{1, 0} : std::vector<int>{-1};
+  for (int first_size : orders)
   for (int round = 0; round < 2; ++round) {
     StreamBatcher batcher(0, S, C);
     std::vector<Results> got(S);
@@ -143,12 +168,27 @@ int main(int argc, char** argv)
     std::vector<std::unique_ptr<Compute>> comp;
     for (int k = 0; k < S; ++k) comp.push_back(batcher.MakeCompute(k));
     std::vector<std::thread> th;
-    for (int k = 0; k < S; ++k)
+    auto start = [&](int k) {
       th.emplace_back([&, k] {
         const Fault f = round == 0 ? NONE : k == 1 ? BAD_POSE_ONLY : k == S - 2 ? BAD_TRIANGULATE : NONE;
         try { run_stream(*comp[k], data[k], got[k], f); } catch (const std::exception& e) { died[k] = e.what(); }
         batcher.Finish(k);
       });
+    };
+    // Which stream pins first is a race between the threads; it is decided here.  Per cohort the first stream of the chosen size starts
+    // alone: its first call (DetectBoxes) pins its images and then waits for the cohort, whose other streams start once the slice is set.
+    std::vector<char> started(S, 0);
+    const int n_coh = std::min(C, S);
+    for (int c = 0; c < n_coh && first_size >= 0; ++c) {
+      int lead = -1;
+      for (int k = c; k < S && lead < 0; k += n_coh) if (size_of(k) == first_size) lead = k;
+      if (lead < 0) continue;                       // (a cohort without that size)
+      start(lead); started[lead] = 1;
+      while (batcher.PinnedSliceBytes(lead) == 0) std::this_thread::yield();
+      const size_t bytes = (size_t)SIZES[first_size][0] * SIZES[first_size][1];
+      CHECK(batcher.PinnedSliceBytes(lead) == ((bytes + 255) & ~size_t(255)));
+    }
+    for (int k = 0; k < S; ++k) if (!started[k]) start(k);
     for (auto& t : th) t.join();
     for (int k = 0; k < S; ++k) {
       CHECK(died[k].empty());
@@ -161,13 +201,23 @@ int main(int argc, char** argv)
       } else {
         CHECK(!got[k].tri_error.empty() && got[k].next2 == ref[k].next2 && got[k].st2 == ref[k].st2 && got[k].po_error.empty());
       }
+      int tracked = 0;                              // the chained call really tracked (a chain that was lost tracks nothing)
+      for (uint8_t s_ : got[k].st2) tracked += s_;
+      CHECK(tracked > (int)got[k].kps.size() / 2);
     }
     const StreamBatcher::Stats st = batcher.stats();
-    std::printf("round %d: LK calls %ld (%ld jobs), pose-only %ld (%ld), keyframe calls %ld (%ld)\n", round, st.lk_calls, st.lk_jobs, st.po_calls, st.po_jobs,
+    std::printf("%s round %d: LK calls %ld (%ld jobs), pose-only %ld (%ld), keyframe calls %ld (%ld)\n",
+                first_size < 0 ? "one size," : first_size == 1 ? "small pins first," : "large pins first,", round, st.lk_calls, st.lk_jobs, st.po_calls, st.po_jobs,
                 st.kf_calls, st.kf_jobs);
     if (round == 0 && C == 1) CHECK(st.lk_jobs == 2L * S && st.po_jobs == (long)S);
+    if (mixed) {
+      // two temporal LK calls per stream; per frame the streams of one size travel together: as many calls as sizes, not as streams
+      CHECK(st.lk_jobs == 2L * S);
+      CHECK(st.lk_calls == 2 * calls_per_frame);
+    }
+    if (!g_failed) std::printf("%s round %d: ok\n", first_size < 0 ? "one size," : first_size == 1 ? "small pins first," : "large pins first,", round);
   }
   if (g_failed) { std::fprintf(stderr, "%d checks failed\n", g_failed); return 1; }
-  std::printf("test_batcher_gpu: ok (%d streams, %d cohorts)\n", S, C);
+  std::printf("test_batcher_gpu: ok (%d streams, %d cohorts%s)\n", S, C, mixed ? ", two image sizes, both pin orders" : "");
   return 0;
 }

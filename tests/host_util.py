@@ -19,12 +19,13 @@ def write_config(path, overrides):
     return write_settings(path, overrides)
 
 
-def write_sequence(root, n_frames=12, step=0.12, seed=0, dt=0.1):
-    """make_lateral_sequence as <root>/seq/{times.txt,image_0,image_1}.  Returns dir, dt, camera centres [n,3]."""
+def write_sequence(root, n_frames=12, step=0.12, seed=0, dt=0.1, h=None, w=None):
+    """make_lateral_sequence as <root>/seq/{times.txt,image_0,image_1}; h, w: the image size (default: KITTI 00's 376 x 1241).
+    Returns dir, dt, camera centres [n,3]."""
     from PIL import Image
 
-    from tools.synth import KITTI_BASELINE, make_lateral_sequence
-    frames, gt, _ = make_lateral_sequence(n_frames=n_frames, step=step, seed=seed)
+    from tools.synth import KITTI_BASELINE, KITTI_H, KITTI_W, make_lateral_sequence
+    frames, gt, _ = make_lateral_sequence(n_frames=n_frames, step=step, seed=seed, h=KITTI_H if h is None else h, w=KITTI_W if w is None else w)
     d = os.path.join(root, "seq")
     for sub in ("image_0", "image_1"):
         os.makedirs(os.path.join(d, sub), exist_ok=True)

@@ -10,11 +10,16 @@ them are fresh (both images given) and which chained (prev = NULL), the points p
     ARENA_SKIP     the same block with slice 1 left out (a stream that sits the call out)
     SEPARATE_HOST  a pinned block per image, the jobs listed in DESCENDING address order
     DEVICE         a device buffer per image, likewise descending
+    ADJACENT_HOST  a pinned block per image which the allocator happened to lay out like an arena: ascending, at a constant distance,
+                   close together -- pointer arithmetic cannot tell it from ARENA, only the runtime can (several allocations)
+    ADJACENT_HOST_SKIP, ADJACENT_DEVICE   the same with slice 1 left out; the same in device memory
 
 facts() turns a call into what ssx_lk_debug_plan is told: per job (slot, fresh, n, strides, next_off) + images_on_device + whether
-jobs[0].next is host memory."""
+jobs[0].next is host memory + whether the `next` images lie in ONE allocation."""
 
 HOST, ARENA, ARENA_SKIP, SEPARATE_HOST, DEVICE = "host", "arena", "arena_skip", "separate_host", "device"
+ADJACENT_HOST, ADJACENT_HOST_SKIP, ADJACENT_DEVICE = "adjacent_host", "adjacent_host_skip", "adjacent_device"
+ADJACENT = (ADJACENT_HOST, ADJACENT_HOST_SKIP, ADJACENT_DEVICE)
 STAGED, IN_ARENA, EACH, IN_PLACE = range(4)                       # ssx_lk_call_info.intake (include/ssx_test_hooks.h)
 
 # (h, w, win, max_level): the nine of test_lk_gpu.py::test_pyramids_borders_and_chains_over_sizes_and_windows, the default parameters on a
@@ -62,6 +67,25 @@ CASES = [case(f"geom-{h}x{w}-win{win}-ml{ml}", h, w, [call([0], True), call([0],
 ] + _intake_cases()
 
 
+def _allocation_cases():
+    """The layouts whose pointers pass the arena's arithmetic although every image is an allocation of its own (a cohort of two image
+    sizes hands ssx_lk_track_batch exactly this: host/stream_batcher.cpp gives the streams of the larger size buffers of their own).
+    2 and 3 jobs (k_lk_pyramid), 17 (the per-level kernels), a left-out slice; a fresh call, then a chained one.  `intake` is what
+    the call takes when the runtime answers "several allocations"; with the answer "one" it is IN_ARENA (tests/test_lk_plan.py plans
+    both).  These cases are planned only: tools/lk_call_trace.py cannot ask an allocator for such a layout."""
+    out = []
+    for nj in (2, 3, 17):
+        fused = nj <= 16
+        n = [0 if j == 1 else 47 + j for j in range(nj)]
+        for layout in ADJACENT if nj > 2 else (ADJACENT_HOST, ADJACENT_DEVICE):
+            out.append(case(f"allocations-120x168-{nj}jobs-{layout}", 120, 168, [call(range(nj), True, layout, n), call(range(nj), False, layout, n)],
+                            intake=EACH if fused and layout != ADJACENT_DEVICE else IN_PLACE, use_fused=fused))
+    return out
+
+
+ALLOCATION_CASES = _allocation_cases()
+
+
 def name(c):
     return c["name"]
 
@@ -76,12 +100,14 @@ def next_offsets(c, k):
     nj, d = len(k["slots"]), slice_bytes(c)
     if k["layout"] == ARENA_SKIP:
         return [(j if j < 1 else j + 1) * d for j in range(nj)]
+    if k["layout"] in ADJACENT:                                         # (a page of the allocator's own between two images)
+        return [(j + 1 if j >= 1 and k["layout"] == ADJACENT_HOST_SKIP else j) * (d + 4096) for j in range(nj)]
     if k["layout"] in (SEPARATE_HOST, DEVICE):
         return [-j * (d + 4096) for j in range(nj)]                     # allocations of their own, descending
     return [j * d for j in range(nj)]
 
 
 def facts(c, k):
-    """-> (jobs for ssvio_amd.lk.debug_plan, images_on_device, next0_is_host)"""
+    """-> (jobs for ssvio_amd.lk.debug_plan, images_on_device, next0_is_host, one_allocation)"""
     jobs = [dict(slot=s, fresh=f, n=n, next_off=o) for s, f, n, o in zip(k["slots"], k["fresh"], k["n"], next_offsets(c, k))]
-    return jobs, int(k["layout"] != HOST), int(k["layout"] != DEVICE)
+    return jobs, int(k["layout"] != HOST), int(k["layout"] not in (DEVICE, ADJACENT_DEVICE)), int(k["layout"] not in ADJACENT)

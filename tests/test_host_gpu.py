@@ -333,15 +333,53 @@ def test_batched_streams_with_asynchronous_backends_finish(built, tmp_path):
             assert len(open(f"{many}.{k}").read().splitlines()) == 14, (window, k)
 
 
-@pytest.mark.parametrize("streams,cohorts", [(6, 1), (9, 2)])
-def test_stream_batcher_results_and_error_isolation(built, streams, cohorts):
+@pytest.mark.parametrize("streams,cohorts,sizes", [pytest.param(6, 1, "one", id="6-1"), pytest.param(9, 2, "one", id="9-2"), pytest.param(6, 1, "mixed", id="6-1-mixed"),
+                                                   pytest.param(9, 2, "mixed", id="9-2-mixed"), pytest.param(9, 3, "mixed", id="9-3-mixed")])
+def test_stream_batcher_results_and_error_isolation(built, streams, cohorts, sizes):
     """tests/host/test_batcher_gpu.cpp: the StreamBatcher driven directly by S threads (masked detection, stereo LK, triangulation, two
     chained temporal LK calls, pose-only -- one frame's calls of FrontEnd); every stream's results are byte for byte those of the same
     calls made one by one through SsxCompute, and a stream that files a request the library rejects gets the exception ALONE: the
-    other streams of the same batched call get their results."""
-    r = subprocess.run([built["batcher_gpu"], str(streams), str(cohorts)], capture_output=True, text=True, timeout=300)
+    other streams of the same batched call get their results.
+    mixed: stream k has image size k % 2 of two, and both rounds run in both pin orders (small images pinned first: the large streams
+    keep pinned buffers of their own, separate allocations; large first: every stream in the arena).  No stream dies of a lost LK
+    chain, every chained call tracks, and a frame costs one LK call per size, not per stream.  With two cohorts the sizes fall into
+    different cohorts; with three every cohort serves both."""
+    r = subprocess.run([built["batcher_gpu"], str(streams), str(cohorts)] + (["mixed"] if sizes == "mixed" else []), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "test_batcher_gpu: ok" in r.stdout
+    if sizes == "mixed":
+        for order in ("small", "large"):
+            for rnd in (0, 1):
+                assert f"{order} pins first, round {rnd}: ok" in r.stdout, r.stdout
+
+
+def test_batched_streams_of_two_image_sizes(built, tmp_path):
+    """A cohort whose sequences differ in image size -- KITTI's own two, 00 at 1241 x 376 beside 04 at 1226 x 370: four batched streams
+    over the two sequences, in one cohort and in two.  Every stream writes, byte for byte, the trajectory of its sequence's single-stream
+    run (the streams of either size keep their LK chains on contexts of that size), and the jobs of one size still share a call."""
+    import re
+    a = hu.write_sequence(os.path.join(str(tmp_path), "a"), n_frames=8, step=0.6, seed=1, h=376, w=1241)
+    b = hu.write_sequence(os.path.join(str(tmp_path), "b"), n_frames=8, step=0.6, seed=3, h=370, w=1226)
+    cfg = hu.write_config(os.path.join(str(tmp_path), "cfg.yaml"), {"Map.ActiveMap.Size": 4, "numFeatures.trackingGood": 100000})   # a keyframe per frame
+    singles = []
+    for k, seq in enumerate((a, b)):
+        out = os.path.join(str(tmp_path), f"single{k}.txt")
+        r = subprocess.run([built["run_kitti"], f"--config_yaml_path={cfg}", f"--kitti_dataset_path={seq['dir']}", f"--trajectory={out}"],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        singles.append(open(out).read())
+        assert len(singles[-1].splitlines()) == 8                      # (every frame's pose is in the file: tracked by temporal LK, its keyframe by stereo LK)
+    assert singles[0] != singles[1]
+    for cohorts in (1, 2):
+        many = os.path.join(str(tmp_path), f"many{cohorts}.txt")
+        r = subprocess.run([built["run_kitti"], f"--config_yaml_path={cfg}", f"--kitti_dataset_path={a['dir']},{b['dir']}", f"--trajectory={many}",
+                            "--streams=4", "--preload=1", f"--batched={cohorts}"], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        for k in range(4):
+            assert open(f"{many}.{k}").read() == singles[k % 2], (cohorts, k)
+        m = re.search(r"batched calls: LK (\d+) \(([\d.]+) jobs each\)", r.stdout)
+        assert m, r.stdout
+        assert float(m.group(2)) > 1.0, r.stdout
 
 
 def test_batched_streams_reproduce_the_single_stream_trajectories(built, tmp_path):

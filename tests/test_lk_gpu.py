@@ -267,3 +267,175 @@ def test_every_image_intake_gives_the_same_bits(po, h, w, max_level, nj):
             for j, (g, o) in enumerate(zip(got, want)):
                 assert _same(g[0], o[0]) and _same(g[1], o[1]) and _same(g[2], o[2]), (layout, k["fresh"], j)
     c.close()
+
+
+def _raw_batch_call(c, slot, prev, nxt, pts):
+    """one job through ssx_lk_track_batch (host images) with the caller's arrays in view -> (status, next_pts, status bytes, err):
+    a refused call returns no result, so what it left in the arrays is looked at here"""
+    import ctypes as C
+    arr = (lk.LkJob * 1)()
+    job = dict(slot=slot, prev_pts=pts, next_pts=pts)
+    _, guess, (npts, st, er) = lk._fill_job(arr[0], job, nxt.ctypes.data_as(lk.u8_p), nxt.strides[0], None if prev is None else prev.ctypes.data_as(lk.u8_p),
+                                            0 if prev is None else prev.strides[0])
+    st[:] = 7; er[:] = -1.0                                            # (neither is a value the tracker writes into all of them)
+    prm = lk.LkParams(11, 3, 30, 0.01, 1e-4, 1)
+    rc = lk._batch_fn(c.lib)(c.handle, 1, arr, nxt.shape[0], nxt.shape[1], C.byref(prm), 0)
+    return rc, guess, npts, st, er
+
+
+def test_a_call_of_another_size_drops_every_chain(po):
+    """include/ssx.h, ssx_lk_track_next / ssx_lk_track_batch: a context holds chains for ONE (rows, cols, win, max_level); a call with
+    another key drops them all, on every slot.  Size A on slot 0, size B on slot 1, then a chained A on slot 0: refused (SsxError's
+    status, no result, next_pts as passed) -- and the refusal changes nothing: slot 1's B chain goes on with the oracle's bytes.  A
+    fresh A call starts a new chain, and the chained call behind it gives the oracle's bytes from the kept pyramid of the right
+    frame."""
+    from ssvio_amd import Context, _lib
+    sizes = {"A": (120, 160), "B": (97, 130)}
+    frames, pts = {}, {}
+    for n_, (h, w) in sizes.items():
+        base = make_stereo_pair(seed=70 + h % 5, h=h, w=w, n_blobs=160)[0]
+        frames[n_] = [np.ascontiguousarray(np.roll(base, (t, 2 * t), (0, 1))) for t in range(4)]
+        gx, gy = np.meshgrid(np.linspace(4.5, w - 5.5, 10), np.linspace(4.5, h - 5.5, 6))
+        pts[n_] = np.stack([gx.ravel(), gy.ravel()], 1).astype(np.float32)
+        assert len(pts[n_]) == 60
+    A, B = frames["A"], frames["B"]
+    c = Context(0)
+
+    def oracle_bytes(got, prev, nxt, p):
+        o = po.lk_track(prev, nxt, p, p)
+        return _same(got[0], o[0]) and _same(got[1], o[1]) and _same(got[2], o[2])
+
+    g = lk.track_batch(c, [dict(slot=0, prev=A[0], next=A[1], prev_pts=pts["A"], next_pts=pts["A"])])[0]                  # 1: fresh, size A, slot 0
+    assert oracle_bytes(g, A[0], A[1], pts["A"])
+    g = lk.track_batch(c, [dict(slot=1, prev=B[0], next=B[1], prev_pts=pts["B"], next_pts=pts["B"])])[0]                  # 2: fresh, size B, slot 1
+    assert oracle_bytes(g, B[0], B[1], pts["B"])
+    rc, guess, npts, st, er = _raw_batch_call(c, 0, None, A[2], pts["A"])                                                # 3: chained, size A, slot 0
+    assert rc == _lib.SSX_ERR_INVALID_ARG and "no previous ssx_lk_track call" in c.lib.ssx_last_error(c.handle).decode()
+    assert _same(npts, guess) and (st == 7).all() and (er == -1.0).all()
+    with pytest.raises(_lib.SsxError):
+        lk.track_batch(c, [dict(slot=0, prev=None, next=A[2], prev_pts=pts["A"], next_pts=pts["A"])])
+    # (the refused call has not re-planned the context: size B's chain is still there)
+    g = lk.track_batch(c, [dict(slot=1, prev=None, next=B[2], prev_pts=pts["B"], next_pts=pts["B"])])[0]
+    assert oracle_bytes(g, B[1], B[2], pts["B"])
+    g = lk.track_batch(c, [dict(slot=0, prev=A[1], next=A[2], prev_pts=pts["A"], next_pts=pts["A"])])[0]                  # 4: fresh, size A, slot 0
+    assert oracle_bytes(g, A[1], A[2], pts["A"])
+    with pytest.raises(_lib.SsxError):                                 # (and now size B's chain is gone in its turn)
+        lk.track_batch(c, [dict(slot=1, prev=None, next=B[3], prev_pts=pts["B"], next_pts=pts["B"])])
+    g = lk.track_batch(c, [dict(slot=0, prev=None, next=A[3], prev_pts=pts["A"], next_pts=pts["A"])])[0]                  # 5: chained, size A, slot 0
+    assert oracle_bytes(g, A[2], A[3], pts["A"])
+    kept, new = A[2], A[3]
+    for level in range(4):
+        if level > 0:
+            kept, new = po.lk_pyr_down(kept), po.lk_pyr_down(new)
+        assert np.array_equal(lk.stage_level(c, 0, level), kept) and np.array_equal(lk.stage_level(c, 1, level), new), level
+    assert lk.stage_level(c, 0, 3).shape == (15, 20)
+    c.close()
+
+
+@pytest.mark.parametrize("nj", [5, 17])
+def test_images_allocated_one_by_one_are_never_one_copy(po, record_property, nj):
+    """A pinned allocation per image, the jobs listed in ASCENDING address order: what a cohort of two image sizes hands the library
+    (host/stream_batcher.cpp: the streams of the larger size keep buffers of their own).  If the allocator happens to place them at
+    equal distances and close together, pointer arithmetic sees an arena, and one copy over the range would cross whatever lies
+    between the allocations.  So the library is ASKED first (ssx_lk_debug_intake: pointer queries only) and must not answer LK_ARENA;
+    only then is the call made -- a fresh one, then a chained one -- and compared with the staged path's bytes.  Whether the allocator
+    produced the adjacent layout is not in the test's hands: it is recorded (the deterministic check of the decision is
+    tests/test_lk_plan.py::test_an_arena_is_one_allocation).  A real arena -- one pinned block, constant distance -- is still LK_ARENA,
+    by the hook and by the call."""
+    import ctypes as C
+    import lk_call_cases as cc
+    from ssvio_amd import Context
+    h, w = 120, 168
+    c, c_ref = Context(0), Context(0)
+    lib = c.lib
+    lib.ssx_host_alloc.restype = C.c_void_p; lib.ssx_host_alloc.argtypes = [C.c_size_t]
+    lib.ssx_host_free.restype = None; lib.ssx_host_free.argtypes = [C.c_void_p]
+    base = [make_stereo_pair(seed=60 + s_, h=h, w=w, n_blobs=200)[0] for s_ in range(nj)]
+    frames = [[np.ascontiguousarray(np.roll(base[s_], (t * (s_ % 2), t * (1 + s_ % 3)), (0, 1))) for t in range(3)] for s_ in range(nj)]
+    gx, gy = np.meshgrid(np.linspace(6, 160, 8), np.linspace(6, 112, 6))
+    grid = np.stack([gx.ravel(), gy.ravel()], 1).astype(np.float32)
+    pts = [grid[:0] if s_ == 1 else grid[:40 + s_ % 9] for s_ in range(nj)]                  # (one job without points)
+    want_split = cc.EACH if nj <= 16 else cc.IN_PLACE                  # k_lk_pyramid up to 16 jobs: a copy per pinned image in front of it
+    pins = []
+
+    def pinned(nbytes):
+        p = lib.ssx_host_alloc(nbytes)
+        assert p
+        pins.append(p)
+        return p
+
+    def one_by_one(images):
+        """-> ascending addresses of separately pinned copies of the images, image j at address j"""
+        addr = sorted(pinned(h * w) for _ in images)
+        for a, img in zip(addr, images):
+            C.memmove(a, img.ctypes.data, img.size)
+        return addr
+
+    def check(got, ref, what):
+        for j, (g, o) in enumerate(zip(got, ref)):
+            assert _same(g[0], o[0]) and _same(g[1], o[1]) and _same(g[2], o[2]), (what, j)
+
+    try:
+        ref = [lk.track_batch(c_ref, [dict(slot=s_, prev=frames[s_][0], next=frames[s_][1], prev_pts=pts[s_], next_pts=pts[s_]) for s_ in range(nj)]),
+               lk.track_batch(c_ref, [dict(slot=s_, prev=None, next=frames[s_][2], prev_pts=pts[s_], next_pts=pts[s_]) for s_ in range(nj)])]
+        assert lk.last_call(c_ref).intake == cc.STAGED
+        for t, fresh in ((1, True), (2, False)):
+            nxt = one_by_one([frames[s_][t] for s_ in range(nj)])
+            prev = one_by_one([frames[s_][t - 1] for s_ in range(nj)]) if fresh else [None] * nj
+            intake, adjacent = lk.debug_intake(c, nxt, h, w)           # ask ...
+            record_property(f"{'fresh' if fresh else 'chained'}_call_pointers_pass_the_arena_arithmetic", adjacent)
+            print(f"{nj} jobs, {'fresh' if fresh else 'chained'} call: separate allocations pass the arena's arithmetic: {adjacent}; distances "
+                  f"{sorted({b - a for a, b in zip(nxt, nxt[1:])})}")
+            assert intake == want_split, (intake, adjacent)
+            got = lk.track_batch_ptrs(c, [dict(slot=s_, prev=prev[s_], next=nxt[s_], stride=w, prev_pts=pts[s_], next_pts=pts[s_]) for s_ in range(nj)], h, w)   # ... then run
+            info = lk.last_call(c)
+            assert (info.intake, info.arena_bytes, bool(info.use_fused)) == (want_split, 0, nj <= 16)
+            check(got, ref[t - 1], ("one by one", t))
+        # one pinned block sliced at a constant distance, on a context of its own: the arena of before
+        a = Context(0)
+        d = (h * w + 255) & ~255
+        for t, fresh in ((1, True), (2, False)):
+            block = [pinned(nj * d) for _ in range(2 if fresh else 1)]
+            for s_ in range(nj):
+                C.memmove(block[0] + s_ * d, frames[s_][t].ctypes.data, h * w)
+                if fresh:
+                    C.memmove(block[1] + s_ * d, frames[s_][t - 1].ctypes.data, h * w)
+            nxt = [block[0] + s_ * d for s_ in range(nj)]
+            assert lk.debug_intake(a, nxt, h, w) == (cc.IN_ARENA, True)
+            got = lk.track_batch_ptrs(a, [dict(slot=s_, prev=block[1] + s_ * d if fresh else None, next=nxt[s_], stride=w, prev_pts=pts[s_], next_pts=pts[s_])
+                                          for s_ in range(nj)], h, w)
+            info = lk.last_call(a)
+            assert (info.intake, info.arena_bytes) == (cc.IN_ARENA, (nj - 1) * d + h * w)
+            check(got, ref[t - 1], ("arena", t))
+            # the allocation must COVER the range: the same distances from further up the block, the last image reaching past its end
+            assert lk.debug_intake(a, [p_ + d - 256 for p_ in nxt], h, w) == (want_split, True)
+        a.close()
+    finally:
+        for p_ in pins:
+            lib.ssx_host_free(p_)
+        c.close(); c_ref.close()
+
+
+def test_a_prepared_batch_is_one_arena(po):
+    """lk.PreparedTrackBatch (what tools/bench_next.py times as the batched LK call) holds its images as the stream batcher does: one
+    pinned arena, a slice per job, taken in one copy; per job the oracle's bytes."""
+    import lk_call_cases as cc
+    from ssvio_amd import Context
+    c = Context(0)
+    S, h, w = 3, 120, 168
+    base = [make_stereo_pair(seed=60 + s_, h=h, w=w, n_blobs=200)[0] for s_ in range(S)]
+    nxt = [np.ascontiguousarray(np.roll(b, (1, 2), (0, 1))) for b in base]
+    gx, gy = np.meshgrid(np.linspace(6, 160, 8), np.linspace(6, 112, 6))
+    pts = np.stack([gx.ravel(), gy.ravel()], 1).astype(np.float32)
+    lk.track_batch(c, [dict(slot=s_, prev=nxt[s_], next=base[s_], prev_pts=pts, next_pts=pts) for s_ in range(S)])          # fills the slots
+    prep = lk.PreparedTrackBatch(c, [dict(slot=s_, prev=None, next=nxt[s_], prev_pts=pts, next_pts=pts) for s_ in range(S)])
+    try:
+        got = prep.run()
+        info = lk.last_call(c)
+        assert (info.intake, info.arena_bytes) == (cc.IN_ARENA, 2 * ((h * w + 255) & ~255) + h * w)
+        for s_, g in enumerate(got):
+            o = po.lk_track(base[s_], nxt[s_], pts, pts)
+            assert _same(g[0], o[0]) and _same(g[1], o[1]) and _same(g[2], o[2]), s_
+    finally:
+        prep.close()
+        c.close()

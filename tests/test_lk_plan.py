@@ -83,29 +83,31 @@ def check_launches(p, k, flags_before):
     assert got == want
 
 
-def expected_intake(c, k, jobs, on_device, next0_is_host, use_fused):
+def expected_intake(c, k, jobs, on_device, next0_is_host, use_fused, one_allocation=True):
     if not on_device:
         return cc.STAGED
     span, offs = c["h"] * c["w"], [j["next_off"] for j in jobs]         # (every case's stride is the image width)
     arena = len(jobs) >= 2 and all(b > a and b - a >= span for a, b in zip(offs, offs[1:])) and offs[-1] - offs[0] + span <= 2 * len(jobs) * span
-    if arena:
+    if arena and one_allocation:                                        # the copy of an arena is ONE copy: it may not leave the allocation
         return cc.IN_ARENA
     return cc.EACH if use_fused and next0_is_host else cc.IN_PLACE
 
 
-@pytest.mark.parametrize("c", cc.CASES, ids=cc.name)
-def test_calls(lib, c):
-    """every call of a case, the slots' flags carried from call to call as the context carries them"""
-    flags = {}
+def plan_case(lib, c, one_allocation=None):
+    """every call of a case, the slots' flags carried from call to call as the context carries them; one_allocation: what the runtime
+    answers when it is asked whether the `next` images lie in one allocation (None: what the case's layout says) -> the intakes"""
+    flags, intakes = {}, []
     for k in c["calls"]:
-        jobs, on_device, next0_is_host = cc.facts(c, k)
+        jobs, on_device, next0_is_host, one = cc.facts(c, k)
+        one = one if one_allocation is None else int(one_allocation)
         before = [flags.get(s, 0) for s in k["slots"]]
-        p = lk.debug_plan(lib, c["h"], c["w"], jobs, before, c["win"], c["max_level"], None, on_device, next0_is_host)
+        p = lk.debug_plan(lib, c["h"], c["w"], jobs, before, c["win"], c["max_level"], None, on_device, next0_is_host, one)
         assert p.status == _lib.SSX_OK, p.error
         check_io(p, c, k)
         check_launches(p, k, before)
-        assert p.intake == expected_intake(c, k, jobs, on_device, next0_is_host, p.use_fused)
-        if c["intake"] is not None:
+        assert p.intake == expected_intake(c, k, jobs, on_device, next0_is_host, p.use_fused, one)
+        assert (p.arena_bytes > 0) == (p.intake == cc.IN_ARENA)
+        if c["intake"] is not None and one_allocation is None:
             assert (p.intake, bool(p.use_fused)) == (c["intake"], c["use_fused"])
         assert p.n_jobs == len(jobs)
         for j, s in enumerate(k["slots"]):                              # have_next, and the kept derivative images only after k_lk_pyramid
@@ -114,15 +116,43 @@ def test_calls(lib, c):
             assert bool(p.slot_flags[j] & 4) == (not k["fresh"][j] and not before[j] & 4)
             assert p.job_roles[j] in (0b1010, 0b0101) and bool(p.job_roles[j] & 1) == bool(p.slot_flags[j] & 4)
             flags[s] = p.slot_flags[j]
+        intakes.append(p.intake)
+    return intakes
+
+
+@pytest.mark.parametrize("c", cc.CASES, ids=cc.name)
+def test_calls(lib, c):
+    plan_case(lib, c)
+
+
+@pytest.mark.parametrize("c", cc.ALLOCATION_CASES, ids=cc.name)
+def test_an_arena_is_one_allocation(lib, c):
+    """Pointers that ascend at equal distances within 2 x jobs images are an arena only if the runtime confirms that they lie in ONE
+    allocation: the arena's images cross in one copy over the whole range.  The same pointers planned with both answers: "several"
+    is never LK_ARENA -- a copy per image in front of k_lk_pyramid when they are host memory, else read where they lie -- and "one"
+    is the arena of before, with the same arena_bytes (check_io)."""
+    host = c["calls"][0]["layout"] != cc.ADJACENT_DEVICE
+    assert plan_case(lib, c) == [c["intake"]] * 2 == [cc.EACH if c["use_fused"] and host else cc.IN_PLACE] * 2
+    assert plan_case(lib, c, one_allocation=False) == [c["intake"]] * 2
+    assert plan_case(lib, c, one_allocation=True) == [cc.IN_ARENA] * 2
+
+
+def test_the_allocation_question_decides_nothing_else(lib):
+    """where the arithmetic already says "no arena" (or the images are staged) the answer is not looked at"""
+    for c in cc.CASES:
+        if c["intake"] not in (None, cc.IN_ARENA):
+            assert plan_case(lib, c, one_allocation=False) == plan_case(lib, c, one_allocation=True) == [c["intake"]] * len(c["calls"]), c["name"]
 
 
 def test_arena_rule_at_its_edges(lib):
     """unequal strides, a gap below one image, a range beyond 2 x jobs images: no arena"""
     h, w = 120, 168
     job = lambda j, off, stride=w: dict(slot=j, fresh=True, n=4, next_off=off, next_stride=stride)
-    plan = lambda jobs: lk.debug_plan(lib, h, w, jobs, images_on_device=1, next0_is_host=1).intake
+    plan = lambda jobs, one=1: lk.debug_plan(lib, h, w, jobs, images_on_device=1, next0_is_host=1, one_allocation=one).intake
     span = h * w
     assert plan([job(0, 0), job(1, span)]) == cc.IN_ARENA
+    assert plan([job(0, 0), job(1, span)], one=0) == cc.EACH             # two allocations back to back
+    assert plan([job(0, 0), job(1, 3 * span)], one=0) == cc.EACH
     assert plan([job(0, 0), job(1, span - 1)]) == cc.EACH
     assert plan([job(0, 0), job(1, 3 * span)]) == cc.IN_ARENA          # range 4 spans = 2 x 2 jobs
     assert plan([job(0, 0), job(1, 3 * span + 1)]) == cc.EACH
