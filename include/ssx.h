@@ -644,6 +644,29 @@ typedef struct ssx_lk_job {
 SSX_API ssx_status ssx_lk_track_batch(ssx_ctx* ctx, int32_t n_jobs, const ssx_lk_job* jobs, int32_t rows, int32_t cols,
                                       const ssx_lk_params* prm, int32_t images_on_device);
 /* ------------------------------------------------------------------------------------------------
+ * Image undistortion: Camera::UndistortImage (src/ssvio/camera.cpp:43-55, a cv::undistort with the camera matrix and
+ * k1 k2 p1 p2), which FrontEnd::GrabSteroImage applies to both images when Camera.NeedUndistortion is set (frontend.cpp:39-45).
+ * The contract is tools/undistort_model.py: the map in f64, operation by operation, quantised to 1/32 pixel; integer
+ * bilinear weights (the 10-bit products of the 5-bit fractions); taps outside the image read 0, each on its own; a non-finite or
+ * far-away source position yields 0.  K = (fx, fy, cx, cy); dist = (k1, k2, p1, p2, k3); iR = the inverse of newK * R, row-major
+ * (the caller's: a rectifying rotation costs nothing).  ssx_undistort_default fills iR for the reference's case, R = I and
+ * newK = K: [1/fx, 0, -cx/fx, 0, 1/fy, -cy/fy, 0, 0, 1]; it is host code and needs no device (a null argument: nothing is written).
+ *
+ * ssx_undistort: n jobs (0 .. SSX_UNDISTORT_MAX_JOBS; a stereo pair is n = 2) of one size rows x cols, 8-bit, strides in bytes, each
+ * with its own parameters, in ONE launch; one upload, one download and one synchronisation whatever n is.
+ * images_on_device != 0: src and dst are read and written where they lie -- device memory or pinned host memory, under the rules
+ * ssx_lk_track_batch states -- so a buffer of ssx_host_alloc filled by this call can go straight into
+ * ssx_lk_track_batch(..., images_on_device = 1); 0: ordinary host memory.  Bytes of dst beyond cols in a pitched row are untouched.
+ * SSX_ERR_INVALID_ARG with a message, before anything is touched: n < 0 or above the limit, a null pointer, a stride smaller than
+ * cols, rows or cols < 1, a dst that overlaps any src of the call (there is no in-place form: the reference clones the source).
+ * SSX_ERR_UNSUPPORTED: rows or cols above 32768.
+ * ------------------------------------------------------------------------------------------------ */
+#define SSX_UNDISTORT_MAX_JOBS 1024
+typedef struct { double K[4]; double dist[5]; /* k1 k2 p1 p2 k3 */ double iR[9]; } ssx_undistort_params;
+typedef struct { const uint8_t* src; int32_t src_stride; uint8_t* dst; int32_t dst_stride; ssx_undistort_params prm; } ssx_undistort_job;
+SSX_API void ssx_undistort_default(const double K4[4], const double dist5[5], ssx_undistort_params* out);
+SSX_API ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device);
+/* ------------------------------------------------------------------------------------------------
  * N3: pose-graph optimisation.
  * Replaces the optimisation of LoopClosing::PoseGraphOptimization
  * (/root/reference/src/ssvio/loopclosing.cpp:458-539): one VertexPose per keyframe (pose_fixed = the initial, the

@@ -10,6 +10,7 @@
 //   ssx::BundleAdjuster          the optimisation of Backend::OptimizeActiveMap (src/ssvio/backend.cpp:78-245)
 //   ssx::StereoFrontEnd          DetectFeatures + FindFeaturesInRight + triangulation in one device-resident call
 //   ssx::calcOpticalFlowPyrLK    cv::calcOpticalFlowPyrLK as frontend.cpp:156-166 / :374-384 call it
+//   ssx::Camera                  Camera::UndistortImage (src/ssvio/camera.cpp:43-55), one image or the frame's pair
 //   ssx::ORBVocabulary           DBoW2 vocabulary: loadFromTextFile / transform / score (loopclosing.cpp:33-41, :84, :633)
 //   ssx::KeyframeDatabase        key_frame_database_ with AddToKeyframeDatabase / DetectLoop / MatchFeatures (loopclosing.cpp:72-145, :646)
 //   ssx::ComputeCorrectPose      LoopClosing::ComputeCorrectPose / OptimizeCurrentPose (loopclosing.cpp:147-351)
@@ -223,6 +224,37 @@ inline void calcOpticalFlowPyrLKNext(Context& ctx, const uint8_t* nextImg, int n
   ctx.check(ssx_lk_track_next(ctx.get(), nextImg, nextStep, rows, cols, n, prevPts.data(), nextPts.data(), status.data(),
                               err.data(), &p, nullptr));
 }
+
+// ssvio::Camera as far as it computes on images: void Camera::UndistortImage(cv::Mat& src, cv::Mat& dst) (camera.cpp:43-55).  The
+// constructor takes what Camera's does -- fx fy cx cy and dist_coef_ = (k1, k2, p1, p2), floats widened, as K_cv is built -- and
+// fixes R = I, new camera matrix = K (ssx_undistort_default).  src and dst are two buffers (the reference undistorts through a
+// clone); host memory unless imagesOnDevice.  UndistortPair is the frame's two images (frontend.cpp:39-45) in one call.
+class Camera {
+ public:
+  Camera(Context& ctx, float fx, float fy, float cx, float cy, float k1 = 0.f, float k2 = 0.f, float p1 = 0.f, float p2 = 0.f) : ctx_(ctx)
+  {
+    const double K4[4] = {fx, fy, cx, cy}, dist5[5] = {k1, k2, p1, p2, 0.0};
+    ssx_undistort_default(K4, dist5, &prm_);
+  }
+  void UndistortImage(const uint8_t* src, int srcStep, uint8_t* dst, int dstStep, int rows, int cols, bool imagesOnDevice = false) const
+  {
+    ssx_undistort_job job{src, srcStep, dst, dstStep, prm_};
+    ctx_.check(ssx_undistort(ctx_.get(), 1, &job, rows, cols, imagesOnDevice ? 1 : 0));
+  }
+  const ssx_undistort_params& params() const { return prm_; }
+
+  static void UndistortPair(const Camera& left, const uint8_t* srcLeft, int srcLeftStep, uint8_t* dstLeft, int dstLeftStep, const Camera& right,
+                            const uint8_t* srcRight, int srcRightStep, uint8_t* dstRight, int dstRightStep, int rows, int cols,
+                            bool imagesOnDevice = false)
+  {
+    const ssx_undistort_job jobs[2] = {{srcLeft, srcLeftStep, dstLeft, dstLeftStep, left.prm_}, {srcRight, srcRightStep, dstRight, dstRightStep, right.prm_}};
+    left.ctx_.check(ssx_undistort(left.ctx_.get(), 2, jobs, rows, cols, imagesOnDevice ? 1 : 0));
+  }
+
+ private:
+  Context& ctx_;
+  ssx_undistort_params prm_{};
+};
 
 // ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>, include/ssvio/orbvocabulary.hpp:10) as LoopClosing
 // uses it: loadFromTextFile, transform(descriptors, BowVector), score(BowVector, BowVector).  A BowVector here is the

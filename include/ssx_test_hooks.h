@@ -231,6 +231,11 @@ SSX_API ssx_status ssx_kfdb_debug_last_batch(ssx_ctx* ctx, int32_t* launches, in
 SSX_API ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t cap, int32_t* ids_out, double* vals_out,
                                       int32_t* n_entries);
 
+/* tests / tools hook of ssx_undistort (csrc/undistort.hip): what the context's last call issued, counted where it is issued, as
+ * ssx_kfdb_debug_last_step counts -- kernel launches, stream synchronisations, bytes sent up (the job table and, for host images,
+ * the sources) and bytes that came down (the results of host images).  All zero after a call that was refused.  Any output may be NULL. */
+SSX_API ssx_status ssx_undistort_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,16 @@ class StereoFrameOut(C.Structure):
                 ("xyz", dbl_p), ("ok", u8_p), ("n_matched", C.c_int32), ("n_triangulated", C.c_int32)]
 
 
+class UndistortParams(C.Structure):
+    """ssx_undistort_params: K = (fx, fy, cx, cy), dist = (k1, k2, p1, p2, k3), iR = inverse of newK * R, row-major"""
+    _fields_ = [("K", C.c_double * 4), ("dist", C.c_double * 5), ("iR", C.c_double * 9)]
+
+
+class UndistortJob(C.Structure):
+    """ssx_undistort_job"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int32), ("prm", UndistortParams)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("calls", C.c_int32), ("total_ms", C.c_double)]
 

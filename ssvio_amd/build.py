@@ -33,6 +33,7 @@ PER_FILE = {
     "lk.hip": ["-ffp-contract=off"],
     "loop.hip": ["-ffp-contract=off"],
     "pnp.hip": ["-ffp-contract=off"],        # the P3P of a hypothesis rounds like tools/pnp_model.py, operation by operation
+    "undistort.hip": ["-ffp-contract=off"],  # the f64 map of a pixel rounds like tools/undistort_model.py, operation by operation
 }
 
 

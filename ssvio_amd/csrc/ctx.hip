@@ -75,6 +75,8 @@ void ssx_ctx_destroy(ssx_ctx* ctx)
   ctx->po_stage.release();
   ctx->pnp_arena.release();
   ctx->pnp_stage.release();
+  ctx->ud_arena.release();
+  ctx->ud_stage.release();
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }

@@ -1,5 +1,6 @@
 // ssvio_amd/host/compute.hpp -- the compute calls the reference's front-end, backend and loop closing make, as one interface
 // the host layer is written against:
+//   UndistortPair   Camera::UndistortImage, twice     (frontend.cpp:39-45 GrabSteroImage, camera.cpp:43-55)
 //   Detect          ORBextractor::Detect              (frontend.cpp:302-344 DetectFeatures)
 //   TrackLK         cv::calcOpticalFlowPyrLK          (frontend.cpp:156-166 TrackLastFrame, :374-384 FindFeaturesInRight)
 //   PoseOnly        the g2o part of EstimateCurrentPose (frontend.cpp:196-270)
@@ -94,6 +95,15 @@ class Compute {
       for (long y = boxes[b + 1]; y <= boxes[b + 3]; ++y)
         for (long x = boxes[b]; x <= boxes[b + 2]; ++x) mask[(size_t)y * img.cols + x] = 0;
     Detect(img, mask.data(), prm, kps);
+  }
+  // Camera::UndistortImage on the frame's two images (frontend.cpp:39-45), prm[0] the left camera's, prm[1] the right one's.  An
+  // implementation without it says so, and a FrontEnd with Camera.NeedUndistortion set refuses to be built on it (the CPU oracle of
+  // the tests: there is no CPU fallback).  left_out / right_out get the size of the inputs; their ids are the caller's.
+  virtual bool CanUndistort() const { return false; }
+  virtual void UndistortPair(const Image& left, const Image& right, const ssx_undistort_params prm[2], Image& left_out, Image& right_out)
+  {
+    (void)left; (void)right; (void)prm; (void)left_out; (void)right_out;
+    throw std::logic_error("Compute::UndistortPair: this implementation cannot undistort images (Camera.NeedUndistortion)");
   }
   // 11x11 window, 3 levels, (COUNT+EPS, 30, 0.01), OPTFLOW_USE_INITIAL_FLOW: next_pts holds the guesses going in.
   // `temporal` marks the frame-to-frame call (the implementation may keep the previous frame's pyramid).

@@ -51,6 +51,8 @@ std::atomic<uint64_t> g_image_id{1};
 
 }  // namespace
 
+uint64_t NewImageId() { return g_image_id.fetch_add(1); }
+
 ImagePtr decode_png_gray(const uint8_t* b, size_t size)
 {
   static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};

@@ -25,6 +25,7 @@ struct Image {
   const uint8_t* ptr() const { return data.data(); }
 };
 using ImagePtr = std::shared_ptr<const Image>;
+uint64_t NewImageId();                    // the next id of the loader's sequence: for an image made from a loaded one (FrontEnd's undistorted frames)
 
 void LoadKittiImagesTimestamps(const std::string& path_to_sequence, std::vector<std::string>& left_paths,
                                std::vector<std::string>& right_paths, std::vector<double>& timestamps);

@@ -31,7 +31,8 @@ void Camera::world2pixel(const double* p_w, const SE3& T_c_w, float* uv) const
   uv[1] = (float)(fy * pr[1] / pr[2] + cy);
 }
 
-FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right)
+FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right,
+                   const ssx_undistort_params* undistort)
     : compute_(compute), map_(std::move(map)), left_camera_(left), right_camera_(right)
 {
   num_features_init_good_ = cfg.Get<int>("numFeatures.initGood");
@@ -39,8 +40,11 @@ FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> ma
   num_features_tracking_bad_ = cfg.Get<int>("numFeatures.trackingBad");
   min_init_landmark_ = (unsigned)cfg.Get<int>("Min.Init.Landmark.Num");
   open_backend_optimization_ = cfg.Get<int>("Backend.Open") != 0;
-  if (cfg.Get<int>("Camera.NeedUndistortion") != 0)
-    throw std::runtime_error("FrontEnd: Camera.NeedUndistortion != 0 is not supported (rectified input only)");
+  need_undistortion_ = cfg.Get<int>("Camera.NeedUndistortion") != 0;
+  if (need_undistortion_ && !compute.CanUndistort())
+    throw std::runtime_error("FrontEnd: Camera.NeedUndistortion != 0 is not supported by this Compute (rectified input only; there is no CPU fallback)");
+  if (need_undistortion_ && !undistort) throw std::runtime_error("FrontEnd: Camera.NeedUndistortion != 0 without the cameras' undistortion parameters");
+  if (need_undistortion_) { undistort_[0] = undistort[0]; undistort_[1] = undistort[1]; }
   if (left.fx != right.fx || left.fy != right.fy || left.cx != right.cx || left.cy != right.cy)
     throw std::runtime_error("FrontEnd: the two cameras must share their intrinsics (rectified stereo rig)");
   // System::GenerateORBextractor (system.cpp:115-128): nNewFeatures for keyframes, nInitFeatures for initialisation
@@ -57,6 +61,13 @@ FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> ma
 // frontend.cpp:34-80
 bool FrontEnd::GrabSteroImage(ImagePtr left, ImagePtr right, double timestamp)
 {
+  if (need_undistortion_) {                                            // frontend.cpp:39-45: before anything else looks at the images
+    Stopwatch sw(times_.undistort, times_.n_undistort);
+    auto l = std::make_shared<Image>(), r = std::make_shared<Image>();
+    compute_.UndistortPair(*left, *right, undistort_, *l, *r);
+    l->id = NewImageId(); r->id = NewImageId();                        // new images: a resident pyramid of the distorted ones is not theirs
+    left = std::move(l); right = std::move(r);
+  }
   std::lock_guard<std::mutex> map_lock(map_->update_mutex);           // frontend.cpp:49: the whole frame is tracked under the map mutex
   current_frame_ = map_->NewFrame(std::move(left), std::move(right), timestamp);
   switch (track_status_) {

@@ -5,8 +5,9 @@
 //              :448-498 BuidInitMap, :500-544 TriangulateNewPoints, :546-580 InsertKeyFrame
 //              Relocalize: what the reference leaves as a TODO in state LOST (:62-66), behind Relocalization.Open
 // Every arithmetic step of those functions is a Compute call; what is restated here is the bookkeeping between them.
-// Not carried over: the viewer hooks (Pangolin), cv::imshow debugging, image undistortion (KITTI is rectified;
-// Camera.NeedUndistortion != 0 is refused), and the mutexes -- the headless runner is single-threaded.
+// Camera.NeedUndistortion != 0 (:39-45): both images of a frame are replaced by Compute::UndistortPair's before anything looks at them; a
+// Compute that cannot undistort (the CPU oracle of the tests) is refused at construction.
+// Not carried over: the viewer hooks (Pangolin), cv::imshow debugging, and the mutexes -- the headless runner is single-threaded.
 #pragma once
 #include <memory>
 #include <vector>
@@ -29,13 +30,16 @@ class LoopClosing;
 enum class FrontendStatus { INITING, TRACKING_GOOD, TRACKING_BAD, LOST };
 
 struct StageTimes {                                   // wall-clock seconds spent inside the compute calls
-  double detect = 0, lk_temporal = 0, lk_stereo = 0, pose_only = 0, triangulate = 0, bundle_adjust = 0;
-  long n_detect = 0, n_lk_temporal = 0, n_lk_stereo = 0, n_pose_only = 0, n_triangulate = 0, n_bundle_adjust = 0;
+  double detect = 0, lk_temporal = 0, lk_stereo = 0, pose_only = 0, triangulate = 0, bundle_adjust = 0, undistort = 0;
+  long n_detect = 0, n_lk_temporal = 0, n_lk_stereo = 0, n_pose_only = 0, n_triangulate = 0, n_bundle_adjust = 0, n_undistort = 0;
 };
 
 class FrontEnd {
  public:
-  FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right);
+  // undistort: the two cameras' parameters (left, right) when Camera.NeedUndistortion is set (System reads Camera{1,2}.k1/k2/p1/p2);
+  // with the key set, a null pointer or a Compute that cannot undistort throws, naming the key
+  FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right,
+           const ssx_undistort_params* undistort = nullptr);
   void SetBackend(Backend* backend) { backend_ = backend; }
   // Relocalization.Open: 1 -- a LOST front-end asks the loop closing's keyframe database where it is (Relocalize below) instead of
   // ignoring every later frame.  Without a LoopClosing the state LOST is final, as in the reference (frontend.cpp:62-66: a TODO).
@@ -76,6 +80,8 @@ class FrontEnd {
   int num_features_init_good_, num_features_tracking_good_, num_features_tracking_bad_;
   unsigned min_init_landmark_;
   bool open_backend_optimization_;
+  bool need_undistortion_ = false;           // Camera.NeedUndistortion
+  ssx_undistort_params undistort_[2] = {};   // left, right
   std::vector<int32_t> boxes_;               // DetectFeatures: the mask's rectangles (x0, y0, x1, y1)
   std::vector<unsigned long> condemned_;     // EstimateCurrentPose: the map points this frame condemned (taken back when it ends LOST and relocalisation is on)
   StageTimes times_;

@@ -21,6 +21,7 @@
 //   and, with Relocalization.Open: 1, behind them one line per attempt of a lost front-end:
 //   reloc_frame <frame id> candidates <n> pairs <n> poses <n> inliers <n> accepted <keyframe id|-1>
 // Relocalization.Open: 1 works per stream of an unbatched --streams; with --batched >= 1 it is refused.
+// Camera.NeedUndistortion: 1 (every frame's pair goes through ssx_undistort first) likewise: per stream of an unbatched --streams, refused with --batched >= 1.
 // Loop closing is per stream.  --batched >= 1 with Loop.Closing.Open: 1 is refused unless --loop_batched=1 is given: the streams of a cohort
 // then share one loop context and one vocabulary, and their inline keyframe steps go to the GPU as ssx_kfdb_process_keyframe_batch calls
 // (every stream still writes the bytes of its single-stream run).  The loop thread (Loop.Closing.Async: 1) is not batched: refused with it.
@@ -122,6 +123,11 @@ int main(int argc, char** argv)
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Open") != 0) {
       std::fprintf(stderr, "--batched=%s with Relocalization.Open: 1 is not supported: a batched stream's loop context belongs to the dispatcher's thread; "
                    "run --streams unbatched, or switch relocalisation off\n", batched_s.c_str());
+      return 2;
+    }
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Camera.NeedUndistortion") != 0) {
+      std::fprintf(stderr, "--batched=%s with Camera.NeedUndistortion: 1 is not supported: the dispatcher has no batched undistortion call yet; "
+                   "run --streams unbatched, or feed rectified images\n", batched_s.c_str());
       return 2;
     }
     if (loop_batched && Setting(config).Get<int>("Loop.Closing.Open") != 0 && Setting(config).Get<int>("Loop.Closing.Async") != 0) {
@@ -268,6 +274,7 @@ int main(int argc, char** argv)
     auto line = [](const char* name, double s, long n) {
       if (n) std::printf("  %-24s %6ld calls  %8.3f ms/call\n", name, n, 1e3 * s / n);
     };
+    line("undistort (pair)", st.undistort, st.n_undistort);
     line("Detect", st.detect, st.n_detect);
     line("LK last -> current", st.lk_temporal, st.n_lk_temporal);
     line("LK left -> right", st.lk_stereo, st.n_lk_stereo);

@@ -26,9 +26,22 @@ System::System(const std::string& config_file_path, std::unique_ptr<Compute> com
   left_camera_ = Camera{fx_l, fy_l, cx_l, cy_l, 0.0, SE3()};
   right_camera_ = Camera{fx_r, fy_r, cx_r, cy_r, baseline, SE3::translation(-(double)baseline, 0, 0)};
 
+  // system.cpp:73-94: the distortion coefficients are read as float and widened, only when the key is set; K_cv is the camera's
+  // intrinsics as float (camera.cpp:47-52), k3 = 0, R = I and the new camera matrix is the old one (cv::undistort's defaults)
+  need_undistortion_ = setting_.Get<int>("Camera.NeedUndistortion") != 0;
+  if (need_undistortion_) {
+    const Camera* cam[2] = {&left_camera_, &right_camera_};
+    for (int c = 0; c < 2; ++c) {
+      const std::string key = c == 0 ? "Camera1." : "Camera2.";
+      const double K4[4] = {cam[c]->fx, cam[c]->fy, cam[c]->cx, cam[c]->cy};
+      const double dist5[5] = {setting_.Get<float>(key + "k1"), setting_.Get<float>(key + "k2"), setting_.Get<float>(key + "p1"), setting_.Get<float>(key + "p2"), 0.0};
+      ssx_undistort_default(K4, dist5, &undistort_[c]);
+    }
+  }
+
   map_ = std::make_shared<Map>((unsigned)setting_.Get<int>("Map.ActiveMap.Size"));
   backend_ = std::make_unique<Backend>(setting_, *compute_, map_, left_camera_, right_camera_);
-  frontend_ = std::make_unique<FrontEnd>(setting_, *compute_, map_, left_camera_, right_camera_);
+  frontend_ = std::make_unique<FrontEnd>(setting_, *compute_, map_, left_camera_, right_camera_, need_undistortion_ ? undistort_ : nullptr);
   frontend_->SetBackend(backend_.get());
 
   // system.cpp:17-41
@@ -86,7 +99,7 @@ void System::Warmup(int rows, int cols)
     auto im = std::make_shared<Image>();
     im->rows = rows; im->cols = cols; im->id = id; im->data.resize((size_t)rows * cols);
     auto h = [](int x, int y, int o) {
-      uint32_t v = (uint32_t)(x * 73856093) ^ (uint32_t)(y * 19349663) ^ (uint32_t)(o * 83492791);
+      uint32_t v = ((uint32_t)x * 73856093u) ^ ((uint32_t)y * 19349663u) ^ ((uint32_t)o * 83492791u);   // (unsigned: the products wrap)
       v ^= v >> 13; v *= 0x5bd1e995u; v ^= v >> 15;
       return (double)(v & 0xffff) / 65535.0;
     };
@@ -107,6 +120,10 @@ void System::Warmup(int rows, int cols)
   // (ids far from the loader's: a resident pyramid or a pinned copy of these images is never mistaken for a frame's)
   const uint64_t id0 = ~uint64_t(0) - 16;
   ImagePtr L0 = make(0.0, id0), R0 = make(9.0, id0 + 1), L1 = make(1.5, id0 + 2), L2 = make(3.0, id0 + 3);
+  if (need_undistortion_) {                                            // the frame's first call: the kernel is loaded, the staging sized
+    Image ul, ur;
+    compute_->UndistortPair(*L0, *R0, undistort_, ul, ur);
+  }
   ssx_orb_params prm{};
   prm.nfeatures = std::max(setting_.Get<int>("ORBextractor.nInitFeatures"), setting_.Get<int>("ORBextractor.nNewFeatures"));
   prm.scale_factor = setting_.Get<float>("ORBextractor.scaleFactor"); prm.nlevels = setting_.Get<int>("ORBextractor.nLevels");

@@ -1,6 +1,6 @@
 // ssvio_amd/host/system.hpp -- ssvio::System without the viewer (/root/reference/src/ssvio/system.cpp:9-128):
 // reads the settings file, builds the stereo rig (GenerateSteroCamera :54-113), the two extractor settings
-// (GenerateORBextractor :115-128), Map, Backend, FrontEnd and -- with Loop.Closing.Open set -- LoopClosing (:17-41);
+// (GenerateORBextractor :115-128), the distortion coefficients when Camera.NeedUndistortion is set (:73-94), Map, Backend, FrontEnd and -- with Loop.Closing.Open set -- LoopClosing (:17-41);
 // RunStep = FrontEnd::GrabSteroImage (:46-52).
 // SaveTrajectoryTUM is the trajectory writer the reference keeps in its viewer
 // (/root/reference/src/ui/pangolin_window_impl.cpp:362-395): every keyframe in id order,
@@ -46,6 +46,8 @@ class System {
   Setting setting_;
   std::unique_ptr<Compute> compute_;
   Camera left_camera_, right_camera_;
+  bool need_undistortion_ = false;                                         // Camera.NeedUndistortion
+  ssx_undistort_params undistort_[2] = {};                                 // left, right: K as the cameras', Camera{1,2}.k1/k2/p1/p2, k3 = 0, R = I
   std::shared_ptr<Map> map_;
   std::unique_ptr<Backend> backend_;
   std::unique_ptr<FrontEnd> frontend_;
