@@ -1,49 +1,62 @@
-// ssvio_amd/host/stream_batcher.cpp -- see stream_batcher.hpp
+// ssvio_amd/host/stream_batcher.cpp -- see stream_batcher.hpp: the request kinds (what a stream files, what a call's jobs must share,
+// the library call) and the three adapters that file them; who is served when is batch_dispatch.hpp
 #include "stream_batcher.hpp"
 
 #include <algorithm>
-#include <chrono>
+#include <array>
 #include <cstring>
 #include <functional>
 #include <map>
 #include <stdexcept>
+#include <tuple>
 
 #include "../../include/ssx_shim.hpp"
+#include "batch_dispatch.hpp"
 
 namespace ssx::host {
 
 namespace {
-enum class St { RUNNING, PENDING_LK, PENDING_PO, PENDING_DET, PENDING_LKS, PENDING_TRI, PENDING_BA, PENDING_LOOP, PENDING_CALL, INFLIGHT, LONGOP, DONE, IDLE };
+enum Kind : int { LK, PO, DET, LKS, TRI, BA, LOOP, CALL, N_KINDS };   // indices into the table of Impl::Kinds
+// what the jobs of one call share -- the keys of Groups
+struct ImageSize {
+  int rows = 0, cols = 0;
+  bool operator==(const ImageSize& o) const { return rows == o.rows && cols == o.cols; }
+  bool operator<(const ImageSize& o) const { return std::tie(rows, cols) < std::tie(o.rows, o.cols); }
+};
+using OrbParamBytes = std::array<unsigned char, sizeof(ssx_orb_params)>;   // (extractor settings are equal when their bytes are)
+OrbParamBytes Bytes(const ssx_orb_params& p)
+{
+  OrbParamBytes b;
+  std::memcpy(b.data(), &p, sizeof p);
+  return b;
+}
+// the per-slot requests
+struct LkReq { ssx_lk_job job{}; ImageSize size; };   // temporal and stereo LK
+struct DetReq { ssx_orb_detect_job job{}; ssx_orb_params prm{}; ImageSize size; };
+struct BaReq { ssx_ba_window* win = nullptr; ssx_ba_result* res = nullptr; };
 // one keyframe step of loop closing as a stream files it (ssx_kfdb_process_keyframe_batch): the job and what a call's jobs must share
-struct LoopReq { ssx_kfdb_step_job job{}; ssx_orb_params prm{}; int rows = 0, cols = 0, levels = 0, min_db = 0, min_gap = 0; float threshold = 0.f; int32_t status = 0; };
+struct LoopReq { ssx_kfdb_step_job job{}; ssx_orb_params prm{}; ImageSize size; int levels = 0, min_db = 0, min_gap = 0; float threshold = 0.f; int32_t status = 0; };
 }
 
 struct StreamBatcher::Impl {
-  // Request slots: k < S is stream k's own thread (one request at a time); S + k is the worker thread of stream k's backend when the
-  // backend is asynchronous (Backend.Async: 1 -- it files window solves while the stream's thread goes on tracking).  A backend slot
-  // rests in IDLE, which no dispatcher waits for.
-  Impl(int device_, int streams) : device(device_), S(streams), po_ctx(device_), ba_ctx(device_), det_ctx(device_),
-                                   tri_ctx(device_), state(2 * (size_t)streams, St::RUNNING), lk_req(streams), lk_rows(streams, 0), lk_cols(streams, 0),
-                                   po_req(streams), det_req(streams), det_prm(streams), tri_req(streams), ba_win(2 * (size_t)streams, nullptr),
-                                   ba_res(2 * (size_t)streams, nullptr), loop_req(2 * (size_t)streams), call_req(2 * (size_t)streams, nullptr),
-                                   error(2 * (size_t)streams)
+  // Request slots (batch_dispatch.hpp): k < S is stream k's own thread; S + k is the worker thread of stream k's backend when the
+  // backend is asynchronous (Backend.Async: 1 -- it files window solves while the stream's thread goes on tracking).
+  // The two dispatchers.  Per frame, pose-only first: the cohort then reaches its next LK request where a straggler from a keyframe
+  // already waits (see the header).  The keyframe path of the streams (FrontEnd::DetectFeatures -> FindFeaturesInRight ->
+  // TriangulateNewPoints -> Backend: masked detection, stereo LK, triangulation, window optimisation) is batched like the per-frame
+  // calls, on contexts of its own beside them.  The EARLIEST stage that has requests is served first, so that streams which reached
+  // their keyframe a little later catch up and all of them meet in one window solve (a batched solve costs what a single one costs).
+  // The loop step follows the window solve inside the backend: served after it, the streams that solved a little later merge into one
+  // loop call; the rare single calls of a correction come last.
+  Impl(int device_, int streams) : device(device_), S(streams), po_ctx(device_), ba_ctx(device_), det_ctx(device_), tri_ctx(device_), lk_req(streams),
+                                   po_req(streams), det_req(streams), tri_req(streams), ba_req(2 * (size_t)streams), loop_req(2 * (size_t)streams),
+                                   call_req(2 * (size_t)streams, nullptr),
+                                   core(streams, Kinds(), {{PO, LK}, false, false}, {{DET, LKS, TRI, BA, LOOP, CALL}, true, true})
   {
-    n_in[(int)St::RUNNING] = streams;
-    n_in[(int)St::IDLE] = streams;
-    for (int k = 0; k < streams; ++k) state[(size_t)S + k] = St::IDLE;
-    for (int k = 0; k < 2 * streams; ++k) sleeper.push_back(std::make_unique<Sleeper>());
-    disp = std::thread([this] { DispatchLoop(); });
-    ba_disp = std::thread([this] { KeyframeLoop(); });
   }
   ~Impl()
   {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      quit = true;
-    }
-    cv_disp.notify_all();
-    if (disp.joinable()) disp.join();
-    if (ba_disp.joinable()) ba_disp.join();
+    // (the streams have finished: the dispatchers, which stop with `core`, are idle)
     if (voc) ssx_voc_destroy(voc);                  // (the streams' databases went with their Systems)
     ssx_host_free(pin_arena);
   }
@@ -77,10 +90,10 @@ struct StreamBatcher::Impl {
     explicit SizeCtx(int device) : lk(device), lks(device) {}
     ssx::Context lk, lks;
   };
-  SizeCtx& ForSize(int rows, int cols)
+  SizeCtx& ForSize(ImageSize size)
   {
     std::lock_guard<std::mutex> lk(size_mu);        // (both dispatchers come here)
-    std::unique_ptr<SizeCtx>& p = size_ctx[{rows, cols}];
+    std::unique_ptr<SizeCtx>& p = size_ctx[size];
     if (!p) p = std::make_unique<SizeCtx>(device);
     return *p;
   }
@@ -104,260 +117,116 @@ struct StreamBatcher::Impl {
     return pin_arena + ((size_t)which * S + k) * pin_slice;
   }
 
-  int count(St s) const { return n_in[(int)s]; }
-  // (m held) -- the dispatchers' conditions can only BECOME true when the last running stream stops running: they are woken then,
-  // not at every one of the S state changes of a round
-  bool Move(int k, St s)
+  // A kind's callable: the requests of a dispatch in groups of equal key(slot), one library call per group -- call(slots, errs), errs[j]
+  // for slots[j] -- and job by job where a call is rejected (Isolated)
+  template <class Key, class Call>
+  static auto Grouped(Key key, Call call)
   {
-    --n_in[(int)state[k]]; ++n_in[(int)s];
-    state[k] = s;
-    return n_in[(int)St::RUNNING] == 0;
-  }
-
-  // the calling stream sleeps until a dispatcher has served its request; throws what the batch call reported.  Every stream sleeps
-  // on a condition variable of its own: S streams woken through one shared mutex queue up behind each other (64 wake-ups x a futex
-  // round trip each: more than the batched call they waited for).
-  void SubmitAndWait(int k, St pending)
-  {
-    bool wake;
-    {
-      std::lock_guard<std::mutex> lk(m);
-      error[k].clear();
-      wake = Move(k, pending);
-    }
-    if (wake) cv_disp.notify_all();
-    Sleeper& sl = *sleeper[k];
-    std::unique_lock<std::mutex> lk(sl.mu);
-    sl.cv.wait(lk, [&] { return sl.done; });
-    sl.done = false;
-    if (!error[k].empty()) throw std::runtime_error(error[k]);
-  }
-  void SetState(int k, St s)
-  {
-    bool wake;
-    {
-      std::lock_guard<std::mutex> lk(m);
-      wake = Move(k, s);
-    }
-    if (wake) cv_disp.notify_all();
-  }
-  // (m held by the caller) the streams of a finished batch run again
-  void Release(const std::vector<int>& who, const std::vector<std::string>& errs)
-  {
-    for (size_t i = 0; i < who.size(); ++i) { error[who[i]] = errs[i]; Move(who[i], who[i] < S ? St::RUNNING : St::IDLE); }
-  }
-  // One batched call for the requests idx (positions in `who`).  If it fails, every request goes once more in a call of its own:
-  // only the stream whose request is at fault sees the error, the others get their results (the library validates a job table before
-  // it touches anything, so a rejected call has not run any of its jobs).
-  template <class F>
-  static void Isolated(const std::vector<size_t>& idx, std::vector<std::string>& errs, long& calls, long& jobs, F&& call)
-  {
-    try {
-      call(idx);
-      ++calls; jobs += (long)idx.size();
-      return;
-    } catch (const std::exception& e) {
-      if (idx.size() == 1) { errs[idx[0]] = e.what(); return; }
-    }
-    for (size_t i : idx) {
-      try { call(std::vector<size_t>{i}); ++calls; ++jobs; } catch (const std::exception& e) { errs[i] = e.what(); }
-    }
-  }
-  // the requests of `who` in groups of equal key (image size, extractor settings ...): one call per group
-  template <class Same>
-  static std::vector<std::vector<size_t>> Groups(size_t n, Same&& same)
-  {
-    std::vector<std::vector<size_t>> g;
-    std::vector<char> taken(n, 0);
-    for (size_t a = 0; a < n; ++a) {
-      if (taken[a]) continue;
-      g.emplace_back();
-      for (size_t b = a; b < n; ++b) if (!taken[b] && same(a, b)) { g.back().push_back(b); taken[b] = 1; }
-    }
-    return g;
-  }
-  void LkCall(ssx::Context& ctx, const std::vector<int>& who, const std::vector<size_t>& sub)
-  {
-    std::vector<ssx_lk_job> jobs;
-    for (size_t i : sub) jobs.push_back(lk_req[who[i]]);
-    ssx_lk_params p;
-    ssx_lk_default_params(&p);
-    p.win = 11; p.max_level = 3; p.max_iters = 30; p.eps = 0.01; p.use_initial_flow = 1;
-    ctx.check(ssx_lk_track_batch(ctx.get(), (int32_t)jobs.size(), jobs.data(), lk_rows[who[sub[0]]], lk_cols[who[sub[0]]], &p, 1));
-  }
-  void WakeStreams(const std::vector<int>& who)
-  {
-    for (int k : who) {
-      Sleeper& sl = *sleeper[k];
-      { std::lock_guard<std::mutex> lk(sl.mu); sl.done = true; }
-      sl.cv.notify_one();
-    }
-  }
-
-  void DispatchLoop()
-  {
-    std::unique_lock<std::mutex> lk(m);
-    std::vector<int> who;
-    using clk = std::chrono::steady_clock;
-    for (;;) {
-      const auto tw0 = clk::now();
-      cv_disp.wait(lk, [&] { return quit || (count(St::RUNNING) == 0 && count(St::PENDING_LK) + count(St::PENDING_PO) > 0); });
-      if (quit) return;
-      st.wait_s += std::chrono::duration<double>(clk::now() - tw0).count();
-      // pose-only first: the cohort then reaches its next LK request where a straggler from a keyframe already waits (see the header)
-      const St kind = count(St::PENDING_PO) > 0 ? St::PENDING_PO : St::PENDING_LK;
-      who.clear();
-      for (int k = 0; k < S; ++k) if (state[k] == kind) { who.push_back(k); Move(k, St::INFLIGHT); }
-      lk.unlock();
-      std::vector<std::string> errs(who.size());
-      long d_calls = 0, d_jobs = 0;
-      const auto tc0 = clk::now();
-      if (kind == St::PENDING_PO) {
-        std::vector<size_t> all(who.size());
-        for (size_t i = 0; i < all.size(); ++i) all[i] = i;
-        Isolated(all, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
-          std::vector<ssx_pose_only_job> jobs;
-          for (size_t i : sub) jobs.push_back(po_req[who[i]]);
-          po_ctx.check(ssx_pose_only_opt_batch(po_ctx.get(), (int32_t)jobs.size(), jobs.data()));
+    return [key, call](const std::vector<int>& who, std::vector<std::string>& errs, long& calls, long& jobs) {
+      std::vector<decltype(key(0))> keys;
+      for (int k : who) keys.push_back(key(k));
+      for (const auto& g : Groups(keys))
+        Isolated(g, errs, calls, jobs, [&](const std::vector<size_t>& sub) {
+          std::vector<int> slots;
+          for (size_t i : sub) slots.push_back(who[i]);
+          std::vector<std::string> e(sub.size());
+          call(slots, e);
+          for (size_t j = 0; j < sub.size(); ++j) if (!e[j].empty()) errs[sub[j]] = e[j];
         });
-      } else {
-        // (jobs of one call share the image size: the streams of another size go in a call of their own, on that size's context --
-        // their chains live there)
-        for (const auto& g : Groups(who.size(), [&](size_t a, size_t b) { return lk_rows[who[a]] == lk_rows[who[b]] && lk_cols[who[a]] == lk_cols[who[b]]; }))
-          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) { LkCall(ForSize(lk_rows[who[sub[0]]], lk_cols[who[sub[0]]]).lk, who, sub); });
-      }
-      const double dt = std::chrono::duration<double>(clk::now() - tc0).count();
-      lk.lock();
-      if (kind == St::PENDING_PO) { st.po_calls += d_calls; st.po_jobs += d_jobs; st.po_s += dt; } else { st.lk_calls += d_calls; st.lk_jobs += d_jobs; st.lk_s += dt; }
-      Release(who, errs);
-      lk.unlock();
-      WakeStreams(who);
-      lk.lock();
-    }
-  }
-
-  // The keyframe path of the streams (FrontEnd::DetectFeatures -> FindFeaturesInRight -> TriangulateNewPoints -> Backend: masked
-  // detection, stereo LK, triangulation, window optimisation), batched like the per-frame calls, on contexts of its own beside them.
-  // The EARLIEST stage that has requests is served first, so that streams which reached their keyframe a little later catch up and
-  // all of them meet in one window solve (a batched solve costs what a single one costs).
-  void KeyframeLoop()
-  {
-    std::unique_lock<std::mutex> lk(m);
-    std::vector<int> who;
-    auto n_kf = [&] {
-      return count(St::PENDING_DET) + count(St::PENDING_LKS) + count(St::PENDING_TRI) + count(St::PENDING_BA) + count(St::PENDING_LOOP) + count(St::PENDING_CALL);
     };
-    for (;;) {
-      // (streams in a call of their own -- LONGOP -- are about to file the next request of this path: wait for them)
-      const bool at_rest = cv_disp.wait_for(lk, std::chrono::milliseconds(2), [&] { return quit || (n_kf() > 0 && count(St::RUNNING) == 0 && count(St::LONGOP) == 0); });
-      if (quit) return;
-      if (!at_rest) {
-        // An asynchronous backend's window solve has waited 2 ms for the front-ends to come to rest -- they may be waiting for IT
-        // (Backend::WaitIdle at the end of a sequence, the map mutex): it is served with what has gathered so far.
-        bool backend_waits = false;
-        for (int k = S; k < 2 * S; ++k) backend_waits = backend_waits || state[k] == St::PENDING_BA || state[k] == St::PENDING_LOOP || state[k] == St::PENDING_CALL;
-        if (!backend_waits) continue;
-      }
-      // (the loop step follows the window solve inside the backend: served after it, the streams that solved a little later merge into
-      // one loop call; the rare single calls of a correction come last)
-      const St kind = count(St::PENDING_DET) > 0 ? St::PENDING_DET : count(St::PENDING_LKS) > 0 ? St::PENDING_LKS : count(St::PENDING_TRI) > 0 ? St::PENDING_TRI
-                      : count(St::PENDING_BA) > 0 ? St::PENDING_BA : count(St::PENDING_LOOP) > 0 ? St::PENDING_LOOP : St::PENDING_CALL;
-      who.clear();
-      for (int k = 0; k < 2 * S; ++k) if (state[k] == kind) { who.push_back(k); Move(k, St::INFLIGHT); }
-      lk.unlock();
-      cv_disp.notify_all();                         // (the per-frame dispatcher does not wait for streams that are in flight here)
-      std::vector<std::string> errs(who.size());
-      long d_calls = 0, d_jobs = 0;
-      const auto tb0 = std::chrono::steady_clock::now();
-      std::vector<size_t> all(who.size());
-      for (size_t i = 0; i < all.size(); ++i) all[i] = i;
-      if (kind == St::PENDING_CALL) {
-        // ComputeCorrectPose, LoopCorrect and the window's loop correction: one at a time, here, so that none runs on the loop context or
-        // the window context beside a batched call of this dispatcher
-        for (size_t i = 0; i < who.size(); ++i) {
-          try { (*call_req[who[i]])(); } catch (const std::exception& e) { errs[i] = e.what(); }
+  }
+  static int NoKey(int) { return 0; }
+
+  std::vector<BatchDispatch::Kind> Kinds()
+  {
+    using Slots = const std::vector<int>&;
+    using Errs = std::vector<std::string>&;
+    // (jobs of one call share the image size: the streams of another size go in a call of their own, on that size's context -- their
+    // chains live there)
+    auto lk_size = [this](int k) { return lk_req[k].size; };
+    auto lk_call = [this](bool stereo) {
+      return [this, stereo](Slots slots, Errs) {
+        const ImageSize size = lk_req[slots[0]].size;
+        SizeCtx& sc = ForSize(size);
+        ssx::Context& ctx = stereo ? sc.lks : sc.lk;
+        std::vector<ssx_lk_job> jobs;
+        for (int k : slots) jobs.push_back(lk_req[k].job);
+        ssx_lk_params p;
+        ssx_lk_default_params(&p);
+        p.win = 11; p.max_level = 3; p.max_iters = 30; p.eps = 0.01; p.use_initial_flow = 1;
+        ctx.check(ssx_lk_track_batch(ctx.get(), (int32_t)jobs.size(), jobs.data(), size.rows, size.cols, &p, 1));
+      };
+    };
+    std::vector<BatchDispatch::Kind> t(N_KINDS);
+    t[LK] = {"temporal LK", Grouped(lk_size, lk_call(false))};
+    t[LKS] = {"stereo LK", Grouped(lk_size, lk_call(true))};
+    t[PO] = {"pose-only", Grouped(NoKey, [this](Slots slots, Errs) {
+      std::vector<ssx_pose_only_job> jobs;
+      for (int k : slots) jobs.push_back(po_req[k]);
+      po_ctx.check(ssx_pose_only_opt_batch(po_ctx.get(), (int32_t)jobs.size(), jobs.data()));
+    })};
+    // detection: the jobs of a call share image size, stride and extractor settings
+    t[DET] = {"detection", Grouped([this](int k) { return std::make_tuple(det_req[k].size, det_req[k].job.stride, Bytes(det_req[k].prm)); }, [this](Slots slots, Errs) {
+      std::vector<ssx_orb_detect_job> jobs;
+      for (int k : slots) jobs.push_back(det_req[k].job);
+      const DetReq& r0 = det_req[slots[0]];
+      const ssx_status rc = ssx_orb_detect_boxes_batch(det_ctx.get(), (int32_t)jobs.size(), jobs.data(), r0.size.rows, r0.size.cols, &r0.prm, 1);
+      // (SSX_ERR_CAPACITY is per image -- the other images of the call are complete: every stream looks at its own count)
+      if (rc != SSX_ERR_CAPACITY) det_ctx.check(rc);
+    })};
+    t[TRI] = {"triangulation", Grouped(NoKey, [this](Slots slots, Errs) {
+      std::vector<ssx_triangulate_job> jobs;
+      for (int k : slots) jobs.push_back(tri_req[k]);
+      tri_ctx.check(ssx_triangulate_batch(tri_ctx.get(), (int32_t)jobs.size(), jobs.data()));
+    })};
+    t[BA] = {"window solve", Grouped(NoKey, [this](Slots slots, Errs) {
+      std::vector<ssx_ba_window*> wins;
+      std::vector<ssx_ba_result> res;
+      for (int k : slots) { wins.push_back(ba_req[k].win); res.push_back(*ba_req[k].res); }
+      ba_ctx.check(ssx_ba_window_solve_batch((int32_t)wins.size(), wins.data(), res.data()));
+      for (size_t j = 0; j < slots.size(); ++j) *ba_req[slots[j]].res = res[j];
+    })};
+    auto loop_key = [this](int k) {
+      const LoopReq& r = loop_req[k];
+      return std::make_tuple(r.size, r.job.stride, Bytes(r.prm), r.levels, r.min_db, r.min_gap, r.threshold);
+    };
+    t[LOOP] = {"loop step", Grouped(loop_key, [this](Slots slots, Errs errs) {
+      std::vector<ssx_kfdb_step_job> jobs;
+      for (int k : slots) { LoopReq& r = loop_req[k]; r.status = SSX_OK; r.job.status_out = &r.status; jobs.push_back(r.job); }
+      const LoopReq& r0 = loop_req[slots[0]];
+      const ssx_status rc = ssx_kfdb_process_keyframe_batch(voc, (int32_t)jobs.size(), jobs.data(), r0.size.rows, r0.size.cols, &r0.prm, r0.levels, r0.min_db,
+                                                            r0.min_gap, r0.threshold, 1);
+      if (rc == SSX_OK) return;
+      // The call returns the first job status that is not SSX_OK: a return value that one of the jobs carries is that job's own
+      // outcome, the other jobs are complete (SSX_ERR_CAPACITY: the stream asks again with the room the count names).  Any other
+      // value is a failure of the whole call.
+      bool per_job = false;
+      for (int k : slots) per_job = per_job || loop_req[k].status == (int32_t)rc;
+      const std::string why = ssx_last_error(loop_ctx->get());
+      if (per_job) {
+        for (size_t j = 0; j < slots.size(); ++j) {
+          const int32_t js = loop_req[slots[j]].status;
+          if (js != SSX_OK && js != SSX_ERR_CAPACITY) errs[j] = "ssx_kfdb_process_keyframe_batch: job status " + std::to_string(js) + ": " + why;
         }
-      } else if (kind == St::PENDING_LOOP) {
-        auto same = [&](size_t a, size_t b) {
-          const LoopReq &x = loop_req[who[a]], &y = loop_req[who[b]];
-          return x.rows == y.rows && x.cols == y.cols && x.job.stride == y.job.stride && std::memcmp(&x.prm, &y.prm, sizeof(ssx_orb_params)) == 0 &&
-                 x.levels == y.levels && x.min_db == y.min_db && x.min_gap == y.min_gap && x.threshold == y.threshold;
-        };
-        for (const auto& g : Groups(who.size(), same))
-          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
-            std::vector<ssx_kfdb_step_job> jobs;
-            for (size_t i : sub) { LoopReq& r = loop_req[who[i]]; r.status = SSX_OK; r.job.status_out = &r.status; jobs.push_back(r.job); }
-            const LoopReq& r0 = loop_req[who[sub[0]]];
-            const ssx_status rc = ssx_kfdb_process_keyframe_batch(voc, (int32_t)jobs.size(), jobs.data(), r0.rows, r0.cols, &r0.prm, r0.levels, r0.min_db, r0.min_gap,
-                                                                  r0.threshold, 1);
-            if (rc == SSX_OK) return;
-            // The call returns the first job status that is not SSX_OK: a return value that one of the jobs carries is that job's own
-            // outcome, the other jobs are complete (SSX_ERR_CAPACITY: the stream asks again with the room the count names).  Any other
-            // value is a failure of the whole call.
-            bool per_job = false;
-            for (size_t i : sub) per_job = per_job || loop_req[who[i]].status == (int32_t)rc;
-            const std::string why = ssx_last_error(loop_ctx->get());
-            if (per_job) {
-              for (size_t i : sub) {
-                const int32_t js = loop_req[who[i]].status;
-                if (js != SSX_OK && js != SSX_ERR_CAPACITY) errs[i] = "ssx_kfdb_process_keyframe_batch: job status " + std::to_string(js) + ": " + why;
-              }
-              return;
-            }
-            // a HIP error: the library had begun (commits may be lost, nothing is pending any more), so no job of the call has a result and
-            // none is tried again; every stream of the call gets the error, and its AddPending stays unserved
-            if (rc == SSX_ERR_HIP) {
-              for (size_t i : sub) errs[i] = "ssx_kfdb_process_keyframe_batch: " + why;
-              return;
-            }
-            loop_ctx->check(rc);                    // rejected before anything was touched: Isolated tries the jobs one by one
-          });
-      } else if (kind == St::PENDING_BA) {
-        Isolated(all, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
-          std::vector<ssx_ba_window*> wins;
-          std::vector<ssx_ba_result> res;
-          for (size_t i : sub) { wins.push_back(ba_win[who[i]]); res.push_back(*ba_res[who[i]]); }
-          ba_ctx.check(ssx_ba_window_solve_batch((int32_t)wins.size(), wins.data(), res.data()));
-          for (size_t j = 0; j < sub.size(); ++j) *ba_res[who[sub[j]]] = res[j];
-        });
-      } else if (kind == St::PENDING_TRI) {
-        Isolated(all, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
-          std::vector<ssx_triangulate_job> jobs;
-          for (size_t i : sub) jobs.push_back(tri_req[who[i]]);
-          tri_ctx.check(ssx_triangulate_batch(tri_ctx.get(), (int32_t)jobs.size(), jobs.data()));
-        });
-      } else if (kind == St::PENDING_LKS) {
-        for (const auto& g : Groups(who.size(), [&](size_t a, size_t b) { return lk_rows[who[a]] == lk_rows[who[b]] && lk_cols[who[a]] == lk_cols[who[b]]; }))
-          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) { LkCall(ForSize(lk_rows[who[sub[0]]], lk_cols[who[sub[0]]]).lks, who, sub); });
-      } else {
-        // detection: the jobs of a call share image size, stride and extractor settings
-        auto same = [&](size_t a, size_t b) {
-          const int ka = who[a], kb = who[b];
-          return lk_rows[kb] == lk_rows[ka] && lk_cols[kb] == lk_cols[ka] && det_req[kb].stride == det_req[ka].stride &&
-                 std::memcmp(&det_prm[kb], &det_prm[ka], sizeof(ssx_orb_params)) == 0;
-        };
-        for (const auto& g : Groups(who.size(), same))
-          Isolated(g, errs, d_calls, d_jobs, [&](const std::vector<size_t>& sub) {
-            std::vector<ssx_orb_detect_job> jobs;
-            for (size_t i : sub) jobs.push_back(det_req[who[i]]);
-            const int k0 = who[sub[0]];
-            const ssx_status rc = ssx_orb_detect_boxes_batch(det_ctx.get(), (int32_t)jobs.size(), jobs.data(), lk_rows[k0], lk_cols[k0], &det_prm[k0], 1);
-            // (SSX_ERR_CAPACITY is per image -- the other images of the call are complete: every stream looks at its own count)
-            if (rc != SSX_ERR_CAPACITY) det_ctx.check(rc);
-          });
+        return;
       }
-      (void)d_calls; (void)d_jobs;
-      const double dtb = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count();
-      lk.lock();
-      if (kind == St::PENDING_BA) { ++st.ba_calls; st.ba_jobs += (long)who.size(); st.ba_s += dtb; }
-      else if (kind == St::PENDING_LOOP) { st.loop_calls += d_calls; st.loop_jobs += d_jobs; st.loop_s += dtb; }
-      else if (kind == St::PENDING_CALL) { st.single_calls += (long)who.size(); st.single_s += dtb; }
-      else { ++st.kf_calls; st.kf_jobs += (long)who.size(); st.kf_s += dtb; }
-      Release(who, errs);
-      lk.unlock();
-      WakeStreams(who);
-      lk.lock();
-    }
+      // a HIP error: the library had begun (commits may be lost, nothing is pending any more), so no job of the call has a result and
+      // none is tried again; every stream of the call gets the error, and its AddPending stays unserved
+      if (rc == SSX_ERR_HIP) {
+        for (std::string& e : errs) e = "ssx_kfdb_process_keyframe_batch: " + why;
+        return;
+      }
+      loop_ctx->check(rc);                          // rejected before anything was touched: Isolated tries the jobs one by one
+    })};
+    // ComputeCorrectPose, LoopCorrect and the window's loop correction: one at a time, here, so that none runs on the loop context or
+    // the window context beside a batched call of this dispatcher
+    t[CALL] = {"single call", [this](Slots slots, Errs errs, long& calls, long& jobs) {
+      for (size_t i = 0; i < slots.size(); ++i) {
+        try { (*call_req[slots[i]])(); } catch (const std::exception& e) { errs[i] = e.what(); }
+      }
+      calls += (long)slots.size(); jobs += (long)slots.size();
+    }};
+    return t;
   }
 
   std::mutex pin_mu;
@@ -366,45 +235,26 @@ struct StreamBatcher::Impl {
   int device, S;
   ssx::Context po_ctx, ba_ctx, det_ctx, tri_ctx;
   std::mutex size_mu;
-  std::map<std::pair<int, int>, std::unique_ptr<SizeCtx>> size_ctx;   // (rows, cols) -> that size's LK contexts
-  std::mutex m;
-  std::condition_variable cv_disp;
-  struct Sleeper { std::mutex mu; std::condition_variable cv; bool done = false; };
-  std::vector<std::unique_ptr<Sleeper>> sleeper;
-  int n_in[16] = {0};                               // streams per state
-  std::vector<St> state;
-  std::vector<ssx_lk_job> lk_req;
-  std::vector<int> lk_rows, lk_cols;
+  std::map<ImageSize, std::unique_ptr<SizeCtx>> size_ctx;   // that size's LK contexts
+  std::vector<LkReq> lk_req;
   std::vector<ssx_pose_only_job> po_req;
-  std::vector<ssx_orb_detect_job> det_req;
-  std::vector<ssx_orb_params> det_prm;
+  std::vector<DetReq> det_req;
   std::vector<ssx_triangulate_job> tri_req;
-  std::vector<ssx_ba_window*> ba_win;
-  std::vector<ssx_ba_result*> ba_res;
+  std::vector<BaReq> ba_req;
   std::mutex loop_mu;                               // the making of the loop context, the vocabulary and the databases
   std::unique_ptr<ssx::Context> loop_ctx;
   ssx_vocabulary* voc = nullptr;
   std::string loop_voc_path;
   std::vector<LoopReq> loop_req;
   std::vector<std::function<void()>*> call_req;
-  std::vector<std::string> error;
-  StreamBatcher::Stats st;
-  bool quit = false;
-  std::thread disp, ba_disp;
+  BatchDispatch core;                               // (last: its threads start when the rest is made and stop before it goes)
 };
 
 namespace {
 
-struct LongOp {                                   // a call the stream makes on its own context (a keyframe's path)
-  StreamBatcher::Impl& im; int k;
-  LongOp(StreamBatcher::Impl& i, int k_) : im(i), k(k_) { im.SetState(k, St::LONGOP); }
-  ~LongOp() { im.SetState(k, St::RUNNING); }
-};
-
 class BatchedBaWindow final : public BaWindow {
  public:
-  BatchedBaWindow(StreamBatcher::Impl& im, int k, const double* K4, const double* cam_ext14, const ssx_ba_options& opt)
-      : im_(im), k_(k), owner_(std::this_thread::get_id())
+  BatchedBaWindow(StreamBatcher::Impl& im, int k, const double* K4, const double* cam_ext14, const ssx_ba_options& opt) : im_(im), k_(k)
   {
     im_.ba_ctx.check(ssx_ba_window_create(im_.ba_ctx.get(), &opt, K4, cam_ext14, &win_));
     im_.ba_ctx.check(ssx_ba_window_set_fix_rule(win_, 1));
@@ -432,17 +282,17 @@ class BatchedBaWindow final : public BaWindow {
   {
     // the stream's own thread files the request in the stream's slot; the worker thread of an asynchronous backend has a slot of its
     // own (the stream's thread goes on filing per-frame requests meanwhile)
-    const int slot = std::this_thread::get_id() == owner_ ? k_ : im_.S + k_;
-    im_.ba_win[slot] = win_; im_.ba_res[slot] = &res;
-    im_.SubmitAndWait(slot, St::PENDING_BA);
+    const int slot = im_.core.Slot(k_);
+    im_.ba_req[slot] = {win_, &res};
+    im_.core.SubmitAndWait(slot, BA);
   }
   void LoopCorrect(int64_t cur_kf_id, const double* corrected_pose7, int n_fused, const int64_t* fused_ids, ssx_ba_window_loop_result* res) override
   {
     // (the windows of a cohort share ba_ctx: the keyframe dispatcher makes the call, never beside one of its batched solves)
     std::function<void()> call = [&] { im_.ba_ctx.check(ssx_ba_window_loop_correct(win_, cur_kf_id, corrected_pose7, n_fused, n_fused > 0 ? fused_ids : nullptr, res)); };
-    const int slot = std::this_thread::get_id() == owner_ ? k_ : im_.S + k_;
+    const int slot = im_.core.Slot(k_);
     im_.call_req[slot] = &call;
-    im_.SubmitAndWait(slot, St::PENDING_CALL);
+    im_.core.SubmitAndWait(slot, CALL);
   }
 
  private:
@@ -451,7 +301,6 @@ class BatchedBaWindow final : public BaWindow {
   void check(ssx_status st) const { if (st != SSX_OK) throw std::runtime_error("ssx_ba_window: edit failed with status " + std::to_string((int)st)); }
   StreamBatcher::Impl& im_;
   int k_;
-  std::thread::id owner_;                            // the stream's thread (it makes the window: Backend's constructor)
   ssx_ba_window* win_ = nullptr;
 };
 
@@ -460,7 +309,7 @@ class BatchedBaWindow final : public BaWindow {
 // dispatcher one at a time.
 class BatchedLoopCompute final : public LoopCompute {
  public:
-  BatchedLoopCompute(StreamBatcher::Impl& im, int k, const std::string& voc_path) : im_(im), k_(k), owner_(std::this_thread::get_id()), db_(im.MakeLoopDatabase(voc_path)) {}
+  BatchedLoopCompute(StreamBatcher::Impl& im, int k, const std::string& voc_path) : im_(im), k_(k), db_(im.MakeLoopDatabase(voc_path)) {}
   ~BatchedLoopCompute() override
   {
     ssx_kfdb_destroy(db_);
@@ -469,7 +318,7 @@ class BatchedLoopCompute final : public LoopCompute {
   void ProcessKeyframe(int64_t kf_id, const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, int min_db_size,
                        int min_id_gap, float threshold, ssx_kfdb_step_result& res, std::vector<int32_t>& pairs) override
   {
-    const int slot = Slot();
+    const int slot = im_.core.Slot(k_);
     const size_t bytes = (size_t)img.rows * img.cols;
     if (bytes > pin_bytes_) {                       // the keyframe's image in a pinned buffer of the stream's own, read there by the GPU
       ssx_host_free(pin_);
@@ -484,8 +333,8 @@ class BatchedLoopCompute final : public LoopCompute {
       r = LoopReq{};
       r.job.db = db_; r.job.kf_id = kf_id; r.job.img = pin_; r.job.stride = img.cols; r.job.n_features = (int32_t)features.size(); r.job.features = features.data();
       r.job.commit_pending = commit_next_ ? 1 : 0; r.job.pairs_cap = (int32_t)(pairs.size() / 2); r.job.pairs_out = pairs.data(); r.job.res = &res;
-      r.prm = prm; r.rows = img.rows; r.cols = img.cols; r.levels = pyramid_levels; r.min_db = min_db_size; r.min_gap = min_id_gap; r.threshold = threshold;
-      im_.SubmitAndWait(slot, St::PENDING_LOOP);
+      r.prm = prm; r.size = {img.rows, img.cols}; r.levels = pyramid_levels; r.min_db = min_db_size; r.min_gap = min_id_gap; r.threshold = threshold;
+      im_.core.SubmitAndWait(slot, LOOP);
       commit_next_ = false;                         // (the call ran: the keyframe of AddPending is stored)
       if (r.status != SSX_ERR_CAPACITY || attempt > 0) break;
       pairs.resize(2 * (size_t)res.n_pairs);        // a larger loop keyframe: the count is known now, the step once more
@@ -506,17 +355,14 @@ class BatchedLoopCompute final : public LoopCompute {
   }
 
  private:
-  // the stream's thread, or the worker of its asynchronous backend (the rule of BatchedBaWindow::Solve)
-  int Slot() const { return std::this_thread::get_id() == owner_ ? k_ : im_.S + k_; }
   void Single(std::function<void()> call)
   {
-    const int slot = Slot();
+    const int slot = im_.core.Slot(k_);
     im_.call_req[slot] = &call;
-    im_.SubmitAndWait(slot, St::PENDING_CALL);
+    im_.core.SubmitAndWait(slot, CALL);
   }
   StreamBatcher::Impl& im_;
   int k_;
-  std::thread::id owner_;                            // the stream's thread (it makes the System)
   ssx_kf_database* db_ = nullptr;
   uint8_t* pin_ = nullptr;
   size_t pin_bytes_ = 0;
@@ -525,13 +371,13 @@ class BatchedLoopCompute final : public LoopCompute {
 
 class BatchedCompute final : public Compute {
  public:
-  BatchedCompute(StreamBatcher::Impl& im, int k) : im_(im), k_(k), frame_(im.device) {}
+  BatchedCompute(StreamBatcher::Impl& im, int k) : im_(im), k_(k), frame_(im.device) { im_.core.Bind(k_); }
   ~BatchedCompute() override { if (own_pins_) { ssx_host_free(pin_[0]); ssx_host_free(pin_[1]); } }
 
   void Detect(const Image& img, const uint8_t* mask, const ssx_orb_params& prm, std::vector<ssx_keypoint>& kps) override
   {
-    owner_ = std::this_thread::get_id();           // (the front-end calls come from the stream's thread)
-    LongOp op(im_, k_);
+    im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
+    BatchDispatch::LongOp op(im_.core, k_);
     kps.assign((size_t)prm.nfeatures + 260 + 64, ssx_keypoint{});
     int32_t n = 0;
     ssx_status st = ssx_orb_detect(frame_.get(), img.ptr(), img.cols, img.rows, img.cols, mask, img.cols, &prm, (int32_t)kps.size(), kps.data(), &n);
@@ -544,19 +390,20 @@ class BatchedCompute final : public Compute {
   }
   void DetectBoxes(const Image& img, const std::vector<int32_t>& boxes, const ssx_orb_params& prm, std::vector<ssx_keypoint>& kps) override
   {
-    owner_ = std::this_thread::get_id();           // (the front-end calls come from the stream's thread)
+    im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
     kps.assign((size_t)prm.nfeatures + 260 + 64, ssx_keypoint{});
     int32_t n = 0;
     const uint8_t* pinned = Pinned(img, 0);        // (the current left image: usually there already, from the frame's temporal LK)
-    ssx_orb_detect_job& q = im_.det_req[k_];
-    q = ssx_orb_detect_job{};
+    DetReq& r = im_.det_req[k_];
+    r = DetReq{};
+    ssx_orb_detect_job& q = r.job;
     q.img = pinned; q.stride = img.cols; q.boxes_xyxy = boxes.data(); q.n_boxes = (int32_t)(boxes.size() / 4);
     q.cap = (int32_t)kps.size(); q.kps_out = kps.data(); q.n_out = &n;
-    im_.det_prm[k_] = prm; im_.lk_rows[k_] = img.rows; im_.lk_cols[k_] = img.cols;
-    im_.SubmitAndWait(k_, St::PENDING_DET);
+    r.prm = prm; r.size = {img.rows, img.cols};
+    im_.core.SubmitAndWait(k_, DET);
     if (n > (int32_t)kps.size()) {
       // (a grid returned more than the bound of ssx.h: once more with the size it asked for, on the stream's own context)
-      LongOp op(im_, k_);
+      BatchDispatch::LongOp op(im_.core, k_);
       kps.assign((size_t)n, ssx_keypoint{});
       frame_.check(ssx_orb_detect_boxes(frame_.get(), img.ptr(), img.cols, img.rows, img.cols, boxes.data(), (int32_t)(boxes.size() / 4), &prm, (int32_t)kps.size(),
                                         kps.data(), &n));
@@ -567,21 +414,22 @@ class BatchedCompute final : public Compute {
   void TrackLK(const Image& prev, const Image& next, const std::vector<float>& prev_pts, std::vector<float>& next_pts, std::vector<uint8_t>& status,
                bool temporal) override
   {
-    owner_ = std::this_thread::get_id();           // (the front-end calls come from the stream's thread)
+    im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
     const int n = (int)(prev_pts.size() / 2);
     status.assign(n, 0);
-    ssx_lk_job& q = im_.lk_req[k_];
-    q = ssx_lk_job{};
+    LkReq& r = im_.lk_req[k_];
+    r = LkReq{};
+    ssx_lk_job& q = r.job;
     q.slot = k_;
     q.n = n; q.prev_pts = prev_pts.data(); q.next_pts = next_pts.data(); q.status = status.data(); q.err = nullptr;
-    im_.lk_rows[k_] = next.rows; im_.lk_cols[k_] = next.cols;
+    r.size = {next.rows, next.cols};
     if (!temporal) {
       // FindFeaturesInRight (frontend.cpp:346-428): left -> right of one frame, both pyramids built afresh, on this stream's slot of
       // its image size's stereo LK context
       if (prev.rows != next.rows || prev.cols != next.cols) throw std::invalid_argument("TrackLK: image sizes differ");
       q.prev = Pinned(prev, 0); q.prev_stride = prev.cols;
       q.next = Pinned(next, 1, q.prev); q.next_stride = next.cols;
-      im_.SubmitAndWait(k_, St::PENDING_LKS);
+      im_.core.SubmitAndWait(k_, LKS);
       return;
     }
     // the frame-to-frame chain: this stream's slot of its image size's LK context keeps the pyramid of its last `next` image.  The new
@@ -592,41 +440,41 @@ class BatchedCompute final : public Compute {
     if (!chained) { q.prev = Pinned(prev, 1); q.prev_stride = prev.cols; }
     q.next = Pinned(next, 0, q.prev); q.next_stride = next.cols;
     chain_next_id_ = 0;                            // (a failed call leaves no chain)
-    im_.SubmitAndWait(k_, St::PENDING_LK);
+    im_.core.SubmitAndWait(k_, LK);
     chain_next_id_ = next.id; chain_rows_ = next.rows; chain_cols_ = next.cols;
   }
 
   int PoseOnly(double* pose_io, const double* K4, int M, const double* xyz, const double* uv, uint8_t* inlier) override
   {
-    owner_ = std::this_thread::get_id();           // (the front-end calls come from the stream's thread)
+    im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
     int32_t n_in = 0;
     ssx_pose_only_job& q = im_.po_req[k_];
     q = ssx_pose_only_job{};
     q.pose_io = pose_io; q.K4 = K4; q.M = M; q.xyz = xyz; q.uv = uv; q.rounds = 4; q.iters = 10; q.chi2_th = 5.991; q.huber_delta = 1.0;
     q.inlier_out = inlier; q.n_inliers = &n_in;
-    im_.SubmitAndWait(k_, St::PENDING_PO);
+    im_.core.SubmitAndWait(k_, PO);
     return n_in;
   }
 
   void Triangulate(int n, const double* uvL, const double* uvR, const ssx_stereo_rig& rig, const double* T_wc, double* xyz, uint8_t* ok) override
   {
-    owner_ = std::this_thread::get_id();           // (the front-end calls come from the stream's thread)
+    im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
     ssx_triangulate_job& q = im_.tri_req[k_];
     q = ssx_triangulate_job{};
     q.n = n; q.uvL = uvL; q.uvR = uvR; q.rig = &rig; q.T_wc = T_wc; q.xyz_out = xyz; q.ok_out = ok;
-    im_.SubmitAndWait(k_, St::PENDING_TRI);
+    im_.core.SubmitAndWait(k_, TRI);
   }
 
   void BundleAdjust(const ssx_ba_problem& prob, const ssx_ba_options& opt, ssx_ba_result& res) override
   {
     // (Backend.Window: 0 -- the re-marshalled map, one window per call)
-    if (std::this_thread::get_id() != owner_) {
+    if (im_.core.Slot(k_) != k_) {
       // the worker thread of an asynchronous backend: a context of its own, and the stream's slot is not touched (its thread is tracking)
       if (!async_ba_) async_ba_ = std::make_unique<ssx::Context>(im_.device);
       async_ba_->check(ssx_ba_solve(async_ba_->get(), &prob, &opt, &res));
       return;
     }
-    LongOp op(im_, k_);
+    BatchDispatch::LongOp op(im_.core, k_);
     frame_.check(ssx_ba_solve(frame_.get(), &prob, &opt, &res));
   }
 
@@ -661,7 +509,6 @@ class BatchedCompute final : public Compute {
 
   StreamBatcher::Impl& im_;
   int k_;
-  std::thread::id owner_ = std::this_thread::get_id();
   std::unique_ptr<ssx::Context> async_ba_;
   ssx::Context frame_;
   uint8_t* pin_[2] = {nullptr, nullptr};
@@ -695,7 +542,7 @@ std::unique_ptr<Compute> StreamBatcher::MakeCompute(int k)
 void StreamBatcher::Finish(int k)
 {
   const int C = (int)impls_.size();
-  if (k >= 0 && k < n_streams_) impls_[k % C]->SetState(k / C, St::DONE);
+  if (k >= 0 && k < n_streams_) impls_[k % C]->core.Finish(k / C);
 }
 
 size_t StreamBatcher::PinnedSliceBytes(int k)
@@ -708,21 +555,25 @@ size_t StreamBatcher::PinnedSliceBytes(int k)
 
 void StreamBatcher::ResetStats()
 {
-  for (auto& im : impls_) {
-    std::lock_guard<std::mutex> lk(im->m);
-    im->st = Stats{};
-  }
+  for (auto& im : impls_) im->core.ResetCounters();
 }
 
 StreamBatcher::Stats StreamBatcher::stats()
 {
   Stats t;
+  long single_jobs = 0;
   for (auto& im : impls_) {
-    std::lock_guard<std::mutex> lk(im->m);
-    const Stats& a = im->st;
-    t.lk_calls += a.lk_calls; t.lk_jobs += a.lk_jobs; t.po_calls += a.po_calls; t.po_jobs += a.po_jobs; t.ba_calls += a.ba_calls; t.ba_jobs += a.ba_jobs;
-    t.kf_calls += a.kf_calls; t.kf_jobs += a.kf_jobs; t.lk_s += a.lk_s; t.po_s += a.po_s; t.ba_s += a.ba_s; t.kf_s += a.kf_s; t.wait_s += a.wait_s;
-    t.loop_calls += a.loop_calls; t.loop_jobs += a.loop_jobs; t.loop_s += a.loop_s; t.single_calls += a.single_calls; t.single_s += a.single_s;
+    auto add = [&](Kind kind, long& calls, long& jobs, double& seconds) {
+      const BatchDispatch::Counters c = im->core.counters(kind);
+      calls += c.calls; jobs += c.jobs; seconds += c.seconds;
+    };
+    add(LK, t.lk_calls, t.lk_jobs, t.lk_s);
+    add(PO, t.po_calls, t.po_jobs, t.po_s);
+    for (Kind kf : {DET, LKS, TRI}) add(kf, t.kf_calls, t.kf_jobs, t.kf_s);
+    add(BA, t.ba_calls, t.ba_jobs, t.ba_s);
+    add(LOOP, t.loop_calls, t.loop_jobs, t.loop_s);
+    add(CALL, t.single_calls, single_jobs, t.single_s);
+    t.wait_s += im->core.wait_s();
   }
   return t;
 }

@@ -22,6 +22,13 @@
 // A cohort may mix image sizes: an LK context holds chains for one size, so the batcher keeps LK contexts per (rows, cols) and a frame
 // costs one LK call per size; the streams of one size still share it.
 //
+// Two pairs of files.  batch_dispatch.{hpp,cpp} is the protocol and knows no library call: the request slots and their states, the
+// streams' sleep and wake-up, the ONE dispatcher loop that both dispatcher threads run (each with its kinds in priority order, its
+// slots and its rest condition), the per-kind counters, the retry that isolates a faulty request, and the rule for which slot a
+// thread files in; tests/host/test_dispatch_units.cpp holds it to its ordering on the CPU, under ThreadSanitizer too.
+// stream_batcher.cpp is a table of the request kinds -- each one's per-slot request, what the jobs of a call must share, and its
+// library call -- and the three adapters (Compute, BaWindow, LoopCompute) that file them.
+//
 // Dispatch order: pose-only before LK.  A stream that comes back from a keyframe is half a frame out of phase with the cohort; with
 // the pose-only batch served first the cohort arrives at its next LK request while the straggler still waits there, and they merge.
 #pragma once
@@ -51,6 +58,7 @@ class StreamBatcher {
   std::unique_ptr<Compute> MakeCompute(int k);
   void Finish(int k);
 
+  // (calls: the library calls made that did not fail; jobs: the requests in them -- one counter per request kind, batch_dispatch.hpp)
   struct Stats {
     long lk_calls = 0, lk_jobs = 0, po_calls = 0, po_jobs = 0, ba_calls = 0, ba_jobs = 0, kf_calls = 0, kf_jobs = 0;   // kf: detection, stereo LK, triangulation
     double lk_s = 0, po_s = 0, ba_s = 0, kf_s = 0;  // seconds inside the batched library calls
