@@ -666,6 +666,37 @@ typedef struct { double K[4]; double dist[5]; /* k1 k2 p1 p2 k3 */ double iR[9];
 typedef struct { const uint8_t* src; int32_t src_stride; uint8_t* dst; int32_t dst_stride; ssx_undistort_params prm; } ssx_undistort_job;
 SSX_API void ssx_undistort_default(const double K4[4], const double dist5[5], ssx_undistort_params* out);
 SSX_API ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device);
+/* The batched form over many streams: a PLAN holds, for one image size, the stored maps of the cameras it was shown, and applies them
+ * to n images in one launch without f64.  The streams of a cohort usually share one rig: one stored map per camera serves them all.
+ * The stored form of a map is tools/undistort_model.py's pack_map -- per pixel three u16: X0 + 2 and Y0 + 2 (the integer position,
+ * clamped to [-2, cols] and [-2, rows]: the clamp keeps every tap's inside / outside test) and a | b << 5 (the two 5-bit fractions);
+ * in memory three planes at a pitch of cols rounded up to 4: 2.8 MB at 1241 x 376, so SSX_UNDISTORT_PLAN_MAX_MAPS of them 179 MB of HBM.
+ * The result of ssx_undistort_plan_apply is, byte for byte, ssx_undistort's.
+ *
+ * ssx_undistort_plan_create: rows, cols >= 1 (SSX_ERR_INVALID_ARG) and at most 65533 a side (SSX_ERR_UNSUPPORTED: position + 2 is a
+ * u16).  The plan lives on ctx (its stream, its error text) and is destroyed before it.
+ * ssx_undistort_plan_add: the index of the parameter set's map.  A set whose bytes equal those of an earlier one gets that one's index
+ * and nothing is launched; a new set launches k_undistort_map once (and synchronises).  Beyond SSX_UNDISTORT_PLAN_MAX_MAPS:
+ * SSX_ERR_CAPACITY with a message, the plan unchanged.
+ * ssx_undistort_plan_apply: n jobs (0 .. SSX_UNDISTORT_MAX_JOBS), each naming a map of the plan, in ONE launch and with ONE
+ * synchronisation whatever n is and whatever maps the jobs name.  images_on_device = 0: ordinary host memory, staged like
+ * ssx_undistort (one copy up, one copy down).  images_on_device != 0: every pointer is device memory or pinned host memory.  Device
+ * images are read and written where they lie.  Host images are never read or written by the kernel tap by tap across PCIe: they are
+ * copied to the device and the results copied back by the DMA engines -- the sources in ONE copy when they stand in job order
+ * ascending, at distances of at least one image, in ONE allocation (an ssx_host_alloc arena, a slice per stream; the rule of
+ * ssx_lk_track_batch, the runtime asked whether the range really is one allocation), else one copy per image; the results in ONE copy
+ * when the destinations stand so, at one constant distance and at a stride of cols (the copy then writes the images' bytes and
+ * nothing between them), else one copy per image, which writes the pixels and leaves the pitch bytes alone.
+ * SSX_ERR_INVALID_ARG with a message, before anything is touched: every refusal of ssx_undistort, a map index the plan does not hold,
+ * and with images_on_device != 0 a pointer that is neither device nor pinned memory. */
+#define SSX_UNDISTORT_PLAN_MAX_MAPS 64
+typedef struct ssx_undistort_plan ssx_undistort_plan;
+typedef struct { const uint8_t* src; int32_t src_stride; uint8_t* dst; int32_t dst_stride; int32_t map; } ssx_undistort_plan_job;
+SSX_API ssx_status ssx_undistort_plan_create(ssx_ctx* ctx, int32_t rows, int32_t cols, ssx_undistort_plan** plan);
+SSX_API ssx_status ssx_undistort_plan_add(ssx_undistort_plan* plan, const ssx_undistort_params* prm, int32_t* map_index);
+SSX_API ssx_status ssx_undistort_plan_apply(ssx_undistort_plan* plan, int32_t n, const ssx_undistort_plan_job* jobs, int32_t images_on_device);
+SSX_API ssx_status ssx_undistort_plan_size(const ssx_undistort_plan* plan, int32_t* rows, int32_t* cols, int32_t* n_maps);
+SSX_API void ssx_undistort_plan_destroy(ssx_undistort_plan* plan);
 /* ------------------------------------------------------------------------------------------------
  * N3: pose-graph optimisation.
  * Replaces the optimisation of LoopClosing::PoseGraphOptimization

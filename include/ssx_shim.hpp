@@ -256,6 +256,40 @@ class Camera {
   ssx_undistort_params prm_{};
 };
 
+// Many streams' frames in one call (ssx_undistort_plan_*): the plan keeps one stored map per camera it was shown (Add: equal parameter
+// bytes -> the index they have) for ONE image size, and Apply undistorts n images, each naming its map, in one launch -- the bytes
+// of Camera::UndistortImage.  Destroy the plan before its Context.
+class UndistortPlan {
+ public:
+  UndistortPlan(Context& ctx, int rows, int cols) : ctx_(ctx) { ctx_.check(ssx_undistort_plan_create(ctx_.get(), rows, cols, &plan_)); }
+  ~UndistortPlan() { ssx_undistort_plan_destroy(plan_); }
+  UndistortPlan(const UndistortPlan&) = delete;
+  UndistortPlan& operator=(const UndistortPlan&) = delete;
+
+  int Add(const ssx_undistort_params& prm)
+  {
+    int32_t m = -1;
+    ctx_.check(ssx_undistort_plan_add(plan_, &prm, &m));
+    return m;
+  }
+  int Add(const Camera& camera) { return Add(camera.params()); }
+  void Apply(const std::vector<ssx_undistort_plan_job>& jobs, bool imagesOnDevice = false)
+  {
+    ctx_.check(ssx_undistort_plan_apply(plan_, (int32_t)jobs.size(), jobs.data(), imagesOnDevice ? 1 : 0));
+  }
+  int maps() const
+  {
+    int32_t n = 0;
+    ssx_undistort_plan_size(plan_, nullptr, nullptr, &n);
+    return n;
+  }
+  ssx_undistort_plan* get() const { return plan_; }
+
+ private:
+  Context& ctx_;
+  ssx_undistort_plan* plan_ = nullptr;
+};
+
 // ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>, include/ssvio/orbvocabulary.hpp:10) as LoopClosing
 // uses it: loadFromTextFile, transform(descriptors, BowVector), score(BowVector, BowVector).  A BowVector here is the
 // sorted (word id, value) pairs of DBoW2::BowVector (a std::map<WordId, WordValue>).

@@ -235,6 +235,14 @@ SSX_API ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, 
  * ssx_kfdb_debug_last_step counts -- kernel launches, stream synchronisations, bytes sent up (the job table and, for host images,
  * the sources) and bytes that came down (the results of host images).  All zero after a call that was refused.  Any output may be NULL. */
 SSX_API ssx_status ssx_undistort_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down);
+/* the same for a plan (ssx_undistort_plan_*): what its last ssx_undistort_plan_add or ssx_undistort_plan_apply issued.  copies_up /
+ * copies_down count the copies that carry images (a staged call's one copy up carries the job table too; otherwise the table goes up
+ * beside them, in bytes_up and not in copies_up).  All zero after a call that was refused, and after an add that found its map. */
+SSX_API ssx_status ssx_undistort_plan_debug_last_call(const ssx_undistort_plan* plan, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up,
+                                                      int64_t* bytes_down, int32_t* copies_up, int32_t* copies_down);
+/* the stored map `map_index` as tools/undistort_model.py's pack_map returns it: out = three planes of rows x cols u16 (xs, ys, ab),
+ * each contiguous */
+SSX_API ssx_status ssx_undistort_plan_debug_map(ssx_undistort_plan* plan, int32_t map_index, uint16_t* out);
 
 #ifdef __cplusplus
 }

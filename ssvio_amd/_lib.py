@@ -205,6 +205,15 @@ class UndistortJob(C.Structure):
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int32), ("prm", UndistortParams)]
 
 
+class UndistortPlanJob(C.Structure):
+    """ssx_undistort_plan_job: `map` is an index ssx_undistort_plan_add returned"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int32), ("map", C.c_int32)]
+
+
+SSX_UNDISTORT_MAX_JOBS = 1024
+SSX_UNDISTORT_PLAN_MAX_MAPS = 64
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("calls", C.c_int32), ("total_ms", C.c_double)]
 

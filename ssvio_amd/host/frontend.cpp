@@ -64,8 +64,8 @@ bool FrontEnd::GrabSteroImage(ImagePtr left, ImagePtr right, double timestamp)
   if (need_undistortion_) {                                            // frontend.cpp:39-45: before anything else looks at the images
     Stopwatch sw(times_.undistort, times_.n_undistort);
     auto l = std::make_shared<Image>(), r = std::make_shared<Image>();
-    compute_.UndistortPair(*left, *right, undistort_, *l, *r);
     l->id = NewImageId(); r->id = NewImageId();                        // new images: a resident pyramid of the distorted ones is not theirs
+    compute_.UndistortPair(*left, *right, undistort_, *l, *r);         // (the ids first: a Compute may keep the results where its next calls look for them)
     left = std::move(l); right = std::move(r);
   }
   std::lock_guard<std::mutex> map_lock(map_->update_mutex);           // frontend.cpp:49: the whole frame is tracked under the map mutex

@@ -3,7 +3,7 @@
 // save the keyframe trajectory in TUM format.  Same two flags (gflags spelling), plus a frame limit and an output path.
 //
 //   ssx_run_kitti --config_yaml_path=cfg.yaml --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=out.txt]
-//                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--warmup=1] [--loop_log=FILE]
+//                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--undistort_batched=0] [--warmup=1] [--loop_log=FILE]
 // The PNG pairs are decoded ahead of the tracker on worker threads (StereoPrefetcher); everything else is the
 // reference's single loop.  --streams=K runs K independent copies of the loop in K threads of this process (each with
 // its own System, GPU contexts and prefetcher) on the same sequence: a single stream is latency-bound, several fill the
@@ -21,7 +21,10 @@
 //   and, with Relocalization.Open: 1, behind them one line per attempt of a lost front-end:
 //   reloc_frame <frame id> candidates <n> pairs <n> poses <n> inliers <n> accepted <keyframe id|-1>
 // Relocalization.Open: 1 works per stream of an unbatched --streams; with --batched >= 1 it is refused.
-// Camera.NeedUndistortion: 1 (every frame's pair goes through ssx_undistort first) likewise: per stream of an unbatched --streams, refused with --batched >= 1.
+// Camera.NeedUndistortion: 1 (every frame's pair goes through ssx_undistort first) works per stream of an unbatched --streams.  --batched >= 1 with the key
+// set is refused unless --undistort_batched=1 is given: the pairs of a cohort's streams then go through the lenses' stored maps in ONE
+// ssx_undistort_plan_apply call per frame (two jobs a stream, one map per camera of the rig), and every stream still writes the bytes of its
+// single-stream run.  With the key 0 or absent the flag changes nothing; without --batched >= 1 it is refused.
 // Loop closing is per stream.  --batched >= 1 with Loop.Closing.Open: 1 is refused unless --loop_batched=1 is given: the streams of a cohort
 // then share one loop context and one vocabulary, and their inline keyframe steps go to the GPU as ssx_kfdb_process_keyframe_batch calls
 // (every stream still writes the bytes of its single-stream run).  The loop thread (Loop.Closing.Async: 1) is not batched: refused with it.
@@ -74,16 +77,17 @@ void WriteLoopLog(ssx::host::System& sys, const std::string& path)
 
 int main(int argc, char** argv)
 {
-  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log, loop_batched_s;
+  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log, loop_batched_s, undistort_batched_s;
   for (int i = 1; i < argc; ++i) {
     if (flag(argv[i], "config_yaml_path", config) || flag(argv[i], "kitti_dataset_path", dataset) || flag(argv[i], "max_frames", max_frames_s) ||
-        flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s) || flag(argv[i], "loop_log", loop_log) || flag(argv[i], "loop_batched", loop_batched_s))
+        flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s) || flag(argv[i], "loop_log", loop_log) || flag(argv[i], "loop_batched", loop_batched_s) ||
+        flag(argv[i], "undistort_batched", undistort_batched_s))
       continue;
     std::fprintf(stderr, "unknown argument %s\n", argv[i]);
     return 2;
   }
   if (config.empty() || dataset.empty()) {
-    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--warmup=1] [--loop_log=<file>]\n",
+    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--undistort_batched=0] [--warmup=1] [--loop_log=<file>]\n",
                  argv[0]);
     return 2;
   }
@@ -125,9 +129,14 @@ int main(int argc, char** argv)
                    "run --streams unbatched, or switch relocalisation off\n", batched_s.c_str());
       return 2;
     }
-    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Camera.NeedUndistortion") != 0) {
-      std::fprintf(stderr, "--batched=%s with Camera.NeedUndistortion: 1 is not supported: the dispatcher has no batched undistortion call yet; "
-                   "run --streams unbatched, or feed rectified images\n", batched_s.c_str());
+    const bool undistort_batched = !undistort_batched_s.empty() && std::atoi(undistort_batched_s.c_str()) != 0;
+    if (undistort_batched && (batched_s.empty() || std::atoi(batched_s.c_str()) <= 0)) {
+      std::fprintf(stderr, "--undistort_batched=1 needs --batched >= 1 (with --streams): it chooses how a batched cohort undistorts its images\n");
+      return 2;
+    }
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Camera.NeedUndistortion") != 0 && !undistort_batched) {
+      std::fprintf(stderr, "--batched=%s with Camera.NeedUndistortion: 1 is not supported without --undistort_batched=1 (the cohort's pairs undistorted in one call "
+                   "per frame); or run --streams unbatched, or feed rectified images\n", batched_s.c_str());
       return 2;
     }
     if (loop_batched && Setting(config).Get<int>("Loop.Closing.Open") != 0 && Setting(config).Get<int>("Loop.Closing.Async") != 0) {
@@ -226,6 +235,9 @@ int main(int argc, char** argv)
                     1e3 * bs.lk_s, 1e3 * bs.lk_s / std::max(1L, bs.lk_calls), 1e3 * bs.po_s, 1e3 * bs.po_s / std::max(1L, bs.po_calls), 1e3 * bs.ba_s,
                     1e3 * bs.ba_s / std::max(1L, bs.ba_calls), bs.kf_calls, bs.kf_jobs / std::max(1.0, (double)bs.kf_calls), 1e3 * bs.kf_s,
                     1e3 * bs.kf_s / std::max(1L, bs.kf_calls), 1e3 * bs.wait_s);
+        if (bs.und_calls)
+          std::printf("batched calls: undistort %ld (%.1f jobs each); und_calls %ld und_jobs %ld und_s %.6f (%.3f ms per call)\n", bs.und_calls,
+                      bs.und_jobs / std::max(1.0, (double)bs.und_calls), bs.und_calls, bs.und_jobs, bs.und_s, 1e3 * bs.und_s / std::max(1L, bs.und_calls));
         if (bs.loop_calls || bs.single_calls)
           std::printf("batched loop steps: loop_calls %ld loop_jobs %ld loop_s %.6f (%.3f ms per call, %.1f jobs each); a correction's single calls %ld, %.1f ms\n",
                       bs.loop_calls, bs.loop_jobs, bs.loop_s, 1e3 * bs.loop_s / std::max(1L, bs.loop_calls), bs.loop_jobs / std::max(1.0, (double)bs.loop_calls),

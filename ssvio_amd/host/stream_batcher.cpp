@@ -16,7 +16,7 @@
 namespace ssx::host {
 
 namespace {
-enum Kind : int { LK, PO, DET, LKS, TRI, BA, LOOP, CALL, N_KINDS };   // indices into the table of Impl::Kinds
+enum Kind : int { LK, PO, DET, LKS, TRI, BA, LOOP, CALL, UND, N_KINDS };   // indices into the table of Impl::Kinds
 // what the jobs of one call share -- the keys of Groups
 struct ImageSize {
   int rows = 0, cols = 0;
@@ -34,6 +34,8 @@ OrbParamBytes Bytes(const ssx_orb_params& p)
 struct LkReq { ssx_lk_job job{}; ImageSize size; };   // temporal and stereo LK
 struct DetReq { ssx_orb_detect_job job{}; ssx_orb_params prm{}; ImageSize size; };
 struct BaReq { ssx_ba_window* win = nullptr; ssx_ba_result* res = nullptr; };
+// a frame's pair through the lenses' maps: two jobs (left, right) of one request, raw images and results in the stream's pinned buffers
+struct UndReq { const uint8_t* src[2] = {nullptr, nullptr}; uint8_t* dst[2] = {nullptr, nullptr}; ssx_undistort_params prm[2] = {}; ImageSize size; };
 // one keyframe step of loop closing as a stream files it (ssx_kfdb_process_keyframe_batch): the job and what a call's jobs must share
 struct LoopReq { ssx_kfdb_step_job job{}; ssx_orb_params prm{}; ImageSize size; int levels = 0, min_db = 0, min_gap = 0; float threshold = 0.f; int32_t status = 0; };
 }
@@ -48,10 +50,12 @@ struct StreamBatcher::Impl {
   // their keyframe a little later catch up and all of them meet in one window solve (a batched solve costs what a single one costs).
   // The loop step follows the window solve inside the backend: served after it, the streams that solved a little later merge into one
   // loop call; the rare single calls of a correction come last.
+  // Undistortion (Camera.NeedUndistortion) is the first call of a frame and is served LAST of the per-frame kinds, by the reasoning of
+  // the header's "pose-only before LK": the later stage first, so that the cohort arrives where a straggler waits.
   Impl(int device_, int streams) : device(device_), S(streams), po_ctx(device_), ba_ctx(device_), det_ctx(device_), tri_ctx(device_), lk_req(streams),
                                    po_req(streams), det_req(streams), tri_req(streams), ba_req(2 * (size_t)streams), loop_req(2 * (size_t)streams),
-                                   call_req(2 * (size_t)streams, nullptr),
-                                   core(streams, Kinds(), {{PO, LK}, false, false}, {{DET, LKS, TRI, BA, LOOP, CALL}, true, true})
+                                   call_req(2 * (size_t)streams, nullptr), und_req(streams),
+                                   core(streams, Kinds(), {{PO, LK, UND}, false, false}, {{DET, LKS, TRI, BA, LOOP, CALL}, true, true})
   {
   }
   ~Impl()
@@ -59,6 +63,7 @@ struct StreamBatcher::Impl {
     // (the streams have finished: the dispatchers, which stop with `core`, are idle)
     if (voc) ssx_voc_destroy(voc);                  // (the streams' databases went with their Systems)
     ssx_host_free(pin_arena);
+    ssx_host_free(raw_arena);
   }
 
   // The cohort's loop context and its ONE vocabulary, loaded when the first stream asks for them (128 streams with a vocabulary each
@@ -98,8 +103,26 @@ struct StreamBatcher::Impl {
     return *p;
   }
 
+  // The undistortion plan of ONE image size on a context of its own (the grouping key of the request, as for LK): the stored maps of the
+  // cameras its streams showed it -- a cohort of one rig has two -- made when the size's first request is served.
+  struct UndSize {
+    UndSize(int device, ImageSize size) : ctx(device) { ctx.check(ssx_undistort_plan_create(ctx.get(), size.rows, size.cols, &plan)); }
+    ~UndSize() { ssx_undistort_plan_destroy(plan); }
+    ssx::Context ctx;
+    ssx_undistort_plan* plan = nullptr;
+  };
+  UndSize& ForUndSize(ImageSize size)
+  {
+    std::lock_guard<std::mutex> lk(size_mu);
+    std::unique_ptr<UndSize>& p = und_size[size];
+    if (!p) p = std::make_unique<UndSize>(device, size);
+    return *p;
+  }
+
   // The streams' pinned image buffers are slices of ONE arena: buffer `which` of stream k at (which * S + k) * slice, the slice sized
-  // by the stream that pins first.  The `next` images of a cohort's LK jobs then lie at a constant distance in one allocation and
+  // by the stream that pins first.  Buffers 0 and 1 are the images the calls read (BatchedCompute::Pinned).  Buffers 2 and 3 take a
+  // frame's raw pair when the images go through undistortion first, whose results are then written into 0 and 1; they are slices
+  // of a second arena of the same shape, made when the first stream undistorts (a cohort that does not pins nothing more).  The `next` images of a cohort's LK jobs then lie at a constant distance in one allocation and
   // cross PCIe in one DMA copy (ssx_lk_track_batch).  In a cohort of several image sizes a stream with SMALLER images than the
   // first one uses its slice all the same (the images of its size are then further apart than the one-copy rule allows and are read
   // one by one); a stream with LARGER images gets nullptr and keeps two pinned buffers of its own (BatchedCompute::Pinned), which
@@ -114,7 +137,10 @@ struct StreamBatcher::Impl {
       if (!pin_arena) throw std::runtime_error("StreamBatcher: no pinned memory for the streams' images");
     }
     if (need > pin_slice) return nullptr;
-    return pin_arena + ((size_t)which * S + k) * pin_slice;
+    if (which < 2) return pin_arena + ((size_t)which * S + k) * pin_slice;
+    if (!raw_arena) raw_arena = static_cast<uint8_t*>(ssx_host_alloc(pin_slice * 2 * (size_t)S));
+    if (!raw_arena) throw std::runtime_error("StreamBatcher: no pinned memory for the streams' raw images");
+    return raw_arena + ((size_t)(which - 2) * S + k) * pin_slice;
   }
 
   // A kind's callable: the requests of a dispatch in groups of equal key(slot), one library call per group -- call(slots, errs), errs[j]
@@ -218,6 +244,21 @@ struct StreamBatcher::Impl {
       }
       loop_ctx->check(rc);                          // rejected before anything was touched: Isolated tries the jobs one by one
     })};
+    // undistortion: the jobs of a call share the image size; its plan holds one map per camera (ssx_undistort_plan_add finds a set it was
+    // shown by its bytes).  All left images, then all right ones: the raw pairs and the results then stand in the arena in ascending
+    // order -- one copy up and, when the whole cohort is in the call, one copy down (ssx_undistort_plan_apply).
+    t[UND] = {"undistortion", Grouped([this](int k) { return und_req[k].size; }, [this](Slots slots, Errs) {
+      UndSize& us = ForUndSize(und_req[slots[0]].size);
+      std::vector<ssx_undistort_plan_job> jobs;
+      for (int side = 0; side < 2; ++side)
+        for (int k : slots) {
+          const UndReq& r = und_req[k];
+          int32_t map = -1;
+          us.ctx.check(ssx_undistort_plan_add(us.plan, &r.prm[side], &map));
+          jobs.push_back({r.src[side], r.size.cols, r.dst[side], r.size.cols, map});
+        }
+      us.ctx.check(ssx_undistort_plan_apply(us.plan, (int32_t)jobs.size(), jobs.data(), 1));
+    })};
     // ComputeCorrectPose, LoopCorrect and the window's loop correction: one at a time, here, so that none runs on the loop context or
     // the window context beside a batched call of this dispatcher
     t[CALL] = {"single call", [this](Slots slots, Errs errs, long& calls, long& jobs) {
@@ -230,12 +271,13 @@ struct StreamBatcher::Impl {
   }
 
   std::mutex pin_mu;
-  uint8_t* pin_arena = nullptr;
+  uint8_t* pin_arena = nullptr, *raw_arena = nullptr;
   size_t pin_slice = 0;
   int device, S;
   ssx::Context po_ctx, ba_ctx, det_ctx, tri_ctx;
   std::mutex size_mu;
   std::map<ImageSize, std::unique_ptr<SizeCtx>> size_ctx;   // that size's LK contexts
+  std::map<ImageSize, std::unique_ptr<UndSize>> und_size;   // that size's undistortion plan
   std::vector<LkReq> lk_req;
   std::vector<ssx_pose_only_job> po_req;
   std::vector<DetReq> det_req;
@@ -247,6 +289,7 @@ struct StreamBatcher::Impl {
   std::string loop_voc_path;
   std::vector<LoopReq> loop_req;
   std::vector<std::function<void()>*> call_req;
+  std::vector<UndReq> und_req;
   BatchDispatch core;                               // (last: its threads start when the rest is made and stop before it goes)
 };
 
@@ -372,7 +415,41 @@ class BatchedLoopCompute final : public LoopCompute {
 class BatchedCompute final : public Compute {
  public:
   BatchedCompute(StreamBatcher::Impl& im, int k) : im_(im), k_(k), frame_(im.device) { im_.core.Bind(k_); }
-  ~BatchedCompute() override { if (own_pins_) { ssx_host_free(pin_[0]); ssx_host_free(pin_[1]); } }
+  ~BatchedCompute() override
+  {
+    if (own_pins_) { ssx_host_free(pin_[0]); ssx_host_free(pin_[1]); }
+    if (own_raw_) { ssx_host_free(raw_[0]); ssx_host_free(raw_[1]); }
+  }
+
+  bool CanUndistort() const override { return true; }
+  // Camera::UndistortImage on the frame's pair as ONE request of two jobs (UND).  This thread copies the raw pair into the stream's
+  // pinned buffers 2 and 3; the call writes the results into buffers 0 and 1, which then hold the frame's images under the ids the
+  // front-end gave them -- the frame's LK calls find them there and copy nothing -- and this thread fills the host images from them.
+  void UndistortPair(const Image& left, const Image& right, const ssx_undistort_params prm[2], Image& left_out, Image& right_out) override
+  {
+    im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
+    if (left.rows != right.rows || left.cols != right.cols) throw std::invalid_argument("UndistortPair: left / right image sizes differ");
+    const size_t bytes = (size_t)left.rows * left.cols;
+    Reserve(bytes);
+    if (bytes > raw_bytes_) {
+      if (own_raw_) { ssx_host_free(raw_[0]); ssx_host_free(raw_[1]); }
+      raw_[0] = own_pins_ ? nullptr : im_.PinSlice(k_, 2, bytes); raw_[1] = own_pins_ ? nullptr : im_.PinSlice(k_, 3, bytes);
+      own_raw_ = !raw_[0] || !raw_[1];
+      if (own_raw_) { raw_[0] = static_cast<uint8_t*>(ssx_host_alloc(bytes)); raw_[1] = static_cast<uint8_t*>(ssx_host_alloc(bytes)); }
+      if (!raw_[0] || !raw_[1]) throw std::runtime_error("StreamBatcher: no pinned memory for the stream's raw images");
+      raw_bytes_ = bytes;
+    }
+    std::memcpy(raw_[0], left.ptr(), bytes); std::memcpy(raw_[1], right.ptr(), bytes);
+    left_out.rows = right_out.rows = left.rows; left_out.cols = right_out.cols = left.cols;
+    left_out.data.resize(bytes); right_out.data.resize(bytes);
+    UndReq& r = im_.und_req[k_];
+    r = UndReq{};
+    r.src[0] = raw_[0]; r.src[1] = raw_[1]; r.dst[0] = pin_[0]; r.dst[1] = pin_[1]; r.prm[0] = prm[0]; r.prm[1] = prm[1]; r.size = {left.rows, left.cols};
+    pin_id_[0] = pin_id_[1] = 0;                   // (the call overwrites both; a failed call leaves nothing there)
+    im_.core.SubmitAndWait(k_, UND);
+    pin_id_[0] = left_out.id; pin_id_[1] = right_out.id;
+    std::memcpy(left_out.data.data(), pin_[0], bytes); std::memcpy(right_out.data.data(), pin_[1], bytes);
+  }
 
   void Detect(const Image& img, const uint8_t* mask, const ssx_orb_params& prm, std::vector<ssx_keypoint>& kps) override
   {
@@ -491,6 +568,17 @@ class BatchedCompute final : public Compute {
   const uint8_t* Pinned(const Image& img, int which, const uint8_t* keep = nullptr)
   {
     const size_t bytes = (size_t)img.rows * img.cols;
+    Reserve(bytes);
+    if (img.id != 0 && pin_id_[which] == img.id) return pin_[which];
+    if (img.id != 0 && pin_id_[which ^ 1] == img.id) return pin_[which ^ 1];
+    if (keep && pin_[which] == keep) which ^= 1;
+    std::memcpy(pin_[which], img.ptr(), bytes);
+    pin_id_[which] = img.id;
+    return pin_[which];
+  }
+  // the stream's two pinned image buffers hold `bytes` each: slices of the cohort's arena, or buffers of its own
+  void Reserve(size_t bytes)
+  {
     if (bytes > pin_bytes_) {
       if (own_pins_) { ssx_host_free(pin_[0]); ssx_host_free(pin_[1]); }
       pin_[0] = im_.PinSlice(k_, 0, bytes); pin_[1] = im_.PinSlice(k_, 1, bytes);
@@ -499,12 +587,6 @@ class BatchedCompute final : public Compute {
       if (!pin_[0] || !pin_[1]) throw std::runtime_error("StreamBatcher: no pinned memory for the stream's images");
       pin_bytes_ = bytes; pin_id_[0] = pin_id_[1] = 0;
     }
-    if (img.id != 0 && pin_id_[which] == img.id) return pin_[which];
-    if (img.id != 0 && pin_id_[which ^ 1] == img.id) return pin_[which ^ 1];
-    if (keep && pin_[which] == keep) which ^= 1;
-    std::memcpy(pin_[which], img.ptr(), bytes);
-    pin_id_[which] = img.id;
-    return pin_[which];
   }
 
   StreamBatcher::Impl& im_;
@@ -515,6 +597,9 @@ class BatchedCompute final : public Compute {
   uint64_t pin_id_[2] = {0, 0};
   size_t pin_bytes_ = 0;
   bool own_pins_ = false;
+  uint8_t* raw_[2] = {nullptr, nullptr};            // a frame's raw pair on its way through undistortion (arena buffers 2 and 3, or its own)
+  size_t raw_bytes_ = 0;
+  bool own_raw_ = false;
   uint64_t chain_next_id_ = 0;
   int chain_rows_ = 0, chain_cols_ = 0;
 };
@@ -573,6 +658,9 @@ StreamBatcher::Stats StreamBatcher::stats()
     add(BA, t.ba_calls, t.ba_jobs, t.ba_s);
     add(LOOP, t.loop_calls, t.loop_jobs, t.loop_s);
     add(CALL, t.single_calls, single_jobs, t.single_s);
+    long und_requests = 0;
+    add(UND, t.und_calls, und_requests, t.und_s);
+    t.und_jobs += 2 * und_requests;                 // (a request is a frame's pair)
     t.wait_s += im->core.wait_s();
   }
   return t;

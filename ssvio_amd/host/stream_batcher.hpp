@@ -19,6 +19,10 @@
 // vocabulary, each has its keyframe database there, and their steps go out as ssx_kfdb_process_keyframe_batch; the calls of a
 // correction are rare and are made by the dispatcher one at a time.
 //
+// Camera.NeedUndistortion: a frame's pair goes through the lenses' stored maps first (Compute::UndistortPair), as one more request kind of the
+// per-frame dispatcher: ONE ssx_undistort_plan_apply for the cohort, two jobs per stream, the maps shared by all streams of one rig.
+// The raw pairs go up from the pinned arena in one DMA copy and the results come down into the arena buffers the LK calls read.
+//
 // A cohort may mix image sizes: an LK context holds chains for one size, so the batcher keeps LK contexts per (rows, cols) and a frame
 // costs one LK call per size; the streams of one size still share it.
 //
@@ -29,7 +33,8 @@
 // stream_batcher.cpp is a table of the request kinds -- each one's per-slot request, what the jobs of a call must share, and its
 // library call -- and the three adapters (Compute, BaWindow, LoopCompute) that file them.
 //
-// Dispatch order: pose-only before LK.  A stream that comes back from a keyframe is half a frame out of phase with the cohort; with
+// Dispatch order: pose-only before LK before undistortion (the later stage first).  Measured with undistortion last: 64 streams, every
+// undistortion call carries all 128 jobs (profiles/undistort_plan/time.txt) -- no order can carry more, so no other was tried.  A stream that comes back from a keyframe is half a frame out of phase with the cohort; with
 // the pose-only batch served first the cohort arrives at its next LK request while the straggler still waits there, and they merge.
 #pragma once
 #include <condition_variable>
@@ -67,6 +72,8 @@ class StreamBatcher {
     double loop_s = 0;
     long single_calls = 0;                           // a correction's calls (ComputeCorrectPose, LoopCorrect, the window's), one at a time
     double single_s = 0;
+    long und_calls = 0, und_jobs = 0;                // undistortion (Camera.NeedUndistortion): ssx_undistort_plan_apply calls and their jobs, two per frame
+    double und_s = 0;
   };
   Stats stats();
   void ResetStats();                                 // (after the streams' warm-up: the counters then describe the frames alone)

@@ -104,6 +104,38 @@ def undistort(img, K, dist, iR=None):
     return remap(img, iu, iv)
 
 
+MAP_MAX_SIDE = 65533                      # the stored position + 2 must fit a u16: side + 2 <= 65535
+
+
+def pack_map(rows, cols, iu, iv):
+    """The stored form of a map (ssx_undistort_plan, csrc/undistort.hip: k_undistort_map): -> (xs, ys, ab), three uint16 [rows, cols].
+    With X0 = iu >> 5, Y0 = iv >> 5, a = iu & 31, b = iv & 31: X0 clamped to [-2, cols] and Y0 to [-2, rows], then
+    xs = X0 + 2, ys = Y0 + 2, ab = a | b << 5.  The clamp keeps every tap's inside / outside test: at -2 both taps of the axis (-2, -1)
+    are outside as they are anywhere below, at `cols` (`rows`) both are outside as they are anywhere above; a pixel whose taps are
+    all outside is 0 whatever its fractions are."""
+    rows, cols = int(rows), int(cols)
+    if rows < 1 or cols < 1 or rows > MAP_MAX_SIDE or cols > MAP_MAX_SIDE:
+        raise ValueError("pack_map: %d x %d: a side is 1 .. %d" % (rows, cols, MAP_MAX_SIDE))
+    iu, iv = np.asarray(iu, dtype=np.int64), np.asarray(iv, dtype=np.int64)
+    if iu.shape != (rows, cols) or iv.shape != (rows, cols):
+        raise ValueError("pack_map: iu and iv are [rows, cols]")
+    X0 = np.clip(iu >> 5, -2, cols)
+    Y0 = np.clip(iv >> 5, -2, rows)
+    return (X0 + 2).astype(np.uint16), (Y0 + 2).astype(np.uint16), ((iu & 31) | ((iv & 31) << 5)).astype(np.uint16)
+
+
+def unpack_map(xs, ys, ab):
+    """-> (iu', iv') int64 with remap(img, iu', iv') == remap(img, iu, iv) for every image of the map's size"""
+    xs, ys, ab = (np.asarray(v).astype(np.int64) for v in (xs, ys, ab))
+    return ((xs - 2) << 5) | (ab & 31), ((ys - 2) << 5) | ((ab >> 5) & 31)
+
+
+def clamped_share(rows, cols, iu, iv):
+    """the share of a map's pixels whose integer position pack_map's clamp changes"""
+    X0, Y0 = np.asarray(iu) >> 5, np.asarray(iv) >> 5
+    return float(((X0 < -2) | (X0 > cols) | (Y0 < -2) | (Y0 > rows)).mean())
+
+
 def all_taps_inside(rows, cols, iu, iv):
     X0, Y0 = iu >> 5, iv >> 5
     return (X0 >= 0) & (X0 + 1 < cols) & (Y0 >= 0) & (Y0 + 1 < rows)
