@@ -918,6 +918,38 @@ SSX_API ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary
                                              float threshold, float ratio, int32_t pairs_cap,
                                              int32_t* pairs_out /* max_candidates x pairs_cap x 2 */,
                                              ssx_reloc_query_result* res);
+/* The same query for one frame of each of n databases of ONE context in one call (the streams of a cohort that lost
+ * tracking together): one launch chain and ONE synchronisation for all jobs; neither number depends on n, on
+ * max_candidates or on the number of stored keyframes (growing a database's arena or table for a commit adds that
+ * growth's own synchronisation, planning a new image shape its own).  Every job has a database of its own; all of them
+ * and the vocabulary belong to one context, the images share rows, cols and stride.  commit_pending != 0:
+ * ssx_kfdb_add_pending(db) first, inside the same chain -- the keyframe is scored and matched like any stored one
+ * (n_scored counts it, it can be cand[0]) and nothing is pending afterwards; a job without it only reads its database,
+ * the pending keyframe included.  Per job, *res and pairs_out (max_candidates x pairs_cap x 2) are bit for bit what
+ * ssx_kfdb_add_pending (when asked for) + ssx_kfdb_relocalize_query return, whatever n is and wherever the job stands in
+ * the table, and the stored contents of every database equal what those calls leave.  images_on_device as
+ * ssx_kfdb_process_keyframe_batch.  Rejected before anything is touched, pending keyframes included: n < 0, a missing
+ * db / res / status_out / image, two jobs with one database, a database of another context, differing strides,
+ * commit_pending with nothing pending or an id that does not ascend, and the argument checks of the single query
+ * (SSX_ERR_INVALID_ARG); n_features * pyramid_levels > 65535 or n * max_candidates > 65535 (SSX_ERR_UNSUPPORTED).
+ * n == 0: SSX_OK.  What depends on the data goes to the job's *status_out -- SSX_ERR_CAPACITY when some candidate has
+ * more than pairs_cap pairs, every count true and the first pairs_cap pairs of each written -- while the other jobs
+ * complete; the call returns the first status that is not SSX_OK, by the rule of ssx_kfdb_process_keyframe_batch.  A HIP
+ * error (SSX_ERR_HIP) leaves the stored keyframes and the pending keyframe of every database as they were.  An empty
+ * database, a job without features, no surviving keypoint or an empty vocabulary: n_candidates = 0 for that job. */
+typedef struct ssx_reloc_query_job {
+  ssx_kf_database* db;
+  const uint8_t* img; int32_t stride;
+  int32_t n_features; const ssx_keypoint* features;
+  int32_t commit_pending;                 /* != 0: ssx_kfdb_add_pending(db) first, inside the same chain */
+  int32_t pairs_cap; int32_t* pairs_out;  /* max_candidates x pairs_cap x 2 */
+  ssx_reloc_query_result* res;
+  int32_t* status_out;                    /* this job's ssx_status */
+} ssx_reloc_query_job;
+SSX_API ssx_status ssx_kfdb_relocalize_query_batch(ssx_vocabulary* voc, int32_t n, const ssx_reloc_query_job* jobs, int32_t rows,
+                                                   int32_t cols, const ssx_orb_params* prm, int32_t pyramid_levels,
+                                                   int32_t max_candidates, float threshold, float ratio,
+                                                   int32_t images_on_device);
 
 /* ------------------------------------------------------------------------------------------------
  * The pose correction of loop closing -- replaces LoopClosing::ComputeCorrectPose (src/ssvio/loopclosing.cpp:147-243)

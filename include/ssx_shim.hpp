@@ -540,6 +540,63 @@ inline std::vector<KeyframeDatabase::KeyframeStep> ProcessNewKeyframes(const ORB
   return out;
 }
 
+// The candidate query of several streams that lost tracking: KeyframeDatabase::RelocalizeQuery for every entry in ONE call
+// (ssx_kfdb_relocalize_query_batch: one launch chain and one synchronisation for all of them).  The databases and the vocabulary belong to
+// one Context, the images share rows, cols and stride.  add_to_database_first: AddToKeyframeDatabase() of the keyframe the database's last
+// step left pending, inside the same call -- that keyframe is a candidate like any stored one.  Per entry the bytes of the single call.
+struct RelocalizeRequest {
+  KeyframeDatabase* database;
+  const uint8_t* image;
+  const std::vector<ssx_keypoint>* features;
+  bool add_to_database_first;
+};
+inline std::vector<std::vector<KeyframeDatabase::RelocCandidate>> RelocalizeQueries(const ORBVocabulary& voc, const RelocalizeRequest* requests, size_t n, int stride, int rows,
+                                                                                    int cols, const ORBextractor& extractor, int max_candidates, float threshold,
+                                                                                    float ratio = 0.75f, int pyramid_levels = 8)
+{
+  if (!voc.get()) throw std::invalid_argument("RelocalizeQueries: no vocabulary loaded");
+  std::vector<std::vector<KeyframeDatabase::RelocCandidate>> out(n);
+  if (n == 0) return out;
+  const size_t K = (size_t)std::max(max_candidates, 1);
+  std::vector<std::vector<int32_t>> pairs(n);
+  std::vector<size_t> cap(n);
+  std::vector<int32_t> status(n, SSX_OK);
+  std::vector<ssx_reloc_query_result> res(n);
+  std::vector<ssx_reloc_query_job> jobs(n);
+  for (size_t j = 0; j < n; ++j) {
+    const RelocalizeRequest& q = requests[j];
+    if (!q.database || !q.features) throw std::invalid_argument("RelocalizeQueries: a request without database or features");
+    cap[j] = std::max<size_t>(4096, q.features->size() * (size_t)std::max(pyramid_levels, 1));
+    pairs[j].resize(2 * K * cap[j]);
+    jobs[j] = ssx_reloc_query_job{q.database->get(), q.image, stride, (int32_t)q.features->size(), q.features->data(), q.add_to_database_first ? 1 : 0,
+                                  (int32_t)cap[j], pairs[j].data(), &res[j], &status[j]};
+  }
+  Context& ctx = requests[0].database->context();
+  ssx_status st = ssx_kfdb_relocalize_query_batch(voc.get(), (int32_t)n, jobs.data(), rows, cols, &extractor.params(), pyramid_levels, max_candidates, threshold, ratio, 0);
+  for (size_t j = 0; j < n && st == SSX_ERR_CAPACITY; ++j) {
+    if (status[j] != SSX_ERR_CAPACITY) continue;             // a larger stored keyframe: the counts are known now, that query once more (its commit is done)
+    for (int32_t c = 0; c < res[j].n_candidates; ++c) cap[j] = std::max(cap[j], (size_t)res[j].cand[c].n_pairs);
+    pairs[j].assign(2 * K * cap[j], 0);
+    jobs[j].commit_pending = 0; jobs[j].pairs_cap = (int32_t)cap[j]; jobs[j].pairs_out = pairs[j].data();
+    const ssx_status again = ssx_kfdb_relocalize_query_batch(voc.get(), 1, &jobs[j], rows, cols, &extractor.params(), pyramid_levels, max_candidates, threshold, ratio, 0);
+    if (again != SSX_OK) ctx.check(again);
+  }
+  for (size_t j = 0; j < n; ++j)
+    if (status[j] != SSX_OK) ctx.check((ssx_status)status[j]);
+  if (st != SSX_OK && st != SSX_ERR_CAPACITY) ctx.check(st);
+  for (size_t j = 0; j < n; ++j) {
+    out[j].resize((size_t)res[j].n_candidates);
+    for (int32_t c = 0; c < res[j].n_candidates; ++c) {
+      const ssx_reloc_candidate& q = res[j].cand[c];
+      KeyframeDatabase::RelocCandidate& o = out[j][(size_t)c];
+      o.key_frame_id = (unsigned long)q.kf_id; o.score = q.score; o.has_descriptors = q.no_descriptors == 0; o.min_distance = q.min_distance;
+      const int32_t* p = pairs[j].data() + 2 * (size_t)c * cap[j];
+      for (int32_t i = 0; i < q.n_pairs; ++i) o.set_valid_feature_matches.emplace_hint(o.set_valid_feature_matches.end(), p[2 * i], p[2 * i + 1]);
+    }
+  }
+  return out;
+}
+
 // The pose of several candidates in ONE call (ssx_pnp_pose_batch): per job solvePnPRansac under the contract of ssx_pnp_ransac (100
 // iterations, 5.991 px as the reference passes them) and, where it found a pose, OptimizeCurrentPose over all pairs from it.  xyz / uv /
 // inlier_out of every job are the caller's arrays; the results are written into the jobs.

@@ -1,5 +1,5 @@
 // ssvio_amd/csrc/kf_batch.hpp -- the jobs of the keyframe database's chain (loop.hip): a device table of them for
-// ssx_kfdb_process_keyframe_batch, one by value as a kernel argument for the single calls; and the job-indexed launches the chain borrows
+// ssx_kfdb_process_keyframe_batch and ssx_kfdb_relocalize_query_batch, one by value as a kernel argument for the single calls; and the job-indexed launches the chain borrows
 // from orb.hip (pyramid, blur, k_describe_at), voc.hip (k_voc_words) and stereo.hip (k_bf_match).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,7 +13,7 @@
 // replicated keypoints, k_describe_at's outputs, the per-feature words and weights); the image of job j is image j of the ORB plan.
 struct KfJobDev {
   int32_t kp0, n_in;              // first pyramid keypoint and their number (features x levels)
-  int32_t n_elig;                 // stored keyframes k_kfdb_score scores, the one this job commits included; 0: the job's workgroups exit
+  int32_t n_elig;                 // stored keyframes k_kfdb_score scores (and k_kfdb_topk ranks), the one this job commits included; 0: the job's workgroups exit
   int32_t commit;                 // != 0: k_kfdb_commit moves c_* into c_blob first
   // the pending arrays in the database's own buffer, each of capacity n_in
   ssx_keypoint* p_kps; uint8_t* p_desc; int32_t* p_cls; int32_t* p_ids; double* p_vals;

@@ -31,10 +31,10 @@
 //                lane by lane over 64-entry chunks like the chain of k_kfdb_score.  Both sums are doubles whose value depends on the order
 //                of the additions, so neither is a tree.
 // k_kfdb_commit  the pending arrays into a blob of the arena and its row into the table.
-// k_kfdb_topk    one workgroup: the K <= 8 largest keys (float bits << 32) | ~row of the scores -- per thread in registers, merged in K
+// k_kfdb_topk    one workgroup per job: the K <= 8 largest keys (float bits << 32) | ~row of the scores -- per thread in registers, merged in K
 //                rounds of a block-wide maximum -- screened by the threshold and by a share of the best, and the match job of every
 //                candidate filled on the device, so that the match kernels run for all K behind it without a round trip.
-// One entry per stage: pairs, compact, bow and commit take (jobs, one) -- a workgroup or a grid row per job of a device table (kf_batch.hpp),
+// One entry per stage: pairs, compact, bow, commit and topk take (jobs, one) -- a workgroup or a grid row per job of a device table (kf_batch.hpp),
 // or with jobs == null the one job as a kernel argument -- and read their counts from the job's StepHdr in device memory.  The score kernel
 // alone keeps k_kfdb_score<LDS> for one query and k_kfdb_score_jobs for a table: merged it was measurably slower (launch_score).
 //
@@ -50,6 +50,9 @@
 //   ssx_kfdb_relocalize_query        the query of a frame that lost tracking: the chain with one job by value into scratch of
 //       its own and over EVERY stored keyframe, k_kfdb_topk, the match kernels over the table it filled, ONE synchronisation.  The database
 //       and its pending keyframe are only read.
+//   ssx_kfdb_relocalize_query_batch  that query for one frame of each of n databases of one context (the lost streams of a batched cohort):
+//       the chain over a job table into scratch of the call, a job's commit of its pending keyframe inside it, k_kfdb_topk with a workgroup
+//       per job, the match kernels once over the n x K table, ONE copy of the n result blocks and ONE synchronisation.
 //   ssx_kfdb_detect_loop / ssx_kfdb_match_features / ssx_kfdb_debug_bow   one stage on a caller's arrays: the score launch, the match
 //       launch and the words + BowVector launch of the chain, each with one job by value.
 #include <algorithm>
@@ -492,8 +495,8 @@ constexpr size_t kMatchPairsOff = 256;             // a block of the match outpu
 // floating-point arithmetic but the narrowing and the one product ratio * f_best, no atomics: a pure function of the scores.
 // Threads 0 .. max_cand - 1 then screen their candidate (f >= threshold, f >= ratio * f_best: both hold for a prefix of the order)
 // and fill its match job, with nl = 0 where there is nothing to match (no candidate, no descriptors on either side).
-__global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const double* scores, int n_rows, const char* arena, const KfRow* rows, int max_cand, float threshold,
-                                                             float ratio, RelocDev* out, KfMatchJob* jobs, RelocMatch mb)
+__device__ __forceinline__ void topk_block(const double* scores, int n_rows, const char* arena, const KfRow* rows, int max_cand, float threshold, float ratio,
+                                           RelocDev* out, const StepHdr* hdr, KfMatchJob* jobs, const RelocMatch& mb)
 {
   __shared__ unsigned long long s_wave[kPairsThreads / 64];
   __shared__ unsigned long long s_top[kTopK];
@@ -538,12 +541,13 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const double* score
   const bool ok = c < max_cand && key != 0 && f >= threshold && f >= ratio * f_best;
   const int n_cand = __popcll(__ballot(ok));
   if (c == 0) { out->n_cand = n_cand; out->pad = 0; }
+  if (hdr && c == 0) { out->h.n_pyr = hdr->n_pyr; out->h.n_bow = hdr->n_bow; out->h.best = hdr->best; }   // a table's block takes its job's header along: one copy brings both down
   if (c >= kTopK) return;
   const int row = (int)~(unsigned)key;
   out->row[c] = ok ? row : -1;
   out->fbits[c] = ok ? (unsigned)(key >> 32) : 0u;
   if (c >= max_cand) return;
-  const int n_cur = out->h.n_pyr;                             // (k_kf_compact's count, an earlier launch)
+  const int n_cur = hdr ? hdr->n_pyr : out->h.n_pyr;          // (k_kf_compact's count, an earlier launch)
   KfMatchJob j{};
   j.cur_desc = mb.cur_desc; j.cur_cls = mb.cur_cls;
   j.idx = mb.idx + (size_t)c * mb.max_nl; j.dist = mb.dist + (size_t)c * mb.max_nl;
@@ -559,6 +563,19 @@ __global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const double* score
     }
   }
   jobs[c] = j;
+}
+
+// One workgroup per job.  The single query: the job `one` and its RelocMatch `mb1` by value, its result block `out` for a header, `jobs`
+// its max_cand match jobs.  A table: job i scores j.n_elig rows of its own database, reads header i of `hdr`, writes block i of `out`
+// and slice i of `jobs`, and finds its slices of the scratch and of the mapped output in entry i of `mbs`.
+__global__ __launch_bounds__(kPairsThreads) void k_kfdb_topk(const KfJobDev* tab, KfJobDev one, const RelocMatch* mbs, RelocMatch mb1, int max_cand, float threshold,
+                                                             float ratio, RelocDev* out, const StepHdr* hdr, KfMatchJob* jobs)
+{
+  const unsigned i = blockIdx.x;
+  with_job(tab, one, i, [&](const KfJobDev& j) __attribute__((always_inline)) {
+    if (tab) topk_block(j.scores, j.n_elig, j.arena, static_cast<const KfRow*>(j.rows), max_cand, threshold, ratio, out + i, hdr + i, jobs + (size_t)i * max_cand, mbs[i]);
+    else topk_block(j.scores, j.n_elig, j.arena, static_cast<const KfRow*>(j.rows), max_cand, threshold, ratio, out, nullptr, jobs, mb1);
+  });
 }
 
 }  // namespace
@@ -867,7 +884,37 @@ hipError_t match_phase(ssx_ctx* ctx, DevBuf& io, HostBuf& stage, MatchEntry* e, 
   return hipSuccess;
 }
 
-void report_stats(const KfChainStats& s, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
+// A query's result block `hh` (`ran`: k_kfdb_topk wrote it) and its K match results in the mapped output `ho` into *res and pairs_out, against
+// the host mirror of its database.  SSX_ERR_CAPACITY: some candidate has more than pairs_cap pairs (every count true, the first pairs_cap written).
+ssx_status reloc_result(const ssx_kf_database* db, const char* who, int job, const RelocDev& hh, bool ran, int K, const char* ho, size_t out_stride, int32_t pairs_cap,
+                        int32_t* pairs_out, ssx_reloc_query_result* res, KfChainStats& st)
+{
+  ssx_ctx* ctx = db->ctx;
+  const int n_db = (int)db->ids.size();
+  res->n_pyramid = hh.h.n_pyr; res->n_bow = hh.h.n_bow;
+  const int n_cand = ran ? std::min(std::max(hh.n_cand, 0), K) : 0;
+  res->n_candidates = n_cand;
+  int over = -1;
+  for (int k = 0; k < n_cand; ++k) {
+    ssx_reloc_candidate& q = res->cand[k];
+    const int row = hh.row[k];
+    if (row < 0 || row >= n_db) { ctx->set_error("%s: %scandidate %d names row %d of %d", who, JobTag(job).s, k, row, n_db); return SSX_ERR_HIP; }
+    q.row = row; q.kf_id = db->ids[row];
+    memcpy(&q.score, &hh.fbits[k], 4);
+    q.no_descriptors = db->rows[row].n_desc < 0 ? 1 : 0;
+    const MatchResult r = match_out_read((const int32_t*)(ho + out_stride * (size_t)k));
+    q.n_pairs = r.n_pairs; q.min_distance = r.min_distance; st.bytes_down += match_out_crossed(r);
+    copy_pairs(r, pairs_cap, pairs_out + (size_t)2 * k * pairs_cap);
+    if (q.n_pairs > pairs_cap && over < 0) over = k;
+  }
+  if (over >= 0) {
+    ctx->set_error("%s: %scandidate %d has %d pairs but capacity %d", who, JobTag(job).s, over, res->cand[over].n_pairs, pairs_cap);
+    return SSX_ERR_CAPACITY;
+  }
+  return SSX_OK;
+}
+
+void report_stats(const KfChainStats& s,int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down)
 {
   if (launches) *launches = s.launches; if (synchronisations) *synchronisations = s.syncs;
   if (bytes_up) *bytes_up = s.bytes_up; if (bytes_down) *bytes_down = s.bytes_down;
@@ -1195,8 +1242,8 @@ ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, c
   hipStream_t s = ctx->stream;
   SSX_HIP_TRY(ctx, chain_enqueue(ctx, voc, db->stage, c, nullptr, st));
   if (n_db > 0) {
-    SSX_PROF(ctx, KID_LOOP_TOPK, hipLaunchKernelGGL(k_kfdb_topk, dim3(1), dim3(kPairsThreads), 0, s, one.scores, n_db, db->arena.as<char>(), db->table.as<KfRow>(), K,
-                                                    threshold, ratio, dh, jobs, mb));
+    SSX_PROF(ctx, KID_LOOP_TOPK, hipLaunchKernelGGL(k_kfdb_topk, dim3(1), dim3(kPairsThreads), 0, s, (const KfJobDev*)nullptr, one, (const RelocMatch*)nullptr, mb, K,
+                                                    threshold, ratio, dh, (const StepHdr*)nullptr, jobs));
     SSX_HIP_TRY(ctx, hipGetLastError());
     ++st.launches;
     if (max_nl > 0) {                                         // (else no stored keyframe has a descriptor: nothing can match)
@@ -1208,28 +1255,155 @@ ssx_status ssx_kfdb_relocalize_query(ssx_kf_database* db, ssx_vocabulary* voc, c
   SSX_HIP_TRY(ctx, hipMemcpyAsync(hh, dh, sizeof(RelocDev), hipMemcpyDeviceToHost, s));
   SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
   ++st.syncs; st.bytes_down += (int64_t)sizeof(RelocDev);
-  res->n_pyramid = hh->h.n_pyr; res->n_bow = hh->h.n_bow;
-  const int n_cand = n_db > 0 ? std::min(std::max(hh->n_cand, 0), K) : 0;
-  res->n_candidates = n_cand;
-  int over = -1;
-  for (int k = 0; k < n_cand; ++k) {
-    ssx_reloc_candidate& q = res->cand[k];
-    const int row = hh->row[k];
-    if (row < 0 || row >= n_db) { ctx->set_error("%s: candidate %d names row %d of %d", who, k, row, n_db); return SSX_ERR_HIP; }
-    q.row = row; q.kf_id = db->ids[row];
-    memcpy(&q.score, &hh->fbits[k], 4);
-    q.no_descriptors = db->rows[row].n_desc < 0 ? 1 : 0;
-    const MatchResult r = match_out_read((const int32_t*)(ho + out_stride * (size_t)k));
-    q.n_pairs = r.n_pairs; q.min_distance = r.min_distance; st.bytes_down += match_out_crossed(r);
-    copy_pairs(r, pairs_cap, pairs_out + (size_t)2 * k * pairs_cap);
-    if (q.n_pairs > pairs_cap && over < 0) over = k;
+  const ssx_status rs = reloc_result(db, who, -1, *hh, n_db > 0, K, ho, out_stride, pairs_cap, pairs_out, res, st);
+  if (rs != SSX_ERR_HIP) db->last = st;
+  return rs;
+}
+
+// The candidate query for one frame of each of n databases of one context (the lost streams of a batched cohort) as ONE enqueue: the
+// chain over a job table as ssx_kfdb_process_keyframe_batch issues it -- a job's commit of its pending keyframe inside it, so that the
+// keyframe is scored and matched like any stored one -- into scratch of the call (voc->io: no database's pending arrays are written),
+// k_kfdb_topk with a workgroup per job, the match kernels once over the n x max_candidates table it filled, ONE copy of the n result
+// blocks and ONE synchronisation.  Each job's scratch and its slice of the mapped output are sized by its own host mirror's largest
+// n_desc (the keyframe it commits included), the match grid by the largest of all.
+ssx_status ssx_kfdb_relocalize_query_batch(ssx_vocabulary* voc, int32_t n, const ssx_reloc_query_job* jobs, int32_t rows, int32_t cols, const ssx_orb_params* prm,
+                                           int32_t pyramid_levels, int32_t max_candidates, float threshold, float ratio, int32_t images_on_device)
+{
+  static const char* const who = "ssx_kfdb_relocalize_query_batch";
+  if (n < 0) return SSX_ERR_INVALID_ARG;
+  if (n == 0) return SSX_OK;
+  if (!voc || !jobs || !prm || rows <= 0 || cols <= 0 || pyramid_levels < 1 || pyramid_levels > ssxorb::MAX_LEVELS || max_candidates < 1 || max_candidates > kTopK ||
+      !std::isfinite(ratio) || ratio < 0.f || ratio > 1.f || !(threshold >= 0.f))
+    return SSX_ERR_INVALID_ARG;
+  ssx_ctx* ctx = voc->ctx;
+  const int K = max_candidates;
+  // ---- nothing is touched before every job has passed ----
+  std::vector<const ssx_kf_database*> seen;
+  for (int j = 0; j < n; ++j) {
+    const ssx_reloc_query_job& q = jobs[j];
+    const FrameArgs fa{q.img, q.stride, rows, cols, prm, q.n_features, q.features, pyramid_levels, q.pairs_cap, q.pairs_out};
+    if (!q.db || !q.res || !q.status_out || !frame_args_ok(fa)) {
+      ctx->set_error("%s: job %d: a missing database / result / status / image / array, a stride below the width or a negative count", who, j);
+      return SSX_ERR_INVALID_ARG;
+    }
+    if (q.db->ctx != ctx) { ctx->set_error("%s: job %d: the database and the vocabulary belong to different contexts", who, j); return SSX_ERR_INVALID_ARG; }
+    if (q.stride != jobs[0].stride) { ctx->set_error("%s: the images of a call share one stride", who); return SSX_ERR_INVALID_ARG; }
+    if (std::find(seen.begin(), seen.end(), q.db) != seen.end()) { ctx->set_error("%s: job %d names the database of an earlier job", who, j); return SSX_ERR_INVALID_ARG; }
+    seen.push_back(q.db);
+    if (ssx_status s = check_pyramid_bound(ctx, who, j, fa)) return s;
+    if (q.commit_pending) {
+      if (!q.db->pending.valid) { ctx->set_error("%s: job %d: commit_pending but no keyframe is pending", who, j); return SSX_ERR_INVALID_ARG; }
+      if (ssx_status s = check_commit(q.db, who, j, q.db->pending.kf_id)) return s;
+    }
   }
-  db->last = st;
-  if (over >= 0) {
-    ctx->set_error("%s: candidate %d has %d pairs but capacity %d", who, over, res->cand[over].n_pairs, pairs_cap);
-    return SSX_ERR_CAPACITY;
+  if ((int64_t)n * K > 65535) { ctx->set_error("%s: %d jobs x %d candidates: more than 65535 match jobs", who, n, K); return SSX_ERR_UNSUPPORTED; }
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  KfChainStats st{};
+  ctx->kf_batch = st;
+  // ---- what every job is, as if its commit had happened ----
+  struct Job { ssx_kf_database::Pending pe; bool commit; int N, n_db, max_nl; size_t blob, keys_stride, out_stride; char* out; };
+  std::vector<Job> J(n);
+  int max_N = 0, max_nl = 0;
+  for (int j = 0; j < n; ++j) {
+    const ssx_reloc_query_job& q = jobs[j];
+    ssx_kf_database* db = q.db;
+    Job& a = J[j];
+    a.commit = q.commit_pending != 0; a.pe = db->pending; a.N = q.n_features * pyramid_levels;
+    a.blob = a.commit ? blob_bytes(a.pe.n_bow, a.pe.n_pyr) : 0;
+    a.n_db = (int)db->ids.size() + (a.commit ? 1 : 0);
+    a.max_nl = a.commit ? a.pe.n_pyr : 0;
+    for (const KfRow& r : db->rows) a.max_nl = std::max(a.max_nl, r.n_desc);
+    a.keys_stride = sort_scratch_bytes(a.max_nl) / 8;
+    a.out_stride = (match_out_bytes(a.max_nl) + 255) & ~size_t(255);
+    max_N = std::max(max_N, a.N); max_nl = std::max(max_nl, a.max_nl);
+    if (a.commit) {                                           // the growth a commit needs, with its own synchronisation as in ssx_kfdb_add_pending
+      int moved = 0;
+      SSX_HIP_TRY(ctx, grow_for_commit(db, a.blob, &moved));
+      st.syncs += moved;
+    }
   }
-  return SSX_OK;
+  // ---- the describe block (the job table and the jobs' RelocMatch at its head), the scratch, the pinned block: every allocation before the first enqueue ----
+  std::vector<ssxorb::DescribeJob> dj(n);
+  for (int j = 0; j < n; ++j) dj[j] = ssxorb::DescribeJob{jobs[j].img, jobs[j].features, jobs[j].n_features};
+  ssxorb::DescribedBatch d;
+  static_assert(sizeof(KfJobDev) % 8 == 0, "the RelocMatch table follows the job table");
+  const size_t o_mb = sizeof(KfJobDev) * (size_t)n;
+  if (ssx_status s = ssxorb::describe_batch_prepare(ctx, n, dj.data(), jobs[0].stride, rows, cols, *prm, pyramid_levels, images_on_device != 0,
+                                                    o_mb + sizeof(RelocMatch) * (size_t)n, &d))
+    return s;
+  st.syncs += d.syncs;
+  KfJobDev* tab = reinterpret_cast<KfJobDev*>(d.host_extra);
+  RelocMatch* mbs = reinterpret_cast<RelocMatch*>(d.host_extra + o_mb);
+  for (int j = 0, kp0 = 0; j < n; kp0 += J[j].N, ++j) {
+    tab[j] = KfJobDev{}; mbs[j] = RelocMatch{};
+    tab[j].kp0 = kp0; tab[j].n_in = J[j].N; tab[j].n_elig = J[j].N > 0 ? J[j].n_db : 0;   // (no features: nothing is scored, no candidate)
+  }
+  Chain c; c.n = n; c.jobs = tab; c.dev_jobs = reinterpret_cast<const KfJobDev*>(d.dev_extra); c.bound = max_N;
+  RelocDev* dh; KfMatchJob* mt; std::vector<char*> frame(n);
+  SSX_HIP_TRY(ctx, chain_reserve(voc->io, voc->stage, c, sizeof(StepHdr) * (size_t)n, [&](auto&& f) {
+    f(dh, sizeof(RelocDev) * (size_t)n); f(mt, sizeof(KfMatchJob) * (size_t)n * K);
+    for (int j = 0; j < n; ++j) {
+      PendArrays pa{};
+      f(frame[j], pend_arrays(nullptr, J[j].N, pa));
+      f(mbs[j].idx, (size_t)4 * K * J[j].max_nl); f(mbs[j].dist, (size_t)4 * K * J[j].max_nl); f(mbs[j].keys, (size_t)8 * K * J[j].keys_stride);
+    }
+  }));
+  // the mapped pinned block: [the n result blocks' copy | per job: a match result per candidate slot, each for the job's max_nl pairs]
+  RelocDev* hh;
+  auto pinned = [&](auto&& f) { f(hh, sizeof(RelocDev) * (size_t)n); for (int j = 0; j < n; ++j) f(J[j].out, J[j].out_stride * (size_t)K); };
+  SSX_HIP_TRY(ctx, voc->stage.reserve(carve(nullptr, pinned)));
+  char* hs = voc->stage.as<char>();
+  carve(hs, pinned);
+  void* dp = nullptr;
+  SSX_HIP_TRY(ctx, hipHostGetDevicePointer(&dp, hs, 0));
+  for (int j = 0; j < n; ++j) {
+    const ssx_reloc_query_job& q = jobs[j];
+    const Job& a = J[j];
+    if (a.commit) commit_job(tab[j], q.db);
+    PendArrays pa{};
+    pend_arrays(frame[j], a.N, pa); job_arrays(tab[j], pa, q.db);
+    RelocMatch& mb = mbs[j];
+    mb.cur_desc = pa.desc; mb.cur_cls = pa.cls; mb.max_nl = a.max_nl; mb.keys_stride = a.keys_stride;
+    if (a.keys_stride == 0) mb.keys = nullptr;
+    mb.out = (char*)dp + (a.out - hs); mb.out_stride = a.out_stride;
+    for (int k = 0; k < K; ++k) match_out_preset((int32_t*)(a.out + a.out_stride * (size_t)k));
+    *q.res = ssx_reloc_query_result{};
+    for (int k = 0; k < kTopK; ++k) { q.res->cand[k].kf_id = -1; q.res->cand[k].row = -1; q.res->cand[k].min_distance = -1; }
+    q.res->n_scored = a.n_db;
+    *q.status_out = SSX_OK;
+  }
+  // ---- one enqueue for all jobs, one copy, one synchronisation ----
+  hipStream_t s = ctx->stream;
+  if (ssx_status e = ssxorb::describe_batch_launch(ctx, n, c.dev_jobs, max_N, &d)) return e;
+  st.launches += d.launches; st.bytes_up += (int64_t)d.bytes_up;
+  c.kps = d.kps; c.desc = d.desc; c.keep = d.keep;
+  SSX_HIP_TRY(ctx, chain_enqueue(ctx, voc, voc->stage, c, nullptr, st));
+  SSX_PROF(ctx, KID_LOOP_TOPK, hipLaunchKernelGGL(k_kfdb_topk, dim3(n), dim3(kPairsThreads), 0, s, c.dev_jobs, KfJobDev{}, reinterpret_cast<const RelocMatch*>(d.dev_extra + o_mb),
+                                                  RelocMatch{}, K, threshold, ratio, dh, c.hdr, mt));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  ++st.launches;
+  if (max_nl > 0) {                                           // (else no keyframe of any job has a descriptor: nothing can match)
+    SSX_HIP_TRY(ctx, launch_match_jobs(ctx, mt, KfMatchJob{}, n * K, max_nl));
+    st.launches += 2;
+  }
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(hh, dh, sizeof(RelocDev) * (size_t)n, hipMemcpyDeviceToHost, s));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
+  ++st.syncs; st.bytes_down += (int64_t)(sizeof(RelocDev) * (size_t)n);
+  // ---- the commits have happened: the host mirrors follow, and nothing is pending there ----
+  for (int j = 0; j < n; ++j)
+    if (J[j].commit) {
+      commit_mirror(jobs[j].db, J[j].pe.kf_id, KfRow{tab[j].c_off, J[j].pe.n_bow, J[j].pe.n_pyr}, J[j].blob);
+      jobs[j].db->pending.valid = false;
+    }
+  ssx_status first = SSX_OK;
+  for (int j = 0; j < n; ++j) {
+    const ssx_reloc_query_job& q = jobs[j];
+    const ssx_status rs = reloc_result(q.db, who, j, hh[j], true, K, J[j].out, J[j].out_stride, q.pairs_cap, q.pairs_out, q.res, st);
+    *q.status_out = rs;
+    if (rs != SSX_OK && first == SSX_OK) first = rs;
+  }
+  ctx->kf_batch = st;
+  return first;
 }
 
 // The keyframe steps of n databases of one context as ONE enqueue of the chain (and the job-indexed kernels of orb.hip / voc.hip /

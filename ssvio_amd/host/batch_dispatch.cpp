@@ -1,6 +1,7 @@
 // ssvio_amd/host/batch_dispatch.cpp -- see batch_dispatch.hpp
 #include "batch_dispatch.hpp"
 
+#include <algorithm>
 #include <chrono>
 #include <stdexcept>
 
@@ -18,6 +19,23 @@ void Isolated(const std::vector<size_t>& idx, std::vector<std::string>& errs, lo
   for (size_t i : idx) {
     try { call(std::vector<size_t>{i}); ++calls; ++jobs; } catch (const std::exception& e) { errs[i] = e.what(); }
   }
+}
+
+std::vector<PoseCall> PackPoseCalls(const std::vector<int>& n_jobs, const std::vector<std::vector<size_t>>& groups, int max_jobs)
+{
+  std::vector<PoseCall> calls;
+  if (max_jobs < 1) throw std::invalid_argument("PackPoseCalls: a call holds at least one job");
+  for (const std::vector<size_t>& g : groups) {
+    int room = 0;                                   // (every group begins a call of its own)
+    for (size_t r : g)
+      for (int first = 0; first < n_jobs.at(r);) {
+        if (room == 0) { calls.emplace_back(); room = max_jobs; }
+        const int count = std::min(n_jobs[r] - first, room);
+        calls.back().push_back(PosePart{r, first, count});
+        first += count; room -= count;
+      }
+  }
+  return calls;
 }
 
 BatchDispatch::BatchDispatch(int streams, std::vector<Kind> kinds, Dispatcher frame, Dispatcher keyframe)

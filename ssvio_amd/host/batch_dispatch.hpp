@@ -38,6 +38,19 @@ std::vector<std::vector<size_t>> Groups(const std::vector<Key>& keys)
   return g;
 }
 
+// The pose jobs of a dispatch's requests (the candidates of every stream that lost tracking) packed into calls of at most max_jobs jobs:
+// a call is a list of (request, first job, count).  The requests of one group (equal key: the intrinsics a call's jobs share) fill calls
+// in the order they stand in, a request that does not fit is cut, and a request without jobs takes no part; the groups follow each other
+// in order of first appearance.  The library makes every job independent of its place in a call, so packing changes no bits.
+struct PosePart {
+  size_t request; int first, count;
+  bool operator==(const PosePart& o) const { return request == o.request && first == o.first && count == o.count; }
+};
+using PoseCall = std::vector<PosePart>;
+std::vector<PoseCall> PackPoseCalls(const std::vector<int>& n_jobs, const std::vector<std::vector<size_t>>& groups, int max_jobs);
+template <class Key>
+std::vector<PoseCall> PackPoseCalls(const std::vector<int>& n_jobs, const std::vector<Key>& keys, int max_jobs) { return PackPoseCalls(n_jobs, Groups(keys), max_jobs); }
+
 class BatchDispatch {
  public:
   // serve(slots, errs, calls, jobs): the requests of `slots` (ascending), all of this kind; errs[i] is what the thread of slots[i]

@@ -20,7 +20,10 @@
 //   error <17 digits> need_correct <0|1> corrected <0|1> fused <n> same_point <n> pg_iters <n> moved_active <n> moved_other <n> skipped <n> duplicate <n>
 //   and, with Relocalization.Open: 1, behind them one line per attempt of a lost front-end:
 //   reloc_frame <frame id> candidates <n> pairs <n> poses <n> inliers <n> accepted <keyframe id|-1>
-// Relocalization.Open: 1 works per stream of an unbatched --streams; with --batched >= 1 it is refused.
+// Relocalization.Open: 1 works per stream of an unbatched --streams.  --batched >= 1 with the key set is refused unless --loop_batched=1 is
+// given (the rule of loop closing): the candidate queries of the streams that lost tracking then go out as ssx_kfdb_relocalize_query_batch
+// calls and the poses of their candidates as packed ssx_pnp_pose_batch calls, and every stream still writes the bytes of its single run.
+// The cohort shares one vocabulary there: with loop closing on, a DBOW2.VOC.Path that is missing or cannot be read is refused at once.
 // Camera.NeedUndistortion: 1 (every frame's pair goes through ssx_undistort first) works per stream of an unbatched --streams.  --batched >= 1 with the key
 // set is refused unless --undistort_batched=1 is given: the pairs of a cohort's streams then go through the lenses' stored maps in ONE
 // ssx_undistort_plan_apply call per frame (two jobs a stream, one map per camera of the rig), and every stream still writes the bytes of its
@@ -119,14 +122,14 @@ int main(int argc, char** argv)
 
     const int streams = streams_s.empty() ? 1 : std::max(1, std::atoi(streams_s.c_str()));
     const bool loop_batched = !loop_batched_s.empty() && std::atoi(loop_batched_s.c_str()) != 0;
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Open") != 0 && !loop_batched) {
+      std::fprintf(stderr, "--batched=%s with Relocalization.Open: 1 is not supported without --loop_batched=1 (the lost streams' queries and poses go through the "
+                   "dispatcher, on the cohort's loop context); or run --streams unbatched, or switch relocalisation off\n", batched_s.c_str());
+      return 2;
+    }
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Loop.Closing.Open") != 0 && !loop_batched) {
       std::fprintf(stderr, "--batched=%s with Loop.Closing.Open: 1 is not supported without --loop_batched=1 (the loop step batched over the streams); "
                    "or run --streams unbatched, or switch loop closing off\n", batched_s.c_str());
-      return 2;
-    }
-    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Open") != 0) {
-      std::fprintf(stderr, "--batched=%s with Relocalization.Open: 1 is not supported: a batched stream's loop context belongs to the dispatcher's thread; "
-                   "run --streams unbatched, or switch relocalisation off\n", batched_s.c_str());
       return 2;
     }
     const bool undistort_batched = !undistort_batched_s.empty() && std::atoi(undistort_batched_s.c_str()) != 0;
@@ -142,6 +145,17 @@ int main(int argc, char** argv)
     if (loop_batched && Setting(config).Get<int>("Loop.Closing.Open") != 0 && Setting(config).Get<int>("Loop.Closing.Async") != 0) {
       std::fprintf(stderr, "--loop_batched=1 with Loop.Closing.Async: 1 is not supported: the batched loop step is the inline one (no third thread per stream)\n");
       return 2;
+    }
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && loop_batched && Setting(config).Get<int>("Relocalization.Open") != 0 &&
+        Setting(config).Get<int>("Loop.Closing.Open") != 0) {
+      // a lost stream asks the cohort's loop context, which loads ONE vocabulary for all streams when the first of them is built: said
+      // here, before a context is made, and not by every stream's thread in turn
+      const std::string voc_path = Setting(config).Get<std::string>("DBOW2.VOC.Path");
+      if (voc_path.empty() || !std::ifstream(voc_path).is_open()) {
+        std::fprintf(stderr, "--batched=%s --loop_batched=1 with Relocalization.Open: 1 is not supported without a vocabulary the cohort can share: "
+                     "DBOW2.VOC.Path \"%s\" cannot be read\n", batched_s.c_str(), voc_path.c_str());
+        return 2;
+      }
     }
     const bool warmup = warmup_s.empty() || std::atoi(warmup_s.c_str()) != 0;
     if (streams > 1) {
@@ -242,6 +256,9 @@ int main(int argc, char** argv)
           std::printf("batched loop steps: loop_calls %ld loop_jobs %ld loop_s %.6f (%.3f ms per call, %.1f jobs each); a correction's single calls %ld, %.1f ms\n",
                       bs.loop_calls, bs.loop_jobs, bs.loop_s, 1e3 * bs.loop_s / std::max(1L, bs.loop_calls), bs.loop_jobs / std::max(1.0, (double)bs.loop_calls),
                       bs.single_calls, 1e3 * bs.single_s);
+        if (bs.reloc_calls || bs.pose_calls)
+          std::printf("batched relocalisation: reloc_calls %ld reloc_jobs %ld pose_calls %ld pose_jobs %ld reloc_s %.6f pose_s %.6f\n", bs.reloc_calls, bs.reloc_jobs,
+                      bs.pose_calls, bs.pose_jobs, bs.reloc_s, bs.pose_s);
       }
       return 0;
     }

@@ -16,7 +16,7 @@
 namespace ssx::host {
 
 namespace {
-enum Kind : int { LK, PO, DET, LKS, TRI, BA, LOOP, CALL, UND, N_KINDS };   // indices into the table of Impl::Kinds
+enum Kind : int { LK, PO, DET, LKS, TRI, BA, LOOP, CALL, UND, RELOC, POSES, N_KINDS };   // indices into the table of Impl::Kinds
 // what the jobs of one call share -- the keys of Groups
 struct ImageSize {
   int rows = 0, cols = 0;
@@ -38,6 +38,11 @@ struct BaReq { ssx_ba_window* win = nullptr; ssx_ba_result* res = nullptr; };
 struct UndReq { const uint8_t* src[2] = {nullptr, nullptr}; uint8_t* dst[2] = {nullptr, nullptr}; ssx_undistort_params prm[2] = {}; ImageSize size; };
 // one keyframe step of loop closing as a stream files it (ssx_kfdb_process_keyframe_batch): the job and what a call's jobs must share
 struct LoopReq { ssx_kfdb_step_job job{}; ssx_orb_params prm{}; ImageSize size; int levels = 0, min_db = 0, min_gap = 0; float threshold = 0.f; int32_t status = 0; };
+// the candidate query of a stream that lost tracking (ssx_kfdb_relocalize_query_batch), in the same form
+struct RelocReq { ssx_reloc_query_job job{}; ssx_orb_params prm{}; ImageSize size; int levels = 0, candidates = 0; float threshold = 0.f, ratio = 0.f; int32_t status = 0; };
+// the pose jobs of that stream's candidates (ssx_pnp_pose_batch): the jobs of a call share the intrinsics
+struct PosesReq { const double* K4 = nullptr; std::vector<ssx_pnp_pose_job>* jobs = nullptr; };
+using K4Bytes = std::array<unsigned char, 4 * sizeof(double)>;
 }
 
 struct StreamBatcher::Impl {
@@ -50,12 +55,18 @@ struct StreamBatcher::Impl {
   // their keyframe a little later catch up and all of them meet in one window solve (a batched solve costs what a single one costs).
   // The loop step follows the window solve inside the backend: served after it, the streams that solved a little later merge into one
   // loop call; the rare single calls of a correction come last.
+  // Relocalisation (a lost stream's candidate query, then the poses of its candidates) stands at the very beginning of a frame and is
+  // served first, the query before the poses: streams that lose tracking at the same frame meet in one query and then in one pose call.
+  // Both run on the loop context and so belong to this dispatcher, never beside a loop step or a correction's call.  The front-end's
+  // thread files them from its own slot while it holds the stream's map mutex; its backend's slot may be blocked on that mutex, but a
+  // backend slot that is not filing rests IDLE, which the rest condition does not wait for, so the rule stands as it is
+  // (tests/host/test_reloc_dispatch_units.cpp).
   // Undistortion (Camera.NeedUndistortion) is the first call of a frame and is served LAST of the per-frame kinds, by the reasoning of
   // the header's "pose-only before LK": the later stage first, so that the cohort arrives where a straggler waits.
   Impl(int device_, int streams) : device(device_), S(streams), po_ctx(device_), ba_ctx(device_), det_ctx(device_), tri_ctx(device_), lk_req(streams),
                                    po_req(streams), det_req(streams), tri_req(streams), ba_req(2 * (size_t)streams), loop_req(2 * (size_t)streams),
-                                   call_req(2 * (size_t)streams, nullptr), und_req(streams),
-                                   core(streams, Kinds(), {{PO, LK, UND}, false, false}, {{DET, LKS, TRI, BA, LOOP, CALL}, true, true})
+                                   call_req(2 * (size_t)streams, nullptr), und_req(streams), reloc_req(2 * (size_t)streams), poses_req(2 * (size_t)streams),
+                                   core(streams, Kinds(), {{PO, LK, UND}, false, false}, {{RELOC, POSES, DET, LKS, TRI, BA, LOOP, CALL}, true, true})
   {
   }
   ~Impl()
@@ -244,6 +255,74 @@ struct StreamBatcher::Impl {
       }
       loop_ctx->check(rc);                          // rejected before anything was touched: Isolated tries the jobs one by one
     })};
+    // the candidate query of the lost streams: the jobs of a call share image size, stride, extractor settings, levels, candidates,
+    // threshold and ratio; statuses and errors as the loop step's
+    auto reloc_key = [this](int k) {
+      const RelocReq& r = reloc_req[k];
+      return std::make_tuple(r.size, r.job.stride, Bytes(r.prm), r.levels, r.candidates, r.threshold, r.ratio);
+    };
+    t[RELOC] = {"relocalisation query", Grouped(reloc_key, [this](Slots slots, Errs errs) {
+      static const std::string who = "ssx_kfdb_relocalize_query_batch: ";
+      std::vector<ssx_reloc_query_job> jobs;
+      for (int k : slots) { RelocReq& r = reloc_req[k]; r.status = SSX_OK; r.job.status_out = &r.status; jobs.push_back(r.job); }
+      const RelocReq& r0 = reloc_req[slots[0]];
+      const ssx_status rc = ssx_kfdb_relocalize_query_batch(voc, (int32_t)jobs.size(), jobs.data(), r0.size.rows, r0.size.cols, &r0.prm, r0.levels, r0.candidates,
+                                                            r0.threshold, r0.ratio, 1);
+      if (rc == SSX_OK) return;
+      bool per_job = false;                         // (the rule of the loop step: a return value that a job carries is that job's own outcome)
+      for (int k : slots) per_job = per_job || reloc_req[k].status == (int32_t)rc;
+      const std::string why = ssx_last_error(loop_ctx->get());
+      if (per_job) {
+        for (size_t j = 0; j < slots.size(); ++j) {
+          const int32_t js = reloc_req[slots[j]].status;
+          if (js != SSX_OK && js != SSX_ERR_CAPACITY) errs[j] = who + "job status " + std::to_string(js) + ": " + why;
+        }
+        return;
+      }
+      if (rc == SSX_ERR_HIP) {                      // the library had begun: no job of the call has a result and none is tried again
+        for (std::string& e : errs) e = who + why;
+        return;
+      }
+      loop_ctx->check(rc);                          // rejected before anything was touched: Isolated tries the jobs one by one
+    })};
+    // the poses of the lost streams' candidates: packed into calls by PackPoseCalls, the out fields copied back to each requester's jobs;
+    // a call that is refused goes once more part by part, so that only the request at fault gets the error
+    t[POSES] = {"relocalisation poses", [this](Slots slots, Errs errs, long& calls, long& jobs) {
+      std::vector<int> counts;
+      std::vector<K4Bytes> keys;
+      for (int k : slots) {
+        counts.push_back((int)poses_req[k].jobs->size());
+        K4Bytes b;
+        std::memcpy(b.data(), poses_req[k].K4, b.size());
+        keys.push_back(b);
+      }
+      for (const PoseCall& pc : PackPoseCalls(counts, keys, SSX_PNP_BATCH_MAX)) {
+        std::vector<size_t> parts(pc.size());
+        for (size_t i = 0; i < parts.size(); ++i) parts[i] = i;
+        std::vector<std::string> part_errs(pc.size());
+        long unused_calls = 0, unused_jobs = 0;
+        Isolated(parts, part_errs, unused_calls, unused_jobs, [&](const std::vector<size_t>& sub) {
+          std::vector<ssx_pnp_pose_job> packed;
+          for (size_t i : sub) {
+            const std::vector<ssx_pnp_pose_job>& src = *poses_req[slots[pc[i].request]].jobs;
+            packed.insert(packed.end(), src.begin() + pc[i].first, src.begin() + pc[i].first + pc[i].count);
+          }
+          loop_ctx->check(ssx_pnp_pose_batch(loop_ctx->get(), poses_req[slots[pc[sub[0]].request]].K4, (int32_t)packed.size(), packed.data(), 100, 5.991, 5.991, 1.0));
+          size_t at = 0;
+          for (size_t i : sub) {
+            std::vector<ssx_pnp_pose_job>& dst = *poses_req[slots[pc[i].request]].jobs;
+            for (int j = 0; j < pc[i].count; ++j, ++at) {
+              ssx_pnp_pose_job& d = dst[(size_t)(pc[i].first + j)];
+              const ssx_pnp_pose_job& q = packed[at];
+              std::memcpy(d.pose_out, q.pose_out, sizeof d.pose_out);
+              d.found = q.found; d.n_ransac_inliers = q.n_ransac_inliers; d.best_hypothesis = q.best_hypothesis; d.n_inliers = q.n_inliers;
+            }
+          }
+          ++calls; jobs += (long)packed.size();
+        });
+        for (size_t i = 0; i < pc.size(); ++i) if (!part_errs[i].empty()) errs[pc[i].request] = part_errs[i];
+      }
+    }};
     // undistortion: the jobs of a call share the image size; its plan holds one map per camera (ssx_undistort_plan_add finds a set it was
     // shown by its bytes).  All left images, then all right ones: the raw pairs and the results then stand in the arena in ascending
     // order -- one copy up and, when the whole cohort is in the call, one copy down (ssx_undistort_plan_apply).
@@ -290,6 +369,8 @@ struct StreamBatcher::Impl {
   std::vector<LoopReq> loop_req;
   std::vector<std::function<void()>*> call_req;
   std::vector<UndReq> und_req;
+  std::vector<RelocReq> reloc_req;
+  std::vector<PosesReq> poses_req;
   BatchDispatch core;                               // (last: its threads start when the rest is made and stop before it goes)
 };
 
@@ -362,14 +443,7 @@ class BatchedLoopCompute final : public LoopCompute {
                        int min_id_gap, float threshold, ssx_kfdb_step_result& res, std::vector<int32_t>& pairs) override
   {
     const int slot = im_.core.Slot(k_);
-    const size_t bytes = (size_t)img.rows * img.cols;
-    if (bytes > pin_bytes_) {                       // the keyframe's image in a pinned buffer of the stream's own, read there by the GPU
-      ssx_host_free(pin_);
-      pin_ = static_cast<uint8_t*>(ssx_host_alloc(bytes));
-      if (!pin_) throw std::runtime_error("StreamBatcher: no pinned memory for the loop step's image");
-      pin_bytes_ = bytes;
-    }
-    std::memcpy(pin_, img.ptr(), bytes);
+    Pin(img);
     pairs.resize(2 * std::max<size_t>(1024, features.size() * (size_t)std::max(pyramid_levels, 1)));
     LoopReq& r = im_.loop_req[slot];
     for (int attempt = 0;; ++attempt) {
@@ -396,8 +470,52 @@ class BatchedLoopCompute final : public LoopCompute {
   {
     Single([&] { im_.loop_ctx->check(ssx_loop_correct(im_.loop_ctx->get(), &prob, 20, &res)); });
   }
+  // The candidate query of a lost front-end as one job of ssx_kfdb_relocalize_query_batch.  The keyframe of AddPending is not in the
+  // database yet (nothing was launched for it): the job carries commit_pending, as the stream's next keyframe step would have
+  void RelocalizeQuery(const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, int max_candidates,
+                       float threshold, float ratio, ssx_reloc_query_result& res, std::vector<std::vector<int32_t>>& pairs) override
+  {
+    const int slot = im_.core.Slot(k_);
+    Pin(img);
+    const size_t K = (size_t)std::max(max_candidates, 1);
+    size_t cap = std::max<size_t>(1024, features.size() * (size_t)std::max(pyramid_levels, 1));
+    std::vector<int32_t> flat;
+    RelocReq& r = im_.reloc_req[slot];
+    for (int attempt = 0;; ++attempt) {
+      flat.assign(2 * K * cap, 0);
+      r = RelocReq{};
+      r.job.db = db_; r.job.img = pin_; r.job.stride = img.cols; r.job.n_features = (int32_t)features.size(); r.job.features = features.data();
+      r.job.commit_pending = commit_next_ ? 1 : 0; r.job.pairs_cap = (int32_t)cap; r.job.pairs_out = flat.data(); r.job.res = &res;
+      r.prm = prm; r.size = {img.rows, img.cols}; r.levels = pyramid_levels; r.candidates = max_candidates; r.threshold = threshold; r.ratio = ratio;
+      im_.core.SubmitAndWait(slot, RELOC);
+      commit_next_ = false;                         // (the call ran: the keyframe of AddPending is stored)
+      if (r.status != SSX_ERR_CAPACITY || attempt > 0) break;
+      for (int c = 0; c < res.n_candidates; ++c) cap = std::max(cap, (size_t)res.cand[c].n_pairs);   // a larger stored keyframe: the counts are known now
+    }
+    if (r.status != SSX_OK) throw std::runtime_error("ssx_kfdb_relocalize_query_batch: job status " + std::to_string(r.status));
+    pairs.assign((size_t)res.n_candidates, {});
+    for (int c = 0; c < res.n_candidates; ++c) pairs[c].assign(flat.begin() + 2 * c * cap, flat.begin() + 2 * (c * cap + (size_t)res.cand[c].n_pairs));
+  }
+  void PosesBatch(const double* K4, std::vector<ssx_pnp_pose_job>& jobs) override
+  {
+    const int slot = im_.core.Slot(k_);
+    im_.poses_req[slot] = PosesReq{K4, &jobs};
+    im_.core.SubmitAndWait(slot, POSES);
+  }
 
  private:
+  // the image in a pinned buffer of the stream's own, read there by the GPU
+  void Pin(const Image& img)
+  {
+    const size_t bytes = (size_t)img.rows * img.cols;
+    if (bytes > pin_bytes_) {
+      ssx_host_free(pin_);
+      pin_ = static_cast<uint8_t*>(ssx_host_alloc(bytes));
+      if (!pin_) throw std::runtime_error("StreamBatcher: no pinned memory for the loop step's image");
+      pin_bytes_ = bytes;
+    }
+    std::memcpy(pin_, img.ptr(), bytes);
+  }
   void Single(std::function<void()> call)
   {
     const int slot = im_.core.Slot(k_);
@@ -660,6 +778,8 @@ StreamBatcher::Stats StreamBatcher::stats()
     add(CALL, t.single_calls, single_jobs, t.single_s);
     long und_requests = 0;
     add(UND, t.und_calls, und_requests, t.und_s);
+    add(RELOC, t.reloc_calls, t.reloc_jobs, t.reloc_s);
+    add(POSES, t.pose_calls, t.pose_jobs, t.pose_s);
     t.und_jobs += 2 * und_requests;                 // (a request is a frame's pair)
     t.wait_s += im->core.wait_s();
   }

@@ -17,7 +17,9 @@
 // pinned buffers (filled by the stream's own thread), nothing is staged inside the batched calls.  Loop closing's keyframe step
 // (LoopCompute::ProcessKeyframe) is one more request kind of that dispatcher: the streams of a cohort share one loop context and ONE
 // vocabulary, each has its keyframe database there, and their steps go out as ssx_kfdb_process_keyframe_batch; the calls of a
-// correction are rare and are made by the dispatcher one at a time.
+// correction are rare and are made by the dispatcher one at a time.  Relocalisation (Relocalization.Open: 1) is two more kinds there: the
+// candidate queries of the streams that lost tracking go out as ONE ssx_kfdb_relocalize_query_batch -- a stream's pending keyframe is
+// committed inside it -- and the pose jobs of their candidates are packed into ssx_pnp_pose_batch calls.
 //
 // Camera.NeedUndistortion: a frame's pair goes through the lenses' stored maps first (Compute::UndistortPair), as one more request kind of the
 // per-frame dispatcher: ONE ssx_undistort_plan_apply for the cohort, two jobs per stream, the maps shared by all streams of one rig.
@@ -74,6 +76,9 @@ class StreamBatcher {
     double single_s = 0;
     long und_calls = 0, und_jobs = 0;                // undistortion (Camera.NeedUndistortion): ssx_undistort_plan_apply calls and their jobs, two per frame
     double und_s = 0;
+    long reloc_calls = 0, reloc_jobs = 0;            // relocalisation: ssx_kfdb_relocalize_query_batch calls and their jobs (one per lost stream and frame)
+    long pose_calls = 0, pose_jobs = 0;              // ssx_pnp_pose_batch calls of the lost streams' candidates and the pose jobs in them
+    double reloc_s = 0, pose_s = 0;
   };
   Stats stats();
   void ResetStats();                                 // (after the streams' warm-up: the counters then describe the frames alone)

@@ -51,9 +51,18 @@ class RelocQueryResult(C.Structure):
                 ("cand", RelocCandidate * RELOC_MAX_CANDIDATES)]
 
 
+class RelocQueryJob(C.Structure):
+    """ssx_reloc_query_job"""
+    _fields_ = [("db", C.c_void_p), ("img", C.c_void_p), ("stride", C.c_int32), ("n_features", C.c_int32), ("features", C.c_void_p),
+                ("commit_pending", C.c_int32), ("pairs_cap", C.c_int32), ("pairs_out", i32_p), ("res", C.POINTER(RelocQueryResult)),
+                ("status_out", i32_p)]
+
+
 def _bind(lib):
     if getattr(lib, "_kfdb_bound", False):
         return
+    lib.ssx_kfdb_relocalize_query_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(RelocQueryJob), C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32,
+                                                    C.c_int32, C.c_float, C.c_float, C.c_int32]
     lib.ssx_kfdb_relocalize_query.argtypes = [C.c_void_p, C.c_void_p, u8_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32, C.c_void_p,
                                               C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, i32_p, C.POINTER(RelocQueryResult)]
     lib.ssx_kfdb_process_keyframe_batch.argtypes = [C.c_void_p, C.c_int32, C.POINTER(StepJob), C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32,
@@ -287,8 +296,57 @@ def process_keyframe_batch(voc, jobs, prm, threshold, pyramid_levels=8, min_db_s
     return out
 
 
+def _reloc_dict(r, pairs, pairs_cap):
+    cands = [dict(kf_id=q.kf_id, score=np.float32(q.score), row=q.row, no_descriptors=bool(q.no_descriptors), n_pairs=q.n_pairs,
+                  min_distance=q.min_distance, pairs=pairs[c, :min(q.n_pairs, pairs_cap)].copy())
+             for c, q in enumerate(r.cand[:max(0, min(r.n_candidates, RELOC_MAX_CANDIDATES))])]
+    return dict(n_pyramid=r.n_pyramid, n_bow=r.n_bow, n_scored=r.n_scored, candidates=cands)
+
+
+def relocalize_query_batch(voc, jobs, prm, max_candidates=4, threshold=0.0, ratio=0.75, pyramid_levels=8, images_on_device=False):
+    """The candidate query of several databases of voc's context in ONE call (ssx_kfdb_relocalize_query_batch).  jobs = dicts of
+    db (KeyframeDatabase), image, features and optionally commit_pending (add_pending() first, inside the call) and pairs_cap; the
+    images share one shape and row stride.  -> one dict per job in relocalize_query's form plus status, the job's ssx_status.
+    SsxError carries .results (that list) when the call reports a job's status; a call that was rejected has touched nothing."""
+    ctx = voc.ctx
+    _bind(ctx.lib)
+    n, K = len(jobs), int(max_candidates)
+    table = (RelocQueryJob * max(n, 1))()
+    res, status, keep = (RelocQueryResult * max(n, 1))(), (C.c_int32 * max(n, 1))(), []
+    shape = None
+    for j, q in enumerate(jobs):
+        image = np.asarray(q["image"])
+        if image.ndim != 2 or image.dtype != np.uint8 or image.strides[1] != 1:
+            image = np.ascontiguousarray(image, dtype=np.uint8)
+        if shape is None:
+            shape = image.shape
+        elif image.shape != shape:
+            raise ValueError("the images of a call share one shape")
+        features = np.ascontiguousarray(q["features"], dtype=KP_DTYPE)
+        cap = q.get("pairs_cap")
+        if cap is None:                                           # bounded by the stored keyframes' descriptors and by those of the
+            cap = q["db"].size()[2]                               # keyframe the job commits (no more than its pyramid keypoints)
+            if q.get("commit_pending"):
+                cap += 65535
+        cap = max(int(cap), 0)
+        pairs = np.zeros((max(K, 1), max(cap, 1), 2), np.int32)
+        keep.append((image, features, pairs, cap))
+        table[j] = RelocQueryJob(q["db"].handle, image.ctypes.data, image.strides[0], len(features), features.ctypes.data,
+                                 1 if q.get("commit_pending") else 0, cap, ptr(pairs, i32_p), C.pointer(res[j]), C.cast(C.byref(status, 4 * j), i32_p))
+    rows, cols = shape if shape is not None else (0, 0)
+    st = ctx.lib.ssx_kfdb_relocalize_query_batch(voc.handle, n, table, rows, cols, C.byref(prm), int(pyramid_levels), K, float(threshold), float(ratio),
+                                                 1 if images_on_device else 0)
+    out = [dict(_reloc_dict(res[j], keep[j][2], keep[j][3]), status=status[j]) for j in range(n)]
+    try:
+        ctx.check(st)
+    except Exception as e:
+        e.results = out
+        raise
+    return out
+
+
 def debug_last_batch(ctx):
-    """tests / tools hook -> dict(launches, syncs, bytes_up, bytes_down) of the context's last process_keyframe_batch"""
+    """tests / tools hook -> dict(launches, syncs, bytes_up, bytes_down) of the context's last process_keyframe_batch or relocalize_query_batch"""
     _bind(ctx.lib)
     a, b, c, d = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
     ctx.check(ctx.lib.ssx_kfdb_debug_last_batch(ctx.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
