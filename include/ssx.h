@@ -951,6 +951,64 @@ SSX_API ssx_status ssx_kfdb_relocalize_query_batch(ssx_vocabulary* voc, int32_t 
                                                    int32_t max_candidates, float threshold, float ratio,
                                                    int32_t images_on_device);
 
+/* The guided search of relocalisation, the second step behind an accepted candidate (tools/guided_model.py states the
+ * rule operation by operation): P map points are projected into the frame with the pose just found, K4 = (fx, fy, cx,
+ * cy) and T_cw12 = [R|t] row-major, in f64 with every operation rounded on its own; a point behind the camera or with a
+ * non-finite camera position is SSX_GUIDED_BEHIND, one that does not fall in [0, cols) x [0, rows) SSX_GUIDED_OUTSIDE.
+ * A point's descriptors are ALL stored descriptors of keyframe point_kf[p] whose class id is point_cls[p]
+ * (SSX_GUIDED_NO_DESCRIPTOR, and no error, for an id that is not stored, a keyframe stored without descriptors or none
+ * of that class).  Feature i of the F frame features is a candidate iff taken[i] == 0 (taken null: none is taken),
+ * |x_i - u| <= radius and |y_i - v| <= radius (edges inclusive) and it has a frame descriptor (SSX_GUIDED_NO_FEATURE
+ * when there is none); its distance is the least Hamming distance over the point's and its own descriptors.  The best
+ * candidate has the lowest distance d1, then the lowest index; d2 is the lowest distance of any OTHER candidate.  The
+ * point is accepted iff d1 <= max_distance (else SSX_GUIDED_DISTANCE) and there is no second or 100 d1 < ratio_pct d2
+ * in integers (else SSX_GUIDED_RATIO).  A feature goes to one point: of the accepted points that claim it the lowest
+ * d1 wins, then the lowest point; the others are SSX_GUIDED_CLAIMED.  Per point: feat_out (-1 unless MATCHED), d1_out,
+ * d2_out (-1 where there is none), status_out, uv_out (nullable; zeros for BEHIND); *n_matched counts the MATCHED.
+ * The result is a pure function of the arguments and the stored keyframes: two calls give the same bytes.
+ * ssx_kfdb_project_match is the stage on a caller's arrays (as ssx_kfdb_match_features is for MatchFeatures): n_cur
+ * frame descriptors with the feature each belongs to, cur_cls[j] in [0, F).
+ * SSX_ERR_INVALID_ARG, before anything is touched (the outputs included): a null required pointer; P, F or n_cur < 0;
+ * a cur_cls outside [0, F); rows or cols < 1; radius negative or not finite; max_distance outside [0, 256]; ratio_pct
+ * outside [0, 100]; a non-finite K4 or T_cw12.  SSX_ERR_UNSUPPORTED: P > 65535.  P == 0, F == 0 or n_cur == 0:
+ * SSX_OK, every point that projects into the image is SSX_GUIDED_NO_FEATURE (or SSX_GUIDED_NO_DESCRIPTOR), *n_matched
+ * = 0.  The database is only read. */
+typedef enum ssx_guided_status {
+  SSX_GUIDED_MATCHED = 0,
+  SSX_GUIDED_BEHIND,
+  SSX_GUIDED_OUTSIDE,
+  SSX_GUIDED_NO_DESCRIPTOR,
+  SSX_GUIDED_NO_FEATURE,
+  SSX_GUIDED_DISTANCE,
+  SSX_GUIDED_RATIO,
+  SSX_GUIDED_CLAIMED
+} ssx_guided_status;
+SSX_API ssx_status ssx_kfdb_project_match(ssx_kf_database* db, const double* K4, const double* T_cw12, int32_t rows,
+                                          int32_t cols, int32_t F, const float* feat_xy /* F x 2 */,
+                                          const uint8_t* taken /* nullable */, int32_t n_cur, const uint8_t* cur_desc,
+                                          const int32_t* cur_cls, int32_t P, const int64_t* point_kf,
+                                          const int32_t* point_cls, const double* xyz, double radius,
+                                          int32_t max_distance, int32_t ratio_pct, int32_t* feat_out, int32_t* d1_out,
+                                          int32_t* d2_out, int32_t* status_out, double* uv_out /* nullable, P x 2 */,
+                                          int32_t* n_matched);
+/* The call the system uses: the frame is described exactly as ssx_kfdb_relocalize_query describes it (on purpose a
+ * second time: a describe on a rare path is cheaper than a "last query" slot every other call on the database would
+ * have to invalidate), and the search reads the described arrays where they lie.  F = n_features, a feature's position
+ * is features[i].x, .y; taken (nullable) has n_features entries.  The outputs are, bit for bit, what
+ * ssx_kfdb_project_match returns on the frame's descriptors and class ids.  One upload behind the describe's, one result
+ * copy and ONE synchronisation (two more the first time an image shape is planned); neither the launches nor the
+ * synchronisations depend on P, n_features or the number of stored keyframes.  The stored keyframes and the pending
+ * keyframe are as before the call.  Refused as ssx_kfdb_project_match, and as the query refuses its frame arguments;
+ * SSX_ERR_UNSUPPORTED also for n_features * pyramid_levels > 65535. */
+SSX_API ssx_status ssx_kfdb_guided_search(ssx_kf_database* db, const uint8_t* img, int32_t stride, int32_t rows,
+                                          int32_t cols, const ssx_orb_params* prm, int32_t n_features,
+                                          const ssx_keypoint* features, int32_t pyramid_levels,
+                                          const uint8_t* taken /* nullable */, const double* K4, const double* T_cw12,
+                                          int32_t P, const int64_t* point_kf, const int32_t* point_cls,
+                                          const double* xyz, double radius, int32_t max_distance, int32_t ratio_pct,
+                                          int32_t* feat_out, int32_t* d1_out, int32_t* d2_out, int32_t* status_out,
+                                          double* uv_out /* nullable, P x 2 */, int32_t* n_matched);
+
 /* ------------------------------------------------------------------------------------------------
  * The pose correction of loop closing -- replaces LoopClosing::ComputeCorrectPose (src/ssvio/loopclosing.cpp:147-243)
  * with its cv::solvePnPRansac call (:205-206) and LoopClosing::OptimizeCurrentPose (:245-351).

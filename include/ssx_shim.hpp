@@ -466,6 +466,33 @@ class KeyframeDatabase {
     return out;
   }
 
+  // The second step of relocalisation (ssx_kfdb_guided_search; the rule: tools/guided_model.py): map points projected into the frame
+  // with the pose just found, T_cw12 = [R|t] row-major, and matched in a window round each projection against the frame's features that
+  // are not `taken` (empty: none is).  Point p's descriptors are the stored descriptors of keyframe point_kf[p] with class id
+  // point_cls[p]; a keyframe that is not stored (yet) gives SSX_GUIDED_NO_DESCRIPTOR and no error.  The database is only read.
+  struct GuidedResult {
+    std::vector<int32_t> feature, d1, d2, status;            // per point: the frame's feature (-1 unless SSX_GUIDED_MATCHED), distances, ssx_guided_status
+    std::vector<double> uv;                                  // per point: its projection
+    int n_matched = 0;
+  };
+  GuidedResult GuidedSearch(const uint8_t* image, int stride, int rows, int cols, const ORBextractor& extractor, const std::vector<ssx_keypoint>& features,
+                            const std::vector<uint8_t>& taken, const double K4[4], const double T_cw12[12], const std::vector<int64_t>& point_kf,
+                            const std::vector<int32_t>& point_cls, const std::vector<double>& xyz, double radius, int max_distance, int ratio_pct,
+                            int pyramid_levels = 8)
+  {
+    const size_t P = point_kf.size();
+    if (point_cls.size() != P || xyz.size() != 3 * P) throw std::invalid_argument("GuidedSearch: one keyframe, one class id and one position per point");
+    if (!taken.empty() && taken.size() != features.size()) throw std::invalid_argument("GuidedSearch: one taken flag per feature");
+    GuidedResult out;
+    out.feature.assign(P, -1); out.d1.assign(P, -1); out.d2.assign(P, -1); out.status.assign(P, 0); out.uv.assign(2 * P, 0.0);
+    int32_t n = 0;
+    ctx_.check(ssx_kfdb_guided_search(db_, image, stride, rows, cols, &extractor.params(), (int32_t)features.size(), features.data(), pyramid_levels,
+                                      taken.empty() ? nullptr : taken.data(), K4, T_cw12, (int32_t)P, point_kf.data(), point_cls.data(), xyz.data(), radius,
+                                      max_distance, ratio_pct, out.feature.data(), out.d1.data(), out.d2.data(), out.status.data(), out.uv.data(), &n));
+    out.n_matched = n;
+    return out;
+  }
+
   // AddToKeyframeDatabase() (:646-649) for the keyframe ProcessNewKeyframe left on the device: no byte crosses PCIe
   void AddToKeyframeDatabase() { ctx_.check(ssx_kfdb_add_pending(db_)); }
 

@@ -220,7 +220,8 @@ SSX_API ssx_status ssx_pnp_debug_p3p(ssx_ctx* ctx, const double* K4, int32_t n, 
 
 /* tests / tools hooks of the per-keyframe step (csrc/loop.hip).  What the database's last ssx_kfdb_process_keyframe issued, each counted
  * where it is issued: kernel launches, stream synchronisations (a new ORB plan's two included), bytes sent up and bytes that came down
- * (the pairs are written by the kernel into mapped pinned memory: 8 bytes of header and 8 per pair).  Any output may be NULL. */
+ * (the pairs are written by the kernel into mapped pinned memory: 8 bytes of header and 8 per pair).  Likewise for the database's last
+ * ssx_kfdb_relocalize_query or ssx_kfdb_guided_search, whichever call came last.  Any output may be NULL. */
 SSX_API ssx_status ssx_kfdb_debug_last_step(const ssx_kf_database* db, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up,
                                             int64_t* bytes_down);
 /* the same for the context's last ssx_kfdb_process_keyframe_batch (all zero after a call that failed before its first synchronisation);

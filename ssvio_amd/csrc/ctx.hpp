@@ -102,7 +102,7 @@ enum SsxKernelId {
   KID_BA_REDUCE_TRIAL, KID_ORB_RESIZE, KID_ORB_FAST, KID_ORB_OCTREE, KID_ORB_ORIENT, KID_ORB_GAUSS, KID_ORB_BRIEF,
   KID_ORB_MISC, KID_ST_BUCKET, KID_ST_MATCH, KID_ST_TRIANGULATE, KID_ST_MISC, KID_POSE_ONLY, KID_BA_COMM, KID_BA_LIN_SCHUR,
   KID_LOOP_SCORE, KID_LOOP_MATCH, KID_LOOP_PAIRS, KID_PNP_RANSAC, KID_LOOP_COMPACT, KID_LOOP_WORDS, KID_LOOP_BOW, KID_LOOP_COMMIT,
-  KID_LC_KEYFRAMES, KID_LC_REANCHOR, KID_WIN_ANCHOR, KID_LOOP_TOPK, KID_UNDISTORT, KID_UNDISTORT_MAP,
+  KID_LC_KEYFRAMES, KID_LC_REANCHOR, KID_WIN_ANCHOR, KID_LOOP_TOPK, KID_LOOP_GUIDED, KID_UNDISTORT, KID_UNDISTORT_MAP,
   KID_UNDISTORT_REMAP, KID_COUNT
 };
 static const char* const kSsxKernelNames[KID_COUNT] = {
@@ -110,7 +110,7 @@ static const char* const kSsxKernelNames[KID_COUNT] = {
   "k_resize", "k_fast_cells", "k_octree", "k_orient", "k_gauss7", "k_orient_brief", "orb_misc", "k_row_bucket", "k_match",
   "k_triangulate_matches", "stereo_misc", "k_pose_only", "ba_allreduce", "k_lin_schur",
   "k_kfdb_score", "kfdb_bf_match", "k_kfdb_pairs", "k_pnp_ransac", "k_kf_compact", "kf_voc_words", "k_kf_bow", "k_kfdb_commit",
-  "k_lc_keyframes", "k_reanchor_points", "k_win_anchor", "k_kfdb_topk", "k_undistort", "k_undistort_map",
+  "k_lc_keyframes", "k_reanchor_points", "k_win_anchor", "k_kfdb_topk", "kfdb_guided", "k_undistort", "k_undistort_map",
   "k_undistort_remap"};
 
 struct SsxProf {

@@ -55,6 +55,8 @@
 //       per job, the match kernels once over the n x K table, ONE copy of the n result blocks and ONE synchronisation.
 //   ssx_kfdb_detect_loop / ssx_kfdb_match_features / ssx_kfdb_debug_bow   one stage on a caller's arrays: the score launch, the match
 //       launch and the words + BowVector launch of the chain, each with one job by value.
+//   ssx_kfdb_guided_search / ssx_kfdb_project_match   the second step of relocalisation, in loop_guided.inc: the describe and
+//       k_kfdb_project -> k_kfdb_claim x 2, ONE synchronisation; the database and its pending keyframe are only read.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -1617,3 +1619,5 @@ ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t 
 #endif
 
 }  // extern "C"
+
+#include "loop_guided.inc"   // ssx_kfdb_project_match, ssx_kfdb_guided_search: k_kfdb_project, k_kfdb_claim

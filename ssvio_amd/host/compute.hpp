@@ -79,6 +79,25 @@ class LoopCompute {
     (void)K4; (void)jobs;
     throw std::logic_error("LoopCompute::PosesBatch: this implementation cannot relocalise");
   }
+  // The second step of relocalisation (Relocalization.Guided.Open: 1; the rule: tools/guided_model.py).  ssx_kfdb_guided_search: P map
+  // points, each with the stored keyframe and the feature index there that hold its descriptors, projected into the frame with T_cw12 =
+  // [R|t] row-major and matched in a window against the features that are not taken.  Per point the frame's feature (-1 unless matched),
+  // the two distances and the ssx_guided_status.  The database and its pending keyframe are only read.
+  struct GuidedParams { double radius = 10.0; int max_distance = 50, ratio_pct = 90; };
+  struct GuidedMatches { std::vector<int32_t> feat, d1, d2, status; int n_matched = 0; };
+  virtual void GuidedSearch(const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, const std::vector<uint8_t>& taken,
+                            const double* K4, const double* T_cw12, const std::vector<int64_t>& point_kf, const std::vector<int32_t>& point_cls,
+                            const std::vector<double>& xyz, const GuidedParams& gp, GuidedMatches& out)
+  {
+    (void)img; (void)features; (void)prm; (void)pyramid_levels; (void)taken; (void)K4; (void)T_cw12; (void)point_kf; (void)point_cls; (void)xyz; (void)gp; (void)out;
+    throw std::logic_error("LoopCompute::GuidedSearch: this implementation has no guided search");
+  }
+  // ssx_loop_pose_opt with chi2 5.991 and Huber 1.0 from pose_io over M pairs; *found = 0 when the refinement has no finite pose
+  virtual void RefinePose(const double* K4, int M, const double* xyz, const double* uv, double* pose_io, uint8_t* inlier_out, int* n_inliers, int* found)
+  {
+    (void)K4; (void)M; (void)xyz; (void)uv; (void)pose_io; (void)inlier_out; (void)n_inliers; (void)found;
+    throw std::logic_error("LoopCompute::RefinePose: this implementation has no guided search");
+  }
 };
 
 class Compute {

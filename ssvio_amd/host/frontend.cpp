@@ -130,6 +130,9 @@ bool FrontEnd::Relocalize()
   const bool ok = reference_kf_ && loop_->Relocalize(current_frame_->frame_id, img, feats, K4, r);
   std::fprintf(stderr, "[frontend] frame %lu: relocalisation %s: %zu features, %d candidates, %d pairs, %d inliers%s\n", current_frame_->frame_id,
                ok ? "succeeded" : "failed", feats.size(), r.candidates, r.pairs, r.inliers, ok ? (" against keyframe " + std::to_string(r.kf_id)).c_str() : "");
+  if (ok && r.guided)                                                  // (Relocalization.Guided.Open: 1 only)
+    std::fprintf(stderr, "[frontend] frame %lu: guided search %s: %d points, %d matched, inliers %d -> %d, matches %d -> %zu\n", current_frame_->frame_id,
+                 r.guided_accepted ? "accepted" : "refused", r.guided_points, r.guided_matches, r.first_inliers, r.guided_inliers, r.first_matches, r.matches.size());
   if (!ok) return false;
   current_frame_->pose = r.T_cw;
   current_frame_->relative_pose_to_kf = r.T_cw * reference_kf_->pose.inverse();      // reference_kf_ stays

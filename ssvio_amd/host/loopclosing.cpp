@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -47,6 +48,16 @@ LoopClosing::LoopClosing(const Setting& cfg, std::unique_ptr<LoopCompute> comput
   if (reloc_open_ && (reloc_candidates_ < 1 || reloc_candidates_ > SSX_RELOC_MAX_CANDIDATES || !(reloc_ratio_ >= 0.f && reloc_ratio_ <= 1.f) || !(reloc_threshold_ >= 0.f)))
     throw std::runtime_error("LoopClosing: Relocalization.Candidates must lie in [1, " + std::to_string(SSX_RELOC_MAX_CANDIDATES) +
                              "], Relocalization.Score.Ratio in [0, 1], and Relocalization.Threshold must not be negative");
+  // the guided search behind an accepted candidate (tools/guided_model.py): off unless its key is set
+  guided_open_ = cfg.Get<int>("Relocalization.Guided.Open") != 0;
+  if (cfg.Has("Relocalization.Guided.Neighbours")) guided_neighbours_ = cfg.Get<int>("Relocalization.Guided.Neighbours");
+  if (cfg.Has("Relocalization.Guided.Radius")) guided_.radius = cfg.Get<double>("Relocalization.Guided.Radius");
+  if (cfg.Has("Relocalization.Guided.Max.Distance")) guided_.max_distance = cfg.Get<int>("Relocalization.Guided.Max.Distance");
+  if (cfg.Has("Relocalization.Guided.Ratio")) guided_.ratio_pct = cfg.Get<int>("Relocalization.Guided.Ratio");
+  if (guided_open_ && (guided_neighbours_ < 0 || !std::isfinite(guided_.radius) || guided_.radius < 0.0 || guided_.max_distance < 0 || guided_.max_distance > 256 ||
+                       guided_.ratio_pct < 0 || guided_.ratio_pct > 100))
+    throw std::runtime_error("LoopClosing: Relocalization.Guided.Neighbours and Relocalization.Guided.Radius must not be negative, "
+                             "Relocalization.Guided.Max.Distance must lie in [0, 256] and Relocalization.Guided.Ratio in [0, 100]");
   async_ = cfg.Get<int>("Loop.Closing.Async") != 0;
   if (async_) worker_ = std::thread([this] { Worker(); });
 }
@@ -300,6 +311,84 @@ void LoopClosing::LoopCorrect(const KeyFramePtr& cur, const KeyFramePtr& loop, c
   rec.points_skipped = res.n_points_skipped;
 }
 
+// The second step behind an accepted candidate (tools/guided_model.py: gather_points, search_by_projection, refine_accept), under the
+// map mutex Relocalize's caller holds.  Gathered: the accepted keyframe, then its guided_neighbours_ neighbours before and after it in
+// the map's id order by increasing distance, the lower id first; of each, in feature order, every feature whose map point is alive, no
+// outlier, not matched by the first pass and not gathered yet, as (position, that keyframe's id, the feature's index = the class id its
+// descriptors were stored under).  One GuidedSearch with the first pass's pose, the first pass's features taken; one RefinePose from
+// that pose over the first pass's surviving pairs followed by the new ones; the result replaces the first iff it has a pose and no
+// fewer inliers.
+void LoopClosing::GuidedStep(const Image& img, const std::vector<ssx_keypoint>& features, const double* K4, RelocResult& out, RelocRecord& rec)
+{
+  std::vector<unsigned long> ids;
+  ids.reserve(map_->GetAllKeyFrames().size());
+  for (const auto& kv : map_->GetAllKeyFrames()) ids.push_back(kv.first);
+  std::sort(ids.begin(), ids.end());
+  const long at = (long)(std::lower_bound(ids.begin(), ids.end(), (unsigned long)out.kf_id) - ids.begin());
+  std::vector<long> order{at};
+  for (long step = 1; step <= (long)guided_neighbours_; ++step)
+    for (long i : {at - step, at + step})
+      if (i >= 0 && i < (long)ids.size()) order.push_back(i);
+  std::unordered_map<long, int> seen;
+  std::vector<uint8_t> taken(features.size(), 0);
+  for (const auto& m : out.matches) { seen[m.second] = 1; taken.at((size_t)m.first) = 1; }
+  std::vector<int64_t> point_kf; std::vector<int32_t> point_cls; std::vector<double> xyz; std::vector<long> point_mp;
+  for (long i : order) {
+    const KeyFramePtr& kf = map_->GetAllKeyFrames().at(ids[(size_t)i]);
+    for (size_t f = 0; f < kf->features_left.size(); ++f) {
+      MapPointPtr mp = map_->Lock(kf->features_left[f]);
+      if (!mp || mp->is_outlier || seen.count((long)mp->id)) continue;
+      seen[(long)mp->id] = 1;
+      point_kf.push_back((int64_t)kf->key_frame_id); point_cls.push_back((int32_t)f); point_mp.push_back((long)mp->id);
+      xyz.insert(xyz.end(), mp->position, mp->position + 3);
+    }
+  }
+  // the model and the kernel share every f64 operation from the matrix on: the 7-vector is converted here
+  double T12[12], R[9];
+  ssx::quat_to_R(out.T_cw.d, R);
+  for (int r = 0; r < 3; ++r) { T12[4 * r] = R[3 * r]; T12[4 * r + 1] = R[3 * r + 1]; T12[4 * r + 2] = R[3 * r + 2]; T12[4 * r + 3] = out.T_cw.d[4 + r]; }
+  // the refinement's pairs: the first pass's survivors, then the new ones
+  std::vector<double> r_xyz, r_uv; std::vector<std::pair<int32_t, long>> r_pair;
+  for (const auto& m : out.matches) {
+    MapPointPtr mp = map_->Lock(m.second);
+    if (!mp) throw std::logic_error("LoopClosing: a map point of the first pass has left the map under the map mutex");
+    r_xyz.insert(r_xyz.end(), mp->position, mp->position + 3);
+    r_uv.push_back(features[(size_t)m.first].x); r_uv.push_back(features[(size_t)m.first].y);
+    r_pair.push_back(m);
+  }
+  LoopCompute::GuidedMatches g;
+  SE3 pose = out.T_cw;
+  std::vector<uint8_t> inlier;
+  int n_after = 0, found = 0;
+  {
+    std::lock_guard<std::mutex> compute_lock(compute_mutex_);
+    compute_->GuidedSearch(img, features, orb_, pyramid_levels_, taken, K4, T12, point_kf, point_cls, xyz, guided_, g);
+    for (size_t p = 0; p < point_kf.size(); ++p) {
+      if (g.status.at(p) != SSX_GUIDED_MATCHED) continue;
+      const int32_t f = g.feat.at(p);
+      r_xyz.insert(r_xyz.end(), xyz.begin() + 3 * (long)p, xyz.begin() + 3 * (long)p + 3);
+      r_uv.push_back(features.at((size_t)f).x); r_uv.push_back(features[(size_t)f].y);
+      r_pair.emplace_back(f, point_mp[p]);
+    }
+    inlier.assign(r_pair.size(), 0);
+    compute_->RefinePose(K4, (int)r_pair.size(), r_xyz.data(), r_uv.data(), pose.d, inlier.data(), &n_after, &found);
+  }
+  rec.guided_points = (int)point_kf.size(); rec.guided_matches = g.n_matched; rec.guided_inliers = found ? n_after : -1;
+  out.guided = true; out.guided_points = rec.guided_points; out.guided_matches = rec.guided_matches; out.guided_inliers = rec.guided_inliers;
+  out.first_inliers = out.inliers; out.first_matches = (int)out.matches.size();
+  if (!found || n_after < out.inliers) return;               // refine_accept: the pose, the inliers and the matches of the first result stand untouched
+  out.guided_accepted = true;
+  out.T_cw = pose; out.inliers = n_after;
+  out.matches.clear();
+  std::unordered_map<long, int> taken_mp;
+  std::unordered_map<int32_t, int> taken_feat;
+  for (size_t i = 0; i < r_pair.size(); ++i) {                // one map point per feature, one feature per map point, first come
+    if (!inlier[i] || taken_mp.count(r_pair[i].second) || taken_feat.count(r_pair[i].first)) continue;
+    taken_mp[r_pair[i].second] = 1; taken_feat[r_pair[i].first] = 1;
+    out.matches.push_back(r_pair[i]);
+  }
+}
+
 // The caller (the front-end, in state LOST) holds Map::update_mutex; the compute lock is taken behind it.  One query, one gather per
 // candidate as Step's for ComputePose, one pose batch, one verdict.
 bool LoopClosing::Relocalize(unsigned long frame_id, const Image& img, const std::vector<ssx_keypoint>& features, const double* K4, RelocResult& out)
@@ -367,6 +456,7 @@ bool LoopClosing::Relocalize(unsigned long frame_id, const Image& img, const std
       out.matches.emplace_back(j.feat[i], j.mp[i]);
     }
     rec.accepted = out.kf_id;
+    if (guided_open_) GuidedStep(img, features, K4, out, rec);
   }
   out.candidates = rec.candidates; out.pairs = rec.pairs;
   if (!out.ok) out.inliers = rec.inliers;

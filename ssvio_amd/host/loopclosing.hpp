@@ -19,6 +19,8 @@
 //                            like Backend::worker_error_.
 // Relocalisation settings: Relocalization.Open (absent = 0), Relocalization.Candidates (absent = 4), Relocalization.Threshold (absent =
 // Loop.Threshold.Heigher), Relocalization.Score.Ratio (absent = 0.75), Relocalization.Min.Inliers (absent = numFeatures.trackingBad).
+// The guided search behind an accepted candidate: Relocalization.Guided.Open (absent = 0), .Neighbours (absent = 2),
+// .Radius (absent = 10.0 px), .Max.Distance (absent = 50), .Ratio (absent = 90, per cent).
 // Settings: Loop.Threshold.Heigher, Loop.Closig.Keyframe.Database.Min.Size, Pyramid.Level (the reference's keys and spelling),
 // Loop.Min.Keyframe.Gap (absent = 20, the constant of :79), Loop.Closing.Async (absent = 0); Loop.Show.Closing.Result is read and ignored.
 // The extractor parameters are those of :689-698 (ORBextractor.nNewFeatures).  The 1 / 15 gates of :226 are the library's.
@@ -86,13 +88,21 @@ class LoopClosing {
     SE3 T_cw;                          // the frame's pose
     std::vector<std::pair<int32_t, long>> matches;   // (feature of the frame, map point) of the pairs that survive the refinement: each feature and each map point once
     int candidates = 0, pairs = 0, inliers = 0;      // of the attempt: candidates named, their pairs in all, the most refined inliers
+    // the guided search, when it ran (Relocalization.Guided.Open: 1 and a candidate accepted): what it gathered and matched, the
+    // second refinement's inliers (-1: no pose), whether its result replaced the first pass's, and the first pass's own figures
+    bool guided = false, guided_accepted = false;
+    int guided_points = 0, guided_matches = 0, guided_inliers = 0, first_inliers = 0, first_matches = 0;
   };
   struct RelocRecord {                 // one per attempt, in order (the runner's --loop_log)
     unsigned long frame_id = 0;
     int candidates = 0, pairs = 0, poses = 0, inliers = 0;
     long accepted = -1;
+    // the guided search behind an accepted candidate (Relocalization.Guided.Open: 1): map points gathered, points it matched to a
+    // feature, inliers of the second refinement (-1: it found no pose)
+    int guided_points = 0, guided_matches = 0, guided_inliers = 0;
   };
   bool relocalization() const { return reloc_open_; }
+  bool guided() const { return guided_open_; }
   bool Relocalize(unsigned long frame_id, const Image& img, const std::vector<ssx_keypoint>& features, const double* K4, RelocResult& out);
   const std::vector<RelocRecord>& reloc_records() const { return reloc_records_; }   // read with the front-end at rest
   void WaitIdle();                     // asynchronous mode: returns when the queue is empty and the thread idle
@@ -104,6 +114,7 @@ class LoopClosing {
  private:
   void Step(const KeyFramePtr& kf);
   void LoopCorrect(const KeyFramePtr& cur, const KeyFramePtr& loop, const SE3& corrected, const std::vector<int32_t>& pairs, Record& rec);
+  void GuidedStep(const Image& img, const std::vector<ssx_keypoint>& features, const double* K4, RelocResult& out, RelocRecord& rec);
   void Worker();
   void RethrowWorkerError();           // queue_mutex_ held
 
@@ -119,6 +130,9 @@ class LoopClosing {
   bool reloc_open_ = false;
   int reloc_candidates_ = 4, reloc_min_inliers_ = 0;
   float reloc_threshold_ = 0, reloc_ratio_ = 0.75f;
+  bool guided_open_ = false;
+  int guided_neighbours_ = 2;
+  LoopCompute::GuidedParams guided_;
   std::vector<RelocRecord> reloc_records_;
   // compute_ is one context, used by one thread at a time: the loop step (this thread or the loop thread) and Relocalize (the
   // front-end's thread).  Lock order everywhere: Map::update_mutex, then this; nothing waits for the map mutex while holding it.

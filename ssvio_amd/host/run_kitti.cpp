@@ -20,6 +20,8 @@
 //   error <17 digits> need_correct <0|1> corrected <0|1> fused <n> same_point <n> pg_iters <n> moved_active <n> moved_other <n> skipped <n> duplicate <n>
 //   and, with Relocalization.Open: 1, behind them one line per attempt of a lost front-end:
 //   reloc_frame <frame id> candidates <n> pairs <n> poses <n> inliers <n> accepted <keyframe id|-1>
+//   and, only with Relocalization.Guided.Open: 1, on the same line: guided_points <n> guided_matches <n> guided_inliers <n|-1>
+//   (--batched >= 1 with that key is refused: the batched dispatcher has no guided search)
 // Relocalization.Open: 1 works per stream of an unbatched --streams.  --batched >= 1 with the key set is refused unless --loop_batched=1 is
 // given (the rule of loop closing): the candidate queries of the streams that lost tracking then go out as ssx_kfdb_relocalize_query_batch
 // calls and the poses of their candidates as packed ssx_pnp_pose_batch calls, and every stream still writes the bytes of its single run.
@@ -71,8 +73,13 @@ void WriteLoopLog(ssx::host::System& sys, const std::string& path)
                  r.inliers, r.error, r.need_correct, r.corrected, r.fused, r.same_point_skipped, r.pg_iterations, r.active_points_moved, r.other_points_moved,
                  r.points_skipped, r.duplicate_skipped);
   // then one line per relocalisation attempt of the front-end (Relocalization.Open: 1), in the same key / value form
-  for (const auto& r : sys.loop_closing()->reloc_records())
-    std::fprintf(f, "reloc_frame %lu candidates %d pairs %d poses %d inliers %d accepted %ld\n", r.frame_id, r.candidates, r.pairs, r.poses, r.inliers, r.accepted);
+  // (with Relocalization.Guided.Open: 1 the guided search's counts behind them; with the key off the line is as it was)
+  const bool guided = sys.loop_closing()->guided();
+  for (const auto& r : sys.loop_closing()->reloc_records()) {
+    std::fprintf(f, "reloc_frame %lu candidates %d pairs %d poses %d inliers %d accepted %ld", r.frame_id, r.candidates, r.pairs, r.poses, r.inliers, r.accepted);
+    if (guided) std::fprintf(f, " guided_points %d guided_matches %d guided_inliers %d", r.guided_points, r.guided_matches, r.guided_inliers);
+    std::fprintf(f, "\n");
+  }
   std::fclose(f);
 }
 
@@ -122,6 +129,11 @@ int main(int argc, char** argv)
 
     const int streams = streams_s.empty() ? 1 : std::max(1, std::atoi(streams_s.c_str()));
     const bool loop_batched = !loop_batched_s.empty() && std::atoi(loop_batched_s.c_str()) != 0;
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Guided.Open") != 0) {
+      std::fprintf(stderr, "--batched=%s with Relocalization.Guided.Open: 1 is not supported (the dispatcher of a batched cohort has no guided search); "
+                   "run --streams unbatched, or switch the guided search off\n", batched_s.c_str());
+      return 2;
+    }
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Open") != 0 && !loop_batched) {
       std::fprintf(stderr, "--batched=%s with Relocalization.Open: 1 is not supported without --loop_batched=1 (the lost streams' queries and poses go through the "
                    "dispatcher, on the cohort's loop context); or run --streams unbatched, or switch relocalisation off\n", batched_s.c_str());

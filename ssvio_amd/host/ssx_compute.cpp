@@ -1,5 +1,6 @@
 // ssvio_amd/host/ssx_compute.cpp -- Compute on libssx.so (see compute.hpp)
 #include <algorithm>
+#include <cmath>
 #include <stdexcept>
 #include <string>
 
@@ -113,6 +114,28 @@ class SsxLoopCompute final : public LoopCompute {
   void PosesBatch(const double* K4, std::vector<ssx_pnp_pose_job>& jobs) override
   {
     ctx_.check(ssx_pnp_pose_batch(ctx_.get(), K4, (int32_t)jobs.size(), jobs.data(), 100, 5.991, 5.991, 1.0));   // :205-206, :301, g2o's Huber
+  }
+  void GuidedSearch(const Image& img, const std::vector<ssx_keypoint>& features, const ssx_orb_params& prm, int pyramid_levels, const std::vector<uint8_t>& taken,
+                    const double* K4, const double* T_cw12, const std::vector<int64_t>& point_kf, const std::vector<int32_t>& point_cls, const std::vector<double>& xyz,
+                    const GuidedParams& gp, GuidedMatches& out) override
+  {
+    const size_t P = point_kf.size();
+    if (point_cls.size() != P || xyz.size() != 3 * P || (!taken.empty() && taken.size() != features.size()))
+      throw std::invalid_argument("GuidedSearch: one keyframe, one class id and one position per point, one flag per feature");
+    out.feat.assign(P, -1); out.d1.assign(P, -1); out.d2.assign(P, -1); out.status.assign(P, 0);
+    int32_t n = 0;
+    ctx_.check(ssx_kfdb_guided_search(db_, img.ptr(), img.cols, img.rows, img.cols, &prm, (int32_t)features.size(), features.data(), pyramid_levels,
+                                      taken.empty() ? nullptr : taken.data(), K4, T_cw12, (int32_t)P, point_kf.data(), point_cls.data(), xyz.data(), gp.radius,
+                                      gp.max_distance, gp.ratio_pct, out.feat.data(), out.d1.data(), out.d2.data(), out.status.data(), nullptr, &n));
+    out.n_matched = n;
+  }
+  void RefinePose(const double* K4, int M, const double* xyz, const double* uv, double* pose_io, uint8_t* inlier_out, int* n_inliers, int* found) override
+  {
+    int32_t n = 0;
+    ctx_.check(ssx_loop_pose_opt(ctx_.get(), pose_io, K4, M, xyz, uv, 5.991, 1.0, inlier_out, &n));   // :301, g2o's Huber
+    bool finite = true;
+    for (int k = 0; k < 7; ++k) finite = finite && std::isfinite(pose_io[k]);
+    *n_inliers = n; *found = finite ? 1 : 0;
   }
 
  private:

@@ -3,6 +3,9 @@
 KeyframeDatabase       ssx_kfdb_*: AddToKeyframeDatabase, DetectLoop and MatchFeatures (reference: src/ssvio/loopclosing.cpp:646-649,
                        :72-103, :105-145), and the per-keyframe step of LoopClosingThread as one call (process_keyframe / add_pending /
                        pending: ProcessNewKeyframe :596-634 + DetectLoop + MatchFeatures, the keyframe left on the device)
+                       and relocalisation: relocalize_query (the candidates of a lost frame and its matches against each) and, behind
+                       an accepted candidate, guided_search / project_match (map points projected with the pose just found and matched
+                       in a window; the rule: tools/guided_model.py)
 process_keyframe_batch ssx_kfdb_process_keyframe_batch: that step for one keyframe of each of several databases, one launch chain
 pnp_ransac             ssx_pnp_ransac: the cv::solvePnPRansac call of ComputeCorrectPose (:205-206) under the contract of
                        tools/pnp_model.py
@@ -84,6 +87,10 @@ def _bind(lib):
     lib.ssx_kfdb_detect_loop.argtypes = [C.c_void_p, C.c_int64, C.c_int32, i32_p, dbl_p, C.c_int32, C.c_float, i32_p, i64_p,
                                          C.POINTER(C.c_float), C.c_int32, dbl_p, i32_p]
     lib.ssx_kfdb_match_features.argtypes = [C.c_void_p, C.c_int64, C.c_int32, u8_p, i32_p, C.c_int32, i32_p, i32_p, i32_p]
+    guided_tail = [C.c_int32, i64_p, i32_p, dbl_p, C.c_double, C.c_int32, C.c_int32, i32_p, i32_p, i32_p, i32_p, dbl_p, i32_p]
+    lib.ssx_kfdb_project_match.argtypes = [C.c_void_p, dbl_p, dbl_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), u8_p, C.c_int32, u8_p, i32_p] + guided_tail
+    lib.ssx_kfdb_guided_search.argtypes = [C.c_void_p, u8_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(OrbParams), C.c_int32, C.c_void_p, C.c_int32, u8_p,
+                                           dbl_p, dbl_p] + guided_tail
     lib._kfdb_bound = True
 
 
@@ -221,6 +228,39 @@ class KeyframeDatabase:
             raise
         return out
 
+    def project_match(self, K4, T_cw, rows, cols, feat_xy, cur_desc, cur_class_id, point_kf, point_cls, xyz, taken=None, radius=10.0, max_distance=50,
+                      ratio_pct=90):
+        """The guided search of relocalisation on a caller's arrays (ssx_kfdb_project_match; the rule: tools/guided_model.py): the points
+        xyz [P, 3], each with the stored keyframe point_kf [P] and the class id point_cls [P] that hold its descriptors, projected with
+        K4 = (fx, fy, cx, cy) and T_cw = 12 doubles [R|t] and matched in a window of `radius` pixels against the frame's features
+        feat_xy [F, 2] (taken [F]: non-zero = no candidate) with descriptors cur_desc [n, 32] of features cur_class_id [n].
+        -> dict(feat, d1, d2, status int32 [P], uv f64 [P, 2], n_matched)"""
+        feat_xy = np.ascontiguousarray(feat_xy, dtype=np.float32).reshape(-1, 2)
+        cur_desc = np.ascontiguousarray(cur_desc, dtype=np.uint8).reshape(-1, 32)
+        cur_class_id = np.ascontiguousarray(cur_class_id, dtype=np.int32).reshape(-1)
+        if len(cur_class_id) != len(cur_desc):
+            raise ValueError("one class_id per descriptor")
+        g = _GuidedCall(K4, T_cw, point_kf, point_cls, xyz, taken, len(feat_xy))
+        nz = lambda arr, t: ptr(arr, t) if arr.size else None   # an empty array has no address worth passing
+        self.ctx.check(self.ctx.lib.ssx_kfdb_project_match(self.handle, ptr(g.K4, dbl_p), ptr(g.T, dbl_p), int(rows), int(cols), len(feat_xy),
+                                                           nz(feat_xy, C.POINTER(C.c_float)), g.taken_p, len(cur_desc), nz(cur_desc, u8_p), nz(cur_class_id, i32_p),
+                                                           *g.tail(radius, max_distance, ratio_pct)))
+        return g.result()
+
+    def guided_search(self, image, features, prm, K4, T_cw, point_kf, point_cls, xyz, taken=None, radius=10.0, max_distance=50, ratio_pct=90,
+                      pyramid_levels=8):
+        """The guided search as the system runs it (ssx_kfdb_guided_search): the frame is described as relocalize_query describes it and
+        the search reads its descriptors on the device.  features [n] KP_DTYPE, taken [n]; the rest and the result as project_match."""
+        image = np.asarray(image)
+        if image.ndim != 2 or image.dtype != np.uint8 or image.strides[1] != 1:
+            image = np.ascontiguousarray(image, dtype=np.uint8)
+        features = np.ascontiguousarray(features, dtype=KP_DTYPE)
+        g = _GuidedCall(K4, T_cw, point_kf, point_cls, xyz, taken, len(features))
+        self.ctx.check(self.ctx.lib.ssx_kfdb_guided_search(self.handle, ptr(image, u8_p), image.strides[0], image.shape[0], image.shape[1], C.byref(prm),
+                                                           len(features), features.ctypes.data_as(C.c_void_p), int(pyramid_levels), g.taken_p,
+                                                           ptr(g.K4, dbl_p), ptr(g.T, dbl_p), *g.tail(radius, max_distance, ratio_pct)))
+        return g.result()
+
     def add_pending(self):
         """AddToKeyframeDatabase for the keyframe of the last process_keyframe, device to device"""
         self.ctx.check(self.ctx.lib.ssx_kfdb_add_pending(self.handle))
@@ -237,10 +277,40 @@ class KeyframeDatabase:
         return dict(kf_id=kf.value, keypoints=kps[:n.value], desc=desc[:n.value], class_id=cls[:n.value], bow=(ids[:nb.value], vals[:nb.value]))
 
     def debug_last_step(self):
-        """tests / tools hook -> dict(launches, syncs, bytes_up, bytes_down) of the last process_keyframe"""
+        """tests / tools hook -> dict(launches, syncs, bytes_up, bytes_down) of the last process_keyframe, relocalize_query or guided_search"""
         a, b, c, d = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
         self.ctx.check(self.ctx.lib.ssx_kfdb_debug_last_step(self.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(launches=a.value, syncs=b.value, bytes_up=c.value, bytes_down=d.value)
+
+
+class _GuidedCall:
+    """the arguments project_match and guided_search share, as contiguous arrays, and their output arrays"""
+
+    def __init__(self, K4, T_cw, point_kf, point_cls, xyz, taken, F):
+        self.K4 = np.ascontiguousarray(K4, dtype=np.float64).reshape(-1)
+        self.T = np.ascontiguousarray(T_cw, dtype=np.float64).reshape(-1)
+        self.kf = np.ascontiguousarray(point_kf, dtype=np.int64).reshape(-1)
+        self.cls = np.ascontiguousarray(point_cls, dtype=np.int32).reshape(-1)
+        self.xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        self.P = P = len(self.xyz)
+        if self.K4.size != 4 or self.T.size != 12 or len(self.kf) != P or len(self.cls) != P:
+            raise ValueError("K4 = (fx, fy, cx, cy), T_cw = 12 doubles [R|t], one keyframe and one class id per point")
+        self.taken = None if taken is None else np.ascontiguousarray(taken, dtype=np.uint8).reshape(-1)
+        if self.taken is not None and len(self.taken) != F:
+            raise ValueError("one taken flag per feature")
+        # (a non-null pointer for `taken set` even when there is no feature)
+        self.taken_p = None if self.taken is None else (ptr(self.taken, u8_p) if F else C.cast(C.create_string_buffer(1), u8_p))
+        self.feat, self.d1, self.d2, self.status = (np.zeros(max(P, 1), np.int32) for _ in range(4))
+        self.uv = np.zeros((max(P, 1), 2), np.float64)
+        self.n = C.c_int32()
+
+    def tail(self, radius, max_distance, ratio_pct):
+        return (self.P, ptr(self.kf, i64_p), ptr(self.cls, i32_p), ptr(self.xyz, dbl_p), float(radius), int(max_distance), int(ratio_pct),
+                ptr(self.feat, i32_p), ptr(self.d1, i32_p), ptr(self.d2, i32_p), ptr(self.status, i32_p), ptr(self.uv, dbl_p), C.byref(self.n))
+
+    def result(self):
+        P = self.P
+        return dict(feat=self.feat[:P], d1=self.d1[:P], d2=self.d2[:P], status=self.status[:P], uv=self.uv[:P], n_matched=self.n.value)
 
 
 def _step_dict(r, pairs, pairs_cap):
