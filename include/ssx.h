@@ -697,6 +697,30 @@ SSX_API ssx_status ssx_undistort_plan_add(ssx_undistort_plan* plan, const ssx_un
 SSX_API ssx_status ssx_undistort_plan_apply(ssx_undistort_plan* plan, int32_t n, const ssx_undistort_plan_job* jobs, int32_t images_on_device);
 SSX_API ssx_status ssx_undistort_plan_size(const ssx_undistort_plan* plan, int32_t* rows, int32_t* cols, int32_t* n_maps);
 SSX_API void ssx_undistort_plan_destroy(ssx_undistort_plan* plan);
+/* Raw stereo rigs: lens models and rectification.  The contract is tools/rectify_model.py.
+ * A lens is SSX_LENS_RADTAN -- coeffs = k1 k2 p1 p2 k3, the map of ssx_undistort, whose entry points are this case -- or SSX_LENS_KB4,
+ * Kannala-Brandt "equidistant" with coeffs = k1 k2 k3 k4 (coeffs[4] is ignored): theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8),
+ * theta = atan(r) by the contract's own atan_c in f64 operations (no library atan); a pixel whose ray has W <= 0 (behind the camera,
+ * or NaN) is 0.  `reserved` is 0.
+ * ssx_undistort_lens / ssx_undistort_plan_add_lens: ssx_undistort / ssx_undistort_plan_add with a lens model per job / per map --
+ * their refusals, limits, images_on_device rules and counters; jobs of mixed models are ONE launch.  In addition a model that is
+ * neither of the two is SSX_ERR_INVALID_ARG before anything is touched.  Two parameter sets are one map when their bytes are equal;
+ * a RADTAN set finds the map its ssx_undistort_params form was added as, and the other way round.
+ * ssx_stereo_rectify: host arithmetic (+ - * / sqrt only, no ctx, no device), rectify() of the contract bit for bit.  rig: the two
+ * cameras (left, right; iR ignored), X_right = R X_left + t (R row-major), and f, cx, cy of the common camera (0: the mean of the
+ * four focal lengths / of the two principal points).  out: the rectifying rotations, newK = (f, f, cx, cy), the baseline, and the two
+ * cameras with iR filled in, ready for the two calls above; the rectified right camera sits at (-baseline, 0, 0).
+ * SSX_ERR_INVALID_ARG, the reason in why (nullable, why_cap bytes, always terminated), out untouched: a null rig or out, an unknown
+ * model, a non-finite input, a zero baseline, max|R R^T - I| > 1e-6, a right camera that is not to the right (vertical and reversed
+ * rigs), optical axes along the baseline. */
+enum { SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1 };
+typedef struct { int32_t model, reserved; double K[4]; double coeffs[5]; double iR[9]; } ssx_lens_params;
+typedef struct { const uint8_t* src; int32_t src_stride; uint8_t* dst; int32_t dst_stride; ssx_lens_params prm; } ssx_lens_job;
+SSX_API ssx_status ssx_undistort_lens(ssx_ctx* ctx, int32_t n, const ssx_lens_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device);
+SSX_API ssx_status ssx_undistort_plan_add_lens(ssx_undistort_plan* plan, const ssx_lens_params* prm, int32_t* map_index);
+typedef struct { ssx_lens_params cam[2]; double R[9], t[3]; double f, cx, cy; } ssx_stereo_raw_rig;
+typedef struct { double R_l[9], R_r[9], newK[4], baseline; ssx_lens_params cam[2]; } ssx_stereo_rectified;
+SSX_API ssx_status ssx_stereo_rectify(const ssx_stereo_raw_rig* rig, ssx_stereo_rectified* out, char* why, int32_t why_cap);
 /* ------------------------------------------------------------------------------------------------
  * N3: pose-graph optimisation.
  * Replaces the optimisation of LoopClosing::PoseGraphOptimization

@@ -251,10 +251,29 @@ class Camera {
     left.ctx_.check(ssx_undistort(left.ctx_.get(), 2, jobs, rows, cols, imagesOnDevice ? 1 : 0));
   }
 
+  // The raw pair of an unrectified rig warped into its common rectified camera (no counterpart in the reference): lenses[0], lenses[1]
+  // are StereoRectify(rig).cam -- either lens model each, the rectifying rotation in iR -- and the two images are one call.
+  static void RectifyPair(Context& ctx, const ssx_lens_params lenses[2], const uint8_t* srcLeft, int srcLeftStep, uint8_t* dstLeft, int dstLeftStep,
+                          const uint8_t* srcRight, int srcRightStep, uint8_t* dstRight, int dstRightStep, int rows, int cols, bool imagesOnDevice = false)
+  {
+    const ssx_lens_job jobs[2] = {{srcLeft, srcLeftStep, dstLeft, dstLeftStep, lenses[0]}, {srcRight, srcRightStep, dstRight, dstRightStep, lenses[1]}};
+    ctx.check(ssx_undistort_lens(ctx.get(), 2, jobs, rows, cols, imagesOnDevice ? 1 : 0));
+  }
+
  private:
   Context& ctx_;
   ssx_undistort_params prm_{};
 };
+
+// ssx_stereo_rectify: the common rectified camera of a raw rig (host arithmetic, no Context); throws std::invalid_argument with the
+// reason for a rig that cannot be rectified
+inline ssx_stereo_rectified StereoRectify(const ssx_stereo_raw_rig& rig)
+{
+  ssx_stereo_rectified out{};
+  char why[160];
+  if (ssx_stereo_rectify(&rig, &out, why, (int32_t)sizeof why) != SSX_OK) throw std::invalid_argument(std::string("ssx::StereoRectify: ") + why);
+  return out;
+}
 
 // Many streams' frames in one call (ssx_undistort_plan_*): the plan keeps one stored map per camera it was shown (Add: equal parameter
 // bytes -> the index they have) for ONE image size, and Apply undistorts n images, each naming its map, in one launch -- the bytes
@@ -273,6 +292,12 @@ class UndistortPlan {
     return m;
   }
   int Add(const Camera& camera) { return Add(camera.params()); }
+  int AddLens(const ssx_lens_params& lens)              // a lens of either model, e.g. StereoRectify(rig).cam[side]
+  {
+    int32_t m = -1;
+    ctx_.check(ssx_undistort_plan_add_lens(plan_, &lens, &m));
+    return m;
+  }
   void Apply(const std::vector<ssx_undistort_plan_job>& jobs, bool imagesOnDevice = false)
   {
     ctx_.check(ssx_undistort_plan_apply(plan_, (int32_t)jobs.size(), jobs.data(), imagesOnDevice ? 1 : 0));

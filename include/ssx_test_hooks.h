@@ -244,6 +244,9 @@ SSX_API ssx_status ssx_undistort_plan_debug_last_call(const ssx_undistort_plan* 
 /* the stored map `map_index` as tools/undistort_model.py's pack_map returns it: out = three planes of rows x cols u16 (xs, ys, ab),
  * each contiguous */
 SSX_API ssx_status ssx_undistort_plan_debug_map(ssx_undistort_plan* plan, int32_t map_index, uint16_t* out);
+/* the device's atan_c and sqrt of the KB4 lens (csrc/undistort.hip: ud_atan) over n host doubles (0 .. 2^24), so that their bits are
+ * compared with tools/rectify_model.py's directly; either output may be NULL */
+SSX_API ssx_status ssx_lens_debug_atan(ssx_ctx* ctx, int32_t n, const double* r, double* atan_out, double* sqrt_out);
 
 #ifdef __cplusplus
 }

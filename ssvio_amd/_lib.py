@@ -212,6 +212,28 @@ class UndistortPlanJob(C.Structure):
 
 SSX_UNDISTORT_MAX_JOBS = 1024
 SSX_UNDISTORT_PLAN_MAX_MAPS = 64
+SSX_LENS_RADTAN, SSX_LENS_KB4 = 0, 1
+
+
+class LensParams(C.Structure):
+    """ssx_lens_params: model = SSX_LENS_*, K = (fx, fy, cx, cy), coeffs = (k1, k2, p1, p2, k3) for RADTAN and (k1, k2, k3, k4, -) for KB4,
+    iR = inverse of newK * R, row-major"""
+    _fields_ = [("model", C.c_int32), ("reserved", C.c_int32), ("K", C.c_double * 4), ("coeffs", C.c_double * 5), ("iR", C.c_double * 9)]
+
+
+class LensJob(C.Structure):
+    """ssx_lens_job"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int32), ("dst", C.c_void_p), ("dst_stride", C.c_int32), ("prm", LensParams)]
+
+
+class StereoRawRig(C.Structure):
+    """ssx_stereo_raw_rig: X_right = R X_left + t; f, cx, cy of the common camera, 0 = the default"""
+    _fields_ = [("cam", LensParams * 2), ("R", C.c_double * 9), ("t", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class StereoRectified(C.Structure):
+    """ssx_stereo_rectified"""
+    _fields_ = [("R_l", C.c_double * 9), ("R_r", C.c_double * 9), ("newK", C.c_double * 4), ("baseline", C.c_double), ("cam", LensParams * 2)]
 
 
 class KernelTime(C.Structure):

@@ -26,8 +26,14 @@
 //                the results come down in one copy, one synchronisation.  images_on_device: only the job table goes up, the kernel reads
 //                and writes the images where they lie (device or pinned memory), nothing comes down.
 //
+// Lens models (contract tools/rectify_model.py): every job and every stored map names its lens, SSX_LENS_RADTAN -- the map
+// above, and what ssx_undistort / ssx_undistort_plan_add pass -- or SSX_LENS_KB4 (Kannala-Brandt, its atan the contract's own f64
+// operations: ud_atan).  The model is wave-uniform, so jobs of mixed models stay one launch.  ssx_stereo_rectify, the common rectified
+// camera of a raw rig, is host arithmetic in this file because of the next sentence.
+//
 // This file is compiled with -ffp-contract=off: every f64 operation rounds on its own, as the model's does
-// (tests/test_undistort_gpu.py: the output is the model's bytes).
+// (tests/test_undistort_gpu.py, tests/test_rectify_gpu.py: the output is the model's bytes; tests/test_rectify_abi.py: ssx_stereo_rectify's
+// are the model's bits).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -47,7 +53,8 @@ struct UdJob {
   const uint8_t* src;
   uint8_t* dst;
   int64_t src_stride, dst_stride;
-  double K[4], dist[5], iR[9];
+  int32_t model, reserved;                  // SSX_LENS_*: one lens a job, so the choice is wave-uniform too
+  double K[4], coeffs[5], iR[9];
 };
 
 // q(t) of the model: 0 for NaN, else round to nearest (ties to even) clamped to [-2^31, 2^31 - 1]
@@ -67,11 +74,43 @@ __device__ __forceinline__ uint32_t ud_tap(const uint8_t* __restrict__ src, int6
   return src[(int64_t)Y * stride + (int64_t)X];
 }
 
+// atan_c of tools/rectify_model.py for r >= 0, in its operations and its order: the reduction at 7/16, 11/16, 19/16, 39/16 with the
+// high / low constants, the 11-term odd polynomial in its two Horner halves.  The four reductions are selects of one quotient's
+// operands, not branches: a wavefront's pixels lie on both sides of a breakpoint, and the one division rounds as the model's does
+// because its operands are the model's.  No library atan.
+__device__ __forceinline__ double ud_atan(double r)
+{
+  const bool c0 = r < 0.4375, c1 = r < 0.6875, c2 = r < 1.1875, c3 = r < 2.4375;
+  const double n1 = 2.0 * r - 1.0, d1 = 2.0 + r;
+  const double n2 = r - 1.0, d2 = r + 1.0;
+  const double n3 = r - 1.5, d3 = 1.0 + 1.5 * r;
+  const double num = c1 ? n1 : c2 ? n2 : c3 ? n3 : -1.0;
+  const double den = c1 ? d1 : c2 ? d2 : c3 ? d3 : r;
+  const double quo = num / den;
+  const double t = c0 ? r : quo;
+  const double hi = c1 ? 4.63647609000806093515e-01 : c2 ? 7.85398163397448278999e-01 : c3 ? 9.82793723247329054082e-01 : 1.57079632679489655800e+00;
+  const double lo = c1 ? 2.26987774529616870924e-17 : c2 ? 3.06161699786838301793e-17 : c3 ? 1.39033110312309984516e-17 : 6.12323399573676603587e-17;
+  const double z = t * t;
+  const double w = z * z;
+  const double s1 = z * (3.33333333333329318027e-01 + w * (1.42857142725034663711e-01 + w * (9.09088713343650656196e-02 + w * (6.66107313738753120669e-02 +
+                         w * (4.97687799461593236017e-02 + w * 1.62858201153657823623e-02)))));
+  const double s2 = w * (-1.99999999998764832476e-01 + w * (-1.11111104054623557880e-01 + w * (-7.69187620504482999495e-02 + w * (-5.83357013379057348645e-02 +
+                         w * -3.65315727442169155270e-02))));
+  const double p = t * (s1 + s2);
+  const double small = t - p;
+  const double big = hi - ((p - lo) - t);
+  double out = c0 ? small : big;
+  if (r >= 73786976294838206464.0) out = 1.57079632679489655800e+00;   // 2^66
+  if (r != r) out = r;
+  return out;
+}
+
 // The map of the model up to its quantisation: the source position (iu, iv) of destination pixel (row i, column j) in 1/32 pixel, f64,
-// one operation per statement in the model's order.  k_undistort and k_undistort_map both call it: the inline map and the stored one
-// cannot drift.
-__device__ __forceinline__ void ud_map(const double* __restrict__ K, const double* __restrict__ dist, const double* __restrict__ iR, int32_t i, int32_t j,
-                                       int32_t* iu_out, int32_t* iv_out)
+// one operation per statement in the model's order (tools/undistort_model.py for SSX_LENS_RADTAN, tools/rectify_model.py's lens_map for
+// SSX_LENS_KB4).  `model` is wave-uniform -- a job's, or a launch's -- so the choice is a scalar branch and neither lens runs the
+// other's chain.  k_undistort and k_undistort_map both call it: the inline map and the stored one cannot drift.
+__device__ __forceinline__ void ud_map(int32_t model, const double* __restrict__ K, const double* __restrict__ dist, const double* __restrict__ iR, int32_t i,
+                                       int32_t j, int32_t* iu_out, int32_t* iv_out)
 {
   const double dj = (double)j, di = (double)i;
   const double X = (dj * iR[0] + di * iR[1]) + iR[2];
@@ -80,6 +119,27 @@ __device__ __forceinline__ void ud_map(const double* __restrict__ K, const doubl
   const double w = 1.0 / W;
   const double x = X * w;
   const double y = Y * w;
+  if (model == SSX_LENS_KB4) {
+    const double xx = x * x;
+    const double yy = y * y;
+    const double r2 = xx + yy;
+    const double r = sqrt(r2);                                   // (f64 sqrt: correctly rounded)
+    const double th = ud_atan(r);
+    const double t2 = th * th;
+    const double k1 = dist[0], k2 = dist[1], k3 = dist[2], k4 = dist[3];
+    const double poly = 1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4)));
+    const double thd = th * poly;
+    const double quo = thd / r;
+    const double s = r == 0.0 ? 1.0 : quo;
+    const double xs = x * s;
+    const double ys = y * s;
+    double u = K[0] * xs + K[2];
+    double v = K[1] * ys + K[3];
+    if (!(W > 0.0)) { u = -HUGE_VAL; v = -HUGE_VAL; }            // behind the camera, or NaN: every tap is outside
+    *iu_out = ud_q(u * 32.0);
+    *iv_out = ud_q(v * 32.0);
+    return;
+  }
   const double x2 = x * x;
   const double y2 = y * y;
   const double r2 = x2 + y2;
@@ -140,7 +200,7 @@ __device__ __forceinline__ uint32_t ud_sample_stored(UdGlobalBytes src, int64_t 
 __device__ __forceinline__ uint32_t ud_pixel(const UdJob& jb, int32_t rows, int32_t cols, int32_t i, int32_t j)
 {
   int32_t iu, iv;
-  ud_map(jb.K, jb.dist, jb.iR, i, j, &iu, &iv);
+  ud_map(jb.model, jb.K, jb.coeffs, jb.iR, i, j, &iu, &iv);
   const int32_t X0 = iu >> 5, Y0 = iv >> 5;                       // arithmetic shifts: |X0|, |Y0| <= 2^26, so X0 + 1 cannot overflow
   return ud_sample(jb.src, jb.src_stride, rows, cols, Y0, X0, (uint32_t)(iu & 31), (uint32_t)(iv & 31));
 }
@@ -166,8 +226,8 @@ __global__ void __launch_bounds__(UD_BX * UD_BY) k_undistort(const UdJob* __rest
 // Three u16 planes (xs, ys, ab of tools/undistort_model.py's pack_map) of `rows` rows at a pitch of cols rounded up to UD_PX, one
 // behind the other: a thread's four pixels are 8 aligned bytes of each plane, and a wavefront's loads are 512 consecutive bytes.
 constexpr int UD_MAP_MAX_SIDE = 65533;      // position + 2 is a u16
-struct UdPrm { double K[4], dist[5], iR[9]; };
-static_assert(sizeof(UdPrm) == sizeof(ssx_undistort_params), "the kernel's parameter block is the ABI's");
+struct UdPrm { int32_t model, reserved; double K[4], coeffs[5], iR[9]; };
+static_assert(sizeof(UdPrm) == sizeof(ssx_lens_params), "the kernel's parameter block is the ABI's");
 
 // grid (ceil(cols / 64), ceil(rows / 4)), block 64 x 4: one pixel a thread.  ud_map, then the packing of the model's pack_map.
 __global__ void __launch_bounds__(UD_BX * UD_BY) k_undistort_map(UdPrm prm, int32_t rows, int32_t cols, int64_t pitch, uint16_t* __restrict__ map)
@@ -176,7 +236,7 @@ __global__ void __launch_bounds__(UD_BX * UD_BY) k_undistort_map(UdPrm prm, int3
   const int32_t j = (int32_t)(blockIdx.x * UD_BX + threadIdx.x);
   if (i >= rows || j >= cols) return;
   int32_t iu, iv;
-  ud_map(prm.K, prm.dist, prm.iR, i, j, &iu, &iv);
+  ud_map(prm.model, prm.K, prm.coeffs, prm.iR, i, j, &iu, &iv);
   int32_t X0 = iu >> 5, Y0 = iv >> 5;
   X0 = X0 < -2 ? -2 : X0 > cols ? cols : X0;
   Y0 = Y0 < -2 ? -2 : Y0 > rows ? rows : Y0;
@@ -185,6 +245,17 @@ __global__ void __launch_bounds__(UD_BX * UD_BY) k_undistort_map(UdPrm prm, int3
   map[plane + at] = (uint16_t)(Y0 + 2);
   map[2 * plane + at] = (uint16_t)((iu & 31) | ((iv & 31) << 5));
 }
+
+#ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h: ssx_lens_debug_atan
+__global__ void __launch_bounds__(256) k_lens_debug_atan(const double* __restrict__ r, int32_t n, double* __restrict__ atan_out, double* __restrict__ sqrt_out)
+{
+  const int32_t k = (int32_t)(blockIdx.x * 256u + threadIdx.x);
+  if (k >= n) return;
+  const double v = r[k];
+  atan_out[k] = ud_atan(v);
+  sqrt_out[k] = sqrt(v);
+}
+#endif
 
 // one job of k_undistort_remap (wave-uniform: scalar loads)
 struct UdRemapJob {
@@ -343,7 +414,7 @@ struct ssx_undistort_plan {
   int32_t rows = 0, cols = 0;
   int64_t pitch = 0;                          // entries of a map row: cols rounded up to UD_PX
   size_t map_bytes = 0;                       // three planes
-  std::vector<ssx_undistort_params> prm;      // prm[m]: the parameter bytes of maps[m]
+  std::vector<ssx_lens_params> prm;           // prm[m]: the parameter bytes of maps[m] (a set of ssx_undistort_plan_add: as its RADTAN lens)
   std::vector<uint16_t*> maps;
   DevBuf arena;
   HostBuf stage;
@@ -362,18 +433,40 @@ void ssx_undistort_default(const double K4[4], const double dist5[5], ssx_undist
   std::memcpy(out->iR, iR, sizeof(out->iR));
 }
 
-ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
+}  // extern "C"
+
+namespace {
+
+inline bool ud_known_model(int32_t model) { return model == SSX_LENS_RADTAN || model == SSX_LENS_KB4; }
+
+// the RADTAN lens that a parameter set of ssx_undistort is: the same bytes whichever entry point it came through
+inline ssx_lens_params ud_as_lens(const ssx_undistort_params& p)
 {
-  if (!ctx) return SSX_ERR_INVALID_ARG;
+  ssx_lens_params l;
+  std::memset(&l, 0, sizeof l);
+  l.model = SSX_LENS_RADTAN;
+  std::memcpy(l.K, p.K, sizeof l.K);
+  std::memcpy(l.coeffs, p.dist, sizeof l.coeffs);
+  std::memcpy(l.iR, p.iR, sizeof l.iR);
+  return l;
+}
+
+// ssx_undistort_lens, and ssx_undistort as its RADTAN case; `who` names the entry point in the messages
+ssx_status ud_run(ssx_ctx* ctx, const char* who, int32_t n, const ssx_lens_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
+{
   ctx->undistort = KfChainStats{};
   // every refusal comes before anything is touched
-  if (n < 0 || n > SSX_UNDISTORT_MAX_JOBS) { ctx->set_error("ssx_undistort: n = %d outside [0, %d]", n, SSX_UNDISTORT_MAX_JOBS); return SSX_ERR_INVALID_ARG; }
-  if (rows < 1 || cols < 1) { ctx->set_error("ssx_undistort: rows = %d, cols = %d (both must be >= 1)", rows, cols); return SSX_ERR_INVALID_ARG; }
-  if (n > 0 && !jobs) { ctx->set_error("ssx_undistort: jobs is null"); return SSX_ERR_INVALID_ARG; }
+  if (n < 0 || n > SSX_UNDISTORT_MAX_JOBS) { ctx->set_error("%s: n = %d outside [0, %d]", who, n, SSX_UNDISTORT_MAX_JOBS); return SSX_ERR_INVALID_ARG; }
+  if (rows < 1 || cols < 1) { ctx->set_error("%s: rows = %d, cols = %d (both must be >= 1)", who, rows, cols); return SSX_ERR_INVALID_ARG; }
+  if (n > 0 && !jobs) { ctx->set_error("%s: jobs is null", who); return SSX_ERR_INVALID_ARG; }
   for (int32_t k = 0; k < n; ++k) {
-    if (!jobs[k].src || !jobs[k].dst) { ctx->set_error("ssx_undistort: job %d has a null %s", k, jobs[k].src ? "dst" : "src"); return SSX_ERR_INVALID_ARG; }
+    if (!jobs[k].src || !jobs[k].dst) { ctx->set_error("%s: job %d has a null %s", who, k, jobs[k].src ? "dst" : "src"); return SSX_ERR_INVALID_ARG; }
     if (jobs[k].src_stride < cols || jobs[k].dst_stride < cols) {
-      ctx->set_error("ssx_undistort: job %d has a stride (src %d, dst %d) smaller than cols = %d", k, jobs[k].src_stride, jobs[k].dst_stride, cols);
+      ctx->set_error("%s: job %d has a stride (src %d, dst %d) smaller than cols = %d", who, k, jobs[k].src_stride, jobs[k].dst_stride, cols);
+      return SSX_ERR_INVALID_ARG;
+    }
+    if (!ud_known_model(jobs[k].prm.model)) {
+      ctx->set_error("%s: job %d names lens model %d (SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1)", who, k, jobs[k].prm.model);
       return SSX_ERR_INVALID_ARG;
     }
   }
@@ -384,12 +477,12 @@ ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs,
       uintptr_t s0, s1;
       ud_span(jobs[s].src, jobs[s].src_stride, rows, cols, &s0, &s1);
       if (d0 < s1 && s0 < d1) {
-        ctx->set_error("ssx_undistort: the dst of job %d overlaps the src of job %d (there is no in-place form)", d, s);
+        ctx->set_error("%s: the dst of job %d overlaps the src of job %d (there is no in-place form)", who, d, s);
         return SSX_ERR_INVALID_ARG;
       }
     }
   }
-  if (rows > UD_MAX_SIDE || cols > UD_MAX_SIDE) { ctx->set_error("ssx_undistort: %d x %d is above %d a side", rows, cols, UD_MAX_SIDE); return SSX_ERR_UNSUPPORTED; }
+  if (rows > UD_MAX_SIDE || cols > UD_MAX_SIDE) { ctx->set_error("%s: %d x %d is above %d a side", who, rows, cols, UD_MAX_SIDE); return SSX_ERR_UNSUPPORTED; }
   if (n == 0) return SSX_OK;
 
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -420,8 +513,9 @@ ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs,
       t.src = jobs[k].src; t.dst = jobs[k].dst;
       t.src_stride = jobs[k].src_stride; t.dst_stride = jobs[k].dst_stride;
     }
+    t.model = jobs[k].prm.model; t.reserved = 0;
     std::memcpy(t.K, jobs[k].prm.K, sizeof(t.K));
-    std::memcpy(t.dist, jobs[k].prm.dist, sizeof(t.dist));
+    std::memcpy(t.coeffs, jobs[k].prm.coeffs, sizeof(t.coeffs));
     std::memcpy(t.iR, jobs[k].prm.iR, sizeof(t.iR));
   }
   SSX_HIP_TRY(ctx, hipMemcpyAsync(dev, stage, up_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -443,6 +537,158 @@ ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs,
     }
   ctx->undistort = st;
   return SSX_OK;
+}
+
+// ssx_undistort_plan_add_lens, and ssx_undistort_plan_add as its RADTAN case (definition below the plan's entry points)
+ssx_status ud_plan_add(ssx_undistort_plan* plan, const char* who, const ssx_lens_params* prm, int32_t* map_index);
+
+// ---- ssx_stereo_rectify: rectify() of tools/rectify_model.py, statement for statement (host f64, this file has no contraction) ----
+const char* const UD_WHY_MODEL = "unknown lens model";
+const char* const UD_WHY_FINITE = "a non-finite input";
+const char* const UD_WHY_BASELINE = "the baseline is zero";
+const char* const UD_WHY_ROTATION = "R is not a rotation: max|R R^T - I| > 1e-6";
+const char* const UD_WHY_SIDE = "the right camera is not to the right of the left one (e1[0] <= 0)";
+const char* const UD_WHY_AXES = "the optical axes lie along the baseline (|e3'|^2 < 1e-12)";
+
+inline bool ud_all_finite(const double* v, int n)
+{
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(v[k])) return false;
+  return true;
+}
+
+// iR = S^T newK^-1 in closed form; in the third column the left-most product is taken first
+inline void ud_rect_iR(const double S[9], double f, double cx, double cy, double iR[9])
+{
+  const double g = 1.0 / f;
+  const double mx = -cx / f;
+  const double my = -cy / f;
+  for (int i = 0; i < 3; ++i) {
+    iR[3 * i + 0] = S[0 + i] * g;
+    iR[3 * i + 1] = S[3 + i] * g;
+    const double a = S[0 + i] * mx;
+    const double b = S[3 + i] * my;
+    const double ab = a + b;
+    iR[3 * i + 2] = ab + S[6 + i];
+  }
+}
+
+// -> nullptr and *o filled, or the model's reason and *o untouched
+const char* ud_rectify(const ssx_stereo_raw_rig& rig, ssx_stereo_rectified* o)
+{
+  for (int s = 0; s < 2; ++s)
+    if (!ud_known_model(rig.cam[s].model)) return UD_WHY_MODEL;
+  const double over[3] = {rig.f, rig.cx, rig.cy};
+  bool fin = ud_all_finite(rig.R, 9) && ud_all_finite(rig.t, 3) && ud_all_finite(over, 3);
+  for (int s = 0; s < 2; ++s) fin = fin && ud_all_finite(rig.cam[s].K, 4) && ud_all_finite(rig.cam[s].coeffs, 5);
+  if (!fin) return UD_WHY_FINITE;
+  const double* R = rig.R;
+  const double* t = rig.t;
+  double c[3];
+  for (int i = 0; i < 3; ++i) {
+    const double a0 = (-R[0 + i]) * t[0];
+    const double a1 = (-R[3 + i]) * t[1];
+    const double a2 = (-R[6 + i]) * t[2];
+    const double a01 = a0 + a1;
+    c[i] = a01 + a2;
+  }
+  const double c00 = c[0] * c[0], c11 = c[1] * c[1], c22 = c[2] * c[2];
+  const double cc = c00 + c11;
+  const double b = std::sqrt(cc + c22);
+  if (b == 0.0) return UD_WHY_BASELINE;
+  double worst = 0.0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double p0 = R[3 * i + 0] * R[3 * j + 0], p1 = R[3 * i + 1] * R[3 * j + 1], p2 = R[3 * i + 2] * R[3 * j + 2];
+      const double p01 = p0 + p1;
+      const double dot = p01 + p2;
+      const double dev = std::fabs(dot - (i == j ? 1.0 : 0.0));
+      if (dev > worst) worst = dev;
+    }
+  if (worst > 1e-6) return UD_WHY_ROTATION;
+  double e1[3], e2[3], e3[3], e3p[3];
+  for (int i = 0; i < 3; ++i) e1[i] = c[i] / b;
+  if (e1[0] <= 0.0) return UD_WHY_SIDE;
+  const double zm[3] = {0.0 + R[6], 0.0 + R[7], 1.0 + R[8]};
+  const double d0 = zm[0] * e1[0], d1 = zm[1] * e1[1], d2 = zm[2] * e1[2];
+  const double d01 = d0 + d1;
+  const double d = d01 + d2;
+  for (int i = 0; i < 3; ++i) {
+    const double de = d * e1[i];
+    e3p[i] = zm[i] - de;
+  }
+  const double q0 = e3p[0] * e3p[0], q1 = e3p[1] * e3p[1], q2 = e3p[2] * e3p[2];
+  const double q01 = q0 + q1;
+  const double n2 = q01 + q2;
+  if (n2 < 1e-12) return UD_WHY_AXES;
+  const double nn = std::sqrt(n2);
+  for (int i = 0; i < 3; ++i) e3[i] = e3p[i] / nn;
+  {
+    const double a0 = e3[1] * e1[2], b0 = e3[2] * e1[1];
+    const double a1 = e3[2] * e1[0], b1 = e3[0] * e1[2];
+    const double a2 = e3[0] * e1[1], b2 = e3[1] * e1[0];
+    e2[0] = a0 - b0; e2[1] = a1 - b1; e2[2] = a2 - b2;
+  }
+  ssx_stereo_rectified r;
+  std::memset(&r, 0, sizeof r);
+  for (int i = 0; i < 3; ++i) { r.R_l[i] = e1[i]; r.R_l[3 + i] = e2[i]; r.R_l[6 + i] = e3[i]; }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double p0 = r.R_l[3 * i + 0] * R[3 * j + 0], p1 = r.R_l[3 * i + 1] * R[3 * j + 1], p2 = r.R_l[3 * i + 2] * R[3 * j + 2];
+      const double p01 = p0 + p1;
+      r.R_r[3 * i + j] = p01 + p2;
+    }
+  const double* Kl = rig.cam[0].K;
+  const double* Kr = rig.cam[1].K;
+  double f = rig.f, cx = rig.cx, cy = rig.cy;
+  if (f == 0.0) {
+    const double sl = Kl[0] + Kl[1], sr = Kr[0] + Kr[1];
+    const double s4 = sl + sr;
+    f = s4 / 4.0;
+  }
+  if (cx == 0.0) { const double s2 = Kl[2] + Kr[2]; cx = s2 / 2.0; }
+  if (cy == 0.0) { const double s2 = Kl[3] + Kr[3]; cy = s2 / 2.0; }
+  r.newK[0] = f; r.newK[1] = f; r.newK[2] = cx; r.newK[3] = cy;
+  r.baseline = b;
+  for (int s = 0; s < 2; ++s) {
+    r.cam[s].model = rig.cam[s].model;                               // (reserved stays 0: equal lenses are equal bytes)
+    std::memcpy(r.cam[s].K, rig.cam[s].K, sizeof r.cam[s].K);
+    std::memcpy(r.cam[s].coeffs, rig.cam[s].coeffs, sizeof r.cam[s].coeffs);
+    ud_rect_iR(s == 0 ? r.R_l : r.R_r, f, cx, cy, r.cam[s].iR);
+  }
+  *o = r;
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+ssx_status ssx_undistort_lens(ssx_ctx* ctx, int32_t n, const ssx_lens_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
+{
+  if (!ctx) return SSX_ERR_INVALID_ARG;
+  return ud_run(ctx, "ssx_undistort_lens", n, jobs, rows, cols, images_on_device);
+}
+
+ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
+{
+  if (!ctx) return SSX_ERR_INVALID_ARG;
+  std::vector<ssx_lens_job> lens;                                    // (a count or a table that will be refused goes through as it is)
+  if (jobs && n > 0 && n <= SSX_UNDISTORT_MAX_JOBS) {
+    lens.resize((size_t)n);
+    for (int32_t k = 0; k < n; ++k) lens[k] = ssx_lens_job{jobs[k].src, jobs[k].src_stride, jobs[k].dst, jobs[k].dst_stride, ud_as_lens(jobs[k].prm)};
+  }
+  return ud_run(ctx, "ssx_undistort", n, lens.empty() ? nullptr : lens.data(), rows, cols, images_on_device);
+}
+
+ssx_status ssx_stereo_rectify(const ssx_stereo_raw_rig* rig, ssx_stereo_rectified* out, char* why, int32_t why_cap)
+{
+  const char* reason = !rig ? "rig is null" : !out ? "out is null" : ud_rectify(*rig, out);
+  if (why && why_cap > 0) {
+    std::strncpy(why, reason ? reason : "", (size_t)why_cap);
+    why[why_cap - 1] = '\0';
+  }
+  return reason ? SSX_ERR_INVALID_ARG : SSX_OK;
 }
 
 // ---- the plan: stored maps of one image size, applied to n images in one launch ----
@@ -487,15 +733,36 @@ ssx_status ssx_undistort_plan_size(const ssx_undistort_plan* plan, int32_t* rows
 ssx_status ssx_undistort_plan_add(ssx_undistort_plan* plan, const ssx_undistort_params* prm, int32_t* map_index)
 {
   if (!plan) return SSX_ERR_INVALID_ARG;
+  ssx_lens_params lens;
+  if (prm) lens = ud_as_lens(*prm);
+  return ud_plan_add(plan, "ssx_undistort_plan_add", prm ? &lens : nullptr, map_index);
+}
+
+ssx_status ssx_undistort_plan_add_lens(ssx_undistort_plan* plan, const ssx_lens_params* prm, int32_t* map_index)
+{
+  if (!plan) return SSX_ERR_INVALID_ARG;
+  return ud_plan_add(plan, "ssx_undistort_plan_add_lens", prm, map_index);
+}
+
+}  // extern "C"
+
+namespace {
+
+ssx_status ud_plan_add(ssx_undistort_plan* plan, const char* who, const ssx_lens_params* prm, int32_t* map_index)
+{
   ssx_ctx* ctx = plan->ctx;
   plan->last = UdPlanStats{};
-  if (!prm || !map_index) { ctx->set_error("ssx_undistort_plan_add: %s is null", prm ? "map_index" : "prm"); return SSX_ERR_INVALID_ARG; }
+  if (!prm || !map_index) { ctx->set_error("%s: %s is null", who, prm ? "map_index" : "prm"); return SSX_ERR_INVALID_ARG; }
+  if (!ud_known_model(prm->model)) {
+    ctx->set_error("%s: lens model %d (SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1)", who, prm->model);
+    return SSX_ERR_INVALID_ARG;
+  }
   // (parameter sets are equal when their bytes are: -0.0 and 0.0, or two NaNs, are different sets with equal maps, which costs a map and
   // no more)
   for (size_t m = 0; m < plan->prm.size(); ++m)
     if (std::memcmp(&plan->prm[m], prm, sizeof *prm) == 0) { *map_index = (int32_t)m; return SSX_OK; }
   if (plan->maps.size() >= SSX_UNDISTORT_PLAN_MAX_MAPS) {
-    ctx->set_error("ssx_undistort_plan_add: the plan holds SSX_UNDISTORT_PLAN_MAX_MAPS = %d maps already", SSX_UNDISTORT_PLAN_MAX_MAPS);
+    ctx->set_error("%s: the plan holds SSX_UNDISTORT_PLAN_MAX_MAPS = %d maps already", who, SSX_UNDISTORT_PLAN_MAX_MAPS);
     return SSX_ERR_CAPACITY;
   }
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -512,7 +779,7 @@ ssx_status ssx_undistort_plan_add(ssx_undistort_plan* plan, const ssx_undistort_
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
     (void)hipFree(map);
-    ctx->set_error("ssx_undistort_plan_add: %s", hipGetErrorString(e));
+    ctx->set_error("%s: %s", who, hipGetErrorString(e));
     return SSX_ERR_HIP;
   }
   plan->last.launches = 1; plan->last.syncs = 1;
@@ -521,6 +788,10 @@ ssx_status ssx_undistort_plan_add(ssx_undistort_plan* plan, const ssx_undistort_
   *map_index = (int32_t)plan->maps.size() - 1;
   return SSX_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 ssx_status ssx_undistort_plan_apply(ssx_undistort_plan* plan, int32_t n, const ssx_undistort_plan_job* jobs, int32_t images_on_device)
 {
@@ -694,6 +965,24 @@ ssx_status ssx_undistort_plan_debug_map(ssx_undistort_plan* plan, int32_t map_in
   // the three planes one behind the other are 3 * rows rows of `pitch` entries: the copy drops the pitch columns
   SSX_HIP_TRY(ctx, hipMemcpy2D(out, (size_t)plan->cols * sizeof(uint16_t), plan->maps[(size_t)map_index], (size_t)plan->pitch * sizeof(uint16_t),
                                (size_t)plan->cols * sizeof(uint16_t), (size_t)3 * (size_t)plan->rows, hipMemcpyDeviceToHost));
+  return SSX_OK;
+}
+
+ssx_status ssx_lens_debug_atan(ssx_ctx* ctx, int32_t n, const double* r, double* atan_out, double* sqrt_out)
+{
+  if (!ctx) return SSX_ERR_INVALID_ARG;
+  if (n < 0 || n > (1 << 24) || (n > 0 && !r)) { ctx->set_error("ssx_lens_debug_atan: n = %d outside [0, 2^24], or r is null", n); return SSX_ERR_INVALID_ARG; }
+  if (n == 0) return SSX_OK;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(double) * (size_t)n;
+  SSX_HIP_TRY(ctx, ctx->ud_arena.reserve(3 * bytes));
+  double* dev = ctx->ud_arena.as<double>();
+  SSX_HIP_TRY(ctx, hipMemcpyAsync(dev, r, bytes, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(k_lens_debug_atan, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dev, n, dev + n, dev + 2 * (size_t)n);
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  if (atan_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(atan_out, dev + n, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (sqrt_out) SSX_HIP_TRY(ctx, hipMemcpyAsync(sqrt_out, dev + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return SSX_OK;
 }
 

@@ -124,6 +124,15 @@ class Compute {
     (void)left; (void)right; (void)prm; (void)left_out; (void)right_out;
     throw std::logic_error("Compute::UndistortPair: this implementation cannot undistort images (Camera.NeedUndistortion)");
   }
+  // Camera.Rectify: the frame's raw pair warped into the common rectified camera, each image through its own lens (radtan or kb4) and
+  // rectifying rotation -- prm[0], prm[1] as ssx_stereo_rectify returns them.  It takes the place of UndistortPair,
+  // under the same rules: an implementation without it says so and a FrontEnd with the key set refuses to be built on it.
+  virtual bool CanRectify() const { return false; }
+  virtual void RectifyPair(const Image& left, const Image& right, const ssx_lens_params prm[2], Image& left_out, Image& right_out)
+  {
+    (void)left; (void)right; (void)prm; (void)left_out; (void)right_out;
+    throw std::logic_error("Compute::RectifyPair: this implementation cannot rectify images (Camera.Rectify)");
+  }
   // 11x11 window, 3 levels, (COUNT+EPS, 30, 0.01), OPTFLOW_USE_INITIAL_FLOW: next_pts holds the guesses going in.
   // `temporal` marks the frame-to-frame call (the implementation may keep the previous frame's pyramid).
   virtual void TrackLK(const Image& prev, const Image& next, const std::vector<float>& prev_pts, std::vector<float>& next_pts,

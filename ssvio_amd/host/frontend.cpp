@@ -32,7 +32,7 @@ void Camera::world2pixel(const double* p_w, const SE3& T_c_w, float* uv) const
 }
 
 FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right,
-                   const ssx_undistort_params* undistort)
+                   const ssx_undistort_params* undistort, const ssx_lens_params* rectify)
     : compute_(compute), map_(std::move(map)), left_camera_(left), right_camera_(right)
 {
   num_features_init_good_ = cfg.Get<int>("numFeatures.initGood");
@@ -45,6 +45,13 @@ FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> ma
     throw std::runtime_error("FrontEnd: Camera.NeedUndistortion != 0 is not supported by this Compute (rectified input only; there is no CPU fallback)");
   if (need_undistortion_ && !undistort) throw std::runtime_error("FrontEnd: Camera.NeedUndistortion != 0 without the cameras' undistortion parameters");
   if (need_undistortion_) { undistort_[0] = undistort[0]; undistort_[1] = undistort[1]; }
+  need_rectify_ = cfg.Get<int>("Camera.Rectify") != 0;
+  if (need_rectify_ && need_undistortion_)
+    throw std::runtime_error("FrontEnd: Camera.Rectify and Camera.NeedUndistortion are both set: rectification removes the lens distortion itself, set one of them");
+  if (need_rectify_ && !compute.CanRectify())
+    throw std::runtime_error("FrontEnd: Camera.Rectify != 0 is not supported by this Compute (rectified input only; there is no CPU fallback)");
+  if (need_rectify_ && !rectify) throw std::runtime_error("FrontEnd: Camera.Rectify != 0 without the two lenses' rectification parameters");
+  if (need_rectify_) { rectify_[0] = rectify[0]; rectify_[1] = rectify[1]; }
   if (left.fx != right.fx || left.fy != right.fy || left.cx != right.cx || left.cy != right.cy)
     throw std::runtime_error("FrontEnd: the two cameras must share their intrinsics (rectified stereo rig)");
   // System::GenerateORBextractor (system.cpp:115-128): nNewFeatures for keyframes, nInitFeatures for initialisation
@@ -66,6 +73,12 @@ bool FrontEnd::GrabSteroImage(ImagePtr left, ImagePtr right, double timestamp)
     auto l = std::make_shared<Image>(), r = std::make_shared<Image>();
     l->id = NewImageId(); r->id = NewImageId();                        // new images: a resident pyramid of the distorted ones is not theirs
     compute_.UndistortPair(*left, *right, undistort_, *l, *r);         // (the ids first: a Compute may keep the results where its next calls look for them)
+    left = std::move(l); right = std::move(r);
+  } else if (need_rectify_) {                                          // in undistortion's place, and in its time
+    Stopwatch sw(times_.undistort, times_.n_undistort);
+    auto l = std::make_shared<Image>(), r = std::make_shared<Image>();
+    l->id = NewImageId(); r->id = NewImageId();
+    compute_.RectifyPair(*left, *right, rectify_, *l, *r);
     left = std::move(l); right = std::move(r);
   }
   std::lock_guard<std::mutex> map_lock(map_->update_mutex);           // frontend.cpp:49: the whole frame is tracked under the map mutex

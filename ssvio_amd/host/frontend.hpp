@@ -7,6 +7,8 @@
 // Every arithmetic step of those functions is a Compute call; what is restated here is the bookkeeping between them.
 // Camera.NeedUndistortion != 0 (:39-45): both images of a frame are replaced by Compute::UndistortPair's before anything looks at them; a
 // Compute that cannot undistort (the CPU oracle of the tests) is refused at construction.
+// Camera.Rectify != 0 (no reference behaviour): the raw pair of a frame is replaced by Compute::RectifyPair's, in the place and
+// under the rules of undistortion; the two keys together are refused.
 // Not carried over: the viewer hooks (Pangolin), cv::imshow debugging, and the mutexes -- the headless runner is single-threaded.
 #pragma once
 #include <memory>
@@ -37,9 +39,11 @@ struct StageTimes {                                   // wall-clock seconds spen
 class FrontEnd {
  public:
   // undistort: the two cameras' parameters (left, right) when Camera.NeedUndistortion is set (System reads Camera{1,2}.k1/k2/p1/p2);
-  // with the key set, a null pointer or a Compute that cannot undistort throws, naming the key
+  // with the key set, a null pointer or a Compute that cannot undistort throws, naming the key.
+  // rectify: the two lenses (left, right) as ssx_stereo_rectify returns them when Camera.Rectify is set (System reads the raw rig); left
+  // and right are then the rectified cameras.  The same refusals, naming that key; both keys set throws, naming both.
   FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> map, const Camera& left, const Camera& right,
-           const ssx_undistort_params* undistort = nullptr);
+           const ssx_undistort_params* undistort = nullptr, const ssx_lens_params* rectify = nullptr);
   void SetBackend(Backend* backend) { backend_ = backend; }
   // Relocalization.Open: 1 -- a LOST front-end asks the loop closing's keyframe database where it is (Relocalize below) instead of
   // ignoring every later frame.  Without a LoopClosing the state LOST is final, as in the reference (frontend.cpp:62-66: a TODO).
@@ -82,6 +86,8 @@ class FrontEnd {
   bool open_backend_optimization_;
   bool need_undistortion_ = false;           // Camera.NeedUndistortion
   ssx_undistort_params undistort_[2] = {};   // left, right
+  bool need_rectify_ = false;                // Camera.Rectify
+  ssx_lens_params rectify_[2] = {};          // left, right
   std::vector<int32_t> boxes_;               // DetectFeatures: the mask's rectangles (x0, y0, x1, y1)
   std::vector<unsigned long> condemned_;     // EstimateCurrentPose: the map points this frame condemned (taken back when it ends LOST and relocalisation is on)
   StageTimes times_;

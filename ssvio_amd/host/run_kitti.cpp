@@ -30,6 +30,8 @@
 // set is refused unless --undistort_batched=1 is given: the pairs of a cohort's streams then go through the lenses' stored maps in ONE
 // ssx_undistort_plan_apply call per frame (two jobs a stream, one map per camera of the rig), and every stream still writes the bytes of its
 // single-stream run.  With the key 0 or absent the flag changes nothing; without --batched >= 1 it is refused.
+// Camera.Rectify: 1 (a raw rig: every frame's pair goes through ssx_undistort_lens into the common rectified camera first; system.hpp)
+// stands under the same rules and the same flag: its maps are stored maps like any other.
 // Loop closing is per stream.  --batched >= 1 with Loop.Closing.Open: 1 is refused unless --loop_batched=1 is given: the streams of a cohort
 // then share one loop context and one vocabulary, and their inline keyframe steps go to the GPU as ssx_kfdb_process_keyframe_batch calls
 // (every stream still writes the bytes of its single-stream run).  The loop thread (Loop.Closing.Async: 1) is not batched: refused with it.
@@ -151,6 +153,11 @@ int main(int argc, char** argv)
     }
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Camera.NeedUndistortion") != 0 && !undistort_batched) {
       std::fprintf(stderr, "--batched=%s with Camera.NeedUndistortion: 1 is not supported without --undistort_batched=1 (the cohort's pairs undistorted in one call "
+                   "per frame); or run --streams unbatched, or feed rectified images\n", batched_s.c_str());
+      return 2;
+    }
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Camera.Rectify") != 0 && !undistort_batched) {
+      std::fprintf(stderr, "--batched=%s with Camera.Rectify: 1 is not supported without --undistort_batched=1 (the cohort's pairs rectified in one call "
                    "per frame); or run --streams unbatched, or feed rectified images\n", batched_s.c_str());
       return 2;
     }

@@ -191,6 +191,19 @@ class SsxCompute final : public Compute {
     frame_.check(ssx_undistort(frame_.get(), 2, jobs, left.rows, left.cols, 0));
   }
 
+  bool CanRectify() const override { return true; }
+
+  // the frame's raw pair in one ssx_undistort_lens call of two jobs, whatever the two lens models are
+  void RectifyPair(const Image& left, const Image& right, const ssx_lens_params prm[2], Image& left_out, Image& right_out) override
+  {
+    if (left.rows != right.rows || left.cols != right.cols) throw std::invalid_argument("RectifyPair: left / right image sizes differ");
+    left_out.rows = right_out.rows = left.rows; left_out.cols = right_out.cols = left.cols;
+    left_out.data.resize(left.data.size()); right_out.data.resize(right.data.size());
+    const ssx_lens_job jobs[2] = {{left.ptr(), left.cols, left_out.data.data(), left.cols, prm[0]},
+                                  {right.ptr(), right.cols, right_out.data.data(), right.cols, prm[1]}};
+    frame_.check(ssx_undistort_lens(frame_.get(), 2, jobs, left.rows, left.cols, 0));
+  }
+
   void TrackLK(const Image& prev, const Image& next, const std::vector<float>& prev_pts, std::vector<float>& next_pts,
                std::vector<uint8_t>& status, bool temporal) override
   {

@@ -35,7 +35,7 @@ struct LkReq { ssx_lk_job job{}; ImageSize size; };   // temporal and stereo LK
 struct DetReq { ssx_orb_detect_job job{}; ssx_orb_params prm{}; ImageSize size; };
 struct BaReq { ssx_ba_window* win = nullptr; ssx_ba_result* res = nullptr; };
 // a frame's pair through the lenses' maps: two jobs (left, right) of one request, raw images and results in the stream's pinned buffers
-struct UndReq { const uint8_t* src[2] = {nullptr, nullptr}; uint8_t* dst[2] = {nullptr, nullptr}; ssx_undistort_params prm[2] = {}; ImageSize size; };
+struct UndReq { const uint8_t* src[2] = {nullptr, nullptr}; uint8_t* dst[2] = {nullptr, nullptr}; ssx_lens_params prm[2] = {}; ImageSize size; };   // (an undistortion request: its RADTAN lenses)
 // one keyframe step of loop closing as a stream files it (ssx_kfdb_process_keyframe_batch): the job and what a call's jobs must share
 struct LoopReq { ssx_kfdb_step_job job{}; ssx_orb_params prm{}; ImageSize size; int levels = 0, min_db = 0, min_gap = 0; float threshold = 0.f; int32_t status = 0; };
 // the candidate query of a stream that lost tracking (ssx_kfdb_relocalize_query_batch), in the same form
@@ -333,7 +333,7 @@ struct StreamBatcher::Impl {
         for (int k : slots) {
           const UndReq& r = und_req[k];
           int32_t map = -1;
-          us.ctx.check(ssx_undistort_plan_add(us.plan, &r.prm[side], &map));
+          us.ctx.check(ssx_undistort_plan_add_lens(us.plan, &r.prm[side], &map));
           jobs.push_back({r.src[side], r.size.cols, r.dst[side], r.size.cols, map});
         }
       us.ctx.check(ssx_undistort_plan_apply(us.plan, (int32_t)jobs.size(), jobs.data(), 1));
@@ -544,6 +544,18 @@ class BatchedCompute final : public Compute {
   // pinned buffers 2 and 3; the call writes the results into buffers 0 and 1, which then hold the frame's images under the ids the
   // front-end gave them -- the frame's LK calls find them there and copy nothing -- and this thread fills the host images from them.
   void UndistortPair(const Image& left, const Image& right, const ssx_undistort_params prm[2], Image& left_out, Image& right_out) override
+  {
+    ssx_lens_params lens[2] = {};                  // (the RADTAN lens a parameter set is: the bytes ssx_undistort_plan_add gives it)
+    for (int s = 0; s < 2; ++s) {
+      lens[s].model = SSX_LENS_RADTAN;
+      std::memcpy(lens[s].K, prm[s].K, sizeof lens[s].K); std::memcpy(lens[s].coeffs, prm[s].dist, sizeof lens[s].coeffs); std::memcpy(lens[s].iR, prm[s].iR, sizeof lens[s].iR);
+    }
+    RectifyPair(left, right, lens, left_out, right_out);
+  }
+
+  bool CanRectify() const override { return true; }
+  // Camera.Rectify: the same request kind -- a map is a map, whatever lens and rotation it was made from
+  void RectifyPair(const Image& left, const Image& right, const ssx_lens_params prm[2], Image& left_out, Image& right_out) override
   {
     im_.core.Bind(k_);                             // (the front-end calls come from the stream's thread)
     if (left.rows != right.rows || left.cols != right.cols) throw std::invalid_argument("UndistortPair: left / right image sizes differ");

@@ -39,9 +39,48 @@ System::System(const std::string& config_file_path, std::unique_ptr<Compute> com
     }
   }
 
+  // Camera.Rectify (no reference behaviour to mirror: every key is read as double): the raw rig of the settings, rectified on the host
+  need_rectify_ = setting_.Get<int>("Camera.Rectify") != 0;
+  if (need_rectify_ && need_undistortion_)
+    throw std::runtime_error("System: Camera.Rectify and Camera.NeedUndistortion are both set in " + config_file_path +
+                             ": rectification removes the lens distortion itself, set one of them");
+  if (need_rectify_) {
+    ssx_stereo_raw_rig rig{};
+    for (int c = 0; c < 2; ++c) {
+      const std::string key = c == 0 ? "Camera1." : "Camera2.";
+      const std::string model = setting_.Has(key + "Model") ? setting_.Get<std::string>(key + "Model") : std::string("radtan");
+      ssx_lens_params& cam = rig.cam[c];
+      if (model == "radtan") cam.model = SSX_LENS_RADTAN;
+      else if (model == "kb4") cam.model = SSX_LENS_KB4;
+      else throw std::runtime_error("System: " + key + "Model: \"" + model + "\" is neither radtan nor kb4 (" + config_file_path + ")");
+      const char* k4[4] = {"fx", "fy", "cx", "cy"};
+      for (int i = 0; i < 4; ++i) cam.K[i] = setting_.Get<double>(key + k4[i]);
+      const char* radtan[5] = {"k1", "k2", "p1", "p2", "k3"};
+      const char* kb4[5] = {"k1", "k2", "k3", "k4", nullptr};
+      for (int i = 0; i < 5; ++i) {
+        const char* name = cam.model == SSX_LENS_KB4 ? kb4[i] : radtan[i];
+        cam.coeffs[i] = name ? setting_.Get<double>(key + name) : 0.0;
+      }
+    }
+    for (int i = 0; i < 9; ++i) rig.R[i] = setting_.Get<double>("Stereo.R21." + std::to_string(i));
+    for (int i = 0; i < 3; ++i) rig.t[i] = setting_.Get<double>("Stereo.t21." + std::to_string(i));
+    rig.f = setting_.Get<double>("Camera.Rectified.f"); rig.cx = setting_.Get<double>("Camera.Rectified.cx"); rig.cy = setting_.Get<double>("Camera.Rectified.cy");
+    char why[160];
+    if (ssx_stereo_rectify(&rig, &rectified_, why, (int32_t)sizeof why) != SSX_OK)
+      throw std::runtime_error("System: Camera.Rectify: the rig of Stereo.R21 / Stereo.t21 / Camera{1,2} in " + config_file_path + " cannot be rectified: " + why);
+    const double* nk = rectified_.newK;
+    left_camera_ = Camera{nk[0], nk[1], nk[2], nk[3], 0.0, SE3()};
+    right_camera_ = Camera{nk[0], nk[1], nk[2], nk[3], rectified_.baseline, SE3::translation(-rectified_.baseline, 0, 0)};
+    const double* Rl = rectified_.R_l;
+    std::printf("Camera.Rectify: common camera f = %.6f, cx = %.6f, cy = %.6f, baseline = %.6f m (Camera.Base.Line is ignored); the trajectory is in the "
+                "rectified left frame, X_rectified = R_l X_left, R_l = [%.9f %.9f %.9f; %.9f %.9f %.9f; %.9f %.9f %.9f]\n",
+                nk[0], nk[2], nk[3], rectified_.baseline, Rl[0], Rl[1], Rl[2], Rl[3], Rl[4], Rl[5], Rl[6], Rl[7], Rl[8]);
+  }
+
   map_ = std::make_shared<Map>((unsigned)setting_.Get<int>("Map.ActiveMap.Size"));
   backend_ = std::make_unique<Backend>(setting_, *compute_, map_, left_camera_, right_camera_);
-  frontend_ = std::make_unique<FrontEnd>(setting_, *compute_, map_, left_camera_, right_camera_, need_undistortion_ ? undistort_ : nullptr);
+  frontend_ = std::make_unique<FrontEnd>(setting_, *compute_, map_, left_camera_, right_camera_, need_undistortion_ ? undistort_ : nullptr,
+                                         need_rectify_ ? rectified_.cam : nullptr);
   frontend_->SetBackend(backend_.get());
 
   // system.cpp:17-41
@@ -123,6 +162,10 @@ void System::Warmup(int rows, int cols)
   if (need_undistortion_) {                                            // the frame's first call: the kernel is loaded, the staging sized
     Image ul, ur;
     compute_->UndistortPair(*L0, *R0, undistort_, ul, ur);
+  }
+  if (need_rectify_) {
+    Image ul, ur;
+    compute_->RectifyPair(*L0, *R0, rectified_.cam, ul, ur);
   }
   ssx_orb_params prm{};
   prm.nfeatures = std::max(setting_.Get<int>("ORBextractor.nInitFeatures"), setting_.Get<int>("ORBextractor.nNewFeatures"));

@@ -24,6 +24,12 @@ class System {
   // Loop.Closing.Open != 0: LoopClosing is built on Compute::MakeLoopCompute(DBOW2.VOC.Path) and attached to the backend; throws,
   // naming the key, when the vocabulary cannot be read.  A Compute without loop closing (MakeLoopCompute returns null: the CPU
   // oracle of the tests) gets one warning line and a system without it.
+  // Camera.Rectify != 0: the settings state a RAW rig -- Camera{1,2}.fx fy cx cy, Camera{1,2}.Model (radtan, the default, or
+  // kb4), Camera{1,2}.k1 k2 p1 p2 k3 (radtan) or k1 k2 k3 k4 (kb4), Stereo.R21.0 .. .8 and Stereo.t21.0 .. .2 (X_right = R21 X_left +
+  // t21), optionally Camera.Rectified.f / .cx / .cy -- all read as double.  ssx_stereo_rectify makes the common camera: both Camera
+  // objects get its intrinsics, the right one sits at (-baseline, 0, 0), Camera.Base.Line is ignored (one line says so), and every
+  // frame's pair goes through Compute::RectifyPair first.  The trajectory is in the RECTIFIED left frame; R_l is printed once.  A rig
+  // ssx_stereo_rectify refuses, an unknown Model, or both keys (with Camera.NeedUndistortion) throw, naming the keys.
   explicit System(const std::string& config_file_path, std::unique_ptr<Compute> compute = nullptr, int device = 0);
   ~System();
 
@@ -39,6 +45,9 @@ class System {
   Map& map() { return *map_; }
   FrontEnd& frontend() { return *frontend_; }
   Backend& backend() { return *backend_; }
+  const Camera& left_camera() const { return left_camera_; }
+  const Camera& right_camera() const { return right_camera_; }
+  const ssx_stereo_rectified* rectified() const { return need_rectify_ ? &rectified_ : nullptr; }   // null: Camera.Rectify is off
   LoopClosing* loop_closing() { return loop_closing_.get(); }              // null: loop closing is off
   void WaitIdle();                                                         // the backend's thread, then the loop thread
 
@@ -48,6 +57,8 @@ class System {
   Camera left_camera_, right_camera_;
   bool need_undistortion_ = false;                                         // Camera.NeedUndistortion
   ssx_undistort_params undistort_[2] = {};                                 // left, right: K as the cameras', Camera{1,2}.k1/k2/p1/p2, k3 = 0, R = I
+  bool need_rectify_ = false;                                              // Camera.Rectify
+  ssx_stereo_rectified rectified_ = {};                                    // ssx_stereo_rectify of the raw rig the settings state
   std::shared_ptr<Map> map_;
   std::unique_ptr<Backend> backend_;
   std::unique_ptr<FrontEnd> frontend_;

@@ -1,12 +1,13 @@
 """Image undistortion over ctypes: ssx_undistort / ssx_undistort_default and the plan of stored maps, ssx_undistort_plan_* (include/ssx.h;
-contract: tools/undistort_model.py)."""
+contract: tools/undistort_model.py); and raw stereo rigs: ssx_stereo_rectify, ssx_undistort_lens, ssx_undistort_plan_add_lens with a lens
+model (radtan or kb4) per image (contract: tools/rectify_model.py)."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
 
-from ._lib import Context, UndistortJob, UndistortParams, UndistortPlanJob, load
+from ._lib import Context, LensJob, LensParams, StereoRawRig, StereoRectified, UndistortJob, UndistortParams, UndistortPlanJob, load
 
 
 def _fns(lib):
@@ -34,6 +35,16 @@ def _fns(lib):
             lib.ssx_undistort_plan_debug_last_call.argtypes = [C.c_void_p, i32_p, i32_p, i64_p, i64_p, i32_p, i32_p]
             lib.ssx_undistort_plan_debug_map.restype = C.c_int
             lib.ssx_undistort_plan_debug_map.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint16)]
+        if hasattr(lib, "ssx_undistort_lens"):                  # (an older build named by SSX_LIB lacks them: the A/B runs of tools/; using one then raises)
+            lib.ssx_undistort_lens.restype = C.c_int
+            lib.ssx_undistort_lens.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LensJob), C.c_int32, C.c_int32, C.c_int32]
+            lib.ssx_undistort_plan_add_lens.restype = C.c_int
+            lib.ssx_undistort_plan_add_lens.argtypes = [C.c_void_p, C.POINTER(LensParams), i32_p]
+            lib.ssx_stereo_rectify.restype = C.c_int
+            lib.ssx_stereo_rectify.argtypes = [C.POINTER(StereoRawRig), C.POINTER(StereoRectified), C.c_char_p, C.c_int32]
+        if hasattr(lib, "ssx_lens_debug_atan"):                 # include/ssx_test_hooks.h
+            lib.ssx_lens_debug_atan.restype = C.c_int
+            lib.ssx_lens_debug_atan.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         lib._undistort_ready = True
     return lib
 
@@ -55,20 +66,71 @@ def make_params(K, dist, iR=None) -> UndistortParams:
     return out
 
 
+def make_lens_params(model, K, coeffs, iR=None) -> LensParams:
+    """model = SSX_LENS_RADTAN (coeffs = k1 k2 p1 p2[ k3]) or SSX_LENS_KB4 (coeffs = k1 k2 k3 k4); K = (fx, fy, cx, cy); iR = 9 doubles
+    (inverse of newK * R), default: ssx_undistort_default's (R = I, newK = K).  Needs no device."""
+    co = [float(v) for v in coeffs] + [0.0] * (5 - len(coeffs))
+    if len(co) != 5:
+        raise ValueError("coeffs has at most 5 entries")
+    base = make_params(K, co, iR)
+    out = LensParams()
+    out.model = int(model)
+    out.K[:] = base.K[:]
+    out.coeffs[:] = base.dist[:]
+    out.iR[:] = base.iR[:]
+    return out
+
+
+def stereo_rectify(cams, R, t, f=None, cx=None, cy=None) -> StereoRectified:
+    """ssx_stereo_rectify (host arithmetic, no device; contract: tools/rectify_model.py's rectify).  cams = the left and the right
+    LensParams (iR ignored), X_right = R X_left + t; f, cx, cy: the common camera's, None or 0 for the default.  -> StereoRectified,
+    whose cam[0], cam[1] are ready for undistort_lens / UndistortPlan.add_lens.  A refused rig raises ValueError with the reason."""
+    lib = _fns(load())
+    rig = StereoRawRig()
+    rig.cam[0], rig.cam[1] = cams
+    rig.R[:] = [float(v) for v in np.asarray(R, dtype=np.float64).reshape(9)]
+    rig.t[:] = [float(v) for v in np.asarray(t, dtype=np.float64).reshape(3)]
+    rig.f, rig.cx, rig.cy = (0.0 if v is None else float(v) for v in (f, cx, cy))
+    out = StereoRectified()
+    why = C.create_string_buffer(160)
+    if lib.ssx_stereo_rectify(C.byref(rig), C.byref(out), why, len(why)) != 0:
+        raise ValueError(why.value.decode())
+    return out
+
+
 def undistort_ptrs(ctx: Context, jobs, rows, cols, images_on_device=True):
-    """ssx_undistort on memory the caller holds: jobs = [(src address, src stride, dst address, dst stride, UndistortParams)]"""
+    """ssx_undistort, or ssx_undistort_lens when the first job's parameters are LensParams, on memory the caller holds:
+    jobs = [(src address, src stride, dst address, dst stride, UndistortParams or LensParams)]"""
     lib = _fns(ctx.lib)
     n = len(jobs)
-    arr = (UndistortJob * max(n, 1))()
+    lens = n > 0 and isinstance(jobs[0][4], LensParams)
+    arr = ((LensJob if lens else UndistortJob) * max(n, 1))()
     for k, (src, ss, dst, ds, prm) in enumerate(jobs):
         arr[k].src = src; arr[k].src_stride = ss; arr[k].dst = dst; arr[k].dst_stride = ds; arr[k].prm = prm
-    ctx.check(lib.ssx_undistort(ctx.handle, n, arr, rows, cols, 1 if images_on_device else 0))
+    ctx.check((lib.ssx_undistort_lens if lens else lib.ssx_undistort)(ctx.handle, n, arr, rows, cols, 1 if images_on_device else 0))
+
+
+def undistort_lens(ctx: Context, images, params, dst_stride=None):
+    """undistort() through ssx_undistort_lens: params is one LensParams per image, of either model"""
+    if not all(isinstance(p, LensParams) for p in params):
+        raise ValueError("one LensParams per image")
+    return undistort(ctx, images, params, dst_stride=dst_stride)
+
+
+def lens_atan(ctx: Context, r):
+    """ssx_lens_debug_atan -> (atan_c(r), sqrt(r)) as the device computes them, float64 arrays of r's shape"""
+    lib = _fns(ctx.lib)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    a, s = np.empty_like(r), np.empty_like(r)
+    dp = C.POINTER(C.c_double)
+    ctx.check(lib.ssx_lens_debug_atan(ctx.handle, r.size, r.ctypes.data_as(dp), a.ctypes.data_as(dp), s.ctypes.data_as(dp)))
+    return a, s
 
 
 def undistort(ctx: Context, images, params, dst_stride=None):
     """One ssx_undistort call over host images.  images: 2-D uint8 arrays of one shape (a row pitch is kept: only the last axis must be
-    contiguous); params: one UndistortParams per image.  -> the undistorted images, contiguous unless dst_stride (bytes, >= cols) is
-    given: then each is the [rows, cols] view of a [rows, dst_stride] buffer of zeros."""
+    contiguous); params: one UndistortParams per image (or one LensParams per image: ssx_undistort_lens).  -> the undistorted images,
+    contiguous unless dst_stride (bytes, >= cols) is given: then each is the [rows, cols] view of a [rows, dst_stride] buffer of zeros."""
     if len(images) != len(params):
         raise ValueError("one parameter set per image")
     if not images:
@@ -119,6 +181,12 @@ class UndistortPlan:
         """-> the index of the parameter set's map; equal bytes return the index they have, a new set launches k_undistort_map once"""
         m = C.c_int32(-1)
         self.ctx.check(self.lib.ssx_undistort_plan_add(self.handle, C.byref(prm), C.byref(m)))
+        return m.value
+
+    def add_lens(self, prm: LensParams) -> int:
+        """add() for a lens of either model (ssx_undistort_plan_add_lens); a RADTAN lens and its UndistortParams form are one map"""
+        m = C.c_int32(-1)
+        self.ctx.check(self.lib.ssx_undistort_plan_add_lens(self.handle, C.byref(prm), C.byref(m)))
         return m.value
 
     def size(self):
