@@ -697,6 +697,29 @@ SSX_API ssx_status ssx_undistort_plan_add(ssx_undistort_plan* plan, const ssx_un
 SSX_API ssx_status ssx_undistort_plan_apply(ssx_undistort_plan* plan, int32_t n, const ssx_undistort_plan_job* jobs, int32_t images_on_device);
 SSX_API ssx_status ssx_undistort_plan_size(const ssx_undistort_plan* plan, int32_t* rows, int32_t* cols, int32_t* n_maps);
 SSX_API void ssx_undistort_plan_destroy(ssx_undistort_plan* plan);
+/* Dense stereo: a disparity for every pixel of a rectified pair, by census + semi-global matching.  The contract is
+ * tools/dense_model.py, integers only, and the device is held to it bit for bit: a 9 x 7 census with a replicated
+ * border, Hamming cost (63 where x - d < 0), `paths` (4 or 8) path directions with penalties 1 <= p1 <= p2 <= 192, the first minimum
+ * of the summed volume, a uniqueness margin in percent (0 .. 99), a left-right check of lr_tolerance whole disparities (-1: off,
+ * at most `disparities`) against the right disparity of the same volume, and an integer sub-pixel step.  disparities is 64 or 128, the
+ * minimum disparity is 0.  Output: int16 in 1/16 pixel, -16 where a pixel is invalid.
+ * ssx_stereo_dense: n pairs (0 .. SSX_DENSE_MAX_JOBS) of one size rows x cols (40 .. 4000 a side), 8-bit, image strides in bytes and
+ * disp_stride in elements, each at least cols.  images_on_device == 0: host memory, staged -- ONE copy up (the job table and the
+ * images), ONE copy down (the maps), ONE synchronisation.  images_on_device != 0: every pointer is device memory or pinned host
+ * memory (ssx_host_alloc) and is read and written where it lies; only the job table goes up.  The census words, the summed volume and
+ * the right keys are workspace of the context: (20 + 2 disparities) bytes per pixel and pair.  A call works through its pairs in
+ * groups whose workspace stays under SSX_DENSE_WORKSPACE_CAP, six launches (two of them fills) per group whatever the image size or
+ * content -- four with lr_tolerance = -1; one pair always runs, whatever it takes (4000 x 4000 at 128: 4.4 GB).
+ * SSX_ERR_INVALID_ARG with a message in ssx_last_error, before anything is touched or launched: a parameter out of range, a
+ * non-zero `reserved`, a null prm / jobs / image / disp, a stride below cols, n or a side out of range. */
+typedef struct { int32_t disparities, p1, p2, uniqueness, lr_tolerance, paths, reserved[2]; } ssx_dense_params;
+typedef struct { const uint8_t* left; int32_t left_stride; const uint8_t* right; int32_t right_stride;
+                 int16_t* disp; int32_t disp_stride; /* in elements */ } ssx_dense_job;
+#define SSX_DENSE_MAX_JOBS 1024
+#define SSX_DENSE_WORKSPACE_CAP (1ull << 30) /* bytes: 8 pairs of 1241 x 376 at 128 disparities */
+SSX_API void ssx_dense_default_params(ssx_dense_params* p); /* 128, 7, 86, 10, 1, 8 */
+SSX_API ssx_status ssx_stereo_dense(ssx_ctx* ctx, int32_t n, const ssx_dense_job* jobs, int32_t rows, int32_t cols,
+                                    const ssx_dense_params* prm, int32_t images_on_device);
 /* Raw stereo rigs: lens models and rectification.  The contract is tools/rectify_model.py.
  * A lens is SSX_LENS_RADTAN -- coeffs = k1 k2 p1 p2 k3, the map of ssx_undistort, whose entry points are this case -- or SSX_LENS_KB4,
  * Kannala-Brandt "equidistant" with coeffs = k1 k2 k3 k4 (coeffs[4] is ignored): theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8),

@@ -11,6 +11,7 @@
 //   ssx::StereoFrontEnd          DetectFeatures + FindFeaturesInRight + triangulation in one device-resident call
 //   ssx::calcOpticalFlowPyrLK    cv::calcOpticalFlowPyrLK as frontend.cpp:156-166 / :374-384 call it
 //   ssx::Camera                  Camera::UndistortImage (src/ssvio/camera.cpp:43-55), one image or the frame's pair
+//   ssx::DenseDisparity          a disparity per pixel of a rectified pair (census + SGM; no counterpart in the reference)
 //   ssx::ORBVocabulary           DBoW2 vocabulary: loadFromTextFile / transform / score (loopclosing.cpp:33-41, :84, :633)
 //   ssx::KeyframeDatabase        key_frame_database_ with AddToKeyframeDatabase / DetectLoop / MatchFeatures (loopclosing.cpp:72-145, :646)
 //   ssx::ComputeCorrectPose      LoopClosing::ComputeCorrectPose / OptimizeCurrentPose (loopclosing.cpp:147-351)
@@ -273,6 +274,18 @@ inline ssx_stereo_rectified StereoRectify(const ssx_stereo_raw_rig& rig)
   char why[160];
   if (ssx_stereo_rectify(&rig, &out, why, (int32_t)sizeof why) != SSX_OK) throw std::invalid_argument(std::string("ssx::StereoRectify: ") + why);
   return out;
+}
+
+// ssx_stereo_dense for one rectified pair (no counterpart in the reference): census + semi-global matching, the bits of
+// tools/dense_model.py.  disp: rows x cols int16 at a pitch of dispStep ELEMENTS, in 1/16 pixel, -16 where a pixel is invalid.
+// prm = nullptr: ssx_dense_default_params.  Host memory unless imagesOnDevice.
+inline void DenseDisparity(Context& ctx, const uint8_t* left, int leftStep, const uint8_t* right, int rightStep, int16_t* disp, int dispStep, int rows,
+                           int cols, const ssx_dense_params* prm = nullptr, bool imagesOnDevice = false)
+{
+  ssx_dense_params def;
+  ssx_dense_default_params(&def);
+  const ssx_dense_job job = {left, leftStep, right, rightStep, disp, dispStep};
+  ctx.check(ssx_stereo_dense(ctx.get(), 1, &job, rows, cols, prm ? prm : &def, imagesOnDevice ? 1 : 0));
 }
 
 // Many streams' frames in one call (ssx_undistort_plan_*): the plan keeps one stored map per camera it was shown (Add: equal parameter

@@ -248,6 +248,18 @@ SSX_API ssx_status ssx_undistort_plan_debug_map(ssx_undistort_plan* plan, int32_
  * compared with tools/rectify_model.py's directly; either output may be NULL */
 SSX_API ssx_status ssx_lens_debug_atan(ssx_ctx* ctx, int32_t n, const double* r, double* atan_out, double* sqrt_out);
 
+/* tests / tools hooks of ssx_stereo_dense (csrc/dense.hip).  What the context's last call issued, counted where it is issued, as
+ * ssx_undistort_debug_last_call counts (a fill of workspace counts as a launch), and the number of groups it worked through.  All
+ * zero after a call that was refused.  Any output may be NULL. */
+SSX_API ssx_status ssx_dense_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down,
+                                             int32_t* groups);
+/* the stages of ONE pair of host images through the kernels of ssx_stereo_dense, named as tools/dense_model.py names them: the census
+ * words of both images (rows x cols u64 each), the path volume L of `direction` (0 .. paths - 1; rows x cols x disparities u8, d
+ * fastest), the summed volume S (u16, the same shape) and the right disparity dR (rows x cols u8).  Any output may be NULL. */
+SSX_API ssx_status ssx_dense_debug_stages(ssx_ctx* ctx, const uint8_t* left, int32_t left_stride, const uint8_t* right, int32_t right_stride,
+                                          int32_t rows, int32_t cols, const ssx_dense_params* prm, int32_t direction, uint64_t* census_left,
+                                          uint64_t* census_right, uint8_t* path_volume, uint16_t* sum_volume, uint8_t* right_disparity);
+
 #ifdef __cplusplus
 }
 #endif

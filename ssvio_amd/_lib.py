@@ -236,6 +236,22 @@ class StereoRectified(C.Structure):
     _fields_ = [("R_l", C.c_double * 9), ("R_r", C.c_double * 9), ("newK", C.c_double * 4), ("baseline", C.c_double), ("cam", LensParams * 2)]
 
 
+class DenseParamsC(C.Structure):
+    """ssx_dense_params"""
+    _fields_ = [("disparities", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("uniqueness", C.c_int32), ("lr_tolerance", C.c_int32),
+                ("paths", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class DenseJob(C.Structure):
+    """ssx_dense_job: image strides in bytes, disp_stride in int16 elements"""
+    _fields_ = [("left", C.c_void_p), ("left_stride", C.c_int32), ("right", C.c_void_p), ("right_stride", C.c_int32),
+                ("disp", C.c_void_p), ("disp_stride", C.c_int32)]
+
+
+SSX_DENSE_MAX_JOBS = 1024
+SSX_DENSE_WORKSPACE_CAP = 1 << 30
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("calls", C.c_int32), ("total_ms", C.c_double)]
 

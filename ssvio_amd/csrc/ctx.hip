@@ -77,6 +77,9 @@ void ssx_ctx_destroy(ssx_ctx* ctx)
   ctx->pnp_stage.release();
   ctx->ud_arena.release();
   ctx->ud_stage.release();
+  ctx->dn_arena.release();
+  ctx->dn_work.release();
+  ctx->dn_stage.release();
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
   if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }

@@ -6,6 +6,7 @@
 //   PoseOnly        the g2o part of EstimateCurrentPose (frontend.cpp:196-270)
 //   Triangulate     ssvio::triangulation + z > 0      (frontend.cpp:448-544)
 //   BundleAdjust    the g2o part of OptimizeActiveMap (backend.cpp:78-205)
+//   DenseDisparity  a disparity for every pixel of a keyframe's pair (no counterpart in the reference; Dense.Open)
 //   LoopCompute     the per-keyframe step, ComputeCorrectPose and LoopCorrect's geometry (loopclosing.cpp:39-70, 147-243, 353-594)
 // SsxCompute is the product implementation: the C ABI of libssx.so on an MI355X, nothing else (no CPU fallback; the
 // constructor throws without a gfx950 device).  The interface exists so tests can run the same host logic against
@@ -132,6 +133,15 @@ class Compute {
   {
     (void)left; (void)right; (void)prm; (void)left_out; (void)right_out;
     throw std::logic_error("Compute::RectifyPair: this implementation cannot rectify images (Camera.Rectify)");
+  }
+  // Dense.Open: the disparity map of a keyframe's rectified pair by census + semi-global matching (ssx_stereo_dense; the contract is
+  // tools/dense_model.py): disp = rows x cols int16 in 1/16 pixel, -16 where a pixel is invalid.  The rules of UndistortPair: an
+  // implementation without it says so and a FrontEnd with the key set refuses to be built on it.
+  virtual bool CanDense() const { return false; }
+  virtual void DenseDisparity(const Image& left, const Image& right, const ssx_dense_params& prm, std::vector<int16_t>& disp)
+  {
+    (void)left; (void)right; (void)prm; (void)disp;
+    throw std::logic_error("Compute::DenseDisparity: this implementation has no dense stereo (Dense.Open)");
   }
   // 11x11 window, 3 levels, (COUNT+EPS, 30, 0.01), OPTFLOW_USE_INITIAL_FLOW: next_pts holds the guesses going in.
   // `temporal` marks the frame-to-frame call (the implementation may keep the previous frame's pyramid).

@@ -22,6 +22,31 @@ struct Stopwatch {
 
 }  // namespace
 
+DenseConfig::DenseConfig(const Setting& cfg)
+{
+  ssx_dense_default_params(&prm);
+  open = cfg.Get<int>("Dense.Open") != 0;
+  const struct { const char* key; int32_t* v; } keys[] = {{"Dense.Disparities", &prm.disparities}, {"Dense.P1", &prm.p1}, {"Dense.P2", &prm.p2},
+                                                          {"Dense.Uniqueness", &prm.uniqueness}, {"Dense.LR.Tolerance", &prm.lr_tolerance}, {"Dense.Paths", &prm.paths}};
+  for (const auto& k : keys)
+    if (cfg.Has(k.key)) *k.v = cfg.Get<int>(k.key);
+  if (cfg.Has("Dense.Cloud.Stride")) cloud_stride = cfg.Get<int>("Dense.Cloud.Stride");
+  if (cfg.Has("Dense.Cloud.Max.Depth")) cloud_max_depth = cfg.Get<double>("Dense.Cloud.Max.Depth");
+  if (open && cloud_stride < 1) throw std::runtime_error("Dense.Cloud.Stride must be at least 1");
+}
+
+void SampleDense(const std::vector<int16_t>& disp, const Image& left, int stride, double bf, double max_depth, std::vector<DenseSample>& out)
+{
+  out.clear();
+  for (int v = 0; v < left.rows; v += stride)
+    for (int u = 0; u < left.cols; u += stride) {
+      const int16_t d = disp[(size_t)v * left.cols + u];
+      if (d <= 0) continue;                                            // (-16: invalid; a valid pixel is at least 16 * 1 - 8)
+      const double z = bf * 16.0 / (double)d;
+      if (z <= max_depth) out.push_back(DenseSample{(uint16_t)u, (uint16_t)v, d, left.data[(size_t)v * left.cols + u]});
+    }
+}
+
 void Camera::world2pixel(const double* p_w, const SE3& T_c_w, float* uv) const
 {
   double pc[3], pr[3];
@@ -52,6 +77,9 @@ FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> ma
     throw std::runtime_error("FrontEnd: Camera.Rectify != 0 is not supported by this Compute (rectified input only; there is no CPU fallback)");
   if (need_rectify_ && !rectify) throw std::runtime_error("FrontEnd: Camera.Rectify != 0 without the two lenses' rectification parameters");
   if (need_rectify_) { rectify_[0] = rectify[0]; rectify_[1] = rectify[1]; }
+  dense_ = DenseConfig(cfg);
+  if (dense_.open && !compute.CanDense())
+    throw std::runtime_error("FrontEnd: Dense.Open != 0 is not supported by this Compute (it has no dense stereo; there is no CPU fallback)");
   if (left.fx != right.fx || left.fy != right.fy || left.cx != right.cx || left.cy != right.cy)
     throw std::runtime_error("FrontEnd: the two cameras must share their intrinsics (rectified stereo rig)");
   // System::GenerateORBextractor (system.cpp:115-128): nNewFeatures for keyframes, nInitFeatures for initialisation
@@ -399,6 +427,13 @@ bool FrontEnd::InsertKeyFrame()
     kf->pose = current_frame_->relative_pose_to_kf * reference_kf_->pose;
     kf->last_key_frame = (long)reference_kf_->key_frame_id;
     kf->relative_pose_to_last_kf = current_frame_->relative_pose_to_kf;
+  }
+  if (dense_.open) {                                                   // while both images are at hand; nothing below looks at the result
+    Stopwatch sw(times_.dense, times_.n_dense);
+    const Image& left = *current_frame_->left_image;
+    compute_.DenseDisparity(left, *current_frame_->right_image, dense_.prm, dense_disp_);
+    SampleDense(dense_disp_, left, dense_.cloud_stride, left_camera_.fx * right_camera_.baseline, dense_.cloud_max_depth, kf->dense_samples);
+    if (dense_sink_) dense_sink_(kf->key_frame_id, dense_disp_, left.rows, left.cols);
   }
   if (backend_) {
     Stopwatch sw(times_.bundle_adjust, times_.n_bundle_adjust);

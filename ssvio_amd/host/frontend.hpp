@@ -9,8 +9,11 @@
 // Compute that cannot undistort (the CPU oracle of the tests) is refused at construction.
 // Camera.Rectify != 0 (no reference behaviour): the raw pair of a frame is replaced by Compute::RectifyPair's, in the place and
 // under the rules of undistortion; the two keys together are refused.
+// Dense.Open != 0 (no reference behaviour): InsertKeyFrame hands the keyframe's pair to Compute::DenseDisparity while both images are
+// at hand, keeps the cloud's samples on the keyframe and shows the full map to the sink, if there is one; nothing else looks at it.
 // Not carried over: the viewer hooks (Pangolin), cv::imshow debugging, and the mutexes -- the headless runner is single-threaded.
 #pragma once
+#include <functional>
 #include <memory>
 #include <vector>
 
@@ -32,9 +35,23 @@ class LoopClosing;
 enum class FrontendStatus { INITING, TRACKING_GOOD, TRACKING_BAD, LOST };
 
 struct StageTimes {                                   // wall-clock seconds spent inside the compute calls
-  double detect = 0, lk_temporal = 0, lk_stereo = 0, pose_only = 0, triangulate = 0, bundle_adjust = 0, undistort = 0;
-  long n_detect = 0, n_lk_temporal = 0, n_lk_stereo = 0, n_pose_only = 0, n_triangulate = 0, n_bundle_adjust = 0, n_undistort = 0;
+  double detect = 0, lk_temporal = 0, lk_stereo = 0, pose_only = 0, triangulate = 0, bundle_adjust = 0, undistort = 0, dense = 0;
+  long n_detect = 0, n_lk_temporal = 0, n_lk_stereo = 0, n_pose_only = 0, n_triangulate = 0, n_bundle_adjust = 0, n_undistort = 0, n_dense = 0;
 };
+
+// Dense.* of the settings.  Every key is absent by default: Dense.Open is off, the matcher's parameters are ssx_dense_default_params',
+// the cloud takes every 4th pixel of every 4th row up to 40 m.
+struct DenseConfig {
+  bool open = false;
+  ssx_dense_params prm{};
+  int cloud_stride = 4;
+  double cloud_max_depth = 40.0;
+  explicit DenseConfig(const Setting& cfg);
+  DenseConfig() { ssx_dense_default_params(&prm); }
+};
+
+// the samples a keyframe keeps of its map: every stride-th pixel of every stride-th row with disp16 > 0 and bf * 16 / disp16 <= max_depth (f64)
+void SampleDense(const std::vector<int16_t>& disp, const Image& left, int stride, double bf, double max_depth, std::vector<DenseSample>& out);
 
 class FrontEnd {
  public:
@@ -55,6 +72,10 @@ class FrontEnd {
   const FramePtr& current_frame() const { return current_frame_; }
   const KeyFramePtr& reference_kf() const { return reference_kf_; }
   StageTimes& times() { return times_; }
+  const DenseConfig& dense() const { return dense_; }
+  // Dense.Open: called with every keyframe's full map (rows x cols int16) at insertion; the map is not kept after the call
+  using DenseSink = std::function<void(unsigned long key_frame_id, const std::vector<int16_t>& disp, int rows, int cols)>;
+  void SetDenseSink(DenseSink sink) { dense_sink_ = std::move(sink); }
 
  private:
   bool SteroInit();
@@ -90,6 +111,9 @@ class FrontEnd {
   ssx_lens_params rectify_[2] = {};          // left, right
   std::vector<int32_t> boxes_;               // DetectFeatures: the mask's rectangles (x0, y0, x1, y1)
   std::vector<unsigned long> condemned_;     // EstimateCurrentPose: the map points this frame condemned (taken back when it ends LOST and relocalisation is on)
+  DenseConfig dense_;                        // Dense.*
+  std::vector<int16_t> dense_disp_;          // the last keyframe's map (reused)
+  DenseSink dense_sink_;
   StageTimes times_;
 };
 

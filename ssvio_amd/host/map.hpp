@@ -57,6 +57,8 @@ struct Frame {
 };
 using FramePtr = std::shared_ptr<Frame>;
 
+struct DenseSample { uint16_t u, v; int16_t disp16; uint8_t intensity; };   // pixel, disparity in 1/16 pixel, the left image's byte
+
 struct KeyFrame {
   unsigned long key_frame_id = 0, frame_id = 0;
   double timestamp = 0;
@@ -70,6 +72,9 @@ struct KeyFrame {
   ImagePtr left_image;
   long loop_key_frame = -1;
   SE3 relative_pose_to_loop_kf;
+  // Dense.Open: what the dense cloud needs of the keyframe's disparity map and nothing more (a KITTI-size map is 0.93 MB and a run has
+  // thousands of keyframes) -- the pixels of every Dense.Cloud.Stride-th row and column that are valid and within Dense.Cloud.Max.Depth
+  std::vector<DenseSample> dense_samples;
 };
 using KeyFramePtr = std::shared_ptr<KeyFrame>;
 

@@ -4,6 +4,7 @@
 //
 //   ssx_run_kitti --config_yaml_path=cfg.yaml --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=out.txt]
 //                 [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--undistort_batched=0] [--warmup=1] [--loop_log=FILE]
+//                 [--dense_dir=DIR] [--dense_ply=FILE]
 // The PNG pairs are decoded ahead of the tracker on worker threads (StereoPrefetcher); everything else is the
 // reference's single loop.  --streams=K runs K independent copies of the loop in K threads of this process (each with
 // its own System, GPU contexts and prefetcher) on the same sequence: a single stream is latency-bound, several fill the
@@ -35,6 +36,10 @@
 // Loop closing is per stream.  --batched >= 1 with Loop.Closing.Open: 1 is refused unless --loop_batched=1 is given: the streams of a cohort
 // then share one loop context and one vocabulary, and their inline keyframe steps go to the GPU as ssx_kfdb_process_keyframe_batch calls
 // (every stream still writes the bytes of its single-stream run).  The loop thread (Loop.Closing.Async: 1) is not batched: refused with it.
+// Dense.Open: 1: every keyframe's pair goes through ssx_stereo_dense at insertion.  --dense_dir=DIR writes each keyframe's full map
+// then, as DIR/kf_%06ld.disp16 by keyframe id: raw little-endian int16, rows x cols, 1/16 pixel, -16 = invalid.  --dense_ply=FILE writes the
+// run's dense cloud at the end (System::SaveDenseCloud).  Stream k of --streams writes DIR.k and FILE.k; the directories must exist.
+// --batched >= 1 with the key set is refused: the dispatcher has no dense request kind.
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -63,6 +68,20 @@ bool flag(const char* arg, const char* name, std::string& out)
   return true;
 }
 
+// --dense_dir: each keyframe's map leaves for its file when the front-end shows it
+void AttachDenseDir(ssx::host::System& sys, const std::string& dir)
+{
+  if (dir.empty() || !sys.frontend().dense().open) return;
+  sys.frontend().SetDenseSink([dir](unsigned long kf_id, const std::vector<int16_t>& disp, int rows, int cols) {
+    char name[32];
+    std::snprintf(name, sizeof name, "/kf_%06ld.disp16", (long)kf_id);
+    std::FILE* f = std::fopen((dir + name).c_str(), "wb");
+    if (!f) throw std::runtime_error("--dense_dir: cannot write " + dir + name);
+    const size_t n = (size_t)rows * cols, put = std::fwrite(disp.data(), sizeof(int16_t), n, f);
+    if (std::fclose(f) != 0 || put != n) throw std::runtime_error("--dense_dir: writing " + dir + name + " failed");
+  });
+}
+
 void WriteLoopLog(ssx::host::System& sys, const std::string& path)
 {
   if (path.empty() || !sys.loop_closing()) return;
@@ -89,17 +108,17 @@ void WriteLoopLog(ssx::host::System& sys, const std::string& path)
 
 int main(int argc, char** argv)
 {
-  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log, loop_batched_s, undistort_batched_s;
+  std::string config, dataset, max_frames_s, trajectory, device_s, threads_s, streams_s, preload_s, batched_s, warmup_s, loop_log, loop_batched_s, undistort_batched_s, dense_dir, dense_ply;
   for (int i = 1; i < argc; ++i) {
     if (flag(argv[i], "config_yaml_path", config) || flag(argv[i], "kitti_dataset_path", dataset) || flag(argv[i], "max_frames", max_frames_s) ||
         flag(argv[i], "trajectory", trajectory) || flag(argv[i], "device", device_s) || flag(argv[i], "decode_threads", threads_s) || flag(argv[i], "streams", streams_s) || flag(argv[i], "preload", preload_s) || flag(argv[i], "batched", batched_s) || flag(argv[i], "warmup", warmup_s) || flag(argv[i], "loop_log", loop_log) || flag(argv[i], "loop_batched", loop_batched_s) ||
-        flag(argv[i], "undistort_batched", undistort_batched_s))
+        flag(argv[i], "undistort_batched", undistort_batched_s) || flag(argv[i], "dense_dir", dense_dir) || flag(argv[i], "dense_ply", dense_ply))
       continue;
     std::fprintf(stderr, "unknown argument %s\n", argv[i]);
     return 2;
   }
   if (config.empty() || dataset.empty()) {
-    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--undistort_batched=0] [--warmup=1] [--loop_log=<file>]\n",
+    std::fprintf(stderr, "usage: %s --config_yaml_path=<yaml> --kitti_dataset_path=<sequence dir> [--max_frames=N] [--trajectory=<tum file>] [--device=0] [--decode_threads=8] [--streams=1] [--preload=0] [--batched=0] [--loop_batched=0] [--undistort_batched=0] [--warmup=1] [--loop_log=<file>] [--dense_dir=<dir>] [--dense_ply=<file>]\n",
                  argv[0]);
     return 2;
   }
@@ -134,6 +153,11 @@ int main(int argc, char** argv)
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Guided.Open") != 0) {
       std::fprintf(stderr, "--batched=%s with Relocalization.Guided.Open: 1 is not supported (the dispatcher of a batched cohort has no guided search); "
                    "run --streams unbatched, or switch the guided search off\n", batched_s.c_str());
+      return 2;
+    }
+    if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Dense.Open") != 0) {
+      std::fprintf(stderr, "--batched=%s with Dense.Open: 1 is not supported (the dispatcher of a batched cohort has no dense request kind); "
+                   "run --streams unbatched, or switch dense stereo off\n", batched_s.c_str());
       return 2;
     }
     if (!batched_s.empty() && std::atoi(batched_s.c_str()) > 0 && Setting(config).Get<int>("Relocalization.Open") != 0 && !loop_batched) {
@@ -215,6 +239,7 @@ int main(int argc, char** argv)
             const size_t num_images = sq.num_images;
             frames[k] = num_images;
             System sys(config, batcher ? batcher->MakeCompute(k) : nullptr, device);
+            AttachDenseDir(sys, dense_dir.empty() ? dense_dir : dense_dir + "." + std::to_string(k));
             std::unique_ptr<StereoPrefetcher> pf;
             if (sq.preloaded.empty()) pf = std::make_unique<StereoPrefetcher>(sq.left_paths, sq.right_paths, num_images, dthreads);
             StereoPrefetcher::Pair first;
@@ -238,6 +263,7 @@ int main(int argc, char** argv)
             if (batcher) batcher->Finish(k);                                  // before the trajectory is written and the System is torn down
             if (!trajectory.empty()) sys.SaveTrajectoryTUM(trajectory + "." + std::to_string(k));
             if (!loop_log.empty()) WriteLoopLog(sys, loop_log + "." + std::to_string(k));
+            if (!dense_ply.empty() && sys.frontend().dense().open) sys.SaveDenseCloud(dense_ply + "." + std::to_string(k));
           } catch (const std::exception& e) {
             errors[k] = e.what();
             arrive();
@@ -282,6 +308,7 @@ int main(int argc, char** argv)
       return 0;
     }
     System system(config, nullptr, device_s.empty() ? 0 : std::atoi(device_s.c_str()));
+    AttachDenseDir(system, dense_dir);
     double t_io = 0, t_step = 0;
     StereoPrefetcher prefetch(left_paths, right_paths, num_images, threads_s.empty() ? 8 : std::atoi(threads_s.c_str()));
     StereoPrefetcher::Pair first;
@@ -309,6 +336,8 @@ int main(int argc, char** argv)
     }
     system.SaveTrajectoryTUM(trajectory);
     WriteLoopLog(system, loop_log);
+    if (!dense_ply.empty() && system.frontend().dense().open)
+      std::printf("dense cloud: %zu points in %s\n", system.SaveDenseCloud(dense_ply), dense_ply.c_str());
 
     const StageTimes& st = system.frontend().times();
     const Backend::Stats& bs = system.backend().stats();
@@ -328,6 +357,7 @@ int main(int argc, char** argv)
     line("LK left -> right", st.lk_stereo, st.n_lk_stereo);
     line("pose-only LM", st.pose_only, st.n_pose_only);
     line("triangulation", st.triangulate, st.n_triangulate);
+    line("dense (keyframe pair)", st.dense, st.n_dense);
     line("keyframe insert + BA", st.bundle_adjust, st.n_bundle_adjust);
     std::printf("  local BA: %ld windows, %ld LM iterations, %ld edges, %ld outlier edges\n", bs.windows, bs.lm_iterations, bs.edges, bs.outlier_edges);
     if (bs.windows)

@@ -204,6 +204,17 @@ class SsxCompute final : public Compute {
     frame_.check(ssx_undistort_lens(frame_.get(), 2, jobs, left.rows, left.cols, 0));
   }
 
+  bool CanDense() const override { return true; }
+
+  // a keyframe's pair in one ssx_stereo_dense call on the per-frame context
+  void DenseDisparity(const Image& left, const Image& right, const ssx_dense_params& prm, std::vector<int16_t>& disp) override
+  {
+    if (left.rows != right.rows || left.cols != right.cols) throw std::invalid_argument("DenseDisparity: left / right image sizes differ");
+    disp.resize((size_t)left.rows * left.cols);
+    const ssx_dense_job job = {left.ptr(), left.cols, right.ptr(), right.cols, disp.data(), left.cols};
+    frame_.check(ssx_stereo_dense(frame_.get(), 1, &job, left.rows, left.cols, &prm, 0));
+  }
+
   void TrackLK(const Image& prev, const Image& next, const std::vector<float>& prev_pts, std::vector<float>& next_pts,
                std::vector<uint8_t>& status, bool temporal) override
   {

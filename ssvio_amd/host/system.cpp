@@ -167,6 +167,10 @@ void System::Warmup(int rows, int cols)
     Image ul, ur;
     compute_->RectifyPair(*L0, *R0, rectified_.cam, ul, ur);
   }
+  if (frontend_->dense().open) {                                       // the keyframe's call: its kernels loaded, its volume allocated
+    std::vector<int16_t> disp;
+    compute_->DenseDisparity(*L0, *R0, frontend_->dense().prm, disp);
+  }
   ssx_orb_params prm{};
   prm.nfeatures = std::max(setting_.Get<int>("ORBextractor.nInitFeatures"), setting_.Get<int>("ORBextractor.nNewFeatures"));
   prm.scale_factor = setting_.Get<float>("ORBextractor.scaleFactor"); prm.nlevels = setting_.Get<int>("ORBextractor.nLevels");
@@ -243,6 +247,39 @@ void System::Warmup(int rows, int cols)
     std::memcpy(prob.K, K4, sizeof(K4)); std::memcpy(prob.cam_ext, ext, sizeof(ext));
     compute_->BundleAdjust(prob, opt, res);
   }
+}
+
+size_t System::SaveDenseCloud(const std::string& path) const
+{
+  backend_->WaitIdle();
+  if (loop_closing_) loop_closing_->WaitIdle();
+  std::lock_guard<std::mutex> map_lock(map_->update_mutex);
+  std::map<unsigned long, KeyFramePtr> ordered(map_->GetAllKeyFrames().begin(), map_->GetAllKeyFrames().end());
+  size_t n = 0;
+  for (auto& kv : ordered) n += kv.second->dense_samples.size();
+  std::ofstream out(path, std::ios_base::out | std::ios_base::trunc | std::ios_base::binary);
+  if (!out.is_open()) throw std::runtime_error("SaveDenseCloud: cannot write " + path);
+  out << "ply\nformat binary_little_endian 1.0\nelement vertex " << n << "\nproperty float x\nproperty float y\nproperty float z\nproperty uchar intensity\nend_header\n";
+  const double fx = left_camera_.fx, fy = left_camera_.fy, cx = left_camera_.cx, cy = left_camera_.cy, bf = left_camera_.fx * right_camera_.baseline;
+  std::vector<char> rows;
+  for (auto& kv : ordered) {
+    const SE3 T_wc = kv.second->pose.inverse();
+    rows.resize(13 * kv.second->dense_samples.size());
+    char* w = rows.data();
+    for (const DenseSample& s : kv.second->dense_samples) {
+      const double z = bf * 16.0 / (double)s.disp16;
+      const double Xc[3] = {((double)s.u - cx) * z / fx, ((double)s.v - cy) * z / fy, z};
+      double Xw[3];
+      T_wc.act(Xc, Xw);
+      const float f[3] = {(float)Xw[0], (float)Xw[1], (float)Xw[2]};
+      std::memcpy(w, f, 12);                                           // (little-endian host, as everywhere in this layer)
+      w[12] = (char)s.intensity;
+      w += 13;
+    }
+    out.write(rows.data(), (std::streamsize)rows.size());
+  }
+  if (!out.good()) throw std::runtime_error("SaveDenseCloud: writing " + path + " failed");
+  return n;
 }
 
 void System::SaveTrajectoryTUM(const std::string& path_in) const

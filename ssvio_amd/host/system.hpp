@@ -40,6 +40,11 @@ class System {
   // Touches neither the map nor the tracker; a run with and without it writes the same trajectory.
   void Warmup(int rows, int cols);
   void SaveTrajectoryTUM(const std::string& path = std::string()) const;   // empty: Trajectory.Save.Path of the settings
+  // Dense.Open: the dense cloud of the run as one binary little-endian PLY (x y z float, intensity uchar), every keyframe in id order
+  // and its samples in row order.  Per sample in f64: z = bf * 16 / disp16 with bf = fx * baseline, Xc = ((u - cx) z / fx, (v - cy) z / fy,
+  // z), Xw = T_wc Xc with the keyframe's pose as it is NOW (after BA and any loop correction), then cast to float.  Under
+  // Camera.Rectify this is the rectified left frame, as the trajectory is.  Returns the number of points written.
+  size_t SaveDenseCloud(const std::string& path) const;
 
   const Setting& setting() const { return setting_; }
   Map& map() { return *map_; }
