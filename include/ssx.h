@@ -720,6 +720,39 @@ typedef struct { const uint8_t* left; int32_t left_stride; const uint8_t* right;
 SSX_API void ssx_dense_default_params(ssx_dense_params* p); /* 128, 7, 86, 10, 1, 8 */
 SSX_API ssx_status ssx_stereo_dense(ssx_ctx* ctx, int32_t n, const ssx_dense_job* jobs, int32_t rows, int32_t cols,
                                     const ssx_dense_params* prm, int32_t images_on_device);
+/* What follows a disparity map: the speckle filter and the samples a keyframe keeps.  The contract is tools/dense_post_model.py
+ * (DESIGN.md 6p), integers only, bit for bit.  A pixel is valid iff its value is > 0.  Two 4-neighbours are joined iff both are valid
+ * and differ by at most speckle_range (1/16 pixel; row ends and the maps of two jobs are no neighbours); every valid pixel whose
+ * connected component has at most speckle_size pixels becomes -16 (the rule of cv::filterSpeckles with newVal = -16); speckle_size = 0:
+ * no filter.  cloud_stride > 0: every cloud_stride-th pixel of every cloud_stride-th row of the FILTERED map whose value is at least
+ * cloud_min_disp16 (ssx_dense_min_disp16: the depth bar z = bf * 16 / disp16 <= max_depth as one integer) is written as an
+ * ssx_dense_sample, in raster order.
+ * clouds: a host array of n, null if and only if cloud_stride == 0.  samples: host memory, or with on_device device / pinned memory,
+ * 8-byte aligned; capacity at least ceil(rows / stride) * ceil(cols / stride), so nothing can overflow; count is written after the
+ * call's one synchronisation.
+ * ssx_dense_postprocess: the stage on the caller's maps -- jobs[k].disp is read and written in place, left is needed only with
+ * cloud_stride > 0, right is ignored.  ssx_stereo_dense_post: the launches of ssx_stereo_dense followed by the stage's on the same
+ * stream; jobs[k].disp may be null when clouds is given (then no map comes down).  With speckle_size = 0 and cloud_stride = 0 it
+ * writes the bytes of ssx_stereo_dense.  Per call ONE copy up, ONE copy down (its size a function of the shapes and the settings: the
+ * counts travel with the samples) and ONE synchronisation; per group at most six launches more (four for the filter, two for the
+ * samples), whatever the image size or content.  Labels and sizes (8 bytes a pixel) take the place of the census words in the chained
+ * call; the stand-alone call carves them from the same workspace under SSX_DENSE_WORKSPACE_CAP.
+ * SSX_ERR_INVALID_ARG with a message before anything is touched: the refusals of ssx_stereo_dense, a field of post out of range, a
+ * non-zero `reserved`, clouds given or missing against cloud_stride, null samples, a capacity too small.  SSX_ERR_HIP with a message
+ * if a labelling loop ever passed its bound (derived from the pixel count; not reachable by a map). */
+typedef struct { int32_t speckle_size;      /* 0 = no filter; 0 .. rows * cols */
+                 int32_t speckle_range;     /* 1/16 pixel, 0 .. 32767 */
+                 int32_t cloud_stride;      /* 0 = no samples; else 1 .. 4000 */
+                 int32_t cloud_min_disp16;  /* 1 .. 32768 */
+                 int32_t reserved[4]; } ssx_dense_post;                       /* 32 bytes, reserved must be 0 */
+typedef struct { uint16_t u, v; int16_t disp16; uint8_t intensity, reserved; } ssx_dense_sample;   /* 8 bytes */
+typedef struct { ssx_dense_sample* samples; int32_t capacity; int32_t count; /* out */ } ssx_dense_cloud;  /* 16 bytes */
+SSX_API void ssx_dense_default_post(ssx_dense_post* p); /* 0, 16, 0, 1: everything off; null is no fault */
+SSX_API int32_t ssx_dense_min_disp16(double bf, double max_depth); /* host code: the smallest d in 1 .. 32767 with bf * 16 / d <= max_depth (f64), else 32768 */
+SSX_API ssx_status ssx_dense_postprocess(ssx_ctx* ctx, int32_t n, const ssx_dense_job* jobs, ssx_dense_cloud* clouds, int32_t rows, int32_t cols,
+                                         const ssx_dense_post* post, int32_t on_device);
+SSX_API ssx_status ssx_stereo_dense_post(ssx_ctx* ctx, int32_t n, const ssx_dense_job* jobs, ssx_dense_cloud* clouds, int32_t rows, int32_t cols,
+                                         const ssx_dense_params* prm, const ssx_dense_post* post, int32_t images_on_device);
 /* Raw stereo rigs: lens models and rectification.  The contract is tools/rectify_model.py.
  * A lens is SSX_LENS_RADTAN -- coeffs = k1 k2 p1 p2 k3, the map of ssx_undistort, whose entry points are this case -- or SSX_LENS_KB4,
  * Kannala-Brandt "equidistant" with coeffs = k1 k2 k3 k4 (coeffs[4] is ignored): theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8),

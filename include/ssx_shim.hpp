@@ -288,6 +288,40 @@ inline void DenseDisparity(Context& ctx, const uint8_t* left, int leftStep, cons
   ctx.check(ssx_stereo_dense(ctx.get(), 1, &job, rows, cols, prm ? prm : &def, imagesOnDevice ? 1 : 0));
 }
 
+// ssx_stereo_dense_post for one rectified pair of host images: the map of DenseDisparity, the speckle filter, and with
+// post.cloud_stride > 0 the samples of the filtered map in raster order (the bits of tools/dense_post_model.py).  disp may be null
+// when samples are asked for: then no map comes down.  samples: null iff post.cloud_stride == 0; resized to what was found.
+inline void DenseDisparity(Context& ctx, const uint8_t* left, int leftStep, const uint8_t* right, int rightStep, int16_t* disp, int dispStep, int rows,
+                           int cols, const ssx_dense_params& prm, const ssx_dense_post& post, std::vector<ssx_dense_sample>* samples)
+{
+  const ssx_dense_job job = {left, leftStep, right, rightStep, disp, dispStep};
+  ssx_dense_cloud cloud = {nullptr, 0, 0};
+  if (samples && post.cloud_stride > 0) {
+    const int s = post.cloud_stride;
+    samples->resize((size_t)((rows + s - 1) / s) * (size_t)((cols + s - 1) / s));
+    cloud.samples = samples->data();
+    cloud.capacity = (int32_t)samples->size();
+  }
+  ctx.check(ssx_stereo_dense_post(ctx.get(), 1, &job, samples ? &cloud : nullptr, rows, cols, &prm, &post, 0));
+  if (samples) samples->resize((size_t)cloud.count);
+}
+
+// ssx_dense_postprocess on one host map, filtered in place; left is needed only with post.cloud_stride > 0 (samples as above)
+inline void DensePostprocess(Context& ctx, int16_t* disp, int dispStep, const uint8_t* left, int leftStep, int rows, int cols, const ssx_dense_post& post,
+                             std::vector<ssx_dense_sample>* samples = nullptr)
+{
+  const ssx_dense_job job = {left, leftStep, nullptr, 0, disp, dispStep};
+  ssx_dense_cloud cloud = {nullptr, 0, 0};
+  if (samples && post.cloud_stride > 0) {
+    const int s = post.cloud_stride;
+    samples->resize((size_t)((rows + s - 1) / s) * (size_t)((cols + s - 1) / s));
+    cloud.samples = samples->data();
+    cloud.capacity = (int32_t)samples->size();
+  }
+  ctx.check(ssx_dense_postprocess(ctx.get(), 1, &job, samples ? &cloud : nullptr, rows, cols, &post, 0));
+  if (samples) samples->resize((size_t)cloud.count);
+}
+
 // Many streams' frames in one call (ssx_undistort_plan_*): the plan keeps one stored map per camera it was shown (Add: equal parameter
 // bytes -> the index they have) for ONE image size, and Apply undistorts n images, each naming its map, in one launch -- the bytes
 // of Camera::UndistortImage.  Destroy the plan before its Context.

@@ -259,6 +259,12 @@ SSX_API ssx_status ssx_dense_debug_last_call(ssx_ctx* ctx, int32_t* launches, in
 SSX_API ssx_status ssx_dense_debug_stages(ssx_ctx* ctx, const uint8_t* left, int32_t left_stride, const uint8_t* right, int32_t right_stride,
                                           int32_t rows, int32_t cols, const ssx_dense_params* prm, int32_t direction, uint64_t* census_left,
                                           uint64_t* census_right, uint8_t* path_volume, uint16_t* sum_volume, uint8_t* right_disparity);
+/* the connected components of ONE host map (rows x cols int16 at a pitch of disp_stride elements) through the labelling kernels of
+ * ssx_dense_postprocess, as tools/dense_post_model.py's components() names them: per pixel the size of its component and its root
+ * (the smallest raster index y * cols + x), 0 and -1 where the pixel is not valid.  Either output may be NULL.
+ * ssx_dense_debug_last_call (above) counts ssx_dense_postprocess and ssx_stereo_dense_post as it counts ssx_stereo_dense. */
+SSX_API ssx_status ssx_dense_debug_components(ssx_ctx* ctx, const int16_t* disp, int32_t disp_stride, int32_t rows, int32_t cols, int32_t speckle_range,
+                                              int32_t* size, int32_t* root);
 
 #ifdef __cplusplus
 }

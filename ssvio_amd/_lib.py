@@ -248,6 +248,22 @@ class DenseJob(C.Structure):
                 ("disp", C.c_void_p), ("disp_stride", C.c_int32)]
 
 
+class DensePostC(C.Structure):
+    """ssx_dense_post"""
+    _fields_ = [("speckle_size", C.c_int32), ("speckle_range", C.c_int32), ("cloud_stride", C.c_int32), ("cloud_min_disp16", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class DenseSample(C.Structure):
+    """ssx_dense_sample"""
+    _fields_ = [("u", C.c_uint16), ("v", C.c_uint16), ("disp16", C.c_int16), ("intensity", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class DenseCloud(C.Structure):
+    """ssx_dense_cloud: count is written by the call"""
+    _fields_ = [("samples", C.c_void_p), ("capacity", C.c_int32), ("count", C.c_int32)]
+
+
 SSX_DENSE_MAX_JOBS = 1024
 SSX_DENSE_WORKSPACE_CAP = 1 << 30
 

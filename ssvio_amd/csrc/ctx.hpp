@@ -103,7 +103,8 @@ enum SsxKernelId {
   KID_ORB_MISC, KID_ST_BUCKET, KID_ST_MATCH, KID_ST_TRIANGULATE, KID_ST_MISC, KID_POSE_ONLY, KID_BA_COMM, KID_BA_LIN_SCHUR,
   KID_LOOP_SCORE, KID_LOOP_MATCH, KID_LOOP_PAIRS, KID_PNP_RANSAC, KID_LOOP_COMPACT, KID_LOOP_WORDS, KID_LOOP_BOW, KID_LOOP_COMMIT,
   KID_LC_KEYFRAMES, KID_LC_REANCHOR, KID_WIN_ANCHOR, KID_LOOP_TOPK, KID_LOOP_GUIDED, KID_UNDISTORT, KID_UNDISTORT_MAP,
-  KID_UNDISTORT_REMAP, KID_DENSE_CENSUS, KID_DENSE_PATHS, KID_DENSE_RIGHT, KID_DENSE_SELECT, KID_COUNT
+  KID_UNDISTORT_REMAP, KID_DENSE_CENSUS, KID_DENSE_PATHS, KID_DENSE_RIGHT, KID_DENSE_SELECT,
+  KID_DENSE_LABEL_TILE, KID_DENSE_LABEL_MERGE, KID_DENSE_LABEL_COUNT, KID_DENSE_SPECKLE, KID_DENSE_SAMPLE_ROWS, KID_DENSE_SAMPLE_WRITE, KID_COUNT
 };
 static const char* const kSsxKernelNames[KID_COUNT] = {
   "k_linearize", "k_reduce_lin", "k_schur", "k_reduce_schur", "k_solve", "k_backsub_residual", "k_reduce_trial",
@@ -111,7 +112,8 @@ static const char* const kSsxKernelNames[KID_COUNT] = {
   "k_triangulate_matches", "stereo_misc", "k_pose_only", "ba_allreduce", "k_lin_schur",
   "k_kfdb_score", "kfdb_bf_match", "k_kfdb_pairs", "k_pnp_ransac", "k_kf_compact", "kf_voc_words", "k_kf_bow", "k_kfdb_commit",
   "k_lc_keyframes", "k_reanchor_points", "k_win_anchor", "k_kfdb_topk", "kfdb_guided", "k_undistort", "k_undistort_map",
-  "k_undistort_remap", "k_dense_census", "k_dense_paths", "k_dense_right", "k_dense_select"};
+  "k_undistort_remap", "k_dense_census", "k_dense_paths", "k_dense_right", "k_dense_select",
+  "k_dense_label_tile", "k_dense_label_merge", "k_dense_label_count", "k_dense_speckle", "k_dense_sample_rows", "k_dense_sample_write"};
 
 struct SsxProf {
   bool on = false;
@@ -175,7 +177,7 @@ struct ssx_ctx {
   KfChainStats undistort;                    // the last ssx_undistort (ssx_undistort_debug_last_call)
   DevBuf dn_arena, dn_work;                  // dense stereo (dense.hip): the job table and staged images / maps; census, volume and right keys of a group
   HostBuf dn_stage;
-  KfChainStats dense;                        // the last ssx_stereo_dense (ssx_dense_debug_last_call)
+  KfChainStats dense;                        // the last ssx_stereo_dense / ssx_stereo_dense_post / ssx_dense_postprocess (ssx_dense_debug_last_call)
   int32_t dense_groups = 0;
 
   std::mutex err_mu;                         // worker threads of a batched call may report failures concurrently

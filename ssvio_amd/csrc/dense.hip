@@ -19,6 +19,9 @@
 // Workspace per job: 16 bytes of census, 2 D bytes of S and 4 bytes of right key per pixel.  A call works through its jobs in groups
 // whose workspace stays under SSX_DENSE_WORKSPACE_CAP (one pair always runs, whatever it takes); the images go up in one copy, the
 // maps come down in one copy, and the call synchronises once.
+//
+// What follows a map -- the speckle filter and the keyframe's samples, ssx_dense_postprocess and the chained ssx_stereo_dense_post -- is
+// dense_post.inc, included at the end of this file (contract: tools/dense_post_model.py).
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -541,3 +544,5 @@ ssx_status ssx_dense_debug_stages(ssx_ctx* ctx, const uint8_t* left, int32_t lef
 #endif
 
 }  // extern "C"
+
+#include "dense_post.inc"   // the speckle filter and the keyframe's samples: ssx_dense_postprocess, ssx_stereo_dense_post

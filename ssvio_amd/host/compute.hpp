@@ -143,6 +143,16 @@ class Compute {
     (void)left; (void)right; (void)prm; (void)disp;
     throw std::logic_error("Compute::DenseDisparity: this implementation has no dense stereo (Dense.Open)");
   }
+  // Dense.Speckle.Size / Dense.Cloud.OnDevice: the keyframe's whole dense step in one call (ssx_stereo_dense_post; the
+  // contract is tools/dense_post_model.py) -- the map of DenseDisparity, the speckle filter of post, and with post.cloud_stride > 0 the
+  // samples of the filtered map in raster order.  want_map = false (only with samples): no map comes down and disp is left empty.
+  virtual bool CanDensePost() const { return false; }
+  virtual void DenseKeyframe(const Image& left, const Image& right, const ssx_dense_params& prm, const ssx_dense_post& post, bool want_map,
+                             std::vector<int16_t>& disp, std::vector<ssx_dense_sample>& samples)
+  {
+    (void)left; (void)right; (void)prm; (void)post; (void)want_map; (void)disp; (void)samples;
+    throw std::logic_error("Compute::DenseKeyframe: this implementation has no speckle filter and no samples on the device (Dense.Speckle.Size, Dense.Cloud.OnDevice)");
+  }
   // 11x11 window, 3 levels, (COUNT+EPS, 30, 0.01), OPTFLOW_USE_INITIAL_FLOW: next_pts holds the guesses going in.
   // `temporal` marks the frame-to-frame call (the implementation may keep the previous frame's pyramid).
   virtual void TrackLK(const Image& prev, const Image& next, const std::vector<float>& prev_pts, std::vector<float>& next_pts,

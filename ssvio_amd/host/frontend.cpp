@@ -3,6 +3,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <stdexcept>
 #include <string>
@@ -33,7 +34,28 @@ DenseConfig::DenseConfig(const Setting& cfg)
   if (cfg.Has("Dense.Cloud.Stride")) cloud_stride = cfg.Get<int>("Dense.Cloud.Stride");
   if (cfg.Has("Dense.Cloud.Max.Depth")) cloud_max_depth = cfg.Get<double>("Dense.Cloud.Max.Depth");
   if (open && cloud_stride < 1) throw std::runtime_error("Dense.Cloud.Stride must be at least 1");
+  if (cfg.Has("Dense.Speckle.Size")) speckle_size = cfg.Get<int>("Dense.Speckle.Size");
+  if (cfg.Has("Dense.Speckle.Range")) speckle_range = cfg.Get<int>("Dense.Speckle.Range");
+  if (cfg.Has("Dense.Cloud.OnDevice")) cloud_on_device = cfg.Get<int>("Dense.Cloud.OnDevice") != 0;
+  if (open && speckle_size < 0) throw std::runtime_error("Dense.Speckle.Size must be at least 0");
+  if (open && (speckle_range < 0 || speckle_range > 32767)) throw std::runtime_error("Dense.Speckle.Range must be in [0, 32767] (1/16 pixel)");
+  if (open && cloud_on_device && cloud_stride > 4000) throw std::runtime_error("Dense.Cloud.Stride must be at most 4000 with Dense.Cloud.OnDevice");
 }
+
+ssx_dense_post DenseConfig::PostFor(double bf) const
+{
+  ssx_dense_post post;
+  ssx_dense_default_post(&post);
+  post.speckle_size = speckle_size;
+  post.speckle_range = speckle_range;
+  post.cloud_stride = cloud_on_device ? cloud_stride : 0;
+  post.cloud_min_disp16 = ssx_dense_min_disp16(bf, cloud_max_depth);
+  return post;
+}
+
+static_assert(sizeof(DenseSample) == sizeof(ssx_dense_sample) && offsetof(DenseSample, u) == offsetof(ssx_dense_sample, u) && offsetof(DenseSample, v) == offsetof(ssx_dense_sample, v) &&
+              offsetof(DenseSample, disp16) == offsetof(ssx_dense_sample, disp16) && offsetof(DenseSample, intensity) == offsetof(ssx_dense_sample, intensity),
+              "a keyframe keeps the device's samples as they are");
 
 void SampleDense(const std::vector<int16_t>& disp, const Image& left, int stride, double bf, double max_depth, std::vector<DenseSample>& out)
 {
@@ -80,6 +102,9 @@ FrontEnd::FrontEnd(const Setting& cfg, Compute& compute, std::shared_ptr<Map> ma
   dense_ = DenseConfig(cfg);
   if (dense_.open && !compute.CanDense())
     throw std::runtime_error("FrontEnd: Dense.Open != 0 is not supported by this Compute (it has no dense stereo; there is no CPU fallback)");
+  if (dense_.use_post() && !compute.CanDensePost())
+    throw std::runtime_error(std::string("FrontEnd: ") + (dense_.speckle_size > 0 ? "Dense.Speckle.Size" : "Dense.Cloud.OnDevice") +
+                             " != 0 is not supported by this Compute (it has no speckle filter and no samples on the device; there is no CPU fallback)");
   if (left.fx != right.fx || left.fy != right.fy || left.cx != right.cx || left.cy != right.cy)
     throw std::runtime_error("FrontEnd: the two cameras must share their intrinsics (rectified stereo rig)");
   // System::GenerateORBextractor (system.cpp:115-128): nNewFeatures for keyframes, nInitFeatures for initialisation
@@ -431,8 +456,21 @@ bool FrontEnd::InsertKeyFrame()
   if (dense_.open) {                                                   // while both images are at hand; nothing below looks at the result
     Stopwatch sw(times_.dense, times_.n_dense);
     const Image& left = *current_frame_->left_image;
-    compute_.DenseDisparity(left, *current_frame_->right_image, dense_.prm, dense_disp_);
-    SampleDense(dense_disp_, left, dense_.cloud_stride, left_camera_.fx * right_camera_.baseline, dense_.cloud_max_depth, kf->dense_samples);
+    const double bf = left_camera_.fx * right_camera_.baseline;
+    if (!dense_.use_post()) {
+      compute_.DenseDisparity(left, *current_frame_->right_image, dense_.prm, dense_disp_);
+      SampleDense(dense_disp_, left, dense_.cloud_stride, bf, dense_.cloud_max_depth, kf->dense_samples);
+    } else {
+      // one call: the map, the filter and (Dense.Cloud.OnDevice) the samples; the full map comes down only for who looks at it
+      const bool want_map = !dense_.cloud_on_device || (bool)dense_sink_;
+      compute_.DenseKeyframe(left, *current_frame_->right_image, dense_.prm, dense_.PostFor(bf), want_map, dense_disp_, dense_smp_);
+      if (dense_.cloud_on_device) {
+        kf->dense_samples.resize(dense_smp_.size());
+        for (size_t i = 0; i < dense_smp_.size(); ++i) kf->dense_samples[i] = DenseSample{dense_smp_[i].u, dense_smp_[i].v, dense_smp_[i].disp16, dense_smp_[i].intensity};
+      } else {
+        SampleDense(dense_disp_, left, dense_.cloud_stride, bf, dense_.cloud_max_depth, kf->dense_samples);
+      }
+    }
     if (dense_sink_) dense_sink_(kf->key_frame_id, dense_disp_, left.rows, left.cols);
   }
   if (backend_) {

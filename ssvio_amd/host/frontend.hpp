@@ -11,6 +11,8 @@
 // under the rules of undistortion; the two keys together are refused.
 // Dense.Open != 0 (no reference behaviour): InsertKeyFrame hands the keyframe's pair to Compute::DenseDisparity while both images are
 // at hand, keeps the cloud's samples on the keyframe and shows the full map to the sink, if there is one; nothing else looks at it.
+// Dense.Speckle.Size / Dense.Cloud.OnDevice: one Compute::DenseKeyframe call instead; with the samples made on the device the
+// full map comes down only when a sink is attached.
 // Not carried over: the viewer hooks (Pangolin), cv::imshow debugging, and the mutexes -- the headless runner is single-threaded.
 #pragma once
 #include <functional>
@@ -41,13 +43,20 @@ struct StageTimes {                                   // wall-clock seconds spen
 
 // Dense.* of the settings.  Every key is absent by default: Dense.Open is off, the matcher's parameters are ssx_dense_default_params',
 // the cloud takes every 4th pixel of every 4th row up to 40 m.
+// Dense.Speckle.Size (0: no filter), Dense.Speckle.Range (16, in 1/16 pixel) and Dense.Cloud.OnDevice (0): with a filter or
+// the samples asked of the device, InsertKeyFrame makes ONE Compute::DenseKeyframe call in place of DenseDisparity; otherwise nothing changes.
 struct DenseConfig {
   bool open = false;
   ssx_dense_params prm{};
   int cloud_stride = 4;
   double cloud_max_depth = 40.0;
+  int speckle_size = 0, speckle_range = 16;
+  bool cloud_on_device = false;
   explicit DenseConfig(const Setting& cfg);
   DenseConfig() { ssx_dense_default_params(&prm); }
+  bool use_post() const { return open && (speckle_size > 0 || cloud_on_device); }
+  // what DenseKeyframe is asked: the filter, and with Dense.Cloud.OnDevice the stride and the depth bar as one integer (bf = fx * baseline)
+  ssx_dense_post PostFor(double bf) const;
 };
 
 // the samples a keyframe keeps of its map: every stride-th pixel of every stride-th row with disp16 > 0 and bf * 16 / disp16 <= max_depth (f64)
@@ -113,6 +122,7 @@ class FrontEnd {
   std::vector<unsigned long> condemned_;     // EstimateCurrentPose: the map points this frame condemned (taken back when it ends LOST and relocalisation is on)
   DenseConfig dense_;                        // Dense.*
   std::vector<int16_t> dense_disp_;          // the last keyframe's map (reused)
+  std::vector<ssx_dense_sample> dense_smp_;  // the last keyframe's samples as the device wrote them (reused)
   DenseSink dense_sink_;
   StageTimes times_;
 };

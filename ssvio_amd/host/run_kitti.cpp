@@ -40,6 +40,8 @@
 // then, as DIR/kf_%06ld.disp16 by keyframe id: raw little-endian int16, rows x cols, 1/16 pixel, -16 = invalid.  --dense_ply=FILE writes the
 // run's dense cloud at the end (System::SaveDenseCloud).  Stream k of --streams writes DIR.k and FILE.k; the directories must exist.
 // --batched >= 1 with the key set is refused: the dispatcher has no dense request kind.
+// Dense.Speckle.Size: N / Dense.Speckle.Range: R: components of at most N pixels leave every map (and the cloud).
+// Dense.Cloud.OnDevice: 1: the cloud's samples are made on the device; the full map then comes down only with --dense_dir.
 #include <chrono>
 #include <condition_variable>
 #include <mutex>

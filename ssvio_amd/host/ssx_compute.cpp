@@ -215,6 +215,24 @@ class SsxCompute final : public Compute {
     frame_.check(ssx_stereo_dense(frame_.get(), 1, &job, left.rows, left.cols, &prm, 0));
   }
 
+  bool CanDensePost() const override { return true; }
+
+  // a keyframe's pair, the filter and the samples in one ssx_stereo_dense_post call on the per-frame context
+  void DenseKeyframe(const Image& left, const Image& right, const ssx_dense_params& prm, const ssx_dense_post& post, bool want_map, std::vector<int16_t>& disp,
+                     std::vector<ssx_dense_sample>& samples) override
+  {
+    if (left.rows != right.rows || left.cols != right.cols) throw std::invalid_argument("DenseKeyframe: left / right image sizes differ");
+    const bool sampling = post.cloud_stride > 0;
+    if (!want_map && !sampling) throw std::invalid_argument("DenseKeyframe: neither the map nor samples are asked for");
+    disp.resize(want_map ? (size_t)left.rows * left.cols : 0);
+    const int s = sampling ? post.cloud_stride : 1;
+    samples.resize(sampling ? (size_t)((left.rows + s - 1) / s) * (size_t)((left.cols + s - 1) / s) : 0);
+    const ssx_dense_job job = {left.ptr(), left.cols, right.ptr(), right.cols, want_map ? disp.data() : nullptr, left.cols};
+    ssx_dense_cloud cloud = {samples.data(), (int32_t)samples.size(), 0};
+    frame_.check(ssx_stereo_dense_post(frame_.get(), 1, &job, sampling ? &cloud : nullptr, left.rows, left.cols, &prm, &post, 0));
+    samples.resize(sampling ? (size_t)cloud.count : 0);
+  }
+
   void TrackLK(const Image& prev, const Image& next, const std::vector<float>& prev_pts, std::vector<float>& next_pts,
                std::vector<uint8_t>& status, bool temporal) override
   {

@@ -169,7 +169,12 @@ void System::Warmup(int rows, int cols)
   }
   if (frontend_->dense().open) {                                       // the keyframe's call: its kernels loaded, its volume allocated
     std::vector<int16_t> disp;
-    compute_->DenseDisparity(*L0, *R0, frontend_->dense().prm, disp);
+    if (frontend_->dense().use_post()) {                               // (the call that will be used, asked as InsertKeyFrame asks it without a sink)
+      std::vector<ssx_dense_sample> smp;
+      compute_->DenseKeyframe(*L0, *R0, frontend_->dense().prm, frontend_->dense().PostFor(left_camera_.fx * right_camera_.baseline), !frontend_->dense().cloud_on_device, disp, smp);
+    } else {
+      compute_->DenseDisparity(*L0, *R0, frontend_->dense().prm, disp);
+    }
   }
   ssx_orb_params prm{};
   prm.nfeatures = std::max(setting_.Get<int>("ORBextractor.nInitFeatures"), setting_.Get<int>("ORBextractor.nNewFeatures"));

@@ -77,5 +77,40 @@ def main():
     print("\n".join(lines))
 
 
+def post():
+    """--post: the runner's phase `dense` (host images) with the samples made on the host or on the device, with and without the speckle
+    filter -> profiles/dense_post/drive.txt.  The same scene at KITTI size; the runs alternate, each repeated."""
+    import host_util as hu
+    from ssvio_amd import build as b
+    from tools import loop_drive, synth
+    _, new = b.build_host()
+    out = arg("out", os.path.join(ROOT, "profiles", "dense_post", "drive.txt"))
+    repeats = int(arg("repeats", "3"))
+    h, w, fx, n = 376, 1241, 718.856, 12
+    variants = {"Dense.Open: 1 (the map down, SampleDense on the host)": {},
+                "+ Dense.Cloud.OnDevice: 1 (samples down, no map)": {"Dense.Cloud.OnDevice": 1},
+                "+ Dense.Speckle.Size: 100 (filtered map down, host samples)": {"Dense.Speckle.Size": 100},
+                "+ both (samples of the filtered map down, no map)": {"Dense.Speckle.Size": 100, "Dense.Cloud.OnDevice": 1}}
+    lines = ["ssx_run_kitti's phase `dense` at %d x %d, %d frames, a keyframe on every frame, host images (tools/dense_drive.py --post):" % (h, w, n),
+             "ms per keyframe as the runner prints it, and RunStep frames per second; median [min - max] of %d alternating runs" % repeats]
+    with tempfile.TemporaryDirectory() as root:
+        seq = hu.write_sequence(os.path.join(root, "seq"), n_frames=n, step=0.25, seed=0, h=h, w=w)
+        drive = dict(K=(fx, fx, w / 2.0, h / 2.0), bf=synth.KITTI_BF)
+        for D in (64, 128):
+            base = {"Camera.width": w, "Camera.height": h, "Dense.Open": 1, "Dense.Disparities": D}
+            cfgs = {k: synth.write_settings(os.path.join(root, "v%d_%d.yaml" % (i, D)), loop_drive.drive_settings(drive, dict(base, **v))) for i, (k, v) in enumerate(variants.items())}
+            ms, fr, trajs = {k: [] for k in variants}, {k: [] for k in variants}, set()
+            for _ in range(repeats):
+                for k in variants:
+                    f, d, _, t = fps(new, cfgs[k], seq["dir"])
+                    ms[k].append(d); fr[k].append(f); trajs.add(t)
+            lines.append("  %d disparities; every run wrote the same trajectory bytes: %s" % (D, len(trajs) == 1))
+            for k in variants:
+                lines.append("    %-62s %7.3f ms [%.3f - %.3f]   %7.1f frames/s [%.1f - %.1f]" % (k, np.median(ms[k]), min(ms[k]), max(ms[k]), np.median(fr[k]), min(fr[k]), max(fr[k])))
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    open(out, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 if __name__ == "__main__":
-    main()
+    post() if "--post" in sys.argv[1:] else main()

@@ -153,7 +153,114 @@ def trace(lines, trace_dir):
             lines.append("    %-16s %9.1f us" % ("sum of medians", total))
 
 
+# ---- the speckle filter and the samples -> profiles/dense_post/time.txt ----
+#     python tools/dense_time.py --post [--parent-lib <libssx.so of the parent commit>] [--out profiles/dense_post/time.txt]
+# Each library is timed in fresh child processes of its own (this script with --post-child, the library named by SSX_LIB), parent and new
+# alternating, three children each: device events around warmed calls on one KITTI-size pair in device memory, and for the new library
+# the per-kernel times of the library's own profiler (HIP events around every launch: ssx_profile_begin / _end).
+POST_CONFIGS = [(64, 4), (128, 8)]
+POST_KERNELS = ["k_dense_label_tile", "k_dense_label_merge", "k_dense_label_count", "k_dense_speckle", "k_dense_sample_rows", "k_dense_sample_write"]
+
+
+def post_child():
+    import json
+
+    from ssvio_amd import _lib
+    from tools import synth
+    torch, dn, ctx, jobs, keep = _setup(1)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        a.record(); fn(); b.record(); torch.cuda.synchronize()
+        reps = min(max(10, int(np.ceil(300.0 / max(a.elapsed_time(b), 1e-3)))), 400)
+        per = []
+        for _ in range(3):
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record(); torch.cuda.synchronize()
+            per.append(a.elapsed_time(b) / reps)
+        return [float(np.median(per)), min(per), max(per), reps]
+
+    res = {}
+    has_post = hasattr(ctx.lib, "ssx_stereo_dense_post")
+    # ssx_stereo_dense bound here, the same way for both libraries: the parent's has none of the new symbols that ssvio_amd.dense binds
+    import ctypes as C
+    plain = ctx.lib.ssx_stereo_dense
+    plain.restype = C.c_int
+    plain.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_lib.DenseJob), C.c_int32, C.c_int32, C.POINTER(_lib.DenseParamsC), C.c_int32]
+    arr = (_lib.DenseJob * 1)(_lib.DenseJob(*jobs[0]))
+    for D, paths in POST_CONFIGS:
+        prm = dn.DenseParams(disparities=D, paths=paths)
+        res["ssx_stereo_dense %d %d" % (D, paths)] = timed(lambda: ctx.check(plain(ctx.handle, 1, arr, ROWS, COLS, C.byref(prm), 1)))
+        if not has_post:
+            continue
+        bar = dn.min_disp16(synth.KITTI_BF, 40.0)
+        posts = {"everything off": dn.DensePost(), "filter 100 / 16": dn.DensePost(100, 16), "filter + samples (stride 4)": dn.DensePost(100, 16, 4, bar),
+                 "samples only, no map asked for": dn.DensePost(0, 16, 4, bar)}
+        for name, post in posts.items():
+            buf = dn.samples_buffers(1, ROWS, COLS, post, device="cuda")[0] if post.cloud_stride > 0 else None
+            clouds = [(buf.data_ptr(), dn.sample_capacity(ROWS, COLS, post))] if buf is not None else None
+            jb = [(l, ls, r, rs, None, 0) for l, ls, r, rs, _, _ in jobs] if name.startswith("samples only") else jobs
+            res["ssx_stereo_dense_post %d %d %s" % (D, paths, name)] = timed(lambda: dn.dense_post_ptrs(ctx, jb, clouds, ROWS, COLS, prm, post, images_on_device=True))
+            if name.startswith("filter + samples"):
+                _lib.profile_begin(ctx)
+                for _ in range(20):
+                    counts = dn.dense_post_ptrs(ctx, jb, clouds, ROWS, COLS, prm, post, images_on_device=True)
+                t = _lib.profile_end(ctx)
+                res["kernels %d %d" % (D, paths)] = {k: [t[k][0], 1e3 * t[k][1] / max(t[k][0], 1)] for k in t if k.startswith("k_dense")}
+                res["samples %d %d" % (D, paths)] = counts[0]
+    ctx.close()
+    print("POSTJSON " + json.dumps(res))
+
+
+def post(out, parent_lib):
+    import json
+    new_lib = os.path.join(ROOT, "ssvio_amd", "libssx.so")
+    runs = {"parent": [], "new": []}
+    for _ in range(3):
+        for who, lib in (("parent", parent_lib), ("new", new_lib)):
+            if not lib:
+                continue
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--post-child"], capture_output=True, text=True, timeout=600, env=dict(os.environ, SSX_LIB=lib))
+            line = [l for l in r.stdout.splitlines() if l.startswith("POSTJSON ")]
+            if r.returncode != 0 or not line:
+                raise SystemExit("the %s child failed (rc %d):\n%s" % (who, r.returncode, (r.stdout + r.stderr)[-2000:]))
+            runs[who].append(json.loads(line[0][9:]))
+    lines = ["ssx_stereo_dense_post at %d x %d (tools/dense_time.py --post), alone on one MI355X: one pair, images, map and samples in device memory" % (ROWS, COLS),
+             "ms per call, median [min - max] over 3 fresh processes per library (parent and new alternating), each the median of 3 windows of ~0.3 s of warmed calls"]
+
+    def spread(who, key):
+        v = [r[key][0] for r in runs[who] if key in r]
+        return "%8.3f [%.3f - %.3f]" % (np.median(v), min(v), max(v)) if v else "   not measured"
+
+    for D, paths in POST_CONFIGS:
+        lines.append("  D = %3d  paths = %d" % (D, paths))
+        key = "ssx_stereo_dense %d %d" % (D, paths)
+        lines.append("    %-52s %s" % ("ssx_stereo_dense, parent commit's library", spread("parent", key)))
+        lines.append("    %-52s %s" % ("ssx_stereo_dense, this library", spread("new", key)))
+        for name in ("everything off", "filter 100 / 16", "filter + samples (stride 4)", "samples only, no map asked for"):
+            lines.append("    %-52s %s" % ("ssx_stereo_dense_post, " + name, spread("new", "ssx_stereo_dense_post %d %d %s" % (D, paths, name))))
+        lines.append("    per kernel (the library's profiler: HIP events around each launch, 20 calls with filter + samples; %d samples a call), us a launch:" % runs["new"][0]["samples %d %d" % (D, paths)])
+        for k in ["k_dense_census", "k_dense_paths", "k_dense_right", "k_dense_select"] + POST_KERNELS:
+            v = [r["kernels %d %d" % (D, paths)][k][1] for r in runs["new"] if k in r["kernels %d %d" % (D, paths)]]
+            if v:
+                lines.append("      %-24s %8.1f [%.1f - %.1f]" % (k, np.median(v), min(v), max(v)))
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    open(out, "w").write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 if __name__ == "__main__":
+    if "--post-child" in sys.argv:
+        post_child()
+        sys.exit(0)
+    if "--post" in sys.argv:
+        post(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "dense_post", "time.txt"),
+             sys.argv[sys.argv.index("--parent-lib") + 1] if "--parent-lib" in sys.argv else None)
+        sys.exit(0)
     if "--child" in sys.argv:
         child(int(sys.argv[sys.argv.index("--child") + 1]))
         sys.exit(0)
