@@ -232,8 +232,8 @@ SSX_API ssx_status ssx_kfdb_debug_last_batch(ssx_ctx* ctx, int32_t* launches, in
 SSX_API ssx_status ssx_kfdb_debug_bow(ssx_vocabulary* voc, const uint8_t* desc, int32_t n, int32_t cap, int32_t* ids_out, double* vals_out,
                                       int32_t* n_entries);
 
-/* tests / tools hook of ssx_undistort (csrc/undistort.hip): what the context's last call issued, counted where it is issued, as
- * ssx_kfdb_debug_last_step counts -- kernel launches, stream synchronisations, bytes sent up (the job table and, for host images,
+/* tests / tools hook of ssx_undistort (csrc/undistort.hip): what the context's last call issued, counted from the lists of copies
+ * it issued (filled once the call has synchronised) -- kernel launches, stream synchronisations, bytes sent up (the job table and, for host images,
  * the sources) and bytes that came down (the results of host images).  All zero after a call that was refused.  Any output may be NULL. */
 SSX_API ssx_status ssx_undistort_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down);
 /* the same for a plan (ssx_undistort_plan_*): what its last ssx_undistort_plan_add or ssx_undistort_plan_apply issued.  copies_up /
@@ -241,6 +241,40 @@ SSX_API ssx_status ssx_undistort_debug_last_call(ssx_ctx* ctx, int32_t* launches
  * beside them, in bytes_up and not in copies_up).  All zero after a call that was refused, and after an add that found its map. */
 SSX_API ssx_status ssx_undistort_plan_debug_last_call(const ssx_undistort_plan* plan, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up,
                                                       int64_t* bytes_down, int32_t* copies_up, int32_t* copies_down);
+/* The call that ssx_undistort (entry 0), ssx_undistort_lens (1) or ssx_undistort_plan_apply (2) would issue, as csrc/undistort.hip
+ * plans it (UdCall), or its refusal.  Needs no GPU and no context: the same checks and the same builder run on jobs stated as facts.
+ *   jobs[k]     src_off / dst_off = the job's pointers minus jobs[0].src, in bytes (flags: the pointer is null instead); the strides;
+ *               tag = its lens model (entries 0, 1) or its map index (entry 2).  jobs = NULL is a null table.
+ *   n_maps      the maps the plan holds (entry 2)
+ *   src_facts / dst_facts   what the entry point would learn from the runtime about that side's images (looked at only where it would
+ *               ask: entry 2 with images_on_device): one_allocation, and kind[k] of image k -- 1 pinned host, 0 device, -1 neither; with
+ *               one_allocation only kind[0] counts.  NULL, or kind = NULL: every image is device memory.
+ * out->status and out->error are what the entry point would return and ssx_last_error would show; the rest is filled for SSX_OK with
+ * n > 0: the launch, the intakes (SSX_UD_*), the spans of the device block in memory order (table, sources, results), per job what its
+ * table entry carries (an offset into the block or SSX_UD_WHERE_IT_LIES, and the strides), the copies in the order they are issued
+ * (host: the caller's address in a space where jobs[0].src - jobs[0].src_off is SSX_UD_BASE, or 0: the pinned staging buffer at
+ * `off`; a down copy is height rows of width bytes), and the counters the call would report.  Returns out->status. */
+enum { SSX_UD_ENTRY_UNDISTORT = 0, SSX_UD_ENTRY_LENS = 1, SSX_UD_ENTRY_PLAN_APPLY = 2 };
+enum { SSX_UD_STAGED = 0, SSX_UD_IN_PLACE = 1, SSX_UD_RANGE = 2, SSX_UD_EACH = 3 };
+enum { SSX_UD_SRC_IS_NULL = 1, SSX_UD_DST_IS_NULL = 2 };
+#define SSX_UD_WHERE_IT_LIES (~(uint64_t)0)
+#define SSX_UD_BASE ((uint64_t)1 << 40)
+typedef struct ssx_undistort_job_facts { int64_t src_off, dst_off; int32_t src_stride, dst_stride, tag, flags; } ssx_undistort_job_facts;
+typedef struct ssx_undistort_side_facts { int32_t one_allocation, reserved; const int8_t* kind; } ssx_undistort_side_facts;
+typedef struct ssx_undistort_call_info {
+  int32_t status;
+  char error[256];
+  int32_t grid[3], block[3], src_intake, dst_intake;
+  uint64_t span_off[3], span_bytes[3], up_bytes, arena_bytes, stage_bytes;
+  int32_t n_jobs, n_up, n_down, launches, syncs, copies_up, copies_down, reserved;
+  int64_t bytes_up, bytes_down;
+  struct { uint64_t src_off, dst_off; int64_t src_stride, dst_stride; } job[1024];
+  struct { uint64_t off, host, bytes, images; } up[1025];
+  struct { uint64_t host, host_pitch, off, dev_pitch, width, height; } down[1024];
+} ssx_undistort_call_info;
+SSX_API ssx_status ssx_undistort_debug_plan(int32_t entry, int32_t rows, int32_t cols, int32_t images_on_device, int32_t n, const ssx_undistort_job_facts* jobs,
+                                            int32_t n_maps, const ssx_undistort_side_facts* src_facts, const ssx_undistort_side_facts* dst_facts,
+                                            ssx_undistort_call_info* out);
 /* the stored map `map_index` as tools/undistort_model.py's pack_map returns it: out = three planes of rows x cols u16 (xs, ys, ab),
  * each contiguous */
 SSX_API ssx_status ssx_undistort_plan_debug_map(ssx_undistort_plan* plan, int32_t map_index, uint16_t* out);

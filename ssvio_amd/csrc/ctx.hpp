@@ -174,7 +174,7 @@ struct ssx_ctx {
   KfChainStats kf_batch;                     // the last ssx_kfdb_process_keyframe_batch (ssx_kfdb_debug_last_batch)
   DevBuf ud_arena;                           // image undistortion (undistort.hip): the job table and, for host images, the staged images
   HostBuf ud_stage;
-  KfChainStats undistort;                    // the last ssx_undistort (ssx_undistort_debug_last_call)
+  struct UdStats : KfChainStats { int32_t copies_up = 0, copies_down = 0; } undistort;   // the last ssx_undistort* (ssx_undistort_debug_last_call reports the four)
   DevBuf dn_arena, dn_work;                  // dense stereo (dense.hip): the job table and staged images / maps; census, volume and right keys of a group
   HostBuf dn_stage;
   KfChainStats dense;                        // the last ssx_stereo_dense / ssx_stereo_dense_post / ssx_dense_postprocess (ssx_dense_debug_last_call)

@@ -29,7 +29,14 @@
 // Lens models (contract tools/rectify_model.py): every job and every stored map names its lens, SSX_LENS_RADTAN -- the map
 // above, and what ssx_undistort / ssx_undistort_plan_add pass -- or SSX_LENS_KB4 (Kannala-Brandt, its atan the contract's own f64
 // operations: ud_atan).  The model is wave-uniform, so jobs of mixed models stay one launch.  ssx_stereo_rectify, the common rectified
-// camera of a raw rig, is host arithmetic in this file because of the next sentence.
+// camera of a raw rig, is host arithmetic in rectify.inc, included at the end of this file because of the last paragraph.
+//
+// The host side: ssx_undistort, ssx_undistort_lens and ssx_undistort_plan_apply are each check, facts, build, issue.
+//   ud_check   every refusal of a job table, one list for the three job structs (a UdView each), with the one overlap search
+//   ud_facts   what only the runtime knows about the image pointers: one allocation or several, pinned host / device / neither
+//   ud_build   the call as a plain value, UdCall: launch, block layout, table entries, intakes, the copies up and down in order
+//   ud_issue   reserve, pack rows, copy up, launch, copy down, synchronise once, unpack rows, count what was issued
+// ud_check and ud_build make no HIP call: ssx_undistort_debug_plan shows their value without a device (tests/test_undistort_call_plan.py).
 //
 // This file is compiled with -ffp-contract=off: every f64 operation rounds on its own, as the model's does
 // (tests/test_undistort_gpu.py, tests/test_rectify_gpu.py: the output is the model's bytes; tests/test_rectify_abi.py: ssx_stereo_rectify's
@@ -302,111 +309,294 @@ __global__ void __launch_bounds__(UD_BX * UD_BY) k_undistort_remap(const UdRemap
   }
 }
 
-// [first, last) of an image in memory: from its pointer to the end of its last row
-inline void ud_span(const uint8_t* p, int64_t stride, int32_t rows, int32_t cols, uintptr_t* first, uintptr_t* last)
+// ---- the host side of a call (the header has its four steps).  ud_check and ud_build make no HIP call and touch no workspace:
+// ssx_undistort_debug_plan runs them without a device, and tests/test_undistort_call_plan.py holds the value to the rules stated here ----
+constexpr int UD_ERR = 256;                 // bytes of the text that says why a call is refused
+enum UdWhich { UD_INLINE = 0, UD_STORED = 1 };   // ssx_undistort / ssx_undistort_lens (k_undistort), ssx_undistort_plan_apply (k_undistort_remap)
+#define UD_REFUSE(status, ...) do { std::snprintf(err, UD_ERR, __VA_ARGS__); return (status); } while (0)
+
+inline bool ud_known_model(int32_t model) { return model == SSX_LENS_RADTAN || model == SSX_LENS_KB4; }
+
+// one job of any entry point as the checks and the plan see it: two images, and `tag` -- its lens model (UD_INLINE) or its map index
+struct UdView { const uint8_t* src; int32_t src_stride; uint8_t* dst; int32_t dst_stride; int32_t tag; };
+struct UdImage { const uint8_t* p; int32_t stride; };
+inline UdImage ud_image(const UdView& v, bool results) { return results ? UdImage{v.dst, v.dst_stride} : UdImage{v.src, v.src_stride}; }
+
+// the bytes of an image from its pointer to the end of its last row, and that as [first, last) in memory
+inline size_t ud_bytes(int32_t stride, int32_t rows, int32_t cols) { return (size_t)((int64_t)(rows - 1) * stride + cols); }
+inline void ud_span(const UdImage& im, int32_t rows, int32_t cols, uintptr_t* first, uintptr_t* last)
 {
-  *first = reinterpret_cast<uintptr_t>(p);
-  *last = *first + (uintptr_t)((int64_t)(rows - 1) * stride + cols);
+  *first = reinterpret_cast<uintptr_t>(im.p);
+  *last = *first + (uintptr_t)ud_bytes(im.stride, rows, cols);
 }
 
-inline size_t ud_bytes(int32_t stride, int32_t rows, int32_t cols) { return (size_t)((int64_t)(rows - 1) * stride + cols); }
-
 // does a dst of the call overlap a src of the call?  Sorted sources and the furthest end among those that begin no later: n log n for
-// the call that is accepted; the pair of a refused call is then found in job order, as ssx_undistort names it
-bool ud_find_overlap(int32_t n, const ssx_undistort_plan_job* jobs, int32_t rows, int32_t cols, int32_t* d_out, int32_t* s_out)
+// the call that is accepted; the pair of a refused call is the first in job order (its dst, then its src)
+bool ud_find_overlap(const std::vector<UdView>& v, int32_t rows, int32_t cols, int32_t* d_out, int32_t* s_out)
 {
   struct Iv { uintptr_t a, b; };
-  std::vector<Iv> src((size_t)std::max(n, 0));
-  for (int32_t k = 0; k < n; ++k) ud_span(jobs[k].src, jobs[k].src_stride, rows, cols, &src[k].a, &src[k].b);
+  const int32_t n = (int32_t)v.size();
+  std::vector<Iv> src(v.size());
+  for (int32_t k = 0; k < n; ++k) ud_span(ud_image(v[k], false), rows, cols, &src[k].a, &src[k].b);
   std::sort(src.begin(), src.end(), [](const Iv& x, const Iv& y) { return x.a < y.a; });
   for (size_t k = 1; k < src.size(); ++k) src[k].b = std::max(src[k].b, src[k - 1].b);
-  bool any = false;
-  for (int32_t d = 0; d < n && !any; ++d) {
-    uintptr_t d0, d1;
-    ud_span(jobs[d].dst, jobs[d].dst_stride, rows, cols, &d0, &d1);
-    const size_t cnt = (size_t)(std::lower_bound(src.begin(), src.end(), d1, [](const Iv& x, uintptr_t v) { return x.a < v; }) - src.begin());
-    any = cnt > 0 && src[cnt - 1].b > d0;
-  }
-  if (!any) return false;
   for (int32_t d = 0; d < n; ++d) {
     uintptr_t d0, d1;
-    ud_span(jobs[d].dst, jobs[d].dst_stride, rows, cols, &d0, &d1);
+    ud_span(ud_image(v[d], true), rows, cols, &d0, &d1);
+    const size_t cnt = (size_t)(std::lower_bound(src.begin(), src.end(), d1, [](const Iv& x, uintptr_t e) { return x.a < e; }) - src.begin());
+    if (cnt == 0 || src[cnt - 1].b <= d0) continue;                             // (exact: the source that ends furthest begins in front of d1)
     for (int32_t s = 0; s < n; ++s) {
       uintptr_t s0, s1;
-      ud_span(jobs[s].src, jobs[s].src_stride, rows, cols, &s0, &s1);
+      ud_span(ud_image(v[s], false), rows, cols, &s0, &s1);
       if (d0 < s1 && s0 < d1) { *d_out = d; *s_out = s; return true; }
     }
   }
   return false;
 }
 
-// Where the images of one side of an images_on_device call lie (the sources, or the results), asked of the runtime: look-ups in its
-// table of allocations, no copy, no launch, no synchronisation.
-//   range    host images that go in ONE copy: in job order ascending, each at least one image behind the last, the whole no longer
-//            than twice the images, and -- the runtime's word, arithmetic is not enough: images allocated one by one can stand just
-//            like that, and one copy over them would cross whatever lies between two allocations -- in ONE allocation (choose_intake
-//            and lk_facts of lk.hip).  Results also stand at one constant distance and at a stride of cols: the 2-D copy that brings
-//            them down then writes the images and nothing between them.
-//   host[k]  otherwise: image k is pinned host memory (a copy of its own) or device memory (used where it lies)
-struct UdImage { const uint8_t* p; int32_t stride; };
-struct UdSide {
-  bool range = false;
-  size_t range_bytes = 0, distance = 0;
-  std::vector<char> host;
-};
-
-// 1: host memory the runtime knows (pinned), 0: device memory, -1: neither
-int ud_kind(const void* p)
+// Every refusal of a job table, before anything is touched, in the order the entry points have always stated them: the count, the
+// image size (UD_INLINE: a plan's was checked when it was created), the table, per job its pointers, its strides and its tag, the
+// overlap, and (UD_INLINE) the largest side.  view(k) is job k of the caller's table, read only once the count and the table are
+// accepted.  -> the status, the text in err, the views in v.
+template <class View>
+ssx_status ud_check(char* err, const char* who, UdWhich which, int32_t n, bool table, int32_t rows, int32_t cols, int32_t n_maps, View&& view, std::vector<UdView>& v)
 {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
-  if (at.type == hipMemoryTypeHost) return 1;
-  if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) return 0;
-  return -1;
+  if (n < 0 || n > SSX_UNDISTORT_MAX_JOBS) UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: n = %d outside [0, %d]", who, n, SSX_UNDISTORT_MAX_JOBS);
+  if (which == UD_INLINE && (rows < 1 || cols < 1)) UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: rows = %d, cols = %d (both must be >= 1)", who, rows, cols);
+  if (n > 0 && !table) UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: jobs is null", who);
+  v.resize((size_t)n);
+  for (int32_t k = 0; k < n; ++k) {
+    const UdView& j = v[k] = view(k);
+    if (!j.src || !j.dst) UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: job %d has a null %s", who, k, j.src ? "dst" : "src");
+    if (j.src_stride < cols || j.dst_stride < cols)
+      UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: job %d has a stride (src %d, dst %d) smaller than cols = %d", who, k, j.src_stride, j.dst_stride, cols);
+    if (which == UD_INLINE && !ud_known_model(j.tag))
+      UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: job %d names lens model %d (SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1)", who, k, j.tag);
+    if (which == UD_STORED && (j.tag < 0 || j.tag >= n_maps)) UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: job %d names map %d, the plan holds %d", who, k, j.tag, n_maps);
+  }
+  int32_t d = 0, s = 0;
+  if (ud_find_overlap(v, rows, cols, &d, &s)) UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: the dst of job %d overlaps the src of job %d (there is no in-place form)", who, d, s);
+  if (which == UD_INLINE && (rows > UD_MAX_SIDE || cols > UD_MAX_SIDE)) UD_REFUSE(SSX_ERR_UNSUPPORTED, "%s: %d x %d is above %d a side", who, rows, cols, UD_MAX_SIDE);
+  return SSX_OK;
 }
 
-bool ud_classify(const std::vector<UdImage>& im, int32_t rows, int32_t cols, bool results, UdSide& side, int32_t* bad)
+// How the images of one side of a call (the sources, or the results) reach the device and leave it:
+//   UD_STAGED    host images, images_on_device = 0: rows packed into pinned staging, one copy each way
+//   UD_IN_PLACE  the kernel reads / writes every image where it lies; nothing is copied
+//   UD_RANGE     pinned host images that go in ONE copy: in job order ascending, each at least one image behind the last, the whole no
+//                longer than twice the images (ud_range_arith), and -- the runtime's word, arithmetic is not enough: images allocated one by
+//                one can stand just like that, and one copy over them would cross whatever lies between two allocations -- in ONE
+//                allocation (choose_intake and lk_facts of lk.hip).  Results also stand at one constant distance and at a stride of cols:
+//                the 2-D copy that brings them down then writes the images and nothing between them.
+//   UD_EACH      otherwise: a pinned host image gets a copy of its own, a device image is used where it lies
+// ssx_undistort* take UD_STAGED or UD_IN_PLACE and ask nothing; ssx_undistort_plan_apply takes any of the four, per side.
+enum UdIntake { UD_STAGED = 0, UD_IN_PLACE, UD_RANGE, UD_EACH };
+
+// What the runtime knows about one side's images and arithmetic does not (ud_facts asks, and only where the answer decides;
+// ssx_undistort_debug_plan is told): do they lie in one allocation, and kind[k] of image k -- when they do, only kind[0] is looked at.
+enum : int8_t { UD_NEITHER = -1, UD_DEVICE = 0, UD_PINNED = 1 };
+struct UdSideFacts { bool one_allocation = false; std::vector<int8_t> kind; };
+struct UdFacts { UdSideFacts src, dst; };
+
+// the arithmetic of UD_RANGE: does it hold; the bytes from the first image to the end of the last; for results their distance
+struct UdRange { bool ok = false; size_t bytes = 0, distance = 0; };
+UdRange ud_range_arith(const std::vector<UdView>& v, bool results, int32_t rows, int32_t cols)
 {
-  const size_t n = im.size();
-  side = UdSide{};
-  side.host.assign(n, 0);
+  const size_t n = v.size();
+  const auto im = [&](size_t k) { return ud_image(v[k], results); };
+  UdRange r;
   size_t longest = 0;
-  for (const UdImage& i : im) longest = std::max(longest, ud_bytes(i.stride, rows, cols));
-  bool ok = n >= 2;
-  for (size_t k = 1; ok && k < n; ++k) ok = im[k].p > im[k - 1].p && (size_t)(im[k].p - im[k - 1].p) >= ud_bytes(im[k - 1].stride, rows, cols);
-  const size_t range = ok ? (size_t)(im[n - 1].p - im[0].p) + ud_bytes(im[n - 1].stride, rows, cols) : 0;
-  ok = ok && range <= 2 * n * longest;
-  if (ok && results) {
-    side.distance = (size_t)(im[1].p - im[0].p);
-    for (size_t k = 0; ok && k < n; ++k) ok = im[k].stride == cols && (k == 0 || (size_t)(im[k].p - im[k - 1].p) == side.distance);
+  for (size_t k = 0; k < n; ++k) longest = std::max(longest, ud_bytes(im(k).stride, rows, cols));
+  r.ok = n >= 2;
+  for (size_t k = 1; r.ok && k < n; ++k) r.ok = im(k).p > im(k - 1).p && (size_t)(im(k).p - im(k - 1).p) >= ud_bytes(im(k - 1).stride, rows, cols);
+  if (r.ok) r.bytes = (size_t)(im(n - 1).p - im(0).p) + ud_bytes(im(n - 1).stride, rows, cols);
+  r.ok = r.ok && r.bytes <= 2 * n * longest;
+  if (r.ok && results) {
+    r.distance = (size_t)(im(1).p - im(0).p);
+    for (size_t k = 0; r.ok && k < n; ++k) r.ok = im(k).stride == cols && (k == 0 || (size_t)(im(k).p - im(k - 1).p) == r.distance);
   }
-  if (ok) {
-    const uint8_t* const last_end = im[n - 1].p + ud_bytes(im[n - 1].stride, rows, cols);
-    hipDeviceptr_t base0 = nullptr, base1 = nullptr;
-    size_t size0 = 0, size1 = 0;
-    const bool one = hipMemGetAddressRange(&base0, &size0, (hipDeviceptr_t)im[0].p) == hipSuccess &&
-                     hipMemGetAddressRange(&base1, &size1, (hipDeviceptr_t)im[n - 1].p) == hipSuccess && base0 == base1 &&
-                     (const uint8_t*)base0 <= im[0].p && last_end <= (const uint8_t*)base0 + size0;
-    if (!one) (void)hipGetLastError();
-    if (one) {
-      const int kind = ud_kind(im[0].p);
-      if (kind < 0) { *bad = 0; return false; }
-      if (kind == 1) { side.range = true; side.range_bytes = range; }
-      return true;                                                             // (one device allocation: every image where it lies)
-    }
-  }
-  for (size_t k = 0; k < n; ++k) {
-    const int kind = ud_kind(im[k].p);
-    if (kind < 0) { *bad = (int32_t)k; return false; }
-    side.host[k] = kind == 1;
+  return r;
+}
+
+// the intake of one side of ssx_undistort_plan_apply with images_on_device; false: image *bad is neither device nor pinned host memory
+// (job 0 when a one-allocation range is of unknown kind, otherwise the first unknown image)
+bool ud_choose(const std::vector<UdView>& v, bool results, int32_t rows, int32_t cols, const UdSideFacts& f, UdIntake* intake, UdRange* r, int32_t* bad)
+{
+  *r = ud_range_arith(v, results, rows, cols);
+  const bool one = r->ok && f.one_allocation;
+  *intake = one && f.kind[0] == UD_PINNED ? UD_RANGE : UD_IN_PLACE;              // (one device allocation: every image where it lies)
+  for (size_t k = 0; k < (one ? 1 : v.size()); ++k) {
+    if (f.kind[k] == UD_NEITHER) { *bad = (int32_t)k; return false; }
+    if (!one && f.kind[k] == UD_PINNED) *intake = UD_EACH;
   }
   return true;
 }
 
-// what a plan's last call issued (ssx_undistort_plan_debug_last_call)
-struct UdPlanStats { int32_t launches = 0, syncs = 0, copies_up = 0, copies_down = 0; int64_t bytes_up = 0, bytes_down = 0; };
+// A call as a plain value.  The device block is [job table | sources] | results, the table at its start and each part at a multiple of
+// 256: everything that is sent lies in front of up_bytes, everything that comes back behind it.
+//   UD_STAGED   sources packed at a pitch of cols, results at a pitch of cols rounded up to a dword (every store but the tail's is one).
+//               ssx_undistort* pack the images of a side as one run; ssx_undistort_plan_apply rounds each image's slot to 256.
+//   UD_RANGE    the sources keep the range's layout (one copy): image k at base + (src_k - src_0), at its own stride; the results are
+//               images of rows * cols bytes at a stride of cols in slots rounded to 256 (one 2-D copy: a row of it is an image)
+//   UD_EACH     pinned host sources stand one by one at their own stride, pinned host results one by one at the dword pitch
+// (UdCallJob, UdUp and UdDown are ssx_undistort_call_info's job, up and down, member for member.)
+constexpr size_t UD_WHERE_IT_LIES = ~size_t(0);                                 // UdCallJob::*_off: the table entry carries the caller's pointer
+struct UdCallJob { size_t src_off, dst_off; int64_t src_stride, dst_stride; };  // what table entry k will carry
+struct UdUp { size_t off; const void* host; size_t bytes, images; };            // to arena + off, from `host` (null: staging + off); images: it carries some
+struct UdDown { void* host; size_t hpitch, off, dpitch, width, height; };       // 2-D to `host` from arena + off; host null: `width` bytes to staging + off
+typedef ssx_ctx::UdStats UdStats;                                               // what a call issued: KfChainStats and the copies that carried images
+struct UdCall {
+  int32_t n = 0, rows = 0, cols = 0;
+  unsigned grid[3] = {0, 0, 0}, block[3] = {UD_BX, UD_BY, 1};
+  UdIntake src_intake, dst_intake;        // UD_STAGED sources are packed into staging before the copies, UD_STAGED results unpacked behind the synchronisation
+  size_t tab_bytes = 0, up_bytes = 0, arena_bytes = 0, stage_bytes = 0;
+  std::vector<UdCallJob> jobs;
+  std::vector<UdUp> up;                   // in the order they are issued: the table first
+  std::vector<UdDown> down;
+};
+
+ssx_status ud_build(char* err, const char* who, UdWhich which, const std::vector<UdView>& v, int32_t rows, int32_t cols, int32_t images_on_device, const UdFacts& facts,
+                    UdCall& c)
+{
+  const size_t n = v.size();
+  const bool staged = images_on_device == 0;
+  c.n = (int32_t)n; c.rows = rows; c.cols = cols;
+  c.grid[0] = (unsigned)((cols + UD_BX * UD_PX - 1) / (UD_BX * UD_PX)); c.grid[1] = (unsigned)((rows + UD_BY - 1) / UD_BY); c.grid[2] = (unsigned)n;
+  c.src_intake = c.dst_intake = staged ? UD_STAGED : UD_IN_PLACE;
+  UdRange sr, dr;
+  int32_t bad = -1;
+  if (!staged && which == UD_STORED && !ud_choose(v, false, rows, cols, facts.src, &c.src_intake, &sr, &bad))
+    UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: the src of job %d is neither device memory nor pinned host memory (images_on_device = %d)", who, bad, images_on_device);
+  if (!staged && which == UD_STORED && !ud_choose(v, true, rows, cols, facts.dst, &c.dst_intake, &dr, &bad))
+    UD_REFUSE(SSX_ERR_INVALID_ARG, "%s: the dst of job %d is neither device memory nor pinned host memory (images_on_device = %d)", who, bad, images_on_device);
+  const size_t img_bytes = (size_t)rows * (size_t)cols, dpitch = ((size_t)cols + 3) & ~size_t(3), dst_bytes = (size_t)rows * dpitch;
+  const auto slot = [&](size_t bytes) { return which == UD_STORED ? (bytes + 255) & ~size_t(255) : bytes; };
+  c.jobs.resize(n);
+  for (size_t k = 0; k < n; ++k) c.jobs[k] = UdCallJob{UD_WHERE_IT_LIES, UD_WHERE_IT_LIES, v[k].src_stride, v[k].dst_stride};
+  Layout lay;
+  c.tab_bytes = (which == UD_INLINE ? sizeof(UdJob) : sizeof(UdRemapJob)) * n;
+  lay.take(c.tab_bytes);
+  if (c.src_intake == UD_STAGED) {
+    const size_t base = lay.take(slot(img_bytes) * n);
+    for (size_t k = 0; k < n; ++k) { c.jobs[k].src_off = base + slot(img_bytes) * k; c.jobs[k].src_stride = cols; }
+  } else if (c.src_intake == UD_RANGE) {
+    const size_t base = lay.take(sr.bytes + 16);
+    for (size_t k = 0; k < n; ++k) c.jobs[k].src_off = base + (size_t)(v[k].src - v[0].src);
+    c.up.push_back(UdUp{base, v[0].src, sr.bytes, 1});
+  }
+  for (size_t k = 0; c.src_intake == UD_EACH && k < n; ++k) {
+    if (facts.src.kind[k] != UD_PINNED) continue;
+    c.jobs[k].src_off = lay.take(ud_bytes(v[k].src_stride, rows, cols));
+    c.up.push_back(UdUp{c.jobs[k].src_off, v[k].src, ud_bytes(v[k].src_stride, rows, cols), 1});
+  }
+  c.up_bytes = lay.off;
+  // the table goes up first: in the one copy of staged sources, else beside the images (ssx_undistort*: its span, plan_apply: its bytes)
+  c.up.insert(c.up.begin(), UdUp{0, nullptr, staged || which == UD_INLINE ? c.up_bytes : c.tab_bytes, staged});
+  if (c.dst_intake == UD_STAGED || c.dst_intake == UD_RANGE) {
+    // UD_RANGE: a row of the copy is an image, rows * cols bytes, `distance` apart on the host -- nothing between the images is written
+    const bool range = c.dst_intake == UD_RANGE;
+    const size_t each = slot(range ? img_bytes : dst_bytes), base = lay.take(each * n);
+    for (size_t k = 0; k < n; ++k) { c.jobs[k].dst_off = base + each * k; c.jobs[k].dst_stride = range ? (int64_t)cols : (int64_t)dpitch; }
+    c.down.push_back(range ? UdDown{v[0].dst, dr.distance, base, each, img_bytes, n} : UdDown{nullptr, 0, base, 0, each * n, 1});
+  }
+  for (size_t k = 0; c.dst_intake == UD_EACH && k < n; ++k) {
+    if (facts.dst.kind[k] != UD_PINNED) continue;                                  // (rows of cols bytes: the pitch bytes of the destination stay)
+    c.jobs[k].dst_off = lay.take(dst_bytes);
+    c.jobs[k].dst_stride = (int64_t)dpitch;
+    c.down.push_back(UdDown{v[k].dst, (size_t)v[k].dst_stride, c.jobs[k].dst_off, dpitch, (size_t)cols, (size_t)rows});
+  }
+  c.arena_bytes = lay.off;
+  c.stage_bytes = staged ? c.arena_bytes : c.up[0].bytes;
+  return SSX_OK;
+}
+
+// what issuing `c` counts: one launch, one synchronisation, the bytes of its copies, and the copies that carry images
+UdStats ud_predict(const UdCall& c)
+{
+  UdStats st{};
+  st.launches = 1; st.syncs = 1;
+  for (const UdUp& u : c.up) { st.bytes_up += (int64_t)u.bytes; st.copies_up += (int32_t)u.images; }
+  for (const UdDown& d : c.down) { st.bytes_down += (int64_t)(d.width * d.height); ++st.copies_down; }
+  return st;
+}
+
+// ---- the asking: look-ups in the runtime's table of allocations, no copy, no launch, no synchronisation ----
+int8_t ud_kind(const void* p)
+{
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return UD_NEITHER; }
+  if (at.type == hipMemoryTypeHost) return UD_PINNED;
+  return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged ? UD_DEVICE : UD_NEITHER;
+}
+
+// one side's facts, asked only where ud_choose will look; false: an image of unknown kind was met (no image behind it is asked)
+bool ud_ask(const std::vector<UdView>& v, bool results, int32_t rows, int32_t cols, UdSideFacts& f)
+{
+  const size_t n = v.size();
+  f.kind.assign(n, UD_DEVICE);
+  const UdRange r = ud_range_arith(v, results, rows, cols);
+  const uint8_t* const first = ud_image(v[0], results).p;
+  hipDeviceptr_t base0 = nullptr, base1 = nullptr;
+  size_t size0 = 0, size1 = 0;
+  f.one_allocation = r.ok && hipMemGetAddressRange(&base0, &size0, (hipDeviceptr_t)first) == hipSuccess &&
+                     hipMemGetAddressRange(&base1, &size1, (hipDeviceptr_t)ud_image(v[n - 1], results).p) == hipSuccess && base0 == base1 &&
+                     (const uint8_t*)base0 <= first && first + r.bytes <= (const uint8_t*)base0 + size0;
+  if (r.ok && !f.one_allocation) (void)hipGetLastError();
+  for (size_t k = 0; k < (f.one_allocation ? 1 : n); ++k)
+    if ((f.kind[k] = ud_kind(ud_image(v[k], results).p)) == UD_NEITHER) return false;
+  return true;
+}
+
+// (ssx_undistort* ask nothing; a side behind a refused one is not asked)
+UdFacts ud_facts(UdWhich which, const std::vector<UdView>& v, int32_t rows, int32_t cols, int32_t images_on_device)
+{
+  UdFacts f;
+  if (which == UD_STORED && images_on_device != 0 && ud_ask(v, false, rows, cols, f.src)) (void)ud_ask(v, true, rows, cols, f.dst);
+  return f;
+}
+
+// ---- the issuing: reserve, fill the table and pack rows into staging, copy up, launch, copy down, synchronise once, unpack rows, count.
+// Entry is UdJob or UdRemapJob (both begin with the pointers and the strides); fill(k, entry) writes the rest of entry k ----
+template <class Entry, class Fill, class Launch>
+ssx_status ud_issue(ssx_ctx* ctx, const UdCall& c, const std::vector<UdView>& v, DevBuf& arena, HostBuf& staging, Fill&& fill, Launch&& launch, UdStats* out)
+{
+  SSX_HIP_TRY(ctx, arena.reserve(c.arena_bytes));
+  SSX_HIP_TRY(ctx, staging.reserve(c.stage_bytes));
+  char* dev = arena.as<char>();
+  char* stage = staging.as<char>();
+  const size_t cols = (size_t)c.cols;
+  Entry* tab = reinterpret_cast<Entry*>(stage);
+  for (int32_t k = 0; k < c.n; ++k) {
+    const UdCallJob& j = c.jobs[k];
+    Entry& t = tab[k];
+    t.src = j.src_off == UD_WHERE_IT_LIES ? v[k].src : reinterpret_cast<const uint8_t*>(dev + j.src_off);
+    t.dst = j.dst_off == UD_WHERE_IT_LIES ? v[k].dst : reinterpret_cast<uint8_t*>(dev + j.dst_off);
+    t.src_stride = j.src_stride; t.dst_stride = j.dst_stride;
+    fill(k, t);
+    if (c.src_intake != UD_STAGED) continue;
+    uint8_t* s = reinterpret_cast<uint8_t*>(stage + j.src_off);
+    for (int32_t r = 0; r < c.rows; ++r) std::memcpy(s + (size_t)r * cols, v[k].src + (size_t)r * v[k].src_stride, cols);
+  }
+  for (const UdUp& u : c.up) SSX_HIP_TRY(ctx, hipMemcpyAsync(dev + u.off, u.host ? u.host : stage + u.off, u.bytes, hipMemcpyHostToDevice, ctx->stream));
+  launch(reinterpret_cast<const Entry*>(dev), dim3(c.grid[0], c.grid[1], c.grid[2]), dim3(c.block[0], c.block[1], c.block[2]));
+  SSX_HIP_TRY(ctx, hipGetLastError());
+  for (const UdDown& d : c.down) {
+    if (d.host) SSX_HIP_TRY(ctx, hipMemcpy2DAsync(d.host, d.hpitch, dev + d.off, d.dpitch, d.width, d.height, hipMemcpyDeviceToHost, ctx->stream));
+    else SSX_HIP_TRY(ctx, hipMemcpyAsync(stage + d.off, dev + d.off, d.width, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (c.dst_intake == UD_STAGED)
+    for (int32_t k = 0; k < c.n; ++k) {
+      const uint8_t* d = reinterpret_cast<const uint8_t*>(stage + c.jobs[k].dst_off);
+      for (int32_t r = 0; r < c.rows; ++r) std::memcpy(v[k].dst + (size_t)r * v[k].dst_stride, d + (size_t)r * (size_t)c.jobs[k].dst_stride, cols);
+    }
+  *out = ud_predict(c);                                                          // (every copy of the lists was issued, and nothing else)
+  return SSX_OK;
+}
 
 }  // namespace
+
+// ---- the entry points ----
 
 // the stored maps of one image size, and the device block and the pinned staging of the calls that apply them
 struct ssx_undistort_plan {
@@ -418,8 +608,94 @@ struct ssx_undistort_plan {
   std::vector<uint16_t*> maps;
   DevBuf arena;
   HostBuf stage;
-  UdPlanStats last;
+  UdStats last;                               // what the last add or apply issued (ssx_undistort_plan_debug_last_call)
 };
+
+namespace {
+
+// the RADTAN lens that a parameter set of ssx_undistort is: the same bytes whichever entry point it came through
+inline ssx_lens_params ud_as_lens(const ssx_undistort_params& p)
+{
+  ssx_lens_params l;
+  std::memset(&l, 0, sizeof l);
+  l.model = SSX_LENS_RADTAN;
+  std::memcpy(l.K, p.K, sizeof l.K);
+  std::memcpy(l.coeffs, p.dist, sizeof l.coeffs);
+  std::memcpy(l.iR, p.iR, sizeof l.iR);
+  return l;
+}
+inline const ssx_lens_params& ud_as_lens(const ssx_lens_params& p) { return p; }
+
+// ssx_undistort_lens (Job = ssx_lens_job), and ssx_undistort (ssx_undistort_job) as its RADTAN case: check, facts, build, issue
+template <class Job>
+ssx_status ud_run(ssx_ctx* ctx, const char* who, int32_t n, const Job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
+{
+  ctx->undistort = UdStats{};
+  char err[UD_ERR] = {0};
+  std::vector<UdView> v;
+  const auto view = [&](int32_t k) { return UdView{jobs[k].src, jobs[k].src_stride, jobs[k].dst, jobs[k].dst_stride, ud_as_lens(jobs[k].prm).model}; };
+  UdCall call;
+  ssx_status st = ud_check(err, who, UD_INLINE, n, jobs != nullptr, rows, cols, 0, view, v);
+  if (st == SSX_OK && n > 0) st = ud_build(err, who, UD_INLINE, v, rows, cols, images_on_device, UdFacts{}, call);
+  if (st != SSX_OK) { ctx->set_error("%s", err); return st; }
+  if (n == 0) return SSX_OK;
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const auto fill = [&](int32_t k, UdJob& t) {
+    const ssx_lens_params& p = ud_as_lens(jobs[k].prm);
+    t.model = p.model; t.reserved = 0;
+    std::memcpy(t.K, p.K, sizeof(t.K));
+    std::memcpy(t.coeffs, p.coeffs, sizeof(t.coeffs));
+    std::memcpy(t.iR, p.iR, sizeof(t.iR));
+  };
+  const auto launch = [&](const UdJob* tab, dim3 grid, dim3 block) {
+    SSX_PROF(ctx, KID_UNDISTORT, hipLaunchKernelGGL(k_undistort, grid, block, 0, ctx->stream, tab, rows, cols));
+  };
+  return ud_issue<UdJob>(ctx, call, v, ctx->ud_arena, ctx->ud_stage, fill, launch, &ctx->undistort);
+}
+
+// ssx_undistort_plan_add_lens, and ssx_undistort_plan_add as its RADTAN case
+ssx_status ud_plan_add(ssx_undistort_plan* plan, const char* who, const ssx_lens_params* prm, int32_t* map_index)
+{
+  ssx_ctx* ctx = plan->ctx;
+  plan->last = UdStats{};
+  if (!prm || !map_index) { ctx->set_error("%s: %s is null", who, prm ? "map_index" : "prm"); return SSX_ERR_INVALID_ARG; }
+  if (!ud_known_model(prm->model)) {
+    ctx->set_error("%s: lens model %d (SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1)", who, prm->model);
+    return SSX_ERR_INVALID_ARG;
+  }
+  // (parameter sets are equal when their bytes are: -0.0 and 0.0, or two NaNs, are different sets with equal maps, which costs a map and
+  // no more)
+  for (size_t m = 0; m < plan->prm.size(); ++m)
+    if (std::memcmp(&plan->prm[m], prm, sizeof *prm) == 0) { *map_index = (int32_t)m; return SSX_OK; }
+  if (plan->maps.size() >= SSX_UNDISTORT_PLAN_MAX_MAPS) {
+    ctx->set_error("%s: the plan holds SSX_UNDISTORT_PLAN_MAX_MAPS = %d maps already", who, SSX_UNDISTORT_PLAN_MAX_MAPS);
+    return SSX_ERR_CAPACITY;
+  }
+  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint16_t* map = nullptr;
+  SSX_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&map), plan->map_bytes));
+  UdPrm k;
+  std::memcpy(&k, prm, sizeof k);
+  const dim3 grid((unsigned)((plan->cols + UD_BX - 1) / UD_BX), (unsigned)((plan->rows + UD_BY - 1) / UD_BY), 1u);
+  hipError_t e = hipMemsetAsync(map, 0, plan->map_bytes, ctx->stream);         // (the pitch columns: read by a row's last thread, never used)
+  if (e == hipSuccess) {
+    SSX_PROF(ctx, KID_UNDISTORT_MAP, hipLaunchKernelGGL(k_undistort_map, grid, dim3(UD_BX, UD_BY), 0, ctx->stream, k, plan->rows, plan->cols, plan->pitch, map));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(map);
+    ctx->set_error("%s: %s", who, hipGetErrorString(e));
+    return SSX_ERR_HIP;
+  }
+  plan->last.launches = 1; plan->last.syncs = 1;
+  plan->maps.push_back(map);
+  plan->prm.push_back(*prm);
+  *map_index = (int32_t)plan->maps.size() - 1;
+  return SSX_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -433,237 +709,6 @@ void ssx_undistort_default(const double K4[4], const double dist5[5], ssx_undist
   std::memcpy(out->iR, iR, sizeof(out->iR));
 }
 
-}  // extern "C"
-
-namespace {
-
-inline bool ud_known_model(int32_t model) { return model == SSX_LENS_RADTAN || model == SSX_LENS_KB4; }
-
-// the RADTAN lens that a parameter set of ssx_undistort is: the same bytes whichever entry point it came through
-inline ssx_lens_params ud_as_lens(const ssx_undistort_params& p)
-{
-  ssx_lens_params l;
-  std::memset(&l, 0, sizeof l);
-  l.model = SSX_LENS_RADTAN;
-  std::memcpy(l.K, p.K, sizeof l.K);
-  std::memcpy(l.coeffs, p.dist, sizeof l.coeffs);
-  std::memcpy(l.iR, p.iR, sizeof l.iR);
-  return l;
-}
-
-// ssx_undistort_lens, and ssx_undistort as its RADTAN case; `who` names the entry point in the messages
-ssx_status ud_run(ssx_ctx* ctx, const char* who, int32_t n, const ssx_lens_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
-{
-  ctx->undistort = KfChainStats{};
-  // every refusal comes before anything is touched
-  if (n < 0 || n > SSX_UNDISTORT_MAX_JOBS) { ctx->set_error("%s: n = %d outside [0, %d]", who, n, SSX_UNDISTORT_MAX_JOBS); return SSX_ERR_INVALID_ARG; }
-  if (rows < 1 || cols < 1) { ctx->set_error("%s: rows = %d, cols = %d (both must be >= 1)", who, rows, cols); return SSX_ERR_INVALID_ARG; }
-  if (n > 0 && !jobs) { ctx->set_error("%s: jobs is null", who); return SSX_ERR_INVALID_ARG; }
-  for (int32_t k = 0; k < n; ++k) {
-    if (!jobs[k].src || !jobs[k].dst) { ctx->set_error("%s: job %d has a null %s", who, k, jobs[k].src ? "dst" : "src"); return SSX_ERR_INVALID_ARG; }
-    if (jobs[k].src_stride < cols || jobs[k].dst_stride < cols) {
-      ctx->set_error("%s: job %d has a stride (src %d, dst %d) smaller than cols = %d", who, k, jobs[k].src_stride, jobs[k].dst_stride, cols);
-      return SSX_ERR_INVALID_ARG;
-    }
-    if (!ud_known_model(jobs[k].prm.model)) {
-      ctx->set_error("%s: job %d names lens model %d (SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1)", who, k, jobs[k].prm.model);
-      return SSX_ERR_INVALID_ARG;
-    }
-  }
-  for (int32_t d = 0; d < n; ++d) {
-    uintptr_t d0, d1;
-    ud_span(jobs[d].dst, jobs[d].dst_stride, rows, cols, &d0, &d1);
-    for (int32_t s = 0; s < n; ++s) {
-      uintptr_t s0, s1;
-      ud_span(jobs[s].src, jobs[s].src_stride, rows, cols, &s0, &s1);
-      if (d0 < s1 && s0 < d1) {
-        ctx->set_error("%s: the dst of job %d overlaps the src of job %d (there is no in-place form)", who, d, s);
-        return SSX_ERR_INVALID_ARG;
-      }
-    }
-  }
-  if (rows > UD_MAX_SIDE || cols > UD_MAX_SIDE) { ctx->set_error("%s: %d x %d is above %d a side", who, rows, cols, UD_MAX_SIDE); return SSX_ERR_UNSUPPORTED; }
-  if (n == 0) return SSX_OK;
-
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const bool staged = images_on_device == 0;
-  // staged images are packed: sources at a pitch of cols, results at a pitch of cols rounded up to a dword (every store but the tail's is one)
-  const size_t src_bytes = (size_t)rows * (size_t)cols, dpitch = ((size_t)cols + 3) & ~size_t(3), dst_bytes = (size_t)rows * dpitch;
-  Layout lay;
-  const size_t o_tab = lay.take(sizeof(UdJob) * (size_t)n);
-  const size_t o_src = staged ? lay.take(src_bytes * (size_t)n) : 0;
-  const size_t up_bytes = lay.off;
-  const size_t o_dst = staged ? lay.take(dst_bytes * (size_t)n) : 0;
-  SSX_HIP_TRY(ctx, ctx->ud_arena.reserve(lay.off));
-  SSX_HIP_TRY(ctx, ctx->ud_stage.reserve(lay.off));
-  char* dev = ctx->ud_arena.as<char>();
-  char* stage = ctx->ud_stage.as<char>();
-  KfChainStats st{};
-
-  UdJob* tab = reinterpret_cast<UdJob*>(stage + o_tab);
-  for (int32_t k = 0; k < n; ++k) {
-    UdJob& t = tab[k];
-    if (staged) {
-      uint8_t* s = reinterpret_cast<uint8_t*>(stage + o_src + src_bytes * (size_t)k);
-      for (int32_t r = 0; r < rows; ++r) std::memcpy(s + (size_t)r * cols, jobs[k].src + (size_t)r * jobs[k].src_stride, (size_t)cols);
-      t.src = reinterpret_cast<const uint8_t*>(dev + o_src + src_bytes * (size_t)k);
-      t.dst = reinterpret_cast<uint8_t*>(dev + o_dst + dst_bytes * (size_t)k);
-      t.src_stride = cols; t.dst_stride = (int64_t)dpitch;
-    } else {
-      t.src = jobs[k].src; t.dst = jobs[k].dst;
-      t.src_stride = jobs[k].src_stride; t.dst_stride = jobs[k].dst_stride;
-    }
-    t.model = jobs[k].prm.model; t.reserved = 0;
-    std::memcpy(t.K, jobs[k].prm.K, sizeof(t.K));
-    std::memcpy(t.coeffs, jobs[k].prm.coeffs, sizeof(t.coeffs));
-    std::memcpy(t.iR, jobs[k].prm.iR, sizeof(t.iR));
-  }
-  SSX_HIP_TRY(ctx, hipMemcpyAsync(dev, stage, up_bytes, hipMemcpyHostToDevice, ctx->stream));
-  st.bytes_up += (int64_t)up_bytes;
-  const dim3 grid((unsigned)((cols + UD_BX * UD_PX - 1) / (UD_BX * UD_PX)), (unsigned)((rows + UD_BY - 1) / UD_BY), (unsigned)n);
-  SSX_PROF(ctx, KID_UNDISTORT, hipLaunchKernelGGL(k_undistort, grid, dim3(UD_BX, UD_BY), 0, ctx->stream, reinterpret_cast<const UdJob*>(dev + o_tab), rows, cols));
-  SSX_HIP_TRY(ctx, hipGetLastError());
-  ++st.launches;
-  if (staged) {
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(stage + o_dst, dev + o_dst, dst_bytes * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    st.bytes_down += (int64_t)(dst_bytes * (size_t)n);
-  }
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  ++st.syncs;
-  if (staged)
-    for (int32_t k = 0; k < n; ++k) {
-      const uint8_t* d = reinterpret_cast<const uint8_t*>(stage + o_dst + dst_bytes * (size_t)k);
-      for (int32_t r = 0; r < rows; ++r) std::memcpy(jobs[k].dst + (size_t)r * jobs[k].dst_stride, d + (size_t)r * dpitch, (size_t)cols);
-    }
-  ctx->undistort = st;
-  return SSX_OK;
-}
-
-// ssx_undistort_plan_add_lens, and ssx_undistort_plan_add as its RADTAN case (definition below the plan's entry points)
-ssx_status ud_plan_add(ssx_undistort_plan* plan, const char* who, const ssx_lens_params* prm, int32_t* map_index);
-
-// ---- ssx_stereo_rectify: rectify() of tools/rectify_model.py, statement for statement (host f64, this file has no contraction) ----
-const char* const UD_WHY_MODEL = "unknown lens model";
-const char* const UD_WHY_FINITE = "a non-finite input";
-const char* const UD_WHY_BASELINE = "the baseline is zero";
-const char* const UD_WHY_ROTATION = "R is not a rotation: max|R R^T - I| > 1e-6";
-const char* const UD_WHY_SIDE = "the right camera is not to the right of the left one (e1[0] <= 0)";
-const char* const UD_WHY_AXES = "the optical axes lie along the baseline (|e3'|^2 < 1e-12)";
-
-inline bool ud_all_finite(const double* v, int n)
-{
-  for (int k = 0; k < n; ++k)
-    if (!std::isfinite(v[k])) return false;
-  return true;
-}
-
-// iR = S^T newK^-1 in closed form; in the third column the left-most product is taken first
-inline void ud_rect_iR(const double S[9], double f, double cx, double cy, double iR[9])
-{
-  const double g = 1.0 / f;
-  const double mx = -cx / f;
-  const double my = -cy / f;
-  for (int i = 0; i < 3; ++i) {
-    iR[3 * i + 0] = S[0 + i] * g;
-    iR[3 * i + 1] = S[3 + i] * g;
-    const double a = S[0 + i] * mx;
-    const double b = S[3 + i] * my;
-    const double ab = a + b;
-    iR[3 * i + 2] = ab + S[6 + i];
-  }
-}
-
-// -> nullptr and *o filled, or the model's reason and *o untouched
-const char* ud_rectify(const ssx_stereo_raw_rig& rig, ssx_stereo_rectified* o)
-{
-  for (int s = 0; s < 2; ++s)
-    if (!ud_known_model(rig.cam[s].model)) return UD_WHY_MODEL;
-  const double over[3] = {rig.f, rig.cx, rig.cy};
-  bool fin = ud_all_finite(rig.R, 9) && ud_all_finite(rig.t, 3) && ud_all_finite(over, 3);
-  for (int s = 0; s < 2; ++s) fin = fin && ud_all_finite(rig.cam[s].K, 4) && ud_all_finite(rig.cam[s].coeffs, 5);
-  if (!fin) return UD_WHY_FINITE;
-  const double* R = rig.R;
-  const double* t = rig.t;
-  double c[3];
-  for (int i = 0; i < 3; ++i) {
-    const double a0 = (-R[0 + i]) * t[0];
-    const double a1 = (-R[3 + i]) * t[1];
-    const double a2 = (-R[6 + i]) * t[2];
-    const double a01 = a0 + a1;
-    c[i] = a01 + a2;
-  }
-  const double c00 = c[0] * c[0], c11 = c[1] * c[1], c22 = c[2] * c[2];
-  const double cc = c00 + c11;
-  const double b = std::sqrt(cc + c22);
-  if (b == 0.0) return UD_WHY_BASELINE;
-  double worst = 0.0;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double p0 = R[3 * i + 0] * R[3 * j + 0], p1 = R[3 * i + 1] * R[3 * j + 1], p2 = R[3 * i + 2] * R[3 * j + 2];
-      const double p01 = p0 + p1;
-      const double dot = p01 + p2;
-      const double dev = std::fabs(dot - (i == j ? 1.0 : 0.0));
-      if (dev > worst) worst = dev;
-    }
-  if (worst > 1e-6) return UD_WHY_ROTATION;
-  double e1[3], e2[3], e3[3], e3p[3];
-  for (int i = 0; i < 3; ++i) e1[i] = c[i] / b;
-  if (e1[0] <= 0.0) return UD_WHY_SIDE;
-  const double zm[3] = {0.0 + R[6], 0.0 + R[7], 1.0 + R[8]};
-  const double d0 = zm[0] * e1[0], d1 = zm[1] * e1[1], d2 = zm[2] * e1[2];
-  const double d01 = d0 + d1;
-  const double d = d01 + d2;
-  for (int i = 0; i < 3; ++i) {
-    const double de = d * e1[i];
-    e3p[i] = zm[i] - de;
-  }
-  const double q0 = e3p[0] * e3p[0], q1 = e3p[1] * e3p[1], q2 = e3p[2] * e3p[2];
-  const double q01 = q0 + q1;
-  const double n2 = q01 + q2;
-  if (n2 < 1e-12) return UD_WHY_AXES;
-  const double nn = std::sqrt(n2);
-  for (int i = 0; i < 3; ++i) e3[i] = e3p[i] / nn;
-  {
-    const double a0 = e3[1] * e1[2], b0 = e3[2] * e1[1];
-    const double a1 = e3[2] * e1[0], b1 = e3[0] * e1[2];
-    const double a2 = e3[0] * e1[1], b2 = e3[1] * e1[0];
-    e2[0] = a0 - b0; e2[1] = a1 - b1; e2[2] = a2 - b2;
-  }
-  ssx_stereo_rectified r;
-  std::memset(&r, 0, sizeof r);
-  for (int i = 0; i < 3; ++i) { r.R_l[i] = e1[i]; r.R_l[3 + i] = e2[i]; r.R_l[6 + i] = e3[i]; }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double p0 = r.R_l[3 * i + 0] * R[3 * j + 0], p1 = r.R_l[3 * i + 1] * R[3 * j + 1], p2 = r.R_l[3 * i + 2] * R[3 * j + 2];
-      const double p01 = p0 + p1;
-      r.R_r[3 * i + j] = p01 + p2;
-    }
-  const double* Kl = rig.cam[0].K;
-  const double* Kr = rig.cam[1].K;
-  double f = rig.f, cx = rig.cx, cy = rig.cy;
-  if (f == 0.0) {
-    const double sl = Kl[0] + Kl[1], sr = Kr[0] + Kr[1];
-    const double s4 = sl + sr;
-    f = s4 / 4.0;
-  }
-  if (cx == 0.0) { const double s2 = Kl[2] + Kr[2]; cx = s2 / 2.0; }
-  if (cy == 0.0) { const double s2 = Kl[3] + Kr[3]; cy = s2 / 2.0; }
-  r.newK[0] = f; r.newK[1] = f; r.newK[2] = cx; r.newK[3] = cy;
-  r.baseline = b;
-  for (int s = 0; s < 2; ++s) {
-    r.cam[s].model = rig.cam[s].model;                               // (reserved stays 0: equal lenses are equal bytes)
-    std::memcpy(r.cam[s].K, rig.cam[s].K, sizeof r.cam[s].K);
-    std::memcpy(r.cam[s].coeffs, rig.cam[s].coeffs, sizeof r.cam[s].coeffs);
-    ud_rect_iR(s == 0 ? r.R_l : r.R_r, f, cx, cy, r.cam[s].iR);
-  }
-  *o = r;
-  return nullptr;
-}
-
-}  // namespace
-
-extern "C" {
-
 ssx_status ssx_undistort_lens(ssx_ctx* ctx, int32_t n, const ssx_lens_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
 {
   if (!ctx) return SSX_ERR_INVALID_ARG;
@@ -673,22 +718,7 @@ ssx_status ssx_undistort_lens(ssx_ctx* ctx, int32_t n, const ssx_lens_job* jobs,
 ssx_status ssx_undistort(ssx_ctx* ctx, int32_t n, const ssx_undistort_job* jobs, int32_t rows, int32_t cols, int32_t images_on_device)
 {
   if (!ctx) return SSX_ERR_INVALID_ARG;
-  std::vector<ssx_lens_job> lens;                                    // (a count or a table that will be refused goes through as it is)
-  if (jobs && n > 0 && n <= SSX_UNDISTORT_MAX_JOBS) {
-    lens.resize((size_t)n);
-    for (int32_t k = 0; k < n; ++k) lens[k] = ssx_lens_job{jobs[k].src, jobs[k].src_stride, jobs[k].dst, jobs[k].dst_stride, ud_as_lens(jobs[k].prm)};
-  }
-  return ud_run(ctx, "ssx_undistort", n, lens.empty() ? nullptr : lens.data(), rows, cols, images_on_device);
-}
-
-ssx_status ssx_stereo_rectify(const ssx_stereo_raw_rig* rig, ssx_stereo_rectified* out, char* why, int32_t why_cap)
-{
-  const char* reason = !rig ? "rig is null" : !out ? "out is null" : ud_rectify(*rig, out);
-  if (why && why_cap > 0) {
-    std::strncpy(why, reason ? reason : "", (size_t)why_cap);
-    why[why_cap - 1] = '\0';
-  }
-  return reason ? SSX_ERR_INVALID_ARG : SSX_OK;
+  return ud_run(ctx, "ssx_undistort", n, jobs, rows, cols, images_on_device);
 }
 
 // ---- the plan: stored maps of one image size, applied to n images in one launch ----
@@ -744,205 +774,80 @@ ssx_status ssx_undistort_plan_add_lens(ssx_undistort_plan* plan, const ssx_lens_
   return ud_plan_add(plan, "ssx_undistort_plan_add_lens", prm, map_index);
 }
 
-}  // extern "C"
-
-namespace {
-
-ssx_status ud_plan_add(ssx_undistort_plan* plan, const char* who, const ssx_lens_params* prm, int32_t* map_index)
-{
-  ssx_ctx* ctx = plan->ctx;
-  plan->last = UdPlanStats{};
-  if (!prm || !map_index) { ctx->set_error("%s: %s is null", who, prm ? "map_index" : "prm"); return SSX_ERR_INVALID_ARG; }
-  if (!ud_known_model(prm->model)) {
-    ctx->set_error("%s: lens model %d (SSX_LENS_RADTAN = 0, SSX_LENS_KB4 = 1)", who, prm->model);
-    return SSX_ERR_INVALID_ARG;
-  }
-  // (parameter sets are equal when their bytes are: -0.0 and 0.0, or two NaNs, are different sets with equal maps, which costs a map and
-  // no more)
-  for (size_t m = 0; m < plan->prm.size(); ++m)
-    if (std::memcmp(&plan->prm[m], prm, sizeof *prm) == 0) { *map_index = (int32_t)m; return SSX_OK; }
-  if (plan->maps.size() >= SSX_UNDISTORT_PLAN_MAX_MAPS) {
-    ctx->set_error("%s: the plan holds SSX_UNDISTORT_PLAN_MAX_MAPS = %d maps already", who, SSX_UNDISTORT_PLAN_MAX_MAPS);
-    return SSX_ERR_CAPACITY;
-  }
-  SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint16_t* map = nullptr;
-  SSX_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&map), plan->map_bytes));
-  UdPrm k;
-  std::memcpy(&k, prm, sizeof k);
-  const dim3 grid((unsigned)((plan->cols + UD_BX - 1) / UD_BX), (unsigned)((plan->rows + UD_BY - 1) / UD_BY), 1u);
-  hipError_t e = hipMemsetAsync(map, 0, plan->map_bytes, ctx->stream);         // (the pitch columns: read by a row's last thread, never used)
-  if (e == hipSuccess) {
-    SSX_PROF(ctx, KID_UNDISTORT_MAP, hipLaunchKernelGGL(k_undistort_map, grid, dim3(UD_BX, UD_BY), 0, ctx->stream, k, plan->rows, plan->cols, plan->pitch, map));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipFree(map);
-    ctx->set_error("%s: %s", who, hipGetErrorString(e));
-    return SSX_ERR_HIP;
-  }
-  plan->last.launches = 1; plan->last.syncs = 1;
-  plan->maps.push_back(map);
-  plan->prm.push_back(*prm);
-  *map_index = (int32_t)plan->maps.size() - 1;
-  return SSX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
+// check, facts, build, issue
 ssx_status ssx_undistort_plan_apply(ssx_undistort_plan* plan, int32_t n, const ssx_undistort_plan_job* jobs, int32_t images_on_device)
 {
   if (!plan) return SSX_ERR_INVALID_ARG;
   ssx_ctx* ctx = plan->ctx;
+  const char* const who = "ssx_undistort_plan_apply";
   const int32_t rows = plan->rows, cols = plan->cols;
-  plan->last = UdPlanStats{};
-  // every refusal comes before anything is touched
-  if (n < 0 || n > SSX_UNDISTORT_MAX_JOBS) { ctx->set_error("ssx_undistort_plan_apply: n = %d outside [0, %d]", n, SSX_UNDISTORT_MAX_JOBS); return SSX_ERR_INVALID_ARG; }
-  if (n > 0 && !jobs) { ctx->set_error("ssx_undistort_plan_apply: jobs is null"); return SSX_ERR_INVALID_ARG; }
-  for (int32_t k = 0; k < n; ++k) {
-    if (!jobs[k].src || !jobs[k].dst) { ctx->set_error("ssx_undistort_plan_apply: job %d has a null %s", k, jobs[k].src ? "dst" : "src"); return SSX_ERR_INVALID_ARG; }
-    if (jobs[k].src_stride < cols || jobs[k].dst_stride < cols) {
-      ctx->set_error("ssx_undistort_plan_apply: job %d has a stride (src %d, dst %d) smaller than cols = %d", k, jobs[k].src_stride, jobs[k].dst_stride, cols);
-      return SSX_ERR_INVALID_ARG;
-    }
-    if (jobs[k].map < 0 || (size_t)jobs[k].map >= plan->maps.size()) {
-      ctx->set_error("ssx_undistort_plan_apply: job %d names map %d, the plan holds %d", k, jobs[k].map, (int)plan->maps.size());
-      return SSX_ERR_INVALID_ARG;
-    }
-  }
-  {
-    int32_t d = 0, s = 0;
-    if (ud_find_overlap(n, jobs, rows, cols, &d, &s)) {
-      ctx->set_error("ssx_undistort_plan_apply: the dst of job %d overlaps the src of job %d (there is no in-place form)", d, s);
-      return SSX_ERR_INVALID_ARG;
-    }
-  }
+  plan->last = UdStats{};
+  char err[UD_ERR] = {0};
+  std::vector<UdView> v;
+  const auto view = [&](int32_t k) { return UdView{jobs[k].src, jobs[k].src_stride, jobs[k].dst, jobs[k].dst_stride, jobs[k].map}; };
+  ssx_status st = ud_check(err, who, UD_STORED, n, jobs != nullptr, rows, cols, (int32_t)plan->maps.size(), view, v);
+  if (st != SSX_OK) { ctx->set_error("%s", err); return st; }
   if (n == 0) return SSX_OK;
   SSX_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const bool staged = images_on_device == 0;
-  UdSide src_side, dst_side;
-  if (!staged) {
-    std::vector<UdImage> si((size_t)n), di((size_t)n);
-    for (int32_t k = 0; k < n; ++k) { si[k] = {jobs[k].src, jobs[k].src_stride}; di[k] = {jobs[k].dst, jobs[k].dst_stride}; }
-    int32_t bad = -1;
-    if (!ud_classify(si, rows, cols, false, src_side, &bad)) {
-      ctx->set_error("ssx_undistort_plan_apply: the src of job %d is neither device memory nor pinned host memory (images_on_device = %d)", bad, images_on_device);
-      return SSX_ERR_INVALID_ARG;
-    }
-    if (!ud_classify(di, rows, cols, true, dst_side, &bad)) {
-      ctx->set_error("ssx_undistort_plan_apply: the dst of job %d is neither device memory nor pinned host memory (images_on_device = %d)", bad, images_on_device);
-      return SSX_ERR_INVALID_ARG;
-    }
-  }
-
-  // the device block: [job table | sources] | results.  Staged images are packed: sources at a pitch of cols, results at a pitch of
-  // cols rounded up to a dword.  Host images of images_on_device: the sources of a range keep the range's layout (one copy), other
-  // host sources stand one by one at their own stride; the results of a range are images of rows * cols bytes at a stride of cols (one
-  // 2-D copy: a row of it is an image), other host results stand one by one at the dword pitch.
-  const size_t img_bytes = (size_t)rows * (size_t)cols, dpitch = ((size_t)cols + 3) & ~size_t(3), dst_bytes = (size_t)rows * dpitch;
-  const size_t range_img = (img_bytes + 255) & ~size_t(255);
-  Layout lay;
-  const size_t o_tab = lay.take(sizeof(UdRemapJob) * (size_t)n);
-  std::vector<size_t> o_src((size_t)n, 0), o_dst((size_t)n, 0);
-  if (staged) {
-    for (int32_t k = 0; k < n; ++k) o_src[k] = lay.take(img_bytes);
-  } else if (src_side.range) {
-    const size_t base = lay.take(src_side.range_bytes + 16);
-    for (int32_t k = 0; k < n; ++k) o_src[k] = base + (size_t)(jobs[k].src - jobs[0].src);
-  } else {
-    for (int32_t k = 0; k < n; ++k) if (src_side.host[k]) o_src[k] = lay.take(ud_bytes(jobs[k].src_stride, rows, cols));
-  }
-  const size_t up_bytes = lay.off;                                              // (staged: what the one copy up carries)
-  const size_t o_dst0 = lay.off;
-  if (staged) {
-    for (int32_t k = 0; k < n; ++k) o_dst[k] = lay.take(dst_bytes);
-  } else if (dst_side.range) {
-    for (int32_t k = 0; k < n; ++k) o_dst[k] = lay.take(range_img);
-  } else {
-    for (int32_t k = 0; k < n; ++k) if (dst_side.host[k]) o_dst[k] = lay.take(dst_bytes);
-  }
-  SSX_HIP_TRY(ctx, plan->arena.reserve(lay.off));
-  SSX_HIP_TRY(ctx, plan->stage.reserve(staged ? lay.off : o_tab + sizeof(UdRemapJob) * (size_t)n));
-  char* dev = plan->arena.as<char>();
-  char* stage = plan->stage.as<char>();
-  hipStream_t s = ctx->stream;
-  UdPlanStats st{};
-
-  UdRemapJob* tab = reinterpret_cast<UdRemapJob*>(stage + o_tab);
-  for (int32_t k = 0; k < n; ++k) {
-    UdRemapJob& t = tab[k];
-    t.map = plan->maps[(size_t)jobs[k].map];
-    if (staged) {
-      uint8_t* h = reinterpret_cast<uint8_t*>(stage + o_src[k]);
-      for (int32_t r = 0; r < rows; ++r) std::memcpy(h + (size_t)r * cols, jobs[k].src + (size_t)r * jobs[k].src_stride, (size_t)cols);
-      t.src = reinterpret_cast<const uint8_t*>(dev + o_src[k]); t.src_stride = cols;
-      t.dst = reinterpret_cast<uint8_t*>(dev + o_dst[k]); t.dst_stride = (int64_t)dpitch;
-      continue;
-    }
-    const bool sh = src_side.range || src_side.host[k], dh = dst_side.range || dst_side.host[k];
-    t.src = sh ? reinterpret_cast<const uint8_t*>(dev + o_src[k]) : jobs[k].src;
-    t.src_stride = jobs[k].src_stride;
-    t.dst = dh ? reinterpret_cast<uint8_t*>(dev + o_dst[k]) : jobs[k].dst;
-    t.dst_stride = !dh ? (int64_t)jobs[k].dst_stride : dst_side.range ? (int64_t)cols : (int64_t)dpitch;
-  }
-  if (staged) {
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(dev, stage, up_bytes, hipMemcpyHostToDevice, s));
-    st.bytes_up += (int64_t)up_bytes; ++st.copies_up;
-  } else {
-    const size_t tab_bytes = sizeof(UdRemapJob) * (size_t)n;
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(dev + o_tab, stage + o_tab, tab_bytes, hipMemcpyHostToDevice, s));
-    st.bytes_up += (int64_t)tab_bytes;
-    if (src_side.range) {
-      SSX_HIP_TRY(ctx, hipMemcpyAsync(dev + o_src[0], jobs[0].src, src_side.range_bytes, hipMemcpyHostToDevice, s));
-      st.bytes_up += (int64_t)src_side.range_bytes; ++st.copies_up;
-    } else {
-      for (int32_t k = 0; k < n; ++k) {
-        if (!src_side.host[k]) continue;
-        const size_t b = ud_bytes(jobs[k].src_stride, rows, cols);
-        SSX_HIP_TRY(ctx, hipMemcpyAsync(dev + o_src[k], jobs[k].src, b, hipMemcpyHostToDevice, s));
-        st.bytes_up += (int64_t)b; ++st.copies_up;
-      }
-    }
-  }
-  const dim3 grid((unsigned)((cols + UD_BX * UD_PX - 1) / (UD_BX * UD_PX)), (unsigned)((rows + UD_BY - 1) / UD_BY), (unsigned)n);
-  SSX_PROF(ctx, KID_UNDISTORT_REMAP, hipLaunchKernelGGL(k_undistort_remap, grid, dim3(UD_BX, UD_BY), 0, s, reinterpret_cast<const UdRemapJob*>(dev + o_tab), rows, cols, plan->pitch));
-  SSX_HIP_TRY(ctx, hipGetLastError());
-  ++st.launches;
-  if (staged) {
-    const size_t down = lay.off - o_dst0;
-    SSX_HIP_TRY(ctx, hipMemcpyAsync(stage + o_dst0, dev + o_dst0, down, hipMemcpyDeviceToHost, s));
-    st.bytes_down += (int64_t)down; ++st.copies_down;
-  } else if (dst_side.range) {
-    // a row of the copy is an image: rows * cols bytes, `distance` apart on the host -- nothing between the images is written
-    SSX_HIP_TRY(ctx, hipMemcpy2DAsync(jobs[0].dst, dst_side.distance, dev + o_dst[0], range_img, img_bytes, (size_t)n, hipMemcpyDeviceToHost, s));
-    st.bytes_down += (int64_t)(img_bytes * (size_t)n); ++st.copies_down;
-  } else {
-    for (int32_t k = 0; k < n; ++k) {
-      if (!dst_side.host[k]) continue;                                          // (rows of cols bytes: the pitch bytes of the destination stay)
-      SSX_HIP_TRY(ctx, hipMemcpy2DAsync(jobs[k].dst, (size_t)jobs[k].dst_stride, dev + o_dst[k], dpitch, (size_t)cols, (size_t)rows, hipMemcpyDeviceToHost, s));
-      st.bytes_down += (int64_t)img_bytes; ++st.copies_down;
-    }
-  }
-  SSX_HIP_TRY(ctx, hipStreamSynchronize(s));
-  ++st.syncs;
-  if (staged)
-    for (int32_t k = 0; k < n; ++k) {
-      const uint8_t* d = reinterpret_cast<const uint8_t*>(stage + o_dst[k]);
-      for (int32_t r = 0; r < rows; ++r) std::memcpy(jobs[k].dst + (size_t)r * jobs[k].dst_stride, d + (size_t)r * dpitch, (size_t)cols);
-    }
-  plan->last = st;
-  return SSX_OK;
+  UdCall call;
+  st = ud_build(err, who, UD_STORED, v, rows, cols, images_on_device, ud_facts(UD_STORED, v, rows, cols, images_on_device), call);
+  if (st != SSX_OK) { ctx->set_error("%s", err); return st; }
+  const auto fill = [&](int32_t k, UdRemapJob& t) { t.map = plan->maps[(size_t)v[k].tag]; };
+  const auto launch = [&](const UdRemapJob* tab, dim3 grid, dim3 block) {
+    SSX_PROF(ctx, KID_UNDISTORT_REMAP, hipLaunchKernelGGL(k_undistort_remap, grid, block, 0, ctx->stream, tab, rows, cols, plan->pitch));
+  };
+  return ud_issue<UdRemapJob>(ctx, call, v, plan->arena, plan->stage, fill, launch, &plan->last);
 }
 
 #ifndef SSX_NO_TEST_HOOKS   // include/ssx_test_hooks.h
+ssx_status ssx_undistort_debug_plan(int32_t entry, int32_t rows, int32_t cols, int32_t images_on_device, int32_t n, const ssx_undistort_job_facts* jobs,
+                                    int32_t n_maps, const ssx_undistort_side_facts* src_facts, const ssx_undistort_side_facts* dst_facts,
+                                    ssx_undistort_call_info* out)
+{
+  static const char* const names[3] = {"ssx_undistort", "ssx_undistort_lens", "ssx_undistort_plan_apply"};
+  if (!out || entry < 0 || entry > 2) return SSX_ERR_INVALID_ARG;
+  std::memset(out, 0, sizeof *out);
+  static_assert(sizeof(out->error) == UD_ERR, "ssx_undistort_call_info::error holds the refusal's text");
+  const UdWhich which = entry == SSX_UD_ENTRY_PLAN_APPLY ? UD_STORED : UD_INLINE;
+  // views whose pointers say what the facts say and are never followed: ud_check and ud_build only compare and subtract them
+  uint8_t* const base = reinterpret_cast<uint8_t*>(uintptr_t(SSX_UD_BASE));
+  const auto view = [&](int32_t k) {
+    const ssx_undistort_job_facts& q = jobs[k];
+    return UdView{q.flags & SSX_UD_SRC_IS_NULL ? nullptr : base + q.src_off, q.src_stride, q.flags & SSX_UD_DST_IS_NULL ? nullptr : base + q.dst_off, q.dst_stride, q.tag};
+  };
+  std::vector<UdView> v;
+  UdCall c;
+  out->status = ud_check(out->error, names[entry], which, n, jobs != nullptr, rows, cols, n_maps, view, v);
+  if (out->status != SSX_OK || n == 0) return (ssx_status)out->status;
+  UdFacts f;
+  const auto told = [&](const ssx_undistort_side_facts* t, UdSideFacts& side) {
+    side.one_allocation = t && t->one_allocation != 0;
+    if (t && t->kind) side.kind.assign(t->kind, t->kind + n); else side.kind.assign((size_t)n, UD_DEVICE);
+  };
+  told(src_facts, f.src); told(dst_facts, f.dst);
+  out->status = ud_build(out->error, names[entry], which, v, rows, cols, images_on_device, f, c);
+  if (out->status != SSX_OK) return (ssx_status)out->status;
+  for (int i = 0; i < 3; ++i) { out->grid[i] = (int32_t)c.grid[i]; out->block[i] = (int32_t)c.block[i]; }
+  out->src_intake = c.src_intake; out->dst_intake = c.dst_intake;
+  const uint64_t parts[4] = {0, (c.tab_bytes + 255) & ~size_t(255), c.up_bytes, c.arena_bytes};     // table, sources, results
+  for (int i = 0; i < 3; ++i) { out->span_off[i] = parts[i]; out->span_bytes[i] = i == 0 ? c.tab_bytes : parts[i + 1] - parts[i]; }
+  out->up_bytes = c.up_bytes; out->arena_bytes = c.arena_bytes; out->stage_bytes = c.stage_bytes;
+  out->n_jobs = c.n; out->n_up = (int32_t)c.up.size(); out->n_down = (int32_t)c.down.size();
+  static_assert(sizeof(UdCallJob) == sizeof(out->job[0]) && sizeof(UdUp) == sizeof(out->up[0]) && sizeof(UdDown) == sizeof(out->down[0]), "member for member");
+  std::memcpy(out->job, c.jobs.data(), sizeof(UdCallJob) * c.jobs.size());
+  std::memcpy(out->up, c.up.data(), sizeof(UdUp) * c.up.size());
+  if (!c.down.empty()) std::memcpy(out->down, c.down.data(), sizeof(UdDown) * c.down.size());
+  const UdStats st = ud_predict(c);
+  out->launches = st.launches; out->syncs = st.syncs; out->copies_up = st.copies_up; out->copies_down = st.copies_down;
+  out->bytes_up = st.bytes_up; out->bytes_down = st.bytes_down;
+  return SSX_OK;
+}
+
 ssx_status ssx_undistort_plan_debug_last_call(const ssx_undistort_plan* plan, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down,
                                               int32_t* copies_up, int32_t* copies_down)
 {
   if (!plan) return SSX_ERR_INVALID_ARG;
-  const UdPlanStats& s = plan->last;
+  const UdStats& s = plan->last;
   if (launches) *launches = s.launches;
   if (synchronisations) *synchronisations = s.syncs;
   if (bytes_up) *bytes_up = s.bytes_up;
@@ -999,3 +904,5 @@ ssx_status ssx_undistort_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_
 #endif
 
 }  // extern "C"
+
+#include "rectify.inc"

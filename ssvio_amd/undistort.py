@@ -10,6 +10,83 @@ import numpy as np
 from ._lib import Context, LensJob, LensParams, StereoRawRig, StereoRectified, UndistortJob, UndistortParams, UndistortPlanJob, load
 
 
+ENTRY_UNDISTORT, ENTRY_LENS, ENTRY_PLAN_APPLY = 0, 1, 2      # include/ssx_test_hooks.h: SSX_UD_ENTRY_*
+STAGED, IN_PLACE, RANGE, EACH = 0, 1, 2, 3                   # SSX_UD_*: how one side's images reach the device
+NEITHER, DEVICE, PINNED = -1, 0, 1                           # a side's facts: kind[k]
+WHERE_IT_LIES, BASE, STAGING = -1, 1 << 40, None             # SSX_UD_WHERE_IT_LIES, SSX_UD_BASE; a copy's host_off when it is the staging buffer
+
+
+class UndistortJobFacts(C.Structure):
+    """ssx_undistort_job_facts: offsets from job 0's src; tag = lens model or map index; flags 1 / 2: src / dst is null"""
+    _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("src_stride", C.c_int32), ("dst_stride", C.c_int32), ("tag", C.c_int32), ("flags", C.c_int32)]
+
+
+class UndistortSideFacts(C.Structure):
+    _fields_ = [("one_allocation", C.c_int32), ("reserved", C.c_int32), ("kind", C.POINTER(C.c_int8))]
+
+
+class _CallJob(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("src_off", "dst_off", "src_stride", "dst_stride")]     # (offsets read as signed: WHERE_IT_LIES is -1)
+
+
+class _CallUp(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("off", "host", "bytes", "images")]
+
+
+class _CallDown(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("host", "host_pitch", "off", "dev_pitch", "width", "height")]
+
+
+class UndistortCallInfo(C.Structure):
+    """ssx_undistort_call_info"""
+    _fields_ = [("status", C.c_int32), ("error", C.c_char * 256), ("grid", C.c_int32 * 3), ("block", C.c_int32 * 3), ("src_intake", C.c_int32),
+                ("dst_intake", C.c_int32), ("span_off", C.c_uint64 * 3), ("span_bytes", C.c_uint64 * 3), ("up_bytes", C.c_uint64),
+                ("arena_bytes", C.c_uint64), ("stage_bytes", C.c_uint64), ("n_jobs", C.c_int32), ("n_up", C.c_int32), ("n_down", C.c_int32),
+                ("launches", C.c_int32), ("syncs", C.c_int32), ("copies_up", C.c_int32), ("copies_down", C.c_int32), ("reserved", C.c_int32),
+                ("bytes_up", C.c_int64), ("bytes_down", C.c_int64), ("job", _CallJob * 1024), ("up", _CallUp * 1025), ("down", _CallDown * 1024)]
+
+
+def debug_plan(entry, rows, cols, jobs, images_on_device=False, n_maps=0, src_facts=None, dst_facts=None, n=None, null_table=False):
+    """ssx_undistort_debug_plan: the call an entry point (ENTRY_*) would issue, planned without a GPU.
+    jobs = [(src_off, src_stride, dst_off, dst_stride, tag)], offsets in bytes from job 0's src, None for a null pointer; n overrides the
+    count handed in; *_facts = (one_allocation, [kind per image]) as the runtime would answer.
+    -> dict: status, error, and for SSX_OK with n > 0: grid, block, src_intake, dst_intake, spans [(off, bytes)] of table / sources /
+    results, up_bytes, arena_bytes, stage_bytes, jobs [dict], up [dict], down [dict], stats (the dict last_call() would return)"""
+    lib = _fns(load())
+    arr = (UndistortJobFacts * max(len(jobs), 1))()
+    for k, (so, ss, do, ds, tag) in enumerate(jobs):
+        arr[k] = UndistortJobFacts(so or 0, do or 0, ss, ds, tag, (1 if so is None else 0) | (2 if do is None else 0))
+    keep, sides = [], []
+    for f in (src_facts, dst_facts):
+        if f is None:
+            sides.append(None)
+            continue
+        kinds = (C.c_int8 * max(len(f[1]), 1))(*f[1])
+        keep.append(kinds)
+        sides.append(C.byref(UndistortSideFacts(1 if f[0] else 0, 0, C.cast(kinds, C.POINTER(C.c_int8)))))
+    info = UndistortCallInfo()
+    st = lib.ssx_undistort_debug_plan(entry, rows, cols, 1 if images_on_device else 0, len(jobs) if n is None else n, None if null_table else arr, n_maps,
+                                      sides[0], sides[1], C.byref(info))
+    assert st == info.status
+    out = dict(status=info.status, error=info.error.decode())
+    if info.status != 0 or info.n_jobs == 0:
+        return out
+    def rec(s):                                                   # a copy's host address -> host_off: from jobs[0].src's origin, or STAGING
+        d = {k: getattr(s, k) for k, _ in s._fields_}
+        if "host" in d:
+            host = d.pop("host")
+            d["host_off"] = host - BASE if host else STAGING
+        return d
+
+    out.update(grid=tuple(info.grid), block=tuple(info.block), src_intake=info.src_intake, dst_intake=info.dst_intake,
+               spans=[(info.span_off[i], info.span_bytes[i]) for i in range(3)], up_bytes=info.up_bytes, arena_bytes=info.arena_bytes,
+               stage_bytes=info.stage_bytes, jobs=[rec(info.job[k]) for k in range(info.n_jobs)], up=[rec(info.up[k]) for k in range(info.n_up)],
+               down=[rec(info.down[k]) for k in range(info.n_down)],
+               stats=dict(launches=info.launches, syncs=info.syncs, bytes_up=info.bytes_up, bytes_down=info.bytes_down, copies_up=info.copies_up,
+                          copies_down=info.copies_down))
+    return out
+
+
 def _fns(lib):
     if not getattr(lib, "_undistort_ready", False):
         lib.ssx_undistort_default.restype = None
@@ -42,6 +119,10 @@ def _fns(lib):
             lib.ssx_undistort_plan_add_lens.argtypes = [C.c_void_p, C.POINTER(LensParams), i32_p]
             lib.ssx_stereo_rectify.restype = C.c_int
             lib.ssx_stereo_rectify.argtypes = [C.POINTER(StereoRawRig), C.POINTER(StereoRectified), C.c_char_p, C.c_int32]
+        if hasattr(lib, "ssx_undistort_debug_plan"):            # include/ssx_test_hooks.h
+            lib.ssx_undistort_debug_plan.restype = C.c_int
+            lib.ssx_undistort_debug_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(UndistortJobFacts), C.c_int32,
+                                                     C.POINTER(UndistortSideFacts), C.POINTER(UndistortSideFacts), C.POINTER(UndistortCallInfo)]
         if hasattr(lib, "ssx_lens_debug_atan"):                 # include/ssx_test_hooks.h
             lib.ssx_lens_debug_atan.restype = C.c_int
             lib.ssx_lens_debug_atan.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
