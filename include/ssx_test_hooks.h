@@ -287,6 +287,13 @@ SSX_API ssx_status ssx_lens_debug_atan(ssx_ctx* ctx, int32_t n, const double* r,
  * zero after a call that was refused.  Any output may be NULL. */
 SSX_API ssx_status ssx_dense_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_t* synchronisations, int64_t* bytes_up, int64_t* bytes_down,
                                              int32_t* groups);
+/* tests hook: the workspace cap the dense calls of ctx group their jobs by, in bytes; 0 = SSX_DENSE_WORKSPACE_CAP (the default).
+ * A call takes as many jobs a group as stay under the cap, at least one, where one job counts as
+ *   pix * (16 + 2 * disparities + 4) + 768 bytes   in ssx_stereo_dense and ssx_stereo_dense_post (census, S and right key per pixel),
+ *   pix * 8 + rows * 4 + 768 bytes                 in ssx_dense_postprocess (label and size per pixel, a count per row),
+ * pix = rows * cols.  The tests work out the cap for a group size from these (tests/test_dense_groups_gpu.py) and assert the groups
+ * that ssx_dense_debug_last_call reports.  The cap stays until it is set again: a test that sets it restores 0. */
+SSX_API ssx_status ssx_dense_debug_set_workspace_cap(ssx_ctx* ctx, uint64_t bytes);
 /* the stages of ONE pair of host images through the kernels of ssx_stereo_dense, named as tools/dense_model.py names them: the census
  * words of both images (rows x cols u64 each), the path volume L of `direction` (0 .. paths - 1; rows x cols x disparities u8, d
  * fastest), the summed volume S (u16, the same shape) and the right disparity dR (rows x cols u8).  Any output may be NULL. */

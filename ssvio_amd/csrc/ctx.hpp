@@ -179,6 +179,9 @@ struct ssx_ctx {
   HostBuf dn_stage;
   KfChainStats dense;                        // the last ssx_stereo_dense / ssx_stereo_dense_post / ssx_dense_postprocess (ssx_dense_debug_last_call)
   int32_t dense_groups = 0;
+#ifndef SSX_NO_TEST_HOOKS
+  uint64_t dense_cap = 0;                    // ssx_dense_debug_set_workspace_cap: the cap the dense calls group by; 0 = SSX_DENSE_WORKSPACE_CAP
+#endif
 
   std::mutex err_mu;                         // worker threads of a batched call may report failures concurrently
 

@@ -336,11 +336,21 @@ ssx_status dn_select(ssx_ctx* ctx, const DnWork& w, const DnJob* tab, int32_t g,
   return SSX_OK;
 }
 
+// the cap a call of ctx groups its jobs by: SSX_DENSE_WORKSPACE_CAP, unless a test has set another (ssx_dense_debug_set_workspace_cap)
+inline size_t dn_cap(const ssx_ctx* ctx)
+{
+#ifndef SSX_NO_TEST_HOOKS
+  if (ctx->dense_cap != 0) return (size_t)ctx->dense_cap;
+#endif
+  (void)ctx;
+  return (size_t)SSX_DENSE_WORKSPACE_CAP;
+}
+
 // jobs per group: as many as stay under the cap, at least one
-inline int32_t dn_group_size(size_t pix, int32_t D, int32_t n)
+inline int32_t dn_group_size(const ssx_ctx* ctx, size_t pix, int32_t D, int32_t n)
 {
   const size_t one = dn_job_bytes(pix, D);
-  const size_t fit = std::max<size_t>(1, (size_t)SSX_DENSE_WORKSPACE_CAP / one);
+  const size_t fit = std::max<size_t>(1, dn_cap(ctx) / one);
   return (int32_t)std::min<size_t>(fit, (size_t)n);
 }
 
@@ -402,7 +412,7 @@ ssx_status ssx_stereo_dense(ssx_ctx* ctx, int32_t n, const ssx_dense_job* jobs, 
   const size_t o_disp = staged ? lay.take(2 * pix * (size_t)n) : 0;
   SSX_HIP_TRY(ctx, ctx->dn_arena.reserve(lay.off));
   SSX_HIP_TRY(ctx, ctx->dn_stage.reserve(lay.off));
-  const int32_t group = dn_group_size(pix, D, n);
+  const int32_t group = dn_group_size(ctx, pix, D, n);
   DnWork w;
   SSX_HIP_TRY(ctx, ctx->dn_work.reserve(dn_carve(w, nullptr, (size_t)group, pix, D), 1.0));
   dn_carve(w, ctx->dn_work.as<char>(), (size_t)group, pix, D);
@@ -467,6 +477,13 @@ ssx_status ssx_dense_debug_last_call(ssx_ctx* ctx, int32_t* launches, int32_t* s
   if (bytes_up) *bytes_up = ctx->dense.bytes_up;
   if (bytes_down) *bytes_down = ctx->dense.bytes_down;
   if (groups) *groups = ctx->dense_groups;
+  return SSX_OK;
+}
+
+ssx_status ssx_dense_debug_set_workspace_cap(ssx_ctx* ctx, uint64_t bytes)
+{
+  if (!ctx) return SSX_ERR_INVALID_ARG;
+  ctx->dense_cap = bytes;
   return SSX_OK;
 }
 

@@ -420,7 +420,7 @@ ssx_status dp_run(ssx_ctx* ctx, const char* who, int32_t n, const ssx_dense_job*
   DpWork pw;
   int32_t group;
   if (chain) {
-    group = dn_group_size(pix, prm->disparities, n);
+    group = dn_group_size(ctx, pix, prm->disparities, n);
     SSX_HIP_TRY(ctx, ctx->dn_work.reserve(dn_carve(w, nullptr, (size_t)group, pix, prm->disparities), 1.0));
     dn_carve(w, ctx->dn_work.as<char>(), (size_t)group, pix, prm->disparities);
     // the census words (16 bytes a pixel) are dead once the paths kernel is done: labels, sizes and row counts (8 bytes a pixel and 4 a
@@ -429,7 +429,7 @@ ssx_status dp_run(ssx_ctx* ctx, const char* who, int32_t n, const ssx_dense_job*
     pw.size = pw.label + (size_t)group * pix;
     pw.row_count = pw.size + (size_t)group * pix;
   } else {
-    group = (int32_t)std::min<size_t>(std::max<size_t>(1, (size_t)SSX_DENSE_WORKSPACE_CAP / dp_job_bytes(pix, rows)), N);
+    group = (int32_t)std::min<size_t>(std::max<size_t>(1, dn_cap(ctx) / dp_job_bytes(pix, rows)), N);
     SSX_HIP_TRY(ctx, ctx->dn_work.reserve(dp_carve(pw, nullptr, (size_t)group, pix, rows), 1.0));
     dp_carve(pw, ctx->dn_work.as<char>(), (size_t)group, pix, rows);
   }

@@ -46,6 +46,8 @@ def _fns(lib):
             lib.ssx_dense_debug_stages.restype = C.c_int
             lib.ssx_dense_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenseParamsC),
                                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.ssx_dense_debug_set_workspace_cap.restype = C.c_int
+            lib.ssx_dense_debug_set_workspace_cap.argtypes = [C.c_void_p, C.c_uint64]
         lib._dense_ready = True
     return lib
 
@@ -269,6 +271,12 @@ def last_call(ctx: Context):
     a, b, c, d, e = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
     ctx.check(lib.ssx_dense_debug_last_call(ctx.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
     return dict(launches=a.value, syncs=b.value, bytes_up=c.value, bytes_down=d.value, groups=e.value)
+
+
+def set_workspace_cap(ctx: Context, nbytes):
+    """ssx_dense_debug_set_workspace_cap: the cap, in bytes, that the context's dense calls group their jobs by from now on; 0 = the
+    default, SSX_DENSE_WORKSPACE_CAP.  A test that sets one restores 0 in a finally."""
+    ctx.check(_fns(ctx.lib).ssx_dense_debug_set_workspace_cap(ctx.handle, int(nbytes)))
 
 
 def stages(ctx: Context, left, right, params=None, direction=0):
